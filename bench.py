@@ -9,9 +9,13 @@ GPU) with the frames already resident in HBM.  Prints ONE JSON line (rank 0).  M
 batch (weak scaling, no data-path collective) and the per-pair 32-byte result records are all-gathered over
 RCCL/xGMI at the end of each step, inside the timed region, on the context's own stream (mav_allgather_results).
 
-After the timed loop, outside the timed region, the outputs the LAST timed step left behind are checked against the
-oracle (records, both masks and boxes bit for bit against the numpy chain evaluated on that step's own flow; that flow
-against the CPU Farneback): `verified_pairs`.  A mismatch makes the process exit non-zero.
+A plain run sets up, warms up, times the steps and prints the line.  Everything else moves behind --full, outside the timed
+region: the outputs the LAST timed step left behind are checked against the oracle (records, both masks and boxes bit for
+bit against the numpy chain evaluated on that step's own flow; that flow against the CPU Farneback): `verified_pairs`, and a
+mismatch makes the process exit non-zero; then the H2D and video legs, the roofline, the CPU baseline, the C2 / C5-share
+configurations and the API loops (each of them can still be switched off with its --no-* option).
+
+--dump-outputs DIR writes what the last timed step computed (what a caller of mav_process_batch_dev receives) to DIR/<name>.npy.
 """
 import argparse
 import hashlib
@@ -148,6 +152,30 @@ def cpu_baseline(prev, nxt, samples, n_sample, levels):
         out["all_cores"] = {"value": n_all / dtp, "unit": "frame-pairs/s", "cores": cores, "host_cores": os.cpu_count(),
                             "pairs": n_all, "seconds": round(dtp, 2), "kind": kind}
     return out
+
+
+DUMP_MASK_SAMPLE = 1 << 21       # pixels of each mask in --dump-outputs: the same seeded positions in every run of one shape and batch
+
+
+def dump_outputs(out_dir, records, mf_buf, md_buf, B, W, H):
+    """--dump-outputs: the last timed step's outputs as a caller receives them, float64 / float32 .npy files in `out_dir`.
+    The per-pair records (box, FoE; every rank's after an all-gather) whole.  Both threshold masks (B x H x W bytes each) as the count
+    of set pixels in every row, plus a fixed seeded sample of DUMP_MASK_SAMPLE pixels (whole masks when they are smaller) and that
+    sample's flat indices.  About 35 MB at 1920x1080 x 64: the sample is fixed, only the row counts (8 bytes per row of the batch)
+    grow with the shape.  Returns the names written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = B * W * H
+    idx = np.arange(n) if n <= DUMP_MASK_SAMPLE else np.sort(np.random.default_rng(20241015).choice(n, DUMP_MASK_SAMPLE, replace=False))
+    arrays = {"records_box": records["box"].astype(np.float64), "records_foe": records["foe"].astype(np.float64),
+              "mask_sample_index": idx.astype(np.float64)}
+    for name, buf in (("mask_fixed", mf_buf), ("mask_dyn", md_buf)):
+        m = buf.download(np.uint8, (B, H, W))
+        arrays[name + "_row_counts"] = m.sum(axis=2, dtype=np.int64).astype(np.float32)
+        arrays[name + "_sample"] = m.reshape(-1)[idx].astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def verify_last_step(ctx, prev, nxt, samples, res, mf_buf, md_buf, pairs, levels):
@@ -794,6 +822,9 @@ def main():
     ap.add_argument("--no-api-loop", action="store_true", help="skip the reference-shaped loops leg (Processor.run_detection_batched / run_detection on host frames)")
     ap.add_argument("--detail", default=None, help="where the verbose record of the run goes (default: gpurun_out/bench_detail.json when that directory exists)")
     ap.add_argument("--no-configs", action="store_true", help="skip the extra BASELINE configuration legs (C2: 1280x720 batch 1; C5 share: 3840x2160, 5 levels, batch 16)")
+    ap.add_argument("--full", action="store_true", help="after the headline: verification against the oracle, H2D and video legs, roofline, CPU "
+                    "baseline, the C2 / C5-share configurations and the API loops (the --no-* options switch single legs off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's records and masks to DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -894,13 +925,16 @@ def main():
 
     # ---- what did the timed loop compute?  (outside the timed region) ----
     verification = None
-    res_last = d_res.download(_lib.RESULT_DTYPE, (B,))
+    want_records = args.full or args.dump_outputs is not None
+    res_last = records = d_res.download(_lib.RESULT_DTYPE, (B,)) if want_records else None
     gathered_distinct = comm_ranks = None
-    if ex is not None:                                 # the gathered block of this rank must be its own records
-        allrec = ex.gathered().view(_lib.RESULT_DTYPE)
-        assert allrec[rank * B:(rank + 1) * B].tobytes() == res_last.tobytes(), "all-gathered records differ from the local ones"
-        if world > 1:                                  # every rank runs different content (frames rolled by 31 px per rank, other samples)
-            gathered_distinct = len({allrec[r * B:(r + 1) * B].tobytes() for r in range(world)})
+    if ex is not None:
+        if want_records:
+            records = allrec = ex.gathered().view(_lib.RESULT_DTYPE)
+        if args.full:                                  # the gathered block of this rank must be its own records
+            assert allrec[rank * B:(rank + 1) * B].tobytes() == res_last.tobytes(), "all-gathered records differ from the local ones"
+            if world > 1:                              # every rank runs different content (frames rolled by 31 px per rank, other samples)
+                gathered_distinct = len({allrec[r * B:(r + 1) * B].tobytes() for r in range(world)})
         comm_ranks = ex.comm_ranks()
         # the ranks part here: the communicator goes, ranks other than 0 leave; rank 0's post-loop legs (verification, H2D, video,
         # roofline) hold nobody
@@ -908,7 +942,9 @@ def main():
         if rank != 0:
             ctx.close()
             return
-    if rank == 0 and not args.no_verify:
+    if rank == 0 and args.dump_outputs is not None:   # before any leg below re-runs the batch into the same buffers
+        dump_outputs(args.dump_outputs, records, d_mf, d_md, B, W, H)
+    if rank == 0 and args.full and not args.no_verify:
         verification = verify_last_step(ctx, prev, nxt, samples, res_last, d_mf, d_md, sorted({0, B - 1}), args.levels)
         # ... and EVERY pair of the timed step against the same batch re-run in the plain schedule
         ok, n_same, differing = equal_plain_schedule(ctx, run_batch, d_res, d_mf, d_md, B, W, H)
@@ -921,7 +957,7 @@ def main():
     #      inside the loop; (2) pipelined: pinned memory, uploads on the context's copy stream into a second buffer set while
     #      the previous batch computes (how a deployment would feed the GPU) ----
     h2d_ms = h2d_pipe_ms = None
-    if rank == 0 and not args.no_profile:
+    if rank == 0 and args.full and not args.no_profile:
         ctx.sync()
         t1 = time.perf_counter()
         for _ in range(2):
@@ -947,7 +983,7 @@ def main():
     #      views of one buffer.  The library recognises the layout and blurs / expands every frame once per group instead of twice
     #      (flow bit-identical to the two-batch form: tests/test_gpu_flow.py); the headline metric stays on independent pairs ----
     video = None
-    if rank == 0 and not args.no_profile:
+    if rank == 0 and args.full and not args.no_profile:
         seq = synth.make_sequence(W, H, B + 1)
         d_seq = ctx.alloc(seq.nbytes).upload(seq)
         n_vid = max(5, min(30, args.steps))
@@ -978,14 +1014,14 @@ def main():
     roofline = None
     ceil = None
     enqueue_ms = None
-    if rank == 0 and not args.no_profile:
+    if rank == 0 and args.full and not args.no_profile:
         enqueue_ms = host_enqueue_ms(ctx, step)
         ceil = measured_ceilings(ctx)
         roofline = sweep_roofline(ctx, run_batch, B, layers, W, H, args.levels, schedule, 1e3 * elapsed / args.steps, ceil)
 
     # ---- the other BASELINE configurations one GPU can hold (never `value`; outside the headline's timed region) ----
     configs = None
-    extra_legs = rank == 0 and world == 1 and (W, H, args.levels) == (1920, 1080, 1)
+    extra_legs = args.full and rank == 0 and world == 1 and (W, H, args.levels) == (1920, 1080, 1)
     if extra_legs and not (args.no_configs and args.no_api_loop):
         # the headline's buffers and its whole context (2.9 GB of workspace, 8.5 GB of flow) are released first: the legs then get the
         # memory a stand-alone run of their configuration would get
@@ -1037,7 +1073,7 @@ def main():
         if roofline:
             full["device_busy_ms"] = roofline["device_busy_ms"]
             full["roofline"] = roofline
-        if world == 1 and args.cpu_pairs > 0:
+        if args.full and world == 1 and args.cpu_pairs > 0:
             full["cpu_baseline"] = cpu_baseline(prev, nxt, samples, min(args.cpu_pairs, B), args.levels)
         if api_loop:
             full["api_loop"] = api_loop

@@ -1,5 +1,5 @@
 """Host side of bench.py that needs no GPU: the ranks of an N-GPU run pin themselves to disjoint core sets, the BLAS pool is capped
-before numpy loads, and the bench line stays a numbers-only record."""
+before numpy loads, the bench line stays a numbers-only record, and --dump-outputs writes bounded, seeded float arrays."""
 import json
 import os
 import subprocess
@@ -93,3 +93,48 @@ def _strings(o):
     elif isinstance(o, (list, tuple)):
         for v in o:
             yield from _strings(v)
+
+
+class _HostBuffer:
+    """Stands in for a DeviceBuffer: download() of host bytes."""
+
+    def __init__(self, a):
+        self.a = a
+
+    def download(self, dtype, shape):
+        return self.a.view(dtype).reshape(shape).copy()
+
+
+def test_dump_outputs_is_float_seeded_and_bounded(tmp_path):
+    """--dump-outputs at the headline's shape (1920x1080, batch 64): float32 / float64 .npy files only, at most 64 MB in all, the same
+    sample positions in every run, and what it writes is what the buffers hold."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from mavflow import _lib
+    W, H, B = 1920, 1080, 64
+    rng = np.random.default_rng(3)
+    rec = np.zeros(B, _lib.RESULT_DTYPE)
+    rec["box"] = rng.integers(-1, W, (B, 4))
+    rec["foe"] = rng.normal(size=(B, 2)) * 500
+    mf = (rng.random(B * H * W, dtype=np.float32) < 0.1).astype(np.uint8)
+    md = mf.copy()
+    md[::7] ^= 1
+    names = bench.dump_outputs(str(tmp_path / "a"), rec, _HostBuffer(mf), _HostBuffer(md), B, W, H)
+    bench.dump_outputs(str(tmp_path / "b"), rec, _HostBuffer(mf), _HostBuffer(md), B, W, H)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == sorted(n + ".npy" for n in names)
+    total = 0
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64), (f, a.dtype)
+        assert a.tobytes() == b.tobytes(), f
+        total += (tmp_path / "a" / f).stat().st_size
+    assert total <= 64 << 20, total
+    out = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    assert np.array_equal(out["records_box"], rec["box"]) and np.array_equal(out["records_foe"], rec["foe"])
+    idx = out["mask_sample_index"].astype(np.int64)
+    assert len(idx) == bench.DUMP_MASK_SAMPLE and np.all(np.diff(idx) > 0) and idx[-1] < B * H * W
+    assert np.array_equal(out["mask_fixed_sample"], mf[idx]) and np.array_equal(out["mask_dyn_sample"], md[idx])
+    assert np.array_equal(out["mask_fixed_row_counts"], mf.reshape(B, H, W).sum(axis=2))
+    assert np.array_equal(out["mask_dyn_row_counts"], md.reshape(B, H, W).sum(axis=2))

@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-SMALL = ["--steps", "2", "--warmup", "1", "--no-profile", "--cpu-pairs", "0", "--no-configs", "--no-api-loop"]
+SMALL = ["--full", "--steps", "2", "--warmup", "1", "--no-profile", "--cpu-pairs", "0", "--no-configs", "--no-api-loop"]
 
 
 def _env(**kw):
@@ -105,7 +105,7 @@ def test_bench_two_ranks_rehearsed_on_one_gpu():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
            str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "8", "--rehearse-on-one-gpu",
-           "--rendezvous", "torch", "--no-profile", "--cpu-pairs", "0", "--no-configs", "--no-api-loop"]
+           "--rendezvous", "torch", "--full", "--no-profile", "--cpu-pairs", "0", "--no-configs", "--no-api-loop"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=420)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -125,8 +125,8 @@ def test_bench_two_ranks_rehearsed_through_the_socket_rendezvous(launcher):
     file named after MASTER_PORT and the launcher's pid).  Ids only: the ncclUniqueId is created and broadcast, the records move
     through the store."""
     import socket
-    tail = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "8", "--rehearse-on-one-gpu", "--no-profile", "--cpu-pairs", "0",
-            "--no-configs", "--no-api-loop"]
+    tail = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "8", "--rehearse-on-one-gpu", "--full", "--no-profile", "--cpu-pairs",
+            "0", "--no-configs", "--no-api-loop"]
     if launcher == "own":
         cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + tail
     else:
@@ -150,8 +150,8 @@ def test_two_ranks_agree_to_fall_back_to_the_torch_path(launcher):
     re-run in child processes on the torch.distributed path (under the launcher's process group, or, with bench.py's own launcher, the
     MASTER_PORT it reserved for exactly this) and rank 0's child prints the one line."""
     import socket
-    tail = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "8", "--rehearse-on-one-gpu", "--simulate-socket-failure", "--no-profile",
-            "--cpu-pairs", "0", "--no-configs", "--no-api-loop"]
+    tail = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "8", "--rehearse-on-one-gpu", "--simulate-socket-failure", "--full",
+            "--no-profile", "--cpu-pairs", "0", "--no-configs", "--no-api-loop"]
     if launcher == "own":
         cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + tail
     else:

@@ -5,7 +5,7 @@ set -u
 for v in "$@"; do
   echo "== ${v:-defaults}"
   opts=""; for kv in $v; do opts="$opts --opt $kv"; done
-  timeout -k 10 200 python bench.py --steps ${STEPS:-30} --cpu-pairs 0 --no-verify --no-configs $opts ${BENCH_ARGS:-} | python -c "
+  timeout -k 10 200 python bench.py --full --steps ${STEPS:-30} --cpu-pairs 0 --no-verify --no-configs $opts ${BENCH_ARGS:-} | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline()); print(d['value'], d['ms_per_step'], d['roofline']['all_kernels_ms'])" || exit 1
 done

@@ -10,9 +10,9 @@ out=$1; mkdir -p "$out"
 B4K="--width 3840 --height 2160 --levels 5 --batch 16"
 CLEAN="--cpu-pairs 0 --no-configs --no-verify --no-profile --no-api-loop"
 # untraced records first: the algorithmic bytes per sweep launch (roofline block) the unions below are quoted on
-timeout -k 10 300 python3 bench.py --steps 10 --warmup 3 --cpu-pairs 0 --no-configs --no-api-loop > "$out/untraced1080.json" 2> "$out/untraced1080.err" || exit 1
-timeout -k 10 300 python3 bench.py --steps 10 --warmup 3 --cpu-pairs 0 --no-configs --no-api-loop $B4K > "$out/untraced4k.json" 2> "$out/untraced4k.err" || exit 1
-timeout -k 10 300 python3 bench.py --steps 200 --warmup 20 --cpu-pairs 0 --no-configs --no-api-loop --width 1280 --height 720 --batch 1 > "$out/untraced720.json" 2> "$out/untraced720.err" || exit 1
+timeout -k 10 300 python3 bench.py --full --steps 10 --warmup 3 --cpu-pairs 0 --no-configs --no-api-loop > "$out/untraced1080.json" 2> "$out/untraced1080.err" || exit 1
+timeout -k 10 300 python3 bench.py --full --steps 10 --warmup 3 --cpu-pairs 0 --no-configs --no-api-loop $B4K > "$out/untraced4k.json" 2> "$out/untraced4k.err" || exit 1
+timeout -k 10 300 python3 bench.py --full --steps 200 --warmup 20 --cpu-pairs 0 --no-configs --no-api-loop --width 1280 --height 720 --batch 1 > "$out/untraced720.json" 2> "$out/untraced720.err" || exit 1
 # 5 + 2 steps each: the stats table then holds 7 identical steps and nothing else
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kt1080" -- python3 bench.py --steps 5 --warmup 2 $CLEAN > "$out/kt1080.json" 2> "$out/kt1080.err" || exit 1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kt4k" -- python3 bench.py --steps 5 --warmup 2 $CLEAN $B4K > "$out/kt4k.json" 2> "$out/kt4k.err" || exit 1
