@@ -35,7 +35,10 @@ extern "C" {
 typedef struct mav_ctx mav_ctx;
 
 /* src/farneback.py:76-80 -- the literal argument list of cv2.calcOpticalFlowFarneback.
- * Defaults (mav_fb_defaults): 0.4, 1, 12, 10, 8, 1.2, 0. Only flags == 0 (box window) is implemented. */
+ * Defaults (mav_fb_defaults): 0.4, 1, 12, 10, 8, 1.2, 0.  flags: 0 or MAV_OPTFLOW_USE_INITIAL_FLOW (box window either way;
+ * OPTFLOW_FARNEBACK_GAUSSIAN = 256 is not implemented: MAV_ERR_ARG).  The bit is accepted so that a cv2 argument list passes as it
+ * is; only mav_farneback_init / mav_farneback_init_dev start from an initial flow, every other entry point starts from zero. */
+#define MAV_OPTFLOW_USE_INITIAL_FLOW 4
 typedef struct {
     double pyr_scale;
     int levels, winsize, iterations, poly_n;
@@ -143,6 +146,13 @@ int mav_layer_dims(const mav_ctx*, int k, int* w, int* h, int* ksize, double* si
  * frames -- next == prev + W*H, in every entry point that takes prev / next, host or device pointers -- the library uploads the run
  * once and blurs / expands every frame once per group instead of twice.  The flow is bit-identical to the two-batch form. */
 int mav_farneback(mav_ctx*, const uint8_t* prev, const uint8_t* next, int batch, float* flow);
+/* cv2.calcOpticalFlowFarneback(prev, next, flow_init, *fb, fb.flags | OPTFLOW_USE_INITIAL_FLOW) for `batch` pairs: pair i starts from
+ * flow_init[i], (batch, H, W, 2) float32 -- e.g. the previous pair's flow of a video.  As optflowgf.cpp does, the field enters at the
+ * coarsest layer computed (k = mav_num_layers() - 1) only: resize(flow_init, layer size, INTER_AREA) * pyr_scale^k builds that layer's
+ * initial matrices; every finer layer upsamples the coarser one's flow as always.  All-zero flow_init = mav_farneback, bit for bit.
+ * flow_init == flow (in place, cv2's idiom) is allowed.  The first call allocates the top layer's field for the pairs of one group
+ * (mav_mem_info's workspace figure grows by it); a context that never calls it holds nothing more. */
+int mav_farneback_init(mav_ctx*, const uint8_t* prev, const uint8_t* next, int batch, const float* flow_init, float* flow);
 /* Detector.derotate [src/detector.py:70-117]: omega = angular difference / dt, (batch,3); dt (batch). */
 int mav_derotate(mav_ctx*, const float* flow, const double* omega, const double* dt, int batch, double* flow_out);
 /* FocusOfExpansion.get_FOE_dense + ransac [src/focus_of_expansion.py:32-86]; samples (batch, 2N, 2) = (row, col)
@@ -218,6 +228,9 @@ int mav_detect(mav_ctx*, const float* flow, const uint32_t* samples, const doubl
 
 /* ---- device-pointer entry points (asynchronous on the context's stream) -------------------------------- */
 int mav_farneback_dev(mav_ctx*, const uint8_t* prev, const uint8_t* next, int batch, float* flow);
+/* mav_farneback_init on device pointers (enqueue only).  flow_init == flow is allowed; ranges that overlap without being the same
+ * field are MAV_ERR_ARG.  mav_last_flow_dev reports `flow`. */
+int mav_farneback_init_dev(mav_ctx*, const uint8_t* prev, const uint8_t* next, int batch, const float* flow_init, float* flow);
 int mav_process_batch_dev(mav_ctx*, const uint8_t* prev, const uint8_t* next, const uint32_t* samples, const double* omega,
                           const double* dt, const uint8_t* frame0, const uint8_t* sky, int batch, const mav_foe_params*,
                           const mav_thr_params*, float* flow, double* phi, uint8_t* mask_fixed, uint8_t* mask_dyn,
@@ -225,7 +238,7 @@ int mav_process_batch_dev(mav_ctx*, const uint8_t* prev, const uint8_t* next, co
 int mav_detect_dev(mav_ctx*, const float* flow, const uint32_t* samples, const double* omega, const double* dt,
                    const uint8_t* frame0, const uint8_t* sky, int batch, const mav_foe_params*, const mav_thr_params*,
                    double* phi, uint8_t* mask_fixed, uint8_t* mask_dyn, mav_result* results);
-/* Device pointer of the flow field the most recent mav_process_batch_dev / mav_farneback_dev call on this context wrote
+/* Device pointer of the flow field the most recent mav_process_batch_dev / mav_farneback_dev / mav_farneback_init_dev call on this context wrote
  * (the caller's buffer, or the context's own workspace when the caller passed flow == NULL); NULL before the first call.
  * Lets a caller that keeps the flow in the workspace (bench.py) still inspect it. */
 /* cv2.cvtColor(COLOR_BGR2GRAY) [src/farneback.py:21,74] on device pointers: (batch, H, W, 3) u8 -> (batch, H, W) u8. */

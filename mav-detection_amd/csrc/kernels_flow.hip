@@ -1223,7 +1223,7 @@ static __device__ __forceinline__ float2 upsample_flow(const float* __restrict__
 }
 
 // Initial M of a layer.  flow = 0 (top layer), resize(prevFlow)*mul evaluated inline (lower layers), or an
-// explicit flow field (stage hook).  The upsampled flow is never written: the first blur sweep overwrites it.
+// explicit flow field (stage hook; the top layer of a call with an initial flow).  The upsampled flow is never written: the first blur sweep overwrites it.
 // One thread per pixel, 64 x 4 pixels per workgroup on a plain 2-D grid.  (Measured alternative, not kept: 64 x 16 tiles in the
 // XCD-aware order with two gathers in flight per thread -- L2 absorbed the gather rows, the kernel ran 5 % slower: its reads
 // that miss L2 are served by the Infinity Cache anyway, and the taller tile halves the number of workgroups in flight.)
@@ -1265,11 +1265,14 @@ void launch_update_matrices(hipStream_t st, const float* R0, const float* R1, si
 }
 
 void launch_update_matrices_flow(hipStream_t st, const float* R0, const float* R1, size_t R_stride, const float* flow,
-                                 size_t f_stride, int G, int w, int h, float* M, size_t M_stride)
+                                 size_t f_stride, int G, int w, int h, float* M, size_t M_stride, int y_begin, int y_end)
 {
-    dim3 grid((w + 63) / 64, (h + 3) / 4, G);
+    if (y_begin < 0) y_begin = 0;
+    if (y_end < 0 || y_end > h) y_end = h;
+    if (y_end <= y_begin) return;
+    dim3 grid((w + 63) / 64, (y_end - y_begin + 3) / 4, G);
     hipLaunchKernelGGL(k_update_matrices<2>, grid, dim3(256), 0, st, R0, R1, R_stride, flow, f_stride, 0, 0, 0.f, 0.0, 0.0,
-                       w, h, M, M_stride, 0, h);
+                       w, h, M, M_stride, y_begin, y_end);
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -4,11 +4,13 @@
 // u8 byte work on images that shrink by 2.25x per level: HBM/latency bound, nothing here is hot.
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
+#include <cmath>
 #include <cstdint>
 
 #include "mavflow_internal.h"
 
-// ---- cv2.resize(INTER_AREA), non-integer ratio: computeResizeAreaTab + resizeArea_<uchar, float> (resize.cpp) ---------
+// ---- cv2.resize(INTER_AREA), non-integer ratio: computeResizeAreaTab + resizeArea_<T, float> (resize.cpp) ------------
 // One destination index d of one axis covers source cells [d*scale, d*scale + scale): an optional partial first cell
 // (s1 - 1, weight wf), whole cells s1 .. s2-1 (weight wm each) and an optional partial last cell (s2, weight wl).
 struct AreaSpan { int s1, s2; float wf, wm, wl; bool first, last; };
@@ -28,13 +30,26 @@ __device__ __forceinline__ AreaSpan area_span(int d, double scale, int ssize)
     a.wl = (float)(fmin(fmin(f2 - (double)s2, 1.0), cell) / cell);
     return a;
 }
-__device__ __forceinline__ float area_row(const uint8_t* __restrict__ S, const AreaSpan& x)
+// channel c of one source row of CN interleaved channels (resizeArea_ keeps one float accumulator per channel: the same sum per channel)
+template <int CN, typename T>
+__device__ __forceinline__ float area_row(const T* __restrict__ S, const AreaSpan& x, int c = 0)
 {
     float buf = 0.f;                                   // buf[dx] += S[si] * alpha, in tab order
-    if (x.first) buf = buf + (float)S[x.s1 - 1] * x.wf;
-    for (int sx = x.s1; sx < x.s2; sx++) buf = buf + (float)S[sx] * x.wm;
-    if (x.last) buf = buf + (float)S[x.s2] * x.wl;
+    if (x.first) buf = buf + (float)S[(size_t)(x.s1 - 1) * CN + c] * x.wf;
+    for (int sx = x.s1; sx < x.s2; sx++) buf = buf + (float)S[(size_t)sx * CN + c] * x.wm;
+    if (x.last) buf = buf + (float)S[(size_t)x.s2 * CN + c] * x.wl;
     return buf;
+}
+// rows in tab order: sum[dx] += beta * buf[dx]; S = channel plane origin, row pitch sw * CN elements
+template <int CN, typename T>
+__device__ __forceinline__ float area_general(const T* __restrict__ S, int sw, const AreaSpan& x, const AreaSpan& y, int c = 0)
+{
+    const size_t pitch = (size_t)sw * CN;
+    float sum = 0.f;
+    if (y.first) sum = sum + y.wf * area_row<CN>(S + (size_t)(y.s1 - 1) * pitch, x, c);
+    for (int sy = y.s1; sy < y.s2; sy++) sum = sum + y.wm * area_row<CN>(S + (size_t)sy * pitch, x, c);
+    if (y.last) sum = sum + y.wl * area_row<CN>(S + (size_t)y.s2 * pitch, x, c);
+    return sum;
 }
 __global__ __launch_bounds__(256) void k_area_resize(const uint8_t* __restrict__ src, size_t src_stride, int sw, int sh,
                                                      uint8_t* __restrict__ dst, size_t dst_stride, int dw, int dh,
@@ -44,10 +59,7 @@ __global__ __launch_bounds__(256) void k_area_resize(const uint8_t* __restrict__
     if (dx >= dw || dy >= dh) return;
     const uint8_t* S = src + blockIdx.z * src_stride;
     const AreaSpan x = area_span(dx, scale_x, sw), y = area_span(dy, scale_y, sh);
-    float sum = 0.f;                                   // sum[dx] += beta * buf[dx], rows in tab order
-    if (y.first) sum = sum + y.wf * area_row(S + (size_t)(y.s1 - 1) * sw, x);
-    for (int sy = y.s1; sy < y.s2; sy++) sum = sum + y.wm * area_row(S + (size_t)sy * sw, x);
-    if (y.last) sum = sum + y.wl * area_row(S + (size_t)y.s2 * sw, x);
+    const float sum = area_general<1>(S, sw, x, y);
     const float r = rintf(sum);                        // saturate_cast<uchar>(float): round half to even, clamp
     dst[blockIdx.z * dst_stride + (size_t)dy * dw + dx] = (uint8_t)(r < 0.f ? 0.f : (r > 255.f ? 255.f : r));
 }
@@ -57,6 +69,66 @@ void launch_area_resize(hipStream_t st, const uint8_t* src, size_t src_stride, i
     const double scale_x = 1.0 / ((double)dw / sw), scale_y = 1.0 / ((double)dh / sh);   // hal::resize: 1. / inv_scale
     hipLaunchKernelGGL(k_area_resize, dim3((dw + 63) / 64, (dh + 3) / 4, B), dim3(256), 0, st, src, src_stride, sw, sh, dst,
                        dst_stride, dw, dh, scale_x, scale_y);
+}
+
+// ---- the initial flow of OPTFLOW_USE_INITIAL_FLOW (optflowgf.cpp): resize(flow0, (dw, dh), INTER_AREA); flow *= scale ----------
+// CV_32FC2, shrinking (or the same size).  Three forms, as cv::resize picks them:
+//   AREA_COPY     dsize == ssize: resize() is a copy
+//   AREA_FAST     both ratios whole numbers (to DBL_EPSILON): resizeAreaFast_<float, float>; with two channels the SIMD helper is off
+//                 (it serves cn 1 / 4 only), so every output is the scalar loop's float sum over the iy x ix block in ofs order (rows,
+//                 then columns), grouped four at a time as the unrolled loop adds them (sum += ((a + b) + c) + d), times 1.f / area
+//   AREA_GENERAL  otherwise: computeResizeAreaTab + resizeArea_<float, float>, the form area_general restates
+// then `flow *= scale` (Mat::convertTo(alpha = scale)): a copy when scale == 1, else dst = src * (float)scale + 0.f per element.
+// One thread per output pixel (both channels) on a 2-D grid; the source is read once, the output is ~1/6 of it at pyr_scale 0.4.
+enum { AREA_COPY = 0, AREA_FAST = 1, AREA_GENERAL = 2 };
+template <int FORM>
+__global__ __launch_bounds__(256) void k_area_resize_flow(const float* __restrict__ src, size_t src_stride, int sw, int sh,
+                                                          float* __restrict__ dst, size_t dst_stride, int dw, int dh, double scale_x,
+                                                          double scale_y, int ix, int iy, float mul, int scaled)
+{
+    const int dx = blockIdx.x * 64 + (threadIdx.x & 63), dy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (dx >= dw || dy >= dh) return;
+    const float* S = src + blockIdx.z * src_stride;
+    float v[2];
+    if (FORM == AREA_COPY) {
+        const float2 p = *(const float2*)(S + ((size_t)dy * sw + dx) * 2);
+        v[0] = p.x; v[1] = p.y;
+    } else if (FORM == AREA_FAST) {
+        const int area = ix * iy;
+        const float inv = 1.f / (float)area;
+        const float* B = S + ((size_t)dy * iy * sw + (size_t)dx * ix) * 2;
+        auto at = [&](int k, int c) { return B[((size_t)(k / ix) * sw + (k % ix)) * 2 + c]; };
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            float sum = 0.f;
+            int k = 0;
+            for (; k <= area - 4; k += 4) sum = sum + (((at(k, c) + at(k + 1, c)) + at(k + 2, c)) + at(k + 3, c));
+            for (; k < area; k++) sum = sum + at(k, c);
+            v[c] = sum * inv;
+        }
+    } else {
+        const AreaSpan x = area_span(dx, scale_x, sw), y = area_span(dy, scale_y, sh);
+        v[0] = area_general<2>(S, sw, x, y, 0);
+        v[1] = area_general<2>(S, sw, x, y, 1);
+    }
+    if (scaled) { v[0] = v[0] * mul + 0.f; v[1] = v[1] * mul + 0.f; }
+    *(float2*)(dst + blockIdx.z * dst_stride + ((size_t)dy * dw + dx) * 2) = make_float2(v[0], v[1]);
+}
+void launch_area_resize_flow(hipStream_t st, const float* src, size_t src_stride, int sw, int sh, float* dst, size_t dst_stride, int dw,
+                             int dh, int B, double scale)
+{
+    const double scale_x = 1.0 / ((double)dw / sw), scale_y = 1.0 / ((double)dh / sh);   // hal::resize: 1. / inv_scale
+    const int ix = (int)nearbyint(scale_x), iy = (int)nearbyint(scale_y);               // saturate_cast<int>
+    const bool fast = fabs(scale_x - ix) < DBL_EPSILON && fabs(scale_y - iy) < DBL_EPSILON;
+    const int scaled = fabs(scale - 1.0) >= DBL_EPSILON;                                  // convertTo's noScale test
+    const dim3 grid((dw + 63) / 64, (dh + 3) / 4, B);
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, src, src_stride, sw, sh, dst, dst_stride, dw, dh, scale_x, scale_y, ix, iy,
+                           (float)scale, scaled);
+    };
+    if (dw == sw && dh == sh) go(k_area_resize_flow<AREA_COPY>);
+    else if (fast) go(k_area_resize_flow<AREA_FAST>);
+    else go(k_area_resize_flow<AREA_GENERAL>);
 }
 
 // ---- analyze_pyramid: the window scan of one level (detector.py:296-310) -----------------------------------------------

@@ -356,6 +356,12 @@ struct mav_ctx {
     size_t ws_bytes = 0;           // its size
     size_t group_bytes = 0, deep_bytes = 0;   // ws_bytes = the group slots + the deep set (0 until a call of more than one group)
     float* flow_ws = nullptr;      // lazily allocated (max_batch) when the caller does not want the flow
+    // OPTFLOW_USE_INITIAL_FLOW (mav_farneback_init / _init_dev): the top layer's initial flow, resize(flow0, INTER_AREA) * scale, of the
+    // pairs that enter the top layer together (a group, or the deep layers' pairs), built before the first launch that reads it -- so a
+    // call may write its flow over flow0 (the cv2 idiom).  Allocated by the first such call, grown on demand; part of ws_bytes.
+    float* init_snap = nullptr;
+    int init_cap = 0;              // pairs it holds
+    size_t init_stride = 0, init_bytes = 0;
     // detection scratch (max_batch)
     FoeScratch foe_sc{nullptr, nullptr, nullptr};
     int foe_sc_n = 0;
@@ -466,7 +472,7 @@ static int alloc_group(mav_ctx* c, int group)
     c->small_g = (int)sg;
     c->ws_ready = true;
     c->group_bytes = total;
-    c->ws_bytes = c->group_bytes + c->deep_bytes;
+    c->ws_bytes = c->group_bytes + c->deep_bytes + c->init_bytes;
     return MAV_OK;
 }
 // The deep layers' work set (deep_layers) does not depend on the group and is reachable only by calls of more than one group
@@ -490,7 +496,7 @@ static int ensure_deep(mav_ctx* c)
     }
     c->deep.I = d[0]; c->deep.R = d[1]; c->deep.Ma = d[2]; c->deep.Mb = d[3]; c->deep.f[0] = d[4]; c->deep.f[1] = d[5];
     c->deep_bytes = bytes;                     // only once the whole set exists
-    c->ws_bytes = c->group_bytes + c->deep_bytes;
+    c->ws_bytes = c->group_bytes + c->deep_bytes + c->init_bytes;
     return MAV_OK;
 }
 // The Farneback workspace (174 MB per 1080p slot, 16 slots by default) belongs to the calls that compute flow: a context created for
@@ -540,7 +546,7 @@ extern "C" int mav_destroy(mav_ctx* c)
         void* wb[] = {w.I, w.R, w.Ma, w.Mb, w.fc[0], w.fc[1], w.Htmp, w.Ic, w.Rc, c->deep.I, c->deep.R, c->deep.Ma, c->deep.Mb, c->deep.f[0], c->deep.f[1]};
         for (void* b : wb) if (b) hipFree(b);
     }
-    void* bufs[] = {c->flow_ws, c->foe_sc.cand, c->foe_sc.count, c->foe_sc.best_key, c->foe_sc.done, c->foe_dev, c->box_acc, c->u64_scratch,
+    void* bufs[] = {c->flow_ws, c->init_snap, c->foe_sc.cand, c->foe_sc.count, c->foe_sc.best_key, c->foe_sc.done, c->foe_dev, c->box_acc, c->u64_scratch,
                     c->i32_scratch, c->derot_dev, c->pyr_ws, c->sat};
     for (void* b : bufs) if (b) hipFree(b);
     for (auto& blk : c->scratch) if (blk.p) hipFree(blk.p);
@@ -566,7 +572,11 @@ extern "C" int mav_create(mav_ctx** out, int device, int W, int H, int max_batch
     if (fb.levels < 0 || fb.winsize < 2 || fb.winsize > 64 || fb.iterations < 1 || fb.poly_n < 1 || fb.poly_n > MAV_MAX_POLY_N)
         return fail(MAV_ERR_ARG, "unsupported Farneback parameters (levels=%d winsize=%d iterations=%d poly_n=%d)", fb.levels,
                     fb.winsize, fb.iterations, fb.poly_n);
-    if (fb.flags != 0) return fail(MAV_ERR_ARG, "only flags == 0 (box window, no initial flow) is implemented, got %d", fb.flags);
+    // OPTFLOW_USE_INITIAL_FLOW is accepted so that a cv2 argument list passes as it is; only the entry points that take an initial flow
+    // (mav_farneback_init / _init_dev) use one, the others start from zero whatever the bit says
+    if (fb.flags & ~MAV_OPTFLOW_USE_INITIAL_FLOW)
+        return fail(MAV_ERR_ARG, "only flags 0 and OPTFLOW_USE_INITIAL_FLOW (4) are implemented (box window; OPTFLOW_FARNEBACK_GAUSSIAN is not), got %d",
+                    fb.flags);
     if (fb.winsize / 2 != 6 && blur_iter_lds_bytes(fb.winsize) > (size_t)160 * 1024)
         return fail(MAV_ERR_ARG, "winsize %d needs %zu bytes of LDS per workgroup in the general sweep kernel, the CU has 163840", fb.winsize,
                     blur_iter_lds_bytes(fb.winsize));
@@ -1283,7 +1293,15 @@ static SweepPlan plan_sweeps(const mav_ctx* c, int k, int g, bool bands_ok)
 // first sweep: pixel rows [16 a0 - 8, 16 a1 + 8) -- what that sweep reads (6-pixel halo) -- which lie below everything the bands
 // above have written into Ma (their odd sweeps end one whole tile row higher); the rows two neighbouring bands both need are
 // simply built twice, to the same values.
-struct BandUpdate { const float* flow_prev; size_t fc_stride; int pw, ph; float mul; };
+struct BandUpdate { const float* flow_prev; size_t fc_stride; int pw, ph; float mul; bool exact; };
+// The initial M of pixel rows [y0, y1) of gs pairs from the source `u` names: zero (flow_prev == nullptr), the coarser layer's flow
+// upsampled (pw x ph, times mul) or -- exact: the top layer of a call with an initial flow -- a field of the layer's own size.
+static void initial_m(hipStream_t st, const BandUpdate& u, const float* r0, const float* r1, size_t rs, int gs, int w, int h, float* M, size_t ms,
+                      int y0 = 0, int y1 = -1)
+{
+    if (u.exact) launch_update_matrices_flow(st, r0, r1, rs, u.flow_prev, u.fc_stride, gs, w, h, M, ms, y0, y1);
+    else launch_update_matrices(st, r0, r1, rs, u.flow_prev, u.fc_stride, u.pw, u.ph, u.mul, gs, w, h, M, ms, y0, y1);
+}
 // phase = 1 (the pairs of the second stream, option "band_phase", off by default): the partition is shifted by half a band -- J + 1 bands,
 // the first and the last of half size.  Two streams that start a group together with the same partition stay in lockstep: both build a
 // band's initial M (HBM-bound) at the same moments and both sweep (cache-bound) at the same moments -- untraced at 3840x2160: 1.3 ms per
@@ -1317,8 +1335,7 @@ static void sweeps_band_major(mav_ctx* c, hipStream_t st, int kid, float* Ma, fl
         if (a1 <= a0) continue;
         if (upd) {
             ProfScope ps(c, K_UPDATE, st);
-            launch_update_matrices(st, r0, r1, rs, upd->flow_prev, upd->fc_stride, upd->pw, upd->ph, upd->mul, gs, lw, lh, Ma, ms,
-                                   a0 == 0 ? 0 : a0 * 16 - 8, j == J - 1 ? lh : a1 * 16 + 8);
+            initial_m(st, *upd, r0, r1, rs, gs, lw, lh, Ma, ms, a0 == 0 ? 0 : a0 * 16 - 8, j == J - 1 ? lh : a1 * 16 + 8);
         }
         for (int it = 0; it < I; it++) {
             const int update = it < I - 1;
@@ -1348,11 +1365,15 @@ static void sweeps_plain(mav_ctx* c, hipStream_t ss, int kid, float* Min, float*
 // Initial M and the `iterations` sweeps of layer k for g pairs whose expansions lie at r0 / r1 (slot stride rs), starting on
 // stream st.  flow_prev = the coarser layer's flow (pw x ph, slot stride fc_stride; nullptr at the top layer); the layer's flow goes to
 // fdst (slot stride fstride).  M ping-pongs through Ma / Mb (slot stride ms).  On return everything has been joined back into st.
+// flow_init (top layer of a call with an initial flow only): the layer's initial flow itself, l.w x l.h, slot stride fi_stride.
 static int layer_sweeps(mav_ctx* c, hipStream_t st, int k, int g, const float* r0g, const float* r1g, size_t rs, const float* flow_prev,
-                        size_t fc_stride, int pw, int ph, float* fdst, size_t fstride, float* Ma, float* Mb, size_t ms)
+                        size_t fc_stride, int pw, int ph, float* fdst, size_t fstride, float* Ma, float* Mb, size_t ms,
+                        const float* flow_init = nullptr, size_t fi_stride = 0)
 {
     const Layer& l = c->layers[k];
     const float mul = (float)(1. / c->fb.pyr_scale);
+    const BandUpdate src = flow_init ? BandUpdate{flow_init, fi_stride, 0, 0, 0.f, true} : BandUpdate{flow_prev, fc_stride, pw, ph, mul, false};
+    auto src_at = [&](int s0) { BandUpdate u = src; if (u.flow_prev) u.flow_prev += (size_t)s0 * u.fc_stride; return u; };   // from pair s0 on
     const bool bands_ok = blur_iter_bands_ok(l.w, c->fb.winsize, ms, rs, fstride, Ma, Mb, r0g, r1g, fdst);
     const SweepPlan p = plan_sweeps(c, k, g, bands_ok);
     const int kid = k == 0 ? K_ITER : K_ITER_COARSE;
@@ -1366,14 +1387,14 @@ static int layer_sweeps(mav_ctx* c, hipStream_t st, int k, int g, const float* r
             float *Min = Ma + (size_t)(s0 & 1) * ms, *Mout = Mb + (size_t)(s0 & 1) * ms;
             const float *r0 = r0g + (size_t)s0 * rs, *r1 = r1g + (size_t)s0 * rs;
             float* fo = fdst + (size_t)s0 * fstride;
-            const BandUpdate bu{flow_prev ? flow_prev + (size_t)s0 * fc_stride : nullptr, fc_stride, pw, ph, mul};
+            const BandUpdate bu = src_at(s0);
             if (p.J > 1) {
                 sweeps_band_major(c, ss, kid, Min, Mout, ms, r0, r1, rs, 1, l.w, l.h, T, p.J, fo, fstride, &bu, true,
                                   (c->band_phase && (s0 & 1) && p.J >= c->band_phase) ? 1 : 0);
                 continue;
             }
             { ProfScope ps(c, K_UPDATE, ss);
-              launch_update_matrices(ss, r0, r1, rs, bu.flow_prev, fc_stride, pw, ph, mul, 1, l.w, l.h, Min, ms); }
+              initial_m(ss, bu, r0, r1, rs, 1, l.w, l.h, Min, ms); }
             sweeps_plain(c, ss, kid, Min, Mout, ms, r0, r1, rs, 1, l, fo, fstride, true);
         }
         prof_close_stream(c, c->pair_stream); prof_close_stream(c, st);
@@ -1392,8 +1413,7 @@ static int layer_sweeps(mav_ctx* c, hipStream_t st, int k, int g, const float* r
             const size_t m_off = (size_t)(idx & 1) * p.half * ms;
             const float *r0 = r0g + (size_t)s0 * rs, *r1 = r1g + (size_t)s0 * rs;
             { ProfScope ps(c, K_UPDATE, ss);
-              launch_update_matrices(ss, r0, r1, rs, flow_prev ? flow_prev + (size_t)s0 * fc_stride : nullptr, fc_stride, pw, ph, mul, gs, l.w, l.h,
-                                     Ma + m_off, ms); }
+              initial_m(ss, src_at(s0), r0, r1, rs, gs, l.w, l.h, Ma + m_off, ms); }
             sweeps_plain(c, ss, K_ITER_COARSE, Ma + m_off, Mb + m_off, ms, r0, r1, rs, gs, l, fdst + (size_t)s0 * fstride, fstride, true);
         }
         prof_close_stream(c, c->pair_stream); prof_close_stream(c, st);
@@ -1403,7 +1423,7 @@ static int layer_sweeps(mav_ctx* c, hipStream_t st, int k, int g, const float* r
     }
     if (!p.m_per_sub) {
         ProfScope ps(c, K_UPDATE, st);
-        launch_update_matrices(st, r0g, r1g, rs, flow_prev, fc_stride, pw, ph, mul, g, l.w, l.h, Ma, ms);
+        initial_m(st, src, r0g, r1g, rs, g, l.w, l.h, Ma, ms);
     }
     // Sub-groups are swept one after the other on one stream, so they all ping-pong M through the SAME two buffers (the first
     // sub-group's slots; option "share_m"): the M lines then stay hot in the Infinity Cache from pair to pair instead of leaving a
@@ -1414,8 +1434,7 @@ static int layer_sweeps(mav_ctx* c, hipStream_t st, int k, int g, const float* r
         const float *r0 = r0g + (size_t)s0 * rs, *r1 = r1g + (size_t)s0 * rs;
         if (p.m_per_sub) {
             ProfScope ps(c, K_UPDATE, st);
-            launch_update_matrices(st, r0, r1, rs, flow_prev ? flow_prev + (size_t)s0 * fc_stride : nullptr, fc_stride, pw, ph, mul, gs, l.w,
-                                   l.h, Ma + m_off, ms);
+            initial_m(st, src_at(s0), r0, r1, rs, gs, l.w, l.h, Ma + m_off, ms);
         }
         float* fo = fdst + (size_t)s0 * fstride;
         if (p.J > 1 && gs == 1) sweeps_band_major(c, st, kid, Ma + m_off, Mb + m_off, ms, r0, r1, rs, gs, l.w, l.h, T, p.J, fo, fstride);
@@ -1526,7 +1545,8 @@ static void pyramid_multi(mav_ctx* c, hipStream_t st, const uint8_t* prev, const
 
 // DEEP LAYERS (kd .. top) of D pairs at once, on the compute stream; the flow of layer kd lands in deep.f[kd & 1], slot stride
 // 2 * c_stride[kd].  See mav_ctx::DeepSet.  Same tile functions on the same data as the per-group path: bit-identical flow.
-static int deep_layers(mav_ctx* c, hipStream_t st, const uint8_t* prev, const uint8_t* next, int D, bool seq)
+// flow_init: the top layer's initial flow of the D pairs (init_snap) or nullptr.
+static int deep_layers(mav_ctx* c, hipStream_t st, const uint8_t* prev, const uint8_t* next, int D, bool seq, const float* flow_init = nullptr)
 {
     const int L = (int)c->layers.size(), kd = c->kd;
     const int F = seq ? D + 1 : 2 * D;
@@ -1542,7 +1562,8 @@ static int deep_layers(mav_ctx* c, hipStream_t st, const uint8_t* prev, const ui
     for (int k = L - 1; k >= kd; k--) {
         const size_t rs = 5 * sk(k);
         const float *r0 = Rk(k), *r1 = Rk(k) + (seq ? rs : rs * (size_t)D);
-        CHK(layer_sweeps(c, st, k, D, r0, r1, rs, flow_prev, fp_stride, pw, ph, c->deep.f[k & 1], 2 * sk(k), c->deep.Ma, c->deep.Mb, 5 * sk(k)));
+        CHK(layer_sweeps(c, st, k, D, r0, r1, rs, flow_prev, fp_stride, pw, ph, c->deep.f[k & 1], 2 * sk(k), c->deep.Ma, c->deep.Mb, 5 * sk(k),
+                         k == L - 1 ? flow_init : nullptr, c->init_stride));
         flow_prev = c->deep.f[k & 1]; fp_stride = 2 * sk(k); pw = c->layers[k].w; ph = c->layers[k].h;
     }
     return MAV_OK;
@@ -1550,7 +1571,8 @@ static int deep_layers(mav_ctx* c, hipStream_t st, const uint8_t* prev, const ui
 
 // One group of g pairs: every coarse layer completely (top layer first: images, expansions, initial M, sweeps), then the finest layer.
 // deep_flow != nullptr: the layers from kd up have been computed already (deep_layers); the group starts at layer kd - 1 with
-// deep_flow (this group's first pair; slot stride deep_stride) as its coarser layer.
+// deep_flow (this group's first pair; slot stride deep_stride) as its coarser layer.  flow_init: the top layer's initial flow of the g
+// pairs (init_snap; only without deep_flow) or nullptr.
 // SMALL GROUPS (is_small_group: one 1080p pair, two 720p pairs ...; BASELINE config 2) are a chain of ~30 dependent launches that
 // each fill a fraction of the chip, ~4.5 us of boundary apiece.  For them the whole pyramid's layer images come from ONE launch and
 // all expansions from ONE launch (k_blur_multi / k_polyexp_multi: the workgroups of several layers in one grid, every layer into a
@@ -1559,7 +1581,7 @@ static int deep_layers(mav_ctx* c, hipStream_t st, const uint8_t* prev, const ui
 // (Measured for such groups and not kept: the finest layer's images and expansions on a side stream underneath the coarse chain;
 // all sweeps of a layer in one launch of resident workgroups that hand M' over through flags -- HISTORY.md.)
 static int flow_group(mav_ctx* c, const uint8_t* prev, const uint8_t* next, int g, bool seq, float* flow_out, const float* deep_flow = nullptr,
-                      size_t deep_stride = 0)
+                      size_t deep_stride = 0, const float* flow_init = nullptr)
 {
     mav_ctx::WorkSet& w = c->ws;
     const hipStream_t st = c->stream;
@@ -1579,7 +1601,8 @@ static int flow_group(mav_ctx* c, const uint8_t* prev, const uint8_t* next, int 
         for (int k = L - 1; k >= 0; k--) {
             const size_t rs = 5 * sk(k);
             const float *r0 = Rk(k), *r1 = Rk(k) + (seq ? rs : rs * (size_t)g);
-            CHK(layer_sweeps(c, st, k, g, r0, r1, rs, flow_prev, fc_stride, pw, ph, k ? w.fc[k & 1] : flow_out, k ? fc_stride : 2 * n0, w.Ma, w.Mb, 5 * n0));
+            CHK(layer_sweeps(c, st, k, g, r0, r1, rs, flow_prev, fc_stride, pw, ph, k ? w.fc[k & 1] : flow_out, k ? fc_stride : 2 * n0, w.Ma, w.Mb, 5 * n0,
+                             k == L - 1 ? flow_init : nullptr, c->init_stride));
             flow_prev = w.fc[k & 1]; pw = c->layers[k].w; ph = c->layers[k].h;
         }
         return MAV_OK;
@@ -1587,7 +1610,8 @@ static int flow_group(mav_ctx* c, const uint8_t* prev, const uint8_t* next, int 
     const float *r0 = nullptr, *r1 = nullptr;
     for (int k = k_top; k >= 0; k--) {
         layer_expansions(c, st, k, prev, next, g, seq, w.I, w.R, &r0, &r1);
-        CHK(layer_sweeps(c, st, k, g, r0, r1, 5 * n0, flow_prev, fp_stride, pw, ph, k ? w.fc[k & 1] : flow_out, k ? fc_stride : 2 * n0, w.Ma, w.Mb, 5 * n0));
+        CHK(layer_sweeps(c, st, k, g, r0, r1, 5 * n0, flow_prev, fp_stride, pw, ph, k ? w.fc[k & 1] : flow_out, k ? fc_stride : 2 * n0, w.Ma, w.Mb, 5 * n0,
+                         k == L - 1 ? flow_init : nullptr, c->init_stride));
         flow_prev = w.fc[k & 1]; fp_stride = fc_stride; pw = c->layers[k].w; ph = c->layers[k].h;
     }
     return MAV_OK;
@@ -1596,10 +1620,41 @@ static int flow_group(mav_ctx* c, const uint8_t* prev, const uint8_t* next, int 
 // does a call of `batch` pairs run its deep layers once for the whole call (deep_layers) instead of once per group?
 static bool use_deep_batch(const mav_ctx* c, int batch) { return c->deep_batch && c->kd > 0 && batch > c->group; }
 
-extern "C" int mav_farneback_dev(mav_ctx* c, const uint8_t* prev, const uint8_t* next, int batch, float* flow)
+// OPTFLOW_USE_INITIAL_FLOW: init_snap for `pairs` pairs (grown on demand: the buffer it replaces may still be read by enqueued work).
+static int ensure_init_snapshot(mav_ctx* c, int pairs)
 {
-    if (!c || !prev || !next || !flow) return fail(MAV_ERR_ARG, "mav_farneback: NULL argument");
-    if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "batch %d outside [1, %d]", batch, c->max_batch);
+    if (pairs <= c->init_cap) return MAV_OK;
+    const Layer& l = c->layers.back();
+    const size_t stride = ((size_t)2 * l.w * l.h + 63) & ~(size_t)63, bytes = sizeof(float) * stride * pairs;
+    if (c->init_snap) CHK(sync_all_streams(c));
+    float* p = nullptr;
+    const hipError_t e = hipMalloc(&p, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? MAV_ERR_OOM : MAV_ERR_HIP, "initial-flow workspace (%zu bytes): %s", bytes, hipGetErrorString(e));
+    }
+    if (c->init_snap) hipFree(c->init_snap);
+    c->init_snap = p; c->init_cap = pairs; c->init_stride = stride; c->init_bytes = bytes;
+    c->ws_bytes = c->group_bytes + c->deep_bytes + c->init_bytes;
+    return MAV_OK;
+}
+// optflowgf.cpp at the top layer k = L - 1 with OPTFLOW_USE_INITIAL_FLOW: flow = resize(flow0, (w_k, h_k), INTER_AREA); flow *= scale_k,
+// scale_k = pyr_scale^k as the repeated product -- for n pairs of flow0 (slot stride 2 W H) into init_snap.
+static void snapshot_initial_flow(mav_ctx* c, const float* flow0, int n)
+{
+    const int top = (int)c->layers.size() - 1;
+    const Layer& l = c->layers[top];
+    double scale = 1;
+    for (int i = 0; i < top; i++) scale *= c->fb.pyr_scale;
+    ProfScope ps(c, K_MISC);
+    launch_area_resize_flow(c->stream, flow0, 2 * c->n0, c->W, c->H, c->init_snap, c->init_stride, l.w, l.h, n, scale);
+}
+
+// flow_init == nullptr: every pair starts from zero (mav_farneback_dev).  Otherwise the top layer's initial M of pair i comes from
+// flow_init[i] (mav_farneback_init_dev); every other layer as always.  The snapshot of a set of pairs is taken right before the first
+// launch that reads it and after every launch that writes flow of an earlier set: flow_init may be flow.
+static int farneback_run(mav_ctx* c, const uint8_t* prev, const uint8_t* next, int batch, const float* flow_init, float* flow)
+{
     HIPCHK(hipSetDevice(c->device));
     CHK(ensure_workspace(c));
     // A frame SEQUENCE -- the caller's two batches are views of one run of batch + 1 consecutive frames, next = prev + one frame,
@@ -1610,21 +1665,45 @@ extern "C" int mav_farneback_dev(mav_ctx* c, const uint8_t* prev, const uint8_t*
     const bool deep = use_deep_batch(c, batch);
     if (deep) CHK(ensure_deep(c));
     const int chunk = deep ? c->deep_cap : batch;
+    if (flow_init) {
+        const int need = deep ? chunk : c->group;
+        CHK(ensure_init_snapshot(c, need < batch ? need : batch));
+    }
     for (int d0 = 0; d0 < batch; d0 += chunk) {
         const int D = batch - d0 < chunk ? batch - d0 : chunk;
         const size_t dstride = deep ? 2 * c->c_stride[c->kd] : 0;
         // (Measured and not kept: the deep chain on a stream of its own underneath the first group's top-layer images / expansions --
         // 592 vs 597 pairs/s at 3840x2160 / 5 layers / 16 pairs: the fork / join events cost more than the overlap hides.)
-        if (deep) CHK(deep_layers(c, c->stream, prev + (size_t)d0 * c->n0, next + (size_t)d0 * c->n0, D, seq));
+        if (deep) {
+            if (flow_init) snapshot_initial_flow(c, flow_init + (size_t)d0 * 2 * c->n0, D);
+            CHK(deep_layers(c, c->stream, prev + (size_t)d0 * c->n0, next + (size_t)d0 * c->n0, D, seq, flow_init ? c->init_snap : nullptr));
+        }
         for (int g0 = d0; g0 < d0 + D; g0 += c->group) {
             const int g = d0 + D - g0 < c->group ? d0 + D - g0 : c->group;
+            if (flow_init && !deep) snapshot_initial_flow(c, flow_init + (size_t)g0 * 2 * c->n0, g);
             CHK(flow_group(c, prev + (size_t)g0 * c->n0, next + (size_t)g0 * c->n0, g, seq, flow + (size_t)g0 * 2 * c->n0,
-                           deep ? c->deep.f[c->kd & 1] + (size_t)(g0 - d0) * dstride : nullptr, dstride));
+                           deep ? c->deep.f[c->kd & 1] + (size_t)(g0 - d0) * dstride : nullptr, dstride,
+                           flow_init && !deep ? c->init_snap : nullptr));
             CHK(check_launch("farneback kernels"));
         }
     }
     c->last_flow = flow;
     return MAV_OK;
+}
+extern "C" int mav_farneback_dev(mav_ctx* c, const uint8_t* prev, const uint8_t* next, int batch, float* flow)
+{
+    if (!c || !prev || !next || !flow) return fail(MAV_ERR_ARG, "mav_farneback: NULL argument");
+    if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "batch %d outside [1, %d]", batch, c->max_batch);
+    return farneback_run(c, prev, next, batch, nullptr, flow);
+}
+extern "C" int mav_farneback_init_dev(mav_ctx* c, const uint8_t* prev, const uint8_t* next, int batch, const float* flow_init, float* flow)
+{
+    if (!c || !prev || !next || !flow_init || !flow) return fail(MAV_ERR_ARG, "mav_farneback_init_dev: NULL argument");
+    if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "batch %d outside [1, %d]", batch, c->max_batch);
+    const size_t n = (size_t)batch * 2 * c->n0;
+    if (flow_init != flow && flow_init < flow + n && flow < flow_init + n)
+        return fail(MAV_ERR_ARG, "mav_farneback_init_dev: flow_init and flow overlap without being the same field");
+    return farneback_run(c, prev, next, batch, flow_init, flow);
 }
 extern "C" const float* mav_last_flow_dev(const mav_ctx* c) { return c ? c->last_flow : nullptr; }
 
@@ -2021,6 +2100,18 @@ extern "C" int mav_farneback(mav_ctx* c, const uint8_t* prev, const uint8_t* nex
     return mav_sync(c);
 }
 
+extern "C" int mav_farneback_init(mav_ctx* c, const uint8_t* prev, const uint8_t* next, int batch, const float* flow_init, float* flow)
+{
+    CHK(check_batch(c, batch, "mav_farneback_init"));
+    if (!prev || !next || !flow_init || !flow) return fail(MAV_ERR_ARG, "mav_farneback_init: NULL argument");
+    const size_t n = c->n0 * batch;
+    DevBuf dp, dn, df;
+    const uint8_t *dprev, *dnext;
+    CHK(upload_frames(c, prev, next, batch, dp, dn, &dprev, &dnext)); CHK(df.upload(c, flow_init, n * 2 * sizeof(float)));
+    CHK(mav_farneback_init_dev(c, dprev, dnext, batch, df.as<float>(), df.as<float>()));      // in place on the device
+    CHK(download(c, flow, df.p, n * 2 * sizeof(float)));
+    return mav_sync(c);
+}
 extern "C" int mav_derotate(mav_ctx* c, const float* flow, const double* omega, const double* dt, int batch, double* flow_out)
 {
     CHK(check_batch(c, batch, "mav_derotate"));

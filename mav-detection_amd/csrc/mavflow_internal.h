@@ -70,9 +70,10 @@ void launch_blur_multi(hipStream_t st, const uint8_t* img, const uint8_t* img2, 
 void launch_update_matrices(hipStream_t st, const float* R0, const float* R1, size_t R_stride, const float* flow_prev,
                             size_t fp_stride, int pw, int ph, float mul, int G, int w, int h, float* M, size_t M_stride,
                             int y_begin = 0, int y_end = -1 /* pixel rows [y_begin, y_end) only; -1 = to the bottom */);
-// explicit per-pixel flow (h x w x 2), used by the stage hook
+// explicit per-pixel flow (h x w x 2): the stage hook, and the top layer of a call with an initial flow (OPTFLOW_USE_INITIAL_FLOW)
 void launch_update_matrices_flow(hipStream_t st, const float* R0, const float* R1, size_t R_stride, const float* flow,
-                                 size_t f_stride, int G, int w, int h, float* M, size_t M_stride);
+                                 size_t f_stride, int G, int w, int h, float* M, size_t M_stride,
+                                 int y_begin = 0, int y_end = -1 /* pixel rows [y_begin, y_end) only; -1 = to the bottom */);
 void launch_blur_iter(hipStream_t st, const float* M_in, float* M_out, size_t M_stride, const float* R0, const float* R1,
                       size_t R_stride, int G, int w, int h, int winsize, int do_update, int store_flow, float* flow, size_t f_stride,
                       int ty0 = 0, int ty1 = -1 /* tile rows [ty0, ty1) of 16 pixel rows; ty1 < 0 = the whole layer */,
@@ -145,6 +146,10 @@ struct PyrPlan {
 };
 void launch_area_resize(hipStream_t st, const uint8_t* src, size_t src_stride, int sw, int sh, uint8_t* dst, size_t dst_stride,
                         int dw, int dh, int B);
+// OPTFLOW_USE_INITIAL_FLOW: B float2 fields sw x sh -> dw x dh (cv2.resize INTER_AREA, fast or general path as OpenCV picks it), times
+// `scale` (flow *= scale).  dw <= sw, dh <= sh; strides in floats.
+void launch_area_resize_flow(hipStream_t st, const float* src, size_t src_stride, int sw, int sh, float* dst, size_t dst_stride, int dw,
+                             int dh, int B, double scale);
 void launch_level_scan(hipStream_t st, const uint8_t* img, size_t stride, int B, int W, int H, unsigned idx_base,
                        unsigned long long* key /*[B], zeroed by the caller*/);
 void launch_pyramid_finalize(hipStream_t st, const unsigned long long* key, const PyrPlan& plan, const uint8_t* img0,

@@ -54,7 +54,10 @@ EXPORTS = [
     "mav_upload_gather", "mav_download_async", "mav_marker_create", "mav_marker_record", "mav_marker_wait", "mav_marker_destroy",
     "mav_tpr_fpr_counts_dev", "mav_bgr2gray_dev", "mav_png_unfilter", "mav_comm_count",
     "mav_marker_query", "mav_frame_step_dev", "mav_frame_step_post", "mav_frame_step_wait", "mav_worker_drain",
+    "mav_farneback_init", "mav_farneback_init_dev",
 ]
+
+OPTFLOW_USE_INITIAL_FLOW = 4                    # FbParams.flags bit (cv2.OPTFLOW_USE_INITIAL_FLOW): see Context.farneback(initial_flow=)
 
 GATHER_ORDERED, GATHER_SOURCES_HELD = 1, 2      # mav_upload_gather flags
 STEP_MAX_GATHER = 4
@@ -118,6 +121,8 @@ def load(path: str | None = None) -> C.CDLL:
     vp = C.c_void_p
     lib.mav_farneback.argtypes = [vp, vp, vp, C.c_int, vp]
     lib.mav_farneback_dev.argtypes = [vp, vp, vp, C.c_int, vp]
+    lib.mav_farneback_init.argtypes = [vp, vp, vp, C.c_int, vp, vp]
+    lib.mav_farneback_init_dev.argtypes = [vp, vp, vp, C.c_int, vp, vp]
     lib.mav_derotate.argtypes = [vp, vp, vp, vp, C.c_int, vp]
     lib.mav_foe_dense.argtypes = [vp, vp, vp, C.c_int, C.POINTER(FoeParams), vp]
     lib.mav_ransac.argtypes = [vp, vp, C.c_int, C.c_double, vp]
@@ -490,14 +495,60 @@ class Context:
             raise ValueError(f"{name}: expected uint8, got {a.dtype}")
         return np.ascontiguousarray(a)
 
-    def farneback(self, prev, nxt) -> np.ndarray:
+    def _flows(self, a, B, name):
+        """(H, W, 2) for a batch of one, or (B, H, W, 2): float32, C-contiguous."""
+        a = np.asarray(a)
+        if a.ndim == 3 and B == 1:
+            a = a[None]
+        if a.shape != (B, self.H, self.W, 2):
+            raise ValueError(f"{name}: expected ({B}, {self.H}, {self.W}, 2) float32, got {a.shape}")
+        if a.dtype != np.float32:
+            raise ValueError(f"{name}: expected float32, got {a.dtype}")
+        return np.ascontiguousarray(a)
+
+    def farneback(self, prev, nxt, initial_flow=None) -> np.ndarray:
+        """cv2.calcOpticalFlowFarneback for a batch of pairs -> (B, H, W, 2) float32.  initial_flow: None starts every pair from zero;
+        an (H, W, 2) field (one pair) or (B, H, W, 2) fields are the starting flow of each pair, as cv2 takes `flow` with
+        OPTFLOW_USE_INITIAL_FLOW set (mav_farneback_init)."""
         prev, nxt = self._imgs(prev, "prev"), self._imgs(nxt, "next")
         if prev.shape != nxt.shape:
             raise ValueError("prev and next differ in shape")
         B = prev.shape[0]
+        init = None if initial_flow is None else self._flows(initial_flow, B, "initial_flow")
         flow = _pinned.empty(self, (B, self.H, self.W, 2), np.float32)
-        check(self.lib.mav_farneback(self.h, _ptr(prev), _ptr(nxt), B, _ptr(flow)))
+        if init is None:
+            check(self.lib.mav_farneback(self.h, _ptr(prev), _ptr(nxt), B, _ptr(flow)))
+        else:
+            check(self.lib.mav_farneback_init(self.h, _ptr(prev), _ptr(nxt), B, _ptr(init), _ptr(flow)))
         return flow
+
+    def farneback_chain(self, frames, initial_flow=None) -> np.ndarray:
+        """cv2's video idiom over a run of frames (n + 1, H, W) u8 -> (n, H, W, 2) float32:
+            flow = calcOpticalFlowFarneback(f[i], f[i + 1], flow, ..., flags | OPTFLOW_USE_INITIAL_FLOW)
+        pair i starts from pair i - 1's flow, pair 0 from initial_flow ((H, W, 2) float32) or from zero when it is None.  The run is
+        uploaded once, the n one-pair calls keep their input and output flow on the device, and one download brings all n back."""
+        frames = self._imgs(frames, "frames")
+        n = frames.shape[0] - 1
+        if n < 1:
+            raise ValueError("a chain needs at least two frames")
+        init = None if initial_flow is None else self._flows(initial_flow, 1, "initial_flow")
+        fbytes, px = self.H * self.W * 2 * 4, self.H * self.W
+        d_frames = self.alloc(frames.nbytes).upload(frames)
+        d_flow = self.alloc(n * fbytes)
+        try:
+            if init is None:                          # zero start: the flags = 0 call (bit-identical to an all-zero initial flow)
+                check(self.lib.mav_farneback_dev(self.h, d_frames.ptr, d_frames.ptr + px, 1, d_flow.ptr))
+            else:
+                check(self.lib.mav_memcpy_h2d(self.h, d_flow.ptr, _ptr(init), fbytes))
+                check(self.lib.mav_farneback_init_dev(self.h, d_frames.ptr, d_frames.ptr + px, 1, d_flow.ptr, d_flow.ptr))
+            for i in range(1, n):
+                check(self.lib.mav_farneback_init_dev(self.h, d_frames.ptr + i * px, d_frames.ptr + (i + 1) * px, 1,
+                                                      d_flow.ptr + (i - 1) * fbytes, d_flow.ptr + i * fbytes))
+            return d_flow.download(np.float32, (n, self.H, self.W, 2))
+        finally:
+            self.sync()
+            d_flow.free()
+            d_frames.free()
 
     def farneback_sequence(self, frames) -> np.ndarray:
         """Flow of every consecutive pair of a run of frames (n + 1, H, W) u8 -> (n, H, W, 2) float32.  The two batches handed to
@@ -712,8 +763,13 @@ class Context:
         check(self.lib.mav_memcpy_d2h(self.h, _ptr(out), p + pair * out.nbytes, out.nbytes))
         return out
 
-    def farneback_dev(self, prev_ptr, next_ptr, batch, flow_ptr):
-        check(self.lib.mav_farneback_dev(self.h, prev_ptr, next_ptr, batch, flow_ptr))
+    def farneback_dev(self, prev_ptr, next_ptr, batch, flow_ptr, flow_init_ptr=None):
+        """Enqueue only.  flow_init_ptr: None = zero start (mav_farneback_dev); a device pointer (it may equal flow_ptr) = the pairs'
+        initial flow (mav_farneback_init_dev)."""
+        if flow_init_ptr is None:
+            check(self.lib.mav_farneback_dev(self.h, prev_ptr, next_ptr, batch, flow_ptr))
+        else:
+            check(self.lib.mav_farneback_init_dev(self.h, prev_ptr, next_ptr, batch, flow_init_ptr, flow_ptr))
 
     # -- multi-GPU record exchange (RCCL through the library, on the context's stream) ------------------------
     def comm_unique_id(self) -> np.ndarray:

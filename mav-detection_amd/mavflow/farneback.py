@@ -85,7 +85,10 @@ class Farneback:
     def process(self) -> np.ndarray:
         _, img = self.capture.read()
         gray = self._gray(img)
-        self.flow = self.ctx.farneback(self.prevgray, gray)[0]
+        # with cv2.OPTFLOW_USE_INITIAL_FLOW in PARAMS["flags"] the call (:76-80) hands cv2 the previous result as its starting flow
+        # (zeros before the first frame); the default flags = 0 starts from zero
+        init = self.flow if self.PARAMS["flags"] & _lib.OPTFLOW_USE_INITIAL_FLOW else None
+        self.flow = self.ctx.farneback(self.prevgray, gray, initial_flow=init)[0]
         self.prevgray = gray
         self.hsv, invalid_frame = flow_to_hsv(self.flow)
         result = hsv_to_bgr(self.hsv)
