@@ -433,6 +433,11 @@ int mav_stage_blur_resize_two_pass(mav_ctx*, const uint8_t* img, int k, float* o
 int mav_stage_polyexp(mav_ctx*, const float* I, int k, float* R);
 /* FarnebackUpdateMatrices at layer k: R0, R1 (5,h,w), flow (h,w,2) -> M (5,h,w) */
 int mav_stage_update_matrices(mav_ctx*, const float* R0, const float* R1, const float* flow, int k, float* M);
+/* the initial M of layer k as a call builds it: from the coarser layer's flow flow_coarse (h_(k+1), w_(k+1), 2), upsampled to
+ * layer k and times 1 / pyr_scale inside the kernel, or from a zero flow when flow_coarse is NULL (MAV_ERR_ARG at the top layer) */
+int mav_stage_update_matrices_from(mav_ctx*, const float* R0, const float* R1, const float* flow_coarse, int k, float* M);
+/* the initial flow of layer k from a frame-size field flow0 (H, W, 2): resize(INTER_AREA) to (h_k, w_k), times pyr_scale^k */
+int mav_stage_initial_flow(mav_ctx*, const float* flow0, int k, float* out);
 /* one FarnebackUpdateFlow_Blur sweep at layer k: M (5,h,w) -> flow (h,w,2) and, if update != 0, M_out (5,h,w) */
 int mav_stage_blur_iter(mav_ctx*, const float* R0, const float* R1, const float* M, int k, int update, float* flow,
                         float* M_out);

@@ -2680,6 +2680,46 @@ extern "C" int mav_stage_update_matrices(mav_ctx* c, const float* R0, const floa
     CHK(download(c, M, dm.p, 5 * n * sizeof(float)));
     return mav_sync(c);
 }
+// The initial M as layer_sweeps builds it for layer k: from the coarser layer's flow (layer k + 1's size, upsampled and times
+// 1 / pyr_scale inside the kernel) or, flow_coarse == NULL, from a zero flow.
+extern "C" int mav_stage_update_matrices_from(mav_ctx* c, const float* R0, const float* R1, const float* flow_coarse, int k, float* M)
+{
+    const Layer* l;
+    CHK(layer_of(c, k, &l));
+    if (!R0 || !R1 || !M) return fail(MAV_ERR_ARG, "mav_stage_update_matrices_from: NULL argument");
+    if (flow_coarse && k + 1 >= (int)c->layers.size())
+        return fail(MAV_ERR_ARG, "mav_stage_update_matrices_from: layer %d is the top layer, it has no coarser flow", k);
+    const size_t n = (size_t)l->w * l->h;
+    const int pw = flow_coarse ? c->layers[k + 1].w : 0, ph = flow_coarse ? c->layers[k + 1].h : 0;
+    const size_t nc = (size_t)pw * ph;
+    const float mul = (float)(1. / c->fb.pyr_scale);
+    DevBuf d0, d1, df, dm;
+    CHK(d0.upload(c, R0, 5 * n * sizeof(float))); CHK(d1.upload(c, R1, 5 * n * sizeof(float)));
+    if (flow_coarse) CHK(df.upload(c, flow_coarse, 2 * nc * sizeof(float)));
+    CHK(dm.alloc(c, 5 * n * sizeof(float)));
+    launch_update_matrices(c->stream, d0.as<float>(), d1.as<float>(), 5 * n, flow_coarse ? df.as<float>() : nullptr, 2 * nc, pw, ph, mul, 1,
+                           l->w, l->h, dm.as<float>(), 5 * n);
+    CHK(check_launch("update_matrices"));
+    CHK(download(c, M, dm.p, 5 * n * sizeof(float)));
+    return mav_sync(c);
+}
+// The initial flow of layer k from a frame-size field as snapshot_initial_flow computes it for the top layer: INTER_AREA resize,
+// then times pyr_scale^k (the repeated product).
+extern "C" int mav_stage_initial_flow(mav_ctx* c, const float* flow0, int k, float* out)
+{
+    const Layer* l;
+    CHK(layer_of(c, k, &l));
+    if (!flow0 || !out) return fail(MAV_ERR_ARG, "mav_stage_initial_flow: NULL argument");
+    const size_t n = (size_t)l->w * l->h;
+    double scale = 1;
+    for (int i = 0; i < k; i++) scale *= c->fb.pyr_scale;
+    DevBuf di, dout;
+    CHK(di.upload(c, flow0, 2 * c->n0 * sizeof(float))); CHK(dout.alloc(c, 2 * n * sizeof(float)));
+    launch_area_resize_flow(c->stream, di.as<float>(), 2 * c->n0, c->W, c->H, dout.as<float>(), 2 * n, l->w, l->h, 1, scale);
+    CHK(check_launch("area_resize_flow"));
+    CHK(download(c, out, dout.p, 2 * n * sizeof(float)));
+    return mav_sync(c);
+}
 extern "C" int mav_stage_blur_iter(mav_ctx* c, const float* R0, const float* R1, const float* M, int k, int update, float* flow, float* M_out)
 {
     const Layer* l;

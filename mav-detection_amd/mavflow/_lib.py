@@ -54,7 +54,7 @@ EXPORTS = [
     "mav_upload_gather", "mav_download_async", "mav_marker_create", "mav_marker_record", "mav_marker_wait", "mav_marker_destroy",
     "mav_tpr_fpr_counts_dev", "mav_bgr2gray_dev", "mav_png_unfilter", "mav_comm_count",
     "mav_marker_query", "mav_frame_step_dev", "mav_frame_step_post", "mav_frame_step_wait", "mav_worker_drain",
-    "mav_farneback_init", "mav_farneback_init_dev",
+    "mav_farneback_init", "mav_farneback_init_dev", "mav_stage_update_matrices_from", "mav_stage_initial_flow",
 ]
 
 OPTFLOW_USE_INITIAL_FLOW = 4                    # FbParams.flags bit (cv2.OPTFLOW_USE_INITIAL_FLOW): see Context.farneback(initial_flow=)
@@ -191,6 +191,8 @@ def load(path: str | None = None) -> C.CDLL:
     lib.mav_stage_polyexp.argtypes = [vp, vp, C.c_int, vp]
     lib.mav_stage_update_matrices.argtypes = [vp, vp, vp, vp, C.c_int, vp]
     lib.mav_stage_blur_iter.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp]
+    lib.mav_stage_update_matrices_from.argtypes = [vp, vp, vp, vp, C.c_int, vp]
+    lib.mav_stage_initial_flow.argtypes = [vp, vp, C.c_int, vp]
     _lib = lib
     return lib
 
@@ -884,6 +886,25 @@ class Context:
         M = np.empty((5, h, w), np.float32)
         check(self.lib.mav_stage_update_matrices(self.h, _ptr(R0), _ptr(R1), _ptr(flow), k, _ptr(M)))
         return M
+
+    def stage_update_matrices_from(self, R0, R1, flow_coarse, k):
+        """The initial M of layer k from the coarser layer's flow (upsampled inside the kernel), or from zero when flow_coarse is None."""
+        w, h, _, _ = self.layer_dims(k)
+        R0 = _arr(R0, np.float32, (5, h, w), "R0"); R1 = _arr(R1, np.float32, (5, h, w), "R1")
+        if flow_coarse is not None:
+            pw, ph = (self.layer_dims(k + 1)[:2] if k + 1 < self.num_layers() else np.shape(flow_coarse)[1::-1])
+            flow_coarse = _arr(flow_coarse, np.float32, (ph, pw, 2), "flow_coarse")
+        M = np.empty((5, h, w), np.float32)
+        check(self.lib.mav_stage_update_matrices_from(self.h, _ptr(R0), _ptr(R1), _ptr(flow_coarse), k, _ptr(M)))
+        return M
+
+    def stage_initial_flow(self, flow0, k):
+        """Layer k's initial flow from a frame-size field: resize(INTER_AREA), times pyr_scale^k."""
+        flow0 = _arr(flow0, np.float32, (self.H, self.W, 2), "flow0")
+        w, h, _, _ = self.layer_dims(k)
+        out = np.empty((h, w, 2), np.float32)
+        check(self.lib.mav_stage_initial_flow(self.h, _ptr(flow0), k, _ptr(out)))
+        return out
 
     def stage_blur_iter(self, R0, R1, M, k, update=True):
         w, h, _, _ = self.layer_dims(k)

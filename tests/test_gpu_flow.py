@@ -50,7 +50,10 @@ def test_blur_resize(ctx640, fb_oracle, pair640, k):
     w, h, sigma, ks = ctx640.layer_dims(k)
     got = ctx640.stage_blur_resize(pair640[0], k)
     exp = fb_oracle.blur_resize(pair640[0], w, h, ks, sigma)
-    np.testing.assert_allclose(got, exp, rtol=0, atol=2e-4)
+    if k == 0:                                                  # 3x3 binomial: every product exact in float32, bit for bit
+        assert np.array_equal(got, exp), int((got != exp).sum())
+    else:                                                       # tests/test_gpu_stages.py BLUR_ATOL (measured 7.6e-5 over its matrix)
+        np.testing.assert_allclose(got, exp, rtol=0, atol=1.6e-4)
 
 
 @pytest.mark.parametrize("size,levels", [((640, 480), 1), ((1920, 1080), 1), ((1000, 562), 1), ((333, 227), 1), ((3840, 2160), 5)])
@@ -79,7 +82,7 @@ def test_polyexp(ctx640, fb_oracle, pair640, k):
     I = fb_oracle.blur_resize(pair640[0], w, h, ks, sigma)
     got = ctx640.stage_polyexp(I, k)
     exp = soa(fb_oracle.polyexp(I))
-    np.testing.assert_allclose(got, exp, rtol=0, atol=2e-4)      # |R| ~ 1e1, f32 sums of ~300 terms of size ~1e2
+    np.testing.assert_allclose(got, exp, rtol=0, atol=1.1e-4)    # tests/test_gpu_stages.py POLY_ATOL (measured 2.8e-5 over its matrix)
 
 
 def _stage_inputs(ctx, fb_oracle, pair, k):
@@ -108,7 +111,7 @@ def test_blur_iter(ctx640, fb_oracle, pair640, k, update):
     eflow, eM = fb_oracle.blur_iter(R[0], R[1], flow, M, 12, update)
     gflow, gM = ctx640.stage_blur_iter(soa(R[0]), soa(R[1]), soa(M), k, update)
     e = epe(gflow, eflow)
-    assert e.max() < 2e-3, e.max()
+    assert e.max() < 5.4e-4, e.max()        # tests/test_gpu_stages.py SWEEP_MAX (measured 1.37e-4 over its matrix, 5.2e-6 at 640x480)
     if update:
         scale = np.abs(eM).max()
         np.testing.assert_allclose(gM, soa(eM), rtol=2e-3, atol=2e-5 * scale)
