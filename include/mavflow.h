@@ -226,6 +226,28 @@ int mav_detect(mav_ctx*, const float* flow, const uint32_t* samples, const doubl
                const uint8_t* frame0, const uint8_t* sky, int batch, const mav_foe_params*, const mav_thr_params*, double* phi,
                uint8_t* mask_fixed, uint8_t* mask_dyn, mav_result* results);
 
+/* The three images Processor.run_detection writes per frame [src/processor.py:364-374], (batch, H, W, 3) u8 BGR each, as the reference
+ * hands them to cv2.imwrite:
+ *   img_result  im_helpers.to_rgb(255 * estimate_fixed): 255 where the fixed-threshold mask is set, 0 elsewhere
+ *   img_flow    im_helpers.get_flow_vis(derotated flow) = flow_vis.flow_to_color(..., convert_to_bgr=True)
+ *   img_phi     im_helpers.apply_colormap(to_rgb(phi, max_value=180.0)) = cv2.applyColorMap(..., COLORMAP_JET)
+ * flow / omega / dt / frame0 / sky as in mav_detect, foe (batch, 2) the pairs' FoE (read only for img_result / img_phi), thresholds as
+ * in mav_detect (NULL = defaults).  Derotation, the fixed mask and phi are recomputed per pixel in the exact arithmetic of the detection
+ * path (no single-precision screen); a frame-0 pair is rendered in float32 as numpy does.  Any image may be NULL (not rendered).
+ * JET entries 200..255 are restated from OpenCV's Jet definition: no image the reference wrote pins them. */
+int mav_render(mav_ctx*, const float* flow, const double* foe, const double* omega, const double* dt, const uint8_t* frame0,
+               const uint8_t* sky, int batch, const mav_thr_params*, uint8_t* img_result, uint8_t* img_flow, uint8_t* img_phi);
+/* The same images from what the most recent mav_detect / mav_process_batch(_dev) / mav_detect_dev / frame step on this context left
+ * resident (flow, derotation constants, FoE, sky, thresholds): the flow is not moved again.  Host outputs, synchronous.  MAV_ERR_STATE
+ * when no such call precedes, its batch differs, or a later call may have overwritten its flow (any other host-pointer call, a flow
+ * call).  Device buffers of a _dev call must still hold what that call read. */
+int mav_last_render(mav_ctx*, int batch, uint8_t* img_result, uint8_t* img_flow, uint8_t* img_phi);
+/* im_helpers.get_flow_vis [src/im_helpers.py:103-112] alone: flow_to_color(flow, convert_to_bgr=True) of (batch, H, W, 2) fields,
+ * float64 (f64 != 0) or float32 (f64 == 0: numpy's float32 arithmetic), -> (batch, H, W, 3) u8 BGR. */
+int mav_flow_to_color(mav_ctx*, const void* flow, int f64, int batch, uint8_t* img);
+/* cv2.applyColorMap(gray, COLORMAP_JET) of n u8 values -> n BGR triples (a 3-channel image: mav_bgr2gray first, as OpenCV does). */
+int mav_colormap_jet(mav_ctx*, const uint8_t* gray, size_t n, uint8_t* bgr);
+
 /* ---- device-pointer entry points (asynchronous on the context's stream) -------------------------------- */
 int mav_farneback_dev(mav_ctx*, const uint8_t* prev, const uint8_t* next, int batch, float* flow);
 /* mav_farneback_init on device pointers (enqueue only).  flow_init == flow is allowed; ranges that overlap without being the same
@@ -244,6 +266,9 @@ int mav_detect_dev(mav_ctx*, const float* flow, const uint32_t* samples, const d
 /* cv2.cvtColor(COLOR_BGR2GRAY) [src/farneback.py:21,74] on device pointers: (batch, H, W, 3) u8 -> (batch, H, W) u8. */
 int mav_bgr2gray_dev(mav_ctx*, const uint8_t* bgr, int batch, uint8_t* gray);
 const float* mav_last_flow_dev(const mav_ctx*);
+/* mav_render on device pointers (enqueue only); the images are written once, nothing else is. */
+int mav_render_dev(mav_ctx*, const float* flow, const double* foe, const double* omega, const double* dt, const uint8_t* frame0,
+                   const uint8_t* sky, int batch, const mav_thr_params*, uint8_t* img_result, uint8_t* img_flow, uint8_t* img_phi);
 /* im_helpers.calculate_tpr_fpr [src/im_helpers.py:244-252, called at src/processor.py:350-351] for device-resident masks against a
  * device-resident ground truth, counts left on the device (4 x int64 per pair: positives, negatives, true / false positives): the
  * validation tail of a batch as one more launch behind mav_process_batch_dev / mav_detect_dev.  gt_images = batch: one ground-truth

@@ -828,3 +828,257 @@ void launch_make_derot(hipStream_t st, const double* omega, const double* dt, co
 {
     hipLaunchKernelGGL(k_make_derot, dim3((B + 63) / 64), dim3(64), 0, st, omega, dt, frame0, B, W, H, out);
 }
+
+// ------------------------------------------------------------------------------------------------------------
+// Result images of Processor.run_detection (src/processor.py:364-374 of the reference), (H, W, 3) u8 BGR each:
+//   result   im_helpers.to_rgb(255 * estimate_fixed): 255 where the fixed-threshold mask is set, 0 elsewhere (an empty mask goes
+//            through 0 / 0 = NaN -> astype(uint8), which is 0 as well)
+//   flow     flow_vis.flow_to_color(derotated flow, convert_to_bgr=True)
+//   phi      cv2.applyColorMap(to_rgb(phi, max_value=180.0), COLORMAP_JET)
+// The render kernel recomputes derotation, mask and phi per pixel with the very device functions k_phi_mask's exact path uses
+// (derot_apply, phi_pixel_exact, phi_pixel_f32): no single-precision screen, so mask and phi are the exact ones.  flow_to_color
+// normalises by the pair's max |flow|, which k_render_radmax reduces first (max is order independent: the reduction is exact).
+
+// cv2.COLORMAP_JET, BGR.  Entries 0..199 are pinned by the reference's media/colorbar.png (tests/golden/colorbar.png); entries
+// 200..255 are NOT pinned by any image the reference wrote: they continue the ramps of OpenCV's Jet (red holds 255 to 223 and falls
+// by 4 per entry to 128, green falls by 4 per entry to 0 at 223, blue stays 0) and agree with the mirror image of entries 0..55.
+struct JetLut { uint8_t bgr[256][3]; };
+__constant__ JetLut c_jet = {{
+    {128, 0, 0}, {132, 0, 0}, {136, 0, 0}, {140, 0, 0}, {144, 0, 0}, {148, 0, 0}, {152, 0, 0}, {156, 0, 0},
+    {160, 0, 0}, {164, 0, 0}, {168, 0, 0}, {172, 0, 0}, {176, 0, 0}, {180, 0, 0}, {184, 0, 0}, {188, 0, 0},
+    {192, 0, 0}, {196, 0, 0}, {200, 0, 0}, {204, 0, 0}, {208, 0, 0}, {212, 0, 0}, {216, 0, 0}, {220, 0, 0},
+    {224, 0, 0}, {228, 0, 0}, {232, 0, 0}, {236, 0, 0}, {240, 0, 0}, {244, 0, 0}, {248, 0, 0}, {252, 0, 0},
+    {255, 0, 0}, {255, 4, 0}, {255, 8, 0}, {255, 12, 0}, {255, 16, 0}, {255, 20, 0}, {255, 24, 0}, {255, 28, 0},
+    {255, 32, 0}, {255, 36, 0}, {255, 40, 0}, {255, 44, 0}, {255, 48, 0}, {255, 52, 0}, {255, 56, 0}, {255, 60, 0},
+    {255, 64, 0}, {255, 68, 0}, {255, 72, 0}, {255, 76, 0}, {255, 80, 0}, {255, 84, 0}, {255, 88, 0}, {255, 92, 0},
+    {255, 96, 0}, {255, 100, 0}, {255, 104, 0}, {255, 108, 0}, {255, 112, 0}, {255, 116, 0}, {255, 120, 0}, {255, 124, 0},
+    {255, 128, 0}, {255, 132, 0}, {255, 136, 0}, {255, 140, 0}, {255, 144, 0}, {255, 148, 0}, {255, 152, 0}, {255, 156, 0},
+    {255, 160, 0}, {255, 164, 0}, {255, 168, 0}, {255, 172, 0}, {255, 176, 0}, {255, 180, 0}, {255, 184, 0}, {255, 188, 0},
+    {255, 192, 0}, {255, 196, 0}, {255, 200, 0}, {255, 204, 0}, {255, 208, 0}, {255, 212, 0}, {255, 216, 0}, {255, 220, 0},
+    {255, 224, 0}, {255, 228, 0}, {255, 232, 0}, {255, 236, 0}, {255, 240, 0}, {255, 244, 0}, {255, 248, 0}, {255, 252, 0},
+    {254, 255, 2}, {250, 255, 6}, {246, 255, 10}, {242, 255, 14}, {238, 255, 18}, {234, 255, 22}, {230, 255, 26}, {226, 255, 30},
+    {222, 255, 34}, {218, 255, 38}, {214, 255, 42}, {210, 255, 46}, {206, 255, 50}, {202, 255, 54}, {198, 255, 58}, {194, 255, 62},
+    {190, 255, 66}, {186, 255, 70}, {182, 255, 74}, {178, 255, 78}, {174, 255, 82}, {170, 255, 86}, {166, 255, 90}, {162, 255, 94},
+    {158, 255, 98}, {154, 255, 102}, {150, 255, 106}, {146, 255, 110}, {142, 255, 114}, {138, 255, 118}, {134, 255, 122}, {130, 255, 126},
+    {126, 255, 130}, {122, 255, 134}, {118, 255, 138}, {114, 255, 142}, {110, 255, 146}, {106, 255, 150}, {102, 255, 154}, {98, 255, 158},
+    {94, 255, 162}, {90, 255, 166}, {86, 255, 170}, {82, 255, 174}, {78, 255, 178}, {74, 255, 182}, {70, 255, 186}, {66, 255, 190},
+    {62, 255, 194}, {58, 255, 198}, {54, 255, 202}, {50, 255, 206}, {46, 255, 210}, {42, 255, 214}, {38, 255, 218}, {34, 255, 222},
+    {30, 255, 226}, {26, 255, 230}, {22, 255, 234}, {18, 255, 238}, {14, 255, 242}, {10, 255, 246}, {6, 255, 250}, {1, 255, 254},
+    {0, 252, 255}, {0, 248, 255}, {0, 244, 255}, {0, 240, 255}, {0, 236, 255}, {0, 232, 255}, {0, 228, 255}, {0, 224, 255},
+    {0, 220, 255}, {0, 216, 255}, {0, 212, 255}, {0, 208, 255}, {0, 204, 255}, {0, 200, 255}, {0, 196, 255}, {0, 192, 255},
+    {0, 188, 255}, {0, 184, 255}, {0, 180, 255}, {0, 176, 255}, {0, 172, 255}, {0, 168, 255}, {0, 164, 255}, {0, 160, 255},
+    {0, 156, 255}, {0, 152, 255}, {0, 148, 255}, {0, 144, 255}, {0, 140, 255}, {0, 136, 255}, {0, 132, 255}, {0, 128, 255},
+    {0, 124, 255}, {0, 120, 255}, {0, 116, 255}, {0, 112, 255}, {0, 108, 255}, {0, 104, 255}, {0, 100, 255}, {0, 96, 255},
+    {0, 92, 255}, {0, 88, 255}, {0, 84, 255}, {0, 80, 255}, {0, 76, 255}, {0, 72, 255}, {0, 68, 255}, {0, 64, 255},
+    {0, 60, 255}, {0, 56, 255}, {0, 52, 255}, {0, 48, 255}, {0, 44, 255}, {0, 40, 255}, {0, 36, 255}, {0, 32, 255},
+    {0, 28, 255}, {0, 24, 255}, {0, 20, 255}, {0, 16, 255}, {0, 12, 255}, {0, 8, 255}, {0, 4, 255}, {0, 0, 255},
+    {0, 0, 252}, {0, 0, 248}, {0, 0, 244}, {0, 0, 240}, {0, 0, 236}, {0, 0, 232}, {0, 0, 228}, {0, 0, 224},
+    {0, 0, 220}, {0, 0, 216}, {0, 0, 212}, {0, 0, 208}, {0, 0, 204}, {0, 0, 200}, {0, 0, 196}, {0, 0, 192},
+    {0, 0, 188}, {0, 0, 184}, {0, 0, 180}, {0, 0, 176}, {0, 0, 172}, {0, 0, 168}, {0, 0, 164}, {0, 0, 160},
+    {0, 0, 156}, {0, 0, 152}, {0, 0, 148}, {0, 0, 144}, {0, 0, 140}, {0, 0, 136}, {0, 0, 132}, {0, 0, 128},
+}};
+
+// flow_vis.make_colorwheel: the 55-entry Middlebury wheel (RY 15, YG 6, GC 4, CB 11, BM 13, MR 6), RGB, entries floor(255 * j / n).
+struct Wheel { uint8_t rgb[55][3]; };
+static constexpr Wheel make_wheel()
+{
+    Wheel w{};
+    const int n[6] = {15, 6, 4, 11, 13, 6};
+    int k = 0;
+    for (int s = 0; s < 6; s++)
+        for (int j = 0; j < n[s]; j++, k++) {
+            const int up = 255 * j / n[s], down = 255 - up;    // floor(255 * j / n): the quotient is exact or not an integer
+            int r = 0, g = 0, b = 0;
+            switch (s) {
+            case 0: r = 255; g = up; break;      // RY
+            case 1: r = down; g = 255; break;    // YG
+            case 2: g = 255; b = up; break;      // GC
+            case 3: g = down; b = 255; break;    // CB
+            case 4: b = 255; r = up; break;      // BM
+            default: b = down; r = 255; break;   // MR
+            }
+            w.rgb[k][0] = (uint8_t)r; w.rgb[k][1] = (uint8_t)g; w.rgb[k][2] = (uint8_t)b;
+        }
+    return w;
+}
+__constant__ Wheel c_wheel = make_wheel();
+
+// floor(255 * col) -> u8 as numpy's astype(uint8) of a value in [0, 255]; NaN -> 0 (x86-64).  Clamped: never wraps.
+static __device__ __forceinline__ unsigned u8_of(double x)
+{
+    return x >= 1.0 ? (x < 255.0 ? (unsigned)x : 255u) : 0u;
+}
+
+// One pixel of flow_uv_to_colors after the normalisation.  fk is the wheel coordinate (a + 1) / 2 * 54 and rad the normalised
+// magnitude in the field's own type; from `f = fk - k0` on numpy works in double for both field types (float32 - int32 -> float64).
+static __device__ __forceinline__ unsigned wheel_bgr(double fk, double rad)
+{
+    const int k0 = (fk >= 0.0 && fk < 55.0) ? (int)floor(fk) : 0;   // a is in [-1, 1]: fk in [0, 54]; NaN -> entry 0, in bounds
+    const int k1 = k0 + 1 == 55 ? 0 : k0 + 1;
+    const double f = fk - (double)k0;
+    unsigned out = 0u;
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const double col0 = (double)c_wheel.rgb[k0][i] / 255.0, col1 = (double)c_wheel.rgb[k1][i] / 255.0;
+        double col = (1.0 - f) * col0 + f * col1;
+        col = rad <= 1.0 ? 1.0 - rad * (1.0 - col) : col * 0.75;
+        out |= u8_of(floor(255.0 * col)) << (8 * (2 - i));           // channel 2 - i: BGR
+    }
+    return out;
+}
+
+// The pair's max |flow| as the reference forms it (flow_to_color: rad = sqrt(u^2 + v^2), rad_max = max(rad)): double for a derotated
+// (or promoted) pair, float32 for a frame-0 pair, stored widened.  radmax[b] zeroed by the caller; |flow| >= 0, so bit order is value order.
+template <typename FlowT>
+__global__ __launch_bounds__(256) void k_render_radmax(const FlowT* __restrict__ flow, const DerotParams* __restrict__ derot, int W, int H,
+                                                       unsigned long long* __restrict__ radmax)
+{
+    const int b = blockIdx.y;
+    const size_t npx = (size_t)W * H;
+    const FlowT* fl = flow + b * npx * 2;
+    const DerotParams* dp = derot ? derot + b : nullptr;
+    const bool f32 = std::is_same<FlowT, float>::value && dp && dp->mode == MAV_PAIR_FRAME0;
+    double m = 0.0;
+    for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < npx; p += (size_t)gridDim.x * 256) {
+        const int y = (int)(p / W), x = (int)(p - (size_t)y * W);
+        const auto rv = flow_raw(fl, W, y, x);
+        double r;
+        if (f32) {
+            const float u = (float)rv.x, v = (float)rv.y;
+            r = (double)sqrtf(u * u + v * v);
+        } else {
+            double u, v;
+            derot_apply(rv, dp, W, H, y, x, &u, &v);
+            r = sqrt(u * u + v * v);
+        }
+        m = r > m ? r : m;
+    }
+    unsigned long long bits = (unsigned long long)__double_as_longlong(m);
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(bits, o);
+        bits = other > bits ? other : bits;
+    }
+    if ((threadIdx.x & 63) == 0 && bits) atomicMax(&radmax[b], bits);
+}
+
+// Four consecutive pixels of the batch per thread (the flattened (B, H, W) index): each image gets three dword stores.
+template <typename FlowT>
+__global__ __launch_bounds__(256) void k_render(const FlowT* __restrict__ flow, const DerotParams* __restrict__ derot,
+                                                const double* __restrict__ foe, const uint8_t* __restrict__ sky, int W, int H, int B,
+                                                mav_thr_params thr, const unsigned long long* __restrict__ radmax,
+                                                uint8_t* __restrict__ o_res, uint8_t* __restrict__ o_flow, uint8_t* __restrict__ o_phi)
+{
+    const size_t npx = (size_t)W * H, total = npx * B;
+    const size_t p0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (p0 >= total) return;
+    const bool need_phi = o_res || o_phi;
+    unsigned px_res[4], px_flow[4], px_phi[4];                 // 0x00BBGGRR-style packed BGR of each pixel (byte 0 = B)
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        px_res[j] = px_flow[j] = px_phi[j] = 0u;
+        const size_t p = p0 + j;
+        if (p >= total) continue;
+        const int b = (int)(p / npx);
+        const size_t q = p - (size_t)b * npx;
+        const int y = (int)(q / W), x = (int)(q - (size_t)y * W);
+        const DerotParams* dp = derot ? derot + b : nullptr;
+        const bool f32 = std::is_same<FlowT, float>::value && dp && dp->mode == MAV_PAIR_FRAME0;
+        const auto rv = flow_raw(flow + b * npx * 2, W, y, x);
+        double u = 0.0, v = 0.0;
+        if (!f32) derot_apply(rv, dp, W, H, y, x, &u, &v);
+        if (need_phi) {
+            const int notsky = !sky || sky[p] == 0;
+            const double d2x = (double)x - foe[2 * b], d2y = (double)y - foe[2 * b + 1];
+            unsigned g;
+            PhiVerdict pv;
+            if (f32) {
+                pv = phi_pixel_f32((float)rv.x, (float)rv.y, (float)d2x, (float)d2y, notsky, (float)thr.fixed_deg, (float)thr.fixed_min_mag,
+                                   (float)thr.dyn_min_mag, (float)thr.dyn_a, (float)thr.dyn_b, (float)thr.dyn_c);
+                // to_int: np.abs(phi) * 255 / 180.0 in float32 (numpy 2 keeps the Python scalars weak), np.around = half to even
+                const float s = fabsf((float)pv.ph) * 255.0f / 180.0f;
+                g = u8_of((double)rintf(s));
+            } else {
+                pv = phi_pixel_exact(u, v, d2x, d2y, notsky, thr.fixed_deg, thr.fixed_min_mag, thr.dyn_min_mag, thr.dyn_a, thr.dyn_b,
+                                     thr.dyn_c);
+                g = u8_of(rint(fabs(pv.ph) * 255.0 / 180.0));
+            }
+            px_res[j] = (pv.bits & 1u) ? 0xFFFFFFu : 0u;
+            px_phi[j] = (unsigned)c_jet.bgr[g][0] | ((unsigned)c_jet.bgr[g][1] << 8) | ((unsigned)c_jet.bgr[g][2] << 16);
+        }
+        if (o_flow) {
+            const double rmax = __longlong_as_double((long long)radmax[b]);
+            if (f32) {
+                // flow_to_color on a float32 array: every step up to the wheel coordinate in float32, np.pi rounded to float32
+                const float rm = (float)rmax + 1e-5f;
+                const float fu = (float)rv.x / rm, fv = (float)rv.y / rm;
+                const float rad = sqrtf(fu * fu + fv * fv);
+                const float a = (float)atan2(-(double)fv, -(double)fu) / 3.14159274f;
+                const float fk = (a + 1.0f) / 2.0f * 54.0f;
+                px_flow[j] = wheel_bgr((double)fk, (double)rad);
+            } else {
+                const double rm = rmax + 1e-5;
+                const double nu = u / rm, nv = v / rm;
+                const double rad = sqrt(nu * nu + nv * nv);
+                const double a = atan2(-nv, -nu) / 3.141592653589793;
+                px_flow[j] = wheel_bgr((a + 1.0) / 2.0 * 54.0, rad);
+            }
+        }
+    }
+    // 4 pixels x 3 bytes = 3 dwords at byte offset 3 * p0 (a multiple of 12); a partial tail or a misaligned image goes byte by byte
+    uint8_t* outs[3] = {o_res, o_flow, o_phi};
+    const unsigned* pxs[3] = {px_res, px_flow, px_phi};
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        uint8_t* o = outs[k];
+        if (!o) continue;
+        const unsigned* px = pxs[k];
+        if (p0 + 4 <= total && ((uintptr_t)o & 3) == 0) {
+            uint32_t* d = (uint32_t*)(o + 3 * p0);
+            d[0] = px[0] | (px[1] << 24);
+            d[1] = (px[1] >> 8) | (px[2] << 16);
+            d[2] = (px[2] >> 16) | (px[3] << 8);
+        } else {
+            for (int j = 0; j < 4 && p0 + j < total; j++)
+                for (int c = 0; c < 3; c++) o[3 * (p0 + j) + c] = (uint8_t)(px[j] >> (8 * c));
+        }
+    }
+}
+
+template <typename FlowT>
+static void launch_render_t(hipStream_t st, const FlowT* flow, const DerotParams* derot, const double* foe, const uint8_t* sky, int B,
+                            int W, int H, mav_thr_params thr, unsigned long long* radmax, uint8_t* res, uint8_t* flow_img, uint8_t* phi_img)
+{
+    if (!res && !flow_img && !phi_img) return;
+    const size_t npx = (size_t)W * H;
+    if (flow_img) {
+        (void)hipMemsetAsync(radmax, 0, sizeof(unsigned long long) * B, st);
+        const int gx = (int)std::min<size_t>((npx + 1023) / 1024, 256);   // up to 4 pixels per thread
+        hipLaunchKernelGGL(k_render_radmax<FlowT>, dim3(gx, B), dim3(256), 0, st, flow, derot, W, H, radmax);
+    }
+    const size_t threads = (npx * B + 3) / 4;
+    hipLaunchKernelGGL(k_render<FlowT>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, flow, derot, foe, sky, W, H, B, thr,
+                       radmax, res, flow_img, phi_img);
+}
+void launch_render_f32(hipStream_t st, const float* flow, const DerotParams* derot, const double* foe, const uint8_t* sky, int B, int W,
+                       int H, mav_thr_params thr, unsigned long long* radmax, uint8_t* res, uint8_t* flow_img, uint8_t* phi_img)
+{
+    launch_render_t<float>(st, flow, derot, foe, sky, B, W, H, thr, radmax, res, flow_img, phi_img);
+}
+void launch_render_f64(hipStream_t st, const double* flow, int B, int W, int H, unsigned long long* radmax, uint8_t* flow_img)
+{
+    launch_render_t<double>(st, flow, nullptr, nullptr, nullptr, B, W, H, mav_thr_params{}, radmax, nullptr, flow_img, nullptr);
+}
+
+// cv2.applyColorMap(img, COLORMAP_JET) of a single-channel u8 image: the LUT.  (A 3-channel image goes through BGR2GRAY first, as
+// in OpenCV; mav_bgr2gray.)
+__global__ __launch_bounds__(256) void k_colormap_jet(const uint8_t* __restrict__ gray, size_t n, uint8_t* __restrict__ bgr)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const unsigned g = gray[i];
+    bgr[3 * i] = c_jet.bgr[g][0]; bgr[3 * i + 1] = c_jet.bgr[g][1]; bgr[3 * i + 2] = c_jet.bgr[g][2];
+}
+void launch_colormap_jet(hipStream_t st, const uint8_t* gray, size_t n, uint8_t* bgr)
+{
+    if (n) hipLaunchKernelGGL(k_colormap_jet, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, gray, n, bgr);
+}

@@ -370,6 +370,15 @@ struct mav_ctx {
     unsigned long long* u64_scratch = nullptr;  // [max_batch*8]
     int* i32_scratch = nullptr;                 // [max_batch]
     DerotParams* derot_dev = nullptr;
+    // result images (mav_render*): per-pair max |flow| and the render calls' own derotation constants (lazily, max_batch), and what the
+    // latest mav_detect_dev left resident for mav_last_render (batch 0: nothing)
+    unsigned long long* render_max = nullptr;
+    DerotParams* render_derot = nullptr;
+    struct LastRender {
+        const float* flow = nullptr; const DerotParams* derot = nullptr; const double* foe = nullptr; const uint8_t* sky = nullptr;
+        mav_thr_params thr{};
+        int batch = 0;
+    } last_render;
     // staging buffers of the host-pointer entry points: slot i of a call re-uses the block slot i of the previous call
     // left behind (grow-only), so the staged path performs no hipMalloc / hipFree once warm
     struct Block { void* p = nullptr; size_t cap = 0; };
@@ -547,7 +556,7 @@ extern "C" int mav_destroy(mav_ctx* c)
         for (void* b : wb) if (b) hipFree(b);
     }
     void* bufs[] = {c->flow_ws, c->init_snap, c->foe_sc.cand, c->foe_sc.count, c->foe_sc.best_key, c->foe_sc.done, c->foe_dev, c->box_acc, c->u64_scratch,
-                    c->i32_scratch, c->derot_dev, c->pyr_ws, c->sat};
+                    c->i32_scratch, c->derot_dev, c->pyr_ws, c->sat, c->render_max, c->render_derot};
     for (void* b : bufs) if (b) hipFree(b);
     for (auto& blk : c->scratch) if (blk.p) hipFree(blk.p);
     for (auto& r : c->prof) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
@@ -1688,6 +1697,7 @@ static int farneback_run(mav_ctx* c, const uint8_t* prev, const uint8_t* next, i
         }
     }
     c->last_flow = flow;
+    c->last_render.batch = 0;        // the flow a previous detection call read may have been overwritten
     return MAV_OK;
 }
 extern "C" int mav_farneback_dev(mav_ctx* c, const uint8_t* prev, const uint8_t* next, int batch, float* flow)
@@ -1757,13 +1767,14 @@ static int ensure_foe_scratch(mav_ctx* c, int N)
 // Per-pair derotation constants.  Device pointers stay on the device (a tiny kernel packs them: no host round trip, the
 // stream never drains); host pointers are packed here and copied.
 static int upload_derot(mav_ctx* c, const double* omega, const double* dt, const uint8_t* frame0, int batch, bool host_ptrs,
-                        const DerotParams** out)
+                        const DerotParams** out, DerotParams* dst = nullptr /* c->derot_dev */)
 {
     *out = nullptr;
     if (!omega && !frame0) return MAV_OK;
+    if (!dst) dst = c->derot_dev;
     if (!host_ptrs) {
-        launch_make_derot(c->stream, omega, dt, frame0, batch, c->W, c->H, c->derot_dev);
-        *out = c->derot_dev;
+        launch_make_derot(c->stream, omega, dt, frame0, batch, c->W, c->H, dst);
+        *out = dst;
         return MAV_OK;
     }
     std::vector<DerotParams> dp(batch);
@@ -1774,9 +1785,9 @@ static int upload_derot(mav_ctx* c, const double* omega, const double* dt, const
         dp[b].sy = c->H * d / 2;
         dp[b].mode = (frame0 && frame0[b]) ? MAV_PAIR_FRAME0 : (omega ? MAV_PAIR_DEROTATE : MAV_PAIR_PROMOTE);
     }
-    HIPCHK(hipMemcpyAsync(c->derot_dev, dp.data(), sizeof(DerotParams) * batch, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(dst, dp.data(), sizeof(DerotParams) * batch, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));  // dp is a local vector
-    *out = c->derot_dev;
+    *out = dst;
     return MAV_OK;
 }
 
@@ -1834,8 +1845,12 @@ extern "C" int mav_detect_dev(mav_ctx* c, const float* flow, const uint32_t* sam
     CHK(upload_derot(c, omega, dt, frame0, batch, false, &derot));
     mav_thr_params t;
     if (tp) t = *tp; else mav_thr_defaults(&t);
-    return detect_dev(c, flow, nullptr, derot, samples, sky, batch, fp, &t, nullptr, phi, mask_fixed, mask_dyn, nullptr, nullptr,
-                      results, nullptr);
+    CHK(detect_dev(c, flow, nullptr, derot, samples, sky, batch, fp, &t, nullptr, phi, mask_fixed, mask_dyn, nullptr, nullptr,
+                   results, nullptr));
+    // what mav_last_render reads: the FoE went to the context's own buffer (detect_dev with foe_out == NULL)
+    c->last_render.flow = flow; c->last_render.derot = derot; c->last_render.foe = c->foe_dev; c->last_render.sky = sky;
+    c->last_render.thr = t; c->last_render.batch = batch;
+    return MAV_OK;
 }
 
 extern "C" int mav_process_batch_dev(mav_ctx* c, const uint8_t* prev, const uint8_t* next, const uint32_t* samples,
@@ -2084,6 +2099,7 @@ static int check_batch(mav_ctx* c, int batch, const char* fn)
     HIPCHK(hipSetDevice(c->device));
     c->scratch_next = 0;              // a new host-pointer call: its staging buffers start again at block 0
     c->last_mf = c->last_md = nullptr; c->last_mask_batch = 0;     // ... and may overwrite the previous call's masks
+    c->last_render.batch = 0;                                       // ... and its flow, FoE and sky
     return MAV_OK;
 }
 
@@ -2560,6 +2576,128 @@ extern "C" int mav_tpr_fpr_counts_dev(mav_ctx* c, const uint8_t* gt, int gt_imag
     return check_launch("tpr_fpr");
 }
 
+// ---- result images (include/mavflow.h: mav_render) ----------------------------------------------------------------------------
+static int ensure_render(mav_ctx* c)
+{
+    if (!c->render_max) HIPCHK(hipMalloc(&c->render_max, sizeof(unsigned long long) * c->max_batch));
+    if (!c->render_derot) HIPCHK(hipMalloc(&c->render_derot, sizeof(DerotParams) * c->max_batch));
+    return MAV_OK;
+}
+static int render_enqueue(mav_ctx* c, const float* flow, const DerotParams* derot, const double* foe, const uint8_t* sky, int batch,
+                          const mav_thr_params& t, uint8_t* img_result, uint8_t* img_flow, uint8_t* img_phi)
+{
+    CHK(ensure_render(c));
+    ProfScope ps(c, K_MISC);
+    launch_render_f32(c->stream, flow, derot, foe, sky, batch, c->W, c->H, t, c->render_max, img_result, img_flow, img_phi);
+    return check_launch("render");
+}
+
+extern "C" int mav_render_dev(mav_ctx* c, const float* flow, const double* foe, const double* omega, const double* dt, const uint8_t* frame0,
+                              const uint8_t* sky, int batch, const mav_thr_params* tp, uint8_t* img_result, uint8_t* img_flow, uint8_t* img_phi)
+{
+    if (!c || !flow || ((img_result || img_phi) && !foe)) return fail(MAV_ERR_ARG, "mav_render_dev: NULL argument");
+    if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "mav_render_dev: batch %d outside [1, %d]", batch, c->max_batch);
+    HIPCHK(hipSetDevice(c->device));
+    CHK(ensure_render(c));
+    const DerotParams* derot = nullptr;
+    CHK(upload_derot(c, omega, dt, frame0, batch, false, &derot, c->render_derot));
+    mav_thr_params t;
+    if (tp) t = *tp; else mav_thr_defaults(&t);
+    return render_enqueue(c, flow, derot, foe, sky, batch, t, img_result, img_flow, img_phi);
+}
+
+// device images -> host, each of (batch, H, W, 3) bytes
+static int download_images(mav_ctx* c, int batch, uint8_t* const dev[3], uint8_t* const host[3])
+{
+    for (int k = 0; k < 3; k++)
+        if (host[k]) CHK(download(c, host[k], dev[k], c->n0 * 3 * batch));
+    return mav_sync(c);
+}
+
+extern "C" int mav_render(mav_ctx* c, const float* flow, const double* foe, const double* omega, const double* dt, const uint8_t* frame0,
+                          const uint8_t* sky, int batch, const mav_thr_params* tp, uint8_t* img_result, uint8_t* img_flow, uint8_t* img_phi)
+{
+    CHK(check_batch(c, batch, "mav_render"));
+    if (!flow || ((img_result || img_phi) && !foe)) return fail(MAV_ERR_ARG, "mav_render: NULL argument");
+    if (!img_result && !img_flow && !img_phi) return MAV_OK;
+    const size_t n = c->n0 * batch;
+    DevBuf df, dfoe, dsky, dom, ddt, df0, dimg[3];
+    CHK(df.upload(c, flow, n * 2 * sizeof(float)));
+    if (foe) CHK(dfoe.upload(c, foe, sizeof(double) * 2 * batch));
+    if (sky) CHK(dsky.upload(c, sky, n));
+    if (omega) CHK(dom.upload(c, omega, sizeof(double) * 3 * batch));
+    if (omega && dt) CHK(ddt.upload(c, dt, sizeof(double) * batch));
+    if (frame0) CHK(df0.upload(c, frame0, batch));
+    uint8_t* const host[3] = {img_result, img_flow, img_phi};
+    uint8_t* dev[3] = {nullptr, nullptr, nullptr};
+    for (int k = 0; k < 3; k++)
+        if (host[k]) { CHK(dimg[k].alloc(c, n * 3)); dev[k] = dimg[k].as<uint8_t>(); }
+    CHK(mav_render_dev(c, df.as<float>(), dfoe.as<double>(), dom.as<double>(), ddt.as<double>(), df0.as<uint8_t>(), dsky.as<uint8_t>(),
+                       batch, tp, dev[0], dev[1], dev[2]));
+    return download_images(c, batch, dev, host);
+}
+
+extern "C" int mav_last_render(mav_ctx* c, int batch, uint8_t* img_result, uint8_t* img_flow, uint8_t* img_phi)
+{
+    if (!c) return fail(MAV_ERR_ARG, "mav_last_render: NULL context");
+    if (!c->last_render.batch || batch != c->last_render.batch)
+        return fail(MAV_ERR_STATE, "mav_last_render: no flow of a %d-pair detection call is resident", batch);
+    HIPCHK(hipSetDevice(c->device));
+    if (!img_result && !img_flow && !img_phi) return MAV_OK;
+    // the images go into the NEXT free staging blocks: the detection call's own blocks (flow, sky of a host-pointer call) stay untouched
+    const size_t mark = c->scratch_next;
+    DevBuf dimg[3];
+    uint8_t* const host[3] = {img_result, img_flow, img_phi};
+    uint8_t* dev[3] = {nullptr, nullptr, nullptr};
+    for (int k = 0; k < 3; k++)
+        if (host[k]) { CHK(dimg[k].alloc(c, c->n0 * 3 * batch)); dev[k] = dimg[k].as<uint8_t>(); }
+    c->scratch_next = mark;          // synchronous: the blocks are free again on return
+    const mav_ctx::LastRender& r = c->last_render;
+    CHK(render_enqueue(c, r.flow, r.derot, r.foe, r.sky, batch, r.thr, dev[0], dev[1], dev[2]));
+    return download_images(c, batch, dev, host);
+}
+
+extern "C" int mav_flow_to_color(mav_ctx* c, const void* flow, int f64, int batch, uint8_t* img)
+{
+    CHK(check_batch(c, batch, "mav_flow_to_color"));
+    if (!flow || !img) return fail(MAV_ERR_ARG, "mav_flow_to_color: NULL argument");
+    const size_t n = c->n0 * batch;
+    DevBuf df, dimg;
+    CHK(df.upload(c, flow, n * 2 * (f64 ? sizeof(double) : sizeof(float))));
+    CHK(dimg.alloc(c, n * 3));
+    CHK(ensure_render(c));
+    const DerotParams* derot = nullptr;
+    if (!f64) {                      // a float32 field: numpy's float32 arithmetic, i.e. the frame-0 form
+        std::vector<uint8_t> all(batch, 1);
+        CHK(upload_derot(c, nullptr, nullptr, all.data(), batch, true, &derot, c->render_derot));
+    }
+    {
+        ProfScope ps(c, K_MISC);
+        if (f64) launch_render_f64(c->stream, df.as<double>(), batch, c->W, c->H, c->render_max, dimg.as<uint8_t>());
+        else launch_render_f32(c->stream, df.as<float>(), derot, nullptr, nullptr, batch, c->W, c->H, mav_thr_params{}, c->render_max, nullptr,
+                               dimg.as<uint8_t>(), nullptr);
+    }
+    CHK(check_launch("render"));
+    CHK(download(c, img, dimg.p, n * 3));
+    return mav_sync(c);
+}
+
+extern "C" int mav_colormap_jet(mav_ctx* c, const uint8_t* gray, size_t n, uint8_t* bgr)
+{
+    if (!c || !gray || !bgr) return fail(MAV_ERR_ARG, "mav_colormap_jet: NULL argument");
+    HIPCHK(hipSetDevice(c->device));
+    c->scratch_next = 0;
+    c->last_mf = c->last_md = nullptr; c->last_mask_batch = 0;
+    c->last_render.batch = 0;
+    if (!n) return MAV_OK;
+    DevBuf dg, dout;
+    CHK(dg.upload(c, gray, n)); CHK(dout.alloc(c, n * 3));
+    launch_colormap_jet(c->stream, dg.as<uint8_t>(), n, dout.as<uint8_t>());
+    CHK(check_launch("colormap"));
+    CHK(download(c, bgr, dout.p, n * 3));
+    return mav_sync(c);
+}
+
 extern "C" int mav_process_batch(mav_ctx* c, const uint8_t* prev, const uint8_t* next, const uint32_t* samples, const double* omega,
                                  const double* dt, const uint8_t* frame0, const uint8_t* sky, int batch, const mav_foe_params* fp,
                                  const mav_thr_params* tp, float* flow, double* phi, uint8_t* mask_fixed, uint8_t* mask_dyn,
@@ -2586,6 +2724,7 @@ static int layer_of(mav_ctx* c, int k, const Layer** l)
     HIPCHK(hipSetDevice(c->device));
     c->scratch_next = 0;
     c->last_mf = c->last_md = nullptr; c->last_mask_batch = 0;
+    c->last_render.batch = 0;
     *l = &c->layers[k];
     return MAV_OK;
 }

@@ -133,6 +133,13 @@ void launch_bgr2gray(hipStream_t st, const uint8_t* bgr, size_t n, uint8_t* gray
 void launch_ransac_only(hipStream_t st, FoeScratch s, int M, int N, double dist2_thr, double* foe);
 void launch_make_derot(hipStream_t st, const double* omega /*null: no rotation*/, const double* dt, const uint8_t* frame0, int B,
                        int W, int H, DerotParams* out);
+// Result images (BGR u8, (B, H, W, 3) each, any may be null): the fixed-mask image, flow_to_color of the derotated flow and the JET
+// colour map of phi.  radmax: [B] scratch.  foe / thr are read only for the result and phi images.
+void launch_render_f32(hipStream_t st, const float* flow, const DerotParams* derot, const double* foe, const uint8_t* sky, int B, int W,
+                       int H, mav_thr_params thr, unsigned long long* radmax, uint8_t* res, uint8_t* flow_img, uint8_t* phi_img);
+// flow_to_color of an already derotated float64 field
+void launch_render_f64(hipStream_t st, const double* flow, int B, int W, int H, unsigned long long* radmax, uint8_t* flow_img);
+void launch_colormap_jet(hipStream_t st, const uint8_t* gray, size_t n, uint8_t* bgr);
 
 // ---- window search (kernels_window.hip, compiled with -ffp-contract=off) -----------------------------------------
 #define MAV_PYR_MAX 32

@@ -55,6 +55,7 @@ EXPORTS = [
     "mav_tpr_fpr_counts_dev", "mav_bgr2gray_dev", "mav_png_unfilter", "mav_comm_count",
     "mav_marker_query", "mav_frame_step_dev", "mav_frame_step_post", "mav_frame_step_wait", "mav_worker_drain",
     "mav_farneback_init", "mav_farneback_init_dev", "mav_stage_update_matrices_from", "mav_stage_initial_flow",
+    "mav_render", "mav_render_dev", "mav_last_render", "mav_flow_to_color", "mav_colormap_jet",
 ]
 
 OPTFLOW_USE_INITIAL_FLOW = 4                    # FbParams.flags bit (cv2.OPTFLOW_USE_INITIAL_FLOW): see Context.farneback(initial_flow=)
@@ -193,6 +194,13 @@ def load(path: str | None = None) -> C.CDLL:
     lib.mav_stage_blur_iter.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp]
     lib.mav_stage_update_matrices_from.argtypes = [vp, vp, vp, vp, C.c_int, vp]
     lib.mav_stage_initial_flow.argtypes = [vp, vp, C.c_int, vp]
+    # ctx, flow, foe, omega, dt, frame0, sky, batch, thr params, img_result, img_flow, img_phi
+    rn = [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(ThrParams), vp, vp, vp]
+    lib.mav_render.argtypes = rn
+    lib.mav_render_dev.argtypes = rn
+    lib.mav_last_render.argtypes = [vp, C.c_int, vp, vp, vp]
+    lib.mav_flow_to_color.argtypes = [vp, vp, C.c_int, C.c_int, vp]
+    lib.mav_colormap_jet.argtypes = [vp, vp, C.c_size_t, vp]
     _lib = lib
     return lib
 
@@ -743,6 +751,69 @@ class Context:
                                   C.byref(fp), C.byref(tp), _ptr(phi), _ptr(mf), _ptr(md), _ptr(res)))
         return dict(phi=phi, mask_fixed=None if mf is None else mf.view(np.bool_),
                     mask_dyn=None if md is None else md.view(np.bool_), results=res)
+
+    # -- result images (processor.py:364-374) ---------------------------------------------------------------
+    IMAGES = ("result", "flow", "phi")
+
+    def _image_outs(self, B, images):
+        bad = set(images) - set(self.IMAGES)
+        if bad:
+            raise ValueError(f"unknown image(s) {sorted(bad)}; choose from {self.IMAGES}")
+        return {k: (np.empty((B, self.H, self.W, 3), np.uint8) if k in images else None) for k in self.IMAGES}
+
+    def render(self, flow, foe, omega=None, dt=None, sky=None, thr_params=None, frame0=None, images=IMAGES):
+        """The three images Processor.run_detection writes per frame, as (B, H, W, 3) u8 BGR arrays: "result" (to_rgb of
+        255 * the fixed mask), "flow" (get_flow_vis of the derotated flow), "phi" (apply_colormap of to_rgb(phi, 180)).
+        flow: float32 (B, H, W, 2) as for detect(); foe (B, 2); omega / dt / sky / frame0 as for detect()."""
+        flow = np.asarray(flow)
+        if flow.dtype != np.float32:
+            raise TypeError(f"render() takes a float32 flow field, got {flow.dtype}")
+        flow = flow[None] if flow.ndim == 3 else flow
+        B = flow.shape[0]
+        flow = _arr(flow, np.float32, (B, self.H, self.W, 2), "flow")
+        foe = _arr(np.asarray(foe, np.float64).reshape(B, 2), np.float64)
+        omega = None if omega is None else _arr(np.asarray(omega, np.float64).reshape(B, 3), np.float64)
+        dt = None if dt is None else _arr(np.asarray(dt, np.float64).reshape(B), np.float64)
+        frame0 = None if frame0 is None else _arr(np.asarray(frame0).reshape(B).astype(np.uint8), np.uint8)
+        sky = None if sky is None else _arr(np.asarray(sky).reshape(B, self.H, self.W).astype(np.uint8), np.uint8)
+        tp = thr_params or thr_defaults()
+        out = self._image_outs(B, images)
+        check(self.lib.mav_render(self.h, _ptr(flow), _ptr(foe), _ptr(omega), _ptr(dt), _ptr(frame0), _ptr(sky), B, C.byref(tp),
+                                  _ptr(out["result"]), _ptr(out["flow"]), _ptr(out["phi"])))
+        return {k: v for k, v in out.items() if v is not None}
+
+    def render_dev(self, flow_ptr, foe_ptr, batch, result_ptr=None, flow_img_ptr=None, phi_img_ptr=None, omega_ptr=None, dt_ptr=None,
+                   frame0_ptr=None, sky_ptr=None, thr_params=None):
+        """mav_render_dev: enqueue only, device pointers."""
+        tp = thr_params or thr_defaults()
+        check(self.lib.mav_render_dev(self.h, flow_ptr, foe_ptr, omega_ptr, dt_ptr, frame0_ptr, sky_ptr, batch, C.byref(tp), result_ptr,
+                                      flow_img_ptr, phi_img_ptr))
+
+    def render_last(self, batch: int, images=IMAGES):
+        """render() of what the most recent detect / process_batch(_dev) / frame step left on the device (flow, FoE, sky,
+        derotation, thresholds): nothing but the images crosses PCIe."""
+        out = self._image_outs(batch, images)
+        check(self.lib.mav_last_render(self.h, int(batch), _ptr(out["result"]), _ptr(out["flow"]), _ptr(out["phi"])))
+        return {k: v for k, v in out.items() if v is not None}
+
+    def flow_to_color(self, flow) -> np.ndarray:
+        """flow_vis.flow_to_color(flow, convert_to_bgr=True) of (B, H, W, 2) fields in their own float type -> (B, H, W, 3) u8."""
+        flow = np.asarray(flow)
+        f64 = flow.dtype != np.float32
+        ft = np.float64 if f64 else np.float32
+        flow = flow[None] if flow.ndim == 3 else flow
+        B = flow.shape[0]
+        flow = _arr(flow, ft, (B, self.H, self.W, 2), "flow")
+        out = np.empty((B, self.H, self.W, 3), np.uint8)
+        check(self.lib.mav_flow_to_color(self.h, _ptr(flow), int(f64), B, _ptr(out)))
+        return out
+
+    def colormap_jet(self, gray) -> np.ndarray:
+        """cv2.applyColorMap(gray, COLORMAP_JET) of a u8 array of any shape -> shape + (3,) BGR."""
+        g = np.ascontiguousarray(gray, np.uint8)
+        out = np.empty(g.shape + (3,), np.uint8)
+        check(self.lib.mav_colormap_jet(self.h, _ptr(g), g.size, _ptr(out)))
+        return out
 
     # -- device-pointer path (bench, multi-GPU) --------------------------------------------------------------
     def process_batch_dev(self, prev_ptr, next_ptr, samples_ptr, batch, results_ptr, flow_ptr=None, omega_ptr=None,

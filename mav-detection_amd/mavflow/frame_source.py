@@ -134,6 +134,46 @@ def imread(path: str) -> Optional[np.ndarray]:
     return np.ascontiguousarray(px[..., 2::-1])      # RGB(A) -> BGR
 
 
+def _chunk(kind: bytes, body: bytes) -> bytes:
+    return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xFFFFFFFF)
+
+
+def encode_png(img: np.ndarray, level: int = 1) -> bytes:
+    """PNG bytes of an 8-bit image as cv2.imencode('.png', img) lays it out: (H, W) or (H, W, 1) gray, (H, W, 3) BGR -> RGB file,
+    (H, W, 4) BGRA -> RGBA file.  Filter type 0 on every row, zlib level `level` (OpenCV's default PNG compression is 1)."""
+    a = np.asarray(img)
+    if a.dtype != np.uint8:
+        raise ValueError(f"imwrite: only 8-bit images are written here, got {a.dtype}")
+    if a.ndim == 3 and a.shape[2] == 1:
+        a = a[:, :, 0]
+    if a.ndim == 2:
+        ctype, rows = 0, a
+    elif a.ndim == 3 and a.shape[2] in (3, 4):
+        ctype = 2 if a.shape[2] == 3 else 6
+        rows = a[:, :, [2, 1, 0] if ctype == 2 else [2, 1, 0, 3]]
+    else:
+        raise ValueError(f"imwrite: expected (H, W), (H, W, 1), (H, W, 3) or (H, W, 4), got {a.shape}")
+    H, W = rows.shape[:2]
+    if H < 1 or W < 1:
+        raise ValueError(f"imwrite: empty image {a.shape}")
+    raw = np.empty((H, 1 + rows[0].size), np.uint8)
+    raw[:, 0] = 0
+    raw[:, 1:] = rows.reshape(H, -1)
+    return (PNG_MAGIC + _chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, ctype, 0, 0, 0))
+            + _chunk(b"IDAT", zlib.compress(raw.tobytes(), level)) + _chunk(b"IEND", b""))
+
+
+def imwrite(path: str, img: np.ndarray) -> bool:
+    """cv2.imwrite(path, img) for PNG files of 8-bit gray or BGR(A) images (the reference writes its result images with it,
+    processor.py:364-374).  Returns True; ValueError for another extension or image type, OSError when the file cannot be written."""
+    if not path.lower().endswith(".png"):
+        raise ValueError(f"imwrite: only .png files are written here, got {path!r}")
+    data = encode_png(img)
+    with open(path, "wb") as f:
+        f.write(data)
+    return True
+
+
 class PngSequenceCapture:
     """cv2.VideoCapture('.../image_%05d.png') for a PNG sequence: frames are the files pattern % k for k = start, start + 1, ... until
     one is missing (OpenCV's image-sequence capture starts at the first existing index among 0 and 1; here: `start`, default the same

@@ -1,6 +1,6 @@
 """The image helpers the hot path names (/root/reference/src/im_helpers.py), on libmavflow where they touch whole frames:
 get_magnitude (:150-159), get_simple_bounding_box (:55-84), calculate_tpr_fpr (:244-252), to_int / to_rgb (:162-200),
-pyramid / sliding_window (:12-52; the levels above 0 are imutils.resize -> cv2.resize(INTER_AREA) restated on the device,
+get_flow_vis / apply_colormap (:103-135, the result images' renderers), pyramid / sliding_window (:12-52; the levels above 0 are imutils.resize -> cv2.resize(INTER_AREA) restated on the device,
 parity unpinned at the cv2 boundary -- DESIGN.md section 2)."""
 from __future__ import annotations
 
@@ -11,6 +11,7 @@ import numpy as np
 from . import _lib
 from .utils import Rectangle
 
+COLORMAP_JET = 2                     # cv2.COLORMAP_JET
 _CTX_CACHE_SIZES = 12                # frame sizes kept at one time (a 1080p image pyramid at scale 1.5 has 9 levels)
 _ctx_cache = {}                      # (W, H) -> Context, least recently used first (dicts keep insertion order)
 
@@ -114,6 +115,40 @@ def to_rgb(img: np.ndarray, max_value: float = None) -> np.ndarray:
     """Grayscale -> 3 equal u8 channels (what cv2.cvtColor(GRAY2RGB) of the normalised image yields)."""
     g = to_int(img, np.uint8, True, max_value=max_value)
     return np.repeat(g[..., None], 3, axis=2)
+
+
+def get_flow_vis(frame: np.ndarray, magnitude_factor: float = 1.0) -> np.ndarray:
+    """flow_vis.flow_to_color(frame, convert_to_bgr=True) (im_helpers.py:103-112): (H, W, 2) flow -> (H, W, 3) u8 BGR, rendered on the
+    device in the field's own float type (a float32 field in float32 as numpy does, anything else in float64).  magnitude_factor is
+    unused, as in the reference."""
+    f = np.asarray(frame)
+    if f.ndim != 3 or f.shape[2] != 2:
+        raise ValueError(f"get_flow_vis: expected an (H, W, 2) flow field, got {f.shape}")
+    if f.dtype != np.float32:
+        f = f.astype(np.float64)
+    return _ctx(f.shape[1], f.shape[0]).flow_to_color(f)[0]
+
+
+def apply_colormap(img: np.ndarray, max_value: float = None, colormap: int = COLORMAP_JET) -> np.ndarray:
+    """cv2.applyColorMap(img, COLORMAP_JET) (im_helpers.py:115-135) on the device: a float image goes through to_int(normalize=True,
+    max_value) first, a 3-channel u8 image through BGR2GRAY (OpenCV's own first step; the identity on equal channels), then the
+    JET table.  JET entries 200..255 are restated from OpenCV's Jet definition, not pinned by an image the reference wrote.
+    The reference's max_value branch overwrites img[0, 0] of a u8 input before restoring the output pixel there: the returned
+    image is the same, the caller's array is left alone here."""
+    if colormap != COLORMAP_JET:
+        raise ValueError(f"apply_colormap: only COLORMAP_JET ({COLORMAP_JET}) is implemented, got {colormap}")
+    a = np.asarray(img)
+    if a.dtype in (np.float32, np.float64):
+        a = to_int(a, np.uint8, True, max_value=max_value)
+    if a.dtype != np.uint8:
+        raise ValueError(f"apply_colormap: expected a u8 or float image, got {a.dtype}")
+    if a.ndim == 3 and a.shape[2] == 3:
+        a = _ctx(a.shape[1], a.shape[0]).bgr2gray(a)[0]
+    elif a.ndim == 3 and a.shape[2] == 1:
+        a = a[:, :, 0]
+    elif a.ndim != 2:
+        raise ValueError(f"apply_colormap: expected (H, W), (H, W, 1) or (H, W, 3), got {a.shape}")
+    return _ctx(a.shape[1], a.shape[0]).colormap_jet(a)
 
 
 def pyramid(image: np.ndarray, scale: float = 1.5, minSize: Tuple[int, int] = (30, 30)) -> Iterator[np.ndarray]:

@@ -12,16 +12,21 @@ out.  Flow, derotated flow and both masks stay on the device as DeviceArray hand
 taken on the device against a ground truth that is uploaded once when the dataset declares it constant.
 
 Each loop writes `{results_path}/image_{i:05d}.json` per frame as the reference's write() does (:83-84) when the dataset (or the
-constructor) names a results_path.  Video / PNG output and the homography branch are outside the hot path and are not reproduced."""
+constructor) names a results_path.  With an explicit images_path each loop also writes the three result images of :364-374 per frame,
+`{images_path}/result-images|derotated|phi/image_{i:05d}.png`, rendered on the device (mav_last_render: one launch behind the
+frame's step, the flow is not moved again) and PNG-encoded by a pool of at most 16 threads off the loop's thread; every file is
+complete when the loop returns.  The video (processed.mp4) and the homography branch are not reproduced."""
 from __future__ import annotations
 
 import json
 import os
+from collections import deque
+from concurrent.futures import ThreadPoolExecutor
 from typing import Dict, Optional, Tuple
 
 import numpy as np
 
-from . import _lib, im_helpers, pipeline, synth, utils
+from . import _lib, frame_source, im_helpers, pipeline, synth, utils
 from .detector import Detector
 from .focus_of_expansion import FocusOfExpansion
 from .frame_result import FrameResult
@@ -154,8 +159,14 @@ class SyntheticDataset:
             self._ctxs, self._stage = [], None
 
 
+# the result images of processor.py:364-374: Context.render's names -> the reference's directories
+IMAGE_DIRS = {"result": "result-images", "flow": "derotated", "phi": "phi"}
+PNG_WORKERS = 16                     # encoder threads at most
+PNG_BACKLOG = 4 * PNG_WORKERS        # files queued before the loop waits for the oldest
+
+
 class Processor:
-    def __init__(self, config: RunConfig, results_path: Optional[str] = None) -> None:
+    def __init__(self, config: RunConfig, results_path: Optional[str] = None, images_path: Optional[str] = None) -> None:
         self.config = config
         self.logger = config.logger
         self.sequence = config.sequence
@@ -180,6 +191,10 @@ class Processor:
         self._stale_pipes = []                           # pipelines over a subset of the lanes now in use, until their last frames are collected
         self._seg_val = None
         self._center = None
+        # the result images (processor.py:364-374): only an explicit images_path turns them on
+        self.images_path = images_path
+        self._png_pool = None
+        self._png_jobs = deque()
 
     def is_active(self) -> bool:
         return self.frame_index < self.dataset.N - 1 and not self.is_exiting
@@ -272,6 +287,25 @@ class Processor:
             os.makedirs(self.results_path, exist_ok=True)
             with open(f"{self.results_path}/image_{i:05d}.json", "w") as f:
                 f.write(json.dumps(utils.get_json(r), indent=4, sort_keys=True))
+
+    # -- result images (processor.py:364-374) ----------------------------------------------------------------------------------------
+    def _write_images(self, ids, imgs) -> None:
+        """Queue the PNG files of frames `ids`; imgs: Context.render's dict of (n, H, W, 3) BGR arrays."""
+        if self._png_pool is None:
+            for d in IMAGE_DIRS.values():
+                os.makedirs(os.path.join(self.images_path, d), exist_ok=True)
+            self._png_pool = ThreadPoolExecutor(max_workers=min(PNG_WORKERS, os.cpu_count() or 1), thread_name_prefix="png")
+        for k, i in enumerate(ids):
+            for name, d in IMAGE_DIRS.items():
+                while len(self._png_jobs) >= PNG_BACKLOG:
+                    self._png_jobs.popleft().result()
+                path = os.path.join(self.images_path, d, f"image_{i:05d}.png")
+                self._png_jobs.append(self._png_pool.submit(frame_source.imwrite, path, imgs[name][k]))
+
+    def _flush_images(self) -> None:
+        """Every queued file written (raises what an encoder raised)."""
+        while self._png_jobs:
+            self._png_jobs.popleft().result()
 
     def _segmentation(self, i: int):
         """Channel 0 of the dataset's segmentation image, contiguous, with the coordinates of its drone pixels (> 127) and the
@@ -379,9 +413,11 @@ class Processor:
             omega, dt = self._rates(i) if i >= 1 else (np.zeros(3), 1.0)
             ticket = pipe.submit(rand1, flow=self.flow_uv, omega=omega, dt=dt, frame0=[i < 1], **kw)
             pending.append((pipe, i, ticket, sky))
-            finish(pipe.depth)
+            # with images the frame is finished at once: its images are rendered from what its step left on the lane's context
+            finish(0 if self.images_path is not None else pipe.depth)
             self.frame_index += 1
         finish(0)
+        self._flush_images()
         return self.detection_results
 
     def _finish_frame(self, pipe, i: int, ticket, sky) -> None:
@@ -391,6 +427,8 @@ class Processor:
         r = self._fill_result(i, (float(rec["foe"][0]), float(rec["foe"][1])), sky, out["counts_fixed"][0], out["counts_dyn"][0])
         self.detection_boxes[i] = utils.Rectangle.from_box(rec["box"])
         self._store(i, r)
+        if self.images_path is not None:
+            self._write_images([i], pipe.pipes[ticket[0]].ctx.render_last(1))
 
     def run_detection_staged(self) -> Dict[int, FrameResult]:
         """The same loop through the reference-named calls one by one (Detector.derotate, get_FOE_dense, the masks): every call
@@ -403,6 +441,7 @@ class Processor:
             if self.flow_uv is None:
                 raise ValueError("Could not load flow field.")
             self._staged_frame(i)
+        self._flush_images()
         return self.detection_results
 
     def _staged_frame(self, i: int) -> None:
@@ -416,6 +455,12 @@ class Processor:
         self.estimate_fixed, self.total_mask = fixed, total
         r = self._fill_result(i, foe, sky, estimate_fixed=fixed, total_mask=total)
         self._store(i, r)
+        if self.images_path is not None:                      # the reference-named helpers, as processor.py:364-374 reads
+            phi = self.focus_of_expansion.get_phi(self.flow_uv_derotated, foe)
+            with np.errstate(invalid="ignore"):               # an empty mask: 0 / 0 -> 0, as in the reference
+                result = im_helpers.to_rgb(255 * np.asarray(fixed))
+            self._write_images([i], dict(result=result[None], flow=im_helpers.get_flow_vis(self.flow_uv_derotated)[None],
+                                         phi=im_helpers.apply_colormap(im_helpers.to_rgb(phi, max_value=180.0))[None]))
         self.frame_index += 1
 
     def run_detection_batched(self, batch: int = 8) -> Dict[int, FrameResult]:
@@ -446,11 +491,12 @@ class Processor:
             ticket = pipe.submit(samples, prev=[p[0] for p in pairs], nxt=[p[1] for p in pairs], omega=omega, dt=dts,
                                  frame0=[i < 1 for i in ids], **kw)
             pending.append((ids, ticket, sky_scores))
-            while len(pending) > pipe.depth:
+            while len(pending) > (0 if self.images_path is not None else pipe.depth):     # images: rendered behind the batch's step
                 self._finish_batch(pipe, *pending.popleft())
         while pending:
             self._finish_batch(pipe, *pending.popleft())
         self.frame_index = self.dataset.N - 1
+        self._flush_images()
         return self.detection_results
 
     def _finish_batch(self, pipe, ids, ticket, sky_scores) -> None:
@@ -460,9 +506,15 @@ class Processor:
             r = self._fill_result(i, (float(rec["foe"][0]), float(rec["foe"][1])), sky_scores[k], out["counts_fixed"][k], out["counts_dyn"][k])
             self.detection_boxes[i] = utils.Rectangle.from_box(rec["box"])
             self._store(i, r)
+        if self.images_path is not None:
+            self._write_images(ids, pipe.pipes[ticket[0]].ctx.render_last(len(ids)))
         self.estimate_fixed, self.total_mask = out["mask_fixed"][-1], out["mask_dyn"][-1]     # of the last frame, as the loop leaves them
 
     def release(self) -> None:
+        self._flush_images()
+        if self._png_pool is not None:
+            self._png_pool.shutdown()
+            self._png_pool = None
         self._close_pipes()
         for c in self._ctxs:
             c.close()
