@@ -346,7 +346,9 @@ int mav_marker_destroy(mav_ctx* /* may be NULL */, void* marker);
  *   6. out_dev[0 : out_bytes] -> out_host (page-locked), then `record_done`.
  * The library copies the struct and the pointer arrays it refers to (gather[i].src_host, wait_before, record_after_flow) when the
  * step is posted; the HOST BUFFERS themselves (frames, par_host, out_host) must stay valid and unchanged until the step's
- * `record_done` marker has fired (mav_frame_step_wait). */
+ * `record_done` marker has fired (mav_frame_step_wait).  A step that fails after part of it has been enqueued (a parameter refused
+ * inside the detection, after the gathers and Farneback) still records `record_after_flow` and `record_done`, behind the upload fence
+ * and what it did enqueue: waiting for its marker before giving the host buffers back stays enough. */
 typedef struct {
     const void* const* src_host; /* count host arrays of bytes_each bytes ... */
     int count;
@@ -401,11 +403,16 @@ int mav_frame_step_dev(mav_ctx*, const mav_frame_step*);
  * worker finish the step it is enqueueing and DROPS the ones still queued. */
 int mav_frame_step_post(mav_ctx*, const mav_frame_step*, uint64_t* ticket);
 /* Block until step `ticket` has been enqueued by the worker and, when `marker` is not NULL (the step's record_done), until that
- * marker has fired.  Returns the step's own return code (and sets mav_last_error to its message). */
+ * marker has fired -- for a failed step too.  Returns the step's own return code (and sets mav_last_error to its message).  The
+ * first wait for a failed ticket reports the failure, even when a drain has reported it already; after that wait no
+ * mav_worker_drain reports it again. */
 int mav_frame_step_wait(mav_ctx*, uint64_t ticket, void* marker);
-/* Block until the worker has enqueued every posted step (device work may still be running); returns the first failed step's code
- * since the last drain, MAV_OK if none.  No-op for a context that never posted. */
+/* Block until the worker has enqueued every posted step (device work may still be running); returns the code of the earliest failed
+ * step that neither an earlier drain nor mav_frame_step_wait has reported, MAV_OK if none.  No-op for a context that never posted. */
 int mav_worker_drain(mav_ctx*);
+/* Block until the worker has enqueued step `ticket` (and every step before it).  Unlike mav_frame_step_wait it delivers nothing: a
+ * failure of the step stays for its wait and for the next drain.  MAV_OK at once for ticket 0 or a context that never posted. */
+int mav_worker_wait_enqueued(mav_ctx*, uint64_t ticket);
 
 /* Frame decode in front of the path [src/datasets/dataset.py:57,223-230: cv2.VideoCapture over image_%05d.png; src/farneback.py:17-21]:
  * the un-filtering pass of a PNG image, host memory, no context.  raw = the inflated IDAT stream of a non-interlaced image (per row a

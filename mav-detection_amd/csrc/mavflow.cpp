@@ -1870,7 +1870,26 @@ extern "C" int mav_process_batch_dev(mav_ctx* c, const uint8_t* prev, const uint
 }
 
 // ---- one iteration of the reference's loop as one call (include/mavflow.h: mav_frame_step) ---------------------------------------
+static int frame_step_body(mav_ctx* c, const mav_frame_step* s, bool* started);
 static int frame_step_enqueue(mav_ctx* c, const mav_frame_step* s)
+{
+    bool started = false;
+    const int rc = frame_step_body(c, s, &started);
+    if (rc != MAV_OK && started) {
+        // the step failed part-way (a refused argument inside the detection, say) after some of it had been enqueued: its gathers may
+        // still be reading host sources the caller holds (MAV_GATHER_SOURCES_HELD).  Every marker of the step is recorded behind
+        // what was enqueued, so that whoever waits for them before giving those sources back still waits for the transfers.
+        const std::string err = g_err;
+        (void)mav_upload_fence(c);
+        for (int i = 0; i < s->n_record_after_flow; i++)
+            if (s->record_after_flow[i]) (void)hipEventRecord((hipEvent_t)s->record_after_flow[i], c->stream);
+        if (s->record_done) (void)hipEventRecord((hipEvent_t)s->record_done, c->stream);
+        (void)hipGetLastError();
+        g_err = err;
+    }
+    return rc;
+}
+static int frame_step_body(mav_ctx* c, const mav_frame_step* s, bool* started)
 {
     if (s->n < 1 || s->n > c->max_batch) return fail(MAV_ERR_ARG, "mav_frame_step: n %d outside [1, %d]", s->n, c->max_batch);
     if (s->n_gather < 0 || s->n_gather > MAV_STEP_MAX_GATHER) return fail(MAV_ERR_ARG, "mav_frame_step: n_gather %d outside [0, %d]", s->n_gather, (int)MAV_STEP_MAX_GATHER);
@@ -1881,11 +1900,12 @@ static int frame_step_enqueue(mav_ctx* c, const mav_frame_step* s)
     if (s->detect && s->gt_dev && (!s->mask_fixed_dev || !s->mask_dyn_dev)) return fail(MAV_ERR_ARG, "mav_frame_step: the counts need both masks");
     if (s->n_bgr && (!s->bgr_dev || !s->gray_dev)) return fail(MAV_ERR_ARG, "mav_frame_step: n_bgr without bgr_dev / gray_dev");
     if (s->out_bytes && (!s->out_host || !s->out_dev)) return fail(MAV_ERR_ARG, "mav_frame_step: out_bytes without out_host / out_dev");
+    if (s->par_bytes && (!s->par_host || !s->par_dev)) return fail(MAV_ERR_ARG, "mav_frame_step: par_bytes without par_host / par_dev");
     HIPCHK(hipSetDevice(c->device));
     for (int i = 0; i < s->n_wait_before; i++)
         if (s->wait_before[i]) HIPCHK(hipEventSynchronize((hipEvent_t)s->wait_before[i]));
+    *started = true;                             // from here on a failure may leave work of this step enqueued
     if (s->par_bytes) {
-        if (!s->par_host || !s->par_dev) return fail(MAV_ERR_ARG, "mav_frame_step: par_bytes without par_host / par_dev");
         CHK(mav_upload_async_unordered(c, s->par_dev, s->par_host, s->par_bytes));
     }
     for (int i = 0; i < s->n_gather; i++)
@@ -1939,9 +1959,10 @@ struct Worker {
     std::deque<StepJob> q;
     uint64_t posted = 0, done = 0;
     bool stop = false;
-    int first_rc = MAV_OK;                                     // first failure since the last drain
-    std::string first_err;
-    std::map<uint64_t, std::pair<int, std::string>> failed;   // by ticket, until somebody waits for it
+    // failures by ticket, until mav_frame_step_wait delivers them.  mav_worker_drain reports the earliest one after `drained` (the
+    // last ticket a drain has covered): a failure is reported once by a drain, and never by a drain once its own ticket has told it
+    std::map<uint64_t, std::pair<int, std::string>> failed;
+    uint64_t drained = 0;
 };
 static void worker_main(mav_ctx* c)
 {
@@ -1964,10 +1985,7 @@ static void worker_main(mav_ctx* c)
         lk.unlock();
         const int rc = frame_step_enqueue(c, &job.s);
         lk.lock();
-        if (rc != MAV_OK) {
-            w->failed[job.ticket] = {rc, g_err};
-            if (w->first_rc == MAV_OK) { w->first_rc = rc; w->first_err = g_err; }
-        }
+        if (rc != MAV_OK) w->failed[job.ticket] = {rc, g_err};
         w->done = job.ticket;
         w->cv_done.notify_all();
     }
@@ -2023,12 +2041,28 @@ extern "C" int mav_frame_step_wait(mav_ctx* c, uint64_t ticket, void* marker)
         auto it = w->failed.find(ticket);
         if (it != w->failed.end()) {
             const int rc = it->second.first;
-            g_err = it->second.second;
+            const std::string err = it->second.second;
             w->failed.erase(it);
+            lk.unlock();
+            // a step that failed part-way recorded its marker behind what it had enqueued (frame_step_enqueue): that has finished too
+            // when this returns; a step refused before it enqueued anything left the marker as it was
+            if (marker) (void)hipEventSynchronize((hipEvent_t)marker);
+            (void)hipGetLastError();
+            g_err = err;
             return rc;
         }
     }
     if (marker) HIPCHK(hipEventSynchronize((hipEvent_t)marker));
+    return MAV_OK;
+}
+extern "C" int mav_worker_wait_enqueued(mav_ctx* c, uint64_t ticket)
+{
+    if (!c) return fail(MAV_ERR_ARG, "mav_worker_wait_enqueued: NULL context");
+    Worker* w = c->worker;
+    if (!w || ticket == 0) return MAV_OK;
+    std::unique_lock<std::mutex> lk(w->m);
+    if (ticket > w->posted) return fail(MAV_ERR_ARG, "mav_worker_wait_enqueued: ticket %llu was never posted", (unsigned long long)ticket);
+    w->cv_done.wait(lk, [&] { return w->done >= ticket; });
     return MAV_OK;
 }
 extern "C" int mav_worker_drain(mav_ctx* c)
@@ -2038,10 +2072,11 @@ extern "C" int mav_worker_drain(mav_ctx* c)
     if (!w) return MAV_OK;
     std::unique_lock<std::mutex> lk(w->m);
     w->cv_done.wait(lk, [&] { return w->done == w->posted; });
-    const int rc = w->first_rc;
-    if (rc != MAV_OK) g_err = w->first_err;
-    w->first_rc = MAV_OK;
-    return rc;
+    auto it = w->failed.upper_bound(w->drained);
+    w->drained = w->posted;
+    if (it == w->failed.end()) return MAV_OK;
+    g_err = it->second.second;
+    return it->second.first;
 }
 
 // ---- host-pointer wrappers -----------------------------------------------------------------------------------

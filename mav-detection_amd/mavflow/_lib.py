@@ -53,7 +53,7 @@ EXPORTS = [
     "mav_membw_probe", "mav_runtime_info", "mav_upload_async_unordered", "mav_mem_info", "mav_profile_intervals",
     "mav_upload_gather", "mav_download_async", "mav_marker_create", "mav_marker_record", "mav_marker_wait", "mav_marker_destroy",
     "mav_tpr_fpr_counts_dev", "mav_bgr2gray_dev", "mav_png_unfilter", "mav_comm_count",
-    "mav_marker_query", "mav_frame_step_dev", "mav_frame_step_post", "mav_frame_step_wait", "mav_worker_drain",
+    "mav_marker_query", "mav_frame_step_dev", "mav_frame_step_post", "mav_frame_step_wait", "mav_worker_drain", "mav_worker_wait_enqueued",
     "mav_farneback_init", "mav_farneback_init_dev", "mav_stage_update_matrices_from", "mav_stage_initial_flow",
     "mav_render", "mav_render_dev", "mav_last_render", "mav_flow_to_color", "mav_colormap_jet",
 ]
@@ -173,6 +173,7 @@ def load(path: str | None = None) -> C.CDLL:
     lib.mav_frame_step_post.argtypes = [vp, C.POINTER(FrameStep), C.POINTER(C.c_uint64)]
     lib.mav_frame_step_wait.argtypes = [vp, C.c_uint64, vp]
     lib.mav_worker_drain.argtypes = [vp]
+    lib.mav_worker_wait_enqueued.argtypes = [vp, C.c_uint64]
     lib.mav_tpr_fpr_counts_dev.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp]
     lib.mav_bgr2gray_dev.argtypes = [vp, vp, C.c_int, vp]
     lib.mav_png_unfilter.argtypes = [vp, C.c_int, C.c_size_t, C.c_int, vp]

@@ -216,7 +216,7 @@ class _DeferredFlow:
     into ONE fused step (upload -> Farneback -> detection -> counts -> download: mav_frame_step) when the handle reaches it, and
     anybody else who looks at the handle first gets it computed on the spot (flush)."""
 
-    __slots__ = ("stage", "frames", "slots", "prev_slot", "next_slot", "k", "handle", "bgr")
+    __slots__ = ("stage", "frames", "slots", "prev_slot", "next_slot", "k", "handle", "bgr", "snap")
 
     def flush(self) -> None:
         self.stage._flush(self)
@@ -236,9 +236,16 @@ class FlowStage:
     The flow is DEFERRED (round 6): flow_of / flow_next decide where everything goes and hand out the handle, but enqueue nothing.
     When the handle reaches a DetectPipeline of the same context -- the reference's loop: get_flow_uv(i), then the detection on it --
     the frames' upload, Farneback and the detection travel as one mav_frame_step; when somebody reads the handle first, or the next
-    flow is asked for, the flow is computed on the spot.  Same launches, same results either way."""
+    flow is asked for, the flow is computed on the spot.  Same launches, same results either way.
+
+    The deferral does not show: flow_of / flow_next have READ the caller's frames when they return (a capture that decodes every
+    frame into one buffer may refill it at once).  A deferred flow's frames are copied into one of SNAP page-locked blocks the stage
+    owns; the fused step sends them from there (mav_upload_gather's MAV_GATHER_SOURCES_HELD: no staging copy), so the copy moves from
+    the library's staging threads to the caller.  A block is refilled only once the step that gathered it has read it -- SNAP calls
+    later, which a loop that collects its batches has long passed."""
 
     RING = 4
+    SNAP = 6
 
     def __init__(self, ctx: "_lib.Context", defer: bool = True):
         self.ctx, self.defer = ctx, bool(defer)
@@ -254,6 +261,10 @@ class FlowStage:
         self._have_prev = False                           # video mode (flow_next): slot of the previous frame
         self._prev_slot = 0
         self._open: Optional[_DeferredFlow] = None        # the one flow that has been handed out but not enqueued
+        self._snap = [None] * self.SNAP                   # page-locked copies of deferred frames (u8 blocks, grown on demand)
+        self._snap_fence = [_Fence(ctx) for _ in range(self.SNAP)]  # ... recorded by the fused step that gathered the block
+        self._snap_ticket = [0] * self.SNAP               # ... which was posted under this ticket (0: enqueued by the caller's thread)
+        self._snap_turn = 0
 
     def _check_frames(self, frames):
         ctx, arrs = self.ctx, []
@@ -263,6 +274,29 @@ class FlowStage:
                 raise ValueError(f"frame {k}: expected ({ctx.H}, {ctx.W}) or ({ctx.H}, {ctx.W}, 3) uint8, got {a.shape} {a.dtype}")
             arrs.append(a if a.flags.c_contiguous else np.ascontiguousarray(a))
         return arrs
+
+    def _snapshot(self, arrs):
+        """Copies of `arrs` in the next snapshot block -> (views of the block, its index).  Waits (only) for the step that gathered the
+        block SNAP calls ago to have read it."""
+        ctx, i = self.ctx, self._snap_turn
+        self._snap_turn = (i + 1) % self.SNAP
+        f = self._snap_fence[i]
+        if f.armed:
+            # the fence is recorded by the worker when it enqueues that step: wait for that (without taking a failure of the step
+            # away from the pipeline that collects it), then for the fence itself
+            check(ctx.lib.mav_worker_wait_enqueued(ctx._h, self._snap_ticket[i]))
+            check(ctx.lib.mav_marker_wait(None, f.m))
+            f.armed = False
+        need = sum(a.nbytes for a in arrs)
+        if self._snap[i] is None or self._snap[i].nbytes < need:
+            self._snap[i] = _lib._pinned.empty(ctx, (need,), np.uint8)
+        out, o = [], 0
+        for a in arrs:
+            v = self._snap[i][o:o + a.nbytes].reshape(a.shape)
+            np.copyto(v, a)
+            out.append(v)
+            o += a.nbytes
+        return out, i
 
     def _upload(self, arrs, slots) -> None:
         """arrs[k] (checked frames) -> gray slot slots[k] of the ring."""
@@ -302,9 +336,11 @@ class FlowStage:
         d.stage, d.frames, d.slots, d.prev_slot, d.next_slot, d.k = self, arrs, list(slots), prev_slot, next_slot, k
         d.bgr = bool(arrs) and arrs[0].ndim == 3
         d.handle = weakref.ref(h)
+        d.snap = None
         # one fused step takes gray frames into CONSECUTIVE slots, or BGR frames (at most the two the staging holds) likewise
         fusable = all(a.ndim == arrs[0].ndim for a in arrs) and all(slots[i + 1] == slots[i] + 1 for i in range(len(slots) - 1))
         if self.defer and fusable:
+            d.frames, d.snap = self._snapshot(arrs)       # the caller may overwrite its arrays once this call has returned
             h._deferred = d
             self._open = d
         else:
@@ -341,11 +377,12 @@ class FlowStage:
 
     def _take(self, d: _DeferredFlow, step: "_lib.FrameStep", keep: list):
         """Write the flow part of a fused step for the deferred flow `d` (called by DetectPipeline.submit, which posts the step): the
-        gather of its frames, BGR -> gray, Farneback, the markers.  Returns a callable to run once the step HAS been posted."""
+        gather of its frames (from the snapshot block), BGR -> gray, Farneback, the markers.  Returns a callable to run once the step
+        HAS been posted, with its ticket."""
         ctx, n0 = self.ctx, self.ctx.W * self.ctx.H
         nf = len(d.frames)
         waits = [self._gray_fence[sl] for sl in d.slots if self._gray_fence[sl].armed]
-        records = [self._gray_fence[sl] for sl in dict.fromkeys((d.prev_slot, d.next_slot))]
+        records = [self._gray_fence[sl] for sl in dict.fromkeys((d.prev_slot, d.next_slot))] + [self._snap_fence[d.snap]]
         g = step.gather[step.n_gather]
         srcs = _ptr_array(d.frames)
         keep.extend((srcs, d.frames))
@@ -372,11 +409,12 @@ class FlowStage:
         keep.append(ra)
         step.record_after_flow, step.n_record_after_flow = C.cast(ra, C.POINTER(C.c_void_p)), len(records)
 
-        def posted():
+        def posted(ticket: int):
             for f in waits:
                 f.armed = False                      # the step waits for them before it overwrites the slots
             for f in records:
                 f.armed = True
+            self._snap_ticket[d.snap] = ticket
             if self._open is d:
                 self._open = None
             h = d.handle()
@@ -387,7 +425,8 @@ class FlowStage:
 
     def flow_of(self, prev: np.ndarray, nxt: np.ndarray) -> DeviceArray:
         """Flow prev -> next as a DeviceArray (H, W, 2) float32.  The handle stays valid: the buffer it points to is re-used by the
-        call after the next one, which first brings a still-referenced handle over to the host."""
+        call after the next one, which first brings a still-referenced handle over to the host.  prev and nxt have been read when
+        this returns (a deferred flow computes from the stage's own copy): the caller may refill them at once."""
         arrs = self._check_frames([prev, nxt])
         self._have_prev = False
         s0 = 2 * self._pair_turn
@@ -397,7 +436,8 @@ class FlowStage:
     def flow_next(self, frame: np.ndarray) -> Optional[DeviceArray]:
         """Video mode, the reference's Farneback.process() (src/farneback.py:73-81): the flow from the previous frame handed in to this
         one; the previous frame's gray image is still on the device (the class's `prevgray`), so one frame crosses PCIe per step.
-        None for the first frame."""
+        None for the first frame.  `frame` has been read when this returns -- also when the handle is dropped unread, where the frame
+        is still the next pair's prev: one persistent capture buffer may be refilled before every call."""
         arrs = self._check_frames([frame])
         slot = (self._prev_slot + 1) % self.RING if self._have_prev else 0
         if self._have_prev:
@@ -423,7 +463,8 @@ class FlowStage:
         for b in [self._gray, self._bgr] + self._flow:
             if b is not None:
                 b.free()
-        for f in self._gray_fence + [self._bgr_fence]:
+        self._snap = [None] * self.SNAP
+        for f in self._gray_fence + [self._bgr_fence] + self._snap_fence:
             f.destroy()
 
 
@@ -530,7 +571,13 @@ class DetectPipeline:
 
         The whole batch -- uploads, fence, Farneback (frames, or a flow FlowStage has deferred), detection, counts, result download,
         marker -- is ONE mav_frame_step, posted to the context's worker thread (worker=True, the default: this thread goes on at once
-        and several lanes enqueue side by side) or enqueued by this thread in one call (worker=False)."""
+        and several lanes enqueue side by side) or enqueued by this thread in one call (worker=False).
+
+        Zero-copy: the per-pair arrays handed in here -- prev / nxt frames, host flow fields, sky and gt images -- are READ UNTIL
+        collect(ticket) returns (the step gathers them from where they are, on the worker thread); keep them unchanged until then.
+        After collect the same arrays may be refilled and submitted again.  A flow handle from FlowStage is exempt: the stage read
+        its frames when it handed the handle out.  sky_shared / gt_shared are uploaded once and recognised by object identity: the
+        device copy is taken the first time an object is seen, an in-place edit of that object later is not seen, a new object is."""
         ctx, lib = self.ctx, self.ctx.lib
         H, W, n0 = ctx.H, ctx.W, self.n0
         dev_flow = deferred = None
@@ -657,9 +704,16 @@ class DetectPipeline:
             s.ticket = ctx.post_step(step)
         else:
             s.ticket = 0
-            check(lib.mav_frame_step_dev(ctx.h, C.byref(step)))
+            rc = lib.mav_frame_step_dev(ctx.h, C.byref(step))
+            if rc != _lib.MAV_OK:
+                # a step that failed part-way has its marker recorded behind what it did enqueue: that has finished before `keep`
+                # goes (a deferred flow stays deferred: its handle computes it when read)
+                try:
+                    check(rc)
+                finally:
+                    lib.mav_marker_wait(None, s.marker)
         if posted is not None:
-            posted()
+            posted(s.ticket)
         s.keep = keep
         s.busy = True
         return si
@@ -667,10 +721,12 @@ class DetectPipeline:
     def _wait_slot(self, s) -> None:
         try:
             if s.ticket:
+                # (a step that failed part-way recorded its marker behind what it had enqueued, and wait_step waits for it then too:
+                # nothing of the step still reads `keep` when it goes)
                 self.ctx.wait_step(s.ticket, s.marker)
             else:
                 check(self.ctx.lib.mav_marker_wait(None, s.marker))
-        finally:                                          # a step that failed has nothing more to wait for: the slot is free either way
+        finally:                                          # the slot is free either way
             s.busy = False
             s.keep = None
 
