@@ -248,6 +248,25 @@ int mav_flow_to_color(mav_ctx*, const void* flow, int f64, int batch, uint8_t* i
 /* cv2.applyColorMap(gray, COLORMAP_JET) of n u8 values -> n BGR triples (a 3-channel image: mav_bgr2gray first, as OpenCV does). */
 int mav_colormap_jet(mav_ctx*, const uint8_t* gray, size_t n, uint8_t* bgr);
 
+/* The frame Processor.run_detection writes to processed.mp4 [src/processor.py:376-392], (batch, H, W, 3) u8 BGR:
+ *   draw_FoE(frame, foe, [0, 255, 0]) then draw_FoE(frame, foe_gt, [255, 255, 255]) [src/focus_of_expansion.py:186-201]: filled discs
+ *   of `radius` (cv2.circle, thickness -1, LINE_8: OpenCV's integer midpoint spans, clipped), centre (int(x), int(y)) truncated toward
+ *   zero, white over green; a disc with |x| > 1e9 or |y| > 1e9 is not drawn;
+ *   mask_rgb = that frame with (150, 0, 150) where mask_fixed is non-zero; overlay = cv2.addWeighted(frame, 0.2, mask_rgb, 0.8, 0.0),
+ *   exactly (p + 4 q + 2) / 5 per byte (no ties: the exact value's fraction is a multiple of .2).
+ * written[b] = 1 when the reference writes the frame (np.sum(result_img) > 0: the mask is non-empty or a disc has a pixel inside the
+ * image), else 0.  frames (batch, H, W, 3), mask_fixed (batch, H, W), foe / foe_gt (batch, 2); radius in [0, MAV_OVERLAY_MAX_RADIUS]
+ * (the reference draws 10).  A NaN coordinate is MAV_ERR_ARG (int(nan) raises in the reference).  The spans are restated from
+ * OpenCV's published routine: no image the reference wrote pins them.  The input frames are not modified. */
+#define MAV_OVERLAY_MAX_RADIUS 4096
+int mav_overlay(mav_ctx*, const uint8_t* frames, const uint8_t* mask_fixed, const double* foe, const double* foe_gt, int batch, int radius,
+                uint8_t* overlay, uint8_t* written);
+/* The same frames from the fixed mask and dense FoE that the most recent mav_detect / mav_process_batch(_dev) / mav_detect_dev / frame
+ * step on this context left resident (the mask is not moved again): host frames and foe_gt in, host overlay and written out,
+ * synchronous.  MAV_ERR_STATE under mav_last_render's rules, and when that call kept no fixed mask (mask_fixed NULL).  The dense FoE
+ * is finite by construction. */
+int mav_last_overlay(mav_ctx*, const uint8_t* frames, const double* foe_gt, int batch, int radius, uint8_t* overlay, uint8_t* written);
+
 /* ---- device-pointer entry points (asynchronous on the context's stream) -------------------------------- */
 int mav_farneback_dev(mav_ctx*, const uint8_t* prev, const uint8_t* next, int batch, float* flow);
 /* mav_farneback_init on device pointers (enqueue only).  flow_init == flow is allowed; ranges that overlap without being the same
@@ -269,6 +288,10 @@ const float* mav_last_flow_dev(const mav_ctx*);
 /* mav_render on device pointers (enqueue only); the images are written once, nothing else is. */
 int mav_render_dev(mav_ctx*, const float* flow, const double* foe, const double* omega, const double* dt, const uint8_t* frame0,
                    const uint8_t* sky, int batch, const mav_thr_params*, uint8_t* img_result, uint8_t* img_flow, uint8_t* img_phi);
+/* mav_overlay on device pointers (enqueue only).  The FoEs are device data and are not inspected on the host: a NaN coordinate draws
+ * no disc here. */
+int mav_overlay_dev(mav_ctx*, const uint8_t* frames, const uint8_t* mask_fixed, const double* foe, const double* foe_gt, int batch,
+                    int radius, uint8_t* overlay, uint8_t* written);
 /* im_helpers.calculate_tpr_fpr [src/im_helpers.py:244-252, called at src/processor.py:350-351] for device-resident masks against a
  * device-resident ground truth, counts left on the device (4 x int64 per pair: positives, negatives, true / false positives): the
  * validation tail of a batch as one more launch behind mav_process_batch_dev / mav_detect_dev.  gt_images = batch: one ground-truth

@@ -376,6 +376,7 @@ struct mav_ctx {
     DerotParams* render_derot = nullptr;
     struct LastRender {
         const float* flow = nullptr; const DerotParams* derot = nullptr; const double* foe = nullptr; const uint8_t* sky = nullptr;
+        const uint8_t* mask_fixed = nullptr;         // the call's fixed mask, if it kept one (mav_last_overlay)
         mav_thr_params thr{};
         int batch = 0;
     } last_render;
@@ -1849,7 +1850,7 @@ extern "C" int mav_detect_dev(mav_ctx* c, const float* flow, const uint32_t* sam
                    results, nullptr));
     // what mav_last_render reads: the FoE went to the context's own buffer (detect_dev with foe_out == NULL)
     c->last_render.flow = flow; c->last_render.derot = derot; c->last_render.foe = c->foe_dev; c->last_render.sky = sky;
-    c->last_render.thr = t; c->last_render.batch = batch;
+    c->last_render.thr = t; c->last_render.batch = batch; c->last_render.mask_fixed = mask_fixed;
     return MAV_OK;
 }
 
@@ -2731,6 +2732,83 @@ extern "C" int mav_colormap_jet(mav_ctx* c, const uint8_t* gray, size_t n, uint8
     CHK(check_launch("colormap"));
     CHK(download(c, bgr, dout.p, n * 3));
     return mav_sync(c);
+}
+
+// ---- the processed.mp4 frame (include/mavflow.h: mav_overlay) ---------------------------------------------------------------------
+static int check_radius(int radius, const char* fn)
+{
+    if (radius < 0 || radius > MAV_OVERLAY_MAX_RADIUS) return fail(MAV_ERR_ARG, "%s: radius %d outside [0, %d]", fn, radius, MAV_OVERLAY_MAX_RADIUS);
+    return MAV_OK;
+}
+// FoEs in host memory: a NaN coordinate is where the reference's int() raises (|v| > 1e9, infinities included, is just not drawn)
+static int check_foe_host(const double* foe, int batch, const char* what, const char* fn)
+{
+    for (int i = 0; i < 2 * batch; i++)
+        if (std::isnan(foe[i])) return fail(MAV_ERR_ARG, "%s: %s[%d][%d] is NaN (int(nan) raises in the reference)", fn, what, i / 2, i % 2);
+    return MAV_OK;
+}
+
+extern "C" int mav_overlay_dev(mav_ctx* c, const uint8_t* frames, const uint8_t* mask_fixed, const double* foe, const double* foe_gt,
+                               int batch, int radius, uint8_t* overlay, uint8_t* written)
+{
+    if (!c || !frames || !mask_fixed || !foe || !foe_gt || !overlay || !written) return fail(MAV_ERR_ARG, "mav_overlay_dev: NULL argument");
+    if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "mav_overlay_dev: batch %d outside [1, %d]", batch, c->max_batch);
+    CHK(check_radius(radius, "mav_overlay_dev"));
+    HIPCHK(hipSetDevice(c->device));
+    ProfScope ps(c, K_MISC);
+    launch_overlay(c->stream, frames, mask_fixed, foe, foe_gt, batch, c->W, c->H, radius, overlay, written);
+    return check_launch("overlay");
+}
+
+// the overlay and the flags -> host, then the stream drained
+static int download_overlay(mav_ctx* c, int batch, const DevBuf& dout, const DevBuf& dw, uint8_t* overlay, uint8_t* written)
+{
+    CHK(download(c, overlay, dout.p, c->n0 * 3 * batch));
+    CHK(download(c, written, dw.p, batch));
+    return mav_sync(c);
+}
+
+extern "C" int mav_overlay(mav_ctx* c, const uint8_t* frames, const uint8_t* mask_fixed, const double* foe, const double* foe_gt, int batch,
+                           int radius, uint8_t* overlay, uint8_t* written)
+{
+    CHK(check_batch(c, batch, "mav_overlay"));
+    if (!frames || !mask_fixed || !foe || !foe_gt || !overlay || !written) return fail(MAV_ERR_ARG, "mav_overlay: NULL argument");
+    CHK(check_radius(radius, "mav_overlay"));
+    CHK(check_foe_host(foe, batch, "foe", "mav_overlay"));
+    CHK(check_foe_host(foe_gt, batch, "foe_gt", "mav_overlay"));
+    const size_t n = c->n0 * batch;
+    DevBuf df, dm, dfoe, dgt, dout, dw;
+    CHK(df.upload(c, frames, n * 3));
+    CHK(dm.upload(c, mask_fixed, n));
+    CHK(dfoe.upload(c, foe, sizeof(double) * 2 * batch));
+    CHK(dgt.upload(c, foe_gt, sizeof(double) * 2 * batch));
+    CHK(dout.alloc(c, n * 3));
+    CHK(dw.alloc(c, batch));
+    CHK(mav_overlay_dev(c, df.as<uint8_t>(), dm.as<uint8_t>(), dfoe.as<double>(), dgt.as<double>(), batch, radius, dout.as<uint8_t>(),
+                        dw.as<uint8_t>()));
+    return download_overlay(c, batch, dout, dw, overlay, written);
+}
+
+extern "C" int mav_last_overlay(mav_ctx* c, const uint8_t* frames, const double* foe_gt, int batch, int radius, uint8_t* overlay, uint8_t* written)
+{
+    if (!c || !frames || !foe_gt || !overlay || !written) return fail(MAV_ERR_ARG, "mav_last_overlay: NULL argument");
+    if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "mav_last_overlay: batch %d outside [1, %d]", batch, c->max_batch);
+    if (!c->last_render.batch || batch != c->last_render.batch || !c->last_render.mask_fixed)
+        return fail(MAV_ERR_STATE, "mav_last_overlay: no fixed mask of a %d-pair detection call is resident", batch);
+    CHK(check_radius(radius, "mav_last_overlay"));
+    CHK(check_foe_host(foe_gt, batch, "foe_gt", "mav_last_overlay"));
+    HIPCHK(hipSetDevice(c->device));
+    // frames and image go into the NEXT free staging blocks: the detection call's own blocks (the mask of a host-pointer call) stay untouched
+    const size_t n = c->n0 * batch, mark = c->scratch_next;
+    DevBuf df, dgt, dout, dw;
+    CHK(df.upload(c, frames, n * 3));
+    CHK(dgt.upload(c, foe_gt, sizeof(double) * 2 * batch));
+    CHK(dout.alloc(c, n * 3));
+    CHK(dw.alloc(c, batch));
+    c->scratch_next = mark;          // synchronous: the blocks are free again on return
+    const mav_ctx::LastRender& r = c->last_render;
+    CHK(mav_overlay_dev(c, df.as<uint8_t>(), r.mask_fixed, r.foe, dgt.as<double>(), batch, radius, dout.as<uint8_t>(), dw.as<uint8_t>()));
+    return download_overlay(c, batch, dout, dw, overlay, written);
 }
 
 extern "C" int mav_process_batch(mav_ctx* c, const uint8_t* prev, const uint8_t* next, const uint32_t* samples, const double* omega,

@@ -140,6 +140,10 @@ void launch_render_f32(hipStream_t st, const float* flow, const DerotParams* der
 // flow_to_color of an already derotated float64 field
 void launch_render_f64(hipStream_t st, const double* flow, int B, int W, int H, unsigned long long* radmax, uint8_t* flow_img);
 void launch_colormap_jet(hipStream_t st, const uint8_t* gray, size_t n, uint8_t* bgr);
+// The processed.mp4 frame: frames (B, H, W, 3) BGR, fixed masks (B, H, W), FoE and ground-truth FoE (B, 2) each -> out (B, H, W, 3)
+// and written[B] (zeroed here, then set by the kernel).  radius in [0, MAV_OVERLAY_MAX_RADIUS].
+void launch_overlay(hipStream_t st, const uint8_t* frames, const uint8_t* mask, const double* foe, const double* foe_gt, int B, int W, int H,
+                    int radius, uint8_t* out, uint8_t* written);
 
 // ---- window search (kernels_window.hip, compiled with -ffp-contract=off) -----------------------------------------
 #define MAV_PYR_MAX 32

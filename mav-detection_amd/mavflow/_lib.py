@@ -56,6 +56,7 @@ EXPORTS = [
     "mav_marker_query", "mav_frame_step_dev", "mav_frame_step_post", "mav_frame_step_wait", "mav_worker_drain", "mav_worker_wait_enqueued",
     "mav_farneback_init", "mav_farneback_init_dev", "mav_stage_update_matrices_from", "mav_stage_initial_flow",
     "mav_render", "mav_render_dev", "mav_last_render", "mav_flow_to_color", "mav_colormap_jet",
+    "mav_overlay", "mav_overlay_dev", "mav_last_overlay",
 ]
 
 OPTFLOW_USE_INITIAL_FLOW = 4                    # FbParams.flags bit (cv2.OPTFLOW_USE_INITIAL_FLOW): see Context.farneback(initial_flow=)
@@ -202,6 +203,10 @@ def load(path: str | None = None) -> C.CDLL:
     lib.mav_last_render.argtypes = [vp, C.c_int, vp, vp, vp]
     lib.mav_flow_to_color.argtypes = [vp, vp, C.c_int, C.c_int, vp]
     lib.mav_colormap_jet.argtypes = [vp, vp, C.c_size_t, vp]
+    # ctx, frames, mask_fixed, foe, foe_gt, batch, radius, overlay, written
+    lib.mav_overlay.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp]
+    lib.mav_overlay_dev.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp]
+    lib.mav_last_overlay.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp]
     _lib = lib
     return lib
 
@@ -815,6 +820,57 @@ class Context:
         out = np.empty(g.shape + (3,), np.uint8)
         check(self.lib.mav_colormap_jet(self.h, _ptr(g), g.size, _ptr(out)))
         return out
+
+    # -- the processed.mp4 frame (processor.py:376-392) ------------------------------------------------------
+    OVERLAY_RADIUS = 10                                 # what the reference's loop draws (draw_FoE's default)
+
+    def _bgr_frames(self, frames) -> np.ndarray:
+        a = np.asarray(frames)
+        a = a[None] if a.ndim == 3 else a
+        if a.ndim != 4 or a.shape[1:] != (self.H, self.W, 3) or a.dtype != np.uint8:
+            raise ValueError(f"frames: expected (batch, {self.H}, {self.W}, 3) uint8, got {a.shape} {a.dtype}")
+        return np.ascontiguousarray(a)
+
+    @staticmethod
+    def _foes(foe, B: int, name: str) -> np.ndarray:
+        """(B, 2) float64 of FoE tuples as draw_FoE takes them: one (x, y) for a batch of one, or B of them.  A coordinate that IS the
+        np.nan object draws nothing in the reference (-> inf: not drawn, as |v| > 1e9); any other NaN goes on to the library, which
+        refuses it (ValueError, as int(nan) raises)."""
+        rows = [foe] if np.ndim(foe) == 1 else list(foe)
+        if len(rows) != B or any(len(r) != 2 for r in rows):
+            raise ValueError(f"{name}: expected {B} (x, y) pairs")
+        return np.array([[np.inf if v is np.nan else float(v) for v in r] for r in rows], np.float64).reshape(B, 2)
+
+    def overlay(self, frames, masks, foe, foe_gt, radius: int = OVERLAY_RADIUS):
+        """The frame the reference's loop writes to processed.mp4 (processor.py:376-392): FoE discs (foe green, foe_gt white over it)
+        on the BGR frame, the fixed mask painted (150, 0, 150), blended 0.2 / 0.8 -> (overlay (B, H, W, 3) u8, written (B,) bool: the
+        reference writes the frame, np.sum(result_img) > 0).  frames (B, H, W, 3) u8, masks (B, H, W), foe / foe_gt (x, y) per pair.
+        The frames are not modified."""
+        frames = self._bgr_frames(frames)
+        B = frames.shape[0]
+        masks = self._imgs(np.asarray(masks).astype(np.uint8), "masks")
+        if masks.shape[0] != B:
+            raise ValueError(f"masks: {masks.shape[0]} for {B} frames")
+        fo, gt = self._foes(foe, B, "foe"), self._foes(foe_gt, B, "foe_gt")
+        out = _pinned.empty(self, frames.shape, np.uint8)
+        wr = np.empty(B, np.uint8)
+        check(self.lib.mav_overlay(self.h, _ptr(frames), _ptr(masks), _ptr(fo), _ptr(gt), B, int(radius), _ptr(out), _ptr(wr)))
+        return out, wr.view(np.bool_)
+
+    def overlay_last(self, frames, foe_gt, radius: int = OVERLAY_RADIUS):
+        """overlay() with the fixed masks and dense FoEs that the most recent detect / process_batch(_dev) / frame step left on the device:
+        the frames go up, the overlays come back, the masks stay put."""
+        frames = self._bgr_frames(frames)
+        B = frames.shape[0]
+        gt = self._foes(foe_gt, B, "foe_gt")
+        out = _pinned.empty(self, frames.shape, np.uint8)
+        wr = np.empty(B, np.uint8)
+        check(self.lib.mav_last_overlay(self.h, _ptr(frames), _ptr(gt), B, int(radius), _ptr(out), _ptr(wr)))
+        return out, wr.view(np.bool_)
+
+    def overlay_dev(self, frames_ptr, mask_ptr, foe_ptr, foe_gt_ptr, batch: int, overlay_ptr, written_ptr, radius: int = OVERLAY_RADIUS):
+        """mav_overlay_dev: enqueue only, device pointers."""
+        check(self.lib.mav_overlay_dev(self.h, frames_ptr, mask_ptr, foe_ptr, foe_gt_ptr, int(batch), int(radius), overlay_ptr, written_ptr))
 
     # -- device-pointer path (bench, multi-GPU) --------------------------------------------------------------
     def process_batch_dev(self, prev_ptr, next_ptr, samples_ptr, batch, results_ptr, flow_ptr=None, omega_ptr=None,

@@ -6,7 +6,7 @@ reference does (rows first, then columns, :70-71) and the constructor consumes t
 run visits the same pixels.  The GPU never generates samples."""
 from __future__ import annotations
 
-from typing import Tuple
+from typing import List, Tuple
 
 import numpy as np
 
@@ -70,3 +70,42 @@ class FocusOfExpansion:
         """The threshold block of processor.py:333-341 -> (estimate_fixed, total_mask); phi is not materialised."""
         _, fixed, total, _ = self._ctx(derotated_flow_uv).phi_mask(derotated_flow_uv, FoE, sky=sky_mask, params=params, want_phi=False)
         return fixed[0], total[0]
+
+    def draw_FoE(self, frame: np.ndarray, FoE: Tuple[float, float], color: List[int] = [0, 42, 255], radius: int = 10) -> np.ndarray:
+        """Draw the FoE as a filled disc, in place, and return the frame (:186-201): cv2.circle(frame, (int(x), int(y)), radius, color,
+        -1) -- OpenCV's integer midpoint spans (disc_half_widths), clipped to the image.  Nothing is drawn when |x| or |y| > 1e9 or a
+        coordinate IS the np.nan object; any other NaN raises ValueError, as int() does.  The kernel of Context.overlay draws the
+        same spans."""
+        if FoE[0] is np.nan or FoE[1] is np.nan or np.abs(FoE[0]) > 1e9 or np.abs(FoE[1]) > 1e9:
+            return frame
+        cx, cy = int(FoE[0]), int(FoE[1])
+        H, W = frame.shape[:2]
+        value = color[0] if frame.ndim == 2 else list(color)[:frame.shape[2]]
+        for k, h in enumerate(disc_half_widths(radius)):
+            for y in {cy - k, cy + k}:
+                x0, x1 = max(cx - h, 0), min(cx + h, W - 1)
+                if 0 <= y < H and x0 <= x1:
+                    frame[y, x0:x1 + 1] = value
+        return frame
+
+
+def disc_half_widths(radius: int) -> List[int]:
+    """Half-width of each row offset 0..radius of cv2.circle(thickness=-1, LINE_8, shift 0): OpenCV's Circle(..., fill=1) emits the
+    spans [cx +- dx] on rows cy +- dy and [cx +- dy] on rows cy +- dx of its integer midpoint walk; a row is its widest span.  Radius 10:
+    10 9 9 9 9 8 8 7 6 4 0.  Restated from the published routine: no image the reference wrote pins it."""
+    r = int(radius)
+    if r < 0:
+        raise ValueError(f"radius {radius} < 0")
+    h = [-1] * (r + 1)
+    err, dx, dy, plus, minus = 0, r, 0, 1, 2 * r - 1
+    while dx >= dy:
+        h[dy] = max(h[dy], dx)
+        h[dx] = max(h[dx], dy)
+        dy += 1
+        err += plus
+        plus += 2
+        if err > 0:
+            err -= minus
+            dx -= 1
+            minus -= 2
+    return h

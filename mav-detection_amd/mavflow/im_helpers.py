@@ -151,6 +151,14 @@ def apply_colormap(img: np.ndarray, max_value: float = None, colormap: int = COL
     return _ctx(a.shape[1], a.shape[0]).colormap_jet(a)
 
 
+def add_weighted(src1: np.ndarray, alpha: float, src2: np.ndarray, beta: float, gamma: float) -> np.ndarray:
+    """cv2.addWeighted of two u8 images (processor.py:391): src1 * alpha + src2 * beta + gamma in float32, rounded to nearest and
+    saturated to u8, as OpenCV does for 8-bit data.  The staged loop's blend; the fast loops blend in the overlay kernel, whose integer
+    form (p + 4 q + 2) / 5 is this function for alpha = 0.2, beta = 0.8 on every (p, q) (tests/test_overlay_cpu.py)."""
+    a = np.asarray(src1).astype(np.float32) * np.float32(alpha) + np.asarray(src2).astype(np.float32) * np.float32(beta)
+    return np.clip(np.rint(a + np.float32(gamma)), 0, 255).astype(np.uint8)
+
+
 def pyramid(image: np.ndarray, scale: float = 1.5, minSize: Tuple[int, int] = (30, 30)) -> Iterator[np.ndarray]:
     """Every level of the reference's generator (:12-35): the image itself, then imutils.resize(previous, width=int(w / scale))
     = cv2.resize(INTER_AREA) until a side drops below minSize.  Levels >= 1 come from the device (mav_stage_pyramid_level, the

@@ -15,7 +15,11 @@ Each loop writes `{results_path}/image_{i:05d}.json` per frame as the reference'
 constructor) names a results_path.  With an explicit images_path each loop also writes the three result images of :364-374 per frame,
 `{images_path}/result-images|derotated|phi/image_{i:05d}.png`, rendered on the device (mav_last_render: one launch behind the
 frame's step, the flow is not moved again) and PNG-encoded by a pool of at most 16 threads off the loop's thread; every file is
-complete when the loop returns.  The video (processed.mp4) and the homography branch are not reproduced."""
+complete when the loop returns.  With a processed_path each loop also writes the frame the reference appends to processed.mp4 (:376-392:
+FoE discs on the frame, the fixed mask painted purple, blended 0.2 / 0.8) as `{processed_path}/image_{i:05d}.png` for every frame the
+reference would write (np.sum(result_img) > 0); the fast loops render it on the device from the resident mask and FoE
+(mav_last_overlay), the staged loop composes it from draw_FoE, the painted mask and add_weighted.  No video container is encoded: the
+reference's etc/bash/pngs_to_mp4.sh turns the sequence into the mp4.  The homography branch is not reproduced."""
 from __future__ import annotations
 
 import json
@@ -166,7 +170,8 @@ PNG_BACKLOG = 4 * PNG_WORKERS        # files queued before the loop waits for th
 
 
 class Processor:
-    def __init__(self, config: RunConfig, results_path: Optional[str] = None, images_path: Optional[str] = None) -> None:
+    def __init__(self, config: RunConfig, results_path: Optional[str] = None, images_path: Optional[str] = None,
+                 processed_path: Optional[str] = None) -> None:
         self.config = config
         self.logger = config.logger
         self.sequence = config.sequence
@@ -193,8 +198,11 @@ class Processor:
         self._center = None
         # the result images (processor.py:364-374): only an explicit images_path turns them on
         self.images_path = images_path
+        # the processed.mp4 frames (processor.py:376-392) as a PNG sequence: only an explicit processed_path turns them on
+        self.processed_path = processed_path
         self._png_pool = None
         self._png_jobs = deque()
+        self._dirs_made = set()
 
     def is_active(self) -> bool:
         return self.frame_index < self.dataset.N - 1 and not self.is_exiting
@@ -289,18 +297,31 @@ class Processor:
                 f.write(json.dumps(utils.get_json(r), indent=4, sort_keys=True))
 
     # -- result images (processor.py:364-374) ----------------------------------------------------------------------------------------
+    def _queue_png(self, d: str, i: int, img) -> None:
+        """Queue the PNG file {d}/image_{i:05d}.png on the encoder pool (at most PNG_BACKLOG files queued)."""
+        if d not in self._dirs_made:
+            os.makedirs(d, exist_ok=True)
+            self._dirs_made.add(d)
+        if self._png_pool is None:
+            self._png_pool = ThreadPoolExecutor(max_workers=min(PNG_WORKERS, os.cpu_count() or 1), thread_name_prefix="png")
+        while len(self._png_jobs) >= PNG_BACKLOG:
+            self._png_jobs.popleft().result()
+        self._png_jobs.append(self._png_pool.submit(frame_source.imwrite, os.path.join(d, f"image_{i:05d}.png"), img))
+
     def _write_images(self, ids, imgs) -> None:
         """Queue the PNG files of frames `ids`; imgs: Context.render's dict of (n, H, W, 3) BGR arrays."""
-        if self._png_pool is None:
-            for d in IMAGE_DIRS.values():
-                os.makedirs(os.path.join(self.images_path, d), exist_ok=True)
-            self._png_pool = ThreadPoolExecutor(max_workers=min(PNG_WORKERS, os.cpu_count() or 1), thread_name_prefix="png")
         for k, i in enumerate(ids):
             for name, d in IMAGE_DIRS.items():
-                while len(self._png_jobs) >= PNG_BACKLOG:
-                    self._png_jobs.popleft().result()
-                path = os.path.join(self.images_path, d, f"image_{i:05d}.png")
-                self._png_jobs.append(self._png_pool.submit(frame_source.imwrite, path, imgs[name][k]))
+                self._queue_png(os.path.join(self.images_path, d), i, imgs[name][k])
+
+    def _write_processed(self, ids, frames, written) -> None:
+        """Queue the processed.mp4 frames of frames `ids` (processor.py:385-394): a frame the reference does not write (nothing in the
+        fixed mask and no disc pixel in the image) gets its message instead of a file."""
+        for k, i in enumerate(ids):
+            if written[k]:
+                self._queue_png(self.processed_path, i, frames[k])
+            else:
+                self.logger.warning("An error occured while processing frames.")
 
     def _flush_images(self) -> None:
         """Every queued file written (raises what an encoder raised)."""
@@ -384,7 +405,7 @@ class Processor:
         pipe = None
         while self.is_active():
             i = self.frame_index
-            self.dataset.get_frame()
+            orig_frame = self.dataset.get_frame()
             self.flow_uv = self.dataset.get_flow_uv(i)
             if self.flow_uv is None:
                 raise ValueError("Could not load flow field.")
@@ -393,7 +414,7 @@ class Processor:
                 # a float64 field is evaluated in float64 from the start by the reference: the fused float32 call would narrow
                 # it, so this frame goes through the float64 kernels (the staged calls)
                 finish(0)
-                self._staged_frame(i)
+                self._staged_frame(i, orig_frame)
                 continue
             on_dev = isinstance(self.flow_uv, pipeline.DeviceArray) and self.flow_uv.on_device
             # (a host flow field -- the .flo seam -- is a 3-launch chain behind a 16.6 MB upload at 1080p: PCIe-bound, one lane; measured
@@ -412,23 +433,31 @@ class Processor:
             rand1[..., 1] = np.random.randint(0, self.flow_uv.shape[1], 2000)
             omega, dt = self._rates(i) if i >= 1 else (np.zeros(3), 1.0)
             ticket = pipe.submit(rand1, flow=self.flow_uv, omega=omega, dt=dt, frame0=[i < 1], **kw)
-            pending.append((pipe, i, ticket, sky))
+            pending.append((pipe, i, ticket, sky, orig_frame))
             # with images the frame is finished at once: its images are rendered from what its step left on the lane's context
-            finish(0 if self.images_path is not None else pipe.depth)
+            finish(0 if self._renders else pipe.depth)
             self.frame_index += 1
         finish(0)
         self._flush_images()
         return self.detection_results
 
-    def _finish_frame(self, pipe, i: int, ticket, sky) -> None:
+    @property
+    def _renders(self) -> bool:
+        """Images or processed frames are rendered from what a step left resident: the loops finish each step before the next."""
+        return self.images_path is not None or self.processed_path is not None
+
+    def _finish_frame(self, pipe, i: int, ticket, sky, orig_frame) -> None:
         out = pipe.collect(ticket)
         rec = out["results"][0]
         self.estimate_fixed, self.total_mask = out["mask_fixed"][0], out["mask_dyn"][0]
         r = self._fill_result(i, (float(rec["foe"][0]), float(rec["foe"][1])), sky, out["counts_fixed"][0], out["counts_dyn"][0])
         self.detection_boxes[i] = utils.Rectangle.from_box(rec["box"])
         self._store(i, r)
+        ctx = pipe.pipes[ticket[0]].ctx
         if self.images_path is not None:
-            self._write_images([i], pipe.pipes[ticket[0]].ctx.render_last(1))
+            self._write_images([i], ctx.render_last(1))
+        if self.processed_path is not None:
+            self._write_processed([i], *ctx.overlay_last(orig_frame, [r.foe_gt]))
 
     def run_detection_staged(self) -> Dict[int, FrameResult]:
         """The same loop through the reference-named calls one by one (Detector.derotate, get_FOE_dense, the masks): every call
@@ -436,15 +465,15 @@ class Processor:
         those shims; run_detection() is the fast form."""
         while self.is_active():
             i = self.frame_index
-            self.dataset.get_frame()
+            orig_frame = self.dataset.get_frame()
             self.flow_uv = self.dataset.get_flow_uv(i)
             if self.flow_uv is None:
                 raise ValueError("Could not load flow field.")
-            self._staged_frame(i)
+            self._staged_frame(i, orig_frame)
         self._flush_images()
         return self.detection_results
 
-    def _staged_frame(self, i: int) -> None:
+    def _staged_frame(self, i: int, orig_frame) -> None:
         """One frame through the reference-named calls (processor.py:306-341), flow already in self.flow_uv."""
         self._derot_frame = i
         self.flow_uv_derotated = self.detector.derotate(i - self.frame_step_size, i, np.asarray(self.flow_uv))
@@ -461,6 +490,17 @@ class Processor:
                 result = im_helpers.to_rgb(255 * np.asarray(fixed))
             self._write_images([i], dict(result=result[None], flow=im_helpers.get_flow_vis(self.flow_uv_derotated)[None],
                                          phi=im_helpers.apply_colormap(im_helpers.to_rgb(phi, max_value=180.0))[None]))
+        if self.processed_path is not None:                   # processor.py:376-394 on a copy: the dataset's array stays as it is
+            frame = np.array(orig_frame, copy=True)
+            with np.errstate(invalid="ignore"):
+                result_img = im_helpers.to_rgb(255 * np.asarray(fixed))
+            for img in (frame, result_img):
+                self.focus_of_expansion.draw_FoE(img, foe, [0, 255, 0])
+                self.focus_of_expansion.draw_FoE(img, r.foe_gt, [255, 255, 255])
+            mask_rgb = np.copy(frame)
+            mask_rgb[fixed] = (150, 0, 150)
+            mask_vis = im_helpers.add_weighted(frame, 0.2, mask_rgb, 1.0 - 0.2, 0.0)
+            self._write_processed([i], [mask_vis], [np.sum(result_img) > 0])
         self.frame_index += 1
 
     def run_detection_batched(self, batch: int = 8) -> Dict[int, FrameResult]:
@@ -478,6 +518,8 @@ class Processor:
         for b0 in range(0, len(idx), batch):
             ids = idx[b0:b0 + batch]
             pairs = [self.dataset.frame_pair(i) for i in ids]
+            # the frames the reference's loop draws on, one get_frame() per frame index as it calls it (only when they are drawn)
+            frames = [self.dataset.get_frame() for _ in ids] if self.processed_path is not None else None
             samples = np.empty((len(ids), 2000, 2), np.uint32)
             for k in range(len(ids)):                      # same draws, same order as get_FOE_dense
                 samples[k, :, 0] = np.random.randint(0, H, 2000)
@@ -490,8 +532,8 @@ class Processor:
             sky_scores = [self.dataset.validate_sky_segment(sk, utils.assert_type(self.dataset.get_depth(i))) for i, sk in zip(ids, skies)]
             ticket = pipe.submit(samples, prev=[p[0] for p in pairs], nxt=[p[1] for p in pairs], omega=omega, dt=dts,
                                  frame0=[i < 1 for i in ids], **kw)
-            pending.append((ids, ticket, sky_scores))
-            while len(pending) > (0 if self.images_path is not None else pipe.depth):     # images: rendered behind the batch's step
+            pending.append((ids, ticket, sky_scores, frames))
+            while len(pending) > (0 if self._renders else pipe.depth):     # images: rendered behind the batch's step
                 self._finish_batch(pipe, *pending.popleft())
         while pending:
             self._finish_batch(pipe, *pending.popleft())
@@ -499,15 +541,20 @@ class Processor:
         self._flush_images()
         return self.detection_results
 
-    def _finish_batch(self, pipe, ids, ticket, sky_scores) -> None:
+    def _finish_batch(self, pipe, ids, ticket, sky_scores, frames) -> None:
         out = pipe.collect(ticket)
+        gts = []
         for k, i in enumerate(ids):
             rec = out["results"][k]
             r = self._fill_result(i, (float(rec["foe"][0]), float(rec["foe"][1])), sky_scores[k], out["counts_fixed"][k], out["counts_dyn"][k])
             self.detection_boxes[i] = utils.Rectangle.from_box(rec["box"])
             self._store(i, r)
+            gts.append(r.foe_gt)
+        ctx = pipe.pipes[ticket[0]].ctx
         if self.images_path is not None:
-            self._write_images(ids, pipe.pipes[ticket[0]].ctx.render_last(len(ids)))
+            self._write_images(ids, ctx.render_last(len(ids)))
+        if self.processed_path is not None:
+            self._write_processed(ids, *ctx.overlay_last(np.stack(frames), gts))
         self.estimate_fixed, self.total_mask = out["mask_fixed"][-1], out["mask_dyn"][-1]     # of the last frame, as the loop leaves them
 
     def release(self) -> None:
