@@ -15,6 +15,7 @@
  *     exceptions cross the boundary.
  *   - a mav_ctx is single-threaded (as the reference's loop is); distinct contexts are independent.
  *   - images are (batch, H, W) u8; flow is (batch, H, W, 2) interleaved (u, v); masks are (batch, H, W) u8 0/1.
+ *     The Farneback `_ex` entry points also take 16-bit and float32 frames (MAV_DEPTH_*), as cv2.calcOpticalFlowFarneback does.
  */
 #ifndef MAVFLOW_H
 #define MAVFLOW_H
@@ -31,6 +32,15 @@ extern "C" {
 #define MAV_ERR_HIP (-2)   /* a HIP runtime call failed */
 #define MAV_ERR_OOM (-3)   /* device allocation failed */
 #define MAV_ERR_STATE (-4) /* context unusable / no GPU */
+
+/* Frame depths of the `_ex` entry points: cv2's depth codes.  cv2 converts every layer's source frame with convertTo(CV_32F) before
+ * GaussianBlur / resize; so does the library -- exactly for 8U and 16U, a copy for 32F -- and everything after the layer image is the
+ * same float32 arithmetic for every depth: frames of any depth that hold the same values give the same flow, bit for bit.  No
+ * rescaling: the solve's 1e-3 regulariser (optflowgf.cpp) makes the flow depend on the intensity scale, as it does in cv2.  Other
+ * codes (signed depths, 64F: narrow on the host first) are MAV_ERR_ARG. */
+#define MAV_DEPTH_8U 0
+#define MAV_DEPTH_16U 2
+#define MAV_DEPTH_32F 5
 
 typedef struct mav_ctx mav_ctx;
 
@@ -132,6 +142,10 @@ int mav_get_option(mav_ctx*, const char* name, long* value);
  * whether the small-batch schedule applies and, per layer, the blur form and how the sweeps run (pairs per launch, bands).
  * bench.py prints it into its record and hashes it together with the kernel sources. */
 int mav_schedule_info(mav_ctx*, int batch, char* buf, size_t cap);
+/* The same for frames of a MAV_DEPTH_* depth: only the layers' "blur" forms depend on it (staged rows of 16U / 32F frames take 2x / 4x
+ * the LDS of 8U ones, and a short Gaussian whose staged tile would not fit goes through the two-pass form).  MAV_DEPTH_8U: the line
+ * of mav_schedule_info, byte for byte. */
+int mav_schedule_info_ex(mav_ctx*, int batch, int depth, char* buf, size_t cap);
 /* Device memory: free / total bytes of the context's GPU (hipMemGetInfo), the bytes this context holds in all (workspace, flow
  * workspace, detection scratch, staging blocks of the host-pointer calls, window-search buffers) and the Farneback workspace alone
  * (0 until a call computes flow).  Any pointer may be NULL. */
@@ -153,6 +167,11 @@ int mav_farneback(mav_ctx*, const uint8_t* prev, const uint8_t* next, int batch,
  * flow_init == flow (in place, cv2's idiom) is allowed.  The first call allocates the top layer's field for the pairs of one group
  * (mav_mem_info's workspace figure grows by it); a context that never calls it holds nothing more. */
 int mav_farneback_init(mav_ctx*, const uint8_t* prev, const uint8_t* next, int batch, const float* flow_init, float* flow);
+/* mav_farneback (flow_init NULL) or mav_farneback_init (flow_init = the pairs' initial flow; it may equal flow) on frames of a
+ * MAV_DEPTH_* depth: (batch, H, W) uint8_t, uint16_t or float, prev and next of the same depth.  MAV_DEPTH_8U gives the flow of
+ * mav_farneback / mav_farneback_init bit for bit; frame runs (next == prev + one frame) are recognised at every depth.  An unknown
+ * depth is MAV_ERR_ARG and nothing is enqueued. */
+int mav_farneback_ex(mav_ctx*, const void* prev, const void* next, int depth, int batch, const float* flow_init, float* flow);
 /* Detector.derotate [src/detector.py:70-117]: omega = angular difference / dt, (batch,3); dt (batch). */
 int mav_derotate(mav_ctx*, const float* flow, const double* omega, const double* dt, int batch, double* flow_out);
 /* FocusOfExpansion.get_FOE_dense + ransac [src/focus_of_expansion.py:32-86]; samples (batch, 2N, 2) = (row, col)
@@ -272,6 +291,8 @@ int mav_farneback_dev(mav_ctx*, const uint8_t* prev, const uint8_t* next, int ba
 /* mav_farneback_init on device pointers (enqueue only).  flow_init == flow is allowed; ranges that overlap without being the same
  * field are MAV_ERR_ARG.  mav_last_flow_dev reports `flow`. */
 int mav_farneback_init_dev(mav_ctx*, const uint8_t* prev, const uint8_t* next, int batch, const float* flow_init, float* flow);
+/* mav_farneback_ex on device pointers (enqueue only); flow_init == flow is allowed (a warm-started chain in place). */
+int mav_farneback_ex_dev(mav_ctx*, const void* prev, const void* next, int depth, int batch, const float* flow_init, float* flow);
 int mav_process_batch_dev(mav_ctx*, const uint8_t* prev, const uint8_t* next, const uint32_t* samples, const double* omega,
                           const double* dt, const uint8_t* frame0, const uint8_t* sky, int batch, const mav_foe_params*,
                           const mav_thr_params*, float* flow, double* phi, uint8_t* mask_fixed, uint8_t* mask_dyn,
@@ -484,6 +505,8 @@ int mav_stage_blur_resize(mav_ctx*, const uint8_t* img, int k, float* out);
 /* the same through the separable two-pass kernels (H x w scratch in memory) that layers with a long Gaussian use: layers with a
  * short one go through ONE fused kernel in the product path, and the two forms must agree bit for bit */
 int mav_stage_blur_resize_two_pass(mav_ctx*, const uint8_t* img, int k, float* out);
+/* either of the two for a frame of a MAV_DEPTH_* depth (two_pass != 0: the two-pass form) */
+int mav_stage_blur_resize_ex(mav_ctx*, const void* img, int depth, int k, int two_pass, float* out);
 /* FarnebackPolyExp of a (h, w) f32 image at layer k -> R as 5 planes (5, h, w) */
 int mav_stage_polyexp(mav_ctx*, const float* I, int k, float* R);
 /* FarnebackUpdateMatrices at layer k: R0, R1 (5,h,w), flow (h,w,2) -> M (5,h,w) */

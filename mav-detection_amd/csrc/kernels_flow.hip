@@ -110,26 +110,47 @@ static __device__ __forceinline__ int reflect101d(int p, int len)
 }
 
 // Image z of a launch over two runs of images (the `prev` frames and the `next` frames of a group): z < split comes from run a.
-static __device__ __forceinline__ const uint8_t* image_of(const uint8_t* a, const uint8_t* b, int split, size_t stride, int z)
+template <typename T>
+static __device__ __forceinline__ const T* image_of(const T* a, const T* b, int split, size_t stride, int z)
 {
     return z < split ? a + (size_t)z * stride : b + (size_t)(z - split) * stride;
 }
 
+// Source depths.  A frame is uint8_t, uint16_t or float (cv2's CV_8U, CV_16U, CV_32F); every loader below converts a pixel with
+// (float)v -- convertTo(CV_32F), exact for both integer depths -- and everything after that conversion is the same arithmetic in the
+// same order for every depth, so frames of any depth that hold the same values give the same bits.  A QUAD is four consecutive pixels,
+// the unit of the staged / aligned loads: one dword of u8, two of u16, four of f32.  The u8 forms keep their dword streams re-aligned
+// with v_alignbyte; the wider forms read their pixels from LDS one element at a time (an element is LDS-addressable, so no re-alignment).
+template <typename T> struct QuadOf;
+template <> struct QuadOf<uint8_t> { typedef uint32_t type; };
+template <> struct QuadOf<uint16_t> { typedef uint2 type; };
+template <> struct QuadOf<float> { typedef uint4 type; };
+template <typename T>      // the wider depths' quads (the u8 forms unpack their dwords where they use them)
+static __device__ __forceinline__ void quad_px(typename QuadOf<T>::type q, float o[4])
+{
+    if constexpr (sizeof(T) == 2) {
+        o[0] = (float)(q.x & 0xffffu); o[1] = (float)(q.x >> 16); o[2] = (float)(q.y & 0xffffu); o[3] = (float)(q.y >> 16);
+    } else {
+        o[0] = __uint_as_float(q.x); o[1] = __uint_as_float(q.y); o[2] = __uint_as_float(q.z); o[3] = __uint_as_float(q.w);
+    }
+}
+
 // Horizontal pass at destination column (s0, f) for the four source rows y0 .. y0 + 3 (clamped to the image): the ONE spelling of
 // this arithmetic, shared by the two-pass and the fused kernel so that both give the same bits.
-static __device__ __forceinline__ void blur_h4(const uint8_t* __restrict__ base, int W, int H, int y0, int s0, float f,
+template <typename T>
+static __device__ __forceinline__ void blur_h4(const T* __restrict__ base, int W, int H, int y0, int s0, float f,
                                                const BlurParams& bp, float out[4])
 {
     const int r = bp.ksize >> 1;
     const int s1 = s0 + 1 < W ? s0 + 1 : s0;
-    const uint8_t* rows[4];
+    const T* rows[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) rows[k] = base + (size_t)min(y0 + k, H - 1) * W;
     float b0[4] = {0.f, 0.f, 0.f, 0.f}, b1[4] = {0.f, 0.f, 0.f, 0.f};
     if (s0 - r >= 0 && s0 + 1 + r < W) {               // interior: B[s0+1] re-uses B[s0]'s pixels shifted by one
         float prev[4];
-        if (bp.ksize == 5) {                               // all 24 bytes of the thread requested before any is used
-            uint8_t px[4][6];
+        if (bp.ksize == 5) {                               // all 24 pixels of the thread requested before any is used
+            T px[4][6];
 #pragma unroll
             for (int k = 0; k < 4; k++)
 #pragma unroll
@@ -141,6 +162,19 @@ static __device__ __forceinline__ void blur_h4(const uint8_t* __restrict__ base,
                 for (int k = 0; k < 4; k++) {
                     b0[k] = fmaf(g, (float)px[k][t], b0[k]);
                     b1[k] = fmaf(g, (float)px[k][t + 1], b1[k]);
+                }
+            }
+        } else if constexpr (sizeof(T) > 1) {              // wider pixels: one aligned element load each, same order as below
+#pragma unroll
+            for (int k = 0; k < 4; k++) prev[k] = (float)rows[k][s0 - r];
+            for (int j = 1; j <= bp.ksize; j++) {
+                const float g = bp.g[j - 1];
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const float nxt = (float)rows[k][s0 - r + j];
+                    b0[k] = fmaf(g, prev[k], b0[k]);
+                    b1[k] = fmaf(g, nxt, b1[k]);
+                    prev[k] = nxt;
                 }
             }
         } else {
@@ -259,6 +293,41 @@ static __device__ __forceinline__ void blur_h4_stream(WordFn rd, int off, float 
     else if (bp.ksize == 13) blur_h4_stream_t<13>(rd, off, f, bp, out);
     else blur_h4_stream_t<0>(rd, off, f, bp, out);
 }
+// blur_h4_stream_t for the wider depths: px(k, j) = pixel j (0 .. ksize) of the thread's k-th staged row, already a float.  The same
+// products in the same order: prev = pixel j - 1, nxt = pixel j for tap j - 1.
+template <int KS, typename PxFn>
+static __device__ __forceinline__ void blur_h4_stream_px(PxFn px, float f, const BlurParams& bp, float out[4])
+{
+    float b0[4] = {0.f, 0.f, 0.f, 0.f}, b1[4] = {0.f, 0.f, 0.f, 0.f}, prev[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) prev[k] = px(k, 0);
+    auto step = [&](int j) {
+        const float g = bp.g[j - 1];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const float nxt = px(k, j);
+            b0[k] = fmaf(g, prev[k], b0[k]);
+            b1[k] = fmaf(g, nxt, b1[k]);
+            prev[k] = nxt;
+        }
+    };
+    if constexpr (KS > 0) {
+#pragma unroll
+        for (int j = 1; j <= KS; j++) step(j);
+    } else {
+        for (int j = 1; j <= bp.ksize; j++) step(j);
+    }
+    const float a0 = 1.f - f;
+#pragma unroll
+    for (int k = 0; k < 4; k++) out[k] = fmaf(b1[k], f, b0[k] * a0);
+}
+template <typename PxFn>
+static __device__ __forceinline__ void blur_h4_stream_px(PxFn px, float f, const BlurParams& bp, float out[4])
+{
+    if (bp.ksize == 5) blur_h4_stream_px<5>(px, f, bp, out);
+    else if (bp.ksize == 13) blur_h4_stream_px<13>(px, f, bp, out);
+    else blur_h4_stream_px<0>(px, f, bp, out);
+}
 
 // The horizontal pass once more, for LONG Gaussians (the two-pass kernels: 37 and 95 taps at 3840 x 2160 / 5 layers), on tap PAIRS
 // kept in LDS.  blur_h4_stream's generic loop fetched every tap with a vector load from global memory and waited for it -- one
@@ -315,16 +384,45 @@ static __device__ __forceinline__ void blur_h4_pairs(WordFn rd, int off, float f
 #pragma unroll
     for (int k = 0; k < 4; k++) out[k] = fmaf(acc[k].y, f, acc[k].x * a0);
 }
+// The pair form for the wider depths: px(k, t) = pixel t of the thread's k-th staged row as a float, G(t) = tap pair t.  Pixels
+// 0 .. ksize only: the u8 form's padding pairs are (0, 0), whose fused multiply-adds leave the accumulators as they are, so stopping at
+// ksize gives the same bits -- and a float frame's staging slack (not written) is never multiplied.  KS > 0: ksize at compile time.
+template <int KS, typename PxFn, typename PairFn>
+static __device__ __forceinline__ void blur_h4_pairs_px(PxFn px, float f, int ksize, PairFn G, float out[4])
+{
+    mav_f2 acc[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) acc[k] = (mav_f2)(0.f, 0.f);
+    auto step = [&](int t) {
+        const mav_f2 g = G(t);
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const float p = px(k, t);
+            acc[k] = __builtin_elementwise_fma(g, (mav_f2)(p, p), acc[k]);
+        }
+    };
+    if constexpr (KS > 0) {
+#pragma unroll
+        for (int t = 0; t <= KS; t++) step(t);
+    } else {
+        for (int t = 0; t <= ksize; t++) step(t);
+    }
+    const float a0 = 1.f - f;
+#pragma unroll
+    for (int k = 0; k < 4; k++) out[k] = fmaf(acc[k].y, f, acc[k].x * a0);
+}
 
-// Source rows [y0, y0 + n_rows) (row index clamped to the image), byte columns [xb, xb + 4 words) of one image -> LDS, row pitch
-// pitch_w dwords; xb is a multiple of 4 (possibly negative).  Columns outside the image hold their BORDER_REFLECT_101 pixels.
-// Dword-addressable rows: coalesced dword loads; frames whose width is no multiple of 4: byte by byte.
-template <int NB = 8>      // NB loads of a thread in flight before the first LDS store
-static __device__ __forceinline__ void stage_rows(const uint8_t* __restrict__ base, int W, int H, int y0, int n_rows, int xb, int words,
+// Source rows [y0, y0 + n_rows) (row index clamped to the image), pixel columns [xb, xb + 4 words) of one image -> LDS, row pitch
+// pitch_w quads (u8: dwords); xb is a multiple of 4 (possibly negative).  Columns outside the image hold their BORDER_REFLECT_101 pixels.
+// Quad-addressable rows: coalesced quad loads (dword / dwordx2 / dwordx4); frames whose width is no multiple of 4: pixel by pixel.
+template <typename T, int NB = 8>      // NB loads of a thread in flight before the first LDS store
+static __device__ __forceinline__ void stage_rows(const T* __restrict__ base, int W, int H, int y0, int n_rows, int xb, int words,
                                                   bool dword_ok, uint32_t* __restrict__ sw, int pitch_w)
 {
+    typedef typename QuadOf<T>::type Q;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint8_t* sb = (uint8_t*)sw;
+    T* sb = (T*)sw;
+    Q* sq = (Q*)sw;
     if (dword_ok) {
         // words inside the image as dwords (xb and W are multiples of 4); the few columns outside it byte by byte, reflected.
         // A wave's (row, 64-word chunk) items go eight at a time: eight independent loads in flight, then eight LDS stores (a plain
@@ -334,7 +432,7 @@ static __device__ __forceinline__ void stage_rows(const uint8_t* __restrict__ ba
         const int n_chunks = (whi - wlo + 63) >> 6, rows_w = n_rows > wv ? (n_rows - wv + 3) >> 2 : 0;
         const int n_items = rows_w * n_chunks;
         for (int it0 = 0; it0 < n_items; it0 += NB) {
-            uint32_t v[NB];
+            Q v[NB];
             int dst[NB];
 #pragma unroll
             for (int u = 0; u < NB; u++) {
@@ -343,16 +441,16 @@ static __device__ __forceinline__ void stage_rows(const uint8_t* __restrict__ ba
                 const int row = wv + 4 * ri, wd = wlo + 64 * ch + lane;
                 const bool ok = it < n_items && wd < whi;
                 dst[u] = ok ? row * pitch_w + wd : -1;
-                const uint32_t* g = (const uint32_t*)(base + (size_t)min(y0 + (ok ? row : 0), H - 1) * W + xb);
+                const Q* g = (const Q*)(base + (size_t)min(y0 + (ok ? row : 0), H - 1) * W + xb);
                 v[u] = g[ok ? wd : wlo];
             }
 #pragma unroll
             for (int u = 0; u < NB; u++)
-                if (dst[u] >= 0) sw[dst[u]] = v[u];
+                if (dst[u] >= 0) sq[dst[u]] = v[u];
         }
         if (n_out > 0)
             for (int row = wv; row < n_rows; row += 4) {
-                const uint8_t* p = base + (size_t)min(y0 + row, H - 1) * W;
+                const T* p = base + (size_t)min(y0 + row, H - 1) * W;
                 for (int j = lane; j < n_out; j += 64) {
                     const int col = j < n_left ? j : 4 * whi + (j - n_left);
                     sb[row * pitch_w * 4 + col] = p[reflect101d(xb + col, W)];
@@ -360,7 +458,7 @@ static __device__ __forceinline__ void stage_rows(const uint8_t* __restrict__ ba
             }
     } else {
         for (int row = wv; row < n_rows; row += 4) {
-            const uint8_t* p = base + (size_t)min(y0 + row, H - 1) * W;
+            const T* p = base + (size_t)min(y0 + row, H - 1) * W;
             for (int j = lane; j < 4 * words; j += 64) sb[row * pitch_w * 4 + j] = p[reflect101d(xb + j, W)];
         }
     }
@@ -412,14 +510,15 @@ static __device__ __forceinline__ float blur_v1(RowFn row, int H, int s0, float 
 }
 
 // direct form (no LDS): every thread walks its own bytes in global memory.  Fallback for scales whose staged rows would not fit LDS.
-__global__ __launch_bounds__(256) void k_blur_resize_h_direct(const uint8_t* __restrict__ img, const uint8_t* __restrict__ img2, int split,
+template <typename T>
+__global__ __launch_bounds__(256) void k_blur_resize_h_direct(const T* __restrict__ img, const T* __restrict__ img2, int split,
                                                               size_t img_stride, int W, int H, int w, BlurParams bp,
                                                               float* __restrict__ tmp, size_t tmp_stride)
 {
     const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
     const int y0 = (blockIdx.y * 4 + (threadIdx.x >> 6)) * 4;
     if (dx >= w || y0 >= H) return;
-    const uint8_t* base = image_of(img, img2, split, img_stride, blockIdx.z);
+    const T* base = image_of(img, img2, split, img_stride, blockIdx.z);
     int s0; float f;
     resize_coord(dx, W, w, bp.scale_x, &s0, &f);
     float o[4];
@@ -432,16 +531,17 @@ __global__ __launch_bounds__(256) void k_blur_resize_h_direct(const uint8_t* __r
 // Staged form: a workgroup owns 64 destination columns x rows_blk source rows; the u8 bytes those need go through LDS once
 // (coalesced dword loads; a thread of the direct form issues (ksize + 1) / 4 dependent dword loads per row from an address of its
 // own -- 24 round trips for the 95-tap layer of the 4K preset -- and neighbouring lanes re-read each other's bytes).
-__global__ __launch_bounds__(256) void k_blur_resize_h(const uint8_t* __restrict__ img, const uint8_t* __restrict__ img2, int split,
+template <typename T>
+__global__ __launch_bounds__(256) void k_blur_resize_h(const T* __restrict__ img, const T* __restrict__ img2, int split,
                                                        size_t img_stride, int W, int H, int w, BlurParams bp,
                                                        float* __restrict__ tmp, size_t tmp_stride, int rows_blk, int pitch_w, int dword_ok)
 {
-    extern __shared__ __attribute__((aligned(16))) uint32_t srows[];         // [rows_blk][pitch_w], then the tap pairs (stage_tap_pairs)
+    extern __shared__ __attribute__((aligned(16))) uint32_t srows[];         // [rows_blk][pitch_w] quads, then the tap pairs (stage_tap_pairs)
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int dx0 = blockIdx.x * 64;
-    const uint8_t* base = image_of(img, img2, split, img_stride, blockIdx.z);
+    const T* base = image_of(img, img2, split, img_stride, blockIdx.z);
     const int dx = dx0 + lane;
-    mav_f2* G2 = (mav_f2*)(srows + ((rows_blk * pitch_w + 1) & ~1));
+    mav_f2* G2 = (mav_f2*)(srows + ((rows_blk * pitch_w * (int)sizeof(T) + 1) & ~1));
     stage_tap_pairs(bp, G2);                                                 // (visible after the first barrier below)
     int s0; float f;
     if (bp.xs) { s0 = bp.xs[min(dx, w - 1)]; f = bp.xf[min(dx, w - 1)]; }
@@ -460,7 +560,11 @@ __global__ __launch_bounds__(256) void k_blur_resize_h(const uint8_t* __restrict
         __syncthreads();
         for (int i = wv * 4; i < n_rows; i += 16) {
             float o[4];
-            blur_h4_pairs([&](int k, int wi) { return srows[min(i + k, n_rows - 1) * pitch_w + wi]; }, off, f, bp.ksize, G2, o);
+            if constexpr (sizeof(T) == 1)
+                blur_h4_pairs([&](int k, int wi) { return srows[min(i + k, n_rows - 1) * pitch_w + wi]; }, off, f, bp.ksize, G2, o);
+            else
+                blur_h4_pairs_px<0>([&](int k, int t) { return (float)((const T*)srows)[(min(i + k, n_rows - 1) * pitch_w) * 4 + off + t]; },
+                                    f, bp.ksize, [&](int t) { return G2[t]; }, o);
             if (dx < w) {
 #pragma unroll
                 for (int k = 0; k < 4; k++)
@@ -494,7 +598,8 @@ __global__ __launch_bounds__(256) void k_blur_resize_v(const float* __restrict__
 // (stage_rows: ~7 coalesced dword loads per thread instead of ~70 single-byte loads) and the horizontal pass reads it from there;
 // pitch_w == 0 (regions too large for LDS): every thread reads its bytes from global memory.
 // one 64 x FB_TH tile of one image: base = the u8 frame, out = the layer image of that frame
-static __device__ __forceinline__ void blur_fused_tile(const uint8_t* __restrict__ base, float* __restrict__ out, int W, int H, int w, int h,
+template <typename T>
+static __device__ __forceinline__ void blur_fused_tile(const T* __restrict__ base, float* __restrict__ out, int W, int H, int w, int h,
                                                        const BlurParams& bp, int rows_cap, int pitch_w, int dword_ok, int tile_x, int tile_y,
                                                        float* __restrict__ hrows)
 {
@@ -524,7 +629,10 @@ static __device__ __forceinline__ void blur_fused_tile(const uint8_t* __restrict
         __syncthreads();
         for (int i = wv * 4; i < n_rows; i += 16) {
             float o[4];
-            blur_h4_stream([&](int k, int wi) { return sw[min(i + k, n_rows - 1) * pitch_w + wi]; }, off, f, bp, o);
+            if constexpr (sizeof(T) == 1)
+                blur_h4_stream([&](int k, int wi) { return sw[min(i + k, n_rows - 1) * pitch_w + wi]; }, off, f, bp, o);
+            else
+                blur_h4_stream_px([&](int k, int t) { return (float)((const T*)sw)[(min(i + k, n_rows - 1) * pitch_w) * 4 + off + t]; }, f, bp, o);
 #pragma unroll
             for (int k = 0; k < 4; k++)
                 if (i + k < n_rows) hrows[(i + k) * 64 + lane] = o[k];
@@ -624,8 +732,8 @@ static __device__ __forceinline__ float blur_v1_interior(const float* __restrict
         return fmaf(b1, f, b0 * (1.f - f));
     }
 }
-template <int KS, int TH>
-static __device__ __forceinline__ void blur_fused_tile_fast(const uint8_t* __restrict__ base, float* __restrict__ out, int W, int H, int w, int h,
+template <typename T, int KS, int TH>
+static __device__ __forceinline__ void blur_fused_tile_fast(const T* __restrict__ base, float* __restrict__ out, int W, int H, int w, int h,
                                                             const BlurParams& bp, int rows_cap, int pitch_w, int tile_x, int tile_y,
                                                             float* __restrict__ hrows)
 {
@@ -648,22 +756,23 @@ static __device__ __forceinline__ void blur_fused_tile_fast(const uint8_t* __res
     const int sa = __builtin_amdgcn_readlane(row_s, 0), sb = __builtin_amdgcn_readlane(row_s, TH - 1);
     const int ylo = max(sa - r, 0), yhi = min(sb + 1 + r, H - 1);
     const int n_rows = min(yhi - ylo + 1, rows_cap);
-    // ---- stage the u8 source rows [ylo, ylo + n_rows), byte columns [xb, xb + 4 words)
+    // ---- stage the source rows [ylo, ylo + n_rows), pixel columns [xb, xb + 4 words)
     {
+        typedef typename QuadOf<T>::type Q;
         const int wlo = xb < 0 ? (-xb) >> 2 : 0, whi = min(words, (W - xb) >> 2);
-        const int nw = whi - wlo;                                            // dwords of a row that lie inside the image
-        const uint8_t* g0 = base + (size_t)ylo * W + (xb + 4 * wlo);         // wave-uniform
-        uint32_t* s00 = sw + wlo;
+        const int nw = whi - wlo;                                            // quads of a row that lie inside the image
+        const T* g0 = base + (size_t)ylo * W + (xb + 4 * wlo);               // wave-uniform
+        Q* s00 = (Q*)sw + wlo;
         for (int c0 = 0; c0 < nw; c0 += 64) {
             const int wd = c0 + lane;
             const bool ok = wd < nw;
             const unsigned lo = 4u * (unsigned)(ok ? wd : 0);
             for (int row0 = wv; row0 < n_rows; row0 += 24) {
-                uint32_t v[6];
+                Q v[6];
 #pragma unroll
                 for (int u = 0; u < 6; u++) {
                     const int row = min(row0 + 4 * u, n_rows - 1);           // (wave-uniform)
-                    v[u] = *(const uint32_t*)(g0 + ((unsigned)(row * W) + lo));
+                    v[u] = *(const Q*)(g0 + ((unsigned)(row * W) + lo));
                 }
 #pragma unroll
                 for (int u = 0; u < 6; u++) {
@@ -673,10 +782,10 @@ static __device__ __forceinline__ void blur_fused_tile_fast(const uint8_t* __res
             }
         }
         const int n_left = 4 * wlo, n_out = n_left + 4 * max(words - whi, 0);
-        if (n_out > 0) {                                                     // the few columns outside the image, reflected, byte by byte
-            uint8_t* sb8 = (uint8_t*)sw;
+        if (n_out > 0) {                                                     // the few columns outside the image, reflected, pixel by pixel
+            T* sb8 = (T*)sw;
             for (int row = wv; row < n_rows; row += 4) {
-                const uint8_t* p = base + (size_t)(ylo + row) * W;
+                const T* p = base + (size_t)(ylo + row) * W;
                 for (int j = lane; j < n_out; j += 64) {
                     const int col = j < n_left ? j : 4 * whi + (j - n_left);
                     sb8[row * pitch_w * 4 + col] = p[reflect101d(xb + col, W)];
@@ -691,7 +800,12 @@ static __device__ __forceinline__ void blur_fused_tile_fast(const uint8_t* __res
         const uint32_t* rw = sw + i * pitch_w;
         // (the pair form pays for 13 taps -- 184 vs 194 us per launch for layer 2 of the 4K preset -- and costs for 5: 64 vs 53 us per
         // launch for layer 1 at 1080p, where the compiler's own mix of scalar-tap FMAs is shorter)
-        if constexpr (KS >= 13) blur_h4_pairs_t<KS>([&](int k, int wi) { return rw[k * pitch_w + wi]; }, off, f, tp, o);
+        if constexpr (sizeof(T) > 1) {
+            const T* re = (const T*)sw + i * pitch_w * 4 + off;
+            if constexpr (KS >= 13)
+                blur_h4_pairs_px<KS>([&](int k, int t) { return (float)re[k * pitch_w * 4 + t]; }, f, KS, [&](int t) { return tp.G[t]; }, o);
+            else blur_h4_stream_px<KS>([&](int k, int t) { return (float)re[k * pitch_w * 4 + t]; }, f, bp, o);
+        } else if constexpr (KS >= 13) blur_h4_pairs_t<KS>([&](int k, int wi) { return rw[k * pitch_w + wi]; }, off, f, tp, o);
         else blur_h4_stream_t<KS>([&](int k, int wi) { return rw[k * pitch_w + wi]; }, off, f, bp, o);
 #pragma unroll
         for (int k = 0; k < 4; k++)
@@ -724,98 +838,118 @@ static int fused_path_of(const BlurParams& bp, int pitch_w, int dword_ok)
 {
     return !fused_fast_ok(bp, pitch_w, dword_ok) ? FP_GENERIC : (bp.ksize == 5 ? FP_FAST5 : FP_FAST13);
 }
-template <int PATH>
-static __device__ __forceinline__ void blur_fused_any(const uint8_t* __restrict__ base, float* __restrict__ out, int W, int H, int w, int h,
+template <typename T, int PATH>
+static __device__ __forceinline__ void blur_fused_any(const T* __restrict__ base, float* __restrict__ out, int W, int H, int w, int h,
                                                       const BlurParams& bp, int rows_cap, int pitch_w, int dword_ok, int th, int tile_x, int tile_y,
                                                       float* __restrict__ hrows)
 {
     // th = tile height chosen by the host (fused_plan): 16, or 8 where 16 rows' source region does not fit LDS (fast tile only)
     const bool fast = PATH == FP_FAST5 || PATH == FP_FAST13 || (PATH == FP_ANY && fused_fast_ok(bp, pitch_w, dword_ok));
     if ((PATH == FP_FAST5 || PATH == FP_ANY) && fast && bp.ksize == 5) {
-        if (th == 16) blur_fused_tile_fast<5, 16>(base, out, W, H, w, h, bp, rows_cap, pitch_w, tile_x, tile_y, hrows);
-        else blur_fused_tile_fast<5, 8>(base, out, W, H, w, h, bp, rows_cap, pitch_w, tile_x, tile_y, hrows);
+        if (th == 16) blur_fused_tile_fast<T, 5, 16>(base, out, W, H, w, h, bp, rows_cap, pitch_w, tile_x, tile_y, hrows);
+        else blur_fused_tile_fast<T, 5, 8>(base, out, W, H, w, h, bp, rows_cap, pitch_w, tile_x, tile_y, hrows);
         return;
     }
     if ((PATH == FP_FAST13 || PATH == FP_ANY) && fast && bp.ksize == 13) {
-        if (th == 16) blur_fused_tile_fast<13, 16>(base, out, W, H, w, h, bp, rows_cap, pitch_w, tile_x, tile_y, hrows);
-        else blur_fused_tile_fast<13, 8>(base, out, W, H, w, h, bp, rows_cap, pitch_w, tile_x, tile_y, hrows);
+        if (th == 16) blur_fused_tile_fast<T, 13, 16>(base, out, W, H, w, h, bp, rows_cap, pitch_w, tile_x, tile_y, hrows);
+        else blur_fused_tile_fast<T, 13, 8>(base, out, W, H, w, h, bp, rows_cap, pitch_w, tile_x, tile_y, hrows);
         return;
     }
     if (PATH == FP_GENERIC || PATH == FP_ANY)
         blur_fused_tile(base, out, W, H, w, h, bp, rows_cap, pitch_w, dword_ok, tile_x, tile_y, hrows);
 }
-template <int PATH>
-__global__ __launch_bounds__(256) void k_blur_resize_fused(const uint8_t* __restrict__ img, const uint8_t* __restrict__ img2, int split,
+template <typename T, int PATH>
+__global__ __launch_bounds__(256) void k_blur_resize_fused(const T* __restrict__ img, const T* __restrict__ img2, int split,
                                                            size_t img_stride, int W, int H, int w, int h, BlurParams bp,
                                                            float* __restrict__ out, size_t out_stride, int rows_cap, int pitch_w, int dword_ok, int th)
 {
-    extern __shared__ __attribute__((aligned(16))) float hrows[];       // [rows_cap][64] f32, then [rows_cap + 3][pitch_w] dwords of u8
-    blur_fused_any<PATH>(image_of(img, img2, split, img_stride, blockIdx.z), out + (size_t)blockIdx.z * out_stride, W, H, w, h, bp, rows_cap,
+    extern __shared__ __attribute__((aligned(16))) float hrows[];       // [rows_cap][64] f32, then [rows_cap + 3][pitch_w] quads of T
+    blur_fused_any<T, PATH>(image_of(img, img2, split, img_stride, blockIdx.z), out + (size_t)blockIdx.z * out_stride, W, H, w, h, bp, rows_cap,
                          pitch_w, dword_ok, th, blockIdx.x, blockIdx.y, hrows);
 }
 
 static int fused_blur_rows(int H, int h, int ksize, int th = FB_TH) { return (int)((th - 1) * ((double)H / h)) + (ksize | 1) + 4; }
-// LDS of a fused tile: rows x 64 f32 of horizontal-pass results, then the staged u8 rows (three rows of slack: the fast tile's
-// horizontal pass works on whole groups of four rows)
-static size_t fused_lds_bytes(int rows, int pitch_w) { return (size_t)rows * 256 + (size_t)(rows + 3) * 4 * pitch_w; }
-// dwords per staged source row: the columns 64 destination pixels need (63 scale + 1 + ksize), the 4-alignment slack and the word
+// LDS of a fused tile: rows x 64 f32 of horizontal-pass results, then the staged rows of esize-byte pixels (three rows of slack: the
+// fast tile's horizontal pass works on whole groups of four rows)
+static size_t fused_lds_bytes(int rows, int pitch_w, int esize = 1) { return (size_t)rows * 256 + (size_t)(rows + 3) * 4 * pitch_w * esize; }
+// quads per staged source row: the columns 64 destination pixels need (63 scale + 1 + ksize), the 4-alignment slack and the quad
 // blur_h4_stream reads ahead
 static int staged_pitch_words(int W, int w, int ksize) { return ((int)(63 * ((double)W / w)) + (ksize | 1) + 2 + 3) / 4 + 3; }
 // How a fused layer's tiles are cut: 64 x 16 with the source region staged in LDS when that fits 64 KB; else, for the fast tile
 // (fused_fast_ok), 64 x 8 staged (layer 2 of the 4K / 5-layer preset: 13 taps at scale 6.25 -- 110 source rows of 420 bytes for 16
-// destination rows); else 64 x 16 unstaged (every thread reads its bytes from global memory).
+// destination rows); else 64 x 16 unstaged (every thread reads its bytes from global memory).  Wider pixels (esize 2 / 4) take the
+// fused form only where a staged 64 x 16 tile fits (blur_resize_is_fused), so for them the plan is always that one.
 struct FusedPlan { int th, rows, pitch_w; size_t lds; };
-static FusedPlan fused_plan(int W, int H, int w, int h, const BlurParams& bp, int dword_ok)
+static FusedPlan fused_plan(int W, int H, int w, int h, const BlurParams& bp, int dword_ok, int esize = 1)
 {
     const int pitch = staged_pitch_words(W, w, bp.ksize);
     FusedPlan p{FB_TH, fused_blur_rows(H, h, bp.ksize), pitch, 0};
-    if (fused_lds_bytes(p.rows, pitch) > 64 * 1024) {
+    if (fused_lds_bytes(p.rows, pitch, esize) > 64 * 1024) {
         const int rows8 = fused_blur_rows(H, h, bp.ksize, 8);
-        if (fused_fast_ok(bp, pitch, dword_ok) && fused_lds_bytes(rows8, pitch) <= 64 * 1024) { p.th = 8; p.rows = rows8; }
+        if (fused_fast_ok(bp, pitch, dword_ok) && fused_lds_bytes(rows8, pitch, esize) <= 64 * 1024) { p.th = 8; p.rows = rows8; }
         else p.pitch_w = 0;
     }
-    p.lds = fused_lds_bytes(p.rows, p.pitch_w);
+    p.lds = fused_lds_bytes(p.rows, p.pitch_w, esize);
     return p;
 }
-bool blur_resize_is_fused(int W, int H, int w, int h, int ksize)
+bool blur_resize_is_fused(int W, int H, int w, int h, int ksize, int esize)
 {
-    return !(w == W && h == H) && ksize <= 13 && H > 2 * ksize && W > 2 * ksize && (size_t)fused_blur_rows(H, h, ksize) * 256 <= 48 * 1024;
+    if (!(!(w == W && h == H) && ksize <= 13 && H > 2 * ksize && W > 2 * ksize && (size_t)fused_blur_rows(H, h, ksize) * 256 <= 48 * 1024))
+        return false;
+    // u8: fused_plan falls back to 64 x 8 staged tiles or to the unstaged tile.  Wider pixels: fused only where the staged region of a
+    // 64 x 16 tile (2x / 4x the bytes of u8) fits the 64 KB default dynamic LDS, whichever tile code the frames' alignment picks; else
+    // the two-pass form, whose staged row block shrinks to fit 48 KB (or reads global memory directly)
+    if (esize == 1) return true;
+    const int pitch = staged_pitch_words(W, w, ksize);
+    return fused_lds_bytes(fused_blur_rows(H, h, ksize), pitch, esize) <= 64 * 1024;
 }
 
 // Layer 0 (scale 1, sigma 0 -> fixed kernel [1/4, 1/2, 1/4], BORDER_REFLECT_101): every product is exact in f32,
 // so this is bit-identical to OpenCV's row-then-column filter.  One thread = 4 consecutive pixels x 4 rows:
-// six aligned u32 row loads + the two neighbour bytes per row, float4 stores.
-static __device__ __forceinline__ void blur3_block(const uint8_t* __restrict__ src, float* __restrict__ dst, int W, int H, int bx, int by)
+// six aligned quad row loads (u8: a dword) + the two neighbour pixels per row, float4 stores.
+template <typename T>
+static __device__ __forceinline__ void blur3_block(const T* __restrict__ src, float* __restrict__ dst, int W, int H, int bx, int by)
 {
+    typedef typename QuadOf<T>::type Q;
     const int x = (bx * 64 + (threadIdx.x & 63)) * 4;
     const int y0 = (by * 4 + (threadIdx.x >> 6)) * 4;
     if (x >= W || y0 >= H) return;
     const int xl = x == 0 ? 1 : x - 1;                    // reflect101
     const int xr = x + 4 >= W ? W - 2 : x + 4;
-    // all 18 loads of the thread first (six rows x {left byte, aligned dword, right byte}); the outputs below are computed
+    // all 18 loads of the thread first (six rows x {left pixel, aligned quad, right pixel}); the outputs below are computed
     // unconditionally and only the stores are predicated, so no load is deferred behind a branch
-    uint32_t qs[6];
-    uint8_t ls[6], rs[6];
+    Q qs[6];
+    T ls[6], rs[6];
 #pragma unroll
     for (int r = 0; r < 6; r++) {
         int yy = y0 - 1 + r;
         yy = yy < 0 ? -yy : (yy >= H ? 2 * H - 2 - yy : yy);
         yy = yy < 0 ? 0 : (yy >= H ? H - 1 : yy);         // rows past the image (tail of the last group): any valid row
-        const uint8_t* p = src + (size_t)yy * W;
-        qs[r] = *(const uint32_t*)(p + x);
+        const T* p = src + (size_t)yy * W;
+        qs[r] = *(const Q*)(p + x);
         ls[r] = p[xl];
         rs[r] = p[xr];
     }
     float hrow[6][4];
 #pragma unroll
     for (int r = 0; r < 6; r++) {
-        const uint32_t q = qs[r];
-        const float a = (float)ls[r], b0 = (float)(q & 255u), b1 = (float)((q >> 8) & 255u), b2 = (float)((q >> 16) & 255u),
-                    b3 = (float)(q >> 24), c = (float)rs[r];
-        hrow[r][0] = 0.5f * b0 + 0.25f * (a + b1);
-        hrow[r][1] = 0.5f * b1 + 0.25f * (b0 + b2);
-        hrow[r][2] = 0.5f * b2 + 0.25f * (b1 + b3);
-        hrow[r][3] = 0.5f * b3 + 0.25f * (b2 + c);
+        if constexpr (sizeof(T) == 1) {
+            const uint32_t q = qs[r];
+            const float a = (float)ls[r], b0 = (float)(q & 255u), b1 = (float)((q >> 8) & 255u), b2 = (float)((q >> 16) & 255u),
+                        b3 = (float)(q >> 24), c = (float)rs[r];
+            hrow[r][0] = 0.5f * b0 + 0.25f * (a + b1);
+            hrow[r][1] = 0.5f * b1 + 0.25f * (b0 + b2);
+            hrow[r][2] = 0.5f * b2 + 0.25f * (b1 + b3);
+            hrow[r][3] = 0.5f * b3 + 0.25f * (b2 + c);
+        } else {                                            // the same four lines on the quad's converted pixels
+            float b[4];
+            quad_px<T>(qs[r], b);
+            const float a = (float)ls[r], c = (float)rs[r];
+            hrow[r][0] = 0.5f * b[0] + 0.25f * (a + b[1]);
+            hrow[r][1] = 0.5f * b[1] + 0.25f * (b[0] + b[2]);
+            hrow[r][2] = 0.5f * b[2] + 0.25f * (b[1] + b[3]);
+            hrow[r][3] = 0.5f * b[3] + 0.25f * (b[2] + c);
+        }
     }
 #pragma unroll
     for (int r = 0; r < 4; r++) {
@@ -830,8 +964,8 @@ static __device__ __forceinline__ void blur3_block(const uint8_t* __restrict__ s
 
 // The layer images of SEVERAL layers in one launch (a small group's pyramid: launch_blur_multi): job 0.. = layers whose blur is the
 // 3x3 form (layer 0) or the fused form; workgroup b belongs to the last job whose first_block is <= b.
-template <int PATH>      // the tile code its fused jobs need (FP_ANY when they differ)
-__global__ __launch_bounds__(256) void k_blur_multi(const uint8_t* __restrict__ img, const uint8_t* __restrict__ img2, int split, size_t img_stride,
+template <typename T, int PATH>      // the tile code its fused jobs need (FP_ANY when they differ)
+__global__ __launch_bounds__(256) void k_blur_multi(const T* __restrict__ img, const T* __restrict__ img2, int split, size_t img_stride,
                                                     int W, int H, int dword_ok, BlurJobs jobs)
 {
     extern __shared__ __attribute__((aligned(16))) float hrows[];
@@ -841,25 +975,38 @@ __global__ __launch_bounds__(256) void k_blur_multi(const uint8_t* __restrict__ 
     const int b = (int)blockIdx.x - J.first_block;
     const int z = b / (J.gx * J.gy), rem = b - z * J.gx * J.gy;
     const int by = rem / J.gx, bx = rem - by * J.gx;
-    const uint8_t* base = image_of(img, img2, split, img_stride, z);
+    const T* base = image_of(img, img2, split, img_stride, z);
     float* out = J.out + (size_t)z * J.out_stride;
-    if (J.fused) blur_fused_any<PATH>(base, out, W, H, J.w, J.h, J.bp, J.rows_cap, J.pitch_w, dword_ok, J.th, bx, by, hrows);
+    if (J.fused) blur_fused_any<T, PATH>(base, out, W, H, J.w, J.h, J.bp, J.rows_cap, J.pitch_w, dword_ok, J.th, bx, by, hrows);
     else blur3_block(base, out, W, H, bx, by);
+}
+// rows are quad-addressable (aligned dword / dwordx2 / dwordx4 loads) when W, the image stride (pixels) and both bases are multiples of
+// four pixels
+template <typename T>
+static int quad_ok(const T* img, const T* img2, size_t img_stride, int W)
+{
+    const uintptr_t m = 4 * sizeof(T) - 1;
+    return (W % 4 == 0 && img_stride % 4 == 0 && ((uintptr_t)img & m) == 0 && ((uintptr_t)img2 & m) == 0) ? 1 : 0;
 }
 // Layer images of several layers of G frames in ONE launch.  jobs[i]: layer size, BlurParams, out / out_stride filled by the caller; a
 // layer qualifies when blur_multi_ok says so (3x3 form or fused form).  Grid bookkeeping and the LDS size are filled here.
-static bool blur3_fast_ok(const uint8_t* img, const uint8_t* img2, size_t img_stride, int W, int H, int w, int h, const BlurParams& bp,
+template <typename T>
+static bool blur3_fast_ok(const T* img, const T* img2, size_t img_stride, int W, int H, int w, int h, const BlurParams& bp,
                           const float* out, size_t out_stride);
-bool blur_multi_ok(const uint8_t* img, const uint8_t* img2, size_t img_stride, int W, int H, int w, int h, BlurParams bp, const float* out,
+template <typename T>
+bool blur_multi_ok(const T* img, const T* img2, size_t img_stride, int W, int H, int w, int h, BlurParams bp, const float* out,
                    size_t out_stride)
 {
-    return blur3_fast_ok(img, img2 ? img2 : img, img_stride, W, H, w, h, bp, out, out_stride) || blur_resize_is_fused(W, H, w, h, bp.ksize);
+    return blur3_fast_ok(img, img2 ? img2 : img, img_stride, W, H, w, h, bp, out, out_stride) ||
+           blur_resize_is_fused(W, H, w, h, bp.ksize, (int)sizeof(T));
 }
-void launch_blur_multi(hipStream_t st, const uint8_t* img, const uint8_t* img2, int split, size_t img_stride, int G, int W, int H, BlurJobs jobs,
+template <typename T>
+void launch_blur_multi(hipStream_t st, const T* img, const T* img2, int split, size_t img_stride, int G, int W, int H, BlurJobs jobs,
                        bool split_by_path)
 {
     if (!img2) { img2 = img; split = G; }
-    const int dword_ok = (W % 4 == 0 && img_stride % 4 == 0 && ((uintptr_t)img & 3) == 0 && ((uintptr_t)img2 & 3) == 0) ? 1 : 0;
+    const int dword_ok = quad_ok(img, img2, img_stride, W);
+    const int esize = (int)sizeof(T);
     if (split_by_path) {      // many frames per layer (the deep layers of a whole call): one launch per tile code -- a launch that mixes
                               // them runs every layer at the occupancy of the hungriest path -- instead of one launch in all
         bool done[MAV_MAX_JOBS] = {false};
@@ -867,7 +1014,7 @@ void launch_blur_multi(hipStream_t st, const uint8_t* img, const uint8_t* img2, 
             if (done[i]) continue;
             auto path_of = [&](const BlurJob& J) {
                 if (J.w == W && J.h == H) return -1;
-                const FusedPlan fp = fused_plan(W, H, J.w, J.h, J.bp, dword_ok);
+                const FusedPlan fp = fused_plan(W, H, J.w, J.h, J.bp, dword_ok, esize);
                 return fused_path_of(J.bp, fp.pitch_w, dword_ok);
             };
             const int p = path_of(jobs.j[i]);
@@ -884,7 +1031,7 @@ void launch_blur_multi(hipStream_t st, const uint8_t* img, const uint8_t* img2, 
         BlurJob& J = jobs.j[i];
         J.fused = !(J.w == W && J.h == H);
         if (J.fused) {
-            const FusedPlan fp = fused_plan(W, H, J.w, J.h, J.bp, dword_ok);
+            const FusedPlan fp = fused_plan(W, H, J.w, J.h, J.bp, dword_ok, esize);
             J.rows_cap = fp.rows; J.pitch_w = fp.pitch_w; J.th = fp.th;
             J.gx = (J.w + 63) / 64; J.gy = (J.h + fp.th - 1) / fp.th;
             lds = std::max(lds, fp.lds);
@@ -902,71 +1049,88 @@ void launch_blur_multi(hipStream_t st, const uint8_t* img, const uint8_t* img2, 
             path = path < 0 ? p : (path == p ? p : FP_ANY);
         }
     switch (path) {
-    case FP_FAST13: hipLaunchKernelGGL(k_blur_multi<FP_FAST13>, dim3(blocks), dim3(256), lds, st, img, img2, split, img_stride, W, H, dword_ok, jobs); break;
-    case FP_GENERIC: hipLaunchKernelGGL(k_blur_multi<FP_GENERIC>, dim3(blocks), dim3(256), lds, st, img, img2, split, img_stride, W, H, dword_ok, jobs); break;
-    case FP_ANY: hipLaunchKernelGGL(k_blur_multi<FP_ANY>, dim3(blocks), dim3(256), lds, st, img, img2, split, img_stride, W, H, dword_ok, jobs); break;
-    default: hipLaunchKernelGGL(k_blur_multi<FP_FAST5>, dim3(blocks), dim3(256), lds, st, img, img2, split, img_stride, W, H, dword_ok, jobs); break;   // (also: no fused job)
+    case FP_FAST13: hipLaunchKernelGGL((k_blur_multi<T, FP_FAST13>), dim3(blocks), dim3(256), lds, st, img, img2, split, img_stride, W, H, dword_ok, jobs); break;
+    case FP_GENERIC: hipLaunchKernelGGL((k_blur_multi<T, FP_GENERIC>), dim3(blocks), dim3(256), lds, st, img, img2, split, img_stride, W, H, dword_ok, jobs); break;
+    case FP_ANY: hipLaunchKernelGGL((k_blur_multi<T, FP_ANY>), dim3(blocks), dim3(256), lds, st, img, img2, split, img_stride, W, H, dword_ok, jobs); break;
+    default: hipLaunchKernelGGL((k_blur_multi<T, FP_FAST5>), dim3(blocks), dim3(256), lds, st, img, img2, split, img_stride, W, H, dword_ok, jobs); break;   // (also: no fused job)
     }
 }
 
 // G images: the first `split` from run img, the rest from run img2 (both with stride img_stride); split >= G: one run.
 // two_pass: force the separable two-pass form through the tmp scratch (the stage hook compares the two forms).
-__global__ __launch_bounds__(256) void k_blur3_u8(const uint8_t* __restrict__ img, const uint8_t* __restrict__ img2, int split,
-                                                  size_t img_stride, int W, int H, float* __restrict__ out, size_t out_stride)
+template <typename T>
+__global__ __launch_bounds__(256) void k_blur3(const T* __restrict__ img, const T* __restrict__ img2, int split,
+                                               size_t img_stride, int W, int H, float* __restrict__ out, size_t out_stride)
 {
     blur3_block(image_of(img, img2, split, img_stride, blockIdx.z), out + (size_t)blockIdx.z * out_stride, W, H, blockIdx.x, blockIdx.y);
 }
 
-static bool blur3_fast_ok(const uint8_t* img, const uint8_t* img2, size_t img_stride, int W, int H, int w, int h, const BlurParams& bp,
+template <typename T>
+static bool blur3_fast_ok(const T* img, const T* img2, size_t img_stride, int W, int H, int w, int h, const BlurParams& bp,
                           const float* out, size_t out_stride)
 {
-    return w == W && h == H && bp.fixed3 && W % 4 == 0 && W >= 8 && H >= 2 && img_stride % 4 == 0 && out_stride % 4 == 0 &&
-           ((uintptr_t)img & 3) == 0 && ((uintptr_t)img2 & 3) == 0 && ((uintptr_t)out & 15) == 0;
+    return w == W && h == H && bp.fixed3 && W >= 8 && H >= 2 && quad_ok(img, img2, img_stride, W) && out_stride % 4 == 0 &&
+           ((uintptr_t)out & 15) == 0;
 }
 // true when launch_blur_resize (two_pass = false) will go through the tmp scratch for these operands
-bool blur_resize_needs_tmp(const uint8_t* img, const uint8_t* img2, size_t img_stride, int W, int H, int w, int h, BlurParams bp,
+template <typename T>
+bool blur_resize_needs_tmp(const T* img, const T* img2, size_t img_stride, int W, int H, int w, int h, BlurParams bp,
                            const float* out, size_t out_stride)
 {
-    return !blur3_fast_ok(img, img2 ? img2 : img, img_stride, W, H, w, h, bp, out, out_stride) && !blur_resize_is_fused(W, H, w, h, bp.ksize);
+    return !blur3_fast_ok(img, img2 ? img2 : img, img_stride, W, H, w, h, bp, out, out_stride) &&
+           !blur_resize_is_fused(W, H, w, h, bp.ksize, (int)sizeof(T));
 }
-void launch_blur_resize(hipStream_t st, const uint8_t* img, const uint8_t* img2, int split, size_t img_stride, int G, int W, int H, int w,
+template <typename T>
+void launch_blur_resize(hipStream_t st, const T* img, const T* img2, int split, size_t img_stride, int G, int W, int H, int w,
                         int h, BlurParams bp, float* tmp, size_t tmp_stride, float* out, size_t out_stride, bool two_pass)
 {
     if (!img2) { img2 = img; split = G; }
     if (blur3_fast_ok(img, img2, img_stride, W, H, w, h, bp, out, out_stride)) {
         dim3 grid((W / 4 + 63) / 64, ((H + 3) / 4 + 3) / 4, G);
-        hipLaunchKernelGGL(k_blur3_u8, grid, dim3(256), 0, st, img, img2, split, img_stride, W, H, out, out_stride);
+        hipLaunchKernelGGL(k_blur3<T>, grid, dim3(256), 0, st, img, img2, split, img_stride, W, H, out, out_stride);
         return;
     }
-    // rows are dword-addressable when W, the image stride and both bases are multiples of 4 (else the staging goes byte by byte)
-    const int dword_ok = (W % 4 == 0 && img_stride % 4 == 0 && ((uintptr_t)img & 3) == 0 && ((uintptr_t)img2 & 3) == 0) ? 1 : 0;
+    const int dword_ok = quad_ok(img, img2, img_stride, W);     // else the staging goes pixel by pixel
+    const int esize = (int)sizeof(T);
     const int pitch_w = staged_pitch_words(W, w, bp.ksize);
-    if (!two_pass && blur_resize_is_fused(W, H, w, h, bp.ksize)) {
-        const FusedPlan fp = fused_plan(W, H, w, h, bp, dword_ok);
+    if (!two_pass && blur_resize_is_fused(W, H, w, h, bp.ksize, esize)) {
+        const FusedPlan fp = fused_plan(W, H, w, h, bp, dword_ok, esize);
         const dim3 grid((w + 63) / 64, (h + fp.th - 1) / fp.th, G);
         switch (fused_path_of(bp, fp.pitch_w, dword_ok)) {
-        case FP_FAST5: hipLaunchKernelGGL(k_blur_resize_fused<FP_FAST5>, grid, dim3(256), fp.lds, st, img, img2, split, img_stride, W, H, w, h, bp, out, out_stride, fp.rows, fp.pitch_w, dword_ok, fp.th); break;
-        case FP_FAST13: hipLaunchKernelGGL(k_blur_resize_fused<FP_FAST13>, grid, dim3(256), fp.lds, st, img, img2, split, img_stride, W, H, w, h, bp, out, out_stride, fp.rows, fp.pitch_w, dword_ok, fp.th); break;
-        default: hipLaunchKernelGGL(k_blur_resize_fused<FP_GENERIC>, grid, dim3(256), fp.lds, st, img, img2, split, img_stride, W, H, w, h, bp, out, out_stride, fp.rows, fp.pitch_w, dword_ok, fp.th); break;
+        case FP_FAST5: hipLaunchKernelGGL((k_blur_resize_fused<T, FP_FAST5>), grid, dim3(256), fp.lds, st, img, img2, split, img_stride, W, H, w, h, bp, out, out_stride, fp.rows, fp.pitch_w, dword_ok, fp.th); break;
+        case FP_FAST13: hipLaunchKernelGGL((k_blur_resize_fused<T, FP_FAST13>), grid, dim3(256), fp.lds, st, img, img2, split, img_stride, W, H, w, h, bp, out, out_stride, fp.rows, fp.pitch_w, dword_ok, fp.th); break;
+        default: hipLaunchKernelGGL((k_blur_resize_fused<T, FP_GENERIC>), grid, dim3(256), fp.lds, st, img, img2, split, img_stride, W, H, w, h, bp, out, out_stride, fp.rows, fp.pitch_w, dword_ok, fp.th); break;
         }
         return;
     }
+    // the staged row block: rows_blk rows of pitch_w quads of esize-byte pixels
     int rows_blk = 16;
-    while (rows_blk > 4 && (size_t)rows_blk * pitch_w * 4 > 48 * 1024) rows_blk >>= 1;
-    if ((size_t)rows_blk * pitch_w * 4 <= 48 * 1024)
+    while (rows_blk > 4 && (size_t)rows_blk * pitch_w * 4 * esize > 48 * 1024) rows_blk >>= 1;
+    if ((size_t)rows_blk * pitch_w * 4 * esize <= 48 * 1024)
     {
         const int gx = (w + 63) / 64, nby = (H + rows_blk - 1) / rows_blk;
         const int gy = nby;                                               // one row block per workgroup (walking several measured slower: 69 vs 47 us)
-        const size_t lds_h = (size_t)((rows_blk * pitch_w + 1) & ~1) * 4 + (size_t)((bp.ksize + 4) & ~3) * 8;    // staged rows + tap pairs
-        hipLaunchKernelGGL(k_blur_resize_h, dim3(gx, gy, G), dim3(256), lds_h, st, img,
+        const size_t lds_h = (size_t)((rows_blk * pitch_w * esize + 1) & ~1) * 4 + (size_t)((bp.ksize + 4) & ~3) * 8;    // staged rows + tap pairs
+        hipLaunchKernelGGL(k_blur_resize_h<T>, dim3(gx, gy, G), dim3(256), lds_h, st, img,
                            img2, split, img_stride, W, H, w, bp, tmp, tmp_stride, rows_blk, pitch_w, dword_ok);
     }
     else
-        hipLaunchKernelGGL(k_blur_resize_h_direct, dim3((w + 63) / 64, ((H + 3) / 4 + 3) / 4, G), dim3(256), 0, st, img, img2, split, img_stride,
+        hipLaunchKernelGGL(k_blur_resize_h_direct<T>, dim3((w + 63) / 64, ((H + 3) / 4 + 3) / 4, G), dim3(256), 0, st, img, img2, split, img_stride,
                            W, H, w, bp, tmp, tmp_stride);
     hipLaunchKernelGGL(k_blur_resize_v, dim3((w + 63) / 64, (h + 3) / 4, G), dim3(256), 0, st, (const float*)tmp, tmp_stride, H, w, h,
                        bp, out, out_stride);
 }
+// the three source depths (mavflow_internal.h)
+#define MAV_BLUR_DEPTH(T)                                                                                                                    \
+    template bool blur_multi_ok<T>(const T*, const T*, size_t, int, int, int, int, BlurParams, const float*, size_t);                        \
+    template void launch_blur_multi<T>(hipStream_t, const T*, const T*, int, size_t, int, int, int, BlurJobs, bool);                          \
+    template bool blur_resize_needs_tmp<T>(const T*, const T*, size_t, int, int, int, int, BlurParams, const float*, size_t);                \
+    template void launch_blur_resize<T>(hipStream_t, const T*, const T*, int, size_t, int, int, int, int, int, BlurParams, float*, size_t,   \
+                                        float*, size_t, bool);
+MAV_BLUR_DEPTH(uint8_t)
+MAV_BLUR_DEPTH(uint16_t)
+MAV_BLUR_DEPTH(float)
+#undef MAV_BLUR_DEPTH
 
 // ------------------------------------------------------------------------------------------------------------
 // FarnebackPolyExp (A.4).  64x16 output tile per workgroup; the (64+2n) x (16+2n) source tile (edge-clamped,

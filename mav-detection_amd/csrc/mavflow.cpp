@@ -1458,7 +1458,8 @@ static int layer_sweeps(mav_ctx* c, hipStream_t st, int k, int g, const float* r
 // seq: `prev` is a run of g + 1 consecutive frames and pair s = (frame s, frame s + 1): every frame is blurred and expanded ONCE.
 // Otherwise, when the 2 g layer images are small (merge_frames), prev and next go through ONE blur and ONE expansion launch of 2 g
 // images instead of two of g: a group of one or two pairs is bound by launch latency, not by bytes.
-static void layer_expansions(mav_ctx* c, hipStream_t st, int k, const uint8_t* prev, const uint8_t* next, int g, bool seq, float* I, float* R,
+template <typename T>
+static void layer_expansions(mav_ctx* c, hipStream_t st, int k, const T* prev, const T* next, int g, bool seq, float* I, float* R,
                              const float** r0, const float** r1)
 {
     mav_ctx::WorkSet& w = c->ws;
@@ -1466,7 +1467,7 @@ static void layer_expansions(mav_ctx* c, hipStream_t st, int k, const uint8_t* p
     const Layer& l = c->layers[k];
     if (seq) {
         { ProfScope ps(c, K_BLUR_RESIZE, st);
-          launch_blur_resize(st, prev, nullptr, 0, n0, g + 1, c->W, c->H, l.w, l.h, blur_of(c, l), w.Htmp, c->htmp_stride, I, n0); }
+          launch_blur_resize<T>(st, prev, nullptr, 0, n0, g + 1, c->W, c->H, l.w, l.h, blur_of(c, l), w.Htmp, c->htmp_stride, I, n0); }
         { ProfScope ps(c, K_POLYEXP, st);
           launch_polyexp(st, I, n0, g + 1, l.w, l.h, c->pc, R, 5 * n0); }
         *r0 = R; *r1 = R + 5 * n0;
@@ -1484,11 +1485,11 @@ static void layer_expansions(mav_ctx* c, hipStream_t st, int k, const uint8_t* p
           launch_polyexp(st, I, n0, 2 * g, l.w, l.h, c->pc, R, 5 * n0); }
         return;
     }
-    const uint8_t* img[2] = {prev, next};
+    const T* img[2] = {prev, next};
     float* Rs[2] = {R, R1};
     for (int i = 0; i < 2; i++) {
         { ProfScope ps(c, K_BLUR_RESIZE, st);
-          launch_blur_resize(st, img[i], nullptr, 0, n0, g, c->W, c->H, l.w, l.h, blur_of(c, l), w.Htmp, c->htmp_stride, I, n0); }
+          launch_blur_resize<T>(st, img[i], nullptr, 0, n0, g, c->W, c->H, l.w, l.h, blur_of(c, l), w.Htmp, c->htmp_stride, I, n0); }
         { ProfScope ps(c, K_POLYEXP, st);
           launch_polyexp(st, I, n0, g, l.w, l.h, c->pc, Rs[i], 5 * n0); }
     }
@@ -1515,8 +1516,8 @@ static bool is_small_group(const mav_ctx* c, int g)
 // The layer images of layers k_lo .. k_hi for F frames (the first `split` from run prev, the rest from run img2; img2 == nullptr: one
 // run) into regions Ik(k) with slot stride sk(k): every layer blur_multi_ok accepts through ONE launch, the others (long Gaussians)
 // through the two-pass kernels in chunks the H x w scratch holds; then ALL their expansions through one launch (per MAV_MAX_JOBS layers).
-template <typename IkFn, typename RkFn, typename SkFn>
-static void pyramid_multi(mav_ctx* c, hipStream_t st, const uint8_t* prev, const uint8_t* img2, int split, int F, int k_lo, int k_hi, IkFn Ik,
+template <typename T, typename IkFn, typename RkFn, typename SkFn>
+static void pyramid_multi(mav_ctx* c, hipStream_t st, const T* prev, const T* img2, int split, int F, int k_lo, int k_hi, IkFn Ik,
                           RkFn Rk, SkFn sk)
 {
     mav_ctx::WorkSet& w = c->ws;
@@ -1540,7 +1541,7 @@ static void pyramid_multi(mav_ctx* c, hipStream_t st, const uint8_t* prev, const
             for (int f0 = 0; f0 < F; f0 += chunk) {
                 const int n = F - f0 < chunk ? F - f0 : chunk;
                 const bool from2 = img2 && f0 >= split;
-                const uint8_t* a = from2 ? img2 + (size_t)(f0 - split) * n0 : prev + (size_t)f0 * n0;
+                const T* a = from2 ? img2 + (size_t)(f0 - split) * n0 : prev + (size_t)f0 * n0;
                 launch_blur_resize(st, a, from2 ? nullptr : img2, from2 ? 0 : split - f0, n0, n, c->W, c->H, l.w, l.h, blur_of(c, l), w.Htmp, per,
                                    Ik(k) + (size_t)f0 * sk(k), sk(k));
             }
@@ -1556,11 +1557,12 @@ static void pyramid_multi(mav_ctx* c, hipStream_t st, const uint8_t* prev, const
 // DEEP LAYERS (kd .. top) of D pairs at once, on the compute stream; the flow of layer kd lands in deep.f[kd & 1], slot stride
 // 2 * c_stride[kd].  See mav_ctx::DeepSet.  Same tile functions on the same data as the per-group path: bit-identical flow.
 // flow_init: the top layer's initial flow of the D pairs (init_snap) or nullptr.
-static int deep_layers(mav_ctx* c, hipStream_t st, const uint8_t* prev, const uint8_t* next, int D, bool seq, const float* flow_init = nullptr)
+template <typename T>
+static int deep_layers(mav_ctx* c, hipStream_t st, const T* prev, const T* next, int D, bool seq, const float* flow_init = nullptr)
 {
     const int L = (int)c->layers.size(), kd = c->kd;
     const int F = seq ? D + 1 : 2 * D;
-    const uint8_t* img2 = seq ? nullptr : next;
+    const T* img2 = seq ? nullptr : next;
     const size_t base = c->c_off[kd];
     auto Ik = [&](int k) { return c->deep.I + (size_t)F * (c->c_off[k] - base); };
     auto Rk = [&](int k) { return c->deep.R + 5 * (size_t)F * (c->c_off[k] - base); };
@@ -1590,7 +1592,8 @@ static int deep_layers(mav_ctx* c, hipStream_t st, const uint8_t* prev, const ui
 // functions on the same data: bit-identical flow (tests/test_gpu_flow.py).
 // (Measured for such groups and not kept: the finest layer's images and expansions on a side stream underneath the coarse chain;
 // all sweeps of a layer in one launch of resident workgroups that hand M' over through flags -- HISTORY.md.)
-static int flow_group(mav_ctx* c, const uint8_t* prev, const uint8_t* next, int g, bool seq, float* flow_out, const float* deep_flow = nullptr,
+template <typename T>
+static int flow_group(mav_ctx* c, const T* prev, const T* next, int g, bool seq, float* flow_out, const float* deep_flow = nullptr,
                       size_t deep_stride = 0, const float* flow_init = nullptr)
 {
     mav_ctx::WorkSet& w = c->ws;
@@ -1603,7 +1606,7 @@ static int flow_group(mav_ctx* c, const uint8_t* prev, const uint8_t* next, int 
     int pw = deep_flow ? c->layers[c->kd].w : 0, ph = deep_flow ? c->layers[c->kd].h : 0;
     if (!deep_flow && is_small_group(c, g)) {
         const int F = seq ? g + 1 : 2 * g;                                // frames: one run of g + 1, or the prev run and the next run
-        const uint8_t* img2 = seq ? nullptr : next;
+        const T* img2 = seq ? nullptr : next;
         auto Ik = [&](int k) { return k ? w.Ic + (size_t)F * c->c_off[k] : w.I; };
         auto Rk = [&](int k) { return k ? w.Rc + 5 * (size_t)F * c->c_off[k] : w.R; };
         auto sk = [&](int k) { return k ? c->c_stride[k] : n0; };
@@ -1663,7 +1666,8 @@ static void snapshot_initial_flow(mav_ctx* c, const float* flow0, int n)
 // flow_init == nullptr: every pair starts from zero (mav_farneback_dev).  Otherwise the top layer's initial M of pair i comes from
 // flow_init[i] (mav_farneback_init_dev); every other layer as always.  The snapshot of a set of pairs is taken right before the first
 // launch that reads it and after every launch that writes flow of an earlier set: flow_init may be flow.
-static int farneback_run(mav_ctx* c, const uint8_t* prev, const uint8_t* next, int batch, const float* flow_init, float* flow)
+template <typename T>
+static int farneback_run(mav_ctx* c, const T* prev, const T* next, int batch, const float* flow_init, float* flow)
 {
     HIPCHK(hipSetDevice(c->device));
     CHK(ensure_workspace(c));
@@ -1716,11 +1720,30 @@ extern "C" int mav_farneback_init_dev(mav_ctx* c, const uint8_t* prev, const uin
         return fail(MAV_ERR_ARG, "mav_farneback_init_dev: flow_init and flow overlap without being the same field");
     return farneback_run(c, prev, next, batch, flow_init, flow);
 }
+// bytes per pixel of a MAV_DEPTH_* code; 0 for any other code
+static int depth_esize(int depth)
+{
+    return depth == MAV_DEPTH_8U ? 1 : depth == MAV_DEPTH_16U ? 2 : depth == MAV_DEPTH_32F ? 4 : 0;
+}
+extern "C" int mav_farneback_ex_dev(mav_ctx* c, const void* prev, const void* next, int depth, int batch, const float* flow_init, float* flow)
+{
+    if (!c || !prev || !next || !flow) return fail(MAV_ERR_ARG, "mav_farneback_ex_dev: NULL argument");
+    if (!depth_esize(depth)) return fail(MAV_ERR_ARG, "mav_farneback_ex_dev: depth %d is none of MAV_DEPTH_8U / 16U / 32F", depth);
+    if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "batch %d outside [1, %d]", batch, c->max_batch);
+    if (flow_init) {
+        const size_t n = (size_t)batch * 2 * c->n0;
+        if (flow_init != flow && flow_init < flow + n && flow < flow_init + n)
+            return fail(MAV_ERR_ARG, "mav_farneback_ex_dev: flow_init and flow overlap without being the same field");
+    }
+    if (depth == MAV_DEPTH_16U) return farneback_run(c, (const uint16_t*)prev, (const uint16_t*)next, batch, flow_init, flow);
+    if (depth == MAV_DEPTH_32F) return farneback_run(c, (const float*)prev, (const float*)next, batch, flow_init, flow);
+    return farneback_run(c, (const uint8_t*)prev, (const uint8_t*)next, batch, flow_init, flow);
+}
 extern "C" const float* mav_last_flow_dev(const mav_ctx* c) { return c ? c->last_flow : nullptr; }
 
 // The schedule a call of `batch` pairs takes with the options in effect, as one line of JSON (bench.py prints it and hashes it):
 // every option of mav_set_option, the group split and, per layer, how its sweeps run.
-extern "C" int mav_schedule_info(mav_ctx* c, int batch, char* buf, size_t cap)
+static int schedule_info(mav_ctx* c, int batch, int esize, char* buf, size_t cap)
 {
     if (!c || !buf || cap < 2) return fail(MAV_ERR_ARG, "mav_schedule_info: NULL argument");
     if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "batch %d outside [1, %d]", batch, c->max_batch);
@@ -1744,7 +1767,7 @@ extern "C" int mav_schedule_info(mav_ctx* c, int batch, char* buf, size_t cap)
         const SweepPlan p = plan_sweeps(c, k, (deep && k >= c->kd) ? D : g, l.w % 4 == 0 && c->fb.winsize / 2 == 6);
         snprintf(t, sizeof(t), "%s{\"layer\": %d, \"w\": %d, \"h\": %d, \"blur\": \"%s\", \"sweeps\": \"%s\", \"pairs_per_launch\": %d, \"bands\": %d}",
                  k ? ", " : "", k, l.w, l.h,
-                 (l.w == c->W && l.h == c->H) ? "3x3" : (blur_resize_is_fused(c->W, c->H, l.w, l.h, l.ksize) ? "fused" : "two-pass"),
+                 (l.w == c->W && l.h == c->H) ? "3x3" : (blur_resize_is_fused(c->W, c->H, l.w, l.h, l.ksize, esize) ? "fused" : "two-pass"),
                  mode_names[p.mode], p.mode == SW_COARSE_TWO ? p.half : (p.mode == SW_TWO_PAIRS ? 1 : p.sub), p.J);
         o += t;
     }
@@ -1752,6 +1775,12 @@ extern "C" int mav_schedule_info(mav_ctx* c, int batch, char* buf, size_t cap)
     if (o.size() + 1 > cap) return fail(MAV_ERR_ARG, "mav_schedule_info: buffer of %zu bytes too small (%zu needed)", cap, o.size() + 1);
     memcpy(buf, o.c_str(), o.size() + 1);
     return MAV_OK;
+}
+extern "C" int mav_schedule_info(mav_ctx* c, int batch, char* buf, size_t cap) { return schedule_info(c, batch, 1, buf, cap); }
+extern "C" int mav_schedule_info_ex(mav_ctx* c, int batch, int depth, char* buf, size_t cap)
+{
+    if (!depth_esize(depth)) return fail(MAV_ERR_ARG, "mav_schedule_info_ex: depth %d is none of MAV_DEPTH_8U / 16U / 32F", depth);
+    return schedule_info(c, batch, depth_esize(depth), buf, cap);
 }
 
 // ---- detection ---------------------------------------------------------------------------------------------
@@ -2109,18 +2138,19 @@ struct DevBuf {
 };
 // The two frame batches of a host-pointer call -> device.  When the caller's batches are views of one run of batch + 1 frames
 // (next == prev + one frame) the run crosses PCIe once and keeps that layout on the device, which mav_farneback_dev recognises.
-static int upload_frames(mav_ctx* c, const uint8_t* prev, const uint8_t* next, int batch, DevBuf& dp, DevBuf& dn, const uint8_t** dprev,
-                         const uint8_t** dnext)
+// esize: bytes per pixel (the frame run is recognised in bytes, whatever the depth).
+static int upload_frames(mav_ctx* c, const void* prev, const void* next, int batch, int esize, DevBuf& dp, DevBuf& dn, const void** dprev,
+                         const void** dnext)
 {
-    const size_t n = c->n0 * batch;
-    if (next == prev + c->n0) {
-        CHK(dp.upload(c, prev, n + c->n0));
+    const size_t fb = c->n0 * esize, n = fb * batch;
+    if ((const char*)next == (const char*)prev + fb) {
+        CHK(dp.upload(c, prev, n + fb));
         CHK(dn.alloc(c, 1));                              // keeps the staging slots of the two call forms aligned
-        *dprev = dp.as<uint8_t>(); *dnext = dp.as<uint8_t>() + c->n0;
+        *dprev = dp.p; *dnext = dp.as<char>() + fb;
         return MAV_OK;
     }
     CHK(dp.upload(c, prev, n)); CHK(dn.upload(c, next, n));
-    *dprev = dp.as<uint8_t>(); *dnext = dn.as<uint8_t>();
+    *dprev = dp.p; *dnext = dn.p;
     return MAV_OK;
 }
 static int download(mav_ctx* c, void* dst, const void* src, size_t bytes)
@@ -2145,9 +2175,9 @@ extern "C" int mav_farneback(mav_ctx* c, const uint8_t* prev, const uint8_t* nex
     if (!prev || !next || !flow) return fail(MAV_ERR_ARG, "mav_farneback: NULL argument");
     const size_t n = c->n0 * batch;
     DevBuf dp, dn, df;
-    const uint8_t *dprev, *dnext;
-    CHK(upload_frames(c, prev, next, batch, dp, dn, &dprev, &dnext)); CHK(df.alloc(c, n * 2 * sizeof(float)));
-    CHK(mav_farneback_dev(c, dprev, dnext, batch, df.as<float>()));
+    const void *dprev, *dnext;
+    CHK(upload_frames(c, prev, next, batch, 1, dp, dn, &dprev, &dnext)); CHK(df.alloc(c, n * 2 * sizeof(float)));
+    CHK(mav_farneback_dev(c, (const uint8_t*)dprev, (const uint8_t*)dnext, batch, df.as<float>()));
     CHK(download(c, flow, df.p, n * 2 * sizeof(float)));
     return mav_sync(c);
 }
@@ -2158,9 +2188,24 @@ extern "C" int mav_farneback_init(mav_ctx* c, const uint8_t* prev, const uint8_t
     if (!prev || !next || !flow_init || !flow) return fail(MAV_ERR_ARG, "mav_farneback_init: NULL argument");
     const size_t n = c->n0 * batch;
     DevBuf dp, dn, df;
-    const uint8_t *dprev, *dnext;
-    CHK(upload_frames(c, prev, next, batch, dp, dn, &dprev, &dnext)); CHK(df.upload(c, flow_init, n * 2 * sizeof(float)));
-    CHK(mav_farneback_init_dev(c, dprev, dnext, batch, df.as<float>(), df.as<float>()));      // in place on the device
+    const void *dprev, *dnext;
+    CHK(upload_frames(c, prev, next, batch, 1, dp, dn, &dprev, &dnext)); CHK(df.upload(c, flow_init, n * 2 * sizeof(float)));
+    CHK(mav_farneback_init_dev(c, (const uint8_t*)dprev, (const uint8_t*)dnext, batch, df.as<float>(), df.as<float>()));      // in place on the device
+    CHK(download(c, flow, df.p, n * 2 * sizeof(float)));
+    return mav_sync(c);
+}
+extern "C" int mav_farneback_ex(mav_ctx* c, const void* prev, const void* next, int depth, int batch, const float* flow_init, float* flow)
+{
+    if (c && !depth_esize(depth)) return fail(MAV_ERR_ARG, "mav_farneback_ex: depth %d is none of MAV_DEPTH_8U / 16U / 32F", depth);
+    CHK(check_batch(c, batch, "mav_farneback_ex"));
+    if (!prev || !next || !flow) return fail(MAV_ERR_ARG, "mav_farneback_ex: NULL argument");
+    const size_t n = c->n0 * batch;
+    DevBuf dp, dn, df;
+    const void *dprev, *dnext;
+    CHK(upload_frames(c, prev, next, batch, depth_esize(depth), dp, dn, &dprev, &dnext));
+    if (flow_init) CHK(df.upload(c, flow_init, n * 2 * sizeof(float)));
+    else CHK(df.alloc(c, n * 2 * sizeof(float)));
+    CHK(mav_farneback_ex_dev(c, dprev, dnext, depth, batch, flow_init ? df.as<float>() : nullptr, df.as<float>()));      // in place on the device
     CHK(download(c, flow, df.p, n * 2 * sizeof(float)));
     return mav_sync(c);
 }
@@ -2544,7 +2589,11 @@ static int process_host(mav_ctx* c, const char* fn, const uint8_t* prev, const u
     DevBuf dp, dn, ds, dflow, dres, dmf, dmd, dsky, dom, ddt, df0, dphi;      // the always-present buffers take the first blocks
     const uint8_t *dprev = nullptr, *dnext = nullptr;
     if (flow_in) CHK(dflow.upload(c, flow_in, n * 2 * sizeof(float)));
-    else { CHK(upload_frames(c, prev, next, batch, dp, dn, &dprev, &dnext)); CHK(dflow.alloc(c, n * 2 * sizeof(float))); }
+    else {
+        const void *vp, *vn;
+        CHK(upload_frames(c, prev, next, batch, 1, dp, dn, &vp, &vn)); CHK(dflow.alloc(c, n * 2 * sizeof(float)));
+        dprev = (const uint8_t*)vp; dnext = (const uint8_t*)vn;
+    }
     CHK(ds.upload(c, samples, sizeof(uint32_t) * 4 * (size_t)f.n_pairs * batch));
     CHK(dres.alloc(c, sizeof(mav_result) * batch));
     if (mask_fixed) CHK(dmf.alloc(c, n));
@@ -2887,24 +2936,36 @@ extern "C" int mav_stage_coefficients(mav_ctx* c, int k, float* g, float* xg, fl
     return MAV_OK;
 }
 
-static int stage_blur_resize(mav_ctx* c, const uint8_t* img, int k, bool two_pass, float* out)
+static int stage_blur_resize(mav_ctx* c, const void* img, int depth, int k, bool two_pass, float* out)
 {
     const Layer* l;
+    if (c && !depth_esize(depth)) return fail(MAV_ERR_ARG, "mav_stage_blur_resize_ex: depth %d is none of MAV_DEPTH_8U / 16U / 32F", depth);
     CHK(layer_of(c, k, &l));
     if (!img || !out) return fail(MAV_ERR_ARG, "mav_stage_blur_resize: NULL argument");
     const size_t n = (size_t)l->w * l->h;
     // the two-pass form's H x w scratch (one frame: 4 bytes per pixel) is a staging block of this call: a diagnostic hook never
     // allocates the Farneback workspace (GBs at 1080p / 4K) nor freezes "deep_frac"
     DevBuf di, dout, dtmp;
-    CHK(di.upload(c, img, c->n0)); CHK(dout.alloc(c, n * sizeof(float))); CHK(dtmp.alloc(c, c->htmp_stride * sizeof(float)));
-    launch_blur_resize(c->stream, di.as<uint8_t>(), nullptr, 0, c->n0, 1, c->W, c->H, l->w, l->h, blur_of(c, *l), dtmp.as<float>(), c->htmp_stride,
-                       dout.as<float>(), n, two_pass);
+    CHK(di.upload(c, img, c->n0 * depth_esize(depth))); CHK(dout.alloc(c, n * sizeof(float))); CHK(dtmp.alloc(c, c->htmp_stride * sizeof(float)));
+    if (depth == MAV_DEPTH_16U)
+        launch_blur_resize<uint16_t>(c->stream, di.as<uint16_t>(), nullptr, 0, c->n0, 1, c->W, c->H, l->w, l->h, blur_of(c, *l), dtmp.as<float>(),
+                           c->htmp_stride, dout.as<float>(), n, two_pass);
+    else if (depth == MAV_DEPTH_32F)
+        launch_blur_resize<float>(c->stream, di.as<float>(), nullptr, 0, c->n0, 1, c->W, c->H, l->w, l->h, blur_of(c, *l), dtmp.as<float>(),
+                           c->htmp_stride, dout.as<float>(), n, two_pass);
+    else
+        launch_blur_resize<uint8_t>(c->stream, di.as<uint8_t>(), nullptr, 0, c->n0, 1, c->W, c->H, l->w, l->h, blur_of(c, *l), dtmp.as<float>(),
+                           c->htmp_stride, dout.as<float>(), n, two_pass);
     CHK(check_launch("blur_resize"));
     CHK(download(c, out, dout.p, n * sizeof(float)));
     return mav_sync(c);
 }
-extern "C" int mav_stage_blur_resize(mav_ctx* c, const uint8_t* img, int k, float* out) { return stage_blur_resize(c, img, k, false, out); }
-extern "C" int mav_stage_blur_resize_two_pass(mav_ctx* c, const uint8_t* img, int k, float* out) { return stage_blur_resize(c, img, k, true, out); }
+extern "C" int mav_stage_blur_resize(mav_ctx* c, const uint8_t* img, int k, float* out) { return stage_blur_resize(c, img, MAV_DEPTH_8U, k, false, out); }
+extern "C" int mav_stage_blur_resize_two_pass(mav_ctx* c, const uint8_t* img, int k, float* out) { return stage_blur_resize(c, img, MAV_DEPTH_8U, k, true, out); }
+extern "C" int mav_stage_blur_resize_ex(mav_ctx* c, const void* img, int depth, int k, int two_pass, float* out)
+{
+    return stage_blur_resize(c, img, depth, k, two_pass != 0, out);
+}
 extern "C" int mav_stage_polyexp(mav_ctx* c, const float* I, int k, float* R)
 {
     const Layer* l;

@@ -51,20 +51,26 @@ struct BlurJobs { int n, pad; BlurJob j[MAV_MAX_JOBS]; };
 // All take G slots; slot s reads/writes base + s*stride (strides in elements).
 // G images from two runs: the first `split` from img, the rest from img2 (same stride); img2 == nullptr: one run.  Layers with a
 // short Gaussian (blur_resize_is_fused) go through one fused kernel and never touch tmp unless two_pass is set.
-void launch_blur_resize(hipStream_t st, const uint8_t* img, const uint8_t* img2, int split, size_t img_stride, int G, int W, int H, int w,
+// The layer-image functions take frames of one of three depths, T = uint8_t, uint16_t or float (instantiated in kernels_flow.hip);
+// esize = sizeof(T).
+template <typename T>
+void launch_blur_resize(hipStream_t st, const T* img, const T* img2, int split, size_t img_stride, int G, int W, int H, int w,
                         int h, BlurParams bp, float* tmp /* G x H x w scratch for the separable passes */, size_t tmp_stride, float* out,
                         size_t out_stride, bool two_pass = false);
-bool blur_resize_is_fused(int W, int H, int w, int h, int ksize);
-bool blur_resize_needs_tmp(const uint8_t* img, const uint8_t* img2, size_t img_stride, int W, int H, int w, int h, BlurParams bp,
+bool blur_resize_is_fused(int W, int H, int w, int h, int ksize, int esize = 1);
+template <typename T>
+bool blur_resize_needs_tmp(const T* img, const T* img2, size_t img_stride, int W, int H, int w, int h, BlurParams bp,
                            const float* out, size_t out_stride);
 void launch_polyexp(hipStream_t st, const float* I, size_t I_stride, int G, int w, int h, const PolyCoef& pc, float* R,
                     size_t R_stride);
 // jobs.j[i]: I, R, I_stride, R_stride, w, h filled by the caller; G images per job
 void launch_polyexp_multi(hipStream_t st, PolyJobs jobs, int G, const PolyCoef& pc);
 // jobs.j[i]: out, out_stride, bp, w, h filled by the caller, for layers blur_multi_ok accepts
-bool blur_multi_ok(const uint8_t* img, const uint8_t* img2, size_t img_stride, int W, int H, int w, int h, BlurParams bp, const float* out,
+template <typename T>
+bool blur_multi_ok(const T* img, const T* img2, size_t img_stride, int W, int H, int w, int h, BlurParams bp, const float* out,
                    size_t out_stride);
-void launch_blur_multi(hipStream_t st, const uint8_t* img, const uint8_t* img2, int split, size_t img_stride, int G, int W, int H, BlurJobs jobs,
+template <typename T>
+void launch_blur_multi(hipStream_t st, const T* img, const T* img2, int split, size_t img_stride, int G, int W, int H, BlurJobs jobs,
                        bool split_by_path = false /* one launch per tile code (fused_path_of) instead of one for all jobs */);
 // flow_prev == nullptr: zero initial flow. Otherwise flow = resize(prev (ph x pw x 2))*mul, evaluated inline.
 void launch_update_matrices(hipStream_t st, const float* R0, const float* R1, size_t R_stride, const float* flow_prev,

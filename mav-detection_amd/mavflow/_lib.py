@@ -55,9 +55,14 @@ EXPORTS = [
     "mav_tpr_fpr_counts_dev", "mav_bgr2gray_dev", "mav_png_unfilter", "mav_comm_count",
     "mav_marker_query", "mav_frame_step_dev", "mav_frame_step_post", "mav_frame_step_wait", "mav_worker_drain", "mav_worker_wait_enqueued",
     "mav_farneback_init", "mav_farneback_init_dev", "mav_stage_update_matrices_from", "mav_stage_initial_flow",
+    "mav_farneback_ex", "mav_farneback_ex_dev", "mav_stage_blur_resize_ex", "mav_schedule_info_ex",
     "mav_render", "mav_render_dev", "mav_last_render", "mav_flow_to_color", "mav_colormap_jet",
     "mav_overlay", "mav_overlay_dev", "mav_last_overlay",
 ]
+
+# Frame depths of the _ex entry points (cv2's depth codes) by numpy dtype.  uint8 frames keep going through the u8 symbols.
+DEPTH_8U, DEPTH_16U, DEPTH_32F = 0, 2, 5
+DEPTHS = {np.dtype(np.uint8): DEPTH_8U, np.dtype(np.uint16): DEPTH_16U, np.dtype(np.float32): DEPTH_32F}
 
 OPTFLOW_USE_INITIAL_FLOW = 4                    # FbParams.flags bit (cv2.OPTFLOW_USE_INITIAL_FLOW): see Context.farneback(initial_flow=)
 
@@ -196,6 +201,10 @@ def load(path: str | None = None) -> C.CDLL:
     lib.mav_stage_blur_iter.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp]
     lib.mav_stage_update_matrices_from.argtypes = [vp, vp, vp, vp, C.c_int, vp]
     lib.mav_stage_initial_flow.argtypes = [vp, vp, C.c_int, vp]
+    lib.mav_farneback_ex.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp]
+    lib.mav_farneback_ex_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp]
+    lib.mav_stage_blur_resize_ex.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
+    lib.mav_schedule_info_ex.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
     # ctx, flow, foe, omega, dt, frame0, sky, batch, thr params, img_result, img_flow, img_phi
     rn = [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(ThrParams), vp, vp, vp]
     lib.mav_render.argtypes = rn
@@ -241,6 +250,14 @@ def thr_defaults() -> ThrParams:
     p = ThrParams()
     load().mav_thr_defaults(C.byref(p))
     return p
+
+
+def _depth_of(dtype, name="frames") -> int:
+    """MAV_DEPTH_* code of a frame dtype; ValueError naming the accepted dtypes for any other."""
+    d = DEPTHS.get(np.dtype(dtype))
+    if d is None:
+        raise ValueError(f"{name}: expected uint8, uint16 or float32 frames (float64 is narrowed to float32), got {np.dtype(dtype)}")
+    return d
 
 
 def _ptr(a):
@@ -454,11 +471,15 @@ class Context:
         check(self.lib.mav_membw_probe(self.h, int(bytes_per_buffer), int(reps), C.byref(g)))
         return g.value
 
-    def schedule_info(self, batch: int) -> dict:
-        """The schedule a call of `batch` pairs takes with the options in effect (every option, group split, per-layer plan)."""
+    def schedule_info(self, batch: int, dtype=None) -> dict:
+        """The schedule a call of `batch` pairs takes with the options in effect (every option, group split, per-layer plan).
+        dtype: the frames' dtype (uint8 / uint16 / float32) -- the per-layer blur form depends on it; None = uint8 (mav_schedule_info)."""
         import json
         buf = C.create_string_buffer(8192)
-        check(self.lib.mav_schedule_info(self.h, int(batch), buf, len(buf)))
+        if dtype is None:
+            check(self.lib.mav_schedule_info(self.h, int(batch), buf, len(buf)))
+        else:
+            check(self.lib.mav_schedule_info_ex(self.h, int(batch), _depth_of(dtype), buf, len(buf)))
         return json.loads(buf.value.decode())
 
     def mem_info(self) -> dict:
@@ -511,6 +532,19 @@ class Context:
             raise ValueError(f"{name}: expected uint8, got {a.dtype}")
         return np.ascontiguousarray(a)
 
+    def _frames(self, a, name):
+        """Frames of the Farneback entry points: (batch, H, W) uint8, uint16 or float32, C-contiguous; float64 is rounded to float32
+        on the host (cv2's convertTo(CV_32F)).  Any other dtype is a ValueError."""
+        a = np.asarray(a)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3 or a.shape[1:] != (self.H, self.W):
+            raise ValueError(f"{name}: expected (batch, {self.H}, {self.W}) frames, got {a.shape}")
+        if a.dtype == np.float64:
+            a = a.astype(np.float32)
+        _depth_of(a.dtype, name)
+        return np.ascontiguousarray(a)
+
     def _flows(self, a, B, name):
         """(H, W, 2) for a batch of one, or (B, H, W, 2): float32, C-contiguous."""
         a = np.asarray(a)
@@ -525,14 +559,21 @@ class Context:
     def farneback(self, prev, nxt, initial_flow=None) -> np.ndarray:
         """cv2.calcOpticalFlowFarneback for a batch of pairs -> (B, H, W, 2) float32.  initial_flow: None starts every pair from zero;
         an (H, W, 2) field (one pair) or (B, H, W, 2) fields are the starting flow of each pair, as cv2 takes `flow` with
-        OPTFLOW_USE_INITIAL_FLOW set (mav_farneback_init)."""
-        prev, nxt = self._imgs(prev, "prev"), self._imgs(nxt, "next")
+        OPTFLOW_USE_INITIAL_FLOW set (mav_farneback_init).  Frames: uint8, uint16 or float32 (float64 is narrowed on the host, as
+        cv2's convertTo does), prev and next of ONE dtype -- unlike cv2, which converts each frame on its own; no rescaling."""
+        prev, nxt = np.asarray(prev), np.asarray(nxt)
+        if prev.dtype != nxt.dtype:
+            raise ValueError(f"prev and next differ in dtype ({prev.dtype} vs {nxt.dtype})")
+        prev, nxt = self._frames(prev, "prev"), self._frames(nxt, "next")
         if prev.shape != nxt.shape:
             raise ValueError("prev and next differ in shape")
         B = prev.shape[0]
         init = None if initial_flow is None else self._flows(initial_flow, B, "initial_flow")
         flow = _pinned.empty(self, (B, self.H, self.W, 2), np.float32)
-        if init is None:
+        if prev.dtype != np.uint8:
+            check(self.lib.mav_farneback_ex(self.h, _ptr(prev), _ptr(nxt), DEPTHS[prev.dtype], B, None if init is None else _ptr(init),
+                                            _ptr(flow)))
+        elif init is None:
             check(self.lib.mav_farneback(self.h, _ptr(prev), _ptr(nxt), B, _ptr(flow)))
         else:
             check(self.lib.mav_farneback_init(self.h, _ptr(prev), _ptr(nxt), B, _ptr(init), _ptr(flow)))
@@ -543,23 +584,32 @@ class Context:
             flow = calcOpticalFlowFarneback(f[i], f[i + 1], flow, ..., flags | OPTFLOW_USE_INITIAL_FLOW)
         pair i starts from pair i - 1's flow, pair 0 from initial_flow ((H, W, 2) float32) or from zero when it is None.  The run is
         uploaded once, the n one-pair calls keep their input and output flow on the device, and one download brings all n back."""
-        frames = self._imgs(frames, "frames")
+        frames = self._frames(frames, "frames")
         n = frames.shape[0] - 1
         if n < 1:
             raise ValueError("a chain needs at least two frames")
         init = None if initial_flow is None else self._flows(initial_flow, 1, "initial_flow")
-        fbytes, px = self.H * self.W * 2 * 4, self.H * self.W
+        fbytes, px = self.H * self.W * 2 * 4, self.H * self.W * frames.itemsize
         d_frames = self.alloc(frames.nbytes).upload(frames)
         d_flow = self.alloc(n * fbytes)
+        depth = DEPTHS[frames.dtype]
+
+        def run(i, f_init, f_out):                    # pair (frame i, frame i + 1): u8 through the u8 symbols, as before
+            a, b = d_frames.ptr + i * px, d_frames.ptr + (i + 1) * px
+            if depth != DEPTH_8U:
+                check(self.lib.mav_farneback_ex_dev(self.h, a, b, depth, 1, f_init, f_out))
+            elif f_init is None:
+                check(self.lib.mav_farneback_dev(self.h, a, b, 1, f_out))
+            else:
+                check(self.lib.mav_farneback_init_dev(self.h, a, b, 1, f_init, f_out))
         try:
             if init is None:                          # zero start: the flags = 0 call (bit-identical to an all-zero initial flow)
-                check(self.lib.mav_farneback_dev(self.h, d_frames.ptr, d_frames.ptr + px, 1, d_flow.ptr))
+                run(0, None, d_flow.ptr)
             else:
                 check(self.lib.mav_memcpy_h2d(self.h, d_flow.ptr, _ptr(init), fbytes))
-                check(self.lib.mav_farneback_init_dev(self.h, d_frames.ptr, d_frames.ptr + px, 1, d_flow.ptr, d_flow.ptr))
+                run(0, d_flow.ptr, d_flow.ptr)
             for i in range(1, n):
-                check(self.lib.mav_farneback_init_dev(self.h, d_frames.ptr + i * px, d_frames.ptr + (i + 1) * px, 1,
-                                                      d_flow.ptr + (i - 1) * fbytes, d_flow.ptr + i * fbytes))
+                run(i, d_flow.ptr + (i - 1) * fbytes, d_flow.ptr + i * fbytes)
             return d_flow.download(np.float32, (n, self.H, self.W, 2))
         finally:
             self.sync()
@@ -571,7 +621,7 @@ class Context:
         the library are views of the one array (next = prev + one frame), which it recognises: the run is uploaded once and every
         frame is blurred and expanded once instead of twice.  Same flow, bit for bit, as farneback(frames[:-1], frames[1:]) on
         separate copies."""
-        frames = self._imgs(frames, "frames")
+        frames = self._frames(frames, "frames")
         if frames.shape[0] < 2:
             raise ValueError("a sequence needs at least two frames")
         return self.farneback(frames[:-1], frames[1:])
@@ -893,9 +943,15 @@ class Context:
         check(self.lib.mav_memcpy_d2h(self.h, _ptr(out), p + pair * out.nbytes, out.nbytes))
         return out
 
-    def farneback_dev(self, prev_ptr, next_ptr, batch, flow_ptr, flow_init_ptr=None):
+    def farneback_dev(self, prev_ptr, next_ptr, batch, flow_ptr, flow_init_ptr=None, depth=None):
         """Enqueue only.  flow_init_ptr: None = zero start (mav_farneback_dev); a device pointer (it may equal flow_ptr) = the pairs'
-        initial flow (mav_farneback_init_dev)."""
+        initial flow (mav_farneback_init_dev).  depth: the frames' dtype (uint8 / uint16 / float32) or a MAV_DEPTH_* code; None =
+        uint8.  Any depth but uint8 goes through mav_farneback_ex_dev."""
+        if depth is not None:
+            d = depth if isinstance(depth, int) and not isinstance(depth, bool) else _depth_of(depth)
+            if d != DEPTH_8U:
+                check(self.lib.mav_farneback_ex_dev(self.h, prev_ptr, next_ptr, d, batch, flow_init_ptr, flow_ptr))
+                return
         if flow_init_ptr is None:
             check(self.lib.mav_farneback_dev(self.h, prev_ptr, next_ptr, batch, flow_ptr))
         else:
@@ -993,9 +1049,17 @@ class Context:
         return dict(g=g, xg=xg, xxg=xxg, ig=ig, blur=blur)
 
     def stage_blur_resize(self, img, k, two_pass=False):
-        img = _arr(img, np.uint8, (self.H, self.W), "img")
+        """Layer image k of one frame (uint8, uint16 or float32; float64 is narrowed on the host)."""
+        img = np.asarray(img)
+        if img.dtype == np.float64:
+            img = img.astype(np.float32)
+        depth = _depth_of(img.dtype, "img")
+        img = _arr(img, img.dtype, (self.H, self.W), "img")
         w, h, _, _ = self.layer_dims(k)
         out = np.empty((h, w), np.float32)
+        if depth != DEPTH_8U:
+            check(self.lib.mav_stage_blur_resize_ex(self.h, _ptr(img), depth, k, int(bool(two_pass)), _ptr(out)))
+            return out
         fn = self.lib.mav_stage_blur_resize_two_pass if two_pass else self.lib.mav_stage_blur_resize
         check(fn(self.h, _ptr(img), k, _ptr(out)))
         return out
