@@ -689,112 +689,126 @@ extern "C" int mav_create(mav_ctx** out, int device, int W, int H, int max_batch
 }
 
 // ---- options: every scheduling / tuning switch of the library lives here (no environment variables) -----------------------------
-struct OptionDesc { const char* name; long lo, hi; };
-static const OptionDesc kOptions[] = {
-    {"group", 1, 1 << 20}, {"group_fine", 0, 1 << 20}, {"bands", 0, 8}, {"pairs_in_flight", 1, 2}, {"band_mb", 8, 1 << 20},
-    {"coarse_cache_mb", 0, 1 << 20}, {"coarse_half", 0, 1 << 20}, {"share_m", 0, 1}, {"share_frames", 0, 1}, {"strip", 0, 1 << 20},
-    {"phi_screen", 0, 1}, {"phi_yloop", 0, 1 << 20}, {"small_batch", 0, 1}, {"sweep_write_through", -1, 1}, {"deep_batch", 0, 1},
-    {"coarse_bands", 0, 1}, {"band_phase", 0, 64}, {"band_skew", -1, 64}, {"deep_frac", 1, 1 << 20},
-};
-static long* option_slot(mav_ctx* c, const char* name, long* tmp)
+// The options that do more than store a value:
+static int set_group(mav_ctx* c, long value)
 {
-    // int / bool members behind one long-typed view: *tmp carries the value, write_back stores it
-    struct { const char* n; long v; } cur[] = {
-        {"group", c->group}, {"group_fine", c->group_fine}, {"bands", c->bands}, {"pairs_in_flight", c->pairs_in_flight},
-        {"band_mb", c->pif_band_mb}, {"coarse_cache_mb", c->coarse_cache_mb}, {"coarse_half", c->coarse_half}, {"share_m", c->share_m},
-        {"share_frames", c->share_frames}, {"strip", c->strip}, {"phi_screen", c->phi_screen}, {"phi_yloop", c->phi_yloop},
-        {"small_batch", c->small_batch}, {"sweep_write_through", c->sweep_wt}, {"deep_batch", c->deep_batch}, {"coarse_bands", c->coarse_bands}, {"band_phase", c->band_phase}, {"band_skew", c->band_skew}, {"deep_frac", c->deep_frac},
-    };
-    for (auto& e : cur) if (!strcmp(e.n, name)) { *tmp = e.v; return tmp; }
+    const int g = value > c->max_batch ? c->max_batch : (int)value;
+    HIPCHK(hipSetDevice(c->device));
+    CHK(sync_all_streams(c));
+    if (g == c->group) return MAV_OK;
+    if (!c->ws_ready) { c->group = g; c->small_g = small_group_cap(c, g); return MAV_OK; }    // nothing allocated yet: the plan changes
+    return alloc_group(c, g);
+}
+static int set_group_fine(mav_ctx* c, long value) { c->group_fine = (int)value; c->group_fine_set = true; return MAV_OK; }
+static int set_bands(mav_ctx* c, long value)             // 0 = back to automatic
+{
+    c->bands_set = value > 0;
+    c->bands = value > 0 ? (int)value : c->bands_auto;
+    return MAV_OK;
+}
+static int set_deep_frac(mav_ctx* c, long value)
+{
+    if (c->ws_ready) return fail(MAV_ERR_STATE, "deep_frac must be set before the first call that computes flow");
+    c->deep_frac = (int)value; c->kd = 0;
+    for (int k = (int)c->layers.size() - 1; k >= 1; k--)
+        if ((size_t)c->layers[k].w * c->layers[k].h * (size_t)value <= c->n0) c->kd = k; else break;
+    return MAV_OK;
+}
+static int set_inline_uploads(mav_ctx* c, long value)
+{
+    if (value < 0 || value > 1) return fail(MAV_ERR_ARG, "option 'inline_uploads' must be 0 or 1, got %ld", value);
+    HIPCHK(hipSetDevice(c->device));
+    if (c->copy_stream) HIPCHK(hipStreamSynchronize(c->copy_stream));      // nothing of the old mode is left in flight
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->inline_uploads = value != 0;
+    return MAV_OK;
+}
+static int set_stream_priority(mav_ctx* c, long value)
+{
+    // The HIP runtime maps streams onto a pool of (by default four) hardware queues PER PRIORITY CLASS, least-used first; which
+    // queue a new stream gets depends on every stream the process has ever made.  Lanes -- contexts that take a stream of small calls
+    // in turn and must not share a queue (pipeline.py) -- ask for a class of their own: -1 = high.  The context's compute stream is
+    // re-created in that class; nothing may be in flight (the call drains it).
+    int lo = 0, hi = 0;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));            // lo = least (numerically largest), hi = greatest
+    if (value < hi || value > lo) return fail(MAV_ERR_ARG, "option 'stream_priority' must be in [%d, %d], got %ld", hi, lo, value);
+    if ((int)value == c->stream_priority) return MAV_OK;
+    CHK(mav_worker_drain(c));
+    CHK(sync_all_streams(c));
+    if (c->copy_stream) HIPCHK(hipStreamSynchronize(c->copy_stream));
+    hipStream_t fresh = nullptr;
+    HIPCHK(hipStreamCreateWithPriority(&fresh, hipStreamNonBlocking, (int)value));
+    HIPCHK(hipStreamDestroy(c->stream));
+    c->stream = fresh;
+    c->stream_priority = (int)value;
+    return MAV_OK;
+}
+static int set_upload_threads(mav_ctx* c, long value)
+{
+    if (c->stager) return fail(MAV_ERR_STATE, "upload_threads must be set before the first mav_upload_gather call");
+    c->upload_threads = (int)value;
+    return MAV_OK;
+}
+// One row per option: its name, its range, the member behind it (an int or a bool), whether it is part of the launch schedule --
+// mav_schedule_info prints exactly those, in this order (bench.py hashes the line) -- and, for the options above, the function that
+// stores it.  mav_get_option, mav_set_option and mav_schedule_info all go through this table: a new option is one row plus its use.
+struct Option {
+    const char* name;
+    long lo, hi;
+    int mav_ctx::*i;
+    bool mav_ctx::*b;
+    bool in_schedule;
+    int (*set)(mav_ctx*, long);
+};
+static const long kAny = 1L << 40;           // a range the option's own function checks (it depends on the device, or has a text of its own)
+static const Option kOptions[] = {
+    {"group", 1, 1 << 20, &mav_ctx::group, nullptr, true, set_group},
+    {"group_fine", 0, 1 << 20, &mav_ctx::group_fine, nullptr, true, set_group_fine},
+    {"bands", 0, 8, &mav_ctx::bands, nullptr, true, set_bands},
+    {"pairs_in_flight", 1, 2, &mav_ctx::pairs_in_flight, nullptr, true, nullptr},
+    {"band_mb", 8, 1 << 20, &mav_ctx::pif_band_mb, nullptr, true, nullptr},
+    {"coarse_cache_mb", 0, 1 << 20, &mav_ctx::coarse_cache_mb, nullptr, true, nullptr},
+    {"coarse_half", 0, 1 << 20, &mav_ctx::coarse_half, nullptr, true, nullptr},
+    {"share_m", 0, 1, nullptr, &mav_ctx::share_m, true, nullptr},
+    {"share_frames", 0, 1, nullptr, &mav_ctx::share_frames, true, nullptr},
+    {"strip", 0, 1 << 20, &mav_ctx::strip, nullptr, true, nullptr},
+    {"phi_screen", 0, 1, nullptr, &mav_ctx::phi_screen, true, nullptr},
+    {"phi_yloop", 0, 1 << 20, &mav_ctx::phi_yloop, nullptr, true, nullptr},
+    {"small_batch", 0, 1, nullptr, &mav_ctx::small_batch, true, nullptr},
+    {"sweep_write_through", -1, 1, &mav_ctx::sweep_wt, nullptr, true, nullptr},
+    {"deep_batch", 0, 1, nullptr, &mav_ctx::deep_batch, true, nullptr},
+    {"coarse_bands", 0, 1, nullptr, &mav_ctx::coarse_bands, true, nullptr},
+    {"band_phase", 0, 64, &mav_ctx::band_phase, nullptr, true, nullptr},
+    {"band_skew", -1, 64, &mav_ctx::band_skew, nullptr, true, nullptr},
+    {"deep_frac", 1, 1 << 20, &mav_ctx::deep_frac, nullptr, true, set_deep_frac},
+    // not part of the launch schedule: the host side of mav_upload_gather, where uploads go, the compute stream's priority class
+    {"upload_threads", 1, 64, &mav_ctx::upload_threads, nullptr, false, set_upload_threads},
+    {"inline_uploads", -kAny, kAny, nullptr, &mav_ctx::inline_uploads, false, set_inline_uploads},
+    {"stream_priority", -kAny, kAny, &mav_ctx::stream_priority, nullptr, false, set_stream_priority},
+};
+static const Option* find_option(const char* name)
+{
+    for (const Option& o : kOptions) if (!strcmp(o.name, name)) return &o;
     return nullptr;
 }
+static long option_value(const mav_ctx* c, const Option& o) { return o.i ? (long)(c->*o.i) : (long)(c->*o.b); }
 extern "C" int mav_get_option(mav_ctx* c, const char* name, long* value)
 {
     if (!c || !name || !value) return fail(MAV_ERR_ARG, "mav_get_option: NULL argument");
-    if (!strcmp(name, "upload_threads")) { *value = c->upload_threads; return MAV_OK; }
-    if (!strcmp(name, "inline_uploads")) { *value = c->inline_uploads; return MAV_OK; }
-    if (!strcmp(name, "stream_priority")) { *value = c->stream_priority; return MAV_OK; }
-    long tmp;
-    if (!option_slot(c, name, &tmp)) return fail(MAV_ERR_ARG, "unknown option '%s'", name);
-    *value = tmp;
+    const Option* o = find_option(name);
+    if (!o) return fail(MAV_ERR_ARG, "unknown option '%s'", name);
+    *value = option_value(c, *o);
     return MAV_OK;
 }
 extern "C" int mav_set_option(mav_ctx* c, const char* name, long value)
 {
     if (!c || !name) return fail(MAV_ERR_ARG, "mav_set_option: NULL argument");
-    if (!strcmp(name, "inline_uploads")) {      // not part of the launch schedule either
-        if (value < 0 || value > 1) return fail(MAV_ERR_ARG, "option 'inline_uploads' must be 0 or 1, got %ld", value);
-        HIPCHK(hipSetDevice(c->device));
-        if (c->copy_stream) HIPCHK(hipStreamSynchronize(c->copy_stream));      // nothing of the old mode is left in flight
-        HIPCHK(hipStreamSynchronize(c->stream));
-        c->inline_uploads = value != 0;
-        return MAV_OK;
-    }
-    if (!strcmp(name, "stream_priority")) {     // not part of the launch schedule
-        // The HIP runtime maps streams onto a pool of (by default four) hardware queues PER PRIORITY CLASS, least-used first; which
-        // queue a new stream gets depends on every stream the process has ever made.  Lanes -- contexts that take a stream of small calls
-        // in turn and must not share a queue (pipeline.py) -- ask for a class of their own: -1 = high.  The context's compute stream is
-        // re-created in that class; nothing may be in flight (the call drains it).
-        int lo = 0, hi = 0;
-        HIPCHK(hipSetDevice(c->device));
-        HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));            // lo = least (numerically largest), hi = greatest
-        if (value < hi || value > lo) return fail(MAV_ERR_ARG, "option 'stream_priority' must be in [%d, %d], got %ld", hi, lo, value);
-        if ((int)value == c->stream_priority) return MAV_OK;
-        CHK(mav_worker_drain(c));
-        CHK(sync_all_streams(c));
-        if (c->copy_stream) HIPCHK(hipStreamSynchronize(c->copy_stream));
-        hipStream_t fresh = nullptr;
-        HIPCHK(hipStreamCreateWithPriority(&fresh, hipStreamNonBlocking, (int)value));
-        HIPCHK(hipStreamDestroy(c->stream));
-        c->stream = fresh;
-        c->stream_priority = (int)value;
-        return MAV_OK;
-    }
-    if (!strcmp(name, "upload_threads")) {      // host side of mav_upload_gather; not part of the launch schedule (mav_schedule_info)
-        if (value < 1 || value > 64) return fail(MAV_ERR_ARG, "option 'upload_threads' must be in [1, 64], got %ld", value);
-        if (c->stager) return fail(MAV_ERR_STATE, "upload_threads must be set before the first mav_upload_gather call");
-        c->upload_threads = (int)value;
-        return MAV_OK;
-    }
-    const OptionDesc* d = nullptr;
-    for (const auto& o : kOptions) if (!strcmp(o.name, name)) d = &o;
-    if (!d) return fail(MAV_ERR_ARG, "unknown option '%s'", name);
-    if (value < d->lo || value > d->hi) return fail(MAV_ERR_ARG, "option '%s' must be in [%ld, %ld], got %ld", name, d->lo, d->hi, value);
-    const int v = (int)value;
-    if (!strcmp(name, "group")) {
-        const int g = v > c->max_batch ? c->max_batch : v;
-        HIPCHK(hipSetDevice(c->device));
-        CHK(sync_all_streams(c));
-        if (g == c->group) return MAV_OK;
-        if (!c->ws_ready) { c->group = g; c->small_g = small_group_cap(c, g); return MAV_OK; }    // nothing allocated yet: the plan changes
-        return alloc_group(c, g);
-    }
-    if (!strcmp(name, "group_fine")) { c->group_fine = v; c->group_fine_set = true; }
-    else if (!strcmp(name, "bands")) {          // 0 = back to automatic
-        c->bands_set = v > 0;
-        c->bands = v > 0 ? v : c->bands_auto;
-    }
-    else if (!strcmp(name, "pairs_in_flight")) c->pairs_in_flight = v;
-    else if (!strcmp(name, "band_mb")) c->pif_band_mb = v;
-    else if (!strcmp(name, "coarse_cache_mb")) c->coarse_cache_mb = v;
-    else if (!strcmp(name, "coarse_half")) c->coarse_half = v;
-    else if (!strcmp(name, "share_m")) c->share_m = v != 0;
-    else if (!strcmp(name, "share_frames")) c->share_frames = v != 0;
-    else if (!strcmp(name, "strip")) c->strip = v;
-    else if (!strcmp(name, "phi_screen")) c->phi_screen = v != 0;
-    else if (!strcmp(name, "phi_yloop")) c->phi_yloop = v;
-    else if (!strcmp(name, "small_batch")) c->small_batch = v != 0;
-    else if (!strcmp(name, "sweep_write_through")) c->sweep_wt = v;
-    else if (!strcmp(name, "deep_batch")) c->deep_batch = v != 0;
-    else if (!strcmp(name, "coarse_bands")) c->coarse_bands = v != 0;
-    else if (!strcmp(name, "band_phase")) c->band_phase = v;
-    else if (!strcmp(name, "band_skew")) c->band_skew = v;
-    else if (!strcmp(name, "deep_frac")) {
-        if (c->ws_ready) return fail(MAV_ERR_STATE, "deep_frac must be set before the first call that computes flow");
-        c->deep_frac = v; c->kd = 0;
-        for (int k = (int)c->layers.size() - 1; k >= 1; k--)
-            if ((size_t)c->layers[k].w * c->layers[k].h * (size_t)v <= c->n0) c->kd = k; else break;
-    }
+    const Option* o = find_option(name);
+    if (!o) return fail(MAV_ERR_ARG, "unknown option '%s'", name);
+    if (value < o->lo || value > o->hi) return fail(MAV_ERR_ARG, "option '%s' must be in [%ld, %ld], got %ld", name, o->lo, o->hi, value);
+    if (o->set) return o->set(c, value);
+    if (o->i) c->*o->i = (int)value; else c->*o->b = value != 0;
     return MAV_OK;
 }
 
@@ -1221,52 +1235,58 @@ static BlurParams blur_of(const mav_ctx* c, const Layer& l)
     return bp;
 }
 
-// How the sweeps of layer k run for a group of g pairs (plan_sweeps decides, layer_sweeps executes, mav_schedule_info reports).
-enum { SW_SEQ = 0, SW_TWO_PAIRS = 1, SW_COARSE_TWO = 2 };
+// How the sweeps of layer k run for a group of g pairs: plan_sweeps decides, layer_sweeps executes, mav_schedule_info reports -- all
+// from these fields alone.  The group is cut into sub-groups of per_launch pairs; sub-group i runs on stream i & 1 of `streams`.
+enum MBuild { M_GROUP, M_SUB, M_BAND };          // the initial M: of the whole group up front / of a sub-group right before its sweeps /
+                                                 // of a sub-group band by band, right before each band's first sweep
+enum MSlot { SLOT_OWN, SLOT_FIRST, SLOT_ALTERNATE };   // the M buffers of the sub-group that starts at pair s0: slot s0 / slot 0 (option
+                                                       // "share_m") / slot (i & 1) * per_launch, one set per stream
 struct SweepPlan {
-    int mode;        // SW_SEQ: sub-groups one after the other on one stream; SW_TWO_PAIRS: finest layer, pairs alternate between two
-                     // streams, each band-major; SW_COARSE_TWO: coarse layer, sub-groups of `half` pairs alternate between two streams
-    int sub;         // pairs per launch (SW_SEQ)
-    int J;           // horizontal bands per pair (finest layer, one pair per launch); 1 = sweep-major
-    int half;        // SW_COARSE_TWO: pairs per launch
-    bool m_per_sub;  // the initial M of a sub-group is built right before its sweeps
+    const char* name;     // what mav_schedule_info calls it
+    int per_launch;       // pairs per sub-group = per launch
+    int streams;          // 1: the compute stream; 2: sub-groups alternate between it and pair_stream (one fork and one join per group)
+    int J;                // horizontal bands per pair (one pair per launch); 1 = sweep-major
+    bool shift_second;    // the second stream's sub-groups use the partition shifted by half a band (option "band_phase")
+    MBuild m_build;
+    MSlot m_slot;
+    bool write_through;   // the sweeps' M' through write-through stores (option "sweep_write_through": by default with two streams only)
 };
 static SweepPlan plan_sweeps(const mav_ctx* c, int k, int g, bool bands_ok)
 {
     const Layer& l = c->layers[k];
     const int T = blur_iter_tile_rows(l.h), I = c->fb.iterations;
-    SweepPlan p{SW_SEQ, g, 1, 0, false};
+    auto wt = [&](int streams) { return c->sweep_wt < 0 ? streams == 2 : c->sweep_wt != 0; };
+    int sub = g;
     // The finest layer's ten sweeps re-read R0/R1 and M: run them `group_fine` pairs at a time so that one sub-group's working
     // set stays resident in the 256 MB Infinity Cache between sweeps.  Coarse layers are small: as many pairs per launch as keep
     // the sweeps' working set cache-sized, to fill the 256 CUs.
-    if (k == 0 && c->group_fine > 0 && c->group_fine < g) p.sub = c->group_fine;
+    if (k == 0 && c->group_fine > 0 && c->group_fine < g) sub = c->group_fine;
     if (k > 0 && c->coarse_cache_mb > 0) {
         const size_t ws = (size_t)l.w * l.h * 80, cap = (size_t)c->coarse_cache_mb << 20;
         const int fit = (int)(cap / (ws ? ws : 1));
-        if (fit < p.sub) p.sub = fit > 1 ? fit : 1;
+        if (fit < sub) sub = fit > 1 ? fit : 1;
     }
     // with per-sub-group sweeps the initial M of a sub-group is built right before its sweeps: M, R0 and R1 are then still in the
     // Infinity Cache when the first sweep reads them (measured -0.5 ms per 64 pairs; doing the same with the blur and the expansion
     // costs more in small launches than it returns)
-    p.m_per_sub = p.sub < g;
+    bool m_per_sub = sub < g;
     const size_t ws_pair = (size_t)l.w * l.h * 80, band_bytes = (size_t)c->pif_band_mb << 20;
     // A COARSE layer whose per-pair working set exceeds a band (layer 1 of the 4K preset: 1536 x 864, 106 MB) is swept exactly like the
     // finest one: pairs alternate between the two streams, each band-major, so that the two pairs in flight occupy 2 x <= band_mb of the
     // Infinity Cache instead of 2 x 106 MB (option "coarse_bands").
     const bool big_coarse = k > 0 && c->coarse_bands && bands_ok && ws_pair > band_bytes && T / (I + 2) >= 2;
-    if (big_coarse) { p.sub = 1; p.m_per_sub = true; }
+    if (big_coarse) { sub = 1; m_per_sub = true; }
     if (k > 0 && !big_coarse && c->pairs_in_flight == 2 && g >= 2) {
         // COARSE LAYERS with two sub-groups in flight: sub-groups of half the cache-sized count alternate between the compute stream
         // and pair_stream, each with its own M slots, for the same reason as the pairs of the finest layer below -- 25.5 - 25.6 vs
         // 26.0 - 26.6 ms per 64 pairs at 1080p with 4 + 4 instead of 8 pairs per launch (3 + 3: 25.7 - 25.8; 8 + 8: 26.4;
         // profiles/r02/ab_coarse_two*.log).
-        p.mode = SW_COARSE_TWO;
-        p.half = p.sub / 2 > 0 ? p.sub / 2 : 1;
-        if (c->coarse_half > 0) p.half = c->coarse_half;
-        if (2 * p.half > g) p.half = (g + 1) / 2;
-        return p;
+        int half = sub / 2 > 0 ? sub / 2 : 1;
+        if (c->coarse_half > 0) half = c->coarse_half;
+        if (2 * half > g) half = (g + 1) / 2;
+        return {"two sub-groups in flight", half, 2, 1, false, M_SUB, SLOT_ALTERNATE, wt(2)};
     }
-    if ((k == 0 || big_coarse) && c->pairs_in_flight == 2 && p.m_per_sub && p.sub == 1 && g >= 2) {
+    if ((k == 0 || big_coarse) && c->pairs_in_flight == 2 && m_per_sub && sub == 1 && g >= 2) {
         // TWO PAIRS IN FLIGHT (finest layer, one pair per launch).  Pair s of the group runs on stream s & 1 -- the compute stream
         // and pair_stream -- and ping-pongs M through slot s & 1.  The two streams never wait for each other inside the group
         // (different pairs: no dependency; one fork and one join event per group), so one stream's launches fill the kernel
@@ -1280,14 +1300,20 @@ static SweepPlan plan_sweeps(const mav_ctx* c, int k, int g, bool bands_ok)
         const int Jmax = T / (I + 2);          // a band needs iterations + 2 tile rows (the skew must not reach the image top)
         if (J > Jmax) J = Jmax;
         if (J < 1) J = 1;
-        if (J == 1 || bands_ok) { p.mode = SW_TWO_PAIRS; p.J = J; return p; }
+        if (J == 1 || bands_ok)
+            return {"two pairs in flight, band-major", 1, 2, J, J > 1 && c->band_phase && J >= c->band_phase, J > 1 ? M_BAND : M_SUB,
+                    SLOT_ALTERNATE, wt(2)};
     }
-    // one stream; bands (finest layer, one pair per launch): at least iterations + 2 tile rows each
-    if (k == 0 && (p.m_per_sub || g == 1) && p.sub == 1 && T >= (I + 2) * c->bands && bands_ok) p.J = c->bands;
-    return p;
+    // ONE STREAM: sub-groups are swept one after the other, so they all ping-pong M through the SAME two buffers (the first
+    // sub-group's slots; option "share_m"): the M lines then stay hot in the Infinity Cache from pair to pair instead of leaving a
+    // dead 83 MB copy behind per pair.  Measured at 1080p, 64 pairs: 27.6 / 28.0 ms shared vs 28.2 / 28.6 ms with per-slot buffers.
+    // Bands (finest layer, one pair per launch) of at least iterations + 2 tile rows each: the pair's whole initial M first, then the
+    // sweeps band-major.
+    const int J = (k == 0 && (m_per_sub || g == 1) && sub == 1 && T >= (I + 2) * c->bands && bands_ok) ? c->bands : 1;
+    return {"one stream", sub, 1, J, false, m_per_sub ? M_SUB : M_GROUP, (m_per_sub && c->share_m) ? SLOT_FIRST : SLOT_OWN, wt(1)};
 }
 
-// The finest layer's sweeps of one pair in BAND-MAJOR order, for frames whose per-pair working set (80 B per pixel: M in, M out,
+// The `iterations` sweeps of gs pairs on stream st.  J > 1: the sweeps of one pair in BAND-MAJOR order, for frames whose per-pair working set (80 B per pixel: M in, M out,
 // R0, R1) does not fit the 256 MB Infinity Cache -- 664 MB at 3840x2160.  The image is cut into J horizontal bands of tile rows
 // and ALL sweeps of a band run before the next band starts, so that a band's M, R0 and R1 stay cache-resident across its sweeps
 // exactly as a whole 1080p pair does.  What makes this legal without recomputing halos is a skew: sweep `it` processes band j as
@@ -1298,7 +1324,8 @@ static SweepPlan plan_sweeps(const mav_ctx* c, int k, int g, bool bands_ok)
 //     while that reader starts 6 pixels above tile row A_(j+1) - it + 1; and the rows of band j - 1 that (it, j) itself reads have
 //     been overwritten by (it + 1, j - 1) only up to one tile row above them.  A skew of one tile row (16 >= 6 pixels) covers both.
 // Every tile is computed exactly once on the same tile grid: results are bit-identical to the sweep-major schedule
-// (tests/test_gpu_flow.py).  One stream, no events.
+// (tests/test_gpu_flow.py).  One stream, no events.  J = 1 is the sweep-major order: every sweep one launch over all tile rows, for
+// any number of pairs gs and any kernel form (bands of their own exist for one pair and the fast form only: blur_iter_bands_ok).
 // upd != nullptr: the initial M (UpdateMatrices from the coarser layer's flow) is built band by band too, right before a band's
 // first sweep: pixel rows [16 a0 - 8, 16 a1 + 8) -- what that sweep reads (6-pixel halo) -- which lie below everything the bands
 // above have written into Ma (their odd sweeps end one whole tile row higher); the rows two neighbouring bands both need are
@@ -1322,10 +1349,8 @@ static void initial_m(hipStream_t st, const BandUpdate& u, const float* r0, cons
 // monotone sequence of boundaries (a band whose rows have all moved above the image top at a late sweep is empty and skipped; its
 // successor then starts at row 0): bit-identical (tests/test_gpu_flow.py).
 static void sweeps_band_major(mav_ctx* c, hipStream_t st, int kid, float* Ma, float* Mb, size_t ms, const float* r0, const float* r1, size_t rs, int gs,
-                              int lw, int lh, int T, int J, float* fo, size_t fstride, const BandUpdate* upd = nullptr, bool two_streams = false,
-                              int phase = 0)
+                              int lw, int lh, int T, int J, float* fo, size_t fstride, const BandUpdate* upd, bool wt, int phase)
 {
-    const bool wt = c->sweep_wt < 0 ? two_streams : c->sweep_wt != 0;
     const int I = c->fb.iterations;
     const int NBands = phase ? J + 1 : J;
     auto bound = [&](int j) -> int {                      // first tile row of band j; bound(NBands) = T
@@ -1359,19 +1384,6 @@ static void sweeps_band_major(mav_ctx* c, hipStream_t st, int kid, float* Ma, fl
     }
 }
 
-// initial M + the `iterations` sweeps of gs pairs, sweep-major, on stream ss
-static void sweeps_plain(mav_ctx* c, hipStream_t ss, int kid, float* Min, float* Mout, size_t ms, const float* r0, const float* r1, size_t rs, int gs,
-                         const Layer& l, float* fo, size_t fstride, bool two_streams = false)
-{
-    const bool wt = c->sweep_wt < 0 ? two_streams : c->sweep_wt != 0;
-    for (int it = 0; it < c->fb.iterations; it++) {
-        const int update = it < c->fb.iterations - 1;
-        { ProfScope ps(c, kid, ss);
-          launch_blur_iter(ss, Min, Mout, ms, r0, r1, rs, gs, l.w, l.h, c->fb.winsize, update, !update, fo, fstride, 0, -1, c->strip, wt); }
-        if (update) { float* t = Min; Min = Mout; Mout = t; }
-    }
-}
-
 // Initial M and the `iterations` sweeps of layer k for g pairs whose expansions lie at r0 / r1 (slot stride rs), starting on
 // stream st.  flow_prev = the coarser layer's flow (pw x ph, slot stride fc_stride; nullptr at the top layer); the layer's flow goes to
 // fdst (slot stride fstride).  M ping-pongs through Ma / Mb (slot stride ms).  On return everything has been joined back into st.
@@ -1384,71 +1396,38 @@ static int layer_sweeps(mav_ctx* c, hipStream_t st, int k, int g, const float* r
     const float mul = (float)(1. / c->fb.pyr_scale);
     const BandUpdate src = flow_init ? BandUpdate{flow_init, fi_stride, 0, 0, 0.f, true} : BandUpdate{flow_prev, fc_stride, pw, ph, mul, false};
     auto src_at = [&](int s0) { BandUpdate u = src; if (u.flow_prev) u.flow_prev += (size_t)s0 * u.fc_stride; return u; };   // from pair s0 on
-    const bool bands_ok = blur_iter_bands_ok(l.w, c->fb.winsize, ms, rs, fstride, Ma, Mb, r0g, r1g, fdst);
-    const SweepPlan p = plan_sweeps(c, k, g, bands_ok);
+    const SweepPlan p = plan_sweeps(c, k, g, blur_iter_bands_ok(l.w, c->fb.winsize, ms, rs, fstride, Ma, Mb, r0g, r1g, fdst));
     const int kid = k == 0 ? K_ITER : K_ITER_COARSE;
     const int T = blur_iter_tile_rows(l.h);
-    if (p.mode == SW_TWO_PAIRS) {
+    if (p.streams == 2) {
         CHK(ensure_pair_stream(c));
         HIPCHK(hipEventRecord(c->pif_fork, st));
         HIPCHK(hipStreamWaitEvent(c->pair_stream, c->pif_fork, 0));
-        for (int s0 = 0; s0 < g; s0++) {
-            const hipStream_t ss = (s0 & 1) ? c->pair_stream : st;
-            float *Min = Ma + (size_t)(s0 & 1) * ms, *Mout = Mb + (size_t)(s0 & 1) * ms;
-            const float *r0 = r0g + (size_t)s0 * rs, *r1 = r1g + (size_t)s0 * rs;
-            float* fo = fdst + (size_t)s0 * fstride;
-            const BandUpdate bu = src_at(s0);
-            if (p.J > 1) {
-                sweeps_band_major(c, ss, kid, Min, Mout, ms, r0, r1, rs, 1, l.w, l.h, T, p.J, fo, fstride, &bu, true,
-                                  (c->band_phase && (s0 & 1) && p.J >= c->band_phase) ? 1 : 0);
-                continue;
-            }
-            { ProfScope ps(c, K_UPDATE, ss);
-              initial_m(ss, bu, r0, r1, rs, 1, l.w, l.h, Min, ms); }
-            sweeps_plain(c, ss, kid, Min, Mout, ms, r0, r1, rs, 1, l, fo, fstride, true);
-        }
-        prof_close_stream(c, c->pair_stream); prof_close_stream(c, st);
-        HIPCHK(hipEventRecord(c->pif_join, c->pair_stream));
-        HIPCHK(hipStreamWaitEvent(st, c->pif_join, 0));
-        return MAV_OK;
     }
-    if (p.mode == SW_COARSE_TWO) {
-        CHK(ensure_pair_stream(c));
-        HIPCHK(hipEventRecord(c->pif_fork, st));
-        HIPCHK(hipStreamWaitEvent(c->pair_stream, c->pif_fork, 0));
-        int idx = 0;
-        for (int s0 = 0; s0 < g; s0 += p.half, idx++) {
-            const int gs = g - s0 < p.half ? g - s0 : p.half;
-            const hipStream_t ss = (idx & 1) ? c->pair_stream : st;
-            const size_t m_off = (size_t)(idx & 1) * p.half * ms;
-            const float *r0 = r0g + (size_t)s0 * rs, *r1 = r1g + (size_t)s0 * rs;
-            { ProfScope ps(c, K_UPDATE, ss);
-              initial_m(ss, src_at(s0), r0, r1, rs, gs, l.w, l.h, Ma + m_off, ms); }
-            sweeps_plain(c, ss, K_ITER_COARSE, Ma + m_off, Mb + m_off, ms, r0, r1, rs, gs, l, fdst + (size_t)s0 * fstride, fstride, true);
-        }
-        prof_close_stream(c, c->pair_stream); prof_close_stream(c, st);
-        HIPCHK(hipEventRecord(c->pif_join, c->pair_stream));
-        HIPCHK(hipStreamWaitEvent(st, c->pif_join, 0));
-        return MAV_OK;
-    }
-    if (!p.m_per_sub) {
+    if (p.m_build == M_GROUP) {
         ProfScope ps(c, K_UPDATE, st);
         initial_m(st, src, r0g, r1g, rs, g, l.w, l.h, Ma, ms);
     }
-    // Sub-groups are swept one after the other on one stream, so they all ping-pong M through the SAME two buffers (the first
-    // sub-group's slots; option "share_m"): the M lines then stay hot in the Infinity Cache from pair to pair instead of leaving a
-    // dead 83 MB copy behind per pair.  Measured at 1080p, 64 pairs: 27.6 / 28.0 ms shared vs 28.2 / 28.6 ms with per-slot buffers.
-    for (int s0 = 0; s0 < g; s0 += p.sub) {
-        const int gs = g - s0 < p.sub ? g - s0 : p.sub;
-        const size_t m_off = (p.m_per_sub && c->share_m) ? 0 : (size_t)s0 * ms;
+    // With two streams the host alternates between them sub-group by sub-group, and within a pair band by band (a band's initial M, then
+    // all its sweeps): the two streams never wait for each other inside the group.
+    for (int s0 = 0, i = 0; s0 < g; s0 += p.per_launch, i++) {
+        const int gs = g - s0 < p.per_launch ? g - s0 : p.per_launch;
+        const bool second = p.streams == 2 && (i & 1);
+        const hipStream_t ss = second ? c->pair_stream : st;
+        const size_t m_off = p.m_slot == SLOT_OWN ? (size_t)s0 * ms : p.m_slot == SLOT_FIRST ? 0 : (size_t)(i & 1) * p.per_launch * ms;
         const float *r0 = r0g + (size_t)s0 * rs, *r1 = r1g + (size_t)s0 * rs;
-        if (p.m_per_sub) {
-            ProfScope ps(c, K_UPDATE, st);
-            initial_m(st, src_at(s0), r0, r1, rs, gs, l.w, l.h, Ma + m_off, ms);
+        const BandUpdate bu = src_at(s0);
+        if (p.m_build == M_SUB) {
+            ProfScope ps(c, K_UPDATE, ss);
+            initial_m(ss, bu, r0, r1, rs, gs, l.w, l.h, Ma + m_off, ms);
         }
-        float* fo = fdst + (size_t)s0 * fstride;
-        if (p.J > 1 && gs == 1) sweeps_band_major(c, st, kid, Ma + m_off, Mb + m_off, ms, r0, r1, rs, gs, l.w, l.h, T, p.J, fo, fstride);
-        else sweeps_plain(c, st, kid, Ma + m_off, Mb + m_off, ms, r0, r1, rs, gs, l, fo, fstride);
+        sweeps_band_major(c, ss, kid, Ma + m_off, Mb + m_off, ms, r0, r1, rs, gs, l.w, l.h, T, p.J, fdst + (size_t)s0 * fstride, fstride,
+                          p.m_build == M_BAND ? &bu : nullptr, p.write_through, p.shift_second && second);
+    }
+    if (p.streams == 2) {
+        prof_close_stream(c, c->pair_stream); prof_close_stream(c, st);
+        HIPCHK(hipEventRecord(c->pif_join, c->pair_stream));
+        HIPCHK(hipStreamWaitEvent(st, c->pif_join, 0));
     }
     return MAV_OK;
 }
@@ -1502,17 +1481,6 @@ static bool is_small_group(const mav_ctx* c, int g)
            (size_t)g * c->n0 * 80 <= ((size_t)c->small_batch_mb << 20);
 }
 
-// One group of g pairs: every coarse layer completely (top layer first: images, expansions, initial M, sweeps), then the finest layer.
-// SMALL GROUPS (is_small_group: one 1080p pair, two 720p pairs ...; BASELINE config 2) are a chain of ~30 dependent launches that
-// each fill a fraction of the chip, ~4.5 us of boundary apiece.  For them the whole pyramid's layer images come from ONE launch and
-// all expansions from ONE launch (k_blur_multi / k_polyexp_multi: the workgroups of several layers in one grid, every layer into a
-// region of its own in Ic / Rc), instead of two launches per layer: the small layers ride along with the finest one.  Same tile
-// functions on the same data: bit-identical flow (tests/test_gpu_flow.py).
-// (Measured for such groups and not kept: the finest layer's images and expansions on a side stream underneath the coarse chain --
-// every event record / wait costs ~6 us on the compute stream and the overlapped kernels slow the chain's own: 0.320 vs 0.306 ms per
-// 1280x720 pair, profiles/r03/c2_side_stream.txt; all sweeps of a layer in one launch of resident workgroups that hand M' over through
-// flags -- a cross-CU hand-off costs what the kernel boundary costs: 0.419 vs 0.305 ms, profiles/r03/c2_resident_sweeps.txt.  For big
-// groups overlapping the finest layer's preparation with the coarse sweeps loses too: profiles/r02/ab_overlap_fine_prep_with_coarse_sweeps.log.)
 // The layer images of layers k_lo .. k_hi for F frames (the first `split` from run prev, the rest from run img2; img2 == nullptr: one
 // run) into regions Ik(k) with slot stride sk(k): every layer blur_multi_ok accepts through ONE launch, the others (long Gaussians)
 // through the two-pass kernels in chunks the H x w scratch holds; then ALL their expansions through one launch (per MAV_MAX_JOBS layers).
@@ -1554,6 +1522,27 @@ static void pyramid_multi(mav_ctx* c, hipStream_t st, const T* prev, const T* im
     flush_poly();
 }
 
+// Where layer k of a walk finds its expansions (pair 0's two; slot stride rs) and puts its flow (slot stride fstride), and the slot
+// stride ms of the M buffers at that layer.
+struct LayerIO { const float *r0, *r1; size_t rs; float* flow; size_t fstride, ms; };
+// Layers k_hi .. k_lo of g pairs, top-down: `at(k)` makes layer k's expansions (unless they exist already) and says where they and the
+// layer's flow lie; then the layer's initial M and sweeps (layer_sweeps), from the flow of the layer above.  flow_prev / fp_stride:
+// the flow of layer k_hi + 1, or nullptr when the walk starts at the top of the pyramid; flow_init: the top layer's initial flow or nullptr.
+template <typename AtFn>
+static int walk_layers(mav_ctx* c, hipStream_t st, int k_hi, int k_lo, int g, AtFn at, float* Ma, float* Mb, const float* flow_prev,
+                       size_t fp_stride, const float* flow_init)
+{
+    const int L = (int)c->layers.size();
+    int pw = flow_prev ? c->layers[k_hi + 1].w : 0, ph = flow_prev ? c->layers[k_hi + 1].h : 0;
+    for (int k = k_hi; k >= k_lo; k--) {
+        const LayerIO io = at(k);
+        CHK(layer_sweeps(c, st, k, g, io.r0, io.r1, io.rs, flow_prev, fp_stride, pw, ph, io.flow, io.fstride, Ma, Mb, io.ms,
+                         k == L - 1 ? flow_init : nullptr, c->init_stride));
+        flow_prev = io.flow; fp_stride = io.fstride; pw = c->layers[k].w; ph = c->layers[k].h;
+    }
+    return MAV_OK;
+}
+
 // DEEP LAYERS (kd .. top) of D pairs at once, on the compute stream; the flow of layer kd lands in deep.f[kd & 1], slot stride
 // 2 * c_stride[kd].  See mav_ctx::DeepSet.  Same tile functions on the same data as the per-group path: bit-identical flow.
 // flow_init: the top layer's initial flow of the D pairs (init_snap) or nullptr.
@@ -1568,17 +1557,11 @@ static int deep_layers(mav_ctx* c, hipStream_t st, const T* prev, const T* next,
     auto Rk = [&](int k) { return c->deep.R + 5 * (size_t)F * (c->c_off[k] - base); };
     auto sk = [&](int k) { return c->c_stride[k]; };
     pyramid_multi(c, st, prev, img2, D, F, kd, L - 1, Ik, Rk, sk);
-    const float* flow_prev = nullptr;
-    int pw = 0, ph = 0;
-    size_t fp_stride = 0;
-    for (int k = L - 1; k >= kd; k--) {
+    auto at = [&](int k) {
         const size_t rs = 5 * sk(k);
-        const float *r0 = Rk(k), *r1 = Rk(k) + (seq ? rs : rs * (size_t)D);
-        CHK(layer_sweeps(c, st, k, D, r0, r1, rs, flow_prev, fp_stride, pw, ph, c->deep.f[k & 1], 2 * sk(k), c->deep.Ma, c->deep.Mb, 5 * sk(k),
-                         k == L - 1 ? flow_init : nullptr, c->init_stride));
-        flow_prev = c->deep.f[k & 1]; fp_stride = 2 * sk(k); pw = c->layers[k].w; ph = c->layers[k].h;
-    }
-    return MAV_OK;
+        return LayerIO{Rk(k), Rk(k) + (seq ? rs : rs * (size_t)D), rs, c->deep.f[k & 1], 2 * sk(k), rs};
+    };
+    return walk_layers(c, st, L - 1, kd, D, at, c->deep.Ma, c->deep.Mb, nullptr, 0, flow_init);
 }
 
 // One group of g pairs: every coarse layer completely (top layer first: images, expansions, initial M, sweeps), then the finest layer.
@@ -1590,8 +1573,11 @@ static int deep_layers(mav_ctx* c, hipStream_t st, const T* prev, const T* next,
 // all expansions from ONE launch (k_blur_multi / k_polyexp_multi: the workgroups of several layers in one grid, every layer into a
 // region of its own in Ic / Rc), instead of two launches per layer: the small layers ride along with the finest one.  Same tile
 // functions on the same data: bit-identical flow (tests/test_gpu_flow.py).
-// (Measured for such groups and not kept: the finest layer's images and expansions on a side stream underneath the coarse chain;
-// all sweeps of a layer in one launch of resident workgroups that hand M' over through flags -- HISTORY.md.)
+// (Measured for such groups and not kept: the finest layer's images and expansions on a side stream underneath the coarse chain --
+// every event record / wait costs ~6 us on the compute stream and the overlapped kernels slow the chain's own: 0.320 vs 0.306 ms per
+// 1280x720 pair, profiles/r03/c2_side_stream.txt; all sweeps of a layer in one launch of resident workgroups that hand M' over through
+// flags -- a cross-CU hand-off costs what the kernel boundary costs: 0.419 vs 0.305 ms, profiles/r03/c2_resident_sweeps.txt.  For big
+// groups overlapping the finest layer's preparation with the coarse sweeps loses too: profiles/r02/ab_overlap_fine_prep_with_coarse_sweeps.log.)
 template <typename T>
 static int flow_group(mav_ctx* c, const T* prev, const T* next, int g, bool seq, float* flow_out, const float* deep_flow = nullptr,
                       size_t deep_stride = 0, const float* flow_init = nullptr)
@@ -1600,10 +1586,8 @@ static int flow_group(mav_ctx* c, const T* prev, const T* next, int g, bool seq,
     const hipStream_t st = c->stream;
     const int L = (int)c->layers.size();
     const size_t n0 = c->n0, fc_stride = 2 * (c->n1 ? c->n1 : 1);
-    const float* flow_prev = deep_flow;
-    size_t fp_stride = deep_flow ? deep_stride : fc_stride;
-    const int k_top = deep_flow ? c->kd - 1 : L - 1;
-    int pw = deep_flow ? c->layers[c->kd].w : 0, ph = deep_flow ? c->layers[c->kd].h : 0;
+    auto flow_of = [&](int k) { return k ? w.fc[k & 1] : flow_out; };
+    auto fstride_of = [&](int k) { return k ? fc_stride : 2 * n0; };
     if (!deep_flow && is_small_group(c, g)) {
         const int F = seq ? g + 1 : 2 * g;                                // frames: one run of g + 1, or the prev run and the next run
         const T* img2 = seq ? nullptr : next;
@@ -1611,23 +1595,18 @@ static int flow_group(mav_ctx* c, const T* prev, const T* next, int g, bool seq,
         auto Rk = [&](int k) { return k ? w.Rc + 5 * (size_t)F * c->c_off[k] : w.R; };
         auto sk = [&](int k) { return k ? c->c_stride[k] : n0; };
         pyramid_multi(c, st, prev, img2, g, F, 0, L - 1, Ik, Rk, sk);
-        for (int k = L - 1; k >= 0; k--) {
+        auto at = [&](int k) {
             const size_t rs = 5 * sk(k);
-            const float *r0 = Rk(k), *r1 = Rk(k) + (seq ? rs : rs * (size_t)g);
-            CHK(layer_sweeps(c, st, k, g, r0, r1, rs, flow_prev, fc_stride, pw, ph, k ? w.fc[k & 1] : flow_out, k ? fc_stride : 2 * n0, w.Ma, w.Mb, 5 * n0,
-                             k == L - 1 ? flow_init : nullptr, c->init_stride));
-            flow_prev = w.fc[k & 1]; pw = c->layers[k].w; ph = c->layers[k].h;
-        }
-        return MAV_OK;
+            return LayerIO{Rk(k), Rk(k) + (seq ? rs : rs * (size_t)g), rs, flow_of(k), fstride_of(k), 5 * n0};
+        };
+        return walk_layers(c, st, L - 1, 0, g, at, w.Ma, w.Mb, nullptr, fc_stride, flow_init);
     }
-    const float *r0 = nullptr, *r1 = nullptr;
-    for (int k = k_top; k >= 0; k--) {
+    auto at = [&](int k) {
+        const float *r0 = nullptr, *r1 = nullptr;
         layer_expansions(c, st, k, prev, next, g, seq, w.I, w.R, &r0, &r1);
-        CHK(layer_sweeps(c, st, k, g, r0, r1, 5 * n0, flow_prev, fp_stride, pw, ph, k ? w.fc[k & 1] : flow_out, k ? fc_stride : 2 * n0, w.Ma, w.Mb, 5 * n0,
-                         k == L - 1 ? flow_init : nullptr, c->init_stride));
-        flow_prev = w.fc[k & 1]; fp_stride = fc_stride; pw = c->layers[k].w; ph = c->layers[k].h;
-    }
-    return MAV_OK;
+        return LayerIO{r0, r1, 5 * n0, flow_of(k), fstride_of(k), 5 * n0};
+    };
+    return walk_layers(c, st, deep_flow ? c->kd - 1 : L - 1, 0, g, at, w.Ma, w.Mb, deep_flow, deep_flow ? deep_stride : fc_stride, flow_init);
 }
 
 // does a call of `batch` pairs run its deep layers once for the whole call (deep_layers) instead of once per group?
@@ -1705,39 +1684,38 @@ static int farneback_run(mav_ctx* c, const T* prev, const T* next, int batch, co
     c->last_render.batch = 0;        // the flow a previous detection call read may have been overwritten
     return MAV_OK;
 }
-extern "C" int mav_farneback_dev(mav_ctx* c, const uint8_t* prev, const uint8_t* next, int batch, float* flow)
-{
-    if (!c || !prev || !next || !flow) return fail(MAV_ERR_ARG, "mav_farneback: NULL argument");
-    if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "batch %d outside [1, %d]", batch, c->max_batch);
-    return farneback_run(c, prev, next, batch, nullptr, flow);
-}
-extern "C" int mav_farneback_init_dev(mav_ctx* c, const uint8_t* prev, const uint8_t* next, int batch, const float* flow_init, float* flow)
-{
-    if (!c || !prev || !next || !flow_init || !flow) return fail(MAV_ERR_ARG, "mav_farneback_init_dev: NULL argument");
-    if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "batch %d outside [1, %d]", batch, c->max_batch);
-    const size_t n = (size_t)batch * 2 * c->n0;
-    if (flow_init != flow && flow_init < flow + n && flow < flow_init + n)
-        return fail(MAV_ERR_ARG, "mav_farneback_init_dev: flow_init and flow overlap without being the same field");
-    return farneback_run(c, prev, next, batch, flow_init, flow);
-}
 // bytes per pixel of a MAV_DEPTH_* code; 0 for any other code
 static int depth_esize(int depth)
 {
     return depth == MAV_DEPTH_8U ? 1 : depth == MAV_DEPTH_16U ? 2 : depth == MAV_DEPTH_32F ? 4 : 0;
 }
-extern "C" int mav_farneback_ex_dev(mav_ctx* c, const void* prev, const void* next, int depth, int batch, const float* flow_init, float* flow)
+// The three device-pointer entry points: fn = the name their messages start with; need_init: flow_init may not be NULL.
+static int farneback_dev(mav_ctx* c, const char* fn, const void* prev, const void* next, int depth, int batch, const float* flow_init,
+                         bool need_init, float* flow)
 {
-    if (!c || !prev || !next || !flow) return fail(MAV_ERR_ARG, "mav_farneback_ex_dev: NULL argument");
-    if (!depth_esize(depth)) return fail(MAV_ERR_ARG, "mav_farneback_ex_dev: depth %d is none of MAV_DEPTH_8U / 16U / 32F", depth);
+    if (!c || !prev || !next || !flow || (need_init && !flow_init)) return fail(MAV_ERR_ARG, "%s: NULL argument", fn);
+    if (!depth_esize(depth)) return fail(MAV_ERR_ARG, "%s: depth %d is none of MAV_DEPTH_8U / 16U / 32F", fn, depth);
     if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "batch %d outside [1, %d]", batch, c->max_batch);
     if (flow_init) {
         const size_t n = (size_t)batch * 2 * c->n0;
         if (flow_init != flow && flow_init < flow + n && flow < flow_init + n)
-            return fail(MAV_ERR_ARG, "mav_farneback_ex_dev: flow_init and flow overlap without being the same field");
+            return fail(MAV_ERR_ARG, "%s: flow_init and flow overlap without being the same field", fn);
     }
     if (depth == MAV_DEPTH_16U) return farneback_run(c, (const uint16_t*)prev, (const uint16_t*)next, batch, flow_init, flow);
     if (depth == MAV_DEPTH_32F) return farneback_run(c, (const float*)prev, (const float*)next, batch, flow_init, flow);
     return farneback_run(c, (const uint8_t*)prev, (const uint8_t*)next, batch, flow_init, flow);
+}
+extern "C" int mav_farneback_dev(mav_ctx* c, const uint8_t* prev, const uint8_t* next, int batch, float* flow)
+{
+    return farneback_dev(c, "mav_farneback", prev, next, MAV_DEPTH_8U, batch, nullptr, false, flow);
+}
+extern "C" int mav_farneback_init_dev(mav_ctx* c, const uint8_t* prev, const uint8_t* next, int batch, const float* flow_init, float* flow)
+{
+    return farneback_dev(c, "mav_farneback_init_dev", prev, next, MAV_DEPTH_8U, batch, flow_init, true, flow);
+}
+extern "C" int mav_farneback_ex_dev(mav_ctx* c, const void* prev, const void* next, int depth, int batch, const float* flow_init, float* flow)
+{
+    return farneback_dev(c, "mav_farneback_ex_dev", prev, next, depth, batch, flow_init, false, flow);
 }
 extern "C" const float* mav_last_flow_dev(const mav_ctx* c) { return c ? c->last_flow : nullptr; }
 
@@ -1749,10 +1727,9 @@ static int schedule_info(mav_ctx* c, int batch, int esize, char* buf, size_t cap
     if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "batch %d outside [1, %d]", batch, c->max_batch);
     std::string o = "{";
     char t[256];
-    for (const auto& d : kOptions) {
-        long v = 0;
-        option_slot(c, d.name, &v);
-        snprintf(t, sizeof(t), "\"%s\": %ld, ", d.name, v);
+    for (const Option& d : kOptions) {
+        if (!d.in_schedule) continue;
+        snprintf(t, sizeof(t), "\"%s\": %ld, ", d.name, option_value(c, d));
         o += t;
     }
     const int g = batch < c->group ? batch : c->group;
@@ -1761,14 +1738,13 @@ static int schedule_info(mav_ctx* c, int batch, int esize, char* buf, size_t cap
     snprintf(t, sizeof(t), "\"pairs_per_group\": %d, \"pyramid_in_two_launches\": %s, \"deep_layers_from\": %d, \"deep_pairs\": %d, \"layers\": [", g,
              (!deep && is_small_group(c, g)) ? "true" : "false", deep ? c->kd : 0, D);
     o += t;
-    static const char* const mode_names[] = {"one stream", "two pairs in flight, band-major", "two sub-groups in flight"};
     for (int k = 0; k < (int)c->layers.size(); k++) {
         const Layer& l = c->layers[k];
         const SweepPlan p = plan_sweeps(c, k, (deep && k >= c->kd) ? D : g, l.w % 4 == 0 && c->fb.winsize / 2 == 6);
         snprintf(t, sizeof(t), "%s{\"layer\": %d, \"w\": %d, \"h\": %d, \"blur\": \"%s\", \"sweeps\": \"%s\", \"pairs_per_launch\": %d, \"bands\": %d}",
                  k ? ", " : "", k, l.w, l.h,
                  (l.w == c->W && l.h == c->H) ? "3x3" : (blur_resize_is_fused(c->W, c->H, l.w, l.h, l.ksize, esize) ? "fused" : "two-pass"),
-                 mode_names[p.mode], p.mode == SW_COARSE_TWO ? p.half : (p.mode == SW_TWO_PAIRS ? 1 : p.sub), p.J);
+                 p.name, p.per_launch, p.J);
         o += t;
     }
     o += "]}";
@@ -2169,45 +2145,34 @@ static int check_batch(mav_ctx* c, int batch, const char* fn)
     return MAV_OK;
 }
 
-extern "C" int mav_farneback(mav_ctx* c, const uint8_t* prev, const uint8_t* next, int batch, float* flow)
+// The three host-pointer entry points: frames (and the initial flow, if any) up, farneback_dev in place on the device, flow down.
+static int farneback_host(mav_ctx* c, const char* fn, const void* prev, const void* next, int depth, int batch, const float* flow_init,
+                          bool need_init, float* flow)
 {
-    CHK(check_batch(c, batch, "mav_farneback"));
-    if (!prev || !next || !flow) return fail(MAV_ERR_ARG, "mav_farneback: NULL argument");
-    const size_t n = c->n0 * batch;
-    DevBuf dp, dn, df;
-    const void *dprev, *dnext;
-    CHK(upload_frames(c, prev, next, batch, 1, dp, dn, &dprev, &dnext)); CHK(df.alloc(c, n * 2 * sizeof(float)));
-    CHK(mav_farneback_dev(c, (const uint8_t*)dprev, (const uint8_t*)dnext, batch, df.as<float>()));
-    CHK(download(c, flow, df.p, n * 2 * sizeof(float)));
-    return mav_sync(c);
-}
-
-extern "C" int mav_farneback_init(mav_ctx* c, const uint8_t* prev, const uint8_t* next, int batch, const float* flow_init, float* flow)
-{
-    CHK(check_batch(c, batch, "mav_farneback_init"));
-    if (!prev || !next || !flow_init || !flow) return fail(MAV_ERR_ARG, "mav_farneback_init: NULL argument");
-    const size_t n = c->n0 * batch;
-    DevBuf dp, dn, df;
-    const void *dprev, *dnext;
-    CHK(upload_frames(c, prev, next, batch, 1, dp, dn, &dprev, &dnext)); CHK(df.upload(c, flow_init, n * 2 * sizeof(float)));
-    CHK(mav_farneback_init_dev(c, (const uint8_t*)dprev, (const uint8_t*)dnext, batch, df.as<float>(), df.as<float>()));      // in place on the device
-    CHK(download(c, flow, df.p, n * 2 * sizeof(float)));
-    return mav_sync(c);
-}
-extern "C" int mav_farneback_ex(mav_ctx* c, const void* prev, const void* next, int depth, int batch, const float* flow_init, float* flow)
-{
-    if (c && !depth_esize(depth)) return fail(MAV_ERR_ARG, "mav_farneback_ex: depth %d is none of MAV_DEPTH_8U / 16U / 32F", depth);
-    CHK(check_batch(c, batch, "mav_farneback_ex"));
-    if (!prev || !next || !flow) return fail(MAV_ERR_ARG, "mav_farneback_ex: NULL argument");
+    if (c && !depth_esize(depth)) return fail(MAV_ERR_ARG, "%s: depth %d is none of MAV_DEPTH_8U / 16U / 32F", fn, depth);
+    CHK(check_batch(c, batch, fn));
+    if (!prev || !next || !flow || (need_init && !flow_init)) return fail(MAV_ERR_ARG, "%s: NULL argument", fn);
     const size_t n = c->n0 * batch;
     DevBuf dp, dn, df;
     const void *dprev, *dnext;
     CHK(upload_frames(c, prev, next, batch, depth_esize(depth), dp, dn, &dprev, &dnext));
     if (flow_init) CHK(df.upload(c, flow_init, n * 2 * sizeof(float)));
     else CHK(df.alloc(c, n * 2 * sizeof(float)));
-    CHK(mav_farneback_ex_dev(c, dprev, dnext, depth, batch, flow_init ? df.as<float>() : nullptr, df.as<float>()));      // in place on the device
+    CHK(farneback_dev(c, fn, dprev, dnext, depth, batch, flow_init ? df.as<float>() : nullptr, false, df.as<float>()));
     CHK(download(c, flow, df.p, n * 2 * sizeof(float)));
     return mav_sync(c);
+}
+extern "C" int mav_farneback(mav_ctx* c, const uint8_t* prev, const uint8_t* next, int batch, float* flow)
+{
+    return farneback_host(c, "mav_farneback", prev, next, MAV_DEPTH_8U, batch, nullptr, false, flow);
+}
+extern "C" int mav_farneback_init(mav_ctx* c, const uint8_t* prev, const uint8_t* next, int batch, const float* flow_init, float* flow)
+{
+    return farneback_host(c, "mav_farneback_init", prev, next, MAV_DEPTH_8U, batch, flow_init, true, flow);
+}
+extern "C" int mav_farneback_ex(mav_ctx* c, const void* prev, const void* next, int depth, int batch, const float* flow_init, float* flow)
+{
+    return farneback_host(c, "mav_farneback_ex", prev, next, depth, batch, flow_init, false, flow);
 }
 extern "C" int mav_derotate(mav_ctx* c, const float* flow, const double* omega, const double* dt, int batch, double* flow_out)
 {
