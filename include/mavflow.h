@@ -464,6 +464,33 @@ int mav_worker_wait_enqueued(mav_ctx*, uint64_t ticket);
  * the PNG specification.  MAV_ERR_ARG for any other filter type.  (zlib inflate and chunk parsing: mavflow/frame_source.py, Python stdlib.) */
 int mav_png_unfilter(const uint8_t* raw, int rows, size_t stride, int bpp, uint8_t* out);
 
+/* ---- PNG files of 8-bit images, encoded on the device -------------------------------------------------------------------------------
+ * What cv2.imwrite(name + ".png", img) stores for the loop's images [src/processor.py:364-374], minus the few hundred bytes of chunk
+ * framing (signature, IHDR, IDAT length + CRC, IEND: mavflow/frame_source.py png_wrap, host code): per image ONE complete RFC 1950 zlib
+ * stream whose inflated bytes are the PNG scanline stream -- per row the filter-type byte 1 (Sub) and W * channels filtered bytes, gray /
+ * RGB / RGBA (the B <-> R swap of a BGR(A) image happens on load).  Images are (count, H, W, channels) u8 of the context's W x H,
+ * channels = 1 (gray), 3 (BGR) or 4 (BGRA); count is not bound by max_batch.  The streams of a call are packed back to back into `out`
+ * from offset 0 in image order; index[i] = (offset, size) of image i.  Any inflater reads them; they are NOT the bytes zlib would
+ * produce (independent 24 KB segments, byte-run matches only) and the same image gives the same bytes on every call.
+ * mav_png_bound: the most bytes one image's stream can take, raw + 5 * ceil(raw / 24576) + 6 with raw = H * (1 + W * channels) -- no
+ * context, no GPU; 0 for a bad argument.
+ * MAV_ERR_ARG: channels not 1 / 3 / 4, count < 1, W * channels >= 2^31 - 1.  out_bytes: the _dev form needs count * mav_png_bound(...)
+ * (it cannot know the sizes); the host forms accept any size and fail with MAV_ERR_ARG, naming the bytes needed, when the streams do
+ * not fit -- count * mav_png_bound(...) always does.  The encoder's workspace (at most 256 MB, or one image's) is allocated by the first
+ * encode call and reported by mav_mem_info. */
+size_t mav_png_bound(int W, int H, int channels);
+int mav_png_encode_dev(mav_ctx*, const uint8_t* imgs_dev, int count, int channels, uint8_t* out_dev, size_t out_bytes,
+                       uint64_t* index_dev /* count x (offset, size) */);          /* enqueue only, on the context's stream */
+int mav_png_encode(mav_ctx*, const uint8_t* imgs_host, int count, int channels, uint8_t* out_host, size_t out_bytes,
+                   uint64_t* index /* count x (offset, size) */);                   /* host in / out, synchronous */
+/* mav_last_render with the images encoded where they were rendered: only the index and the streams cross PCIe.  index: (images wanted)
+ * x batch entries, result / flow / phi order.  MAV_ERR_STATE exactly as mav_last_render. */
+int mav_last_render_png(mav_ctx*, int batch, int want_result, int want_flow, int want_phi, uint8_t* out_host, size_t out_bytes,
+                        uint64_t* index);
+/* mav_last_overlay likewise: frames and foe_gt up, `batch` streams and the written flags back.  MAV_ERR_* exactly as mav_last_overlay. */
+int mav_last_overlay_png(mav_ctx*, const uint8_t* frames, const double* foe_gt, int batch, int radius, uint8_t* out_host,
+                         size_t out_bytes, uint64_t* index, uint8_t* written);
+
 /* HIP-event timing on the context's stream (bench.py): start/stop bracket enqueued work; stop synchronises. */
 int mav_timer_start(mav_ctx*);
 int mav_timer_stop(mav_ctx*, float* ms);

@@ -385,6 +385,8 @@ struct mav_ctx {
     struct Block { void* p = nullptr; size_t cap = 0; };
     std::vector<Block> scratch;
     size_t scratch_next = 0;
+    uint8_t* png_ws = nullptr;                  // PNG encoder: segment slots and records of one chunk of images (first encode call, grow-only)
+    size_t png_ws_bytes = 0;
     uint8_t* pyr_ws = nullptr;                  // analyze_pyramid level images (lazily, max_batch)
     size_t pyr_ws_bytes = 0;
     unsigned long long* sat = nullptr;          // optimize_window summed-area tables (lazily, max_batch)
@@ -557,7 +559,7 @@ extern "C" int mav_destroy(mav_ctx* c)
         for (void* b : wb) if (b) hipFree(b);
     }
     void* bufs[] = {c->flow_ws, c->init_snap, c->foe_sc.cand, c->foe_sc.count, c->foe_sc.best_key, c->foe_sc.done, c->foe_dev, c->box_acc, c->u64_scratch,
-                    c->i32_scratch, c->derot_dev, c->pyr_ws, c->sat, c->render_max, c->render_derot};
+                    c->i32_scratch, c->derot_dev, c->pyr_ws, c->sat, c->render_max, c->render_derot, c->png_ws};
     for (void* b : bufs) if (b) hipFree(b);
     for (auto& blk : c->scratch) if (blk.p) hipFree(blk.p);
     for (auto& r : c->prof) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
@@ -833,7 +835,7 @@ extern "C" int mav_mem_info(mav_ctx* c, size_t* dev_free, size_t* dev_total, siz
     if (workspace_bytes) *workspace_bytes = c->ws_bytes;
     if (ctx_bytes) {
         const size_t B = (size_t)c->max_batch;
-        size_t n = c->ws_bytes + c->pyr_ws_bytes;
+        size_t n = c->ws_bytes + c->pyr_ws_bytes + c->png_ws_bytes;
         if (c->flow_ws) n += sizeof(float) * 2 * c->n0 * B;
         if (c->sat) n += sizeof(unsigned long long) * (size_t)(c->W + 1) * (c->H + 1) * B;
         if (c->foe_sc.cand) n += sizeof(double) * 2 * (size_t)c->foe_sc_n * B;
@@ -2823,6 +2825,134 @@ extern "C" int mav_last_overlay(mav_ctx* c, const uint8_t* frames, const double*
     const mav_ctx::LastRender& r = c->last_render;
     CHK(mav_overlay_dev(c, df.as<uint8_t>(), r.mask_fixed, r.foe, dgt.as<double>(), batch, radius, dout.as<uint8_t>(), dw.as<uint8_t>()));
     return download_overlay(c, batch, dout, dw, overlay, written);
+}
+
+// ---- PNG files of device-resident images (include/mavflow.h: mav_png_encode) -------------------------------------------------------
+static size_t png_raw(int W, int H, int channels) { return (size_t)H * ((size_t)W * channels + 1); }
+extern "C" size_t mav_png_bound(int W, int H, int channels)
+{
+    if (W < 1 || H < 1 || (channels != 1 && channels != 3 && channels != 4)) return 0;
+    const size_t raw = png_raw(W, H, channels);
+    return raw + 5 * png_segments(raw) + 6;
+}
+static int check_png_args(mav_ctx* c, const char* fn, int count, int channels, size_t out_bytes, bool need_bound)
+{
+    if (!c) return fail(MAV_ERR_ARG, "%s: NULL context", fn);
+    if (channels != 1 && channels != 3 && channels != 4) return fail(MAV_ERR_ARG, "%s: channels %d is none of 1 (gray), 3 (BGR), 4 (BGRA)", fn, channels);
+    if (count < 1) return fail(MAV_ERR_ARG, "%s: count %d < 1", fn, count);
+    if ((size_t)c->W * channels >= ((size_t)1 << 31) - 1) return fail(MAV_ERR_ARG, "%s: a row of %d x %d bytes is too long", fn, c->W, channels);
+    const size_t bound = mav_png_bound(c->W, c->H, channels);
+    if (need_bound && out_bytes / bound < (size_t)count)
+        return fail(MAV_ERR_ARG, "%s: out_bytes %zu < count x mav_png_bound = %d x %zu", fn, out_bytes, count, bound);
+    return MAV_OK;
+}
+// The encoder's workspace holds the segments of one CHUNK of images (at most kPngChunkBytes, one image at least): a call of many
+// images runs the launch chain once per chunk, every chunk packing its streams behind the previous one's.
+static const size_t kPngChunkBytes = (size_t)256 << 20;
+extern "C" int mav_png_encode_dev(mav_ctx* c, const uint8_t* imgs, int count, int channels, uint8_t* out, size_t out_bytes, uint64_t* index)
+{
+    CHK(check_png_args(c, "mav_png_encode_dev", count, channels, out_bytes, true));
+    if (!imgs || !out || !index) return fail(MAV_ERR_ARG, "mav_png_encode_dev: NULL argument");
+    HIPCHK(hipSetDevice(c->device));
+    const size_t per = (png_workspace_per_image(png_raw(c->W, c->H, channels)) + 15) & ~(size_t)15;
+    size_t chunk = kPngChunkBytes / per;
+    if (chunk < 1) chunk = 1;
+    if (chunk > (size_t)count) chunk = count;
+    if (chunk > 65535) chunk = 65535;
+    if (c->png_ws_bytes < chunk * per) {
+        if (c->png_ws) { HIPCHK(hipStreamSynchronize(c->stream)); hipFree(c->png_ws); c->png_ws = nullptr; c->png_ws_bytes = 0; }
+        if (hipMalloc(&c->png_ws, chunk * per) != hipSuccess) {
+            (void)hipGetLastError();
+            c->png_ws = nullptr;
+            return fail(MAV_ERR_OOM, "mav_png_encode_dev: %zu bytes of encoder workspace", chunk * per);
+        }
+        c->png_ws_bytes = chunk * per;
+    }
+    ProfScope ps(c, K_MISC);
+    for (int i0 = 0; i0 < count; i0 += (int)chunk) {
+        const int n = count - i0 < (int)chunk ? count - i0 : (int)chunk;
+        launch_png_encode(c->stream, imgs, i0, n, c->W, c->H, channels, c->png_ws, out, (unsigned long long*)index);
+    }
+    return check_launch("png_encode");
+}
+// the index, then the streams (packed from offset 0) of `count` encoded images -> host
+static int download_png(mav_ctx* c, const char* fn, int count, const DevBuf& dout, const DevBuf& didx, uint8_t* out_host, size_t out_bytes,
+                        uint64_t* index)
+{
+    CHK(download(c, index, didx.p, sizeof(uint64_t) * 2 * count));
+    CHK(mav_sync(c));
+    const size_t total = (size_t)(index[2 * (count - 1)] + index[2 * (count - 1) + 1]);
+    if (total > out_bytes) return fail(MAV_ERR_ARG, "%s: out_bytes %zu, the %d streams take %zu", fn, out_bytes, count, total);
+    CHK(download(c, out_host, dout.p, total));
+    return mav_sync(c);
+}
+extern "C" int mav_png_encode(mav_ctx* c, const uint8_t* imgs, int count, int channels, uint8_t* out_host, size_t out_bytes, uint64_t* index)
+{
+    CHK(check_png_args(c, "mav_png_encode", count, channels, out_bytes, false));
+    if (!imgs || !out_host || !index) return fail(MAV_ERR_ARG, "mav_png_encode: NULL argument");
+    HIPCHK(hipSetDevice(c->device));
+    c->scratch_next = 0;
+    c->last_mf = c->last_md = nullptr; c->last_mask_batch = 0;
+    c->last_render.batch = 0;
+    const size_t bound = mav_png_bound(c->W, c->H, channels) * count;
+    DevBuf di, dout, didx;
+    CHK(di.upload(c, imgs, c->n0 * channels * count));
+    CHK(dout.alloc(c, bound));
+    CHK(didx.alloc(c, sizeof(uint64_t) * 2 * count));
+    CHK(mav_png_encode_dev(c, di.as<uint8_t>(), count, channels, dout.as<uint8_t>(), bound, didx.as<uint64_t>()));
+    return download_png(c, "mav_png_encode", count, dout, didx, out_host, out_bytes, index);
+}
+
+extern "C" int mav_last_render_png(mav_ctx* c, int batch, int want_result, int want_flow, int want_phi, uint8_t* out_host, size_t out_bytes,
+                                   uint64_t* index)
+{
+    if (!c) return fail(MAV_ERR_ARG, "mav_last_render_png: NULL context");
+    if (!c->last_render.batch || batch != c->last_render.batch)
+        return fail(MAV_ERR_STATE, "mav_last_render_png: no flow of a %d-pair detection call is resident", batch);
+    HIPCHK(hipSetDevice(c->device));
+    const int want[3] = {want_result != 0, want_flow != 0, want_phi != 0}, nimg = want[0] + want[1] + want[2];
+    if (!nimg) return MAV_OK;
+    if (!out_host || !index) return fail(MAV_ERR_ARG, "mav_last_render_png: NULL argument");
+    const size_t per = c->n0 * 3 * batch, bound = mav_png_bound(c->W, c->H, 3) * nimg * batch, mark = c->scratch_next;
+    // as mav_last_render: the NEXT free staging blocks, the detection call's own blocks stay untouched
+    DevBuf dimg, dout, didx;
+    CHK(dimg.alloc(c, per * nimg));
+    CHK(dout.alloc(c, bound));
+    CHK(didx.alloc(c, sizeof(uint64_t) * 2 * nimg * batch));
+    c->scratch_next = mark;
+    uint8_t* dev[3] = {nullptr, nullptr, nullptr};
+    for (int k = 0, j = 0; k < 3; k++)
+        if (want[k]) dev[k] = dimg.as<uint8_t>() + per * j++;
+    const mav_ctx::LastRender& r = c->last_render;
+    CHK(render_enqueue(c, r.flow, r.derot, r.foe, r.sky, batch, r.thr, dev[0], dev[1], dev[2]));
+    CHK(mav_png_encode_dev(c, dimg.as<uint8_t>(), nimg * batch, 3, dout.as<uint8_t>(), bound, didx.as<uint64_t>()));
+    return download_png(c, "mav_last_render_png", nimg * batch, dout, didx, out_host, out_bytes, index);
+}
+
+extern "C" int mav_last_overlay_png(mav_ctx* c, const uint8_t* frames, const double* foe_gt, int batch, int radius, uint8_t* out_host,
+                                    size_t out_bytes, uint64_t* index, uint8_t* written)
+{
+    if (!c || !frames || !foe_gt || !out_host || !index || !written) return fail(MAV_ERR_ARG, "mav_last_overlay_png: NULL argument");
+    if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "mav_last_overlay_png: batch %d outside [1, %d]", batch, c->max_batch);
+    if (!c->last_render.batch || batch != c->last_render.batch || !c->last_render.mask_fixed)
+        return fail(MAV_ERR_STATE, "mav_last_overlay_png: no fixed mask of a %d-pair detection call is resident", batch);
+    CHK(check_radius(radius, "mav_last_overlay_png"));
+    CHK(check_foe_host(foe_gt, batch, "foe_gt", "mav_last_overlay_png"));
+    HIPCHK(hipSetDevice(c->device));
+    const size_t n = c->n0 * batch, bound = mav_png_bound(c->W, c->H, 3) * batch, mark = c->scratch_next;
+    DevBuf df, dgt, dimg, dw, dout, didx;
+    CHK(df.upload(c, frames, n * 3));
+    CHK(dgt.upload(c, foe_gt, sizeof(double) * 2 * batch));
+    CHK(dimg.alloc(c, n * 3));
+    CHK(dw.alloc(c, batch));
+    CHK(dout.alloc(c, bound));
+    CHK(didx.alloc(c, sizeof(uint64_t) * 2 * batch));
+    c->scratch_next = mark;
+    const mav_ctx::LastRender& r = c->last_render;
+    CHK(mav_overlay_dev(c, df.as<uint8_t>(), r.mask_fixed, r.foe, dgt.as<double>(), batch, radius, dimg.as<uint8_t>(), dw.as<uint8_t>()));
+    CHK(mav_png_encode_dev(c, dimg.as<uint8_t>(), batch, 3, dout.as<uint8_t>(), bound, didx.as<uint64_t>()));
+    CHK(download(c, written, dw.p, batch));
+    return download_png(c, "mav_last_overlay_png", batch, dout, didx, out_host, out_bytes, index);
 }
 
 extern "C" int mav_process_batch(mav_ctx* c, const uint8_t* prev, const uint8_t* next, const uint32_t* samples, const double* omega,

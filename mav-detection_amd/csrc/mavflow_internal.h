@@ -173,3 +173,15 @@ void launch_pyramid_finalize(hipStream_t st, const unsigned long long* key, cons
                              const uint8_t* ws, int B, int64_t* out /*[B][6]*/);
 void launch_optimize_window(hipStream_t st, const uint8_t* img, int B, int W, int H, unsigned long long* sat /*[B][(H+1)(W+1)]*/,
                             const int32_t* win_in, int64_t* score, int32_t* win_out);
+
+// ---- PNG encoder (kernels_png.hip) ------------------------------------------------------------------------------------
+// An image's scanline stream (per row the filter byte + W * C bytes) is deflated in independent segments of MAV_PNG_SEG bytes, one
+// workgroup each; a segment costs at most its length + 5 bytes (the stored form) and is built in a slot of MAV_PNG_SLOT bytes.
+#define MAV_PNG_SEG 24576
+#define MAV_PNG_SLOT (MAV_PNG_SEG + 16)
+size_t png_segments(size_t raw);                 // segments of a scanline stream of `raw` bytes
+size_t png_workspace_per_image(size_t raw);      // device bytes launch_png_encode needs per image of a launch chain
+// images img0 .. img0 + nimg - 1 of `imgs` ((H, W, C) u8 each; C = 1 gray, 3 BGR, 4 BGRA) -> their zlib streams, packed into `out`
+// behind the streams of the images before them; index[i] = (offset, size) of image i.  index[img0 - 1] must be complete (same stream).
+void launch_png_encode(hipStream_t st, const uint8_t* imgs, int img0, int nimg, int W, int H, int C, uint8_t* ws, uint8_t* out,
+                       unsigned long long* index);

@@ -58,6 +58,7 @@ EXPORTS = [
     "mav_farneback_ex", "mav_farneback_ex_dev", "mav_stage_blur_resize_ex", "mav_schedule_info_ex",
     "mav_render", "mav_render_dev", "mav_last_render", "mav_flow_to_color", "mav_colormap_jet",
     "mav_overlay", "mav_overlay_dev", "mav_last_overlay",
+    "mav_png_bound", "mav_png_encode", "mav_png_encode_dev", "mav_last_render_png", "mav_last_overlay_png",
 ]
 
 # Frame depths of the _ex entry points (cv2's depth codes) by numpy dtype.  uint8 frames keep going through the u8 symbols.
@@ -113,7 +114,7 @@ def load(path: str | None = None) -> C.CDLL:
     lib.mav_last_flow_dev.restype = C.c_void_p
     for name in EXPORTS:
         fn = getattr(lib, name)
-        if name not in ("mav_last_error", "mav_stream", "mav_fb_defaults", "mav_foe_defaults", "mav_thr_defaults", "mav_last_flow_dev"):
+        if name not in ("mav_last_error", "mav_stream", "mav_fb_defaults", "mav_foe_defaults", "mav_thr_defaults", "mav_last_flow_dev", "mav_png_bound"):
             fn.restype = C.c_int
     lib.mav_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FbParams)]
     lib.mav_destroy.argtypes = [C.c_void_p]
@@ -216,6 +217,12 @@ def load(path: str | None = None) -> C.CDLL:
     lib.mav_overlay.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp]
     lib.mav_overlay_dev.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp]
     lib.mav_last_overlay.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp]
+    lib.mav_png_bound.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.mav_png_bound.restype = C.c_size_t
+    lib.mav_png_encode.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_size_t, vp]
+    lib.mav_png_encode_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_size_t, vp]
+    lib.mav_last_render_png.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp]
+    lib.mav_last_overlay_png.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_size_t, vp, vp]
     _lib = lib
     return lib
 
@@ -921,6 +928,67 @@ class Context:
     def overlay_dev(self, frames_ptr, mask_ptr, foe_ptr, foe_gt_ptr, batch: int, overlay_ptr, written_ptr, radius: int = OVERLAY_RADIUS):
         """mav_overlay_dev: enqueue only, device pointers."""
         check(self.lib.mav_overlay_dev(self.h, frames_ptr, mask_ptr, foe_ptr, foe_gt_ptr, int(batch), int(radius), overlay_ptr, written_ptr))
+
+    # -- PNG files encoded on the device -----------------------------------------------------------------------
+    def _png_out(self, count: int, channels: int):
+        """(stream buffer of count x mav_png_bound bytes, index (count, 2) uint64).  The buffer is kept between calls (grow-only): it
+        is virtual memory until written, and the pages the streams really take are then touched once."""
+        need = self.lib.mav_png_bound(self.W, self.H, channels) * count
+        buf = getattr(self, "_png_buf", None)
+        if buf is None or buf.size < need:
+            buf = self._png_buf = np.empty(need, np.uint8)
+        return buf[:need], np.empty((count, 2), np.uint64)
+
+    def _png_files(self, out, index, channels: int, wrap: bool = True):
+        """the files of the streams in `out` -- or, wrap=False, (W, H, channels, stream bytes) tuples for frame_source.png_wrap, for a
+        caller that adds the chunk framing (two CRC passes over the stream) somewhere else, e.g. on its writer threads"""
+        from .frame_source import png_wrap
+        streams = [out[int(o):int(o) + int(n)].tobytes() for o, n in index]
+        return [png_wrap(self.W, self.H, channels, z) if wrap else (self.W, self.H, channels, z) for z in streams]
+
+    def png_encode(self, imgs) -> list:
+        """Complete PNG files (bytes) of 8-bit images, deflated on the device: (H, W) / (H, W, 1) gray, (H, W, 3) BGR, (H, W, 4) BGRA, or a
+        batch of them with one more leading axis (a 3-d array whose last axis is 1, 3 or 4 long is ONE image).  Any PNG reader decodes
+        them to exactly the pixels frame_source.encode_png's files hold; the bytes differ (Sub filter, run-length matches)."""
+        a = np.asarray(imgs)
+        if a.dtype != np.uint8:
+            raise TypeError(f"png_encode() takes uint8 images, got {a.dtype}")
+        if a.ndim == 2:
+            a = a[None, :, :, None]
+        elif a.ndim == 3:
+            a = a[None] if a.shape == (self.H, self.W, a.shape[2]) and a.shape[2] in (1, 3, 4) else a[..., None]
+        if a.ndim != 4 or a.shape[1:3] != (self.H, self.W) or a.shape[0] < 1:
+            raise ValueError(f"png_encode(): expected (batch, {self.H}, {self.W}[, channels]) images, got {np.shape(imgs)}")
+        count, ch = a.shape[0], a.shape[3]
+        if ch not in (1, 3, 4):
+            raise ValueError(f"png_encode(): channels must be 1, 3 or 4, got {ch}")
+        a = np.ascontiguousarray(a)
+        out, index = self._png_out(count, ch)
+        check(self.lib.mav_png_encode(self.h, _ptr(a), count, ch, _ptr(out), out.size, _ptr(index)))
+        return self._png_files(out, index, ch)
+
+    def render_last_png(self, batch: int, images=IMAGES, wrap: bool = True) -> dict:
+        """render_last() as PNG files: {name: [bytes per pair]}; rendered and deflated on the device, only the files' data comes back.
+        wrap=False: png_wrap's argument tuples instead of files (see _png_files)."""
+        bad = set(images) - set(self.IMAGES)
+        if bad:
+            raise ValueError(f"unknown image(s) {sorted(bad)}; choose from {self.IMAGES}")
+        names = [k for k in self.IMAGES if k in images]
+        out, index = self._png_out(max(1, len(names)) * int(batch), 3)
+        check(self.lib.mav_last_render_png(self.h, int(batch), int("result" in names), int("flow" in names), int("phi" in names), _ptr(out),
+                                           out.size, _ptr(index)))
+        files = self._png_files(out, index, 3, wrap) if names else []
+        return {k: files[j * batch:(j + 1) * batch] for j, k in enumerate(names)}
+
+    def overlay_last_png(self, frames, foe_gt, radius: int = OVERLAY_RADIUS, wrap: bool = True):
+        """overlay_last() as PNG files: ([bytes per pair], written (B,) bool).  wrap=False: as render_last_png."""
+        frames = self._bgr_frames(frames)
+        B = frames.shape[0]
+        gt = self._foes(foe_gt, B, "foe_gt")
+        out, index = self._png_out(B, 3)
+        wr = np.empty(B, np.uint8)
+        check(self.lib.mav_last_overlay_png(self.h, _ptr(frames), _ptr(gt), B, int(radius), _ptr(out), out.size, _ptr(index), _ptr(wr)))
+        return self._png_files(out, index, 3, wrap), wr.view(np.bool_)
 
     # -- device-pointer path (bench, multi-GPU) --------------------------------------------------------------
     def process_batch_dev(self, prev_ptr, next_ptr, samples_ptr, batch, results_ptr, flow_ptr=None, omega_ptr=None,

@@ -8,6 +8,8 @@ cv2 is not part of this build; this module is that capture for PNG sequences:
                                          interlaced; 16-bit samples are narrowed to their high byte, which is what cv2.imread's
                                          default flag does (libpng's png_set_strip_16).
     imread(path) -> BGR u8 (H, W, 3)     what cv2.imread(path) (IMREAD_COLOR) returns: gray replicated, alpha dropped, palette expanded.
+    png_wrap(W, H, channels, zstream)    the PNG file around a zlib stream of scanline data that was deflated elsewhere (on the device:
+                                         Context.png_encode / render_last_png / overlay_last_png).
     PngSequenceCapture(pattern)          cv2.VideoCapture(pattern)'s read() / get(3|4|7) / isOpened() / release() for an image sequence.
 
 The decoder is pinned by PIL-decoded fixtures generated in the build container (tools/gen_png_fixtures.py,
@@ -161,6 +163,19 @@ def encode_png(img: np.ndarray, level: int = 1) -> bytes:
     raw[:, 1:] = rows.reshape(H, -1)
     return (PNG_MAGIC + _chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, ctype, 0, 0, 0))
             + _chunk(b"IDAT", zlib.compress(raw.tobytes(), level)) + _chunk(b"IEND", b""))
+
+
+def png_wrap(W: int, H: int, channels: int, zstream: bytes) -> bytes:
+    """The PNG file around a finished zlib stream of the scanline data (Context.png_encode builds such streams on the device): signature,
+    IHDR (8-bit; colour type 0 gray / 2 RGB / 6 RGBA, as encode_png writes them), one IDAT, IEND."""
+    ctype = {1: 0, 3: 2, 4: 6}.get(channels)
+    if ctype is None:
+        raise ValueError(f"png_wrap: channels must be 1, 3 or 4, got {channels}")
+    if W < 1 or H < 1:
+        raise ValueError(f"png_wrap: empty image {W} x {H}")
+    crc = zlib.crc32(zstream, zlib.crc32(b"IDAT")) & 0xFFFFFFFF          # the stream is read in place: a memoryview is as good as bytes
+    return b"".join((PNG_MAGIC, _chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, ctype, 0, 0, 0)), struct.pack(">I", len(zstream)), b"IDAT",
+                     zstream, struct.pack(">I", crc), _chunk(b"IEND", b"")))
 
 
 def imwrite(path: str, img: np.ndarray) -> bool:

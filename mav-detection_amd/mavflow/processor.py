@@ -15,7 +15,9 @@ Each loop writes `{results_path}/image_{i:05d}.json` per frame as the reference'
 constructor) names a results_path.  With an explicit images_path each loop also writes the three result images of :364-374 per frame,
 `{images_path}/result-images|derotated|phi/image_{i:05d}.png`, rendered on the device (mav_last_render: one launch behind the
 frame's step, the flow is not moved again) and PNG-encoded by a pool of at most 16 threads off the loop's thread; every file is
-complete when the loop returns.  With a processed_path each loop also writes the frame the reference appends to processed.mp4 (:376-392:
+complete when the loop returns.  Processor(..., png_encoder="device") moves the encoder of the fast loops to where the pixels are
+(mav_last_render_png / mav_last_overlay_png: only the compressed streams cross PCIe, the pool adds the chunk framing and writes); the files decode to
+the same pixels, their bytes differ.  The staged loop always encodes on the host.  With a processed_path each loop also writes the frame the reference appends to processed.mp4 (:376-392:
 FoE discs on the frame, the fixed mask painted purple, blended 0.2 / 0.8) as `{processed_path}/image_{i:05d}.png` for every frame the
 reference would write (np.sum(result_img) > 0); the fast loops render it on the device from the resident mask and FoE
 (mav_last_overlay), the staged loop composes it from draw_FoE, the painted mask and add_weighted.  No video container is encoded: the
@@ -169,9 +171,18 @@ PNG_WORKERS = 16                     # encoder threads at most
 PNG_BACKLOG = 4 * PNG_WORKERS        # files queued before the loop waits for the oldest
 
 
+def _write_stream(path: str, stream) -> None:
+    """The PNG file around a zlib stream the device produced (stream: frame_source.png_wrap's argument tuple)."""
+    with open(path, "wb") as f:
+        f.write(frame_source.png_wrap(*stream))
+
+
 class Processor:
     def __init__(self, config: RunConfig, results_path: Optional[str] = None, images_path: Optional[str] = None,
-                 processed_path: Optional[str] = None) -> None:
+                 processed_path: Optional[str] = None, png_encoder: str = "host") -> None:
+        if png_encoder not in ("host", "device"):
+            raise ValueError(f"png_encoder must be 'host' or 'device', got {png_encoder!r}")
+        self.png_encoder = png_encoder
         self.config = config
         self.logger = config.logger
         self.sequence = config.sequence
@@ -298,7 +309,8 @@ class Processor:
 
     # -- result images (processor.py:364-374) ----------------------------------------------------------------------------------------
     def _queue_png(self, d: str, i: int, img) -> None:
-        """Queue the PNG file {d}/image_{i:05d}.png on the encoder pool (at most PNG_BACKLOG files queued)."""
+        """Queue the PNG file {d}/image_{i:05d}.png on the encoder pool (at most PNG_BACKLOG files queued).  img: an image to encode, or
+        the stream of one encoded on the device (png_wrap's argument tuple), which only remains to be framed and written."""
         if d not in self._dirs_made:
             os.makedirs(d, exist_ok=True)
             self._dirs_made.add(d)
@@ -306,10 +318,11 @@ class Processor:
             self._png_pool = ThreadPoolExecutor(max_workers=min(PNG_WORKERS, os.cpu_count() or 1), thread_name_prefix="png")
         while len(self._png_jobs) >= PNG_BACKLOG:
             self._png_jobs.popleft().result()
-        self._png_jobs.append(self._png_pool.submit(frame_source.imwrite, os.path.join(d, f"image_{i:05d}.png"), img))
+        job = _write_stream if isinstance(img, tuple) else frame_source.imwrite
+        self._png_jobs.append(self._png_pool.submit(job, os.path.join(d, f"image_{i:05d}.png"), img))
 
     def _write_images(self, ids, imgs) -> None:
-        """Queue the PNG files of frames `ids`; imgs: Context.render's dict of (n, H, W, 3) BGR arrays."""
+        """Queue the PNG files of frames `ids`; imgs: Context.render's dict of (n, H, W, 3) BGR arrays, or render_last_png's of files."""
         for k, i in enumerate(ids):
             for name, d in IMAGE_DIRS.items():
                 self._queue_png(os.path.join(self.images_path, d), i, imgs[name][k])
@@ -454,10 +467,11 @@ class Processor:
         self.detection_boxes[i] = utils.Rectangle.from_box(rec["box"])
         self._store(i, r)
         ctx = pipe.pipes[ticket[0]].ctx
+        dev = self.png_encoder == "device"
         if self.images_path is not None:
-            self._write_images([i], ctx.render_last(1))
+            self._write_images([i], ctx.render_last_png(1, wrap=False) if dev else ctx.render_last(1))
         if self.processed_path is not None:
-            self._write_processed([i], *ctx.overlay_last(orig_frame, [r.foe_gt]))
+            self._write_processed([i], *(ctx.overlay_last_png(orig_frame, [r.foe_gt], wrap=False) if dev else ctx.overlay_last(orig_frame, [r.foe_gt])))
 
     def run_detection_staged(self) -> Dict[int, FrameResult]:
         """The same loop through the reference-named calls one by one (Detector.derotate, get_FOE_dense, the masks): every call
@@ -551,10 +565,12 @@ class Processor:
             self._store(i, r)
             gts.append(r.foe_gt)
         ctx = pipe.pipes[ticket[0]].ctx
+        dev = self.png_encoder == "device"
         if self.images_path is not None:
-            self._write_images(ids, ctx.render_last(len(ids)))
+            self._write_images(ids, ctx.render_last_png(len(ids), wrap=False) if dev else ctx.render_last(len(ids)))
         if self.processed_path is not None:
-            self._write_processed(ids, *ctx.overlay_last(np.stack(frames), gts))
+            frames = np.stack(frames)
+            self._write_processed(ids, *(ctx.overlay_last_png(frames, gts, wrap=False) if dev else ctx.overlay_last(frames, gts)))
         self.estimate_fixed, self.total_mask = out["mask_fixed"][-1], out["mask_dyn"][-1]     # of the last frame, as the loop leaves them
 
     def release(self) -> None:
