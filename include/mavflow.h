@@ -491,6 +491,55 @@ int mav_last_render_png(mav_ctx*, int batch, int want_result, int want_flow, int
 int mav_last_overlay_png(mav_ctx*, const uint8_t* frames, const double* foe_gt, int batch, int radius, uint8_t* out_host,
                          size_t out_bytes, uint64_t* index, uint8_t* written);
 
+/* ---- sparse optical flow: Shi-Tomasi corners and the pyramidal Lucas-Kanade tracker ------------------------------------------------
+ * cv2.goodFeaturesToTrack [src/lucas_kanade.py:53] and cv2.calcOpticalFlowPyrLK [src/lucas_kanade.py:60] on ONE 8-bit gray frame (pair)
+ * of the context's W x H per call: the sparse path is sequential, the features of call i are the tracked points of call i - 1.
+ * Restated from OpenCV's published routines with every window sum kept as an exact integer sum; cv2 itself is not pinned.
+ * Defaults: the reference's parameters, corners 2000 / 0.2 / 7 / 7 (Sobel aperture 3, min-eigenvalue score, no mask), tracker
+ * winSize (21, 21), maxLevel 3, criteria (EPS | COUNT, 30, 0.01), flags 0, minEigThreshold 1e-4.
+ * THE RESIDENT FRAME: the context keeps the frame it saw last (the `next` of mav_lk_track, or the frame given to mav_good_features) and
+ * its pyramid on the device.  Passing NULL for `prev` / `gray` means that frame: a video uploads every frame once and builds its
+ * pyramid once.  MAV_ERR_STATE when there is none.  The workspace (two pyramids, one derivative pyramid, the eigenvalue map, candidates,
+ * points: 12 bytes per pixel + 3.2 MB) is allocated by the first of these calls and reported by mav_mem_info. */
+typedef struct {
+    int max_corners;          /* 1 .. MAV_LK_MAX_POINTS */
+    double quality_level;     /* > 0 */
+    double min_distance;      /* < 1: no distance test */
+    int block_size;           /* odd, 1 .. 15 */
+} mav_gftt_params;
+typedef struct {
+    int win_w, win_h;         /* odd, 3 .. MAV_LK_MAX_WIN */
+    int max_level;            /* 0 .. MAV_LK_MAX_LEVEL; lowered so that every level above 0 is wider than win_w and higher than win_h */
+    int max_count;            /* clamped to [0, 100] as cv2 does */
+    double epsilon;           /* clamped to [0, 10] as cv2 does */
+    double min_eig_threshold;
+} mav_lk_params;
+#define MAV_LK_MAX_POINTS 65536     /* points per mav_lk_track call, corners per mav_good_features call */
+#define MAV_LK_MAX_WIN 33           /* the tracker keeps a point's window (3 int16 planes) in LDS, four points per workgroup */
+#define MAV_LK_MAX_LEVEL 7
+#define MAV_GFTT_MAX_CANDIDATES 262144 /* local maxima above the quality threshold one frame may have; more is MAV_ERR_ARG, never a silent cut */
+void mav_gftt_defaults(mav_gftt_params*);
+void mav_lk_defaults(mav_lk_params*);
+/* corners (max_corners, 2) float32 (x, y) in acceptance order (strongest first; ties by linear index, larger first), *count of them.
+ * gray NULL: the resident frame; otherwise `gray` is uploaded and becomes the resident frame.  Eigenvalue map, threshold, non-maximum
+ * test and candidate compaction run on the device; the sort and the greedy minimum-distance pick run on the host inside the call. */
+int mav_good_features(mav_ctx*, const uint8_t* gray, const mav_gftt_params* /* NULL = defaults */, float* corners, int* count);
+/* next_pts (n, 2) float32 and status (n) u8 for pts (n, 2) float32, 0 <= n <= MAV_LK_MAX_POINTS.  NaN / inf / far-away points are not
+ * errors: they end with status 0 as in cv2.  `next` becomes the resident frame.  cv2's error output is not computed. */
+int mav_lk_track(mav_ctx*, const uint8_t* prev /* NULL: the resident frame */, const uint8_t* next, const float* pts, int n,
+                 const mav_lk_params* /* NULL = defaults */, float* next_pts, uint8_t* status);
+/* Device-pointer forms.  mav_lk_track_dev only enqueues (frames are copied into the workspace on the device).  mav_good_features_dev
+ * takes a device frame but returns host corners: the pick is host code, so the call synchronises. */
+int mav_good_features_dev(mav_ctx*, const uint8_t* gray_dev, const mav_gftt_params*, float* corners_host, int* count);
+int mav_lk_track_dev(mav_ctx*, const uint8_t* prev_dev, const uint8_t* next_dev, const float* pts_dev, int n, const mav_lk_params*,
+                     float* next_pts_dev, uint8_t* status_dev);
+/* Iterations the tracker's loop ran per (point, level) in the most recent track call: hist[i] = how many ran i iterations
+ * (i = 0: left the level at the first bounds test), MAV_LK_HIST_BINS bins, the last one = more.  Levels skipped before the loop do not count. */
+#define MAV_LK_HIST_BINS 104
+int mav_lk_last_iterations(mav_ctx*, uint32_t* hist);
+/* size of level `level` (0 .. MAV_LK_MAX_LEVEL) of the tracker's pyramid: level l + 1 = ((w + 1) / 2, (h + 1) / 2) */
+int mav_lk_level_dims(const mav_ctx*, int level, int* w, int* h);
+
 /* HIP-event timing on the context's stream (bench.py): start/stop bracket enqueued work; stop synchronises. */
 int mav_timer_start(mav_ctx*);
 int mav_timer_stop(mav_ctx*, float* ms);
@@ -561,6 +610,12 @@ int mav_stage_coefficients(mav_ctx*, int k, float* g, float* xg, float* xxg, flo
 
 /* pyramid level `level` (>= 0) of one u8 image: (h_l, w_l) u8, sizes from mav_pyramid_dims */
 int mav_stage_pyramid_level(mav_ctx*, const uint8_t* img, double scale, int level, uint8_t* out);
+
+/* sparse optical flow, one u8 image each (the resident frame is dropped): level `level` of the tracker's pyramid (h_l, w_l) u8; that
+ * level's Scharr pairs (h_l, w_l, 2) int16 = (Ix, Iy); the min-eigenvalue map (H, W) float32 of mav_good_features for a block size */
+int mav_stage_lk_pyramid(mav_ctx*, const uint8_t* img, int level, uint8_t* out);
+int mav_stage_lk_scharr(mav_ctx*, const uint8_t* img, int level, int16_t* out);
+int mav_stage_min_eigen(mav_ctx*, const uint8_t* img, int block_size, float* out);
 
 #ifdef __cplusplus
 }

@@ -273,11 +273,29 @@ struct Stager {
         }
     }
 };
-enum KernelId { K_BLUR_RESIZE, K_POLYEXP, K_UPDATE, K_ITER, K_ITER_COARSE, K_FOE, K_PHI, K_MISC, K_COUNT };
+enum KernelId { K_BLUR_RESIZE, K_POLYEXP, K_UPDATE, K_ITER, K_ITER_COARSE, K_FOE, K_PHI, K_MISC, K_LK_CORNERS, K_LK_PYRAMID, K_LK_TRACK, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"blur_resize", "polyexp", "update_matrices", "blur_iter", "blur_iter_coarse",
-                                                  "foe_ransac", "phi_mask_box", "misc"};
+                                                  "foe_ransac", "phi_mask_box", "misc", "lk_corners", "lk_pyramid", "lk_track"};
 struct ProfRec { int kid; hipEvent_t a, b; int stream; };
 struct ProfInterval { int kid; float t0, t1; int stream; };      // ms since the profile was switched on
+
+// Sparse optical flow (mav_good_features / mav_lk_track): everything it owns, allocated by the first such call (ensure_lk).
+struct LkState {
+    LkLevels dims{};                 // every level the frame size allows (MAV_LK_MAX_LEVEL + 1 at most), whatever the window
+    size_t pyr_elems = 0;            // elements of one pyramid block
+    uint8_t* pyr[2] = {nullptr, nullptr};   // two frame slots: the resident frame and the one before / after it
+    int built[2] = {0, 0};           // levels of the slot's pyramid that are valid (0: the slot holds no frame)
+    int cur = -1;                    // slot of the resident frame, -1: none
+    short2* deriv = nullptr;         // Scharr pairs of ONE slot's levels
+    int deriv_slot = -1, deriv_levels = 0;
+    float* eig = nullptr;            // (H, W) min-eigenvalue map
+    uint2* cand = nullptr;           // MAV_GFTT_MAX_CANDIDATES x (value bits, linear index)
+    unsigned* counters = nullptr;    // [0] max key, [1] candidate count, [2 ..] iteration histogram (MAV_LK_HIST)
+    float *pts = nullptr, *out = nullptr;   // MAV_LK_MAX_POINTS x 2 each
+    uint8_t* status = nullptr;       // MAV_LK_MAX_POINTS
+    size_t bytes = 0;                // all of the above (mav_mem_info)
+    bool hist_valid = false;
+};
 
 struct mav_ctx {
     int device = 0, W = 0, H = 0, max_batch = 0, group = 0, group_fine = 1;
@@ -385,6 +403,7 @@ struct mav_ctx {
     struct Block { void* p = nullptr; size_t cap = 0; };
     std::vector<Block> scratch;
     size_t scratch_next = 0;
+    LkState lk;                                 // sparse optical flow workspace (first mav_good_features / mav_lk_track call)
     uint8_t* png_ws = nullptr;                  // PNG encoder: segment slots and records of one chunk of images (first encode call, grow-only)
     size_t png_ws_bytes = 0;
     uint8_t* pyr_ws = nullptr;                  // analyze_pyramid level images (lazily, max_batch)
@@ -559,7 +578,8 @@ extern "C" int mav_destroy(mav_ctx* c)
         for (void* b : wb) if (b) hipFree(b);
     }
     void* bufs[] = {c->flow_ws, c->init_snap, c->foe_sc.cand, c->foe_sc.count, c->foe_sc.best_key, c->foe_sc.done, c->foe_dev, c->box_acc, c->u64_scratch,
-                    c->i32_scratch, c->derot_dev, c->pyr_ws, c->sat, c->render_max, c->render_derot, c->png_ws};
+                    c->i32_scratch, c->derot_dev, c->pyr_ws, c->sat, c->render_max, c->render_derot, c->png_ws,
+                    c->lk.pyr[0], c->lk.pyr[1], c->lk.deriv, c->lk.eig, c->lk.cand, c->lk.counters, c->lk.pts, c->lk.out, c->lk.status};
     for (void* b : bufs) if (b) hipFree(b);
     for (auto& blk : c->scratch) if (blk.p) hipFree(blk.p);
     for (auto& r : c->prof) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
@@ -835,7 +855,7 @@ extern "C" int mav_mem_info(mav_ctx* c, size_t* dev_free, size_t* dev_total, siz
     if (workspace_bytes) *workspace_bytes = c->ws_bytes;
     if (ctx_bytes) {
         const size_t B = (size_t)c->max_batch;
-        size_t n = c->ws_bytes + c->pyr_ws_bytes + c->png_ws_bytes;
+        size_t n = c->ws_bytes + c->pyr_ws_bytes + c->png_ws_bytes + c->lk.bytes;
         if (c->flow_ws) n += sizeof(float) * 2 * c->n0 * B;
         if (c->sat) n += sizeof(unsigned long long) * (size_t)(c->W + 1) * (c->H + 1) * B;
         if (c->foe_sc.cand) n += sizeof(double) * 2 * (size_t)c->foe_sc_n * B;
@@ -3229,4 +3249,328 @@ extern "C" int mav_allgather_results(mav_ctx* c, void* comm, const void* local_d
     CHK(rccl_sym("ncclAllGather", &fn));
     int rc = ((nccl_allgather_t)fn)(local_dev, all_dev, bytes_per_rank, /* ncclInt8 */ 0, comm, c->stream);
     return rc ? fail(MAV_ERR_HIP, "ncclAllGather failed: %d", rc) : MAV_OK;
+}
+
+// ---- sparse optical flow: Shi-Tomasi corners + pyramidal Lucas-Kanade (kernels_lk.hip) ---------------------------------------------
+extern "C" void mav_gftt_defaults(mav_gftt_params* p) { *p = mav_gftt_params{2000, 0.2, 7.0, 7}; }
+extern "C" void mav_lk_defaults(mav_lk_params* p) { *p = mav_lk_params{21, 21, 3, 30, 0.01, 1e-4}; }
+
+static void lk_level_dims(int W, int H, LkLevels* lv)
+{
+    size_t off = 0;
+    int w = W, h = H;
+    lv->n = 0;
+    for (int l = 0; l <= MAV_LK_MAX_LEVEL; l++) {
+        lv->w[l] = w; lv->h[l] = h; lv->off[l] = (unsigned)off;
+        lv->n = l + 1;
+        off += ((size_t)w * h + 63) & ~(size_t)63;
+        if (w == 1 && h == 1) break;
+        w = (w + 1) / 2; h = (h + 1) / 2;
+    }
+    for (int l = lv->n; l < MAV_LK_MAX_LEVELS; l++) { lv->w[l] = lv->h[l] = 0; lv->off[l] = 0; }
+}
+extern "C" int mav_lk_level_dims(const mav_ctx* c, int level, int* w, int* h)
+{
+    if (!c) return fail(MAV_ERR_ARG, "mav_lk_level_dims: NULL context");
+    LkLevels lv;
+    lk_level_dims(c->W, c->H, &lv);
+    if (level < 0 || level >= lv.n) return fail(MAV_ERR_ARG, "mav_lk_level_dims: level %d outside [0, %d]", level, lv.n - 1);
+    if (w) *w = lv.w[level]; if (h) *h = lv.h[level];
+    return MAV_OK;
+}
+
+// Argument checks that need no device (and no context): refused before anything is touched.
+static int check_gftt_params(const mav_gftt_params& p, const char* fn)
+{
+    if (p.max_corners < 1 || p.max_corners > MAV_LK_MAX_POINTS)
+        return fail(MAV_ERR_ARG, "%s: max_corners %d outside [1, %d]", fn, p.max_corners, MAV_LK_MAX_POINTS);
+    if (!(p.quality_level > 0) || !std::isfinite(p.quality_level)) return fail(MAV_ERR_ARG, "%s: quality_level %g must be positive", fn, p.quality_level);
+    if (!(p.min_distance >= 0) || !std::isfinite(p.min_distance)) return fail(MAV_ERR_ARG, "%s: min_distance %g must be >= 0", fn, p.min_distance);
+    if (p.block_size < 1 || p.block_size > 15 || p.block_size % 2 == 0)
+        return fail(MAV_ERR_ARG, "%s: block_size %d must be odd and in [1, 15] (the tile's halo in LDS)", fn, p.block_size);
+    return MAV_OK;
+}
+static int check_lk_params(mav_lk_params& p, int n, const char* fn)
+{
+    if (p.win_w < 3 || p.win_h < 3 || p.win_w % 2 == 0 || p.win_h % 2 == 0)
+        return fail(MAV_ERR_ARG, "%s: window %d x %d must be odd and at least 3 x 3", fn, p.win_w, p.win_h);
+    if (p.win_w > MAV_LK_MAX_WIN || p.win_h > MAV_LK_MAX_WIN)
+        return fail(MAV_ERR_ARG, "%s: window %d x %d exceeds %d x %d (a point's window lives in LDS, four points per workgroup)", fn, p.win_w, p.win_h,
+                    MAV_LK_MAX_WIN, MAV_LK_MAX_WIN);
+    if (p.max_level < 0 || p.max_level > MAV_LK_MAX_LEVEL) return fail(MAV_ERR_ARG, "%s: max_level %d outside [0, %d]", fn, p.max_level, MAV_LK_MAX_LEVEL);
+    if (n < 0 || n > MAV_LK_MAX_POINTS) return fail(MAV_ERR_ARG, "%s: %d points outside [0, %d]", fn, n, MAV_LK_MAX_POINTS);
+    if (std::isnan(p.epsilon) || std::isnan(p.min_eig_threshold)) return fail(MAV_ERR_ARG, "%s: epsilon / min_eig_threshold is NaN", fn);
+    p.max_count = std::min(std::max(p.max_count, 0), 100);            // cv2's own clamps of the termination criteria
+    p.epsilon = std::min(std::max(p.epsilon, 0.), 10.);
+    return MAV_OK;
+}
+
+static int ensure_lk(mav_ctx* c)
+{
+    LkState& k = c->lk;
+    if (k.bytes) return MAV_OK;
+    lk_level_dims(c->W, c->H, &k.dims);
+    k.pyr_elems = (size_t)k.dims.off[k.dims.n - 1] + (((size_t)k.dims.w[k.dims.n - 1] * k.dims.h[k.dims.n - 1] + 63) & ~(size_t)63);
+    const size_t sizes[] = {k.pyr_elems, k.pyr_elems, k.pyr_elems * sizeof(short2), c->n0 * sizeof(float), (size_t)MAV_GFTT_MAX_CANDIDATES * sizeof(uint2),
+                            (2 + MAV_LK_HIST) * sizeof(unsigned), (size_t)MAV_LK_MAX_POINTS * 2 * sizeof(float),
+                            (size_t)MAV_LK_MAX_POINTS * 2 * sizeof(float), (size_t)MAV_LK_MAX_POINTS};
+    void** const ptrs[] = {(void**)&k.pyr[0], (void**)&k.pyr[1], (void**)&k.deriv, (void**)&k.eig, (void**)&k.cand, (void**)&k.counters, (void**)&k.pts,
+                           (void**)&k.out, (void**)&k.status};
+    size_t total = 0;
+    for (size_t i = 0; i < sizeof(sizes) / sizeof(sizes[0]); i++) {
+        if (hipMalloc(ptrs[i], sizes[i]) != hipSuccess) {
+            (void)hipGetLastError();
+            for (size_t j = 0; j < i; j++) { hipFree(*ptrs[j]); *ptrs[j] = nullptr; }
+            return fail(MAV_ERR_OOM, "sparse optical flow workspace (%zu bytes)", sizes[i]);
+        }
+        total += sizes[i];
+    }
+    k.bytes = total;
+    k.cur = -1; k.built[0] = k.built[1] = 0; k.deriv_slot = -1; k.deriv_levels = 0;
+    return MAV_OK;
+}
+
+// levels in use for a window: building stops before the first level whose width <= win_w or height <= win_h
+static int lk_levels_for(const LkState& k, const mav_lk_params& p)
+{
+    int n = 1;
+    while (n <= p.max_level && n < k.dims.n && k.dims.w[n] > p.win_w && k.dims.h[n] > p.win_h) n++;
+    return n;
+}
+// a frame into a slot: level 0 only; the coarser levels come with lk_build
+static int lk_load(mav_ctx* c, int slot, const uint8_t* img, bool host)
+{
+    LkState& k = c->lk;
+    HIPCHK(hipMemcpyAsync(k.pyr[slot], img, c->n0, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
+    k.built[slot] = 1;
+    if (k.deriv_slot == slot) { k.deriv_slot = -1; k.deriv_levels = 0; }
+    return MAV_OK;
+}
+static void lk_build(mav_ctx* c, int slot, int levels)
+{
+    LkState& k = c->lk;
+    if (k.built[slot] >= levels) return;
+    ProfScope ps(c, K_LK_PYRAMID);
+    for (int l = k.built[slot]; l < levels; l++)
+        launch_lk_pyrdown(c->stream, k.pyr[slot] + k.dims.off[l - 1], k.dims.w[l - 1], k.dims.h[l - 1], k.pyr[slot] + k.dims.off[l], k.dims.w[l], k.dims.h[l]);
+    k.built[slot] = levels;
+}
+static void lk_derivatives(mav_ctx* c, int slot, int levels)
+{
+    LkState& k = c->lk;
+    if (k.deriv_slot == slot && k.deriv_levels >= levels) return;
+    ProfScope ps(c, K_LK_PYRAMID);
+    launch_lk_scharr(c->stream, k.pyr[slot], k.dims, levels, k.deriv);
+    k.deriv_slot = slot; k.deriv_levels = levels;
+}
+
+// Corner detection on slot `slot`: device part, then the host's sort and greedy pick.  Synchronises.
+static int good_features_run(mav_ctx* c, int slot, const mav_gftt_params& p, float* corners, int* count, const char* fn)
+{
+    LkState& k = c->lk;
+    const int W = c->W, H = c->H;
+    const float s = (float)(1.0 / (4.0 * p.block_size * 255.0)), s2 = s * s;
+    {
+        ProfScope ps(c, K_LK_CORNERS);
+        HIPCHK(hipMemsetAsync(k.counters, 0, 2 * sizeof(unsigned), c->stream));
+        launch_min_eig(c->stream, k.pyr[slot], W, H, p.block_size, s2, k.eig, k.counters);
+        launch_corner_candidates(c->stream, k.eig, W, H, k.counters, p.quality_level, k.cand, k.counters + 1, MAV_GFTT_MAX_CANDIDATES);
+    }
+    CHK(check_launch("corner detection"));
+    unsigned cnt[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(cnt, k.counters, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const unsigned nc = cnt[1];
+    if (nc > MAV_GFTT_MAX_CANDIDATES)
+        return fail(MAV_ERR_ARG, "%s: the frame has %u corner candidates, the buffer holds %d (raise quality_level)", fn, nc, MAV_GFTT_MAX_CANDIDATES);
+    std::vector<uint2> cand(nc);
+    if (nc) {
+        HIPCHK(hipMemcpyAsync(cand.data(), k.cand, (size_t)nc * sizeof(uint2), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    // value descending (positive floats order as their bits), ties by linear index descending
+    std::vector<unsigned long long> keys(nc);
+    for (unsigned i = 0; i < nc; i++) keys[i] = ((unsigned long long)cand[i].x << 32) | cand[i].y;
+    std::sort(keys.begin(), keys.end(), std::greater<unsigned long long>());
+    int n = 0;
+    if (p.min_distance >= 1) {
+        // greedy pick over a grid of cells of ceil(min_distance): an accepted corner nearer than min_distance lies in a neighbouring cell
+        const int cell = (int)ceil(p.min_distance), gw = (W + cell - 1) / cell, gh = (H + cell - 1) / cell;
+        const double md2 = p.min_distance * p.min_distance;
+        std::vector<std::vector<unsigned>> grid((size_t)gw * gh);
+        for (unsigned i = 0; i < nc && n < p.max_corners; i++) {
+            const unsigned idx = (unsigned)(keys[i] & 0xffffffffu);
+            const int y = (int)(idx / (unsigned)W), x = (int)(idx - (unsigned)y * W), cx = x / cell, cy = y / cell;
+            bool good = true;
+            for (int yy = std::max(cy - 1, 0); good && yy <= std::min(cy + 1, gh - 1); yy++)
+                for (int xx = std::max(cx - 1, 0); good && xx <= std::min(cx + 1, gw - 1); xx++)
+                    for (unsigned o : grid[(size_t)yy * gw + xx]) {
+                        const int oy = (int)(o / (unsigned)W), ox = (int)(o - (unsigned)oy * W);
+                        const double dx = x - ox, dy = y - oy;
+                        if (dx * dx + dy * dy < md2) { good = false; break; }
+                    }
+            if (!good) continue;
+            grid[(size_t)cy * gw + cx].push_back(idx);
+            corners[2 * n] = (float)x; corners[2 * n + 1] = (float)y;
+            n++;
+        }
+    } else {
+        for (unsigned i = 0; i < nc && n < p.max_corners; i++, n++) {
+            const unsigned idx = (unsigned)(keys[i] & 0xffffffffu);
+            corners[2 * n] = (float)(idx % (unsigned)W); corners[2 * n + 1] = (float)(idx / (unsigned)W);
+        }
+    }
+    *count = n;
+    return MAV_OK;
+}
+static int good_features_entry(mav_ctx* c, const uint8_t* gray, bool host, const mav_gftt_params* pp, float* corners, int* count, const char* fn)
+{
+    mav_gftt_params p;
+    if (pp) p = *pp; else mav_gftt_defaults(&p);
+    CHK(check_gftt_params(p, fn));
+    if (!c || !corners || !count) return fail(MAV_ERR_ARG, "%s: NULL argument", fn);
+    HIPCHK(hipSetDevice(c->device));
+    if (!gray && (!c->lk.bytes || c->lk.cur < 0)) return fail(MAV_ERR_STATE, "%s: gray is NULL and no frame is resident", fn);
+    CHK(ensure_lk(c));
+    LkState& k = c->lk;
+    if (gray) {
+        const int slot = k.cur < 0 ? 0 : k.cur;          // replaces the resident frame
+        CHK(lk_load(c, slot, gray, host));
+        k.cur = slot;
+    }
+    return good_features_run(c, k.cur, p, corners, count, fn);
+}
+extern "C" int mav_good_features(mav_ctx* c, const uint8_t* gray, const mav_gftt_params* p, float* corners, int* count)
+{
+    return good_features_entry(c, gray, true, p, corners, count, "mav_good_features");
+}
+extern "C" int mav_good_features_dev(mav_ctx* c, const uint8_t* gray, const mav_gftt_params* p, float* corners, int* count)
+{
+    return good_features_entry(c, gray, false, p, corners, count, "mav_good_features_dev");
+}
+
+// prev (or the resident frame) and next into the two slots, pyramids, derivatives, one tracker launch.  pts / out / status: device.
+static int lk_track_enqueue(mav_ctx* c, const uint8_t* prev, const uint8_t* next, bool host, const float* pts, int n, const mav_lk_params& p,
+                            float* out, uint8_t* status)
+{
+    LkState& k = c->lk;
+    int sp;
+    if (prev) { sp = k.cur < 0 ? 0 : k.cur; CHK(lk_load(c, sp, prev, host)); }
+    else sp = k.cur;
+    const int sn = 1 - sp;
+    k.cur = -1;                                           // until everything below has been enqueued
+    CHK(lk_load(c, sn, next, host));
+    const int levels = lk_levels_for(k, p);
+    lk_build(c, sp, levels);
+    lk_build(c, sn, levels);
+    lk_derivatives(c, sp, levels);
+    HIPCHK(hipMemsetAsync(k.counters + 2, 0, MAV_LK_HIST * sizeof(unsigned), c->stream));
+    LkTrackArgs a;
+    a.I = k.pyr[sp]; a.J = k.pyr[sn]; a.D = k.deriv; a.lv = k.dims; a.lv.n = levels;
+    a.pts = pts; a.n = n; a.win_w = p.win_w; a.win_h = p.win_h; a.max_count = p.max_count;
+    a.eps2 = p.epsilon * p.epsilon; a.min_eig = (float)p.min_eig_threshold;
+    a.out = out; a.status = status; a.iter_hist = k.counters + 2;
+    {
+        ProfScope ps(c, K_LK_TRACK);
+        launch_lk_track(c->stream, a);
+    }
+    CHK(check_launch("lk_track"));
+    k.cur = sn; k.hist_valid = true;
+    return MAV_OK;
+}
+static int lk_track_check(mav_ctx* c, const uint8_t* prev, const uint8_t* next, const void* pts, int n, const mav_lk_params* pp, const void* out,
+                          const void* status, mav_lk_params* p, const char* fn)
+{
+    if (pp) *p = *pp; else mav_lk_defaults(p);
+    CHK(check_lk_params(*p, n, fn));
+    if (!c || !next || (n > 0 && (!pts || !out || !status))) return fail(MAV_ERR_ARG, "%s: NULL argument", fn);
+    HIPCHK(hipSetDevice(c->device));
+    if (!prev && (!c->lk.bytes || c->lk.cur < 0)) return fail(MAV_ERR_STATE, "%s: prev is NULL and no frame is resident", fn);
+    return ensure_lk(c);
+}
+extern "C" int mav_lk_track(mav_ctx* c, const uint8_t* prev, const uint8_t* next, const float* pts, int n, const mav_lk_params* pp, float* next_pts,
+                            uint8_t* status)
+{
+    mav_lk_params p;
+    CHK(lk_track_check(c, prev, next, pts, n, pp, next_pts, status, &p, "mav_lk_track"));
+    LkState& k = c->lk;
+    if (n) HIPCHK(hipMemcpyAsync(k.pts, pts, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    CHK(lk_track_enqueue(c, prev, next, true, k.pts, n, p, k.out, k.status));
+    if (n) {
+        HIPCHK(hipMemcpyAsync(next_pts, k.out, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(status, k.status, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    }
+    return mav_sync(c);
+}
+extern "C" int mav_lk_track_dev(mav_ctx* c, const uint8_t* prev, const uint8_t* next, const float* pts, int n, const mav_lk_params* pp,
+                                float* next_pts, uint8_t* status)
+{
+    mav_lk_params p;
+    CHK(lk_track_check(c, prev, next, pts, n, pp, next_pts, status, &p, "mav_lk_track_dev"));
+    return lk_track_enqueue(c, prev, next, false, pts, n, p, next_pts, status);
+}
+extern "C" int mav_lk_last_iterations(mav_ctx* c, uint32_t* hist)
+{
+    if (!c || !hist) return fail(MAV_ERR_ARG, "mav_lk_last_iterations: NULL argument");
+    if (!c->lk.bytes || !c->lk.hist_valid) return fail(MAV_ERR_STATE, "mav_lk_last_iterations: no track call precedes");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(hist, c->lk.counters + 2, MAV_LK_HIST * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    return mav_sync(c);
+}
+
+// stage hooks: one image through slot 0; the resident frame is dropped
+static int lk_stage_begin(mav_ctx* c, const uint8_t* img, const void* out, const char* fn)
+{
+    if (!c || !img || !out) return fail(MAV_ERR_ARG, "%s: NULL argument", fn);
+    HIPCHK(hipSetDevice(c->device));
+    CHK(ensure_lk(c));
+    c->lk.cur = -1; c->lk.built[1] = 0;
+    return lk_load(c, 0, img, true);
+}
+static int lk_stage_level(mav_ctx* c, int level, const char* fn)
+{
+    if (level < 0 || level >= c->lk.dims.n) return fail(MAV_ERR_ARG, "%s: level %d outside [0, %d]", fn, level, c->lk.dims.n - 1);
+    return MAV_OK;
+}
+extern "C" int mav_stage_lk_pyramid(mav_ctx* c, const uint8_t* img, int level, uint8_t* out)
+{
+    CHK(lk_stage_begin(c, img, out, "mav_stage_lk_pyramid"));
+    CHK(lk_stage_level(c, level, "mav_stage_lk_pyramid"));
+    LkState& k = c->lk;
+    lk_build(c, 0, level + 1);
+    CHK(check_launch("lk pyramid"));
+    CHK(download(c, out, k.pyr[0] + k.dims.off[level], (size_t)k.dims.w[level] * k.dims.h[level]));
+    const int rc = mav_sync(c);
+    k.built[0] = 0;
+    return rc;
+}
+extern "C" int mav_stage_lk_scharr(mav_ctx* c, const uint8_t* img, int level, int16_t* out)
+{
+    CHK(lk_stage_begin(c, img, out, "mav_stage_lk_scharr"));
+    CHK(lk_stage_level(c, level, "mav_stage_lk_scharr"));
+    LkState& k = c->lk;
+    lk_build(c, 0, level + 1);
+    lk_derivatives(c, 0, level + 1);
+    CHK(check_launch("lk scharr"));
+    CHK(download(c, out, k.deriv + k.dims.off[level], (size_t)k.dims.w[level] * k.dims.h[level] * sizeof(short2)));
+    const int rc = mav_sync(c);
+    k.built[0] = 0; k.deriv_slot = -1; k.deriv_levels = 0;
+    return rc;
+}
+extern "C" int mav_stage_min_eigen(mav_ctx* c, const uint8_t* img, int block_size, float* out)
+{
+    mav_gftt_params p;
+    mav_gftt_defaults(&p);
+    p.block_size = block_size;
+    CHK(check_gftt_params(p, "mav_stage_min_eigen"));
+    CHK(lk_stage_begin(c, img, out, "mav_stage_min_eigen"));
+    LkState& k = c->lk;
+    const float s = (float)(1.0 / (4.0 * block_size * 255.0)), s2 = s * s;
+    HIPCHK(hipMemsetAsync(k.counters, 0, 2 * sizeof(unsigned), c->stream));
+    launch_min_eig(c->stream, k.pyr[0], c->W, c->H, block_size, s2, k.eig, k.counters);
+    CHK(check_launch("min_eig"));
+    CHK(download(c, out, k.eig, c->n0 * sizeof(float)));
+    const int rc = mav_sync(c);
+    k.built[0] = 0;
+    return rc;
 }

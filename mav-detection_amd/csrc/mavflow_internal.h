@@ -185,3 +185,31 @@ size_t png_workspace_per_image(size_t raw);      // device bytes launch_png_enco
 // behind the streams of the images before them; index[i] = (offset, size) of image i.  index[img0 - 1] must be complete (same stream).
 void launch_png_encode(hipStream_t st, const uint8_t* imgs, int img0, int nimg, int W, int H, int C, uint8_t* ws, uint8_t* out,
                        unsigned long long* index);
+
+// ---- sparse optical flow (kernels_lk.hip, compiled with -ffp-contract=off) -----------------------------------------------------------
+// Levels of the tracker's pyramid for one frame size (level l + 1 = ((w + 1) / 2, (h + 1) / 2)); off[l]: first element of level l
+// inside a frame's u8 pyramid block and inside the int16-pair derivative block.
+#define MAV_LK_MAX_LEVELS 8
+#define MAV_LK_HIST 104           // iteration-count histogram: bins 0 .. 102 iterations, last bin = more
+struct LkLevels { int n; int w[MAV_LK_MAX_LEVELS], h[MAV_LK_MAX_LEVELS]; unsigned off[MAV_LK_MAX_LEVELS]; };
+struct LkTrackArgs {
+    const uint8_t *I, *J;         // pyramid blocks of the previous / next frame
+    const short2* D;              // Scharr pairs of the previous frame's levels
+    LkLevels lv;                  // n = levels in use
+    const float* pts;             // (n, 2)
+    int n, win_w, win_h, max_count;
+    double eps2;                  // epsilon^2
+    float min_eig;
+    float* out;                   // (n, 2)
+    uint8_t* status;              // (n)
+    unsigned* iter_hist;          // [MAV_LK_HIST] or null: iterations per (point, level) that reached the loop
+};
+// min-eigenvalue map of a W x H u8 image (block_size odd, <= 15) and its maximum as an ordered key (*maxkey zeroed by the caller)
+void launch_min_eig(hipStream_t st, const uint8_t* img, int W, int H, int block_size, float s2, float* eig, unsigned* maxkey);
+// candidates (value bits, linear index) appended at cand[*count++] while *count < cap (*count zeroed by the caller, counts past cap)
+void launch_corner_candidates(hipStream_t st, const float* eig, int W, int H, const unsigned* maxkey, double quality, uint2* cand,
+                              unsigned* count, unsigned cap);
+void launch_lk_pyrdown(hipStream_t st, const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh);
+void launch_lk_scharr(hipStream_t st, const uint8_t* pyr, const LkLevels& lv, int levels, short2* out);
+size_t lk_track_lds_bytes(int win_w, int win_h);
+void launch_lk_track(hipStream_t st, const LkTrackArgs& a);

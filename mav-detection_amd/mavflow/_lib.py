@@ -31,6 +31,20 @@ class ThrParams(C.Structure):
                 ("dyn_a", C.c_double), ("dyn_b", C.c_double), ("dyn_c", C.c_double)]
 
 
+class GfttParams(C.Structure):
+    """mav_gftt_params: cv2.goodFeaturesToTrack's maxCorners, qualityLevel, minDistance, blockSize."""
+    _fields_ = [("max_corners", C.c_int), ("quality_level", C.c_double), ("min_distance", C.c_double), ("block_size", C.c_int)]
+
+
+class LkParams(C.Structure):
+    """mav_lk_params: cv2.calcOpticalFlowPyrLK's winSize, maxLevel, criteria (count, epsilon), minEigThreshold."""
+    _fields_ = [("win_w", C.c_int), ("win_h", C.c_int), ("max_level", C.c_int), ("max_count", C.c_int), ("epsilon", C.c_double),
+                ("min_eig_threshold", C.c_double)]
+
+
+LK_MAX_POINTS, LK_MAX_WIN, LK_MAX_LEVEL, LK_HIST_BINS, GFTT_MAX_CANDIDATES = 65536, 33, 7, 104, 262144
+
+
 class Result(C.Structure):
     _fields_ = [("box", C.c_int32 * 4), ("foe", C.c_double * 2)]
 
@@ -59,6 +73,8 @@ EXPORTS = [
     "mav_render", "mav_render_dev", "mav_last_render", "mav_flow_to_color", "mav_colormap_jet",
     "mav_overlay", "mav_overlay_dev", "mav_last_overlay",
     "mav_png_bound", "mav_png_encode", "mav_png_encode_dev", "mav_last_render_png", "mav_last_overlay_png",
+    "mav_gftt_defaults", "mav_lk_defaults", "mav_good_features", "mav_good_features_dev", "mav_lk_track", "mav_lk_track_dev",
+    "mav_lk_last_iterations", "mav_lk_level_dims", "mav_stage_lk_pyramid", "mav_stage_lk_scharr", "mav_stage_min_eigen",
 ]
 
 # Frame depths of the _ex entry points (cv2's depth codes) by numpy dtype.  uint8 frames keep going through the u8 symbols.
@@ -114,7 +130,8 @@ def load(path: str | None = None) -> C.CDLL:
     lib.mav_last_flow_dev.restype = C.c_void_p
     for name in EXPORTS:
         fn = getattr(lib, name)
-        if name not in ("mav_last_error", "mav_stream", "mav_fb_defaults", "mav_foe_defaults", "mav_thr_defaults", "mav_last_flow_dev", "mav_png_bound"):
+        if name not in ("mav_last_error", "mav_stream", "mav_fb_defaults", "mav_foe_defaults", "mav_thr_defaults", "mav_last_flow_dev", "mav_png_bound",
+                        "mav_gftt_defaults", "mav_lk_defaults"):
             fn.restype = C.c_int
     lib.mav_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FbParams)]
     lib.mav_destroy.argtypes = [C.c_void_p]
@@ -223,6 +240,18 @@ def load(path: str | None = None) -> C.CDLL:
     lib.mav_png_encode_dev.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_size_t, vp]
     lib.mav_last_render_png.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp]
     lib.mav_last_overlay_png.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_size_t, vp, vp]
+    lib.mav_gftt_defaults.argtypes = [C.POINTER(GfttParams)]
+    lib.mav_lk_defaults.argtypes = [C.POINTER(LkParams)]
+    lib.mav_good_features.argtypes = [vp, vp, C.POINTER(GfttParams), vp, C.POINTER(C.c_int)]
+    lib.mav_good_features_dev.argtypes = [vp, vp, C.POINTER(GfttParams), vp, C.POINTER(C.c_int)]
+    # ctx, prev, next, pts, n, params, next_pts, status
+    lib.mav_lk_track.argtypes = [vp, vp, vp, vp, C.c_int, C.POINTER(LkParams), vp, vp]
+    lib.mav_lk_track_dev.argtypes = [vp, vp, vp, vp, C.c_int, C.POINTER(LkParams), vp, vp]
+    lib.mav_lk_last_iterations.argtypes = [vp, vp]
+    lib.mav_lk_level_dims.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.mav_stage_lk_pyramid.argtypes = [vp, vp, C.c_int, vp]
+    lib.mav_stage_lk_scharr.argtypes = [vp, vp, C.c_int, vp]
+    lib.mav_stage_min_eigen.argtypes = [vp, vp, C.c_int, vp]
     _lib = lib
     return lib
 
@@ -256,6 +285,41 @@ def foe_defaults() -> FoeParams:
 def thr_defaults() -> ThrParams:
     p = ThrParams()
     load().mav_thr_defaults(C.byref(p))
+    return p
+
+
+def gftt_defaults(**kw) -> GfttParams:
+    """cv2.goodFeaturesToTrack's parameters, the reference's values by default; keywords: the struct's fields or cv2's names."""
+    p = GfttParams()
+    load().mav_gftt_defaults(C.byref(p))
+    names = {"maxCorners": "max_corners", "qualityLevel": "quality_level", "minDistance": "min_distance", "blockSize": "block_size"}
+    for k, v in kw.items():
+        k = names.get(k, k)
+        if k not in dict(GfttParams._fields_):
+            raise TypeError(f"good_features: unknown parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def lk_defaults(**kw) -> LkParams:
+    """cv2.calcOpticalFlowPyrLK's parameters, the reference's values by default; keywords: the struct's fields, or cv2's winSize = (w, h),
+    maxLevel, criteria = (type, count, epsilon), minEigThreshold."""
+    p = LkParams()
+    load().mav_lk_defaults(C.byref(p))
+    names = {"maxLevel": "max_level", "minEigThreshold": "min_eig_threshold"}
+    for k, v in kw.items():
+        if k == "winSize":
+            p.win_w, p.win_h = int(v[0]), int(v[1])
+        elif k == "criteria":                    # (TERM_CRITERIA_COUNT = 1 | TERM_CRITERIA_EPS = 2, count, epsilon)
+            if int(v[0]) & 1:
+                p.max_count = int(v[1])
+            if int(v[0]) & 2:
+                p.epsilon = float(v[2])
+        else:
+            k = names.get(k, k)
+            if k not in dict(LkParams._fields_):
+                raise TypeError(f"lk_track: unknown parameter {k!r}")
+            setattr(p, k, v)
     return p
 
 
@@ -1084,6 +1148,72 @@ class Context:
         out = C.c_double()
         check(self.lib.mav_profile_busy(self.h, ",".join(names).encode(), C.byref(out)))
         return out.value
+
+    # -- sparse optical flow ---------------------------------------------------------------------------------
+    def _gray1(self, a, name):
+        return None if a is None else _arr(np.asarray(a), np.uint8, (self.H, self.W), name)
+
+    def good_features(self, gray, **params) -> np.ndarray:
+        """cv2.goodFeaturesToTrack(gray, mask=None, **params) on one (H, W) uint8 frame -> (n, 2) float32 corners (x, y), strongest first.
+        gray None: the context's resident frame (the `nxt` of the last lk_track, or the last frame given here)."""
+        p = gftt_defaults(**params)
+        gray = self._gray1(gray, "gray")
+        out = np.empty((max(int(p.max_corners), 1), 2), np.float32)
+        n = C.c_int()
+        check(self.lib.mav_good_features(self.h, _ptr(gray), C.byref(p), _ptr(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def lk_track(self, prev, nxt, pts, **params):
+        """cv2.calcOpticalFlowPyrLK(prev, nxt, pts, None, **params) -> (next_pts (n, 2) float32, status (n,) uint8).  prev None: the
+        resident frame.  `nxt` becomes the resident frame."""
+        p = lk_defaults(**params)
+        prev, nxt = self._gray1(prev, "prev"), self._gray1(nxt, "nxt")
+        pts = _arr(np.asarray(pts, np.float32).reshape(-1, 2), np.float32)
+        n = pts.shape[0]
+        out, status = np.empty((n, 2), np.float32), np.empty(n, np.uint8)
+        check(self.lib.mav_lk_track(self.h, _ptr(prev), _ptr(nxt), _ptr(pts) if n else None, n, C.byref(p), _ptr(out) if n else None,
+                                    _ptr(status) if n else None))
+        return out, status
+
+    def lk_track_dev(self, prev_ptr, next_ptr, pts_ptr, n: int, next_pts_ptr, status_ptr, **params):
+        """mav_lk_track_dev: device pointers, enqueue only."""
+        check(self.lib.mav_lk_track_dev(self.h, prev_ptr, next_ptr, pts_ptr, int(n), C.byref(lk_defaults(**params)), next_pts_ptr, status_ptr))
+
+    def good_features_dev(self, gray_ptr, **params) -> np.ndarray:
+        """mav_good_features_dev: a device frame (None: the resident one) -> host corners; synchronises for the host-side pick."""
+        p = gftt_defaults(**params)
+        out = np.empty((max(int(p.max_corners), 1), 2), np.float32)
+        n = C.c_int()
+        check(self.lib.mav_good_features_dev(self.h, gray_ptr, C.byref(p), _ptr(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def lk_last_iterations(self) -> np.ndarray:
+        """Iterations per (point, level) of the latest track call as a histogram (LK_HIST_BINS bins, the last = more)."""
+        h = np.empty(LK_HIST_BINS, np.uint32)
+        check(self.lib.mav_lk_last_iterations(self.h, _ptr(h)))
+        return h
+
+    def lk_level_dims(self, level: int):
+        w, h = C.c_int(), C.c_int()
+        check(self.lib.mav_lk_level_dims(self.h, int(level), C.byref(w), C.byref(h)))
+        return w.value, h.value
+
+    def stage_lk_pyramid(self, img, level: int) -> np.ndarray:
+        w, h = self.lk_level_dims(level)
+        out = np.empty((h, w), np.uint8)
+        check(self.lib.mav_stage_lk_pyramid(self.h, _ptr(self._gray1(img, "img")), int(level), _ptr(out)))
+        return out
+
+    def stage_lk_scharr(self, img, level: int) -> np.ndarray:
+        w, h = self.lk_level_dims(level)
+        out = np.empty((h, w, 2), np.int16)
+        check(self.lib.mav_stage_lk_scharr(self.h, _ptr(self._gray1(img, "img")), int(level), _ptr(out)))
+        return out
+
+    def stage_min_eigen(self, img, block_size: int = 7) -> np.ndarray:
+        out = np.empty((self.H, self.W), np.float32)
+        check(self.lib.mav_stage_min_eigen(self.h, _ptr(self._gray1(img, "img")), int(block_size), _ptr(out)))
+        return out
 
     # -- stage hooks (parity tests) --------------------------------------------------------------------------
     def stage_phi_mask(self, flow32, foe, omega=None, dt=None, sky=None, params: ThrParams | None = None, want_phi=False):

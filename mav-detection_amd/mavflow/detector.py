@@ -13,15 +13,62 @@ from .frame_result import FrameResult
 
 
 class LucasKanade:
-    """Only what the hot path reads from the reference's sparse tracker (lucas_kanade.py:9-32): the frame shape, the
-    corner budget, and the constructor's draw from the global RNG."""
+    """The reference's sparse tracker (lucas_kanade.py:9-63): Shi-Tomasi corners, re-detected when fewer than a third of the budget
+    remain, tracked from frame to frame by pyramidal Lucas-Kanade -- both on libmavflow (Context.good_features / lk_track).
+    The constructor keeps the reference's fields and its one draw from the global RNG and touches no GPU; the device context (one of
+    its own: it holds the previous frame and its pyramid between calls) comes with the first get_features."""
 
     def __init__(self, old_frame: np.ndarray) -> None:
         self.old_frame = old_frame
         self.num_corners = 2000
         self.minimum_num_corners = self.num_corners // 3
         self.total_num_corners = self.num_corners + self.minimum_num_corners
+        self.corners = np.zeros((self.total_num_corners, 2), dtype=np.uint)
+        self.num_features = 0
+        self.features: list = []
+        self.feature_params = dict(maxCorners=self.num_corners, qualityLevel=0.2, minDistance=7, blockSize=7)
+        # criteria: cv2.TERM_CRITERIA_EPS | cv2.TERM_CRITERIA_COUNT = 3
+        self.lk_params = dict(winSize=(21, 21), criteria=(3, 30, 0.01))
         self.color = np.random.randint(0, 255, (self.total_num_corners, 3))
+        self._ctx = None
+        self._resident = None           # the gray frame the context holds (the `frame` of the previous call)
+
+    def _context(self, H: int, W: int):
+        from . import _lib
+        if self._ctx is None or not self._ctx.alive or (self._ctx.W, self._ctx.H) != (W, H):
+            self._ctx, self._resident = _lib.Context(W, H, 1), None
+        return self._ctx
+
+    def get_features(self, frame: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """LK optical flow from the previous frame to `frame` (BGR): (old_features (n, 2) float32, good_new (n, 2) float32,
+        status (n, 1) uint8), cv2's shapes.  Every feature is tracked whatever its last status and .features becomes the tracked
+        points; new corners are appended when fewer than minimum_num_corners features remain.  An all-black previous frame returns
+        three empty arrays.  Each frame crosses to the device once as a gray image: the previous call's `frame` is still there
+        (recognised by identity -- a frame changed in place after it was handed in is not noticed: assign a new array to
+        .old_frame instead)."""
+        H, W = np.shape(self.old_frame)[:2]
+        self.mask = np.zeros_like(self.old_frame)
+        ctx = self._context(H, W)
+        frame_gray = ctx.bgr2gray(np.asarray(frame))[0]
+        held = self._resident is not None and self._resident[0] is self.old_frame         # the context holds old_gray already
+        self.old_gray = self._resident[1] if held else ctx.bgr2gray(np.asarray(self.old_frame).astype(np.uint8))[0]
+        self.old_frame = frame
+        self._resident = None
+
+        if np.sum(self.old_gray) < 1:
+            return np.zeros(0), np.zeros(0), np.zeros(0)
+
+        if len(self.features) < self.minimum_num_corners:
+            new_features = ctx.good_features(None if held else self.old_gray, **self.feature_params)
+            held = True
+            for feature in new_features:
+                self.features.append(feature)
+
+        old_features = np.array(self.features).astype(np.float32).reshape(-1, 2)
+        good_new, status = ctx.lk_track(None if held else self.old_gray, frame_gray, old_features, **self.lk_params)
+        self.features = good_new.tolist()
+        self._resident = (frame, frame_gray)
+        return old_features, good_new, status.reshape(-1, 1)
 
 
 class Detector:

@@ -1,5 +1,5 @@
 """FocusOfExpansion -- the dense FoE fit and the per-pixel radial residual on libmavflow, behind the reference's
-call signatures (/root/reference/src/focus_of_expansion.py:13-86,150-184).
+call signatures (/root/reference/src/focus_of_expansion.py:13-184), and the sparse fit on the device tracker.
 
 RNG ownership: get_FOE_dense draws its 2N sample coordinates from the global legacy numpy stream exactly as the
 reference does (rows first, then columns, :70-71) and the constructor consumes the same draws (:24,26), so a seeded
@@ -56,6 +56,58 @@ class FocusOfExpansion:
         rand1[..., 1] = np.random.randint(0, flow_uv.shape[1], N * 2)
         foe = self._ctx(flow_uv).foe_dense(flow_uv, rand1, self._foe_params(N))[0]
         return (float(foe[0]), float(foe[1]))
+
+    def get_FOE_sparse(self, old_frame: np.ndarray, new_frame: np.ndarray) -> Tuple[float, float]:
+        """FoE from sparse optical flow (:88-148): the tracker's features (lucas_kanade.get_features: corners and tracking on the
+        device) extend per-feature traces; a trace of two or more points gives a line from its newest point back over up to
+        roll_back steps, each line is intersected with one drawn at random (one np.random.randint per line, in the reference's
+        order), and the device RANSAC vote picks the FoE.  The trace bookkeeping is the reference's host code, a few thousand scalars
+        per frame -- including the line end's wrap through uint16 and the halving loop that tests the y coordinate against the frame
+        WIDTH.  One departure: where the reference's halving loop would never end (a trace point with a negative y wraps to > 65000
+        for every diff), it stops once diff has reached zero."""
+        from . import utils
+        if np.sum(old_frame) < 1:
+            return (np.nan, np.nan)
+
+        old_features, new_features, status = self.lucas_kanade.get_features(new_frame)
+        self.mask = np.zeros_like(old_frame)
+        self.lines = []
+        intersections = np.zeros((len(new_features), 2))
+
+        def as_uint16(v):            # ndarray.astype(np.uint16) of a float64 pair as x86 numpy does it: truncate, then wrap
+            return (np.trunc(v).astype(np.int64) & 0xFFFF).astype(np.uint16)
+
+        for i, (new, old) in enumerate(zip(new_features, old_features)):
+            if status[i] != 1:
+                continue
+            a, b, c, d = [int(x) for x in [*new.ravel(), *old.ravel()]]
+            l = self.trace[i, 0] + 1
+            self.trace[i, l] = c
+            self.trace[i, l + 1] = d
+            self.trace[i, 0] += 2
+            self.num_features += 1
+
+            if l >= 3:
+                k = 1 if l < 1 + self.roll_back * 2 else l - self.roll_back * 2
+                a, b = self.trace[i, l:l + 2]
+                c, d = self.trace[i, k:k + 2]
+                diff = np.array([float(c) - float(a), float(d) - float(b)])
+                new_xy = as_uint16(np.array([a, b]) + diff)
+                # "Let flow vector fit inside image bounds" -- the reference's test, as it is
+                while new_xy[1] < 0.0 or new_xy[1] > new_frame.shape[1]:
+                    if not diff.any():
+                        break
+                    diff /= 2.0
+                    new_xy = as_uint16(np.array([a, b]) + diff)
+                self.lines.append(((a, b), (new_xy[0], new_xy[1])))
+
+        with np.errstate(over="ignore"):     # the lines' end points are int32 / uint16 scalars, as in the reference: products may wrap
+            for i, line_a in enumerate(self.lines):
+                line_b = self.lines[np.random.randint(0, len(self.lines))]
+                intersections[i, :] = utils.line_intersection(line_a, line_b)
+
+        intersections = intersections[intersections[:, 0] != 0.0, :]
+        return self.ransac(intersections)
 
     def get_phi(self, derotated_flow_uv: np.ndarray, FoE: Tuple[float, float]) -> np.ndarray:
         """Angle (degrees) between each flow vector and the ray from the FoE through its pixel; max goes to .max_flow.

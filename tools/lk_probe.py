@@ -1,0 +1,90 @@
+"""Cost of the sparse optical-flow path per frame of a device-resident video.
+
+    python tools/lk_probe.py [--frames 50] [--warmup 8] [--sizes 1280x720,1920x1080]
+
+Per size: a synthetic zoom sequence (synth.make_sequence) is uploaded once; every frame then does what LucasKanade.get_features does on
+the device -- corner detection on the resident frame (mav_good_features_dev(NULL): eigenvalue map, threshold, non-maximum test and
+compaction on the device, sort and greedy pick on the host), then one mav_lk_track_dev from the resident frame to the next one (the
+new frame's pyramid, the previous frame's Scharr pairs, the tracker).  Reported per frame, median over the timed frames:
+  corners_dev_ms   HIP-event time of the class "lk_corners"            corners_host_ms  wall time of the call minus that
+  pyramid_ms       class "lk_pyramid" (pyrDown chain + Scharr)          track_ms         class "lk_track"
+  get_features_ms  wall time of detector.LucasKanade.get_features on host BGR frames (gray conversion, uploads and downloads included)
+and the histogram of tracker iterations per (point, level) over all timed frames.  Prints one JSON line."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "mav-detection_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+from mavflow import _lib, synth  # noqa: E402
+from mavflow.detector import LucasKanade  # noqa: E402
+
+
+def probe(W: int, H: int, frames: int, warmup: int) -> dict:
+    n = frames + warmup + 1
+    seq = synth.make_sequence(W, H, n, seed=0)
+    rows = {k: [] for k in ("corners_dev_ms", "corners_host_ms", "pyramid_ms", "track_ms", "candidates_points")}
+    hist = np.zeros(_lib.LK_HIST_BINS, np.int64)
+    with _lib.Context(W, H, 1) as c:
+        dev = [c.alloc(W * H).upload(f) for f in seq]
+        d_pts, d_out, d_status = c.alloc(_lib.LK_MAX_POINTS * 8), c.alloc(_lib.LK_MAX_POINTS * 8), c.alloc(_lib.LK_MAX_POINTS)
+        pts = c.good_features_dev(dev[0].ptr)
+        c.profile_enable(1)
+        last = {k: 0.0 for k in ("lk_corners", "lk_pyramid", "lk_track")}
+        for i in range(1, n):
+            t0 = time.perf_counter()
+            corners = c.good_features_dev(None)
+            wall = (time.perf_counter() - t0) * 1e3
+            d_pts.upload(corners)
+            c.lk_track_dev(None, dev[i].ptr, d_pts.ptr, len(corners), d_out.ptr, d_status.ptr)
+            c.sync()
+            prof = c.profile_get()
+            step = {k: prof[k][0] - last[k] for k in last}
+            last = {k: prof[k][0] for k in last}
+            if i > warmup:
+                rows["corners_dev_ms"].append(step["lk_corners"])
+                rows["corners_host_ms"].append(wall - step["lk_corners"])
+                rows["pyramid_ms"].append(step["lk_pyramid"])
+                rows["track_ms"].append(step["lk_track"])
+                rows["candidates_points"].append(len(corners))
+                hist += c.lk_last_iterations()
+        c.profile_enable(0)
+    # the Python class on host frames
+    bgr = [np.repeat(f[..., None], 3, axis=2) for f in seq]
+    lk = LucasKanade(bgr[0])
+    wall = []
+    for i in range(1, n):
+        t0 = time.perf_counter()
+        lk.get_features(bgr[i])
+        if i > warmup:
+            wall.append((time.perf_counter() - t0) * 1e3)
+    out = dict(W=W, H=H, frames=frames, points_median=int(np.median(rows.pop("candidates_points"))))
+    out.update({k: round(float(np.median(v)), 4) for k, v in rows.items()})
+    out["get_features_ms"] = round(float(np.median(wall)), 4)
+    nz = np.nonzero(hist)[0]
+    out["iterations_mean"] = round(float((hist * np.arange(len(hist))).sum() / max(hist.sum(), 1)), 3)
+    out["iterations_hist"] = {int(i): int(hist[i]) for i in nz}
+    return out
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=8)
+    ap.add_argument("--sizes", default="1280x720,1920x1080")
+    a = ap.parse_args()
+    res = [probe(*(int(v) for v in s.split("x")), a.frames, a.warmup) for s in a.sizes.split(",")]
+    print(json.dumps(dict(tool="lk_probe", results=res)))
+
+
+if __name__ == "__main__":
+    main()
