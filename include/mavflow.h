@@ -146,9 +146,9 @@ int mav_schedule_info(mav_ctx*, int batch, char* buf, size_t cap);
  * the LDS of 8U ones, and a short Gaussian whose staged tile would not fit goes through the two-pass form).  MAV_DEPTH_8U: the line
  * of mav_schedule_info, byte for byte. */
 int mav_schedule_info_ex(mav_ctx*, int batch, int depth, char* buf, size_t cap);
-/* Device memory: free / total bytes of the context's GPU (hipMemGetInfo), the bytes this context holds in all (workspace, flow
- * workspace, detection scratch, staging blocks of the host-pointer calls, window-search buffers) and the Farneback workspace alone
- * (0 until a call computes flow).  Any pointer may be NULL. */
+/* Device memory: free / total bytes of the context's GPU (hipMemGetInfo), the bytes this context holds in all -- ctx_bytes is the sum
+ * of the context's live device allocations, whatever they serve (memory from mav_dev_alloc is the caller's and not in it) -- and of
+ * those the Farneback workspace alone (0 until a call computes flow).  Any pointer may be NULL. */
 int mav_mem_info(mav_ctx*, size_t* dev_free, size_t* dev_total, size_t* ctx_bytes, size_t* workspace_bytes);
 int mav_num_layers(const mav_ctx*);
 int mav_layer_dims(const mav_ctx*, int k, int* w, int* h, int* ksize, double* sigma);
@@ -363,7 +363,9 @@ int mav_upload_gather(mav_ctx*, void* dst_dev, const void* const* src_host, int 
 int mav_download_async(mav_ctx*, void* dst_host, const void* src_dev, size_t bytes);
 /* Markers: "everything enqueued on the context's stream so far" as an object the host can wait for WITHOUT draining the stream
  * (mav_sync also waits for whatever was enqueued after the marker).  A loop that keeps two batches in flight records one per batch
- * behind the batch's result download and waits for it when it needs those results. */
+ * behind the batch's result download and waits for it when it needs those results.  A marker may outlive the context it was
+ * recorded on, but once that context is destroyed (mav_destroy drains its streams: everything the marker stood behind has finished)
+ * it is only to be destroyed, not waited for or queried: the runtime's event still refers to the context's stream. */
 int mav_marker_create(mav_ctx*, void** marker_out);
 int mav_marker_record(mav_ctx*, void* marker);
 int mav_marker_wait(mav_ctx* /* may be NULL */, void* marker);

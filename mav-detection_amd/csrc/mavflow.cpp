@@ -1,6 +1,7 @@
 // Host side of libmavflow.so: the C-ABI of include/mavflow.h over the gfx950 kernels.
 // Owns the context (stream, pyramid tables, workspace), schedules the per-layer launches in groups of pairs that
 // keep the iteration working set cache-sized, and maps every failure to an error code + message.
+#include <assert.h>
 #include <dlfcn.h>
 #include <math.h>
 #include <float.h>
@@ -192,6 +193,59 @@ static void resize_coord_host(int o, int S, int d, double scale, int* s0, float*
     *s0 = s; *f = t;
 }
 
+// ---- device memory: the ledger of what a context owns ----------------------------------------------------------------------------
+// Every device allocation of a context is recorded (pointer, size, tag) where it is taken, so that mav_destroy frees and mav_mem_info
+// counts whatever exists.  A vector searched linearly: a context holds a few dozen allocations, and only alloc / release / total look
+// at it -- a call whose buffers exist already never comes here.  No lock: a context is single-threaded (include/mavflow.h).
+enum MemTag { MEM_WORKSPACE, MEM_OTHER };       // the Farneback workspace (group slots, deep set, initial-flow snapshot) | everything else
+struct DevMem {
+    struct Out { void** pp; template <typename T> Out(T** p) : pp((void**)p) {} };     // the address of a device pointer of any type
+    struct Want { Out out; size_t bytes; };
+    struct Rec { void* p; size_t bytes; MemTag tag; };
+    std::vector<Rec> recs;
+
+    int alloc(Out out, size_t bytes, MemTag tag, const char* what)
+    {
+        void* p = nullptr;
+        const hipError_t e = hipMalloc(&p, bytes ? bytes : 1);     // (never NULL: a record is a live allocation)
+        if (e != hipSuccess) {
+            (void)hipGetLastError();           // reported here: it must not surface again at the next launch check
+            return fail(e == hipErrorOutOfMemory ? MAV_ERR_OOM : MAV_ERR_HIP, "%s (%zu bytes): %s", what, bytes, hipGetErrorString(e));
+        }
+        recs.push_back({p, bytes, tag});
+        *out.pp = p;
+        return MAV_OK;
+    }
+    // all or nothing: either every destination is set, or none is touched and nothing stays allocated (the set's records are the
+    // ledger's last ones until the destinations are written: nothing else allocates meanwhile, a context being single-threaded)
+    int alloc_set(std::initializer_list<Want> set, MemTag tag, const char* what)
+    {
+        const size_t mark = recs.size();
+        void* p = nullptr;
+        for (const Want& w : set)
+            if (const int rc = alloc(&p, w.bytes, tag, what); rc != MAV_OK) {
+                while (recs.size() > mark) release(recs.back().p);
+                return rc;
+            }
+        size_t i = mark;
+        for (const Want& w : set) *w.out.pp = recs[i++].p;
+        return MAV_OK;
+    }
+    void release(void* p)          // NULL, or a pointer this ledger gave out: anything else is a bookkeeping mistake of the caller
+    {
+        for (size_t i = recs.size(); p && i-- > 0;)
+            if (recs[i].p == p) { recs.erase(recs.begin() + i); hipFree(p); return; }
+        assert(!p && "DevMem::release: a pointer the ledger has no record of");
+    }
+    void release_all() { while (!recs.empty()) release(recs.back().p); }
+    size_t total(MemTag tag) const
+    {
+        size_t n = 0;
+        for (const Rec& r : recs) if (r.tag == tag) n += r.bytes;
+        return n;
+    }
+};
+
 // ---- context -------------------------------------------------------------------------------------------
 struct Layer {
     int w, h, ksize;
@@ -293,7 +347,6 @@ struct LkState {
     unsigned* counters = nullptr;    // [0] max key, [1] candidate count, [2 ..] iteration histogram (MAV_LK_HIST)
     float *pts = nullptr, *out = nullptr;   // MAV_LK_MAX_POINTS x 2 each
     uint8_t* status = nullptr;       // MAV_LK_MAX_POINTS
-    size_t bytes = 0;                // all of the above (mav_mem_info)
     bool hist_valid = false;
 };
 
@@ -370,16 +423,15 @@ struct mav_ctx {
     bool phi_screen = true;          // "phi_screen": the float32 screen in front of the exact phi / threshold arithmetic
     int phi_yloop = 0;               // "phi_yloop": 16-row blocks per workgroup of the phi kernel (0 = automatic)
     size_t htmp_stride = 0;
+    DevMem mem;                    // every device allocation below (and the layers' tables): owner, byte counts, release at mav_destroy
     bool ws_ready = false;         // the Farneback workspace exists (ensure_workspace: allocated by the first call that computes flow)
-    size_t ws_bytes = 0;           // its size
-    size_t group_bytes = 0, deep_bytes = 0;   // ws_bytes = the group slots + the deep set (0 until a call of more than one group)
-    float* flow_ws = nullptr;      // lazily allocated (max_batch) when the caller does not want the flow
+    float* flow_ws = nullptr;      // lazily allocated (max_batch) when the caller does not want the flow (ensure_flow_ws)
     // OPTFLOW_USE_INITIAL_FLOW (mav_farneback_init / _init_dev): the top layer's initial flow, resize(flow0, INTER_AREA) * scale, of the
     // pairs that enter the top layer together (a group, or the deep layers' pairs), built before the first launch that reads it -- so a
-    // call may write its flow over flow0 (the cv2 idiom).  Allocated by the first such call, grown on demand; part of ws_bytes.
+    // call may write its flow over flow0 (the cv2 idiom).  Allocated by the first such call, grown on demand; part of the workspace.
     float* init_snap = nullptr;
     int init_cap = 0;              // pairs it holds
-    size_t init_stride = 0, init_bytes = 0;
+    size_t init_stride = 0;
     // detection scratch (max_batch)
     FoeScratch foe_sc{nullptr, nullptr, nullptr};
     int foe_sc_n = 0;
@@ -405,9 +457,9 @@ struct mav_ctx {
     size_t scratch_next = 0;
     LkState lk;                                 // sparse optical flow workspace (first mav_good_features / mav_lk_track call)
     uint8_t* png_ws = nullptr;                  // PNG encoder: segment slots and records of one chunk of images (first encode call, grow-only)
-    size_t png_ws_bytes = 0;
+    size_t png_ws_cap = 0;                      // bytes it holds
     uint8_t* pyr_ws = nullptr;                  // analyze_pyramid level images (lazily, max_batch)
-    size_t pyr_ws_bytes = 0;
+    size_t pyr_ws_cap = 0;
     unsigned long long* sat = nullptr;          // optimize_window summed-area tables (lazily, max_batch)
     hipEvent_t t0 = nullptr, t1 = nullptr;
     int profiling = 0;               // 0 off; 1 = HIP events around every launch; 2 = around every RUN of launches of one class on a stream
@@ -459,13 +511,6 @@ struct ProfScope {
     }
 };
 
-static void free_layer(Layer& l)
-{
-    if (l.g) hipFree(l.g);
-    if (l.coord) hipFree(l.coord);
-    l.g = nullptr; l.coord = nullptr;
-}
-
 // Pairs of the largest group the small-group schedule can take (is_small_group) when the context runs groups of `group` pairs.
 static int small_group_cap(const mav_ctx* c, int group)
 {
@@ -479,31 +524,19 @@ static int alloc_group(mav_ctx* c, int group)
     const size_t g = (size_t)group, nc = 2 * (c->n1 ? c->n1 : 1);
     // I / I2 hold the 2 g frames of a group (prev and next in one launch; a frame sequence of g pairs has g + 1 <= 2 g frames);
     // Htmp holds g + 1 (the two-pass blur never runs over more frames per launch)
-    enum { NB = 9 };
     // Ic / Rc: for the largest group the small-group schedule can take (is_small_group), 2 g frames of every coarse layer
-    const size_t sg = (size_t)small_group_cap(c, group);
-    const size_t elems[NB] = {c->n0 * 2 * g, 10 * c->n0 * g, 5 * c->n0 * g, 5 * c->n0 * g, nc * g, nc * g, c->htmp_stride * (g + 1),
-                              sg ? 2 * sg * c->c_total : 1, sg ? 10 * sg * c->c_total : 1};
-    float* fresh[NB] = {nullptr};
-    size_t total = 0;
-    for (int i = 0; i < NB; i++) {
-        const hipError_t e = hipMalloc(&fresh[i], sizeof(float) * elems[i]);
-        if (e != hipSuccess) {
-            for (int j = 0; j < NB; j++) if (fresh[j]) hipFree(fresh[j]);
-            (void)hipGetLastError();
-            return fail(e == hipErrorOutOfMemory ? MAV_ERR_OOM : MAV_ERR_HIP, "workspace for group %d (%zu bytes for buffer %d): %s", group,
-                        sizeof(float) * elems[i], i, hipGetErrorString(e));
-        }
-        total += sizeof(float) * elems[i];
-    }
+    const size_t sg = (size_t)small_group_cap(c, group), F = sizeof(float);
+    mav_ctx::WorkSet n;            // the new set, in full before the old one goes
     mav_ctx::WorkSet& w = c->ws;
-    float** bufs[NB] = {&w.I, &w.R, &w.Ma, &w.Mb, &w.fc[0], &w.fc[1], &w.Htmp, &w.Ic, &w.Rc};
-    for (int i = 0; i < NB; i++) { if (*bufs[i]) hipFree(*bufs[i]); *bufs[i] = fresh[i]; }
+    CHK(c->mem.alloc_set({{&n.I, F * c->n0 * 2 * g}, {&n.R, F * 10 * c->n0 * g}, {&n.Ma, F * 5 * c->n0 * g}, {&n.Mb, F * 5 * c->n0 * g},
+                          {&n.fc[0], F * nc * g}, {&n.fc[1], F * nc * g}, {&n.Htmp, F * c->htmp_stride * (g + 1)},
+                          {&n.Ic, F * (sg ? 2 * sg * c->c_total : 1)}, {&n.Rc, F * (sg ? 10 * sg * c->c_total : 1)}},
+                         MEM_WORKSPACE, ("Farneback workspace: a buffer of the slots of group " + std::to_string(group)).c_str()));
+    for (float* old : {w.I, w.R, w.Ma, w.Mb, w.fc[0], w.fc[1], w.Htmp, w.Ic, w.Rc}) c->mem.release(old);
+    w = n;
     c->group = group;
     c->small_g = (int)sg;
     c->ws_ready = true;
-    c->group_bytes = total;
-    c->ws_bytes = c->group_bytes + c->deep_bytes + c->init_bytes;
     return MAV_OK;
 }
 // The deep layers' work set (deep_layers) does not depend on the group and is reachable only by calls of more than one group
@@ -512,23 +545,10 @@ static int alloc_group(mav_ctx* c, int group)
 static int ensure_deep(mav_ctx* c)
 {
     if (c->kd <= 0 || c->deep.I) return MAV_OK;
-    const size_t D = (size_t)c->deep_cap, dt = c->c_total - c->c_off[c->kd], top = c->c_stride[c->kd];
-    const size_t de[6] = {2 * D * dt, 10 * D * dt, 5 * D * top, 5 * D * top, 2 * D * top, 2 * D * top};
-    float* d[6] = {nullptr};
-    size_t bytes = 0;
-    for (int i = 0; i < 6; i++) {
-        const hipError_t e = hipMalloc(&d[i], sizeof(float) * de[i]);
-        if (e != hipSuccess) {
-            for (int j = 0; j < 6; j++) if (d[j]) hipFree(d[j]);
-            (void)hipGetLastError();
-            return fail(e == hipErrorOutOfMemory ? MAV_ERR_OOM : MAV_ERR_HIP, "deep-layer workspace (%zu bytes): %s", sizeof(float) * de[i], hipGetErrorString(e));
-        }
-        bytes += sizeof(float) * de[i];
-    }
-    c->deep.I = d[0]; c->deep.R = d[1]; c->deep.Ma = d[2]; c->deep.Mb = d[3]; c->deep.f[0] = d[4]; c->deep.f[1] = d[5];
-    c->deep_bytes = bytes;                     // only once the whole set exists
-    c->ws_bytes = c->group_bytes + c->deep_bytes + c->init_bytes;
-    return MAV_OK;
+    const size_t D = (size_t)c->deep_cap, dt = c->c_total - c->c_off[c->kd], top = c->c_stride[c->kd], F = sizeof(float);
+    mav_ctx::DeepSet& d = c->deep;
+    return c->mem.alloc_set({{&d.I, F * 2 * D * dt}, {&d.R, F * 10 * D * dt}, {&d.Ma, F * 5 * D * top}, {&d.Mb, F * 5 * D * top},
+                             {&d.f[0], F * 2 * D * top}, {&d.f[1], F * 2 * D * top}}, MEM_WORKSPACE, "Farneback workspace: a buffer of the deep layers");
 }
 // The Farneback workspace (174 MB per 1080p slot, 16 slots by default) belongs to the calls that compute flow: a context created for
 // mav_bbox / mav_tpr_fpr_counts / mav_phi_mask / mav_detect never pays for it (the reference's helpers are stateless free functions,
@@ -562,6 +582,34 @@ static int sync_all_streams(mav_ctx* c)
     return MAV_OK;
 }
 
+// A grow-only buffer: *p holds *cap bytes and is replaced by one of `need` bytes when that is more (contents are not kept).  `cap` is NULL
+// when the caller keeps the capacity in a unit of its own and has decided already.  The caller says on which streams enqueued work may
+// still read the old buffer -- they are drained before it goes -- and whether it goes before the new one is taken (RELEASE_FIRST: the peak
+// is the larger of the two; after a failed allocation the context holds neither, *p NULL and *cap 0) or after (ALLOC_FIRST: a failed
+// allocation leaves *p and *cap as they were, the context stays usable).
+enum ReadOn { READ_ON_COMPUTE, READ_ON_ALL };           // the compute stream | the compute stream and the pair stream
+enum GrowOrder { RELEASE_FIRST, ALLOC_FIRST };
+static int grow_buffer(mav_ctx* c, DevMem::Out p, size_t* cap, size_t need, MemTag tag, ReadOn streams, GrowOrder order, const char* what)
+{
+    if (cap && need <= *cap) return MAV_OK;
+    void* old = *p.pp;
+    if (old && streams == READ_ON_ALL) CHK(sync_all_streams(c));
+    else if (old) HIPCHK(hipStreamSynchronize(c->stream));
+    if (order == RELEASE_FIRST) {
+        c->mem.release(old);
+        old = *p.pp = nullptr;
+        if (cap) *cap = 0;
+    }
+    CHK(c->mem.alloc(p, need, tag, what));
+    c->mem.release(old);
+    if (cap) *cap = need;
+    return MAV_OK;
+}
+static int ensure_flow_ws(mav_ctx* c)          // the flow of a call whose caller does not want to see it
+{
+    return c->flow_ws ? MAV_OK : c->mem.alloc(&c->flow_ws, sizeof(float) * 2 * c->n0 * c->max_batch, MEM_OTHER, "flow buffer");
+}
+
 static void stop_worker(mav_ctx* c);
 extern "C" int mav_destroy(mav_ctx* c)
 {
@@ -571,17 +619,7 @@ extern "C" int mav_destroy(mav_ctx* c)
     (void)sync_all_streams(c);
     if (c->copy_stream) hipStreamSynchronize(c->copy_stream);
     if (c->stager) { c->stager->shutdown(); delete c->stager; c->stager = nullptr; }
-    for (auto& l : c->layers) free_layer(l);
-    {
-        mav_ctx::WorkSet& w = c->ws;
-        void* wb[] = {w.I, w.R, w.Ma, w.Mb, w.fc[0], w.fc[1], w.Htmp, w.Ic, w.Rc, c->deep.I, c->deep.R, c->deep.Ma, c->deep.Mb, c->deep.f[0], c->deep.f[1]};
-        for (void* b : wb) if (b) hipFree(b);
-    }
-    void* bufs[] = {c->flow_ws, c->init_snap, c->foe_sc.cand, c->foe_sc.count, c->foe_sc.best_key, c->foe_sc.done, c->foe_dev, c->box_acc, c->u64_scratch,
-                    c->i32_scratch, c->derot_dev, c->pyr_ws, c->sat, c->render_max, c->render_derot, c->png_ws,
-                    c->lk.pyr[0], c->lk.pyr[1], c->lk.deriv, c->lk.eig, c->lk.cand, c->lk.counters, c->lk.pts, c->lk.out, c->lk.status};
-    for (void* b : bufs) if (b) hipFree(b);
-    for (auto& blk : c->scratch) if (blk.p) hipFree(blk.p);
+    c->mem.release_all();
     for (auto& r : c->prof) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
     if (c->prof_base) hipEventDestroy(c->prof_base);
     for (hipEvent_t e : {c->t0, c->t1, c->copy_done, c->compute_mark, c->gather_done, c->pif_fork, c->pif_join}) if (e) hipEventDestroy(e);
@@ -624,16 +662,15 @@ extern "C" int mav_create(mav_ctx** out, int device, int W, int H, int max_batch
 
     mav_ctx* c = new mav_ctx();
     c->device = device; c->W = W; c->H = H; c->max_batch = max_batch; c->fb = fb;
-    auto bail = [&](int code) { mav_destroy(c); return code; };
-#define HIPB(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { fail(e_ == hipErrorOutOfMemory ? MAV_ERR_OOM : MAV_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); return bail(e_ == hipErrorOutOfMemory ? MAV_ERR_OOM : MAV_ERR_HIP); } } while (0)
+    struct Guard { mav_ctx* c; ~Guard() { mav_destroy(c); } } half_built{c};      // any failure below destroys what exists by then
     // The compute stream now; the copy stream (overlapped uploads) and the pair stream (two pairs in flight) with their events when a
     // call first needs them (ensure_copy_stream / ensure_pair_stream): a context that serves one-pair calls as one of several LANES
     // (mavflow/pipeline.py) then owns exactly one stream, i.e. one hardware queue of the runtime's small pool -- streams beyond the
     // pool's size share queues, and two lanes whose streams share one do not overlap at all.
-    HIPB(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    HIPB(hipEventCreate(&c->t0));
-    HIPB(hipEventCreate(&c->t1));
-    if (!prepare_poly(fb.poly_n, fb.poly_sigma, &c->pc)) { fail(MAV_ERR_ARG, "poly_sigma %g gives a singular moment matrix", fb.poly_sigma); return bail(MAV_ERR_ARG); }
+    HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    HIPCHK(hipEventCreate(&c->t0));
+    HIPCHK(hipEventCreate(&c->t1));
+    if (!prepare_poly(fb.poly_n, fb.poly_sigma, &c->pc)) return fail(MAV_ERR_ARG, "poly_sigma %g gives a singular moment matrix", fb.poly_sigma);
 
     // layer selection exactly as optflowgf.cpp (A.1): levels is the number of EXTRA layers actually reachable
     int levels = 0;
@@ -654,17 +691,17 @@ extern "C" int mav_create(mav_ctx** out, int device, int W, int H, int max_batch
         if (l.ksize < 3) l.ksize = 3;
         l.w = cv_round(W * scale);
         l.h = cv_round(H * scale);
-        if (l.w < 1 || l.h < 1) { fail(MAV_ERR_ARG, "layer %d collapses to %dx%d", k, l.w, l.h); return bail(MAV_ERR_ARG); }
+        if (l.w < 1 || l.h < 1) return fail(MAV_ERR_ARG, "layer %d collapses to %dx%d", k, l.w, l.h);
         std::vector<float> g;
         gaussian_kernel(l.ksize, l.sigma, g);
-        HIPB(hipMalloc(&l.g, g.size() * sizeof(float)));
-        HIPB(hipMemcpy(l.g, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice));
+        CHK(c->mem.alloc(&l.g, g.size() * sizeof(float), MEM_OTHER, "layer taps"));
+        HIPCHK(hipMemcpy(l.g, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice));
         if (k > 0) {                                    // the layer's resize coordinates, once (the kernels used to evaluate them per thread, in double)
             std::vector<int> tab(2 * (size_t)(l.w + l.h));
             for (int x = 0; x < l.w; x++) resize_coord_host(x, W, l.w, (double)W / l.w, &tab[x], (float*)&tab[l.w + x]);
             for (int y = 0; y < l.h; y++) resize_coord_host(y, H, l.h, (double)H / l.h, &tab[2 * l.w + y], (float*)&tab[2 * l.w + l.h + y]);
-            HIPB(hipMalloc(&l.coord, tab.size() * sizeof(int)));
-            HIPB(hipMemcpy(l.coord, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+            CHK(c->mem.alloc(&l.coord, tab.size() * sizeof(int), MEM_OTHER, "layer resize coordinates"));
+            HIPCHK(hipMemcpy(l.coord, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
         }
     }
     c->n0 = (size_t)W * H;
@@ -696,16 +733,13 @@ extern "C" int mav_create(mav_ctx** out, int device, int W, int H, int max_batch
     c->group = group;                                   // the workspace itself comes with the first call that computes flow (ensure_workspace)
     c->small_g = small_group_cap(c, group);
     const size_t B = (size_t)max_batch;
-    HIPB(hipMalloc(&c->foe_dev, sizeof(double) * 2 * B));
-    HIPB(hipMalloc(&c->box_acc, sizeof(int32_t) * 4 * B));
-    HIPB(hipMalloc(&c->u64_scratch, sizeof(unsigned long long) * 8 * B));   // two count blocks of 4 per pair
-    HIPB(hipMalloc(&c->i32_scratch, sizeof(int) * B));
-    HIPB(hipMalloc(&c->derot_dev, sizeof(DerotParams) * B));
-    HIPB(hipMalloc(&c->foe_sc.count, sizeof(int) * B));
-    HIPB(hipMalloc(&c->foe_sc.best_key, sizeof(unsigned long long) * B));
-    HIPB(hipMalloc(&c->foe_sc.done, sizeof(unsigned) * 2 * B));
-    HIPB(hipMemset(c->foe_sc.done, 0, sizeof(unsigned) * 2 * B));
-#undef HIPB
+    CHK(c->mem.alloc_set({{&c->foe_dev, sizeof(double) * 2 * B}, {&c->box_acc, sizeof(int32_t) * 4 * B},
+                          {&c->u64_scratch, sizeof(unsigned long long) * 8 * B},       // two count blocks of 4 per pair
+                          {&c->i32_scratch, sizeof(int) * B}, {&c->derot_dev, sizeof(DerotParams) * B}, {&c->foe_sc.count, sizeof(int) * B},
+                          {&c->foe_sc.best_key, sizeof(unsigned long long) * B}, {&c->foe_sc.done, sizeof(unsigned) * 2 * B}},
+                         MEM_OTHER, "detection scratch"));
+    HIPCHK(hipMemset(c->foe_sc.done, 0, sizeof(unsigned) * 2 * B));
+    half_built.c = nullptr;
     *out = c;
     return MAV_OK;
 }
@@ -842,8 +876,8 @@ extern "C" int mav_layer_dims(const mav_ctx* c, int k, int* w, int* h, int* ksiz
     return MAV_OK;
 }
 
-// Device memory: what the GPU has free / in total (hipMemGetInfo) and what THIS context holds -- the Farneback workspace (0 until a
-// call computes flow), the flow workspace, the detection scratch, the staging blocks of the host-pointer calls, the window-search buffers.
+// Device memory: what the GPU has free / in total (hipMemGetInfo) and what THIS context holds -- the sum of its live device allocations
+// as its ledger has them, and of those the Farneback workspace alone (0 until a call computes flow).
 extern "C" int mav_mem_info(mav_ctx* c, size_t* dev_free, size_t* dev_total, size_t* ctx_bytes, size_t* workspace_bytes)
 {
     if (!c) return fail(MAV_ERR_ARG, "mav_mem_info: NULL context");
@@ -852,19 +886,8 @@ extern "C" int mav_mem_info(mav_ctx* c, size_t* dev_free, size_t* dev_total, siz
     HIPCHK(hipMemGetInfo(&fr, &tot));
     if (dev_free) *dev_free = fr;
     if (dev_total) *dev_total = tot;
-    if (workspace_bytes) *workspace_bytes = c->ws_bytes;
-    if (ctx_bytes) {
-        const size_t B = (size_t)c->max_batch;
-        size_t n = c->ws_bytes + c->pyr_ws_bytes + c->png_ws_bytes + c->lk.bytes;
-        if (c->flow_ws) n += sizeof(float) * 2 * c->n0 * B;
-        if (c->sat) n += sizeof(unsigned long long) * (size_t)(c->W + 1) * (c->H + 1) * B;
-        if (c->foe_sc.cand) n += sizeof(double) * 2 * (size_t)c->foe_sc_n * B;
-        n += B * (sizeof(double) * 2 + sizeof(int32_t) * 4 + sizeof(unsigned long long) * 8 + sizeof(int) + sizeof(DerotParams) + sizeof(int) +
-                  sizeof(unsigned long long) + sizeof(unsigned) * 2);
-        for (const auto& l : c->layers) n += sizeof(float) * l.ksize + (l.coord ? sizeof(int) * 2 * (size_t)(l.w + l.h) : 0);
-        for (const auto& b : c->scratch) n += b.cap;
-        *ctx_bytes = n;
-    }
+    if (workspace_bytes) *workspace_bytes = c->mem.total(MEM_WORKSPACE);
+    if (ctx_bytes) *ctx_bytes = c->mem.total(MEM_WORKSPACE) + c->mem.total(MEM_OTHER);
     return MAV_OK;
 }
 
@@ -1089,7 +1112,10 @@ extern "C" int mav_marker_record(mav_ctx* c, void* marker)
 }
 extern "C" int mav_marker_wait(mav_ctx* c, void* marker)
 {
-    (void)c;                     // waiting needs no context: a marker may outlive the one it was recorded on (mav_destroy drains the streams)
+    // Waiting needs no context, and a marker may outlive the one it was recorded on -- as an object.  Once that context is destroyed
+    // everything the marker stood behind has finished (mav_destroy drains the streams) and the caller must answer "done" by itself, as
+    // the Python layer's _Marker does: the runtime's event still refers to the stream it was last recorded on, which is gone.
+    (void)c;
     if (!marker) return fail(MAV_ERR_ARG, "mav_marker_wait: NULL marker");
     HIPCHK(hipEventSynchronize((hipEvent_t)marker));
     return MAV_OK;
@@ -1221,9 +1247,7 @@ extern "C" int mav_membw_probe(mav_ctx* c, size_t bytes_per_buffer, int reps, do
     HIPCHK(hipSetDevice(c->device));
     const size_t bytes = bytes_per_buffer & ~(size_t)4095;
     float* buf[4] = {nullptr, nullptr, nullptr, nullptr};
-    int rc = MAV_OK;
-    for (int i = 0; i < 4 && rc == MAV_OK; i++)
-        if (hipMalloc(&buf[i], bytes) != hipSuccess) rc = fail(MAV_ERR_OOM, "mav_membw_probe: %zu bytes", bytes);
+    int rc = c->mem.alloc_set({{&buf[0], bytes}, {&buf[1], bytes}, {&buf[2], bytes}, {&buf[3], bytes}}, MEM_OTHER, "mav_membw_probe");
     float ms = 0.f;
     if (rc == MAV_OK) {
         for (int i = 0; i < 3; i++) hipMemsetAsync(buf[i], 0, bytes, c->stream);
@@ -1234,7 +1258,7 @@ extern "C" int mav_membw_probe(mav_ctx* c, size_t bytes_per_buffer, int reps, do
         if (hipEventSynchronize(c->t1) != hipSuccess || hipEventElapsedTime(&ms, c->t0, c->t1) != hipSuccess || hipGetLastError() != hipSuccess)
             rc = fail(MAV_ERR_HIP, "mav_membw_probe: launch or timing failed");
     }
-    for (float* b : buf) if (b) hipFree(b);
+    for (float* b : buf) c->mem.release(b);
     if (rc == MAV_OK) *gbs = 4.0 * (double)bytes * reps / (ms * 1e-3) / 1e9;
     return rc;
 }
@@ -1640,16 +1664,9 @@ static int ensure_init_snapshot(mav_ctx* c, int pairs)
     if (pairs <= c->init_cap) return MAV_OK;
     const Layer& l = c->layers.back();
     const size_t stride = ((size_t)2 * l.w * l.h + 63) & ~(size_t)63, bytes = sizeof(float) * stride * pairs;
-    if (c->init_snap) CHK(sync_all_streams(c));
-    float* p = nullptr;
-    const hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? MAV_ERR_OOM : MAV_ERR_HIP, "initial-flow workspace (%zu bytes): %s", bytes, hipGetErrorString(e));
-    }
-    if (c->init_snap) hipFree(c->init_snap);
-    c->init_snap = p; c->init_cap = pairs; c->init_stride = stride; c->init_bytes = bytes;
-    c->ws_bytes = c->group_bytes + c->deep_bytes + c->init_bytes;
+    // the buffer it replaces may still be read on either stream; the new one first, so that a failed call leaves the context usable
+    CHK(grow_buffer(c, &c->init_snap, nullptr, bytes, MEM_WORKSPACE, READ_ON_ALL, ALLOC_FIRST, "Farneback workspace: initial-flow snapshot"));
+    c->init_cap = pairs; c->init_stride = stride;
     return MAV_OK;
 }
 // optflowgf.cpp at the top layer k = L - 1 with OPTFLOW_USE_INITIAL_FLOW: flow = resize(flow0, (w_k, h_k), INTER_AREA); flow *= scale_k,
@@ -1785,9 +1802,8 @@ extern "C" int mav_schedule_info_ex(mav_ctx* c, int batch, int depth, char* buf,
 static int ensure_foe_scratch(mav_ctx* c, int N)
 {
     if (N <= c->foe_sc_n) return MAV_OK;
-    if (c->foe_sc.cand) hipFree(c->foe_sc.cand);
-    c->foe_sc.cand = nullptr; c->foe_sc_n = 0;
-    HIPCHK(hipMalloc(&c->foe_sc.cand, sizeof(double) * 2 * (size_t)N * c->max_batch));
+    c->foe_sc_n = 0;
+    CHK(grow_buffer(c, &c->foe_sc.cand, nullptr, sizeof(double) * 2 * (size_t)N * c->max_batch, MEM_OTHER, READ_ON_COMPUTE, RELEASE_FIRST, "FoE candidates"));
     c->foe_sc_n = N;
     return MAV_OK;
 }
@@ -1890,7 +1906,7 @@ extern "C" int mav_process_batch_dev(mav_ctx* c, const uint8_t* prev, const uint
     if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "batch %d outside [1, %d]", batch, c->max_batch);
     HIPCHK(hipSetDevice(c->device));
     if (!flow) {
-        if (!c->flow_ws) HIPCHK(hipMalloc(&c->flow_ws, sizeof(float) * 2 * c->n0 * c->max_batch));
+        CHK(ensure_flow_ws(c));
         flow = c->flow_ws;
     }
     CHK(mav_farneback_dev(c, prev, next, batch, flow));
@@ -1943,7 +1959,7 @@ static int frame_step_body(mav_ctx* c, const mav_frame_step* s, bool* started)
     float* flow = s->flow_dev;
     if (s->compute_flow) {
         if (!flow) {                             // nobody wants to see the flow: the context's own buffer, as mav_process_batch_dev
-            if (!c->flow_ws) HIPCHK(hipMalloc(&c->flow_ws, sizeof(float) * 2 * c->n0 * c->max_batch));
+            CHK(ensure_flow_ws(c));
             flow = c->flow_ws;
         }
         CHK(mav_farneback_dev(c, s->prev_dev, s->next_dev, s->n, flow));
@@ -2117,12 +2133,7 @@ struct DevBuf {
     {
         if (c->scratch_next == c->scratch.size()) c->scratch.emplace_back();
         mav_ctx::Block& b = c->scratch[c->scratch_next++];
-        if (b.cap < bytes || !b.p) {
-            if (b.p) { HIPCHK(hipStreamSynchronize(c->stream)); hipFree(b.p); b.p = nullptr; b.cap = 0; }
-            const size_t want = bytes ? bytes : 1;
-            HIPCHK(hipMalloc(&b.p, want));
-            b.cap = want;
-        }
+        CHK(grow_buffer(c, &b.p, &b.cap, bytes ? bytes : 1, MEM_OTHER, READ_ON_COMPUTE, RELEASE_FIRST, "staging block"));
         p = b.p;
         return MAV_OK;
     }
@@ -2459,13 +2470,7 @@ static size_t pyr_bytes(const PyrPlan& p, int batch_cap)
 }
 static int ensure_pyr_ws(mav_ctx* c, const PyrPlan& p)
 {
-    const size_t need = pyr_bytes(p, c->max_batch);
-    if (need <= c->pyr_ws_bytes) return MAV_OK;
-    if (c->pyr_ws) { HIPCHK(hipStreamSynchronize(c->stream)); hipFree(c->pyr_ws); }
-    c->pyr_ws = nullptr; c->pyr_ws_bytes = 0;
-    if (hipMalloc(&c->pyr_ws, need) != hipSuccess) return fail(MAV_ERR_OOM, "pyramid workspace (%zu bytes)", need);
-    c->pyr_ws_bytes = need;
-    return MAV_OK;
+    return grow_buffer(c, &c->pyr_ws, &c->pyr_ws_cap, pyr_bytes(p, c->max_batch), MEM_OTHER, READ_ON_COMPUTE, RELEASE_FIRST, "pyramid workspace");
 }
 // levels 1 .. upto of `batch` images (device pointer img0) into the workspace
 static void build_pyramid(mav_ctx* c, const PyrPlan& p, const uint8_t* img0, int batch, int upto)
@@ -2536,8 +2541,7 @@ extern "C" int mav_optimize_window(mav_ctx* c, const uint8_t* img, int batch, co
 {
     CHK(check_batch(c, batch, "mav_optimize_window"));
     if (!img || !window_in || !score || !window_out) return fail(MAV_ERR_ARG, "mav_optimize_window: NULL argument");
-    if (!c->sat && hipMalloc(&c->sat, sizeof(unsigned long long) * (size_t)(c->W + 1) * (c->H + 1) * c->max_batch) != hipSuccess)
-        return fail(MAV_ERR_OOM, "summed-area tables");
+    if (!c->sat) CHK(c->mem.alloc(&c->sat, sizeof(unsigned long long) * (size_t)(c->W + 1) * (c->H + 1) * c->max_batch, MEM_OTHER, "summed-area tables"));
     DevBuf di, dw, ds, dwo;
     CHK(di.upload(c, img, c->n0 * batch)); CHK(dw.upload(c, window_in, sizeof(int32_t) * 4 * batch));
     CHK(ds.alloc(c, sizeof(int64_t) * batch)); CHK(dwo.alloc(c, sizeof(int32_t) * 4 * batch));
@@ -2651,9 +2655,9 @@ extern "C" int mav_tpr_fpr_counts_dev(mav_ctx* c, const uint8_t* gt, int gt_imag
 // ---- result images (include/mavflow.h: mav_render) ----------------------------------------------------------------------------
 static int ensure_render(mav_ctx* c)
 {
-    if (!c->render_max) HIPCHK(hipMalloc(&c->render_max, sizeof(unsigned long long) * c->max_batch));
-    if (!c->render_derot) HIPCHK(hipMalloc(&c->render_derot, sizeof(DerotParams) * c->max_batch));
-    return MAV_OK;
+    if (c->render_max) return MAV_OK;
+    return c->mem.alloc_set({{&c->render_max, sizeof(unsigned long long) * c->max_batch}, {&c->render_derot, sizeof(DerotParams) * c->max_batch}},
+                            MEM_OTHER, "render scratch");
 }
 static int render_enqueue(mav_ctx* c, const float* flow, const DerotParams* derot, const double* foe, const uint8_t* sky, int batch,
                           const mav_thr_params& t, uint8_t* img_result, uint8_t* img_flow, uint8_t* img_phi)
@@ -2879,15 +2883,7 @@ extern "C" int mav_png_encode_dev(mav_ctx* c, const uint8_t* imgs, int count, in
     if (chunk < 1) chunk = 1;
     if (chunk > (size_t)count) chunk = count;
     if (chunk > 65535) chunk = 65535;
-    if (c->png_ws_bytes < chunk * per) {
-        if (c->png_ws) { HIPCHK(hipStreamSynchronize(c->stream)); hipFree(c->png_ws); c->png_ws = nullptr; c->png_ws_bytes = 0; }
-        if (hipMalloc(&c->png_ws, chunk * per) != hipSuccess) {
-            (void)hipGetLastError();
-            c->png_ws = nullptr;
-            return fail(MAV_ERR_OOM, "mav_png_encode_dev: %zu bytes of encoder workspace", chunk * per);
-        }
-        c->png_ws_bytes = chunk * per;
-    }
+    CHK(grow_buffer(c, &c->png_ws, &c->png_ws_cap, chunk * per, MEM_OTHER, READ_ON_COMPUTE, RELEASE_FIRST, "PNG encoder workspace"));
     ProfScope ps(c, K_MISC);
     for (int i0 = 0; i0 < count; i0 += (int)chunk) {
         const int n = count - i0 < (int)chunk ? count - i0 : (int)chunk;
@@ -3308,25 +3304,13 @@ static int check_lk_params(mav_lk_params& p, int n, const char* fn)
 static int ensure_lk(mav_ctx* c)
 {
     LkState& k = c->lk;
-    if (k.bytes) return MAV_OK;
+    if (k.status) return MAV_OK;                  // (all or nothing: any one of the set tells)
     lk_level_dims(c->W, c->H, &k.dims);
     k.pyr_elems = (size_t)k.dims.off[k.dims.n - 1] + (((size_t)k.dims.w[k.dims.n - 1] * k.dims.h[k.dims.n - 1] + 63) & ~(size_t)63);
-    const size_t sizes[] = {k.pyr_elems, k.pyr_elems, k.pyr_elems * sizeof(short2), c->n0 * sizeof(float), (size_t)MAV_GFTT_MAX_CANDIDATES * sizeof(uint2),
-                            (2 + MAV_LK_HIST) * sizeof(unsigned), (size_t)MAV_LK_MAX_POINTS * 2 * sizeof(float),
-                            (size_t)MAV_LK_MAX_POINTS * 2 * sizeof(float), (size_t)MAV_LK_MAX_POINTS};
-    void** const ptrs[] = {(void**)&k.pyr[0], (void**)&k.pyr[1], (void**)&k.deriv, (void**)&k.eig, (void**)&k.cand, (void**)&k.counters, (void**)&k.pts,
-                           (void**)&k.out, (void**)&k.status};
-    size_t total = 0;
-    for (size_t i = 0; i < sizeof(sizes) / sizeof(sizes[0]); i++) {
-        if (hipMalloc(ptrs[i], sizes[i]) != hipSuccess) {
-            (void)hipGetLastError();
-            for (size_t j = 0; j < i; j++) { hipFree(*ptrs[j]); *ptrs[j] = nullptr; }
-            return fail(MAV_ERR_OOM, "sparse optical flow workspace (%zu bytes)", sizes[i]);
-        }
-        total += sizes[i];
-    }
-    k.bytes = total;
-    k.cur = -1; k.built[0] = k.built[1] = 0; k.deriv_slot = -1; k.deriv_levels = 0;
+    const size_t pts = (size_t)MAV_LK_MAX_POINTS * 2 * sizeof(float);
+    CHK(c->mem.alloc_set({{&k.pyr[0], k.pyr_elems}, {&k.pyr[1], k.pyr_elems}, {&k.deriv, k.pyr_elems * sizeof(short2)}, {&k.eig, c->n0 * sizeof(float)},
+                          {&k.cand, (size_t)MAV_GFTT_MAX_CANDIDATES * sizeof(uint2)}, {&k.counters, (2 + MAV_LK_HIST) * sizeof(unsigned)},
+                          {&k.pts, pts}, {&k.out, pts}, {&k.status, (size_t)MAV_LK_MAX_POINTS}}, MEM_OTHER, "sparse optical flow workspace"));
     return MAV_OK;
 }
 
@@ -3430,7 +3414,7 @@ static int good_features_entry(mav_ctx* c, const uint8_t* gray, bool host, const
     CHK(check_gftt_params(p, fn));
     if (!c || !corners || !count) return fail(MAV_ERR_ARG, "%s: NULL argument", fn);
     HIPCHK(hipSetDevice(c->device));
-    if (!gray && (!c->lk.bytes || c->lk.cur < 0)) return fail(MAV_ERR_STATE, "%s: gray is NULL and no frame is resident", fn);
+    if (!gray && c->lk.cur < 0) return fail(MAV_ERR_STATE, "%s: gray is NULL and no frame is resident", fn);
     CHK(ensure_lk(c));
     LkState& k = c->lk;
     if (gray) {
@@ -3485,7 +3469,7 @@ static int lk_track_check(mav_ctx* c, const uint8_t* prev, const uint8_t* next, 
     CHK(check_lk_params(*p, n, fn));
     if (!c || !next || (n > 0 && (!pts || !out || !status))) return fail(MAV_ERR_ARG, "%s: NULL argument", fn);
     HIPCHK(hipSetDevice(c->device));
-    if (!prev && (!c->lk.bytes || c->lk.cur < 0)) return fail(MAV_ERR_STATE, "%s: prev is NULL and no frame is resident", fn);
+    if (!prev && c->lk.cur < 0) return fail(MAV_ERR_STATE, "%s: prev is NULL and no frame is resident", fn);
     return ensure_lk(c);
 }
 extern "C" int mav_lk_track(mav_ctx* c, const uint8_t* prev, const uint8_t* next, const float* pts, int n, const mav_lk_params* pp, float* next_pts,
@@ -3512,7 +3496,7 @@ extern "C" int mav_lk_track_dev(mav_ctx* c, const uint8_t* prev, const uint8_t* 
 extern "C" int mav_lk_last_iterations(mav_ctx* c, uint32_t* hist)
 {
     if (!c || !hist) return fail(MAV_ERR_ARG, "mav_lk_last_iterations: NULL argument");
-    if (!c->lk.bytes || !c->lk.hist_valid) return fail(MAV_ERR_STATE, "mav_lk_last_iterations: no track call precedes");
+    if (!c->lk.hist_valid) return fail(MAV_ERR_STATE, "mav_lk_last_iterations: no track call precedes");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipMemcpyAsync(hist, c->lk.counters + 2, MAV_LK_HIST * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     return mav_sync(c);

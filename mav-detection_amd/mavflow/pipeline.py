@@ -141,9 +141,14 @@ class _Marker:
         check(ctx.lib.mav_marker_record(ctx.h, m))
 
     def wait(self) -> None:
-        check(self.ctx.lib.mav_marker_wait(None, self.m))
+        # A closed context has drained its streams (mav_destroy): whatever the marker stands behind has finished.  The runtime must not
+        # be asked then: its event still points at the stream it was last recorded on, which is gone with the context.
+        if self.ctx.alive:
+            check(self.ctx.lib.mav_marker_wait(None, self.m))
 
     def done(self) -> bool:
+        if not self.ctx.alive:
+            return True
         d = C.c_int(0)
         check(self.ctx.lib.mav_marker_query(None, self.m, C.byref(d)))
         return bool(d.value)

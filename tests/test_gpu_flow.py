@@ -405,9 +405,11 @@ def test_options_are_reported_and_validated(mav):
     """Every scheduling switch is an option of the context (the library reads no environment variable): set / get round trip,
     range errors as ValueError, and mav_schedule_info reports the options and the per-layer plan a call will take."""
     from mavflow import _lib
-    src = "".join(open(os.path.join(os.path.dirname(_lib.__file__), "..", "csrc", f)).read()
-                  for f in ("mavflow.cpp", "kernels_flow.hip", "kernels_detect.hip", "kernels_window.hip"))
-    assert "getenv" not in src
+    csrc = os.path.join(os.path.dirname(_lib.__file__), "..", "csrc")
+    sources = sorted(os.path.join(d, f) for d, _, files in os.walk(csrc) for f in files if f.endswith((".hip", ".cpp", ".h")))
+    assert {"mavflow.cpp", "mavflow_internal.h", "kernels_flow.hip", "kernels_detect.hip", "kernels_window.hip"} <= {os.path.basename(f) for f in sources}
+    for f in sources:                                            # every source file there is, whatever is added later
+        assert "getenv" not in open(f).read(), f
     with _lib.Context(1920, 1080, 64) as c:
         info = c.schedule_info(64)
         assert info["group"] == 16 and info["pairs_in_flight"] == 2 and info["pairs_per_group"] == 16

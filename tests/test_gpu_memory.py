@@ -154,3 +154,82 @@ def test_two_contexts_in_two_threads_are_independent(mav):
     for t in threads:
         t.join()
     assert not errors, errors
+
+
+def _walk(ctx, d):
+    """Every call of a context that allocates device memory lazily, once each: [(step, mem_info after it)]."""
+    from mavflow import _lib
+    prev, nxt, smp, B = d["prev"], d["nxt"], d["samples"], d["prev"].shape[0]
+    marks = []
+
+    def step(name, fn):
+        out = fn()
+        marks.append((name, ctx.mem_info()))
+        return out
+
+    def process_batch_dev_without_flow():                       # nobody wants the flow: the context's own flow buffer
+        bufs = [ctx.alloc(a.nbytes).upload(a) for a in (prev, nxt, smp)] + [ctx.alloc(B * _lib.RESULT_DTYPE.itemsize)]
+        try:
+            ctx.process_batch_dev(bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, B, bufs[3].ptr)
+            ctx.sync()
+        finally:
+            for b in bufs:                                      # caller-owned memory: not the context's, and not in dev_free afterwards
+                b.free()
+
+    def sparse():
+        pts = ctx.good_features(prev[0])
+        ctx.lk_track(None, nxt[0], pts)
+
+    step("bbox", lambda: ctx.bbox(prev))
+    flow = step("farneback, several groups", lambda: ctx.farneback(prev, nxt).copy())
+    step("farneback with an initial flow", lambda: ctx.farneback(prev, nxt, initial_flow=flow))
+    out = step("process_batch", lambda: ctx.process_batch(prev, nxt, smp))
+    step("process_batch_dev without a flow pointer", process_batch_dev_without_flow)
+    foe = [(ctx.W / 2.0, ctx.H / 2.0)] * B
+    step("render", lambda: ctx.render(flow, foe))
+    step("overlay", lambda: ctx.overlay(d["bgr"], out["mask_fixed"], foe, foe))
+    step("png_encode", lambda: ctx.png_encode(prev))
+    step("analyze_pyramid", lambda: ctx.analyze_pyramid(prev))
+    step("optimize_window", lambda: ctx.optimize_window(prev, [(40, 30, 64, 64)] * B))
+    step("good_features + lk_track", sparse)
+    step("flow_to_color of a float64 field", lambda: ctx.flow_to_color(flow.astype(np.float64)))    # 16 bytes per pixel: grows staging block 0
+    return marks
+
+
+def test_every_lazy_allocation_is_counted_kept_when_warm_and_given_back(mav):
+    """The context's device memory from outside, over every call that allocates lazily (_walk): mav_mem_info's ctx_bytes never
+    decreases from one call to the next, the host call with the largest staging buffer grows it, a second pass over the same calls
+    leaves ctx_bytes and workspace_bytes exactly where the first left them (nothing is reallocated once warm), and close() gives
+    everything back: the device's free memory, read from a small context that stays open, is the same after every walk in a fresh
+    context -- a buffer mav_destroy forgets would make every walk take more than the one before.
+    Measured on one MI355X, six walks in a process that had done nothing else, before and after the ledger went in (the same figures
+    from both libraries): dev_free 308 363 132 928 after the first walk's close(), 308 354 744 320 after each of the other five.  The
+    HIP runtime keeps 8 MiB more from the second walk on (pools of its own: in a process that other tests have warmed the first two
+    readings agree as well), so a walk whose reading is not compared goes first, the next two must agree to the byte -- the parent's
+    spread over five repetitions is zero --, and the first may exceed them by that 8 MiB at most."""
+    from mavflow import _lib
+    W, H, B = 320, 240, 4
+    prev, nxt = synth.make_batch(W, H, B, distinct=B)
+    d = dict(prev=prev, nxt=nxt, samples=np.stack([synth.foe_samples(W, H, b) for b in range(B)]),
+             bgr=np.ascontiguousarray(np.stack([prev, nxt, prev], axis=-1)))
+    free_after = []
+    with _lib.Context(64, 48, 1) as probe:
+        probe.bbox(np.zeros((48, 64), np.uint8))
+        for walk in range(3):
+            with _lib.Context(W, H, B) as ctx:
+                ctx.set_option("group", 2)                       # 4 pairs = 2 groups: the deep layers' set comes too
+                last = ctx.mem_info()
+                assert last["workspace_bytes"] == 0
+                for name, info in _walk(ctx, d):
+                    print(f"walk {walk}: ctx_bytes {info['ctx_bytes']:>10} workspace_bytes {info['workspace_bytes']:>10} after {name}")
+                    assert info["ctx_bytes"] >= last["ctx_bytes"] and info["workspace_bytes"] >= last["workspace_bytes"], name
+                    if name.startswith("flow_to_color"):
+                        assert info["ctx_bytes"] > last["ctx_bytes"], name
+                    last = info
+                assert 0 < last["workspace_bytes"] < last["ctx_bytes"]
+                for name, info in _walk(ctx, d):                 # warm: every buffer exists and is large enough
+                    assert (info["ctx_bytes"], info["workspace_bytes"]) == (last["ctx_bytes"], last["workspace_bytes"]), name
+            free_after.append(probe.mem_info()["dev_free"])
+            print(f"walk {walk}: dev_free after close() {free_after[-1]}")
+    assert free_after[2] == free_after[1], free_after            # a later walk takes no more than the one before: nothing leaks
+    assert free_after[0] - free_after[1] <= 8 * MB, free_after

@@ -368,3 +368,35 @@ def test_a_step_refused_inside_the_detection_leaves_the_pipeline_usable(mav, wor
         assert freed >= held // 2, (freed, held)                     # (allocation granularity and other tenants of the device)
         ctx.sync()
     ref.close()
+
+
+def test_a_marker_of_a_closed_context_is_done_without_asking_the_runtime(mav):
+    """A handle retired by pipe.close() is read after its context has gone (test_gpu_api_loop.py does so): mav_destroy has drained the
+    streams, so the marker behind the handle's copy has fired, but the runtime's event still refers to the destroyed stream and must
+    not be waited for or queried -- doing so gave "operation not permitted on an event last recorded in a capturing stream" when the
+    heap had reused the stream's memory.  _Marker answers by itself then, and leaves no error behind for the next call."""
+    from mavflow import _lib
+    from mavflow.pipeline import _Marker
+    asked = []
+    with _lib.Context(64, 48, 1) as ctx:
+        img = np.zeros((48, 64), np.uint8)
+        img[5:9, 7:20] = 200
+        ctx.bbox(img)
+        m = _Marker(ctx)
+        assert m.done() in (True, False)                                   # alive: the runtime answers
+        m.wait()
+        assert m.done() is True
+        lib = ctx.lib
+    assert not ctx.alive
+
+    class Spy:                                                             # the library behind the marker, counting what is asked of it
+        def __getattr__(self, name):
+            if name in ("mav_marker_wait", "mav_marker_query"):
+                asked.append(name)
+            return getattr(lib, name)
+    ctx.lib = Spy()
+    m.wait()
+    assert m.done() is True and asked == []
+    ctx.lib = lib
+    with _lib.Context(64, 48, 1) as other:                                 # nothing sticky is left for the next launch check
+        assert tuple(other.bbox(img)[0]) == (7, 5, 19, 8)
