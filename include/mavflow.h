@@ -502,7 +502,9 @@ int mav_last_overlay_png(mav_ctx*, const uint8_t* frames, const double* foe_gt, 
  * THE RESIDENT FRAME: the context keeps the frame it saw last (the `next` of mav_lk_track, or the frame given to mav_good_features) and
  * its pyramid on the device.  Passing NULL for `prev` / `gray` means that frame: a video uploads every frame once and builds its
  * pyramid once.  MAV_ERR_STATE when there is none.  The workspace (two pyramids, one derivative pyramid, the eigenvalue map, candidates,
- * points: 12 bytes per pixel + 3.2 MB) is allocated by the first of these calls and reported by mav_mem_info. */
+ * points: 12 bytes per pixel + 3.2 MB; 6 898 868 bytes at 640 x 480) is allocated by the first of these calls and reported by
+ * mav_mem_info.  The device sort and pick add 12 bytes to it: the sort is in place, the pick's grid of accepted corners lives in the
+ * eigenvalue map (dead once the candidates are out), a host mask is staged in the frame slot that no call reads again. */
 typedef struct {
     int max_corners;          /* 1 .. MAV_LK_MAX_POINTS */
     double quality_level;     /* > 0 */
@@ -523,18 +525,37 @@ typedef struct {
 void mav_gftt_defaults(mav_gftt_params*);
 void mav_lk_defaults(mav_lk_params*);
 /* corners (max_corners, 2) float32 (x, y) in acceptance order (strongest first; ties by linear index, larger first), *count of them.
- * gray NULL: the resident frame; otherwise `gray` is uploaded and becomes the resident frame.  Eigenvalue map, threshold, non-maximum
- * test and candidate compaction run on the device; the sort and the greedy minimum-distance pick run on the host inside the call. */
+ * gray NULL: the resident frame; otherwise `gray` is uploaded and becomes the resident frame.  Everything runs on the device:
+ * eigenvalue map, threshold, non-maximum test, candidate compaction, the sort and the greedy minimum-distance pick; the
+ * call brings back the count and the corners and synchronises once. */
 int mav_good_features(mav_ctx*, const uint8_t* gray, const mav_gftt_params* /* NULL = defaults */, float* corners, int* count);
+/* The same with cv2's `mask` argument: (H, W) u8 or NULL (= mav_good_features bit for bit).  As cv2 does it (restated from OpenCV's
+ * published routine, unpinned like the rest): quality_level multiplies the maximum of the eigenvalue map over the pixels whose mask byte
+ * is non-zero; the threshold and the 3 x 3 non-maximum test see the whole map (a masked-out neighbour still suppresses); only pixels
+ * with a non-zero mask byte become corners.  An all-zero mask: no corner, no error. */
+int mav_good_features_ex(mav_ctx*, const uint8_t* gray, const uint8_t* mask, const mav_gftt_params*, float* corners, int* count);
 /* next_pts (n, 2) float32 and status (n) u8 for pts (n, 2) float32, 0 <= n <= MAV_LK_MAX_POINTS.  NaN / inf / far-away points are not
  * errors: they end with status 0 as in cv2.  `next` becomes the resident frame.  cv2's error output is not computed. */
 int mav_lk_track(mav_ctx*, const uint8_t* prev /* NULL: the resident frame */, const uint8_t* next, const float* pts, int n,
                  const mav_lk_params* /* NULL = defaults */, float* next_pts, uint8_t* status);
 /* Device-pointer forms.  mav_lk_track_dev only enqueues (frames are copied into the workspace on the device).  mav_good_features_dev
- * takes a device frame but returns host corners: the pick is host code, so the call synchronises. */
+ * takes a device frame and returns host corners: its outputs are host memory, so the call synchronises (once). */
 int mav_good_features_dev(mav_ctx*, const uint8_t* gray_dev, const mav_gftt_params*, float* corners_host, int* count);
 int mav_lk_track_dev(mav_ctx*, const uint8_t* prev_dev, const uint8_t* next_dev, const float* pts_dev, int n, const mav_lk_params*,
                      float* next_pts_dev, uint8_t* status_dev);
+/* Corners with device pointers in AND out: only enqueues on the context's stream.  gray_dev NULL: the resident frame; mask_dev (H, W) u8
+ * or NULL.  corners_dev holds max_corners x 2 floats, entries from *count_dev on are left as they were.  The host cannot see a candidate
+ * overflow here: *count_dev = -(number of candidates) and no corner is written (never a silent cut). */
+int mav_good_features_ex_dev(mav_ctx*, const uint8_t* gray_dev, const uint8_t* mask_dev, const mav_gftt_params*, float* corners_dev,
+                             int32_t* count_dev);
+/* mav_lk_track_dev sized for n_max points whose count lives on the device: waves with index >= *n_dev leave at once without touching
+ * memory (all of them if *n_dev is negative); *n_dev == n_max gives the bytes of mav_lk_track_dev(n_max).  mav_lk_last_iterations counts
+ * the points that ran.  With mav_good_features_ex_dev: corners -> track as one chain, no host call in between. */
+int mav_lk_track_ex_dev(mav_ctx*, const uint8_t* prev_dev, const uint8_t* next_dev, const float* pts_dev, int n_max, const int32_t* n_dev,
+                        const mav_lk_params*, float* next_pts_dev, uint8_t* status_dev);
+/* What the most recent corner pick did: stats[0] = chunks of 1024 ranks it walked, stats[1] = rounds over all chunks.
+ * Synchronises. */
+int mav_gftt_last_pick(mav_ctx*, uint32_t* stats);
 /* Iterations the tracker's loop ran per (point, level) in the most recent track call: hist[i] = how many ran i iterations
  * (i = 0: left the level at the first bounds test), MAV_LK_HIST_BINS bins, the last one = more.  Levels skipped before the loop do not count. */
 #define MAV_LK_HIST_BINS 104
@@ -618,6 +639,9 @@ int mav_stage_pyramid_level(mav_ctx*, const uint8_t* img, double scale, int leve
 int mav_stage_lk_pyramid(mav_ctx*, const uint8_t* img, int level, uint8_t* out);
 int mav_stage_lk_scharr(mav_ctx*, const uint8_t* img, int level, int16_t* out);
 int mav_stage_min_eigen(mav_ctx*, const uint8_t* img, int block_size, float* out);
+/* the device sort and pick of mav_good_features on n host candidate keys, (value bits << 32) | linear index: distinct, index < W * H,
+ * any order, n <= MAV_GFTT_MAX_CANDIDATES.  quality_level and block_size are not used.  The resident frame stays. */
+int mav_stage_corner_pick(mav_ctx*, const uint64_t* keys, int n, const mav_gftt_params*, float* corners, int* count);
 
 #ifdef __cplusplus
 }

@@ -29,12 +29,13 @@ __device__ __forceinline__ float float_of(unsigned k) { return __uint_as_float((
 // One 16 x 16 tile per workgroup.  Sobel 3x3 pairs of the tile and its halo of r = block / 2 go to LDS as int16 (|d| <= 1020); the
 // derivative at a halo position outside the image is the derivative AT the REFLECT_101 position (boxFilter reflects the product
 // images, which is not the derivative of the reflected frame: dx * dy would change sign).  Box sums of dx*dx, dx*dy, dy*dy are
-// separable integer sums (<= 225 x 1020^2 < 2^31), then five float32 operations.  The tile's maximum goes to *maxkey.
+// separable integer sums (<= 225 x 1020^2 < 2^31), then five float32 operations.  The tile's maximum goes to *maxkey; with a mask
+// (cv2's minMaxLoc(eig, ..., mask)) only pixels whose mask byte is non-zero take part in it, the map itself is the whole map.
 #define EIG_TILE 16
 #define EIG_MAX_R 7
 #define EIG_T (EIG_TILE + 2 * EIG_MAX_R)
-__global__ __launch_bounds__(256) void k_min_eig(const uint8_t* __restrict__ img, int W, int H, int r, float s2, float* __restrict__ eig,
-                                                 unsigned* __restrict__ maxkey)
+__global__ __launch_bounds__(256) void k_min_eig(const uint8_t* __restrict__ img, const uint8_t* __restrict__ mask, int W, int H, int r, float s2,
+                                                 float* __restrict__ eig, unsigned* __restrict__ maxkey)
 {
     __shared__ short2 d[EIG_T * EIG_T];
     __shared__ int hs[3][EIG_T * EIG_TILE];
@@ -74,7 +75,7 @@ __global__ __launch_bounds__(256) void k_min_eig(const uint8_t* __restrict__ img
         const float a = (float)xx * s2 * 0.5f, b = (float)xy * s2, c = (float)yy * s2 * 0.5f;
         const float e = (a + c) - sqrtf((a - c) * (a - c) + b * b);
         eig[(size_t)y * W + x] = e;
-        key = key_of(e);
+        if (!mask || mask[(size_t)y * W + x]) key = key_of(e);
     }
     for (int m = 32; m >= 1; m >>= 1) { const unsigned o = __shfl_xor(key, m); key = o > key ? o : key; }
     if ((tid & 63) == 0) wmax[tid >> 6] = key;
@@ -86,14 +87,17 @@ __global__ __launch_bounds__(256) void k_min_eig(const uint8_t* __restrict__ img
 }
 
 // threshold (eig > max * qualityLevel), the 3x3 non-maximum test on interior pixels, atomic append of (value bits, linear index).
-// *count keeps counting past cap: the host reports the capacity needed.  The append order is arbitrary; the host's total order is not.
-__global__ __launch_bounds__(256) void k_corner_candidates(const float* __restrict__ eig, int W, int H, const unsigned* __restrict__ maxkey,
-                                                           double quality, uint2* __restrict__ cand, unsigned* __restrict__ count, unsigned cap)
+// *count keeps counting past cap: the pick reports the capacity needed.  The append order is arbitrary; the pick's total order is not.
+// A masked-out pixel is no candidate but still suppresses its neighbours; an all-zero mask leaves *maxkey at 0 = NaN: no candidate.
+__global__ __launch_bounds__(256) void k_corner_candidates(const float* __restrict__ eig, const uint8_t* __restrict__ mask, int W, int H,
+                                                           const unsigned* __restrict__ maxkey, double quality, uint2* __restrict__ cand,
+                                                           unsigned* __restrict__ count, unsigned cap)
 {
     const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (size_t)W * H) return;
     const int y = (int)(idx / W), x = (int)(idx - (size_t)y * W);
     if (x < 1 || x > W - 2 || y < 1 || y > H - 2) return;
+    if (mask && !mask[idx]) return;
     const float thr = (float)((double)float_of(*maxkey) * quality);
     const float v = eig[idx];
     if (!(v > thr)) return;
@@ -104,17 +108,188 @@ __global__ __launch_bounds__(256) void k_corner_candidates(const float* __restri
     if (slot < cap) cand[slot] = make_uint2(__float_as_uint(v), (unsigned)idx);
 }
 
-void launch_min_eig(hipStream_t st, const uint8_t* img, int W, int H, int block_size, float s2, float* eig, unsigned* maxkey)
+void launch_min_eig(hipStream_t st, const uint8_t* img, const uint8_t* mask, int W, int H, int block_size, float s2, float* eig, unsigned* maxkey)
 {
     dim3 grid((W + EIG_TILE - 1) / EIG_TILE, (H + EIG_TILE - 1) / EIG_TILE);
-    hipLaunchKernelGGL(k_min_eig, grid, dim3(256), 0, st, img, W, H, block_size / 2, s2, eig, maxkey);
+    hipLaunchKernelGGL(k_min_eig, grid, dim3(256), 0, st, img, mask, W, H, block_size / 2, s2, eig, maxkey);
 }
-void launch_corner_candidates(hipStream_t st, const float* eig, int W, int H, const unsigned* maxkey, double quality, uint2* cand,
-                              unsigned* count, unsigned cap)
+void launch_corner_candidates(hipStream_t st, const float* eig, const uint8_t* mask, int W, int H, const unsigned* maxkey, double quality,
+                              uint2* cand, unsigned* count, unsigned cap)
 {
     const size_t n = (size_t)W * H;
-    hipLaunchKernelGGL(k_corner_candidates, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, eig, W, H, maxkey, quality, cand, count, cap);
+    hipLaunchKernelGGL(k_corner_candidates, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, eig, mask, W, H, maxkey, quality, cand, count, cap);
 }
+
+// ---- corners: the sort and the greedy minimum-distance pick ----------------------------------------------------------------------
+// Every launch below is enqueued without the host knowing the candidate count n: kernels read it from *n_ptr, and workgroups (whole
+// launches, for a small n) beyond it leave.  n > cap (overflow) makes every sort kernel leave and the pick report -n.
+//
+// Sort: bitonic, in place, descending by the key (value bits << 32) | linear index, over Np = n rounded up to a power of two (cap is
+// one); the first launch turns cand[n .. Np) into zero keys, which sort behind every candidate.  Strides below PICK_SORT_CHUNK run in
+// LDS (32 KB of keys per workgroup), the others as one launch per (k, j) step.
+#define PICK_SORT_CHUNK 4096u
+#define PICK_WG 1024
+__device__ __forceinline__ unsigned long long pick_key(uint2 c) { return ((unsigned long long)c.x << 32) | c.y; }
+__device__ __forceinline__ uint2 pick_unkey(unsigned long long k) { return make_uint2((unsigned)(k >> 32), (unsigned)k); }
+__device__ __forceinline__ unsigned pick_np2(unsigned n) { return n <= 1 ? 1u : 1u << (32 - __clz(n - 1)); }
+
+// k_from == 0: the chunk's own sort, k = 2 .. min(Np, chunk).  Otherwise the strides chunk / 2 .. 1 of merge step k = k_from.
+__global__ __launch_bounds__(PICK_WG) void k_pick_sort_local(uint2* __restrict__ cand, const unsigned* __restrict__ n_ptr, unsigned cap, unsigned k_from)
+{
+    __shared__ unsigned long long s[PICK_SORT_CHUNK];
+    const unsigned n = *n_ptr;
+    if (n > cap) return;
+    const unsigned Np = pick_np2(n), base = blockIdx.x * PICK_SORT_CHUNK;
+    if (k_from > Np || base >= Np) return;
+    const unsigned L = Np < PICK_SORT_CHUNK ? Np : PICK_SORT_CHUNK, tid = threadIdx.x;
+    for (unsigned t = tid; t < L; t += PICK_WG) s[t] = base + t < n || k_from ? pick_key(cand[base + t]) : 0ull;
+    __syncthreads();
+    for (unsigned k = k_from ? k_from : 2; k <= (k_from ? k_from : L); k <<= 1)
+        for (unsigned j = (k >> 1) < (L >> 1) ? (k >> 1) : (L >> 1); j > 0; j >>= 1) {
+            for (unsigned t = tid; t < (L >> 1); t += PICK_WG) {
+                const unsigned i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+                const bool desc = ((base + i) & k) == 0;
+                const unsigned long long a = s[i], b = s[l];
+                if ((a < b) == desc) { s[i] = b; s[l] = a; }
+            }
+            __syncthreads();
+        }
+    for (unsigned t = tid; t < L; t += PICK_WG) cand[base + t] = pick_unkey(s[t]);
+}
+// one compare-exchange step (k, j) with j >= PICK_SORT_CHUNK: a thread owns the pair (i, i | j)
+__global__ __launch_bounds__(256) void k_pick_sort_global(uint2* __restrict__ cand, const unsigned* __restrict__ n_ptr, unsigned cap, unsigned k, unsigned j)
+{
+    const unsigned n = *n_ptr;
+    if (n > cap) return;
+    const unsigned Np = pick_np2(n), t = blockIdx.x * 256 + threadIdx.x;
+    if (k > Np || t >= (Np >> 1)) return;
+    const unsigned i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+    const unsigned long long a = pick_key(cand[i]), b = pick_key(cand[l]);
+    if ((a < b) == ((i & k) == 0)) { cand[i] = pick_unkey(b); cand[l] = pick_unkey(a); }
+}
+void launch_pick_sort(hipStream_t st, uint2* cand, const unsigned* n_ptr, unsigned cap)
+{
+    const unsigned chunks = (cap + PICK_SORT_CHUNK - 1) / PICK_SORT_CHUNK;
+    hipLaunchKernelGGL(k_pick_sort_local, dim3(chunks), dim3(PICK_WG), 0, st, cand, n_ptr, cap, 0u);
+    for (unsigned k = 2 * PICK_SORT_CHUNK; k <= cap; k <<= 1) {
+        for (unsigned j = k >> 1; j >= PICK_SORT_CHUNK; j >>= 1)
+            hipLaunchKernelGGL(k_pick_sort_global, dim3((cap / 2 + 255) / 256), dim3(256), 0, st, cand, n_ptr, cap, k, j);
+        hipLaunchKernelGGL(k_pick_sort_local, dim3(chunks), dim3(PICK_WG), 0, st, cand, n_ptr, cap, k);
+    }
+}
+
+// Pick: ONE workgroup walks the sorted candidates in chunks of PICK_WG ranks.  Accepted corners of earlier chunks live in a grid of
+// cells of `cell` = ceil(min_distance) pixels (a.grid, zeroed by the caller; slot = linear index + 1, filled front to back): a corner
+// nearer than min_distance lies in one of the 3 x 3 cells around, and a cell holds at most `slots` corners (pairwise >= min_distance
+// apart inside cell x cell pixels: 1 for cell 1, 2 for cell 2, at most 4 otherwise -- one per quadrant).  Per chunk:
+//   1. a candidate in range of a grid corner is rejected; the others (survivors) are compacted in rank order into LDS;
+//   2. rounds over the survivors: undecided -> rejected if an earlier survivor in range is accepted, accepted if every earlier
+//      survivor in range is rejected (or there is none), otherwise it waits at that survivor.  Decisions are final, so reading a state
+//      while its owner writes it only delays; the first undecided survivor always decides, so a chunk needs at most PICK_WG rounds;
+//   3. the accepted ones take the next output places in rank order (cut at max_corners) and go into the grid.
+// The loop ends with the candidates or with max_corners accepted: exactly the sequential greedy rule with its early stop.
+__device__ __forceinline__ bool pick_in_range(int x, int y, int ox, int oy, double md2)
+{
+    const double dx = x - ox, dy = y - oy;
+    return dx * dx + dy * dy < md2;
+}
+__global__ __launch_bounds__(PICK_WG) void k_corner_pick(LkPickArgs a)
+{
+    __shared__ int s_x[PICK_WG], s_y[PICK_WG], s_state[PICK_WG];
+    __shared__ int s_wcount[PICK_WG / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, W = a.W, maxc = a.max_corners;
+    const unsigned n = *a.n_ptr;
+    if (n > a.cap) {                                          // overflow: the count, negated, and no corner
+        if (tid == 0) { *a.count = -(int)n; a.stats[0] = 0; a.stats[1] = 0; }
+        return;
+    }
+    if (!a.pick) {                                            // min_distance < 1: the first max_corners in key order
+        const unsigned m = n < (unsigned)maxc ? n : (unsigned)maxc;
+        for (unsigned i = tid; i < m; i += PICK_WG) {
+            const unsigned idx = a.cand[i].y, y = idx / (unsigned)W;
+            a.corners[2 * i] = (float)(idx - y * W); a.corners[2 * i + 1] = (float)y;
+        }
+        if (tid == 0) { *a.count = (int)m; a.stats[0] = 0; a.stats[1] = 0; }
+        return;
+    }
+    int acc = 0;
+    unsigned chunks = 0, rounds = 0;
+    for (unsigned base = 0; base < n && acc < maxc; base += PICK_WG, chunks++) {
+        const unsigned r = base + tid;
+        int x = 0, y = 0;
+        bool alive = false;
+        if (r < n) {
+            const unsigned idx = a.cand[r].y;
+            y = (int)(idx / (unsigned)W); x = (int)(idx - (unsigned)y * W);
+            alive = true;
+            const int cx = x / a.cell, cy = y / a.cell;
+            const int y1 = cy + 1 < a.gh ? cy + 1 : a.gh - 1, x1 = cx + 1 < a.gw ? cx + 1 : a.gw - 1;
+            for (int yy = cy > 0 ? cy - 1 : 0; alive && yy <= y1; yy++)
+                for (int xx = cx > 0 ? cx - 1 : 0; alive && xx <= x1; xx++) {
+                    const unsigned* cellp = a.grid + ((size_t)yy * a.gw + xx) * a.slots;
+                    for (int s = 0; s < a.slots; s++) {
+                        // the slot may have been written by another wave of this workgroup one chunk ago: read it at the L2
+                        const unsigned v = __hip_atomic_load(cellp + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (!v) break;
+                        const int oy = (int)((v - 1) / (unsigned)W), ox = (int)((v - 1) - (unsigned)oy * W);
+                        if (pick_in_range(x, y, ox, oy, a.md2)) { alive = false; break; }
+                    }
+                }
+        }
+        // survivors, compacted in rank order
+        unsigned long long bal = __ballot(alive);
+        if (lane == 0) s_wcount[wv] = __popcll(bal);
+        __syncthreads();
+        int off = 0, S = 0;
+        for (int w = 0; w < PICK_WG / 64; w++) { if (w < wv) off += s_wcount[w]; S += s_wcount[w]; }
+        if (alive) {
+            const int pos = off + __popcll(bal & ((1ull << lane) - 1));
+            s_x[pos] = x; s_y[pos] = y; s_state[pos] = 0;
+        }
+        __syncthreads();
+        // rounds: thread t owns survivor t.  state 0 undecided, 1 accepted, 2 rejected
+        const bool mine = tid < S;
+        const int mx = mine ? s_x[tid] : 0, my = mine ? s_y[tid] : 0;
+        int st = 0, ptr = 0;
+        for (;;) {
+            if (mine && st == 0) {
+                while (ptr < tid) {
+                    if (pick_in_range(mx, my, s_x[ptr], s_y[ptr], a.md2)) {
+                        const int o = __hip_atomic_load(&s_state[ptr], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        if (o == 1) st = 2;
+                        if (o != 2) break;
+                    }
+                    ptr++;
+                }
+                if (st == 0 && ptr == tid) st = 1;
+                if (st) __hip_atomic_store(&s_state[tid], st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            rounds++;
+            if (!__syncthreads_or(mine && st == 0)) break;
+        }
+        // output places in rank order
+        const bool isacc = mine && st == 1;
+        bal = __ballot(isacc);
+        if (lane == 0) s_wcount[wv] = __popcll(bal);
+        __syncthreads();
+        off = 0;
+        int T = 0;
+        for (int w = 0; w < PICK_WG / 64; w++) { if (w < wv) off += s_wcount[w]; T += s_wcount[w]; }
+        const int o = acc + off + __popcll(bal & ((1ull << lane) - 1));
+        if (isacc && o < maxc) {
+            a.corners[2 * o] = (float)mx; a.corners[2 * o + 1] = (float)my;
+            unsigned* cellp = a.grid + ((size_t)(my / a.cell) * a.gw + mx / a.cell) * a.slots;
+            const unsigned v = (unsigned)my * (unsigned)W + (unsigned)mx + 1u;
+            for (int s = 0; s < a.slots; s++)
+                if (atomicCAS(cellp + s, 0u, v) == 0u) break;
+        }
+        acc += T;
+        __threadfence();
+        __syncthreads();
+    }
+    if (tid == 0) { *a.count = acc < maxc ? acc : maxc; a.stats[0] = chunks; a.stats[1] = rounds; }
+}
+void launch_corner_pick(hipStream_t st, const LkPickArgs& a) { hipLaunchKernelGGL(k_corner_pick, dim3(1), dim3(PICK_WG), 0, st, a); }
 
 // ---- pyramid: pyrDown, 5x5 [1 4 6 4 1] x [1 4 6 4 1], REFLECT_101, (sum + 128) >> 8 -----------------------------------------------
 __global__ __launch_bounds__(256) void k_lk_pyrdown(const uint8_t* __restrict__ src, int sw, int sh, uint8_t* __restrict__ dst, int dw, int dh)
@@ -196,7 +371,9 @@ __global__ __launch_bounds__(256) void k_lk_track(LkTrackArgs a)
     extern __shared__ short lk_lds[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int p = blockIdx.x * 4 + wv;
-    if (p >= a.n) return;                                     // wave-uniform; the kernel has no barrier
+    int n = a.n;
+    if (a.n_dev) { const int m = *a.n_dev; n = m < n ? m : n; }      // the count lives on the device: waves beyond it (all, if negative) leave
+    if (p >= n) return;                                       // wave-uniform; the kernel has no barrier
     const int win_w = a.win_w, win_h = a.win_h, npix = win_w * win_h;
     short* Iw = lk_lds + (size_t)wv * 3 * npix;
     short* Dx = Iw + npix;

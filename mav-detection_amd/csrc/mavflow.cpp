@@ -327,13 +327,14 @@ struct Stager {
         }
     }
 };
-enum KernelId { K_BLUR_RESIZE, K_POLYEXP, K_UPDATE, K_ITER, K_ITER_COARSE, K_FOE, K_PHI, K_MISC, K_LK_CORNERS, K_LK_PYRAMID, K_LK_TRACK, K_COUNT };
+enum KernelId { K_BLUR_RESIZE, K_POLYEXP, K_UPDATE, K_ITER, K_ITER_COARSE, K_FOE, K_PHI, K_MISC, K_LK_CORNERS, K_LK_PYRAMID, K_LK_TRACK, K_LK_PICK, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"blur_resize", "polyexp", "update_matrices", "blur_iter", "blur_iter_coarse",
-                                                  "foe_ransac", "phi_mask_box", "misc", "lk_corners", "lk_pyramid", "lk_track"};
+                                                  "foe_ransac", "phi_mask_box", "misc", "lk_corners", "lk_pyramid", "lk_track", "lk_pick"};
 struct ProfRec { int kid; hipEvent_t a, b; int stream; };
 struct ProfInterval { int kid; float t0, t1; int stream; };      // ms since the profile was switched on
 
 // Sparse optical flow (mav_good_features / mav_lk_track): everything it owns, allocated by the first such call (ensure_lk).
+enum { LK_CNT_PICKED = 2 + MAV_LK_HIST, LK_CNT_STATS, LK_CNT_N = LK_CNT_STATS + 2 };   // corner count of the host forms; chunks, rounds
 struct LkState {
     LkLevels dims{};                 // every level the frame size allows (MAV_LK_MAX_LEVEL + 1 at most), whatever the window
     size_t pyr_elems = 0;            // elements of one pyramid block
@@ -342,12 +343,14 @@ struct LkState {
     int cur = -1;                    // slot of the resident frame, -1: none
     short2* deriv = nullptr;         // Scharr pairs of ONE slot's levels
     int deriv_slot = -1, deriv_levels = 0;
-    float* eig = nullptr;            // (H, W) min-eigenvalue map
+    float* eig = nullptr;            // (H, W) min-eigenvalue map; dead once the candidates are out: the pick's grid of accepted corners
+    size_t eig_words = 0;            // W * H, or the largest grid where a one-pixel-wide frame makes that larger
     uint2* cand = nullptr;           // MAV_GFTT_MAX_CANDIDATES x (value bits, linear index)
-    unsigned* counters = nullptr;    // [0] max key, [1] candidate count, [2 ..] iteration histogram (MAV_LK_HIST)
+    unsigned* counters = nullptr;    // [0] max key, [1] candidate count, [2 ..] iteration histogram (MAV_LK_HIST), then LK_CNT_*
     float *pts = nullptr, *out = nullptr;   // MAV_LK_MAX_POINTS x 2 each
     uint8_t* status = nullptr;       // MAV_LK_MAX_POINTS
     bool hist_valid = false;
+    std::vector<float> fetch;        // host staging of the host forms' corners: kept, so a call allocates nothing
 };
 
 struct mav_ctx {
@@ -3308,8 +3311,11 @@ static int ensure_lk(mav_ctx* c)
     lk_level_dims(c->W, c->H, &k.dims);
     k.pyr_elems = (size_t)k.dims.off[k.dims.n - 1] + (((size_t)k.dims.w[k.dims.n - 1] * k.dims.h[k.dims.n - 1] + 63) & ~(size_t)63);
     const size_t pts = (size_t)MAV_LK_MAX_POINTS * 2 * sizeof(float);
-    CHK(c->mem.alloc_set({{&k.pyr[0], k.pyr_elems}, {&k.pyr[1], k.pyr_elems}, {&k.deriv, k.pyr_elems * sizeof(short2)}, {&k.eig, c->n0 * sizeof(float)},
-                          {&k.cand, (size_t)MAV_GFTT_MAX_CANDIDATES * sizeof(uint2)}, {&k.counters, (2 + MAV_LK_HIST) * sizeof(unsigned)},
+    // the pick's grid at its largest: cells of 1 (1 slot), 2 (2 slots) or 3 pixels (4 slots); W * H unless the frame is one pixel wide
+    const size_t W = c->W, H = c->H;
+    k.eig_words = std::max({c->n0, 2 * ((W + 1) / 2) * ((H + 1) / 2), 4 * ((W + 2) / 3) * ((H + 2) / 3)});
+    CHK(c->mem.alloc_set({{&k.pyr[0], k.pyr_elems}, {&k.pyr[1], k.pyr_elems}, {&k.deriv, k.pyr_elems * sizeof(short2)}, {&k.eig, k.eig_words * sizeof(float)},
+                          {&k.cand, (size_t)MAV_GFTT_MAX_CANDIDATES * sizeof(uint2)}, {&k.counters, LK_CNT_N * sizeof(unsigned)},
                           {&k.pts, pts}, {&k.out, pts}, {&k.status, (size_t)MAV_LK_MAX_POINTS}}, MEM_OTHER, "sparse optical flow workspace"));
     return MAV_OK;
 }
@@ -3348,8 +3354,32 @@ static void lk_derivatives(mav_ctx* c, int slot, int levels)
     k.deriv_slot = slot; k.deriv_levels = levels;
 }
 
-// Corner detection on slot `slot`: device part, then the host's sort and greedy pick.  Synchronises.
-static int good_features_run(mav_ctx* c, int slot, const mav_gftt_params& p, float* corners, int* count, const char* fn)
+// The sort and the pick of cand[0 .. counters[1]) into corners / count (device memory), enqueue only.
+static int corner_pick_enqueue(mav_ctx* c, const mav_gftt_params& p, float* corners, int* count)
+{
+    LkState& k = c->lk;
+    LkPickArgs a;
+    a.cand = k.cand; a.n_ptr = k.counters + 1; a.cap = MAV_GFTT_MAX_CANDIDATES;
+    a.W = c->W; a.max_corners = p.max_corners;
+    a.pick = p.min_distance >= 1;
+    // cells of ceil(min_distance) pixels, as many as the frame needs; one cell when min_distance exceeds the frame
+    const double cd = std::min(ceil(p.min_distance), (double)std::max(c->W, c->H));
+    a.cell = a.pick ? (int)cd : std::max(c->W, c->H);
+    a.gw = (c->W + a.cell - 1) / a.cell; a.gh = (c->H + a.cell - 1) / a.cell;
+    a.slots = a.cell == 1 ? 1 : a.cell == 2 ? 2 : 4;
+    a.md2 = p.min_distance * p.min_distance;
+    a.grid = reinterpret_cast<unsigned*>(k.eig);
+    a.corners = corners; a.count = count; a.stats = k.counters + LK_CNT_STATS;
+    const size_t words = (size_t)a.gw * a.gh * a.slots;
+    if (words > k.eig_words) return fail(MAV_ERR_STATE, "corner pick: a grid of %zu words in a buffer of %zu", words, k.eig_words);
+    ProfScope ps(c, K_LK_PICK);
+    if (a.pick) HIPCHK(hipMemsetAsync(a.grid, 0, words * sizeof(unsigned), c->stream));
+    launch_pick_sort(c->stream, k.cand, a.n_ptr, a.cap);
+    launch_corner_pick(c->stream, a);
+    return check_launch("corner pick");
+}
+// Corner detection on slot `slot`, enqueue only: eigenvalue map, candidates, sort, pick.  mask / corners / count: device memory.
+static int good_features_enqueue(mav_ctx* c, int slot, const uint8_t* mask, const mav_gftt_params& p, float* corners, int* count)
 {
     LkState& k = c->lk;
     const int W = c->W, H = c->H;
@@ -3357,57 +3387,32 @@ static int good_features_run(mav_ctx* c, int slot, const mav_gftt_params& p, flo
     {
         ProfScope ps(c, K_LK_CORNERS);
         HIPCHK(hipMemsetAsync(k.counters, 0, 2 * sizeof(unsigned), c->stream));
-        launch_min_eig(c->stream, k.pyr[slot], W, H, p.block_size, s2, k.eig, k.counters);
-        launch_corner_candidates(c->stream, k.eig, W, H, k.counters, p.quality_level, k.cand, k.counters + 1, MAV_GFTT_MAX_CANDIDATES);
+        launch_min_eig(c->stream, k.pyr[slot], mask, W, H, p.block_size, s2, k.eig, k.counters);
+        launch_corner_candidates(c->stream, k.eig, mask, W, H, k.counters, p.quality_level, k.cand, k.counters + 1, MAV_GFTT_MAX_CANDIDATES);
     }
     CHK(check_launch("corner detection"));
-    unsigned cnt[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(cnt, k.counters, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    const unsigned nc = cnt[1];
-    if (nc > MAV_GFTT_MAX_CANDIDATES)
-        return fail(MAV_ERR_ARG, "%s: the frame has %u corner candidates, the buffer holds %d (raise quality_level)", fn, nc, MAV_GFTT_MAX_CANDIDATES);
-    std::vector<uint2> cand(nc);
-    if (nc) {
-        HIPCHK(hipMemcpyAsync(cand.data(), k.cand, (size_t)nc * sizeof(uint2), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    // value descending (positive floats order as their bits), ties by linear index descending
-    std::vector<unsigned long long> keys(nc);
-    for (unsigned i = 0; i < nc; i++) keys[i] = ((unsigned long long)cand[i].x << 32) | cand[i].y;
-    std::sort(keys.begin(), keys.end(), std::greater<unsigned long long>());
+    return corner_pick_enqueue(c, p, corners, count);
+}
+// The host forms' end: the count and count x 8 bytes come back; one synchronisation.  A negative count is an overflow.
+static int corner_pick_fetch(mav_ctx* c, const mav_gftt_params& p, float* corners, int* count, const char* fn)
+{
+    LkState& k = c->lk;
+    // the count and the corners in one stream-ordered pair of copies: the corners' size is max_corners, known to the host
+    std::vector<float>& buf = k.fetch;
+    if (buf.size() < (size_t)p.max_corners * 2) buf.resize((size_t)p.max_corners * 2);
     int n = 0;
-    if (p.min_distance >= 1) {
-        // greedy pick over a grid of cells of ceil(min_distance): an accepted corner nearer than min_distance lies in a neighbouring cell
-        const int cell = (int)ceil(p.min_distance), gw = (W + cell - 1) / cell, gh = (H + cell - 1) / cell;
-        const double md2 = p.min_distance * p.min_distance;
-        std::vector<std::vector<unsigned>> grid((size_t)gw * gh);
-        for (unsigned i = 0; i < nc && n < p.max_corners; i++) {
-            const unsigned idx = (unsigned)(keys[i] & 0xffffffffu);
-            const int y = (int)(idx / (unsigned)W), x = (int)(idx - (unsigned)y * W), cx = x / cell, cy = y / cell;
-            bool good = true;
-            for (int yy = std::max(cy - 1, 0); good && yy <= std::min(cy + 1, gh - 1); yy++)
-                for (int xx = std::max(cx - 1, 0); good && xx <= std::min(cx + 1, gw - 1); xx++)
-                    for (unsigned o : grid[(size_t)yy * gw + xx]) {
-                        const int oy = (int)(o / (unsigned)W), ox = (int)(o - (unsigned)oy * W);
-                        const double dx = x - ox, dy = y - oy;
-                        if (dx * dx + dy * dy < md2) { good = false; break; }
-                    }
-            if (!good) continue;
-            grid[(size_t)cy * gw + cx].push_back(idx);
-            corners[2 * n] = (float)x; corners[2 * n + 1] = (float)y;
-            n++;
-        }
-    } else {
-        for (unsigned i = 0; i < nc && n < p.max_corners; i++, n++) {
-            const unsigned idx = (unsigned)(keys[i] & 0xffffffffu);
-            corners[2 * n] = (float)(idx % (unsigned)W); corners[2 * n + 1] = (float)(idx / (unsigned)W);
-        }
-    }
+    HIPCHK(hipMemcpyAsync(&n, k.counters + LK_CNT_PICKED, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(buf.data(), k.out, (size_t)p.max_corners * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (n < 0)
+        return fail(MAV_ERR_ARG, "%s: the frame has %u corner candidates, the buffer holds %d (raise quality_level)", fn, (unsigned)-(long long)n,
+                    MAV_GFTT_MAX_CANDIDATES);
+    memcpy(corners, buf.data(), (size_t)n * 2 * sizeof(float));
     *count = n;
     return MAV_OK;
 }
-static int good_features_entry(mav_ctx* c, const uint8_t* gray, bool host, const mav_gftt_params* pp, float* corners, int* count, const char* fn)
+static int good_features_entry(mav_ctx* c, const uint8_t* gray, const uint8_t* mask, bool host, bool host_out, const mav_gftt_params* pp,
+                               float* corners, int* count, const char* fn)
 {
     mav_gftt_params p;
     if (pp) p = *pp; else mav_gftt_defaults(&p);
@@ -3422,20 +3427,47 @@ static int good_features_entry(mav_ctx* c, const uint8_t* gray, bool host, const
         CHK(lk_load(c, slot, gray, host));
         k.cur = slot;
     }
-    return good_features_run(c, k.cur, p, corners, count, fn);
+    if (mask && host) {
+        // a host mask is staged in the other frame slot: no call reads that slot's frame again (a track call loads `next` into it)
+        const int other = 1 - k.cur;
+        HIPCHK(hipMemcpyAsync(k.pyr[other], mask, c->n0, hipMemcpyHostToDevice, c->stream));
+        k.built[other] = 0;
+        if (k.deriv_slot == other) { k.deriv_slot = -1; k.deriv_levels = 0; }
+        mask = k.pyr[other];
+    }
+    if (!host_out) return good_features_enqueue(c, k.cur, mask, p, corners, count);
+    CHK(good_features_enqueue(c, k.cur, mask, p, k.out, reinterpret_cast<int*>(k.counters + LK_CNT_PICKED)));
+    return corner_pick_fetch(c, p, corners, count, fn);
 }
 extern "C" int mav_good_features(mav_ctx* c, const uint8_t* gray, const mav_gftt_params* p, float* corners, int* count)
 {
-    return good_features_entry(c, gray, true, p, corners, count, "mav_good_features");
+    return good_features_entry(c, gray, nullptr, true, true, p, corners, count, "mav_good_features");
 }
 extern "C" int mav_good_features_dev(mav_ctx* c, const uint8_t* gray, const mav_gftt_params* p, float* corners, int* count)
 {
-    return good_features_entry(c, gray, false, p, corners, count, "mav_good_features_dev");
+    return good_features_entry(c, gray, nullptr, false, true, p, corners, count, "mav_good_features_dev");
+}
+extern "C" int mav_good_features_ex(mav_ctx* c, const uint8_t* gray, const uint8_t* mask, const mav_gftt_params* p, float* corners, int* count)
+{
+    return good_features_entry(c, gray, mask, true, true, p, corners, count, "mav_good_features_ex");
+}
+extern "C" int mav_good_features_ex_dev(mav_ctx* c, const uint8_t* gray, const uint8_t* mask, const mav_gftt_params* p, float* corners,
+                                        int32_t* count)
+{
+    return good_features_entry(c, gray, mask, false, false, p, corners, count, "mav_good_features_ex_dev");
+}
+extern "C" int mav_gftt_last_pick(mav_ctx* c, uint32_t* stats)
+{
+    if (!c || !stats) return fail(MAV_ERR_ARG, "mav_gftt_last_pick: NULL argument");
+    if (!c->lk.counters) return fail(MAV_ERR_STATE, "mav_gftt_last_pick: no corner call precedes");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(stats, c->lk.counters + LK_CNT_STATS, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    return mav_sync(c);
 }
 
 // prev (or the resident frame) and next into the two slots, pyramids, derivatives, one tracker launch.  pts / out / status: device.
 static int lk_track_enqueue(mav_ctx* c, const uint8_t* prev, const uint8_t* next, bool host, const float* pts, int n, const mav_lk_params& p,
-                            float* out, uint8_t* status)
+                            float* out, uint8_t* status, const int* n_dev = nullptr)
 {
     LkState& k = c->lk;
     int sp;
@@ -3453,7 +3485,7 @@ static int lk_track_enqueue(mav_ctx* c, const uint8_t* prev, const uint8_t* next
     a.I = k.pyr[sp]; a.J = k.pyr[sn]; a.D = k.deriv; a.lv = k.dims; a.lv.n = levels;
     a.pts = pts; a.n = n; a.win_w = p.win_w; a.win_h = p.win_h; a.max_count = p.max_count;
     a.eps2 = p.epsilon * p.epsilon; a.min_eig = (float)p.min_eig_threshold;
-    a.out = out; a.status = status; a.iter_hist = k.counters + 2;
+    a.out = out; a.status = status; a.iter_hist = k.counters + 2; a.n_dev = n_dev;
     {
         ProfScope ps(c, K_LK_TRACK);
         launch_lk_track(c->stream, a);
@@ -3492,6 +3524,14 @@ extern "C" int mav_lk_track_dev(mav_ctx* c, const uint8_t* prev, const uint8_t* 
     mav_lk_params p;
     CHK(lk_track_check(c, prev, next, pts, n, pp, next_pts, status, &p, "mav_lk_track_dev"));
     return lk_track_enqueue(c, prev, next, false, pts, n, p, next_pts, status);
+}
+extern "C" int mav_lk_track_ex_dev(mav_ctx* c, const uint8_t* prev, const uint8_t* next, const float* pts, int n_max, const int32_t* n_dev,
+                                   const mav_lk_params* pp, float* next_pts, uint8_t* status)
+{
+    mav_lk_params p;
+    CHK(lk_track_check(c, prev, next, pts, n_max, pp, next_pts, status, &p, "mav_lk_track_ex_dev"));
+    if (!n_dev) return fail(MAV_ERR_ARG, "mav_lk_track_ex_dev: NULL argument");
+    return lk_track_enqueue(c, prev, next, false, pts, n_max, p, next_pts, status, n_dev);
 }
 extern "C" int mav_lk_last_iterations(mav_ctx* c, uint32_t* hist)
 {
@@ -3551,10 +3591,31 @@ extern "C" int mav_stage_min_eigen(mav_ctx* c, const uint8_t* img, int block_siz
     LkState& k = c->lk;
     const float s = (float)(1.0 / (4.0 * block_size * 255.0)), s2 = s * s;
     HIPCHK(hipMemsetAsync(k.counters, 0, 2 * sizeof(unsigned), c->stream));
-    launch_min_eig(c->stream, k.pyr[0], c->W, c->H, block_size, s2, k.eig, k.counters);
+    launch_min_eig(c->stream, k.pyr[0], nullptr, c->W, c->H, block_size, s2, k.eig, k.counters);
     CHK(check_launch("min_eig"));
     CHK(download(c, out, k.eig, c->n0 * sizeof(float)));
     const int rc = mav_sync(c);
     k.built[0] = 0;
     return rc;
+}
+extern "C" int mav_stage_corner_pick(mav_ctx* c, const uint64_t* keys, int n, const mav_gftt_params* pp, float* corners, int* count)
+{
+    mav_gftt_params p;
+    if (pp) p = *pp; else mav_gftt_defaults(&p);
+    CHK(check_gftt_params(p, "mav_stage_corner_pick"));
+    if (!c || (n > 0 && !keys) || !corners || !count) return fail(MAV_ERR_ARG, "mav_stage_corner_pick: NULL argument");
+    if (n < 0 || n > MAV_GFTT_MAX_CANDIDATES) return fail(MAV_ERR_ARG, "mav_stage_corner_pick: %d keys outside [0, %d]", n, MAV_GFTT_MAX_CANDIDATES);
+    for (int i = 0; i < n; i++)
+        if ((keys[i] & 0xffffffffu) >= c->n0) return fail(MAV_ERR_ARG, "mav_stage_corner_pick: key %d has index %u outside the frame", i, (unsigned)keys[i]);
+    HIPCHK(hipSetDevice(c->device));
+    CHK(ensure_lk(c));
+    LkState& k = c->lk;
+    // a key is (value bits << 32) | index; a candidate in memory is the pair (value bits, index)
+    std::vector<uint2> cand((size_t)n);
+    for (int i = 0; i < n; i++) cand[i] = make_uint2((unsigned)(keys[i] >> 32), (unsigned)keys[i]);
+    const unsigned cnt[2] = {0u, (unsigned)n};
+    HIPCHK(hipMemcpyAsync(k.counters, cnt, sizeof(cnt), hipMemcpyHostToDevice, c->stream));
+    if (n) HIPCHK(hipMemcpyAsync(k.cand, cand.data(), (size_t)n * sizeof(uint2), hipMemcpyHostToDevice, c->stream));
+    CHK(corner_pick_enqueue(c, p, k.out, reinterpret_cast<int*>(k.counters + LK_CNT_PICKED)));
+    return corner_pick_fetch(c, p, corners, count, "mav_stage_corner_pick");
 }

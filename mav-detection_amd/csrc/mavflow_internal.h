@@ -203,12 +203,31 @@ struct LkTrackArgs {
     float* out;                   // (n, 2)
     uint8_t* status;              // (n)
     unsigned* iter_hist;          // [MAV_LK_HIST] or null: iterations per (point, level) that reached the loop
+    const int* n_dev;             // null, or the device's own point count: min(*n_dev, n) points run, none if it is negative
+};
+struct LkPickArgs {
+    const uint2* cand;            // sorted candidates (value bits, linear index)
+    const unsigned* n_ptr;        // their count; > cap: overflow
+    unsigned cap;
+    int W, max_corners;
+    int pick;                     // 0: min_distance < 1, no distance test
+    int cell, gw, gh, slots;      // the grid of accepted corners: gw x gh cells of cell x cell pixels, `slots` words each
+    double md2;                   // min_distance^2
+    unsigned* grid;               // gw * gh * slots words, zeroed by the caller
+    float* corners;               // (max_corners, 2); entries from *count on are left alone
+    int* count;                   // accepted corners, or -(candidates) on overflow
+    unsigned* stats;              // [0] chunks, [1] rounds of this pick
 };
 // min-eigenvalue map of a W x H u8 image (block_size odd, <= 15) and its maximum as an ordered key (*maxkey zeroed by the caller)
-void launch_min_eig(hipStream_t st, const uint8_t* img, int W, int H, int block_size, float s2, float* eig, unsigned* maxkey);
+// mask (H, W) u8 or null: only pixels with a non-zero mask byte enter the maximum (and become candidates below)
+void launch_min_eig(hipStream_t st, const uint8_t* img, const uint8_t* mask, int W, int H, int block_size, float s2, float* eig, unsigned* maxkey);
 // candidates (value bits, linear index) appended at cand[*count++] while *count < cap (*count zeroed by the caller, counts past cap)
-void launch_corner_candidates(hipStream_t st, const float* eig, int W, int H, const unsigned* maxkey, double quality, uint2* cand,
-                              unsigned* count, unsigned cap);
+void launch_corner_candidates(hipStream_t st, const float* eig, const uint8_t* mask, int W, int H, const unsigned* maxkey, double quality,
+                              uint2* cand, unsigned* count, unsigned cap);
+// in-place descending sort of cand[0 .. *n_ptr) by (value bits << 32) | index (cap: a power of two, the buffer's size), then the pick;
+// neither needs the host to know *n_ptr
+void launch_pick_sort(hipStream_t st, uint2* cand, const unsigned* n_ptr, unsigned cap);
+void launch_corner_pick(hipStream_t st, const LkPickArgs& a);
 void launch_lk_pyrdown(hipStream_t st, const uint8_t* src, int sw, int sh, uint8_t* dst, int dw, int dh);
 void launch_lk_scharr(hipStream_t st, const uint8_t* pyr, const LkLevels& lv, int levels, short2* out);
 size_t lk_track_lds_bytes(int win_w, int win_h);

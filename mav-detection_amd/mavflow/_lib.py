@@ -75,6 +75,7 @@ EXPORTS = [
     "mav_png_bound", "mav_png_encode", "mav_png_encode_dev", "mav_last_render_png", "mav_last_overlay_png",
     "mav_gftt_defaults", "mav_lk_defaults", "mav_good_features", "mav_good_features_dev", "mav_lk_track", "mav_lk_track_dev",
     "mav_lk_last_iterations", "mav_lk_level_dims", "mav_stage_lk_pyramid", "mav_stage_lk_scharr", "mav_stage_min_eigen",
+    "mav_good_features_ex", "mav_good_features_ex_dev", "mav_lk_track_ex_dev", "mav_gftt_last_pick", "mav_stage_corner_pick",
 ]
 
 # Frame depths of the _ex entry points (cv2's depth codes) by numpy dtype.  uint8 frames keep going through the u8 symbols.
@@ -252,6 +253,13 @@ def load(path: str | None = None) -> C.CDLL:
     lib.mav_stage_lk_pyramid.argtypes = [vp, vp, C.c_int, vp]
     lib.mav_stage_lk_scharr.argtypes = [vp, vp, C.c_int, vp]
     lib.mav_stage_min_eigen.argtypes = [vp, vp, C.c_int, vp]
+    # ctx, gray, mask, params, corners, count
+    lib.mav_good_features_ex.argtypes = [vp, vp, vp, C.POINTER(GfttParams), vp, C.POINTER(C.c_int)]
+    lib.mav_good_features_ex_dev.argtypes = [vp, vp, vp, C.POINTER(GfttParams), vp, vp]
+    # ctx, prev, next, pts, n_max, n_dev, params, next_pts, status
+    lib.mav_lk_track_ex_dev.argtypes = [vp, vp, vp, vp, C.c_int, vp, C.POINTER(LkParams), vp, vp]
+    lib.mav_gftt_last_pick.argtypes = [vp, vp]
+    lib.mav_stage_corner_pick.argtypes = [vp, vp, C.c_int, C.POINTER(GfttParams), vp, C.POINTER(C.c_int)]
     _lib = lib
     return lib
 
@@ -1153,14 +1161,51 @@ class Context:
     def _gray1(self, a, name):
         return None if a is None else _arr(np.asarray(a), np.uint8, (self.H, self.W), name)
 
-    def good_features(self, gray, **params) -> np.ndarray:
-        """cv2.goodFeaturesToTrack(gray, mask=None, **params) on one (H, W) uint8 frame -> (n, 2) float32 corners (x, y), strongest first.
-        gray None: the context's resident frame (the `nxt` of the last lk_track, or the last frame given here)."""
+    def _mask1(self, mask):
+        """cv2's mask: an (H, W) uint8 array (non-zero = the pixel takes part) or None; ValueError for any other shape or dtype."""
+        if mask is None:
+            return None
+        mask = np.asarray(mask)
+        if mask.dtype != np.uint8 or mask.shape != (self.H, self.W):
+            raise ValueError(f"mask: expected a uint8 array of shape {(self.H, self.W)}, got {mask.dtype} {mask.shape}")
+        return np.ascontiguousarray(mask)
+
+    def good_features(self, gray, mask=None, **params) -> np.ndarray:
+        """cv2.goodFeaturesToTrack(gray, mask=mask, **params) on one (H, W) uint8 frame -> (n, 2) float32 corners (x, y), strongest
+        first.  gray None: the context's resident frame (the `nxt` of the last lk_track, or the last frame given here)."""
         p = gftt_defaults(**params)
-        gray = self._gray1(gray, "gray")
+        gray, mask = self._gray1(gray, "gray"), self._mask1(mask)
         out = np.empty((max(int(p.max_corners), 1), 2), np.float32)
         n = C.c_int()
-        check(self.lib.mav_good_features(self.h, _ptr(gray), C.byref(p), _ptr(out), C.byref(n)))
+        if mask is None:
+            check(self.lib.mav_good_features(self.h, _ptr(gray), C.byref(p), _ptr(out), C.byref(n)))
+        else:
+            check(self.lib.mav_good_features_ex(self.h, _ptr(gray), _ptr(mask), C.byref(p), _ptr(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def good_features_enqueue(self, gray_ptr, corners_ptr, count_ptr, mask_ptr=None, **params):
+        """mav_good_features_ex_dev: device pointers in and out, enqueue only.  gray_ptr None: the resident frame.  corners_ptr:
+        max_corners x 2 float32, count_ptr: one int32 (the corner count, or -(candidates) when they overflow the buffer)."""
+        check(self.lib.mav_good_features_ex_dev(self.h, gray_ptr, mask_ptr, C.byref(gftt_defaults(**params)), corners_ptr, count_ptr))
+
+    def lk_track_enqueue(self, prev_ptr, next_ptr, pts_ptr, n_max: int, n_ptr, next_pts_ptr, status_ptr, **params):
+        """mav_lk_track_ex_dev: mav_lk_track_dev for up to n_max points whose count is the int32 at the device pointer n_ptr."""
+        check(self.lib.mav_lk_track_ex_dev(self.h, prev_ptr, next_ptr, pts_ptr, int(n_max), n_ptr, C.byref(lk_defaults(**params)), next_pts_ptr,
+                                           status_ptr))
+
+    def gftt_last_pick(self):
+        """(chunks, rounds) of the most recent corner pick on the device."""
+        st = np.zeros(2, np.uint32)
+        check(self.lib.mav_gftt_last_pick(self.h, _ptr(st)))
+        return int(st[0]), int(st[1])
+
+    def stage_corner_pick(self, keys, **params) -> np.ndarray:
+        """The device sort and pick on host candidate keys (value bits << 32 | linear index, uint64, any order) -> (n, 2) float32."""
+        p = gftt_defaults(**params)
+        keys = _arr(np.asarray(keys, np.uint64).reshape(-1), np.uint64)
+        out = np.empty((max(int(p.max_corners), 1), 2), np.float32)
+        n = C.c_int()
+        check(self.lib.mav_stage_corner_pick(self.h, _ptr(keys) if len(keys) else None, len(keys), C.byref(p), _ptr(out), C.byref(n)))
         return out[:n.value].copy()
 
     def lk_track(self, prev, nxt, pts, **params):
@@ -1180,7 +1225,7 @@ class Context:
         check(self.lib.mav_lk_track_dev(self.h, prev_ptr, next_ptr, pts_ptr, int(n), C.byref(lk_defaults(**params)), next_pts_ptr, status_ptr))
 
     def good_features_dev(self, gray_ptr, **params) -> np.ndarray:
-        """mav_good_features_dev: a device frame (None: the resident one) -> host corners; synchronises for the host-side pick."""
+        """mav_good_features_dev: a device frame (None: the resident one) -> host corners; synchronises once, to bring them back."""
         p = gftt_defaults(**params)
         out = np.empty((max(int(p.max_corners), 1), 2), np.float32)
         n = C.c_int()

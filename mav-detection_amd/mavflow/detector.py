@@ -59,7 +59,7 @@ class LucasKanade:
             return np.zeros(0), np.zeros(0), np.zeros(0)
 
         if len(self.features) < self.minimum_num_corners:
-            new_features = ctx.good_features(None if held else self.old_gray, **self.feature_params)
+            new_features = ctx.good_features(None if held else self.old_gray, mask=None, **self.feature_params)
             held = True
             for feature in new_features:
                 self.features.append(feature)

@@ -3,12 +3,16 @@
     python tools/lk_probe.py [--frames 50] [--warmup 8] [--sizes 1280x720,1920x1080]
 
 Per size: a synthetic zoom sequence (synth.make_sequence) is uploaded once; every frame then does what LucasKanade.get_features does on
-the device -- corner detection on the resident frame (mav_good_features_dev(NULL): eigenvalue map, threshold, non-maximum test and
-compaction on the device, sort and greedy pick on the host), then one mav_lk_track_dev from the resident frame to the next one (the
-new frame's pyramid, the previous frame's Scharr pairs, the tracker).  Reported per frame, median over the timed frames:
+the device -- corner detection on the resident frame (mav_good_features_dev(NULL): eigenvalue map, threshold, non-maximum test,
+compaction, sort and greedy pick on the device, the corners brought back), then one mav_lk_track_dev from the resident frame to the
+next one (the new frame's pyramid, the previous frame's Scharr pairs, the tracker).  Reported per frame, median over the timed frames:
   corners_dev_ms   HIP-event time of the class "lk_corners"            corners_host_ms  wall time of the call minus that
+  pick_ms          class "lk_pick" (sort + pick; inside corners_host_ms: corners_dev_ms + corners_host_ms is the call's wall time)
   pyramid_ms       class "lk_pyramid" (pyrDown chain + Scharr)          track_ms         class "lk_track"
+  pick_chunks, pick_rounds  what the pick did (mav_gftt_last_pick)
   get_features_ms  wall time of detector.LucasKanade.get_features on host BGR frames (gray conversion, uploads and downloads included)
+  chain_ms         wall time per frame of the enqueue-only chain, in a pass of its own without profiling: good_features_enqueue(None)
+                   then lk_track_enqueue reading the count on the device, one sync() per frame
 and the histogram of tracker iterations per (point, level) over all timed frames.  Prints one JSON line."""
 from __future__ import annotations
 
@@ -32,18 +36,20 @@ from mavflow.detector import LucasKanade  # noqa: E402
 def probe(W: int, H: int, frames: int, warmup: int) -> dict:
     n = frames + warmup + 1
     seq = synth.make_sequence(W, H, n, seed=0)
-    rows = {k: [] for k in ("corners_dev_ms", "corners_host_ms", "pyramid_ms", "track_ms", "candidates_points")}
+    rows = {k: [] for k in ("corners_dev_ms", "corners_host_ms", "pick_ms", "pyramid_ms", "track_ms", "pick_chunks", "pick_rounds",
+                           "candidates_points")}
     hist = np.zeros(_lib.LK_HIST_BINS, np.int64)
     with _lib.Context(W, H, 1) as c:
         dev = [c.alloc(W * H).upload(f) for f in seq]
         d_pts, d_out, d_status = c.alloc(_lib.LK_MAX_POINTS * 8), c.alloc(_lib.LK_MAX_POINTS * 8), c.alloc(_lib.LK_MAX_POINTS)
         pts = c.good_features_dev(dev[0].ptr)
         c.profile_enable(1)
-        last = {k: 0.0 for k in ("lk_corners", "lk_pyramid", "lk_track")}
+        last = {k: 0.0 for k in ("lk_corners", "lk_pick", "lk_pyramid", "lk_track")}
         for i in range(1, n):
             t0 = time.perf_counter()
             corners = c.good_features_dev(None)
             wall = (time.perf_counter() - t0) * 1e3
+            chunks, rounds = c.gftt_last_pick()
             d_pts.upload(corners)
             c.lk_track_dev(None, dev[i].ptr, d_pts.ptr, len(corners), d_out.ptr, d_status.ptr)
             c.sync()
@@ -53,11 +59,26 @@ def probe(W: int, H: int, frames: int, warmup: int) -> dict:
             if i > warmup:
                 rows["corners_dev_ms"].append(step["lk_corners"])
                 rows["corners_host_ms"].append(wall - step["lk_corners"])
+                rows["pick_ms"].append(step["lk_pick"])
+                rows["pick_chunks"].append(chunks)
+                rows["pick_rounds"].append(rounds)
                 rows["pyramid_ms"].append(step["lk_pyramid"])
                 rows["track_ms"].append(step["lk_track"])
                 rows["candidates_points"].append(len(corners))
                 hist += c.lk_last_iterations()
         c.profile_enable(0)
+        # the enqueue-only chain: the corner count never leaves the device
+        mc = _lib.gftt_defaults().max_corners
+        d_count = c.alloc(4)
+        c.good_features_dev(dev[0].ptr)
+        chain = []
+        for i in range(1, n):
+            t0 = time.perf_counter()
+            c.good_features_enqueue(None, d_pts.ptr, d_count.ptr)
+            c.lk_track_enqueue(None, dev[i].ptr, d_pts.ptr, mc, d_count.ptr, d_out.ptr, d_status.ptr)
+            c.sync()
+            if i > warmup:
+                chain.append((time.perf_counter() - t0) * 1e3)
     # the Python class on host frames
     bgr = [np.repeat(f[..., None], 3, axis=2) for f in seq]
     lk = LucasKanade(bgr[0])
@@ -70,6 +91,7 @@ def probe(W: int, H: int, frames: int, warmup: int) -> dict:
     out = dict(W=W, H=H, frames=frames, points_median=int(np.median(rows.pop("candidates_points"))))
     out.update({k: round(float(np.median(v)), 4) for k, v in rows.items()})
     out["get_features_ms"] = round(float(np.median(wall)), 4)
+    out["chain_ms"] = round(float(np.median(chain)), 4)
     nz = np.nonzero(hist)[0]
     out["iterations_mean"] = round(float((hist * np.arange(len(hist))).sum() / max(hist.sum(), 1)), 3)
     out["iterations_hist"] = {int(i): int(hist[i]) for i in nz}
