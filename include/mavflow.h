@@ -45,10 +45,12 @@ extern "C" {
 typedef struct mav_ctx mav_ctx;
 
 /* src/farneback.py:76-80 -- the literal argument list of cv2.calcOpticalFlowFarneback.
- * Defaults (mav_fb_defaults): 0.4, 1, 12, 10, 8, 1.2, 0.  flags: 0 or MAV_OPTFLOW_USE_INITIAL_FLOW (box window either way;
- * OPTFLOW_FARNEBACK_GAUSSIAN = 256 is not implemented: MAV_ERR_ARG).  The bit is accepted so that a cv2 argument list passes as it
- * is; only mav_farneback_init / mav_farneback_init_dev start from an initial flow, every other entry point starts from zero. */
+ * Defaults (mav_fb_defaults): 0.4, 1, 12, 10, 8, 1.2, 0.  flags: 0 or MAV_OPTFLOW_USE_INITIAL_FLOW.  The bit is accepted so that a
+ * cv2 argument list passes as it is; only mav_farneback_init / mav_farneback_init_dev start from an initial flow, every other entry
+ * point starts from zero.  OPTFLOW_FARNEBACK_GAUSSIAN = 256 is not a flag of mav_create (MAV_ERR_ARG): the window is a property of
+ * the context, chosen with mav_set_window below; mask the bit and call mav_set_window(ctx, MAV_WINDOW_GAUSSIAN). */
 #define MAV_OPTFLOW_USE_INITIAL_FLOW 4
+#define MAV_OPTFLOW_FARNEBACK_GAUSSIAN 256 /* cv2's value, for callers that translate a cv2 argument list; see mav_set_window */
 typedef struct {
     double pyr_scale;
     int levels, winsize, iterations, poly_n;
@@ -138,9 +140,21 @@ int mav_device_count(void);       /* <= 0 when no GPU is visible */
  * None of them changes a result bit (tests/test_gpu_flow.py, tests/test_gpu_screen.py). */
 int mav_set_option(mav_ctx*, const char* name, long value);
 int mav_get_option(mav_ctx*, const char* name, long* value);
+/* The sweep's window: MAV_WINDOW_BOX (default; cv2's default flags) or MAV_WINDOW_GAUSSIAN (cv2's OPTFLOW_FARNEBACK_GAUSSIAN:
+ * FarnebackUpdateFlow_GaussianBlur -- two (2m+1)-tap weighted sums, m = winsize / 2, sigma = 0.3 m, in place of the two box sums, all
+ * in float32, and that path's own 2x2 solve).  Every entry point that computes flow follows it: mav_farneback*, mav_process_batch*,
+ * mav_frame_step* with compute_flow, mav_stage_blur_iter.  Same tiles, launches, bands and streams as the box window; the flow of
+ * a Gaussian context is bit-identical across schedules, as the box window's is.  mav_set_window drains the context's worker and
+ * streams first; other values are MAV_ERR_ARG.  The definition (taps included) is restated from OpenCV 4.x and not pinned against
+ * a cv2 build: see DESIGN.md section 8. */
+#define MAV_WINDOW_BOX 0
+#define MAV_WINDOW_GAUSSIAN 1
+int mav_set_window(mav_ctx*, int window);
+int mav_get_window(mav_ctx*, int* window);
 /* The schedule a call of `batch` pairs takes with the options in effect, as one line of JSON: every option above, the group split,
  * whether the small-batch schedule applies and, per layer, the blur form and how the sweeps run (pairs per launch, bands).
- * bench.py prints it into its record and hashes it together with the kernel sources. */
+ * bench.py prints it into its record and hashes it together with the kernel sources.  A context with the Gaussian window appends
+ * one field, "window": "gaussian"; a box context's line does not mention the window. */
 int mav_schedule_info(mav_ctx*, int batch, char* buf, size_t cap);
 /* The same for frames of a MAV_DEPTH_* depth: only the layers' "blur" forms depend on it (staged rows of 16U / 32F frames take 2x / 4x
  * the LDS of 8U ones, and a short Gaussian whose staged tile would not fit goes through the two-pass form).  MAV_DEPTH_8U: the line
@@ -615,7 +629,8 @@ int mav_stage_update_matrices(mav_ctx*, const float* R0, const float* R1, const 
 int mav_stage_update_matrices_from(mav_ctx*, const float* R0, const float* R1, const float* flow_coarse, int k, float* M);
 /* the initial flow of layer k from a frame-size field flow0 (H, W, 2): resize(INTER_AREA) to (h_k, w_k), times pyr_scale^k */
 int mav_stage_initial_flow(mav_ctx*, const float* flow0, int k, float* out);
-/* one FarnebackUpdateFlow_Blur sweep at layer k: M (5,h,w) -> flow (h,w,2) and, if update != 0, M_out (5,h,w) */
+/* one FarnebackUpdateFlow_Blur sweep (FarnebackUpdateFlow_GaussianBlur on a context with MAV_WINDOW_GAUSSIAN) at layer k:
+ * M (5,h,w) -> flow (h,w,2) and, if update != 0, M_out (5,h,w) */
 int mav_stage_blur_iter(mav_ctx*, const float* R0, const float* R1, const float* M, int k, int update, float* flow,
                         float* M_out);
 

@@ -1807,6 +1807,265 @@ __global__ __launch_bounds__(256) void k_blur_iter_fast(const float* __restrict_
     STAMP_ADD(0, ts0, ts1); STAMP_ADD(1, ts1, ts2); STAMP_ADD(2, ts2, ts3); STAMP_ADD(4, ts3, ts4); STAMP_ADD(6, ts0, ts4); STAMP_ADD(7, 0ull, 1ull);
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// The sweep with a Gaussian window (OPTFLOW_FARNEBACK_GAUSSIAN; FarnebackUpdateFlow_GaussianBlur): sibling kernels of the two box
+// forms above -- same tiles, same m-pixel halo, same launch geometry, same bytes in and out -- so the box kernels compile exactly as
+// they did without them.  The two sliding box sums become two (2m+1)-tap weighted sums, everything in float32, nothing fused, one
+// fixed order per pixel (tests/gauss_window_ref.py restates it in numpy; the kernels equal it bit for bit):
+//   V(y, x) = M(y, x) k0;  for i = 1..m:  V += (M(max(y - i, 0), x) + M(min(y + i, h - 1), x)) k_i
+//   S(y, x) = V(y, x) k0;  for i = 1..m:  S += (V(y, max(x - i, 0)) + V(y, min(x + i, w - 1))) k_i
+// The taps do not sum to 1 and there is no 1 / winsize^2 scale.  Phases, LDS layout and the barrier are those of the box forms:
+// what changes is the arithmetic of the two passes (19 operations per output and plane at m = 6 against the sliding sums' 2).
+// ------------------------------------------------------------------------------------------------------------
+void gauss_taps(int winsize, GaussTaps* out)
+{
+    const int m = winsize / 2;
+    const double sigma = m * 0.3;
+    float t[MAV_MAX_WIN_HALF + 1];
+    double s = 1.;                                     // as the CPU code has it: starts at 1, and the centre tap counts twice too
+    for (int i = 0; i <= m; i++) {
+        t[i] = (float)exp(-i * i / (2 * sigma * sigma));
+        s += t[i] * 2;
+    }
+    s = 1. / s;
+    for (int i = 0; i <= MAV_MAX_WIN_HALF; i++) out->k[i] = i <= m ? (float)(t[i] * s) : 0.f;
+}
+
+// one weighted sum: centre c and the taps' pairs at c -+ i * step, in the order every form uses
+template <int M_T>
+static __device__ __forceinline__ float gauss_sum(const float* p, int step, int m_rt, const GaussTaps& gt)
+{
+#pragma clang fp contract(off)
+    const int m = M_T > 0 ? M_T : m_rt;
+    float a = p[0] * gt.k[0];
+    if (M_T > 0) {
+#pragma unroll
+        for (int i = 1; i <= M_T; i++) a += (p[-i * step] + p[i * step]) * gt.k[i];
+    } else {
+        for (int i = 1; i <= m; i++) a += (p[-i * step] + p[i * step]) * gt.k[i];
+    }
+    return a;
+}
+
+// the 2x2 solve as the Gaussian CPU path has it: products and differences in float32, the regularised reciprocal and the final
+// product in double.  (solve_px above is the box path's, which sums in double on the CPU.)
+static __device__ __forceinline__ void solve_gauss_px(float g11, float g12, float g22, float h1, float h2, float* u, float* v)
+{
+#pragma clang fp contract(off)
+    const float d = g11 * g22 - g12 * g12;
+    const double idet = 1.0 / ((double)d + 1e-3);
+    *u = (float)((double)(g11 * h2 - g12 * h1) * idet);
+    *v = (float)((double)(g22 * h1 - g12 * h2) * idet);
+}
+
+template <int M_T>
+__global__ __launch_bounds__(256) void k_gauss_iter_generic(const float* __restrict__ M_in, float* __restrict__ M_out, size_t M_stride,
+                                                            const float* __restrict__ R0, const float* __restrict__ R1, size_t R_stride,
+                                                            int w, int h, int m_rt, int pitch, int plane, GaussTaps gt, int do_update,
+                                                            float* __restrict__ flow, size_t f_stride)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int m = M_T > 0 ? M_T : m_rt;
+    const int ext = MAV_TILE + 2 * m;
+    const int tid = threadIdx.x;
+    const int s = blockIdx.z;
+    const int x0 = blockIdx.x * MAV_TILE, y0 = blockIdx.y * MAV_TILE;
+    const size_t npx = (size_t)w * h;
+    const float* Min = M_in + (size_t)s * M_stride;
+
+    for (int c = 0; c < 5; c++) {
+        const float* P = Min + c * npx;
+        float* L = lds + c * plane;
+        for (int i = tid; i < ext * ext; i += 256) {
+            const int ly = i / ext, lx = i - ly * ext;
+            const int gx = clampi(x0 - m + lx, 0, w - 1), gy = clampi(y0 - m + ly, 0, h - 1);
+            L[ly * pitch + lx] = P[(size_t)gy * w + gx];
+        }
+    }
+    __syncthreads();
+    // vertical sums in place: output row y reads rows y .. y + 2m and is stored at row y, which no later output reads
+    for (int t = tid; t < 5 * ext; t += 256) {
+        const int c = t / ext, lx = t - c * ext;
+        float* col = lds + c * plane + lx;
+        for (int y = 0; y < MAV_TILE; y++) col[y * pitch] = gauss_sum<M_T>(col + (y + m) * pitch, pitch, m, gt);
+    }
+    __syncthreads();
+    for (int t = tid; t < 5 * MAV_TILE; t += 256) {
+        const int c = t >> 5, y = t & 31;
+        float* row = lds + c * plane + y * pitch;
+        for (int x = 0; x < MAV_TILE; x++) row[x] = gauss_sum<M_T>(row + x + m, 1, m, gt);
+    }
+    __syncthreads();
+    const float* R0p = R0 + (size_t)s * R_stride;
+    const float* R1p = R1 + (size_t)s * R_stride;
+    float* Mo = M_out + (size_t)s * M_stride;
+    float* fo = flow + (size_t)s * f_stride;
+    const int lx = tid & 31;
+    const int gx = x0 + lx;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int ly = (tid >> 5) + 8 * j;
+        const int gy = y0 + ly;
+        if (gx >= w || gy >= h) continue;
+        const float* L = lds + ly * pitch + lx;
+        float u, v;
+        solve_gauss_px(L[0], L[plane], L[2 * plane], L[3 * plane], L[4 * plane], &u, &v);
+        *(float2*)(fo + ((size_t)gy * w + gx) * 2) = make_float2(u, v);
+        if (do_update) update_px(R0p, R1p, npx, w, h, gx, gy, u, v, Mo);
+    }
+}
+
+// The fast form (see k_blur_iter_fast for the tile, the lane assignment and the single barrier): phase A takes its 13-tap vertical
+// sums from the 28 rows a thread already holds in registers, phase B its horizontal sums from the 16 floats it reads from LDS.
+template <int M_T, bool AL = true, bool WT = false>
+__global__ __launch_bounds__(256) void k_gauss_iter_fast(const float* __restrict__ M_in, float* __restrict__ M_out,
+                                                         size_t M_stride, const float* __restrict__ R0,
+                                                         const float* __restrict__ R1, size_t R_stride, int w, int h,
+                                                         TileMap tm, GaussTaps gt,
+                                                         int do_update, int store_flow, float* __restrict__ flow, size_t f_stride)
+{
+#pragma clang fp contract(off)
+    constexpr int EXT_X = FT_X + 2 * M_T;
+    constexpr int EXT_Y = FT_Y + 2 * M_T;
+    constexpr int PITCH = (EXT_X + 3) & ~3;
+    constexpr int PLANE = FT_Y * PITCH + (EXT_X - (FT_Y * PITCH) % 32 + 64) % 32;
+    static_assert(PLANE % 4 == 0 && EXT_X % 2 == 0, "plane must keep 16-byte alignment");
+    __shared__ __attribute__((aligned(16))) float vs[5 * PLANE];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wv = tid >> 6;
+    int s, tx, ty;
+    if (!tile_of_block(tm, &s, &tx, &ty)) return;
+    const int x0 = tx * FT_X, y0 = ty * FT_Y;
+    const size_t npx = (size_t)w * h;
+    const float* Min = M_in + (size_t)s * M_stride;
+    const float* R0p = R0 + (size_t)s * R_stride;
+    const float* R1p = R1 + (size_t)s * R_stride;
+
+    float q[4][5];
+    int gys[4];
+    const int gxc = min(x0 + lane, w - 1);
+    if (do_update) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            gys[j] = min(y0 + wv * 4 + j, h - 1);
+            const size_t idx = (size_t)gys[j] * w + gxc;
+#pragma unroll
+            for (int c = 0; c < 5; c++) q[j][c] = R0p[c * npx + idx];
+        }
+    }
+
+    if (x0 >= M_T && x0 + FT_X + M_T <= w) {
+        constexpr int NP = EXT_X / 2;
+        for (int t = tid; t < 5 * NP; t += 256) {
+            const int c = t / NP, pr = t - c * NP;
+            const float* col = Min + c * npx + (x0 - M_T + 2 * pr);
+            float2 v[EXT_Y];
+#pragma unroll
+            for (int i = 0; i < EXT_Y; i++) {
+                const float* pp = col + (size_t)clampi(y0 - M_T + i, 0, h - 1) * w;
+                if (AL) v[i] = *(const float2*)pp;
+                else { const F2U t = *(const F2U*)pp; v[i] = make_float2(t.x, t.y); }
+            }
+            float* out = vs + c * PLANE + 2 * pr;
+#pragma unroll
+            for (int y = 0; y < FT_Y; y++) {
+                float sx = v[y + M_T].x * gt.k[0], sy = v[y + M_T].y * gt.k[0];
+#pragma unroll
+                for (int i = 1; i <= M_T; i++) {
+                    sx += (v[y + M_T - i].x + v[y + M_T + i].x) * gt.k[i];
+                    sy += (v[y + M_T - i].y + v[y + M_T + i].y) * gt.k[i];
+                }
+                *(float2*)(out + y * PITCH) = make_float2(sx, sy);
+            }
+        }
+    } else {
+        for (int t = tid; t < 5 * EXT_X; t += 256) {
+            const int c = t / EXT_X, lx = t - c * EXT_X;
+            const int gx = clampi(x0 - M_T + lx, 0, w - 1);
+            const float* col = Min + c * npx + gx;
+            float v[EXT_Y];
+#pragma unroll
+            for (int i = 0; i < EXT_Y; i++) v[i] = col[(size_t)clampi(y0 - M_T + i, 0, h - 1) * w];
+            float* out = vs + c * PLANE + lx;
+#pragma unroll
+            for (int y = 0; y < FT_Y; y++) out[y * PITCH] = gauss_sum<M_T>(v + y + M_T, 1, M_T, gt);
+        }
+    }
+    __syncthreads();
+
+    {
+        const int quad = (lane & 31) >> 2;
+        const int grp = (lane >> 5) * 2 + ((quad == 1 || quad == 2 || quad == 4 || quad == 7) ? 1 : 0);
+        const int qpos = (quad == 0 || quad == 1) ? 0 : ((quad == 3 || quad == 2) ? 1 : ((quad == 5 || quad == 4) ? 2 : 3));
+        const int pos = qpos * 4 + (lane & 3);
+        const int ly = wv * 4 + grp;
+        const int lx0 = pos * 4;
+        const int gx = x0 + lx0, gy = y0 + ly;
+        float S[5][4];
+#pragma unroll
+        for (int c = 0; c < 5; c++) {
+            const float4* p = (const float4*)(vs + c * PLANE + ly * PITCH + lx0);
+            constexpr int NV = (4 + 2 * M_T + 3) / 4;
+            float f[4 * NV];
+#pragma unroll
+            for (int k = 0; k < NV; k++) {
+                const float4 t4 = p[k];
+                f[4 * k] = t4.x; f[4 * k + 1] = t4.y; f[4 * k + 2] = t4.z; f[4 * k + 3] = t4.w;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++) S[c][j] = gauss_sum<M_T>(f + j + M_T, 1, M_T, gt);
+        }
+        float u[4], v[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) solve_gauss_px(S[0][j], S[1][j], S[2][j], S[3][j], S[4][j], &u[j], &v[j]);
+        if (store_flow && gx < w && gy < h) {
+            float* fo = flow + (size_t)s * f_stride + ((size_t)gy * w + gx) * 2;
+            if (AL) {
+                *(float4*)fo = make_float4(u[0], v[0], u[1], v[1]);
+                *(float4*)(fo + 4) = make_float4(u[2], v[2], u[3], v[3]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    if (gx + j < w) *(float2*)(fo + 2 * j) = make_float2(u[j], v[j]);
+            }
+        }
+        if (!do_update) return;
+        *(float4*)(vs + ly * PITCH + lx0) = make_float4(u[0], u[1], u[2], u[3]);
+        *(float4*)(vs + PLANE + ly * PITCH + lx0) = make_float4(v[0], v[1], v[2], v[3]);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+    float* Mo = M_out + (size_t)s * M_stride;
+    const bool colok = x0 + lane < w;
+#pragma unroll
+    for (int jb = 0; jb < 4; jb += 2) {
+        GatherPx g[2];
+        float fu[2], fv[2];
+#pragma unroll
+        for (int jj = 0; jj < 2; jj++) {
+            const int ly = wv * 4 + jb + jj;
+            fu[jj] = vs[ly * PITCH + lane];
+            fv[jj] = vs[PLANE + ly * PITCH + lane];
+            gather_issue(R1p, npx, w, h, gxc, gys[jb + jj], fu[jj], fv[jj], g[jj]);
+        }
+#pragma unroll
+        for (int jj = 0; jj < 2; jj++) {
+            float o[5];
+            update_finish(q[jb + jj], g[jj], w, h, gxc, gys[jb + jj], fu[jj], fv[jj], o);
+            if (colok && y0 + wv * 4 + jb + jj < h) {
+                const size_t idx = (size_t)gys[jb + jj] * w + gxc;
+#pragma unroll
+                for (int c = 0; c < 5; c++) {
+                    if constexpr (WT) __hip_atomic_store((unsigned*)(Mo + c * npx + idx), __float_as_uint(o[c]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    else Mo[c * npx + idx] = o[c];
+                }
+            }
+        }
+    }
+}
+
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 int blur_iter_tile_rows(int h) { return (h + FT_Y - 1) / FT_Y; }
 static bool blur_iter_vec_ok(int w, size_t M_stride, size_t R_stride, size_t f_stride, const void* M_in, const void* M_out, const void* R0,
@@ -1821,11 +2080,53 @@ bool blur_iter_bands_ok(int w, int winsize, size_t M_stride, size_t R_stride, si
     return winsize / 2 == 6 && blur_iter_vec_ok(w, M_stride, R_stride, f_stride, M_in, M_out, R0, R1, flow);
 }
 
+// The Gaussian window: the dispatch of launch_blur_iter below, form for form, onto the sibling kernels.
+static void launch_gauss_iter(hipStream_t st, const float* M_in, float* M_out, size_t M_stride, const float* R0, const float* R1,
+                              size_t R_stride, int G, int w, int h, int winsize, int do_update, int store_flow, float* flow, size_t f_stride,
+                              int ty0, int ty1, int strip, bool write_through, const GaussTaps& gt)
+{
+    int ext, pitch, plane;
+    const int m = winsize / 2;
+    dim3 grid((w + MAV_TILE - 1) / MAV_TILE, (h + MAV_TILE - 1) / MAV_TILE, G);
+    const bool vec_ok = blur_iter_vec_ok(w, M_stride, R_stride, f_stride, M_in, M_out, R0, R1, flow);
+    if (m == 6 && vec_ok) {
+        const TileMap tm = make_tile_map(w, h, G, FT_X, FT_Y, ty0, ty1, strip);
+        if (tm.n_tiles == 0) return;
+        if (write_through && do_update)
+            hipLaunchKernelGGL((k_gauss_iter_fast<6, true, true>), dim3(tile_grid(tm)), dim3(256), 0, st, M_in, M_out, M_stride, R0, R1, R_stride, w,
+                               h, tm, gt, do_update, store_flow, flow, f_stride);
+        else
+            hipLaunchKernelGGL(k_gauss_iter_fast<6>, dim3(tile_grid(tm)), dim3(256), 0, st, M_in, M_out, M_stride, R0, R1, R_stride, w, h,
+                               tm, gt, do_update, store_flow, flow, f_stride);
+        return;
+    }
+    if (m == 6 && f_stride % 2 == 0 && ((uintptr_t)flow & 7) == 0) {
+        const TileMap tm = make_tile_map(w, h, G, FT_X, FT_Y, 0, -1, strip);
+        if (write_through && do_update)
+            hipLaunchKernelGGL((k_gauss_iter_fast<6, false, true>), dim3(tile_grid(tm)), dim3(256), 0, st, M_in, M_out, M_stride, R0, R1, R_stride,
+                               w, h, tm, gt, do_update, store_flow, flow, f_stride);
+        else
+            hipLaunchKernelGGL((k_gauss_iter_fast<6, false>), dim3(tile_grid(tm)), dim3(256), 0, st, M_in, M_out, M_stride, R0, R1, R_stride,
+                               w, h, tm, gt, do_update, store_flow, flow, f_stride);
+        return;
+    }
+    iter_geometry(m, &ext, &pitch, &plane);
+    const size_t lds = sizeof(float) * 5 * (size_t)plane;
+    if (m == 6)
+        hipLaunchKernelGGL(k_gauss_iter_generic<6>, grid, dim3(256), lds, st, M_in, M_out, M_stride, R0, R1, R_stride, w, h, m,
+                           pitch, plane, gt, do_update, flow, f_stride);
+    else
+        hipLaunchKernelGGL(k_gauss_iter_generic<0>, grid, dim3(256), lds, st, M_in, M_out, M_stride, R0, R1, R_stride, w, h, m,
+                           pitch, plane, gt, do_update, flow, f_stride);
+}
+
 // tile rows [ty0, ty1) only (ty1 < 0: the whole layer).  Band launches exist for the fast form only (blur_iter_bands_ok).
 void launch_blur_iter(hipStream_t st, const float* M_in, float* M_out, size_t M_stride, const float* R0, const float* R1,
                       size_t R_stride, int G, int w, int h, int winsize, int do_update, int store_flow, float* flow, size_t f_stride,
-                      int ty0, int ty1, int strip, bool write_through)
+                      int ty0, int ty1, int strip, bool write_through, const GaussTaps* gauss)
 {
+    if (gauss) return launch_gauss_iter(st, M_in, M_out, M_stride, R0, R1, R_stride, G, w, h, winsize, do_update, store_flow, flow, f_stride,
+                                        ty0, ty1, strip, write_through, *gauss);
     int ext, pitch, plane;
     const int m = winsize / 2;
     const float scale = (float)(1.0 / ((double)winsize * winsize));
@@ -1868,7 +2169,8 @@ const char* blur_iter_prepare(int winsize)
 {
     const size_t lds = blur_iter_lds_bytes(winsize);
     if (lds <= (size_t)64 * 1024) return nullptr;
-    const hipError_t e = hipFuncSetAttribute((const void*)k_blur_iter_generic<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute((const void*)k_blur_iter_generic<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gauss_iter_generic<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }
 

@@ -406,6 +406,8 @@ struct mav_ctx {
     bool small_batch = true;                  // option "small_batch"
     int sweep_wt = -1;                        // option "sweep_write_through": -1 = in the two-stream schedules only (default), 0 / 1 = never / always
     int small_batch_mb = 200;                 // option "small_batch_mb": ... for groups of at most this much finest-layer sweep working set
+    int window = MAV_WINDOW_BOX;     // mav_set_window: the sweeps' window (not an option: a box context's schedule line never names it)
+    GaussTaps gauss;                 // the Gaussian window's taps for fb.winsize (mav_create)
     int bands = 1;                   // option "bands": the finest layer's sweeps in band-major order over this many skewed bands
     // option "pairs_in_flight" (1 or 2): the finest layer's per-pair work (initial M + sweeps) of a group alternates between the
     // compute stream and pair_stream, every pair band-major over bands of at most pif_band_mb of working set (layer_sweeps)
@@ -648,8 +650,8 @@ extern "C" int mav_create(mav_ctx** out, int device, int W, int H, int max_batch
     // OPTFLOW_USE_INITIAL_FLOW is accepted so that a cv2 argument list passes as it is; only the entry points that take an initial flow
     // (mav_farneback_init / _init_dev) use one, the others start from zero whatever the bit says
     if (fb.flags & ~MAV_OPTFLOW_USE_INITIAL_FLOW)
-        return fail(MAV_ERR_ARG, "only flags 0 and OPTFLOW_USE_INITIAL_FLOW (4) are implemented (box window; OPTFLOW_FARNEBACK_GAUSSIAN is not), got %d",
-                    fb.flags);
+        return fail(MAV_ERR_ARG, "mav_create takes flags 0 and OPTFLOW_USE_INITIAL_FLOW (4) only, got %d (OPTFLOW_FARNEBACK_GAUSSIAN = 256 is "
+                    "chosen with mav_set_window(ctx, MAV_WINDOW_GAUSSIAN): mask the bit)", fb.flags);
     if (fb.winsize / 2 != 6 && blur_iter_lds_bytes(fb.winsize) > (size_t)160 * 1024)
         return fail(MAV_ERR_ARG, "winsize %d needs %zu bytes of LDS per workgroup in the general sweep kernel, the CU has 163840", fb.winsize,
                     blur_iter_lds_bytes(fb.winsize));
@@ -665,6 +667,7 @@ extern "C" int mav_create(mav_ctx** out, int device, int W, int H, int max_batch
 
     mav_ctx* c = new mav_ctx();
     c->device = device; c->W = W; c->H = H; c->max_batch = max_batch; c->fb = fb;
+    gauss_taps(fb.winsize, &c->gauss);
     struct Guard { mav_ctx* c; ~Guard() { mav_destroy(c); } } half_built{c};      // any failure below destroys what exists by then
     // The compute stream now; the copy stream (overlapped uploads) and the pair stream (two pairs in flight) with their events when a
     // call first needs them (ensure_copy_stream / ensure_pair_stream): a context that serves one-pair calls as one of several LANES
@@ -868,6 +871,26 @@ extern "C" int mav_set_option(mav_ctx* c, const char* name, long value)
     if (value < o->lo || value > o->hi) return fail(MAV_ERR_ARG, "option '%s' must be in [%ld, %ld], got %ld", name, o->lo, o->hi, value);
     if (o->set) return o->set(c, value);
     if (o->i) c->*o->i = (int)value; else c->*o->b = value != 0;
+    return MAV_OK;
+}
+
+// The sweeps' window.  Not a row of kOptions: mav_schedule_info prints that table, and a box context's line is pinned byte for byte.
+static const GaussTaps* window_taps(const mav_ctx* c) { return c->window == MAV_WINDOW_GAUSSIAN ? &c->gauss : nullptr; }
+extern "C" int mav_set_window(mav_ctx* c, int window)
+{
+    if (!c) return fail(MAV_ERR_ARG, "mav_set_window: NULL context");
+    if (window != MAV_WINDOW_BOX && window != MAV_WINDOW_GAUSSIAN)
+        return fail(MAV_ERR_ARG, "mav_set_window: window must be MAV_WINDOW_BOX (0) or MAV_WINDOW_GAUSSIAN (1), got %d", window);
+    HIPCHK(hipSetDevice(c->device));
+    CHK(mav_worker_drain(c));                  // nothing enqueued with the old window is still to come, nothing of it is in flight
+    CHK(sync_all_streams(c));
+    c->window = window;
+    return MAV_OK;
+}
+extern "C" int mav_get_window(mav_ctx* c, int* window)
+{
+    if (!c || !window) return fail(MAV_ERR_ARG, "mav_get_window: NULL argument");
+    *window = c->window;
     return MAV_OK;
 }
 
@@ -1428,7 +1451,7 @@ static void sweeps_band_major(mav_ctx* c, hipStream_t st, int kid, float* Ma, fl
             if (ty1 <= ty0) continue;
             ProfScope ps(c, kid, st);
             launch_blur_iter(st, (it & 1) ? Mb : Ma, (it & 1) ? Ma : Mb, ms, r0, r1, rs, gs, lw, lh, c->fb.winsize, update, !update, fo,
-                             fstride, ty0, ty1, c->strip, wt);
+                             fstride, ty0, ty1, c->strip, wt, window_taps(c));
         }
     }
 }
@@ -1789,7 +1812,7 @@ static int schedule_info(mav_ctx* c, int batch, int esize, char* buf, size_t cap
                  p.name, p.per_launch, p.J);
         o += t;
     }
-    o += "]}";
+    o += c->window == MAV_WINDOW_GAUSSIAN ? "], \"window\": \"gaussian\"}" : "]}";
     if (o.size() + 1 > cap) return fail(MAV_ERR_ARG, "mav_schedule_info: buffer of %zu bytes too small (%zu needed)", cap, o.size() + 1);
     memcpy(buf, o.c_str(), o.size() + 1);
     return MAV_OK;
@@ -3157,7 +3180,7 @@ extern "C" int mav_stage_blur_iter(mav_ctx* c, const float* R0, const float* R1,
     CHK(d0.upload(c, R0, 5 * n * sizeof(float))); CHK(d1.upload(c, R1, 5 * n * sizeof(float)));
     CHK(dm.upload(c, M, 5 * n * sizeof(float))); CHK(dmo.alloc(c, 5 * n * sizeof(float))); CHK(df.alloc(c, 2 * n * sizeof(float)));
     launch_blur_iter(c->stream, dm.as<float>(), dmo.as<float>(), 5 * n, d0.as<float>(), d1.as<float>(), 5 * n, 1, l->w, l->h,
-                     c->fb.winsize, update, 1, df.as<float>(), 2 * n, 0, -1, c->strip);
+                     c->fb.winsize, update, 1, df.as<float>(), 2 * n, 0, -1, c->strip, false, window_taps(c));
     CHK(check_launch("blur_iter"));
     CHK(download(c, flow, df.p, 2 * n * sizeof(float)));
     if (update) CHK(download(c, M_out, dmo.p, 5 * n * sizeof(float)));

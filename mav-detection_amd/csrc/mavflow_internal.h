@@ -80,18 +80,23 @@ void launch_update_matrices(hipStream_t st, const float* R0, const float* R1, si
 void launch_update_matrices_flow(hipStream_t st, const float* R0, const float* R1, size_t R_stride, const float* flow,
                                  size_t f_stride, int G, int w, int h, float* M, size_t M_stride,
                                  int y_begin = 0, int y_end = -1 /* pixel rows [y_begin, y_end) only; -1 = to the bottom */);
+// The Gaussian window of the sweep (OPTFLOW_FARNEBACK_GAUSSIAN): taps k[0..m], m = winsize / 2, as gauss_taps() computes them on the host.
+#define MAV_MAX_WIN_HALF 32                     // winsize <= 64 (mav_create)
+struct GaussTaps { float k[MAV_MAX_WIN_HALF + 1]; };
+void gauss_taps(int winsize, GaussTaps* out);
 void launch_blur_iter(hipStream_t st, const float* M_in, float* M_out, size_t M_stride, const float* R0, const float* R1,
                       size_t R_stride, int G, int w, int h, int winsize, int do_update, int store_flow, float* flow, size_t f_stride,
                       int ty0 = 0, int ty1 = -1 /* tile rows [ty0, ty1) of 16 pixel rows; ty1 < 0 = the whole layer */,
                       int strip = 0 /* width in tiles of the tile order's column strips; 0 = automatic */,
-                      bool write_through = false /* M' through sc1 stores: see k_blur_iter_fast */);
+                      bool write_through = false /* M' through sc1 stores: see k_blur_iter_fast */,
+                      const GaussTaps* gauss = nullptr /* OPTFLOW_FARNEBACK_GAUSSIAN: the window's taps; nullptr = box window */);
 int blur_iter_tile_rows(int h);                 // 16-pixel tile rows of a layer of height h
 // band launches (ty0 / ty1) are honoured only by the fast sweep kernel: true when launch_blur_iter will take it for these operands
 bool blur_iter_bands_ok(int w, int winsize, size_t M_stride, size_t R_stride, size_t f_stride, const void* M_in, const void* M_out,
                         const void* R0, const void* R1, const void* flow);
 // store_flow == 0: the sweep's flow is consumed inside the kernel only (valid when do_update != 0)
 size_t blur_iter_lds_bytes(int winsize);
-const char* blur_iter_prepare(int winsize);   // grants the general sweep kernel its dynamic LDS on the current device
+const char* blur_iter_prepare(int winsize);   // grants the general sweep kernels (both windows) their dynamic LDS on the current device
 
 void launch_probe_r3w1(hipStream_t st, const float* a, const float* b, const float* c, float* d, size_t n_float4);   // calibration
 

@@ -76,6 +76,7 @@ EXPORTS = [
     "mav_gftt_defaults", "mav_lk_defaults", "mav_good_features", "mav_good_features_dev", "mav_lk_track", "mav_lk_track_dev",
     "mav_lk_last_iterations", "mav_lk_level_dims", "mav_stage_lk_pyramid", "mav_stage_lk_scharr", "mav_stage_min_eigen",
     "mav_good_features_ex", "mav_good_features_ex_dev", "mav_lk_track_ex_dev", "mav_gftt_last_pick", "mav_stage_corner_pick",
+    "mav_set_window", "mav_get_window",
 ]
 
 # Frame depths of the _ex entry points (cv2's depth codes) by numpy dtype.  uint8 frames keep going through the u8 symbols.
@@ -83,6 +84,11 @@ DEPTH_8U, DEPTH_16U, DEPTH_32F = 0, 2, 5
 DEPTHS = {np.dtype(np.uint8): DEPTH_8U, np.dtype(np.uint16): DEPTH_16U, np.dtype(np.float32): DEPTH_32F}
 
 OPTFLOW_USE_INITIAL_FLOW = 4                    # FbParams.flags bit (cv2.OPTFLOW_USE_INITIAL_FLOW): see Context.farneback(initial_flow=)
+# cv2.OPTFLOW_FARNEBACK_GAUSSIAN.  Not an FbParams.flags bit (mav_create refuses it): the window belongs to the context --
+# Context(window="gaussian") / Context.set_window; mavflow.farneback translates a cv2 argument list that carries the bit.
+OPTFLOW_FARNEBACK_GAUSSIAN = 256
+WINDOW_BOX, WINDOW_GAUSSIAN = 0, 1
+WINDOWS = {"box": WINDOW_BOX, "gaussian": WINDOW_GAUSSIAN}
 
 GATHER_ORDERED, GATHER_SOURCES_HELD = 1, 2      # mav_upload_gather flags
 STEP_MAX_GATHER = 4
@@ -139,6 +145,8 @@ def load(path: str | None = None) -> C.CDLL:
     lib.mav_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
     lib.mav_get_option.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_long)]
     lib.mav_schedule_info.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t]
+    lib.mav_set_window.argtypes = [C.c_void_p, C.c_int]
+    lib.mav_get_window.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     lib.mav_runtime_info.argtypes = [C.c_char_p, C.c_size_t]
     lib.mav_membw_probe.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_double)]
     lib.mav_num_layers.argtypes = [C.c_void_p]
@@ -339,6 +347,16 @@ def _depth_of(dtype, name="frames") -> int:
     return d
 
 
+def _window_code(window) -> int:
+    """"box" / "gaussian", or a MAV_WINDOW_* code as it is (the library range-checks it); anything else is a ValueError like every
+    bad argument."""
+    if isinstance(window, str) and window in WINDOWS:
+        return WINDOWS[window]
+    if isinstance(window, (int, np.integer)) and not isinstance(window, bool):
+        return int(window)
+    raise ValueError(f"window must be 'box' or 'gaussian', got {window!r}")
+
+
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -470,7 +488,7 @@ class DeviceBuffer:
 class Context:
     """One mav_ctx: (device, W, H, max_batch, Farneback parameters)."""
 
-    def __init__(self, W: int, H: int, max_batch: int = 1, fb: FbParams | None = None, device: int = 0):
+    def __init__(self, W: int, H: int, max_batch: int = 1, fb: FbParams | None = None, device: int = 0, window="box"):
         self.lib = load()
         self.W, self.H, self.max_batch = int(W), int(H), int(max_batch)
         self.fb = fb if fb is not None else fb_defaults()
@@ -478,6 +496,12 @@ class Context:
         check(self.lib.mav_create(C.byref(h), device, self.W, self.H, self.max_batch, C.byref(self.fb)))
         self._h = h
         self._posted = False                  # steps have been posted to the context's worker thread since the last drain
+        if window not in ("box", WINDOW_BOX):
+            try:
+                self.set_window(window)
+            except Exception:
+                self.close()
+                raise
 
     # A context is single-threaded.  Once a step has been posted (post_step) the library's worker thread is that thread until it has
     # enqueued everything posted; `h` -- what every other call of this binding passes as the context -- therefore drains the worker
@@ -544,6 +568,17 @@ class Context:
         check(self.lib.mav_get_option(self.h, name.encode(), C.byref(v)))
         return v.value
 
+    def set_window(self, window) -> None:
+        """The sweeps' window: "box" (cv2's default) or "gaussian" (cv2.OPTFLOW_FARNEBACK_GAUSSIAN), or the MAV_WINDOW_* code
+        (mav_set_window: drains the context first).  Every call that computes flow follows it from then on."""
+        check(self.lib.mav_set_window(self.h, _window_code(window)))
+
+    @property
+    def window(self) -> str:
+        v = C.c_int()
+        check(self.lib.mav_get_window(self.h, C.byref(v)))
+        return {code: name for name, code in WINDOWS.items()}[v.value]
+
     def membw_probe(self, bytes_per_buffer: int, reps: int = 20) -> float:
         """GB/s of a plain 3-reads-1-write streaming kernel over four buffers of that size (calibration for bench.py's roofline)."""
         g = C.c_double()
@@ -559,7 +594,9 @@ class Context:
             check(self.lib.mav_schedule_info(self.h, int(batch), buf, len(buf)))
         else:
             check(self.lib.mav_schedule_info_ex(self.h, int(batch), _depth_of(dtype), buf, len(buf)))
-        return json.loads(buf.value.decode())
+        info = json.loads(buf.value.decode())
+        info.setdefault("window", "box")      # the library's line names the window of a Gaussian context only
+        return info
 
     def mem_info(self) -> dict:
         """Device memory in bytes: free / total of the GPU, what this context holds in all, and its Farneback workspace alone

@@ -6,6 +6,8 @@ reference's behaviour -- it returns a BGR visualisation and falls back to the pr
 flow -- and additionally exposes the dense field as .flow, which the reference computes and throws away."""
 from __future__ import annotations
 
+import builtins
+
 import numpy as np
 
 from . import _lib
@@ -52,6 +54,41 @@ def flow_to_bgr(flow: np.ndarray) -> np.ndarray:
     return hsv_to_bgr(flow_to_hsv(flow)[0])
 
 
+_CTX_CACHE_SIZES = 8                 # contexts kept by calcOpticalFlowFarneback, least recently used first
+_ctx_cache = {}                      # (W, H, parameters, window) -> Context
+
+
+def calcOpticalFlowFarneback(prev, next, flow, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags) -> np.ndarray:
+    """cv2.calcOpticalFlowFarneback's literal signature on libmavflow: a cv2 argument list passes as it is.  flags: 0,
+    OPTFLOW_USE_INITIAL_FLOW (4: `flow` is the starting field), OPTFLOW_FARNEBACK_GAUSSIAN (256: the Gaussian window) or both.
+    Returns the float32 (H, W, 2) field (a new array; `flow` is not written).  Contexts are kept per (W, H, parameters, window),
+    as im_helpers keeps them per frame size, and only dropped, never closed, when the cache lets go of them."""
+    known = _lib.OPTFLOW_USE_INITIAL_FLOW | _lib.OPTFLOW_FARNEBACK_GAUSSIAN
+    if int(flags) & ~known:
+        raise ValueError(f"flags must be a combination of OPTFLOW_USE_INITIAL_FLOW (4) and OPTFLOW_FARNEBACK_GAUSSIAN (256), got {flags}")
+    prev, nxt = np.asarray(prev), np.asarray(next)
+    if prev.ndim != 2 or prev.shape != nxt.shape:
+        raise ValueError("prev and next must be single-channel images of one size")
+    H, W = prev.shape
+    window = "gaussian" if int(flags) & _lib.OPTFLOW_FARNEBACK_GAUSSIAN else "box"
+    key = (W, H, float(pyr_scale), int(levels), int(winsize), int(iterations), int(poly_n), float(poly_sigma), window)
+    ctx = _ctx_cache.pop(key, None)
+    if ctx is None or not ctx.alive:
+        fb = _lib.fb_defaults()
+        fb.pyr_scale, fb.levels, fb.winsize, fb.iterations = float(pyr_scale), int(levels), int(winsize), int(iterations)
+        fb.poly_n, fb.poly_sigma, fb.flags = int(poly_n), float(poly_sigma), 0
+        ctx = _lib.Context(W, H, 1, fb, window=window)
+    _ctx_cache[key] = ctx
+    while len(_ctx_cache) > _CTX_CACHE_SIZES:
+        _ctx_cache.pop(builtins.next(iter(_ctx_cache)))      # (`next` is cv2's argument name here)
+    init = None
+    if int(flags) & _lib.OPTFLOW_USE_INITIAL_FLOW:
+        if flow is None:
+            raise ValueError("OPTFLOW_USE_INITIAL_FLOW needs the starting field in `flow`")
+        init = flow
+    return np.array(ctx.farneback(prev, nxt, initial_flow=init)[0])
+
+
 class Farneback:
     PARAMS = dict(pyr_scale=0.4, levels=1, winsize=12, iterations=10, poly_n=8, poly_sigma=1.2, flags=0)
 
@@ -63,7 +100,10 @@ class Farneback:
         fb = _lib.fb_defaults()
         for k, v in self.PARAMS.items():
             setattr(fb, k, v)
-        self.ctx = _lib.Context(W, H, 1, fb)
+        # cv2.OPTFLOW_FARNEBACK_GAUSSIAN in PARAMS["flags"] selects the context's window; mav_create itself takes the bit for an error
+        gaussian = bool(fb.flags & _lib.OPTFLOW_FARNEBACK_GAUSSIAN)
+        fb.flags &= ~_lib.OPTFLOW_FARNEBACK_GAUSSIAN
+        self.ctx = _lib.Context(W, H, 1, fb, window="gaussian" if gaussian else "box")
         self.prevgray = self._gray(prev)
         self.flow = np.zeros((H, W, 2), np.float32)
         self.history_length = 1

@@ -42,8 +42,10 @@ class FarnebackFlowProvider:
 
     def __init__(self, get_gray: Callable[[int], np.ndarray], width: int, height: int, img_path: Optional[str] = None,
                  write_flo: bool = False, window: int = 1, n_frames: Optional[int] = None, on_device: bool = False,
-                 lanes: Optional[int] = None) -> None:
-        """on_device (window = 1): get_flow_uv returns a pipeline.DeviceArray -- the field stays on the GPU until somebody reads it,
+                 lanes: Optional[int] = None, flow_window: str = "box") -> None:
+        """flow_window: the sweeps' window of every context the provider owns, "box" or "gaussian" (cv2.OPTFLOW_FARNEBACK_GAUSSIAN;
+        `window` above is the older name of the sequence length and keeps that meaning).
+        on_device (window = 1): get_flow_uv returns a pipeline.DeviceArray -- the field stays on the GPU until somebody reads it,
         which Processor.run_detection never does (BGR frames are converted there too); off by default: a host float32 array.
         lanes: contexts the on-device seam takes in turn (None: pipeline.auto_lanes -- 4 up to ~720p, 3 at 1080p, 1 beyond)."""
         from . import _lib
@@ -51,7 +53,7 @@ class FarnebackFlowProvider:
         if window < 1 or (window > 1 and n_frames is None):
             raise ValueError("window must be >= 1, and a window > 1 needs n_frames")
         self.window, self.n_frames = int(window), n_frames
-        self.ctx = _lib.Context(width, height, self.window)
+        self.ctx = _lib.Context(width, height, self.window, window=flow_window)
         self._cache: dict = {}
         self._stage = None
         self._lane_ctxs = []
@@ -60,7 +62,7 @@ class FarnebackFlowProvider:
                 raise ValueError("on_device needs window = 1")
             from . import pipeline
             n = lanes or pipeline.auto_lanes(width, height, 1)
-            self._lane_ctxs = [_lib.Context(width, height, 1) for _ in range(n - 1)]
+            self._lane_ctxs = [_lib.Context(width, height, 1, window=flow_window) for _ in range(n - 1)]
             self._stage = pipeline.LanedFlowStage([self.ctx] + self._lane_ctxs)
         if write_flo and not img_path:
             raise ValueError("write_flo needs img_path")
