@@ -1440,12 +1440,104 @@ void launch_update_matrices_flow(hipStream_t st, const float* R0, const float* R
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// One FarnebackUpdateFlow_Blur sweep (A.6), fused: (2m+1)^2 box sum of the 5 M planes -> 2x2 solve -> flow, and
+// The sweep's window: a compile-time policy of the two sweep kernels below (box: FarnebackUpdateFlow_Blur; Gaussian:
+// OPTFLOW_FARNEBACK_GAUSSIAN, FarnebackUpdateFlow_GaussianBlur).  Tiles, halo, LDS layout, launch geometry and the bytes moved are the
+// same for both; a policy holds what differs: the kernel argument, how a run of N + 2m values becomes N windowed sums, the 2x2 solve.
+//   sums<M_T, N, REGS>(m_rt, in, out)   in(i), i = 0 .. N + 2m - 1, reads input i; out(j, s), j = 0 .. N - 1, takes sum j, the one over
+//       inputs j .. j + 2m.  Whatever sum j + 1 needs of input j is read before out(j, ...) runs, so out(j) may overwrite input j (the
+//       generic form sums in place in LDS).  m = M_T when M_T > 0 (the loops over the taps unroll), else m_rt.  REGS: inputs and
+//       outputs are registers, so the loop over the outputs unrolls fully; otherwise they are LDS and it unrolls in part.  A value is
+//       whatever in() returns: a float, or the float2 of a column pair (the fast form's phase A; each half has the float's arithmetic).
+//   solve(g11, g12, g22, h1, h2, &u, &v)   the flow of one pixel from its five sums.
+// Every pass of both kernel forms takes its sums from sums() and its flow from solve(); nothing else in them knows the window.
+// Box: the sum of the first 2m + 1 values, then slide; the 1 / winsize^2 scale goes in front of the solve.
+// Gaussian: everything in float32, nothing fused, one fixed order per value (tests/gauss_window_ref.py restates it in numpy; the kernels
+// equal it bit for bit) -- vertically, then horizontally on the result, with edge-clamped coordinates:
+//   V(y, x) = M(y, x) k0;  for i = 1..m:  V += (M(max(y - i, 0), x) + M(min(y + i, h - 1), x)) k_i
+//   S(y, x) = V(y, x) k0;  for i = 1..m:  S += (V(y, max(x - i, 0)) + V(y, min(x + i, w - 1))) k_i
+// The taps do not sum to 1 and there is no 1 / winsize^2 scale: 19 operations per output and plane at m = 6 against the box's 2.
+// ------------------------------------------------------------------------------------------------------------
+struct BoxWindow {
+    float scale;                                       // 1 / winsize^2
+    template <int M_T, int N, bool REGS, typename In, typename Out>
+    __device__ __forceinline__ void sums(int m_rt, In in, Out out) const
+    {
+        const int win = 2 * (M_T > 0 ? M_T : m_rt) + 1;
+        constexpr int UNROLL = REGS ? N : 8;
+        decltype(in(0)) sum{};
+#pragma unroll
+        for (int k = 0; k < win; k++) sum += in(k);
+#pragma unroll UNROLL
+        for (int j = 0; j < N; j++) {
+            const auto s = sum;
+            if (j < N - 1) sum += in(j + win) - in(j);
+            out(j, s);
+        }
+    }
+    __device__ __forceinline__ void solve(float g11, float g12, float g22, float h1, float h2, float* u, float* v) const
+    {
+        solve_px(g11 * scale, g12 * scale, g22 * scale, h1 * scale, h2 * scale, u, v);
+    }
+};
+
+void gauss_taps(int winsize, GaussTaps* out)
+{
+    const int m = winsize / 2;
+    const double sigma = m * 0.3;
+    float t[MAV_MAX_WIN_HALF + 1];
+    double s = 1.;                                     // as the CPU code has it: starts at 1, and the centre tap counts twice too
+    for (int i = 0; i <= m; i++) {
+        t[i] = (float)exp(-i * i / (2 * sigma * sigma));
+        s += t[i] * 2;
+    }
+    s = 1. / s;
+    for (int i = 0; i <= MAV_MAX_WIN_HALF; i++) out->k[i] = i <= m ? (float)(t[i] * s) : 0.f;
+}
+
+// the 2x2 solve as the Gaussian CPU path has it: products and differences in float32, the regularised reciprocal and the final
+// product in double.  (solve_px above is the box path's, which sums in double on the CPU.)
+static __device__ __forceinline__ void solve_gauss_px(float g11, float g12, float g22, float h1, float h2, float* u, float* v)
+{
+#pragma clang fp contract(off)
+    const float d = g11 * g22 - g12 * g12;
+    const double idet = 1.0 / ((double)d + 1e-3);
+    *u = (float)((double)(g11 * h2 - g12 * h1) * idet);
+    *v = (float)((double)(g22 * h1 - g12 * h2) * idet);
+}
+
+struct GaussWindow {
+    GaussTaps gt;
+    template <int M_T, int N, bool REGS, typename In, typename Out>
+    __device__ __forceinline__ void sums(int m_rt, In in, Out out) const
+    {
+#pragma clang fp contract(off)
+        const int m = M_T > 0 ? M_T : m_rt;
+        constexpr int UNROLL = REGS ? N : 2;           // LDS forms: 2 outputs in flight (8, as the box has it, halves the generic form's occupancy)
+#pragma unroll UNROLL
+        for (int j = 0; j < N; j++) {                  // centre j + m, then the taps' pairs at -+ i: the order every form uses
+            auto a = in(j + m) * gt.k[0];
+            if (M_T > 0) {
+#pragma unroll
+                for (int i = 1; i <= M_T; i++) a += (in(j + m - i) + in(j + m + i)) * gt.k[i];
+            } else {
+                for (int i = 1; i <= m; i++) a += (in(j + m - i) + in(j + m + i)) * gt.k[i];
+            }
+            out(j, a);
+        }
+    }
+    __device__ __forceinline__ void solve(float g11, float g12, float g22, float h1, float h2, float* u, float* v) const
+    {
+        solve_gauss_px(g11, g12, g22, h1, h2, u, v);
+    }
+};
+
+// ------------------------------------------------------------------------------------------------------------
+// One FarnebackUpdateFlow_Blur sweep (A.6), fused: (2m+1)^2 windowed sum of the 5 M planes -> 2x2 solve -> flow, and
 // (all sweeps but the last) UpdateMatrices with the new flow -> M'.  32x32 pixel tile per 256-thread workgroup.
 //   phase 1  M tile + m-pixel halo (edge-clamped = replicate border) -> LDS, 5 planes, odd row pitch
-//   phase 2  vertical sliding sums, one thread per (plane, column), written back in place
-//   phase 3  horizontal sliding sums, one thread per (plane, row), in place
-//   phase 4  per pixel: scale, solve, store flow; gather R1, store M'
+//   phase 2  vertical windowed sums, one thread per (plane, column), written back in place
+//   phase 3  horizontal windowed sums, one thread per (plane, row), in place
+//   phase 4  per pixel: solve, store flow; gather R1, store M'
 // LDS for winsize 12: 5 x 1996 floats = 39.9 KB -> 4 workgroups (16 waves) per CU.
 // ------------------------------------------------------------------------------------------------------------
 static inline void iter_geometry(int m, int* ext, int* pitch, int* plane)
@@ -1464,16 +1556,15 @@ size_t blur_iter_lds_bytes(int winsize)
     return sizeof(float) * 5 * (size_t)plane;
 }
 
-template <int M_T>
+template <typename Win, int M_T>
 __global__ __launch_bounds__(256) void k_blur_iter_generic(const float* __restrict__ M_in, float* __restrict__ M_out, size_t M_stride,
                                                    const float* __restrict__ R0, const float* __restrict__ R1, size_t R_stride,
-                                                   int w, int h, int m_rt, int pitch, int plane, float scale, int do_update,
+                                                   int w, int h, int m_rt, int pitch, int plane, Win win, int do_update,
                                                    float* __restrict__ flow, size_t f_stride)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int m = M_T > 0 ? M_T : m_rt;
     const int ext = MAV_TILE + 2 * m;
-    const int win = 2 * m + 1;
     const int tid = threadIdx.x;
     const int s = blockIdx.z;
     const int x0 = blockIdx.x * MAV_TILE, y0 = blockIdx.y * MAV_TILE;
@@ -1493,29 +1584,13 @@ __global__ __launch_bounds__(256) void k_blur_iter_generic(const float* __restri
     for (int t = tid; t < 5 * ext; t += 256) {
         const int c = t / ext, lx = t - c * ext;
         float* col = lds + c * plane + lx;
-        float sum = 0.f;
-#pragma unroll
-        for (int k = 0; k < win; k++) sum += col[k * pitch];
-#pragma unroll 8
-        for (int y = 0; y < MAV_TILE; y++) {
-            const float out = sum;
-            if (y < MAV_TILE - 1) sum += col[(y + win) * pitch] - col[y * pitch];
-            col[y * pitch] = out;
-        }
+        win.template sums<M_T, MAV_TILE, false>(m, [&](int i) { return col[i * pitch]; }, [&](int y, float a) { col[y * pitch] = a; });
     }
     __syncthreads();
     for (int t = tid; t < 5 * MAV_TILE; t += 256) {
         const int c = t >> 5, y = t & 31;
         float* row = lds + c * plane + y * pitch;
-        float sum = 0.f;
-#pragma unroll
-        for (int k = 0; k < win; k++) sum += row[k];
-#pragma unroll 8
-        for (int x = 0; x < MAV_TILE; x++) {
-            const float out = sum;
-            if (x < MAV_TILE - 1) sum += row[x + win] - row[x];
-            row[x] = out;
-        }
+        win.template sums<M_T, MAV_TILE, false>(m, [&](int i) { return row[i]; }, [&](int x, float a) { row[x] = a; });
     }
     __syncthreads();
     const float* R0p = R0 + (size_t)s * R_stride;
@@ -1530,10 +1605,8 @@ __global__ __launch_bounds__(256) void k_blur_iter_generic(const float* __restri
         const int gy = y0 + ly;
         if (gx >= w || gy >= h) continue;
         const float* L = lds + ly * pitch + lx;
-        const float g11 = L[0] * scale, g12 = L[plane] * scale, g22 = L[2 * plane] * scale, h1 = L[3 * plane] * scale,
-                    h2 = L[4 * plane] * scale;
         float u, v;
-        solve_px(g11, g12, g22, h1, h2, &u, &v);
+        win.solve(L[0], L[plane], L[2 * plane], L[3 * plane], L[4 * plane], &u, &v);
         *(float2*)(fo + ((size_t)gy * w + gx) * 2) = make_float2(u, v);
         if (do_update) update_px(R0p, R1p, npx, w, h, gx, gy, u, v, Mo);
     }
@@ -1546,11 +1619,11 @@ __global__ __launch_bounds__(256) void k_blur_iter_generic(const float* __restri
 // The kernel is built around memory latency (the v1-v3 profiles showed ~7 serialized round trips per tile):
 //   entry    the R0 values phase C will need are requested first (they depend on nothing)
 //   phase A  one thread per (plane, PAIR of tile columns): the 16+2m rows of its two columns arrive as float2 loads, all
-//            independent and in flight together; vertical sliding sums in registers; only the 16 sums go to LDS
+//            independent and in flight together; vertical windowed sums in registers; only the 16 sums go to LDS
 //   barrier  (the only one)
 //   phase B  one thread per 4 consecutive pixels of a row.  Lanes are assigned by the hardware's ds_read_b128 lane
 //            groups ({0-3,12-15,20-27}, {4-11,16-19,28-31}, +32): each group reads 16 consecutive float4 of ONE row =
-//            all 64 banks once, conflict-free at any pitch.  Horizontal sliding sums, 2x2 solve.  Wave v owns tile rows
+//            all 64 banks once, conflict-free at any pitch.  Horizontal windowed sums, 2x2 solve.  Wave v owns tile rows
 //            4v..4v+3 in phases B and C, and nobody else reads those LDS rows, so it parks its flow in the rows of planes
 //            0/1 it has just finished reading: no second barrier, no extra LDS.
 //   phase C  UpdateMatrices with lane = pixel column (64 consecutive pixels per wave): the R1 gathers of two pixels
@@ -1630,16 +1703,15 @@ struct __attribute__((packed, aligned(4))) F2U { float x, y; };     // two adjac
 // neighbour on the other stream has to share; alone on one stream (one pair per call) the same stores cost 3 % (0.305 vs 0.297 ms
 // per 1280x720 pair), so launch_blur_iter's callers ask for it in the two-stream schedules only.  Write-through for the initial M
 // (k_update_matrices) and for the expansions (k_polyexp) was measured too: -0.7 % and +-0.
-template <int M_T, bool AL = true, bool WT = false>
+template <typename Win, int M_T, bool AL, bool WT>
 __global__ __launch_bounds__(256) void k_blur_iter_fast(const float* __restrict__ M_in, float* __restrict__ M_out,
                                                         size_t M_stride, const float* __restrict__ R0,
                                                         const float* __restrict__ R1, size_t R_stride, int w, int h,
-                                                        TileMap tm, float scale,
+                                                        TileMap tm, Win win,
                                                         int do_update, int store_flow, float* __restrict__ flow, size_t f_stride)
 {
     constexpr int EXT_X = FT_X + 2 * M_T;              // 76
     constexpr int EXT_Y = FT_Y + 2 * M_T;              // 28
-    constexpr int WIN = 2 * M_T + 1;                   // 13
     constexpr int PITCH = (EXT_X + 3) & ~3;            // 76
     constexpr int PLANE = FT_Y * PITCH + (EXT_X - (FT_Y * PITCH) % 32 + 64) % 32;   // = EXT_X (mod 32): phase-A lanes stay on distinct banks across planes
     static_assert(PLANE % 4 == 0 && EXT_X % 2 == 0, "plane must keep 16-byte alignment");
@@ -1682,16 +1754,7 @@ __global__ __launch_bounds__(256) void k_blur_iter_fast(const float* __restrict_
                 else { const F2U t = *(const F2U*)pp; v[i] = make_float2(t.x, t.y); }
             }
             float* out = vs + c * PLANE + 2 * pr;
-            float sx = 0.f, sy = 0.f;
-#pragma unroll
-            for (int i = 0; i < WIN; i++) { sx += v[i].x; sy += v[i].y; }
-            *(float2*)out = make_float2(sx, sy);
-#pragma unroll
-            for (int y = 1; y < FT_Y; y++) {
-                sx += v[y + WIN - 1].x - v[y - 1].x;
-                sy += v[y + WIN - 1].y - v[y - 1].y;
-                *(float2*)(out + y * PITCH) = make_float2(sx, sy);
-            }
+            win.template sums<M_T, FT_Y, true>(M_T, [&](int i) { return v[i]; }, [&](int y, float2 a) { *(float2*)(out + y * PITCH) = a; });
         }
     } else {                                           // tiles touching the left/right image edge: clamped scalar columns
         for (int t = tid; t < 5 * EXT_X; t += 256) {
@@ -1702,15 +1765,7 @@ __global__ __launch_bounds__(256) void k_blur_iter_fast(const float* __restrict_
 #pragma unroll
             for (int i = 0; i < EXT_Y; i++) v[i] = col[(size_t)clampi(y0 - M_T + i, 0, h - 1) * w];
             float* out = vs + c * PLANE + lx;
-            float sum = 0.f;
-#pragma unroll
-            for (int i = 0; i < WIN; i++) sum += v[i];
-            out[0] = sum;
-#pragma unroll
-            for (int y = 1; y < FT_Y; y++) {
-                sum += v[y + WIN - 1] - v[y - 1];
-                out[y * PITCH] = sum;
-            }
+            win.template sums<M_T, FT_Y, true>(M_T, [&](int i) { return v[i]; }, [&](int y, float a) { out[y * PITCH] = a; });
         }
     }
     STAMP(ts1);
@@ -1737,20 +1792,11 @@ __global__ __launch_bounds__(256) void k_blur_iter_fast(const float* __restrict_
                 const float4 t4 = p[k];
                 f[4 * k] = t4.x; f[4 * k + 1] = t4.y; f[4 * k + 2] = t4.z; f[4 * k + 3] = t4.w;
             }
-            float a = 0.f;
-#pragma unroll
-            for (int k = 0; k < WIN; k++) a += f[k];
-            S[c][0] = a;
-#pragma unroll
-            for (int j = 1; j < 4; j++) {
-                a += f[j + WIN - 1] - f[j - 1];
-                S[c][j] = a;
-            }
+            win.template sums<M_T, 4, true>(M_T, [&](int i) { return f[i]; }, [&](int j, float a) { S[c][j] = a; });
         }
         float u[4], v[4];
 #pragma unroll
-        for (int j = 0; j < 4; j++)
-            solve_px(S[0][j] * scale, S[1][j] * scale, S[2][j] * scale, S[3][j] * scale, S[4][j] * scale, &u[j], &v[j]);
+        for (int j = 0; j < 4; j++) win.solve(S[0][j], S[1][j], S[2][j], S[3][j], S[4][j], &u[j], &v[j]);
         if (store_flow && gx < w && gy < h) {
             float* fo = flow + (size_t)s * f_stride + ((size_t)gy * w + gx) * 2;
             if (AL) {                                        // w % 4 == 0: the 4 pixels are all inside or all outside
@@ -1807,265 +1853,6 @@ __global__ __launch_bounds__(256) void k_blur_iter_fast(const float* __restrict_
     STAMP_ADD(0, ts0, ts1); STAMP_ADD(1, ts1, ts2); STAMP_ADD(2, ts2, ts3); STAMP_ADD(4, ts3, ts4); STAMP_ADD(6, ts0, ts4); STAMP_ADD(7, 0ull, 1ull);
 }
 
-// ------------------------------------------------------------------------------------------------------------
-// The sweep with a Gaussian window (OPTFLOW_FARNEBACK_GAUSSIAN; FarnebackUpdateFlow_GaussianBlur): sibling kernels of the two box
-// forms above -- same tiles, same m-pixel halo, same launch geometry, same bytes in and out -- so the box kernels compile exactly as
-// they did without them.  The two sliding box sums become two (2m+1)-tap weighted sums, everything in float32, nothing fused, one
-// fixed order per pixel (tests/gauss_window_ref.py restates it in numpy; the kernels equal it bit for bit):
-//   V(y, x) = M(y, x) k0;  for i = 1..m:  V += (M(max(y - i, 0), x) + M(min(y + i, h - 1), x)) k_i
-//   S(y, x) = V(y, x) k0;  for i = 1..m:  S += (V(y, max(x - i, 0)) + V(y, min(x + i, w - 1))) k_i
-// The taps do not sum to 1 and there is no 1 / winsize^2 scale.  Phases, LDS layout and the barrier are those of the box forms:
-// what changes is the arithmetic of the two passes (19 operations per output and plane at m = 6 against the sliding sums' 2).
-// ------------------------------------------------------------------------------------------------------------
-void gauss_taps(int winsize, GaussTaps* out)
-{
-    const int m = winsize / 2;
-    const double sigma = m * 0.3;
-    float t[MAV_MAX_WIN_HALF + 1];
-    double s = 1.;                                     // as the CPU code has it: starts at 1, and the centre tap counts twice too
-    for (int i = 0; i <= m; i++) {
-        t[i] = (float)exp(-i * i / (2 * sigma * sigma));
-        s += t[i] * 2;
-    }
-    s = 1. / s;
-    for (int i = 0; i <= MAV_MAX_WIN_HALF; i++) out->k[i] = i <= m ? (float)(t[i] * s) : 0.f;
-}
-
-// one weighted sum: centre c and the taps' pairs at c -+ i * step, in the order every form uses
-template <int M_T>
-static __device__ __forceinline__ float gauss_sum(const float* p, int step, int m_rt, const GaussTaps& gt)
-{
-#pragma clang fp contract(off)
-    const int m = M_T > 0 ? M_T : m_rt;
-    float a = p[0] * gt.k[0];
-    if (M_T > 0) {
-#pragma unroll
-        for (int i = 1; i <= M_T; i++) a += (p[-i * step] + p[i * step]) * gt.k[i];
-    } else {
-        for (int i = 1; i <= m; i++) a += (p[-i * step] + p[i * step]) * gt.k[i];
-    }
-    return a;
-}
-
-// the 2x2 solve as the Gaussian CPU path has it: products and differences in float32, the regularised reciprocal and the final
-// product in double.  (solve_px above is the box path's, which sums in double on the CPU.)
-static __device__ __forceinline__ void solve_gauss_px(float g11, float g12, float g22, float h1, float h2, float* u, float* v)
-{
-#pragma clang fp contract(off)
-    const float d = g11 * g22 - g12 * g12;
-    const double idet = 1.0 / ((double)d + 1e-3);
-    *u = (float)((double)(g11 * h2 - g12 * h1) * idet);
-    *v = (float)((double)(g22 * h1 - g12 * h2) * idet);
-}
-
-template <int M_T>
-__global__ __launch_bounds__(256) void k_gauss_iter_generic(const float* __restrict__ M_in, float* __restrict__ M_out, size_t M_stride,
-                                                            const float* __restrict__ R0, const float* __restrict__ R1, size_t R_stride,
-                                                            int w, int h, int m_rt, int pitch, int plane, GaussTaps gt, int do_update,
-                                                            float* __restrict__ flow, size_t f_stride)
-{
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int m = M_T > 0 ? M_T : m_rt;
-    const int ext = MAV_TILE + 2 * m;
-    const int tid = threadIdx.x;
-    const int s = blockIdx.z;
-    const int x0 = blockIdx.x * MAV_TILE, y0 = blockIdx.y * MAV_TILE;
-    const size_t npx = (size_t)w * h;
-    const float* Min = M_in + (size_t)s * M_stride;
-
-    for (int c = 0; c < 5; c++) {
-        const float* P = Min + c * npx;
-        float* L = lds + c * plane;
-        for (int i = tid; i < ext * ext; i += 256) {
-            const int ly = i / ext, lx = i - ly * ext;
-            const int gx = clampi(x0 - m + lx, 0, w - 1), gy = clampi(y0 - m + ly, 0, h - 1);
-            L[ly * pitch + lx] = P[(size_t)gy * w + gx];
-        }
-    }
-    __syncthreads();
-    // vertical sums in place: output row y reads rows y .. y + 2m and is stored at row y, which no later output reads
-    for (int t = tid; t < 5 * ext; t += 256) {
-        const int c = t / ext, lx = t - c * ext;
-        float* col = lds + c * plane + lx;
-        for (int y = 0; y < MAV_TILE; y++) col[y * pitch] = gauss_sum<M_T>(col + (y + m) * pitch, pitch, m, gt);
-    }
-    __syncthreads();
-    for (int t = tid; t < 5 * MAV_TILE; t += 256) {
-        const int c = t >> 5, y = t & 31;
-        float* row = lds + c * plane + y * pitch;
-        for (int x = 0; x < MAV_TILE; x++) row[x] = gauss_sum<M_T>(row + x + m, 1, m, gt);
-    }
-    __syncthreads();
-    const float* R0p = R0 + (size_t)s * R_stride;
-    const float* R1p = R1 + (size_t)s * R_stride;
-    float* Mo = M_out + (size_t)s * M_stride;
-    float* fo = flow + (size_t)s * f_stride;
-    const int lx = tid & 31;
-    const int gx = x0 + lx;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int ly = (tid >> 5) + 8 * j;
-        const int gy = y0 + ly;
-        if (gx >= w || gy >= h) continue;
-        const float* L = lds + ly * pitch + lx;
-        float u, v;
-        solve_gauss_px(L[0], L[plane], L[2 * plane], L[3 * plane], L[4 * plane], &u, &v);
-        *(float2*)(fo + ((size_t)gy * w + gx) * 2) = make_float2(u, v);
-        if (do_update) update_px(R0p, R1p, npx, w, h, gx, gy, u, v, Mo);
-    }
-}
-
-// The fast form (see k_blur_iter_fast for the tile, the lane assignment and the single barrier): phase A takes its 13-tap vertical
-// sums from the 28 rows a thread already holds in registers, phase B its horizontal sums from the 16 floats it reads from LDS.
-template <int M_T, bool AL = true, bool WT = false>
-__global__ __launch_bounds__(256) void k_gauss_iter_fast(const float* __restrict__ M_in, float* __restrict__ M_out,
-                                                         size_t M_stride, const float* __restrict__ R0,
-                                                         const float* __restrict__ R1, size_t R_stride, int w, int h,
-                                                         TileMap tm, GaussTaps gt,
-                                                         int do_update, int store_flow, float* __restrict__ flow, size_t f_stride)
-{
-#pragma clang fp contract(off)
-    constexpr int EXT_X = FT_X + 2 * M_T;
-    constexpr int EXT_Y = FT_Y + 2 * M_T;
-    constexpr int PITCH = (EXT_X + 3) & ~3;
-    constexpr int PLANE = FT_Y * PITCH + (EXT_X - (FT_Y * PITCH) % 32 + 64) % 32;
-    static_assert(PLANE % 4 == 0 && EXT_X % 2 == 0, "plane must keep 16-byte alignment");
-    __shared__ __attribute__((aligned(16))) float vs[5 * PLANE];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wv = tid >> 6;
-    int s, tx, ty;
-    if (!tile_of_block(tm, &s, &tx, &ty)) return;
-    const int x0 = tx * FT_X, y0 = ty * FT_Y;
-    const size_t npx = (size_t)w * h;
-    const float* Min = M_in + (size_t)s * M_stride;
-    const float* R0p = R0 + (size_t)s * R_stride;
-    const float* R1p = R1 + (size_t)s * R_stride;
-
-    float q[4][5];
-    int gys[4];
-    const int gxc = min(x0 + lane, w - 1);
-    if (do_update) {
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            gys[j] = min(y0 + wv * 4 + j, h - 1);
-            const size_t idx = (size_t)gys[j] * w + gxc;
-#pragma unroll
-            for (int c = 0; c < 5; c++) q[j][c] = R0p[c * npx + idx];
-        }
-    }
-
-    if (x0 >= M_T && x0 + FT_X + M_T <= w) {
-        constexpr int NP = EXT_X / 2;
-        for (int t = tid; t < 5 * NP; t += 256) {
-            const int c = t / NP, pr = t - c * NP;
-            const float* col = Min + c * npx + (x0 - M_T + 2 * pr);
-            float2 v[EXT_Y];
-#pragma unroll
-            for (int i = 0; i < EXT_Y; i++) {
-                const float* pp = col + (size_t)clampi(y0 - M_T + i, 0, h - 1) * w;
-                if (AL) v[i] = *(const float2*)pp;
-                else { const F2U t = *(const F2U*)pp; v[i] = make_float2(t.x, t.y); }
-            }
-            float* out = vs + c * PLANE + 2 * pr;
-#pragma unroll
-            for (int y = 0; y < FT_Y; y++) {
-                float sx = v[y + M_T].x * gt.k[0], sy = v[y + M_T].y * gt.k[0];
-#pragma unroll
-                for (int i = 1; i <= M_T; i++) {
-                    sx += (v[y + M_T - i].x + v[y + M_T + i].x) * gt.k[i];
-                    sy += (v[y + M_T - i].y + v[y + M_T + i].y) * gt.k[i];
-                }
-                *(float2*)(out + y * PITCH) = make_float2(sx, sy);
-            }
-        }
-    } else {
-        for (int t = tid; t < 5 * EXT_X; t += 256) {
-            const int c = t / EXT_X, lx = t - c * EXT_X;
-            const int gx = clampi(x0 - M_T + lx, 0, w - 1);
-            const float* col = Min + c * npx + gx;
-            float v[EXT_Y];
-#pragma unroll
-            for (int i = 0; i < EXT_Y; i++) v[i] = col[(size_t)clampi(y0 - M_T + i, 0, h - 1) * w];
-            float* out = vs + c * PLANE + lx;
-#pragma unroll
-            for (int y = 0; y < FT_Y; y++) out[y * PITCH] = gauss_sum<M_T>(v + y + M_T, 1, M_T, gt);
-        }
-    }
-    __syncthreads();
-
-    {
-        const int quad = (lane & 31) >> 2;
-        const int grp = (lane >> 5) * 2 + ((quad == 1 || quad == 2 || quad == 4 || quad == 7) ? 1 : 0);
-        const int qpos = (quad == 0 || quad == 1) ? 0 : ((quad == 3 || quad == 2) ? 1 : ((quad == 5 || quad == 4) ? 2 : 3));
-        const int pos = qpos * 4 + (lane & 3);
-        const int ly = wv * 4 + grp;
-        const int lx0 = pos * 4;
-        const int gx = x0 + lx0, gy = y0 + ly;
-        float S[5][4];
-#pragma unroll
-        for (int c = 0; c < 5; c++) {
-            const float4* p = (const float4*)(vs + c * PLANE + ly * PITCH + lx0);
-            constexpr int NV = (4 + 2 * M_T + 3) / 4;
-            float f[4 * NV];
-#pragma unroll
-            for (int k = 0; k < NV; k++) {
-                const float4 t4 = p[k];
-                f[4 * k] = t4.x; f[4 * k + 1] = t4.y; f[4 * k + 2] = t4.z; f[4 * k + 3] = t4.w;
-            }
-#pragma unroll
-            for (int j = 0; j < 4; j++) S[c][j] = gauss_sum<M_T>(f + j + M_T, 1, M_T, gt);
-        }
-        float u[4], v[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) solve_gauss_px(S[0][j], S[1][j], S[2][j], S[3][j], S[4][j], &u[j], &v[j]);
-        if (store_flow && gx < w && gy < h) {
-            float* fo = flow + (size_t)s * f_stride + ((size_t)gy * w + gx) * 2;
-            if (AL) {
-                *(float4*)fo = make_float4(u[0], v[0], u[1], v[1]);
-                *(float4*)(fo + 4) = make_float4(u[2], v[2], u[3], v[3]);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    if (gx + j < w) *(float2*)(fo + 2 * j) = make_float2(u[j], v[j]);
-            }
-        }
-        if (!do_update) return;
-        *(float4*)(vs + ly * PITCH + lx0) = make_float4(u[0], u[1], u[2], u[3]);
-        *(float4*)(vs + PLANE + ly * PITCH + lx0) = make_float4(v[0], v[1], v[2], v[3]);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-    float* Mo = M_out + (size_t)s * M_stride;
-    const bool colok = x0 + lane < w;
-#pragma unroll
-    for (int jb = 0; jb < 4; jb += 2) {
-        GatherPx g[2];
-        float fu[2], fv[2];
-#pragma unroll
-        for (int jj = 0; jj < 2; jj++) {
-            const int ly = wv * 4 + jb + jj;
-            fu[jj] = vs[ly * PITCH + lane];
-            fv[jj] = vs[PLANE + ly * PITCH + lane];
-            gather_issue(R1p, npx, w, h, gxc, gys[jb + jj], fu[jj], fv[jj], g[jj]);
-        }
-#pragma unroll
-        for (int jj = 0; jj < 2; jj++) {
-            float o[5];
-            update_finish(q[jb + jj], g[jj], w, h, gxc, gys[jb + jj], fu[jj], fv[jj], o);
-            if (colok && y0 + wv * 4 + jb + jj < h) {
-                const size_t idx = (size_t)gys[jb + jj] * w + gxc;
-#pragma unroll
-                for (int c = 0; c < 5; c++) {
-                    if constexpr (WT) __hip_atomic_store((unsigned*)(Mo + c * npx + idx), __float_as_uint(o[c]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    else Mo[c * npx + idx] = o[c];
-                }
-            }
-        }
-    }
-}
-
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 int blur_iter_tile_rows(int h) { return (h + FT_Y - 1) / FT_Y; }
 static bool blur_iter_vec_ok(int w, size_t M_stride, size_t R_stride, size_t f_stride, const void* M_in, const void* M_out, const void* R0,
@@ -2080,87 +1867,57 @@ bool blur_iter_bands_ok(int w, int winsize, size_t M_stride, size_t R_stride, si
     return winsize / 2 == 6 && blur_iter_vec_ok(w, M_stride, R_stride, f_stride, M_in, M_out, R0, R1, flow);
 }
 
-// The Gaussian window: the dispatch of launch_blur_iter below, form for form, onto the sibling kernels.
-static void launch_gauss_iter(hipStream_t st, const float* M_in, float* M_out, size_t M_stride, const float* R0, const float* R1,
-                              size_t R_stride, int G, int w, int h, int winsize, int do_update, int store_flow, float* flow, size_t f_stride,
-                              int ty0, int ty1, int strip, bool write_through, const GaussTaps& gt)
+// the fast form's launch; wt: M' through write-through stores
+template <typename Win, bool AL>
+static void launch_sweep_fast(hipStream_t st, const TileMap& tm, bool wt, const float* M_in, float* M_out, size_t M_stride, const float* R0,
+                              const float* R1, size_t R_stride, int w, int h, const Win& win, int do_update, int store_flow, float* flow,
+                              size_t f_stride)
 {
-    int ext, pitch, plane;
+    const auto k = wt ? k_blur_iter_fast<Win, 6, AL, true> : k_blur_iter_fast<Win, 6, AL, false>;
+    hipLaunchKernelGGL(k, dim3(tile_grid(tm)), dim3(256), 0, st, M_in, M_out, M_stride, R0, R1, R_stride, w, h, tm, win, do_update,
+                       store_flow, flow, f_stride);
+}
+
+// One sweep launch of either window, three tiers: the fast form as written (AL), its relaxed form for any width / alignment, the
+// generic form.
+template <typename Win>
+static void launch_sweep(hipStream_t st, const float* M_in, float* M_out, size_t M_stride, const float* R0, const float* R1,
+                         size_t R_stride, int G, int w, int h, int winsize, int do_update, int store_flow, float* flow, size_t f_stride,
+                         int ty0, int ty1, int strip, bool write_through, const Win& win)
+{
     const int m = winsize / 2;
-    dim3 grid((w + MAV_TILE - 1) / MAV_TILE, (h + MAV_TILE - 1) / MAV_TILE, G);
-    const bool vec_ok = blur_iter_vec_ok(w, M_stride, R_stride, f_stride, M_in, M_out, R0, R1, flow);
-    if (m == 6 && vec_ok) {
+    const bool wt = write_through && do_update;
+    if (m == 6 && blur_iter_vec_ok(w, M_stride, R_stride, f_stride, M_in, M_out, R0, R1, flow)) {
         const TileMap tm = make_tile_map(w, h, G, FT_X, FT_Y, ty0, ty1, strip);
         if (tm.n_tiles == 0) return;
-        if (write_through && do_update)
-            hipLaunchKernelGGL((k_gauss_iter_fast<6, true, true>), dim3(tile_grid(tm)), dim3(256), 0, st, M_in, M_out, M_stride, R0, R1, R_stride, w,
-                               h, tm, gt, do_update, store_flow, flow, f_stride);
-        else
-            hipLaunchKernelGGL(k_gauss_iter_fast<6>, dim3(tile_grid(tm)), dim3(256), 0, st, M_in, M_out, M_stride, R0, R1, R_stride, w, h,
-                               tm, gt, do_update, store_flow, flow, f_stride);
-        return;
+        return launch_sweep_fast<Win, true>(st, tm, wt, M_in, M_out, M_stride, R0, R1, R_stride, w, h, win, do_update, store_flow, flow, f_stride);
     }
-    if (m == 6 && f_stride % 2 == 0 && ((uintptr_t)flow & 7) == 0) {
+    if (m == 6 && f_stride % 2 == 0 && ((uintptr_t)flow & 7) == 0) {    // any width / alignment: relaxed form of the same kernel
         const TileMap tm = make_tile_map(w, h, G, FT_X, FT_Y, 0, -1, strip);
-        if (write_through && do_update)
-            hipLaunchKernelGGL((k_gauss_iter_fast<6, false, true>), dim3(tile_grid(tm)), dim3(256), 0, st, M_in, M_out, M_stride, R0, R1, R_stride,
-                               w, h, tm, gt, do_update, store_flow, flow, f_stride);
-        else
-            hipLaunchKernelGGL((k_gauss_iter_fast<6, false>), dim3(tile_grid(tm)), dim3(256), 0, st, M_in, M_out, M_stride, R0, R1, R_stride,
-                               w, h, tm, gt, do_update, store_flow, flow, f_stride);
-        return;
+        return launch_sweep_fast<Win, false>(st, tm, wt, M_in, M_out, M_stride, R0, R1, R_stride, w, h, win, do_update, store_flow, flow, f_stride);
     }
+    int ext, pitch, plane;
     iter_geometry(m, &ext, &pitch, &plane);
     const size_t lds = sizeof(float) * 5 * (size_t)plane;
-    if (m == 6)
-        hipLaunchKernelGGL(k_gauss_iter_generic<6>, grid, dim3(256), lds, st, M_in, M_out, M_stride, R0, R1, R_stride, w, h, m,
-                           pitch, plane, gt, do_update, flow, f_stride);
-    else
-        hipLaunchKernelGGL(k_gauss_iter_generic<0>, grid, dim3(256), lds, st, M_in, M_out, M_stride, R0, R1, R_stride, w, h, m,
-                           pitch, plane, gt, do_update, flow, f_stride);
+    const dim3 grid((w + MAV_TILE - 1) / MAV_TILE, (h + MAV_TILE - 1) / MAV_TILE, G);
+    // m != 6: dynamic LDS above the default limit was granted by blur_iter_prepare() when the context was created
+    const auto k = m == 6 ? k_blur_iter_generic<Win, 6> : k_blur_iter_generic<Win, 0>;
+    hipLaunchKernelGGL(k, grid, dim3(256), lds, st, M_in, M_out, M_stride, R0, R1, R_stride, w, h, m, pitch, plane, win, do_update, flow,
+                       f_stride);
 }
 
 // tile rows [ty0, ty1) only (ty1 < 0: the whole layer).  Band launches exist for the fast form only (blur_iter_bands_ok).
+// gauss: the taps of the Gaussian window, or nullptr for the box window.
 void launch_blur_iter(hipStream_t st, const float* M_in, float* M_out, size_t M_stride, const float* R0, const float* R1,
                       size_t R_stride, int G, int w, int h, int winsize, int do_update, int store_flow, float* flow, size_t f_stride,
                       int ty0, int ty1, int strip, bool write_through, const GaussTaps* gauss)
 {
-    if (gauss) return launch_gauss_iter(st, M_in, M_out, M_stride, R0, R1, R_stride, G, w, h, winsize, do_update, store_flow, flow, f_stride,
-                                        ty0, ty1, strip, write_through, *gauss);
-    int ext, pitch, plane;
-    const int m = winsize / 2;
-    const float scale = (float)(1.0 / ((double)winsize * winsize));
-    dim3 grid((w + MAV_TILE - 1) / MAV_TILE, (h + MAV_TILE - 1) / MAV_TILE, G);
-    const bool vec_ok = blur_iter_vec_ok(w, M_stride, R_stride, f_stride, M_in, M_out, R0, R1, flow);
-    if (m == 6 && vec_ok) {
-        const TileMap tm = make_tile_map(w, h, G, FT_X, FT_Y, ty0, ty1, strip);
-        if (tm.n_tiles == 0) return;
-        if (write_through && do_update)
-            hipLaunchKernelGGL((k_blur_iter_fast<6, true, true>), dim3(tile_grid(tm)), dim3(256), 0, st, M_in, M_out, M_stride, R0, R1, R_stride, w,
-                               h, tm, scale, do_update, store_flow, flow, f_stride);
-        else
-            hipLaunchKernelGGL(k_blur_iter_fast<6>, dim3(tile_grid(tm)), dim3(256), 0, st, M_in, M_out, M_stride, R0, R1, R_stride, w, h,
-                               tm, scale, do_update, store_flow, flow, f_stride);
-        return;
-    }
-    if (m == 6 && f_stride % 2 == 0 && ((uintptr_t)flow & 7) == 0) {    // any width / alignment: relaxed form of the same kernel
-        const TileMap tm = make_tile_map(w, h, G, FT_X, FT_Y, 0, -1, strip);
-        if (write_through && do_update)
-            hipLaunchKernelGGL((k_blur_iter_fast<6, false, true>), dim3(tile_grid(tm)), dim3(256), 0, st, M_in, M_out, M_stride, R0, R1, R_stride,
-                               w, h, tm, scale, do_update, store_flow, flow, f_stride);
-        else
-            hipLaunchKernelGGL((k_blur_iter_fast<6, false>), dim3(tile_grid(tm)), dim3(256), 0, st, M_in, M_out, M_stride, R0, R1, R_stride,
-                               w, h, tm, scale, do_update, store_flow, flow, f_stride);
-        return;
-    }
-    iter_geometry(m, &ext, &pitch, &plane);
-    const size_t lds = sizeof(float) * 5 * (size_t)plane;
-    if (m == 6)
-        hipLaunchKernelGGL(k_blur_iter_generic<6>, grid, dim3(256), lds, st, M_in, M_out, M_stride, R0, R1, R_stride, w, h, m,
-                           pitch, plane, scale, do_update, flow, f_stride);
-    else       // dynamic LDS above the default limit was granted by blur_iter_prepare() when the context was created
-        hipLaunchKernelGGL(k_blur_iter_generic<0>, grid, dim3(256), lds, st, M_in, M_out, M_stride, R0, R1, R_stride, w, h, m,
-                           pitch, plane, scale, do_update, flow, f_stride);
+    if (gauss)
+        launch_sweep(st, M_in, M_out, M_stride, R0, R1, R_stride, G, w, h, winsize, do_update, store_flow, flow, f_stride, ty0, ty1, strip,
+                     write_through, GaussWindow{*gauss});
+    else
+        launch_sweep(st, M_in, M_out, M_stride, R0, R1, R_stride, G, w, h, winsize, do_update, store_flow, flow, f_stride, ty0, ty1, strip,
+                     write_through, BoxWindow{(float)(1.0 / ((double)winsize * winsize))});
 }
 
 // The general-winsize sweep needs 5 x (32 + 2m)^2 floats of dynamic LDS; above the 64 KB default a kernel must be granted
@@ -2169,8 +1926,8 @@ const char* blur_iter_prepare(int winsize)
 {
     const size_t lds = blur_iter_lds_bytes(winsize);
     if (lds <= (size_t)64 * 1024) return nullptr;
-    hipError_t e = hipFuncSetAttribute((const void*)k_blur_iter_generic<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_gauss_iter_generic<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute((const void*)k_blur_iter_generic<BoxWindow, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_blur_iter_generic<GaussWindow, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }
 

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE -- the Gaussian-window sweep (cv2.OPTFLOW_FARNEBACK_GAUSSIAN, FarnebackUpdateFlow_GaussianBlur) restated in
-numpy, operation for operation as the library's kernels compute it (kernels_flow.hip k_gauss_iter_fast / k_gauss_iter_generic):
+numpy, operation for operation as the library's kernels compute it (kernels_flow.hip GaussWindow, the window policy of k_blur_iter_fast / k_blur_iter_generic):
 float32 everywhere, no fused multiply-add, one fixed order per pixel, and the solve's mixed widths.  The kernels are held to this
 file bit for bit (tests/test_gpu_gauss_window.py).
 

@@ -15,20 +15,12 @@ import numpy as np
 import pytest
 
 import gauss_window_ref as gw
-from stage_cases import CASES, FORMS, crafted_flow, images, smooth_flow, sweep_lds_bytes
+from stage_cases import CASES, FORMS, crafted_flow, images, smooth_flow, sweep_form
 
 pytestmark = pytest.mark.gpu
 
 STAGE_CASES = [c for c in CASES if (c.W, c.H) not in ((1920, 1080), (3840, 2160))]
 STAGE_IDS = [c.name for c in STAGE_CASES]
-
-
-def _sweep_form(w: int, winsize: int) -> str:
-    """kernels_flow.hip launch_gauss_iter's dispatch (the box dispatch, form for form; stage_cases.sweep_form, copied on purpose:
-    this file must notice when the Gaussian dispatch stops following it)."""
-    if winsize // 2 == 6:
-        return "fast<6>" if w % 4 == 0 else "fast<6,false>"
-    return "generic<0>+lds>64K" if sweep_lds_bytes(winsize) > 64 * 1024 else "generic<0>"
 
 
 def soa(a):
@@ -41,7 +33,7 @@ def test_stage_cases_reach_every_testable_form(mav):
     reached = set()
     for case in STAGE_CASES:
         with _lib.Context(case.W, case.H, 1, case.fb(), window="gaussian") as ctx:
-            reached |= {_sweep_form(ctx.layer_dims(k)[0], case.winsize) for k in range(ctx.num_layers())}
+            reached |= {sweep_form(ctx.layer_dims(k)[0], case.winsize) for k in range(ctx.num_layers())}
     assert reached == FORMS["sweep"], reached
 
 
@@ -58,7 +50,7 @@ def test_sweep_bit_for_bit(mav, fb_oracle, case):
             w, h, sigma, ks = ctx.layer_dims(k)
             R = [fb_oracle.polyexp(fb_oracle.blur_resize(img, w, h, ks, sigma), case.poly_n, case.poly_sigma) for img in imgs]
             R0, R1 = soa(R[0]), soa(R[1])
-            form = _sweep_form(w, case.winsize)
+            form = sweep_form(w, case.winsize)
             for tag, flow in (("smooth", smooth_flow(w, h)), ("crafted", crafted_flow(w, h))):
                 M = fb_oracle.update_matrices(R[0], R[1], flow)
                 want = gw.sweep(M, case.winsize)

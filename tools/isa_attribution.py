@@ -2,7 +2,7 @@
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -gline-tables-only -I include -S --cuda-device-only \\
           -o /tmp/kernels_flow.s mav-detection_amd/csrc/kernels_flow.hip
-    python tools/isa_attribution.py /tmp/kernels_flow.s _Z16k_blur_iter_fastILi6ELb1ELb1EE
+    python tools/isa_attribution.py /tmp/kernels_flow.s _Z16k_blur_iter_fastI9BoxWindowLi6ELb1ELb1EE
 
 Every instruction between the kernel's label and its s_endpgm is assigned to the source line of the last `.loc` directive in front of
 it (the innermost inlined frame, as the assembler prints it) and counted per region of kernels_flow.hip and per class: scalar ALU / moves
@@ -19,6 +19,7 @@ REGIONS = [                                   # (first line, last line, name) in
     ("col_interior", "column pass, interior tile (float2 columns, 28 clamped row addresses)"),
     ("col_edge", "column pass, tiles on the left / right image edge (scalar columns)"),
     ("row_solve", "row pass from LDS + 2x2 solve + flow store / park"),
+    ("window", "window policy: the windowed sums of both passes, the solve's scale (BoxWindow / GaussWindow)"),
     ("update", "update phase: gather R1 (gather_issue), UpdateMatrices (update_finish), M' stores"),
 ]
 
@@ -42,6 +43,8 @@ def region_lines(src):
     r["gather_issue"] = (find("void gather_issue("), find("void update_finish(") - 1)
     r["update_finish"] = (find("void update_finish("), find("struct __attribute__((packed, aligned(4))) F2U") - 1)
     r["solve_px"] = (find("void solve_px("), find("float2 upsample_flow(") - 1)
+    r["window"] = (find("struct BoxWindow {"), find("void iter_geometry(") - 1)
+    r["solve_gauss_px"] = (find("void solve_gauss_px("), find("struct GaussWindow {") - 1)
     r["clampi"] = (find("int clampi("), find("int clampi("))
     return r, k
 
@@ -67,7 +70,7 @@ def classify(op):
 import os
 SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mav-detection_amd", "csrc", "kernels_flow.hip")
 R, kline = region_lines(SRC)
-fold = {"gather_issue": "update", "update_finish": "update", "solve_px": "row_solve"}
+fold = {"gather_issue": "update", "update_finish": "update", "solve_px": "row_solve", "solve_gauss_px": "row_solve"}
 counts, classes = {}, ["s_alu/mov", "s_waitcnt", "s_branch/barrier/nop", "s_load", "v_alu", "vmem", "lds", "other"]
 files = {}
 inside, line, fileno = False, 0, 0
@@ -102,7 +105,7 @@ for raw in open(path):
             reg = "col_interior(clampi)"
         reg = fold.get(reg, reg)
     else:
-        reg = "hip headers (min / floorf / fmaf / shuffles)"
+        reg = "hip headers (min / floorf / fmaf / shuffles / float2 operators)"
     counts.setdefault(reg, dict.fromkeys(classes, 0))[classify(op)] += 1
 
 print(f"{sym}: static instruction counts by source region ({os.path.basename(SRC)}, kernel at line {kline})")
