@@ -137,7 +137,8 @@ int mav_device_count(void);       /* <= 0 when no GPU is visible */
  *                      The runtime keeps a pool of hardware queues per priority class and hands a new stream the least-used queue of its
  *                      class: which queue a lane gets otherwise depends on every stream the process has ever made (one idle context created
  *                      before three lanes: 0.31 instead of 0.215 ms per 1280x720 frame).  Lanes take a class of their own
- * None of them changes a result bit (tests/test_gpu_flow.py, tests/test_gpu_screen.py). */
+ * None of them changes a result bit (tests/test_gpu_flow.py, tests/test_gpu_screen.py; "phi_yloop" and "phi_screen":
+ * tests/test_gpu_detect_forms.py). */
 int mav_set_option(mav_ctx*, const char* name, long value);
 int mav_get_option(mav_ctx*, const char* name, long* value);
 /* The sweep's window: MAV_WINDOW_BOX (default; cv2's default flags) or MAV_WINDOW_GAUSSIAN (cv2's OPTFLOW_FARNEBACK_GAUSSIAN:
