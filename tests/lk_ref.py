@@ -10,6 +10,9 @@ import numpy as np
 F = np.float32
 W_BITS = 14
 HIST_BINS = 104
+# the ways a point leaves a level of the tracker: the first bounds test, the minimum-eigenvalue test, the bounds test of an iteration,
+# |delta| <= epsilon, the oscillation rule, the iteration count (max-count-0: a count of 0, the loop never runs)
+EXITS = ("outside-first", "min-eig", "outside-iter", "eps", "oscillation", "max-count", "max-count-0")
 
 
 def reflect101(p, n):
@@ -159,9 +162,12 @@ def _window(img, ix, iy, win, wts, shift, zero_outside):
     return (v + (1 << (shift - 1))) >> shift
 
 
-def lk_track(prev, nxt, pts, win=(21, 21), max_level=3, max_count=30, epsilon=0.01, min_eig_threshold=1e-4, want_hist=False):
+def lk_track(prev, nxt, pts, win=(21, 21), max_level=3, max_count=30, epsilon=0.01, min_eig_threshold=1e-4, want_hist=False,
+             want_exits=False):
     """cv2.calcOpticalFlowPyrLK(prev, nxt, pts, None, winSize=win, maxLevel=max_level, criteria=(EPS | COUNT, max_count, epsilon),
-    minEigThreshold=min_eig_threshold) without the error output: (next_pts (n, 2) float32, status (n,) uint8[, iteration histogram])."""
+    minEigThreshold=min_eig_threshold) without the error output: (next_pts (n, 2) float32, status (n,) uint8[, iteration histogram]
+    [, exits]).  exits (want_exits): how many (point, level) visits left the level by each way out, {(exit, "0" | "coarser"): count}
+    over EXITS -- bookkeeping only, no arithmetic depends on it."""
     max_count = min(max(int(max_count), 0), 100)
     epsilon = min(max(float(epsilon), 0.0), 10.0)
     eps2 = epsilon * epsilon
@@ -174,6 +180,11 @@ def lk_track(prev, nxt, pts, win=(21, 21), max_level=3, max_count=30, epsilon=0.
     hist = np.zeros(HIST_BINS, np.uint32)
     halfx, halfy = F((win[0] - 1) * 0.5), F((win[1] - 1) * 0.5)
     SC = F(1.0 / (1 << 20))
+    exits = {(e, g): 0 for e in EXITS for g in ("0", "coarser")}
+
+    def left(name, lv, count):
+        exits[(name, "0" if lv == 0 else "coarser")] += int(count)
+
     for lv in range(L - 1, -1, -1):
         I, J = pp[lv], pn[lv]
         d = scharr(I)
@@ -190,6 +201,7 @@ def lk_track(prev, nxt, pts, win=(21, 21), max_level=3, max_count=30, epsilon=0.
         if lv == 0:
             status[~ok] = 0
         sel = np.nonzero(ok)[0]
+        left("outside-first", lv, n - len(sel))
         if not len(sel):
             continue
         ix, iy = fx[sel].astype(np.int64), fy[sel].astype(np.int64)
@@ -205,6 +217,7 @@ def lk_track(prev, nxt, pts, win=(21, 21), max_level=3, max_count=30, epsilon=0.
         good = ~((min_eig < F(min_eig_threshold)) | (D < np.finfo(F).eps))
         if lv == 0:
             status[sel[~good]] = 0
+        left("min-eig", lv, len(good) - np.count_nonzero(good))
         sel, Iw, dx, dy = sel[good], Iw[good], dx[good], dy[good]
         A11, A12, A22 = A11[good], A12[good], A22[good]
         D = F(1) / D[good]
@@ -219,6 +232,7 @@ def lk_track(prev, nxt, pts, win=(21, 21), max_level=3, max_count=30, epsilon=0.
             if lv == 0:
                 status[sel[act[~ok]]] = 0
             iters[act[~ok]] = j
+            left("outside-iter", lv, len(ok) - np.count_nonzero(ok))
             act, gx, gy = act[ok], gx[ok], gy[ok]
             if not len(act):
                 break
@@ -241,7 +255,11 @@ def lk_track(prev, nxt, pts, win=(21, 21), max_level=3, max_count=30, epsilon=0.
             pdx[act], pdy[act] = ddx, ddy
             done = small | osc
             iters[act[done]] = j + 1
+            left("eps", lv, np.count_nonzero(small))
+            left("oscillation", lv, np.count_nonzero(osc))
             act = act[~done]
         iters[act] = max_count
+        left("max-count" if max_count else "max-count-0", lv, len(act))
         hist += np.bincount(np.minimum(iters, HIST_BINS - 1), minlength=HIST_BINS).astype(np.uint32)
-    return (out, status, hist) if want_hist else (out, status)
+    res = (out, status, hist) if want_hist else (out, status)
+    return res + (exits,) if want_exits else res

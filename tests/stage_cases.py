@@ -5,6 +5,9 @@ The library dispatches a stage to one of several kernels on the layer's width, t
 flow.  Each case below names the forms it is there to reach; tests/test_gpu_stages.py::test_every_kernel_form_is_reached derives the
 forms from the same predicates the dispatch uses (kernels_flow.hip launch_blur_iter / launch_polyexp / launch_blur_resize,
 kernels_window.hip launch_area_resize_flow) and fails when a form of FORMS is no longer reached.
+
+The sibling tables: tests/detect_cases.py (detection path, kernels_detect.hip), tests/sparse_cases.py (sparse path, kernels_lk.hip)
+and tests/window_cases.py (window search, kernels_window.hip).
 """
 from __future__ import annotations
 
