@@ -550,7 +550,8 @@ int mav_good_features(mav_ctx*, const uint8_t* gray, const mav_gftt_params* /* N
  * with a non-zero mask byte become corners.  An all-zero mask: no corner, no error. */
 int mav_good_features_ex(mav_ctx*, const uint8_t* gray, const uint8_t* mask, const mav_gftt_params*, float* corners, int* count);
 /* next_pts (n, 2) float32 and status (n) u8 for pts (n, 2) float32, 0 <= n <= MAV_LK_MAX_POINTS.  NaN / inf / far-away points are not
- * errors: they end with status 0 as in cv2.  `next` becomes the resident frame.  cv2's error output is not computed. */
+ * errors: they end with status 0 as in cv2.  `next` becomes the resident frame.  cv2's error output is not computed (mav_lk_track_err computes it), so this is the
+ * status of a C++ call with err == NULL: the final bounds test that comes with err is not run. */
 int mav_lk_track(mav_ctx*, const uint8_t* prev /* NULL: the resident frame */, const uint8_t* next, const float* pts, int n,
                  const mav_lk_params* /* NULL = defaults */, float* next_pts, uint8_t* status);
 /* Device-pointer forms.  mav_lk_track_dev only enqueues (frames are copied into the workspace on the device).  mav_good_features_dev
@@ -568,6 +569,38 @@ int mav_good_features_ex_dev(mav_ctx*, const uint8_t* gray_dev, const uint8_t* m
  * the points that ran.  With mav_good_features_ex_dev: corners -> track as one chain, no host call in between. */
 int mav_lk_track_ex_dev(mav_ctx*, const uint8_t* prev_dev, const uint8_t* next_dev, const float* pts_dev, int n_max, const int32_t* n_dev,
                         const mav_lk_params*, float* next_pts_dev, uint8_t* status_dev);
+/* The tracker with cv2's `err` output and cv2's two flags.  Like the rest of the sparse path this is OpenCV 4.x lkpyramid.cpp RESTATED
+ * and unpinned against a cv2 build.  flags: 0 or any OR of
+ *   MAV_OPTFLOW_USE_INITIAL_FLOW      next_pts is read first: a point's start at the top level is next_pts[p] * (1 / 2^level) instead of
+ *                                     the scaled previous point (then next_pts must not be NULL for n > 0)
+ *   MAV_OPTFLOW_LK_GET_MIN_EIGENVALS  err[p] = the float32 minimum eigenvalue the min_eig_threshold test looks at, of level 0 (written
+ *                                     before that test, so a point the test rejects carries it too); 0 when level 0 fails the first
+ *                                     bounds test.  Without an err buffer the flag changes nothing.
+ * any other bit is MAV_ERR_ARG and nothing is enqueued.  err (n) float32 or NULL.  Without GET_MIN_EIGENVALS, err is cv2's L1 error: for
+ * a point whose status is still 1 after level 0, q = next_pts[p] - halfWin; floor(q) must pass the bounds test every level uses
+ * (-win <= floor < size, finite) or the STATUS BECOMES 0 and err stays 0 -- the test cv2 runs only when err is asked for, which its
+ * Python call always does; otherwise err = (sum over the window of |J(q + k) - I(p + k)|) / (32 win_w win_h), the sum an exact integer
+ * (< 2^24, so no summation order is involved), the division in float32.  err = 0 for every point that ends with status 0.
+ * mav_lk_last_iterations does not count the error pass.  flags == 0 && err == NULL: mav_lk_track, byte for byte (no final bounds test).
+ * prev NULL: the resident frame; resident-frame rules, pyramid reuse and parameter checks are mav_lk_track's. */
+#define MAV_OPTFLOW_LK_GET_MIN_EIGENVALS 8      /* cv2's value; MAV_OPTFLOW_USE_INITIAL_FLOW (4) is defined above */
+int mav_lk_track_err(mav_ctx*, const uint8_t* prev, const uint8_t* next, const float* pts, int n, const mav_lk_params*, int flags,
+                     float* next_pts, uint8_t* status, float* err);
+/* enqueue only; n_dev may be NULL (n_max points run).  Entries from min(*n_dev, n_max) on are left as they were in next_pts, status AND
+ * err.  pts_dev == next_pts_dev is allowed (each wave reads its point before it writes). */
+int mav_lk_track_err_dev(mav_ctx*, const uint8_t* prev_dev, const uint8_t* next_dev, const float* pts_dev, int n_max, const int32_t* n_dev,
+                         const mav_lk_params*, int flags, float* next_pts_dev, uint8_t* status_dev, float* err_dev);
+/* Corners with cv2's useHarrisDetector / k.  use_harris == 0: the corresponding entry point above, bit for bit.  Otherwise the map is
+ * OpenCV's cornerHarris as goodFeaturesToTrack calls it (restated, unpinned): the same integer Sobel and box sums and the same scale s2
+ * as the min-eigenvalue map, then a = xx s2, b = xy s2, c = yy s2, t = a + c, response = (a c - b b) - (k t) t in float32 in this order,
+ * k rounded to float32 once.  Responses may be negative; a corner is always above max * quality_level > 0.  A non-finite k is
+ * MAV_ERR_ARG.  Threshold, non-maximum test, mask, sort and pick are those of mav_good_features_ex. */
+typedef struct { int use_harris; double k; } mav_corner_score;   /* mav_corner_score_defaults: 0, 0.04 */
+void mav_corner_score_defaults(mav_corner_score*);
+int mav_good_features_score(mav_ctx*, const uint8_t* gray, const uint8_t* mask, const mav_gftt_params*, const mav_corner_score* /* NULL = defaults */,
+                            float* corners, int* count);
+int mav_good_features_score_dev(mav_ctx*, const uint8_t* gray_dev, const uint8_t* mask_dev, const mav_gftt_params*, const mav_corner_score*,
+                                float* corners_dev, int32_t* count_dev);  /* enqueue only, as mav_good_features_ex_dev */
 /* What the most recent corner pick did: stats[0] = chunks of 1024 ranks it walked, stats[1] = rounds over all chunks.
  * Synchronises. */
 int mav_gftt_last_pick(mav_ctx*, uint32_t* stats);
@@ -655,6 +688,8 @@ int mav_stage_pyramid_level(mav_ctx*, const uint8_t* img, double scale, int leve
 int mav_stage_lk_pyramid(mav_ctx*, const uint8_t* img, int level, uint8_t* out);
 int mav_stage_lk_scharr(mav_ctx*, const uint8_t* img, int level, int16_t* out);
 int mav_stage_min_eigen(mav_ctx*, const uint8_t* img, int block_size, float* out);
+/* the same map with a score: the Harris response for use_harris != 0, mav_stage_min_eigen's bytes otherwise (NULL = defaults) */
+int mav_stage_corner_response(mav_ctx*, const uint8_t* img, int block_size, const mav_corner_score*, float* out);
 /* the device sort and pick of mav_good_features on n host candidate keys, (value bits << 32) | linear index: distinct, index < W * H,
  * any order, n <= MAV_GFTT_MAX_CANDIDATES.  quality_level and block_size are not used.  The resident frame stays. */
 int mav_stage_corner_pick(mav_ctx*, const uint64_t* keys, int n, const mav_gftt_params*, float* corners, int* count);

@@ -31,10 +31,34 @@ __device__ __forceinline__ float float_of(unsigned k) { return __uint_as_float((
 // images, which is not the derivative of the reflected frame: dx * dy would change sign).  Box sums of dx*dx, dx*dy, dy*dy are
 // separable integer sums (<= 225 x 1020^2 < 2^31), then five float32 operations.  The tile's maximum goes to *maxkey; with a mask
 // (cv2's minMaxLoc(eig, ..., mask)) only pixels whose mask byte is non-zero take part in it, the map itself is the whole map.
+//
+// The score is a compile-time policy of the kernel: it holds the kernel's float argument(s) and turns a pixel's three box sums into the
+// map's value.  Everything before it (Sobel, halo, box sums) and after it (the store, the masked maximum) is the one body.
+//   MinEigScore     cornerMinEigenVal, five float32 operations (mav_good_features and every form of it)
+//   HarrisScore     cornerHarris as goodFeaturesToTrack(useHarrisDetector = true) calls it: the same sums and the same scale, then
+//                   a = xx s2, b = xy s2, c = yy s2, t = a + c, (a c - b b) - (k t) t, float32 in this order with k rounded to float32
+//                   once (the form of OpenCV's vector path).  Responses may be negative: key_of orders floats of either sign.
 #define EIG_TILE 16
 #define EIG_MAX_R 7
 #define EIG_T (EIG_TILE + 2 * EIG_MAX_R)
-__global__ __launch_bounds__(256) void k_min_eig(const uint8_t* __restrict__ img, const uint8_t* __restrict__ mask, int W, int H, int r, float s2,
+struct MinEigScore {
+    float s2;
+    __device__ __forceinline__ float operator()(int xx, int xy, int yy) const
+    {
+        const float a = (float)xx * s2 * 0.5f, b = (float)xy * s2, c = (float)yy * s2 * 0.5f;
+        return (a + c) - sqrtf((a - c) * (a - c) + b * b);
+    }
+};
+struct HarrisScore {
+    float s2, k;
+    __device__ __forceinline__ float operator()(int xx, int xy, int yy) const
+    {
+        const float a = (float)xx * s2, b = (float)xy * s2, c = (float)yy * s2, t = a + c;
+        return (a * c - b * b) - (k * t) * t;
+    }
+};
+template <typename Score>
+__global__ __launch_bounds__(256) void k_min_eig(const uint8_t* __restrict__ img, const uint8_t* __restrict__ mask, int W, int H, int r, Score score,
                                                  float* __restrict__ eig, unsigned* __restrict__ maxkey)
 {
     __shared__ short2 d[EIG_T * EIG_T];
@@ -72,8 +96,7 @@ __global__ __launch_bounds__(256) void k_min_eig(const uint8_t* __restrict__ img
             const int k = (ty + j) * EIG_TILE + tx;
             xx += hs[0][k]; xy += hs[1][k]; yy += hs[2][k];
         }
-        const float a = (float)xx * s2 * 0.5f, b = (float)xy * s2, c = (float)yy * s2 * 0.5f;
-        const float e = (a + c) - sqrtf((a - c) * (a - c) + b * b);
+        const float e = score(xx, xy, yy);
         eig[(size_t)y * W + x] = e;
         if (!mask || mask[(size_t)y * W + x]) key = key_of(e);
     }
@@ -111,7 +134,13 @@ __global__ __launch_bounds__(256) void k_corner_candidates(const float* __restri
 void launch_min_eig(hipStream_t st, const uint8_t* img, const uint8_t* mask, int W, int H, int block_size, float s2, float* eig, unsigned* maxkey)
 {
     dim3 grid((W + EIG_TILE - 1) / EIG_TILE, (H + EIG_TILE - 1) / EIG_TILE);
-    hipLaunchKernelGGL(k_min_eig, grid, dim3(256), 0, st, img, mask, W, H, block_size / 2, s2, eig, maxkey);
+    hipLaunchKernelGGL(k_min_eig<MinEigScore>, grid, dim3(256), 0, st, img, mask, W, H, block_size / 2, MinEigScore{s2}, eig, maxkey);
+}
+void launch_harris(hipStream_t st, const uint8_t* img, const uint8_t* mask, int W, int H, int block_size, float s2, float k, float* eig,
+                   unsigned* maxkey)
+{
+    dim3 grid((W + EIG_TILE - 1) / EIG_TILE, (H + EIG_TILE - 1) / EIG_TILE);
+    hipLaunchKernelGGL(k_min_eig<HarrisScore>, grid, dim3(256), 0, st, img, mask, W, H, block_size / 2, HarrisScore{s2, k}, eig, maxkey);
 }
 void launch_corner_candidates(hipStream_t st, const float* eig, const uint8_t* mask, int W, int H, const unsigned* maxkey, double quality,
                               uint2* cand, unsigned* count, unsigned cap)
@@ -366,7 +395,20 @@ __device__ __forceinline__ int lk_image_value(const uint8_t* __restrict__ img, i
     return ((int)ra[xa] * q.w00 + (int)ra[xb] * q.w01 + (int)rb[xa] * q.w10 + (int)rb[xb] * q.w11 + 256) >> 9;
 }
 
-__global__ __launch_bounds__(256) void k_lk_track(LkTrackArgs a)
+// The form is a compile-time policy of the one body.  LkPlain (mav_lk_track, _dev, _ex_dev) is the tracker as it always was.  LkErr
+// takes cv2's `err` output and the flags at run time (LkTrackErrArgs), same launch shape and LDS:
+//   OPTFLOW_USE_INITIAL_FLOW       the top level starts at out[p] * (1 / 2^level), read before anything is written (out is in and out)
+//   OPTFLOW_LK_GET_MIN_EIGENVALS   err = minEig of every level that passes the first bounds test, written before the threshold test, so
+//                                  level 0's stays; 0 when level 0 fails the first bounds test
+//   err without that flag          a point still at status 1 after level 0's loop: q = out - halfWin, the bounds test on floor(q)
+//                                  (failing it clears the status, err stays 0), then S = sum |J(q + k) - Iw[k]| over the window with
+//                                  the iteration's own interpolation, Iw = level 0's plane still in LDS; err = (float)S / (float)(32 w h)
+//                                  (a float32 division).  S is an exact integer <= 8160 x 33 x 33 < 2^24: no summation order in it.
+// The iteration histogram does not count the error pass.
+struct LkPlain { typedef LkTrackArgs Args; static constexpr bool ERR = false; };
+struct LkErr { typedef LkTrackErrArgs Args; static constexpr bool ERR = true; };
+template <typename Form>
+__global__ __launch_bounds__(256) void k_lk_track(typename Form::Args a)
 {
     extern __shared__ short lk_lds[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -379,6 +421,9 @@ __global__ __launch_bounds__(256) void k_lk_track(LkTrackArgs a)
     short* Dx = Iw + npix;
     short* Dy = Dx + npix;
     const float ptx = a.pts[2 * p], pty = a.pts[2 * p + 1];
+    float gx = 0.f, gy = 0.f, errv = 0.f;                     // LkErr only: the initial position, the error output
+    if constexpr (Form::ERR)
+        if (a.flags & MAV_OPTFLOW_USE_INITIAL_FLOW) { gx = a.out[2 * p]; gy = a.out[2 * p + 1]; }
     const float halfx = (win_w - 1) * 0.5f, halfy = (win_h - 1) * 0.5f;
     const float FLT_SCALE = 1.f / (1 << 20);
     float outx = 0.f, outy = 0.f;
@@ -388,11 +433,13 @@ __global__ __launch_bounds__(256) void k_lk_track(LkTrackArgs a)
         const float sc = 1.f / (float)(1 << level);
         float px = ptx * sc, py = pty * sc, nx, ny;
         if (level == a.lv.n - 1) { nx = px; ny = py; } else { nx = outx * 2.f; ny = outy * 2.f; }
+        if constexpr (Form::ERR)
+            if (level == a.lv.n - 1 && (a.flags & MAV_OPTFLOW_USE_INITIAL_FLOW)) { nx = gx * sc; ny = gy * sc; }
         outx = nx; outy = ny;
         px -= halfx; py -= halfy;
         float fx = floorf(px), fy = floorf(py);
         if (!(fx >= (float)-win_w && fx < (float)w && fy >= (float)-win_h && fy < (float)h)) {
-            if (level == 0) status = 0;
+            if (level == 0) { status = 0; errv = 0.f; }
             continue;
         }
         const uint8_t* I = a.I + a.lv.off[level];
@@ -419,6 +466,8 @@ __global__ __launch_bounds__(256) void k_lk_track(LkTrackArgs a)
         const float A11 = (float)(double)s11 * FLT_SCALE, A12 = (float)(double)s12 * FLT_SCALE, A22 = (float)(double)s22 * FLT_SCALE;
         float Dt = A11 * A22 - A12 * A12;
         const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (float)(2 * win_w * win_h);
+        if constexpr (Form::ERR)
+            if (a.flags & MAV_OPTFLOW_LK_GET_MIN_EIGENVALS) errv = minEig;
         if (minEig < a.min_eig || Dt < FLT_EPSILON) {
             if (level == 0) status = 0;
             continue;
@@ -456,14 +505,42 @@ __global__ __launch_bounds__(256) void k_lk_track(LkTrackArgs a)
         }
         if (lane == 0 && a.iter_hist) atomicAdd(a.iter_hist + (j < MAV_LK_HIST - 1 ? j : MAV_LK_HIST - 1), 1u);
     }
+    if constexpr (Form::ERR) {
+        if (a.err && status && !(a.flags & MAV_OPTFLOW_LK_GET_MIN_EIGENVALS)) {
+            const int w = a.lv.w[0], h = a.lv.h[0];
+            const float qx = outx - halfx, qy = outy - halfy;
+            const float fx = floorf(qx), fy = floorf(qy);
+            if (!(fx >= (float)-win_w && fx < (float)w && fy >= (float)-win_h && fy < (float)h)) status = 0;
+            else {
+                const int ix = (int)fx, iy = (int)fy;
+                const LkWeights q = lk_weights(qx - fx, qy - fy);
+                const uint8_t* J = a.J + a.lv.off[0];
+                long long S = 0;
+                for (int k = lane; k < npix; k += 64) {
+                    const int jj = k / win_w, i = k - jj * win_w;
+                    const int diff = lk_image_value(J, w, h, ix + i, iy + jj, q) - (int)Iw[k];
+                    S += (long long)(diff < 0 ? -diff : diff);
+                }
+                S = wave_sum(S);
+                errv = (float)S / (float)(32 * win_w * win_h);
+            }
+        }
+    }
     if (lane == 0) {
         a.out[2 * p] = outx; a.out[2 * p + 1] = outy;
         a.status[p] = (uint8_t)status;
+        if constexpr (Form::ERR)
+            if (a.err) a.err[p] = errv;
     }
 }
 size_t lk_track_lds_bytes(int win_w, int win_h) { return (size_t)4 * 3 * win_w * win_h * sizeof(short); }
 void launch_lk_track(hipStream_t st, const LkTrackArgs& a)
 {
     if (a.n < 1) return;
-    hipLaunchKernelGGL(k_lk_track, dim3((a.n + 3) / 4), dim3(256), lk_track_lds_bytes(a.win_w, a.win_h), st, a);
+    hipLaunchKernelGGL(k_lk_track<LkPlain>, dim3((a.n + 3) / 4), dim3(256), lk_track_lds_bytes(a.win_w, a.win_h), st, a);
+}
+void launch_lk_track_err(hipStream_t st, const LkTrackErrArgs& a)
+{
+    if (a.n < 1) return;
+    hipLaunchKernelGGL(k_lk_track<LkErr>, dim3((a.n + 3) / 4), dim3(256), lk_track_lds_bytes(a.win_w, a.win_h), st, a);
 }

@@ -3276,6 +3276,7 @@ extern "C" int mav_allgather_results(mav_ctx* c, void* comm, const void* local_d
 // ---- sparse optical flow: Shi-Tomasi corners + pyramidal Lucas-Kanade (kernels_lk.hip) ---------------------------------------------
 extern "C" void mav_gftt_defaults(mav_gftt_params* p) { *p = mav_gftt_params{2000, 0.2, 7.0, 7}; }
 extern "C" void mav_lk_defaults(mav_lk_params* p) { *p = mav_lk_params{21, 21, 3, 30, 0.01, 1e-4}; }
+extern "C" void mav_corner_score_defaults(mav_corner_score* s) { *s = mav_corner_score{0, 0.04}; }
 
 static void lk_level_dims(int W, int H, LkLevels* lv)
 {
@@ -3310,6 +3311,12 @@ static int check_gftt_params(const mav_gftt_params& p, const char* fn)
     if (!(p.min_distance >= 0) || !std::isfinite(p.min_distance)) return fail(MAV_ERR_ARG, "%s: min_distance %g must be >= 0", fn, p.min_distance);
     if (p.block_size < 1 || p.block_size > 15 || p.block_size % 2 == 0)
         return fail(MAV_ERR_ARG, "%s: block_size %d must be odd and in [1, 15] (the tile's halo in LDS)", fn, p.block_size);
+    return MAV_OK;
+}
+static int check_corner_score(const mav_corner_score* sp, mav_corner_score* s, const char* fn)
+{
+    if (sp) *s = *sp; else mav_corner_score_defaults(s);
+    if (!std::isfinite(s->k)) return fail(MAV_ERR_ARG, "%s: k %g must be finite", fn, s->k);
     return MAV_OK;
 }
 static int check_lk_params(mav_lk_params& p, int n, const char* fn)
@@ -3401,16 +3408,24 @@ static int corner_pick_enqueue(mav_ctx* c, const mav_gftt_params& p, float* corn
     launch_corner_pick(c->stream, a);
     return check_launch("corner pick");
 }
-// Corner detection on slot `slot`, enqueue only: eigenvalue map, candidates, sort, pick.  mask / corners / count: device memory.
-static int good_features_enqueue(mav_ctx* c, int slot, const uint8_t* mask, const mav_gftt_params& p, float* corners, int* count)
+// The score map of slot `slot` into k.eig and its (masked) maximum into counters[0]: min-eigenvalue, or the Harris response.
+static void corner_map_enqueue(mav_ctx* c, int slot, const uint8_t* mask, int block_size, const mav_corner_score& sc)
+{
+    LkState& k = c->lk;
+    const float s = (float)(1.0 / (4.0 * block_size * 255.0)), s2 = s * s;
+    if (sc.use_harris) launch_harris(c->stream, k.pyr[slot], mask, c->W, c->H, block_size, s2, (float)sc.k, k.eig, k.counters);
+    else launch_min_eig(c->stream, k.pyr[slot], mask, c->W, c->H, block_size, s2, k.eig, k.counters);
+}
+// Corner detection on slot `slot`, enqueue only: score map, candidates, sort, pick.  mask / corners / count: device memory.
+static int good_features_enqueue(mav_ctx* c, int slot, const uint8_t* mask, const mav_gftt_params& p, const mav_corner_score& sc, float* corners,
+                                 int* count)
 {
     LkState& k = c->lk;
     const int W = c->W, H = c->H;
-    const float s = (float)(1.0 / (4.0 * p.block_size * 255.0)), s2 = s * s;
     {
         ProfScope ps(c, K_LK_CORNERS);
         HIPCHK(hipMemsetAsync(k.counters, 0, 2 * sizeof(unsigned), c->stream));
-        launch_min_eig(c->stream, k.pyr[slot], mask, W, H, p.block_size, s2, k.eig, k.counters);
+        corner_map_enqueue(c, slot, mask, p.block_size, sc);
         launch_corner_candidates(c->stream, k.eig, mask, W, H, k.counters, p.quality_level, k.cand, k.counters + 1, MAV_GFTT_MAX_CANDIDATES);
     }
     CHK(check_launch("corner detection"));
@@ -3435,11 +3450,13 @@ static int corner_pick_fetch(mav_ctx* c, const mav_gftt_params& p, float* corner
     return MAV_OK;
 }
 static int good_features_entry(mav_ctx* c, const uint8_t* gray, const uint8_t* mask, bool host, bool host_out, const mav_gftt_params* pp,
-                               float* corners, int* count, const char* fn)
+                               float* corners, int* count, const char* fn, const mav_corner_score* scp = nullptr)
 {
     mav_gftt_params p;
+    mav_corner_score sc;
     if (pp) p = *pp; else mav_gftt_defaults(&p);
     CHK(check_gftt_params(p, fn));
+    CHK(check_corner_score(scp, &sc, fn));
     if (!c || !corners || !count) return fail(MAV_ERR_ARG, "%s: NULL argument", fn);
     HIPCHK(hipSetDevice(c->device));
     if (!gray && c->lk.cur < 0) return fail(MAV_ERR_STATE, "%s: gray is NULL and no frame is resident", fn);
@@ -3458,8 +3475,8 @@ static int good_features_entry(mav_ctx* c, const uint8_t* gray, const uint8_t* m
         if (k.deriv_slot == other) { k.deriv_slot = -1; k.deriv_levels = 0; }
         mask = k.pyr[other];
     }
-    if (!host_out) return good_features_enqueue(c, k.cur, mask, p, corners, count);
-    CHK(good_features_enqueue(c, k.cur, mask, p, k.out, reinterpret_cast<int*>(k.counters + LK_CNT_PICKED)));
+    if (!host_out) return good_features_enqueue(c, k.cur, mask, p, sc, corners, count);
+    CHK(good_features_enqueue(c, k.cur, mask, p, sc, k.out, reinterpret_cast<int*>(k.counters + LK_CNT_PICKED)));
     return corner_pick_fetch(c, p, corners, count, fn);
 }
 extern "C" int mav_good_features(mav_ctx* c, const uint8_t* gray, const mav_gftt_params* p, float* corners, int* count)
@@ -3479,6 +3496,16 @@ extern "C" int mav_good_features_ex_dev(mav_ctx* c, const uint8_t* gray, const u
 {
     return good_features_entry(c, gray, mask, false, false, p, corners, count, "mav_good_features_ex_dev");
 }
+extern "C" int mav_good_features_score(mav_ctx* c, const uint8_t* gray, const uint8_t* mask, const mav_gftt_params* p, const mav_corner_score* sc,
+                                       float* corners, int* count)
+{
+    return good_features_entry(c, gray, mask, true, true, p, corners, count, "mav_good_features_score", sc);
+}
+extern "C" int mav_good_features_score_dev(mav_ctx* c, const uint8_t* gray, const uint8_t* mask, const mav_gftt_params* p,
+                                           const mav_corner_score* sc, float* corners, int32_t* count)
+{
+    return good_features_entry(c, gray, mask, false, false, p, corners, count, "mav_good_features_score_dev", sc);
+}
 extern "C" int mav_gftt_last_pick(mav_ctx* c, uint32_t* stats)
 {
     if (!c || !stats) return fail(MAV_ERR_ARG, "mav_gftt_last_pick: NULL argument");
@@ -3489,8 +3516,10 @@ extern "C" int mav_gftt_last_pick(mav_ctx* c, uint32_t* stats)
 }
 
 // prev (or the resident frame) and next into the two slots, pyramids, derivatives, one tracker launch.  pts / out / status: device.
+// ext: the tracker's second form (mav_lk_track_err*), with its flags and err (device, may be null).
+struct LkErrOut { int flags; float* err; };
 static int lk_track_enqueue(mav_ctx* c, const uint8_t* prev, const uint8_t* next, bool host, const float* pts, int n, const mav_lk_params& p,
-                            float* out, uint8_t* status, const int* n_dev = nullptr)
+                            float* out, uint8_t* status, const int* n_dev = nullptr, const LkErrOut* ext = nullptr)
 {
     LkState& k = c->lk;
     int sp;
@@ -3504,14 +3533,15 @@ static int lk_track_enqueue(mav_ctx* c, const uint8_t* prev, const uint8_t* next
     lk_build(c, sn, levels);
     lk_derivatives(c, sp, levels);
     HIPCHK(hipMemsetAsync(k.counters + 2, 0, MAV_LK_HIST * sizeof(unsigned), c->stream));
-    LkTrackArgs a;
+    LkTrackErrArgs a{};
     a.I = k.pyr[sp]; a.J = k.pyr[sn]; a.D = k.deriv; a.lv = k.dims; a.lv.n = levels;
     a.pts = pts; a.n = n; a.win_w = p.win_w; a.win_h = p.win_h; a.max_count = p.max_count;
     a.eps2 = p.epsilon * p.epsilon; a.min_eig = (float)p.min_eig_threshold;
     a.out = out; a.status = status; a.iter_hist = k.counters + 2; a.n_dev = n_dev;
     {
         ProfScope ps(c, K_LK_TRACK);
-        launch_lk_track(c->stream, a);
+        if (ext) { a.flags = ext->flags; a.err = ext->err; launch_lk_track_err(c->stream, a); }
+        else launch_lk_track(c->stream, a);
     }
     CHK(check_launch("lk_track"));
     k.cur = sn; k.hist_valid = true;
@@ -3555,6 +3585,44 @@ extern "C" int mav_lk_track_ex_dev(mav_ctx* c, const uint8_t* prev, const uint8_
     CHK(lk_track_check(c, prev, next, pts, n_max, pp, next_pts, status, &p, "mav_lk_track_ex_dev"));
     if (!n_dev) return fail(MAV_ERR_ARG, "mav_lk_track_ex_dev: NULL argument");
     return lk_track_enqueue(c, prev, next, false, pts, n_max, p, next_pts, status, n_dev);
+}
+static int lk_err_flags_check(int flags, int n, const void* next_pts, const char* fn)
+{
+    if (flags & ~(MAV_OPTFLOW_USE_INITIAL_FLOW | MAV_OPTFLOW_LK_GET_MIN_EIGENVALS))
+        return fail(MAV_ERR_ARG, "%s: flags %d: only MAV_OPTFLOW_USE_INITIAL_FLOW (4) and MAV_OPTFLOW_LK_GET_MIN_EIGENVALS (8) are known", fn, flags);
+    if ((flags & MAV_OPTFLOW_USE_INITIAL_FLOW) && n > 0 && !next_pts)
+        return fail(MAV_ERR_ARG, "%s: MAV_OPTFLOW_USE_INITIAL_FLOW needs the starting positions in next_pts", fn);
+    return MAV_OK;
+}
+extern "C" int mav_lk_track_err(mav_ctx* c, const uint8_t* prev, const uint8_t* next, const float* pts, int n, const mav_lk_params* pp, int flags,
+                                float* next_pts, uint8_t* status, float* err)
+{
+    mav_lk_params p;
+    CHK(lk_err_flags_check(flags, n, next_pts, "mav_lk_track_err"));
+    CHK(lk_track_check(c, prev, next, pts, n, pp, next_pts, status, &p, "mav_lk_track_err"));
+    LkState& k = c->lk;
+    const size_t pb = (size_t)n * 2 * sizeof(float);
+    // err is staged in the candidate buffer: dead once a pick has run, and every use is ordered on the one stream
+    static_assert((size_t)MAV_GFTT_MAX_CANDIDATES * sizeof(uint2) >= (size_t)MAV_LK_MAX_POINTS * sizeof(float), "err staging");
+    const LkErrOut ext{flags, err ? reinterpret_cast<float*>(k.cand) : nullptr};
+    if (n) HIPCHK(hipMemcpyAsync(k.pts, pts, pb, hipMemcpyHostToDevice, c->stream));
+    if (n && (flags & MAV_OPTFLOW_USE_INITIAL_FLOW)) HIPCHK(hipMemcpyAsync(k.out, next_pts, pb, hipMemcpyHostToDevice, c->stream));
+    CHK(lk_track_enqueue(c, prev, next, true, k.pts, n, p, k.out, k.status, nullptr, &ext));
+    if (n) {
+        HIPCHK(hipMemcpyAsync(next_pts, k.out, pb, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(status, k.status, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        if (err) HIPCHK(hipMemcpyAsync(err, ext.err, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
+    return mav_sync(c);
+}
+extern "C" int mav_lk_track_err_dev(mav_ctx* c, const uint8_t* prev, const uint8_t* next, const float* pts, int n_max, const int32_t* n_dev,
+                                    const mav_lk_params* pp, int flags, float* next_pts, uint8_t* status, float* err)
+{
+    mav_lk_params p;
+    CHK(lk_err_flags_check(flags, n_max, next_pts, "mav_lk_track_err_dev"));
+    CHK(lk_track_check(c, prev, next, pts, n_max, pp, next_pts, status, &p, "mav_lk_track_err_dev"));
+    const LkErrOut ext{flags, err};
+    return lk_track_enqueue(c, prev, next, false, pts, n_max, p, next_pts, status, n_dev, &ext);
 }
 extern "C" int mav_lk_last_iterations(mav_ctx* c, uint32_t* hist)
 {
@@ -3604,22 +3672,31 @@ extern "C" int mav_stage_lk_scharr(mav_ctx* c, const uint8_t* img, int level, in
     k.built[0] = 0; k.deriv_slot = -1; k.deriv_levels = 0;
     return rc;
 }
-extern "C" int mav_stage_min_eigen(mav_ctx* c, const uint8_t* img, int block_size, float* out)
+static int stage_corner_map(mav_ctx* c, const uint8_t* img, int block_size, const mav_corner_score* scp, float* out, const char* fn)
 {
     mav_gftt_params p;
+    mav_corner_score sc;
     mav_gftt_defaults(&p);
     p.block_size = block_size;
-    CHK(check_gftt_params(p, "mav_stage_min_eigen"));
-    CHK(lk_stage_begin(c, img, out, "mav_stage_min_eigen"));
+    CHK(check_gftt_params(p, fn));
+    CHK(check_corner_score(scp, &sc, fn));
+    CHK(lk_stage_begin(c, img, out, fn));
     LkState& k = c->lk;
-    const float s = (float)(1.0 / (4.0 * block_size * 255.0)), s2 = s * s;
     HIPCHK(hipMemsetAsync(k.counters, 0, 2 * sizeof(unsigned), c->stream));
-    launch_min_eig(c->stream, k.pyr[0], nullptr, c->W, c->H, block_size, s2, k.eig, k.counters);
+    corner_map_enqueue(c, 0, nullptr, block_size, sc);
     CHK(check_launch("min_eig"));
     CHK(download(c, out, k.eig, c->n0 * sizeof(float)));
     const int rc = mav_sync(c);
     k.built[0] = 0;
     return rc;
+}
+extern "C" int mav_stage_min_eigen(mav_ctx* c, const uint8_t* img, int block_size, float* out)
+{
+    return stage_corner_map(c, img, block_size, nullptr, out, "mav_stage_min_eigen");
+}
+extern "C" int mav_stage_corner_response(mav_ctx* c, const uint8_t* img, int block_size, const mav_corner_score* sc, float* out)
+{
+    return stage_corner_map(c, img, block_size, sc, out, "mav_stage_corner_response");
 }
 extern "C" int mav_stage_corner_pick(mav_ctx* c, const uint64_t* keys, int n, const mav_gftt_params* pp, float* corners, int* count)
 {

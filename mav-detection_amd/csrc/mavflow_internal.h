@@ -210,6 +210,11 @@ struct LkTrackArgs {
     unsigned* iter_hist;          // [MAV_LK_HIST] or null: iterations per (point, level) that reached the loop
     const int* n_dev;             // null, or the device's own point count: min(*n_dev, n) points run, none if it is negative
 };
+// the tracker's second form: cv2's `err` output and flags (kernels_lk.hip LkErr).  With USE_INITIAL_FLOW `out` is read before it is written.
+struct LkTrackErrArgs : LkTrackArgs {
+    float* err;                   // (n) or null
+    int flags;                    // MAV_OPTFLOW_USE_INITIAL_FLOW | MAV_OPTFLOW_LK_GET_MIN_EIGENVALS
+};
 struct LkPickArgs {
     const uint2* cand;            // sorted candidates (value bits, linear index)
     const unsigned* n_ptr;        // their count; > cap: overflow
@@ -226,6 +231,9 @@ struct LkPickArgs {
 // min-eigenvalue map of a W x H u8 image (block_size odd, <= 15) and its maximum as an ordered key (*maxkey zeroed by the caller)
 // mask (H, W) u8 or null: only pixels with a non-zero mask byte enter the maximum (and become candidates below)
 void launch_min_eig(hipStream_t st, const uint8_t* img, const uint8_t* mask, int W, int H, int block_size, float s2, float* eig, unsigned* maxkey);
+// the same map with the Harris response (a c - b b) - (k (a + c)) (a + c) as the score
+void launch_harris(hipStream_t st, const uint8_t* img, const uint8_t* mask, int W, int H, int block_size, float s2, float k, float* eig,
+                   unsigned* maxkey);
 // candidates (value bits, linear index) appended at cand[*count++] while *count < cap (*count zeroed by the caller, counts past cap)
 void launch_corner_candidates(hipStream_t st, const float* eig, const uint8_t* mask, int W, int H, const unsigned* maxkey, double quality,
                               uint2* cand, unsigned* count, unsigned cap);
@@ -237,3 +245,4 @@ void launch_lk_pyrdown(hipStream_t st, const uint8_t* src, int sw, int sh, uint8
 void launch_lk_scharr(hipStream_t st, const uint8_t* pyr, const LkLevels& lv, int levels, short2* out);
 size_t lk_track_lds_bytes(int win_w, int win_h);
 void launch_lk_track(hipStream_t st, const LkTrackArgs& a);
+void launch_lk_track_err(hipStream_t st, const LkTrackErrArgs& a);

@@ -45,6 +45,11 @@ class LkParams(C.Structure):
 LK_MAX_POINTS, LK_MAX_WIN, LK_MAX_LEVEL, LK_HIST_BINS, GFTT_MAX_CANDIDATES = 65536, 33, 7, 104, 262144
 
 
+class CornerScore(C.Structure):
+    """mav_corner_score: cv2.goodFeaturesToTrack's useHarrisDetector and k."""
+    _fields_ = [("use_harris", C.c_int), ("k", C.c_double)]
+
+
 class Result(C.Structure):
     _fields_ = [("box", C.c_int32 * 4), ("foe", C.c_double * 2)]
 
@@ -77,13 +82,17 @@ EXPORTS = [
     "mav_lk_last_iterations", "mav_lk_level_dims", "mav_stage_lk_pyramid", "mav_stage_lk_scharr", "mav_stage_min_eigen",
     "mav_good_features_ex", "mav_good_features_ex_dev", "mav_lk_track_ex_dev", "mav_gftt_last_pick", "mav_stage_corner_pick",
     "mav_set_window", "mav_get_window",
+    "mav_lk_track_err", "mav_lk_track_err_dev", "mav_corner_score_defaults", "mav_good_features_score", "mav_good_features_score_dev",
+    "mav_stage_corner_response",
 ]
 
 # Frame depths of the _ex entry points (cv2's depth codes) by numpy dtype.  uint8 frames keep going through the u8 symbols.
 DEPTH_8U, DEPTH_16U, DEPTH_32F = 0, 2, 5
 DEPTHS = {np.dtype(np.uint8): DEPTH_8U, np.dtype(np.uint16): DEPTH_16U, np.dtype(np.float32): DEPTH_32F}
 
-OPTFLOW_USE_INITIAL_FLOW = 4                    # FbParams.flags bit (cv2.OPTFLOW_USE_INITIAL_FLOW): see Context.farneback(initial_flow=)
+OPTFLOW_USE_INITIAL_FLOW = 4                    # FbParams.flags bit (cv2.OPTFLOW_USE_INITIAL_FLOW): see Context.farneback(initial_flow=);
+#                                                 and a `flags` bit of Context.lk_track_err (the starting positions come in next_pts)
+OPTFLOW_LK_GET_MIN_EIGENVALS = 8                # cv2.OPTFLOW_LK_GET_MIN_EIGENVALS: Context.lk_track_err's err is the minimum eigenvalue
 # cv2.OPTFLOW_FARNEBACK_GAUSSIAN.  Not an FbParams.flags bit (mav_create refuses it): the window belongs to the context --
 # Context(window="gaussian") / Context.set_window; mavflow.farneback translates a cv2 argument list that carries the bit.
 OPTFLOW_FARNEBACK_GAUSSIAN = 256
@@ -138,7 +147,7 @@ def load(path: str | None = None) -> C.CDLL:
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("mav_last_error", "mav_stream", "mav_fb_defaults", "mav_foe_defaults", "mav_thr_defaults", "mav_last_flow_dev", "mav_png_bound",
-                        "mav_gftt_defaults", "mav_lk_defaults"):
+                        "mav_gftt_defaults", "mav_lk_defaults", "mav_corner_score_defaults"):
             fn.restype = C.c_int
     lib.mav_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FbParams)]
     lib.mav_destroy.argtypes = [C.c_void_p]
@@ -268,6 +277,14 @@ def load(path: str | None = None) -> C.CDLL:
     lib.mav_lk_track_ex_dev.argtypes = [vp, vp, vp, vp, C.c_int, vp, C.POINTER(LkParams), vp, vp]
     lib.mav_gftt_last_pick.argtypes = [vp, vp]
     lib.mav_stage_corner_pick.argtypes = [vp, vp, C.c_int, C.POINTER(GfttParams), vp, C.POINTER(C.c_int)]
+    # ctx, prev, next, pts, n, params, flags, next_pts, status, err
+    lib.mav_lk_track_err.argtypes = [vp, vp, vp, vp, C.c_int, C.POINTER(LkParams), C.c_int, vp, vp, vp]
+    # ctx, prev, next, pts, n_max, n_dev, params, flags, next_pts, status, err
+    lib.mav_lk_track_err_dev.argtypes = [vp, vp, vp, vp, C.c_int, vp, C.POINTER(LkParams), C.c_int, vp, vp, vp]
+    lib.mav_corner_score_defaults.argtypes = [C.POINTER(CornerScore)]
+    lib.mav_good_features_score.argtypes = [vp, vp, vp, C.POINTER(GfttParams), C.POINTER(CornerScore), vp, C.POINTER(C.c_int)]
+    lib.mav_good_features_score_dev.argtypes = [vp, vp, vp, C.POINTER(GfttParams), C.POINTER(CornerScore), vp, vp]
+    lib.mav_stage_corner_response.argtypes = [vp, vp, C.c_int, C.POINTER(CornerScore), vp]
     _lib = lib
     return lib
 
@@ -315,6 +332,14 @@ def gftt_defaults(**kw) -> GfttParams:
             raise TypeError(f"good_features: unknown parameter {k!r}")
         setattr(p, k, v)
     return p
+
+
+def corner_score(useHarrisDetector=False, k=0.04) -> CornerScore:
+    """cv2.goodFeaturesToTrack's useHarrisDetector / k as a mav_corner_score."""
+    s = CornerScore()
+    load().mav_corner_score_defaults(C.byref(s))
+    s.use_harris, s.k = int(bool(useHarrisDetector)), float(k)
+    return s
 
 
 def lk_defaults(**kw) -> LkParams:
@@ -1207,23 +1232,33 @@ class Context:
             raise ValueError(f"mask: expected a uint8 array of shape {(self.H, self.W)}, got {mask.dtype} {mask.shape}")
         return np.ascontiguousarray(mask)
 
-    def good_features(self, gray, mask=None, **params) -> np.ndarray:
-        """cv2.goodFeaturesToTrack(gray, mask=mask, **params) on one (H, W) uint8 frame -> (n, 2) float32 corners (x, y), strongest
-        first.  gray None: the context's resident frame (the `nxt` of the last lk_track, or the last frame given here)."""
+    def good_features(self, gray, mask=None, useHarrisDetector=False, k=0.04, **params) -> np.ndarray:
+        """cv2.goodFeaturesToTrack(gray, mask=mask, useHarrisDetector=..., k=..., **params) on one (H, W) uint8 frame -> (n, 2) float32
+        corners (x, y), strongest first.  gray None: the context's resident frame (the `nxt` of the last lk_track, or the last frame
+        given here).  useHarrisDetector: the Harris response with `k` as the score (mav_good_features_score)."""
         p = gftt_defaults(**params)
         gray, mask = self._gray1(gray, "gray"), self._mask1(mask)
         out = np.empty((max(int(p.max_corners), 1), 2), np.float32)
         n = C.c_int()
-        if mask is None:
+        if useHarrisDetector:
+            sc = corner_score(True, k)
+            check(self.lib.mav_good_features_score(self.h, _ptr(gray), _ptr(mask), C.byref(p), C.byref(sc), _ptr(out), C.byref(n)))
+        elif mask is None:
             check(self.lib.mav_good_features(self.h, _ptr(gray), C.byref(p), _ptr(out), C.byref(n)))
         else:
             check(self.lib.mav_good_features_ex(self.h, _ptr(gray), _ptr(mask), C.byref(p), _ptr(out), C.byref(n)))
         return out[:n.value].copy()
 
-    def good_features_enqueue(self, gray_ptr, corners_ptr, count_ptr, mask_ptr=None, **params):
+    def good_features_enqueue(self, gray_ptr, corners_ptr, count_ptr, mask_ptr=None, useHarrisDetector=False, k=0.04, **params):
         """mav_good_features_ex_dev: device pointers in and out, enqueue only.  gray_ptr None: the resident frame.  corners_ptr:
-        max_corners x 2 float32, count_ptr: one int32 (the corner count, or -(candidates) when they overflow the buffer)."""
-        check(self.lib.mav_good_features_ex_dev(self.h, gray_ptr, mask_ptr, C.byref(gftt_defaults(**params)), corners_ptr, count_ptr))
+        max_corners x 2 float32, count_ptr: one int32 (the corner count, or -(candidates) when they overflow the buffer).
+        useHarrisDetector: mav_good_features_score_dev with the Harris response and `k`."""
+        p = gftt_defaults(**params)
+        if useHarrisDetector:
+            sc = corner_score(True, k)
+            check(self.lib.mav_good_features_score_dev(self.h, gray_ptr, mask_ptr, C.byref(p), C.byref(sc), corners_ptr, count_ptr))
+        else:
+            check(self.lib.mav_good_features_ex_dev(self.h, gray_ptr, mask_ptr, C.byref(p), corners_ptr, count_ptr))
 
     def lk_track_enqueue(self, prev_ptr, next_ptr, pts_ptr, n_max: int, n_ptr, next_pts_ptr, status_ptr, **params):
         """mav_lk_track_ex_dev: mav_lk_track_dev for up to n_max points whose count is the int32 at the device pointer n_ptr."""
@@ -1256,6 +1291,32 @@ class Context:
         check(self.lib.mav_lk_track(self.h, _ptr(prev), _ptr(nxt), _ptr(pts) if n else None, n, C.byref(p), _ptr(out) if n else None,
                                     _ptr(status) if n else None))
         return out, status
+
+    def lk_track_err(self, prev, nxt, pts, next_pts=None, flags=0, **params):
+        """cv2.calcOpticalFlowPyrLK(prev, nxt, pts, next_pts, flags=flags, **params) as cv2's Python call runs it, err always computed
+        -> (next_pts (n, 2) float32, status (n,) uint8, err (n,) float32).  flags: 0 or an OR of OPTFLOW_USE_INITIAL_FLOW (the
+        starting positions are `next_pts`, which is not written) and OPTFLOW_LK_GET_MIN_EIGENVALS (err is level 0's minimum
+        eigenvalue).  With err comes cv2's final bounds test: a point whose last position leaves the bounds ends with status 0, where
+        lk_track keeps it at 1.  prev None: the resident frame; `nxt` becomes the resident frame."""
+        p = lk_defaults(**params)
+        prev, nxt = self._gray1(prev, "prev"), self._gray1(nxt, "nxt")
+        pts = _arr(np.asarray(pts, np.float32).reshape(-1, 2), np.float32)
+        n = pts.shape[0]
+        out = np.empty((n, 2), np.float32)
+        if int(flags) & OPTFLOW_USE_INITIAL_FLOW:
+            if next_pts is None:
+                raise ValueError("lk_track_err: OPTFLOW_USE_INITIAL_FLOW needs the starting positions in next_pts")
+            out[:] = _arr(np.asarray(next_pts, np.float32).reshape(-1, 2), np.float32, (n, 2), "next_pts")
+        status, err = np.empty(n, np.uint8), np.empty(n, np.float32)
+        check(self.lib.mav_lk_track_err(self.h, _ptr(prev), _ptr(nxt), _ptr(pts) if n else None, n, C.byref(p), int(flags),
+                                        _ptr(out) if n else None, _ptr(status) if n else None, _ptr(err) if n else None))
+        return out, status, err
+
+    def lk_track_err_enqueue(self, prev_ptr, next_ptr, pts_ptr, n_max: int, n_ptr, next_pts_ptr, status_ptr, err_ptr, flags=0, **params):
+        """mav_lk_track_err_dev: device pointers, enqueue only.  n_ptr: the int32 point count on the device, or None (n_max points
+        run).  next_pts_ptr is read first under OPTFLOW_USE_INITIAL_FLOW and may equal pts_ptr; err_ptr may be None."""
+        check(self.lib.mav_lk_track_err_dev(self.h, prev_ptr, next_ptr, pts_ptr, int(n_max), n_ptr, C.byref(lk_defaults(**params)), int(flags),
+                                            next_pts_ptr, status_ptr, err_ptr))
 
     def lk_track_dev(self, prev_ptr, next_ptr, pts_ptr, n: int, next_pts_ptr, status_ptr, **params):
         """mav_lk_track_dev: device pointers, enqueue only."""
@@ -1295,6 +1356,13 @@ class Context:
     def stage_min_eigen(self, img, block_size: int = 7) -> np.ndarray:
         out = np.empty((self.H, self.W), np.float32)
         check(self.lib.mav_stage_min_eigen(self.h, _ptr(self._gray1(img, "img")), int(block_size), _ptr(out)))
+        return out
+
+    def stage_corner_response(self, img, block_size: int = 7, useHarrisDetector=False, k=0.04) -> np.ndarray:
+        """The corner score map (H, W) float32: the Harris response, or stage_min_eigen's bytes without useHarrisDetector."""
+        out = np.empty((self.H, self.W), np.float32)
+        sc = corner_score(useHarrisDetector, k)
+        check(self.lib.mav_stage_corner_response(self.h, _ptr(self._gray1(img, "img")), int(block_size), C.byref(sc), _ptr(out)))
         return out
 
     # -- stage hooks (parity tests) --------------------------------------------------------------------------

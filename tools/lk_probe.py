@@ -13,7 +13,16 @@ next one (the new frame's pyramid, the previous frame's Scharr pairs, the tracke
   get_features_ms  wall time of detector.LucasKanade.get_features on host BGR frames (gray conversion, uploads and downloads included)
   chain_ms         wall time per frame of the enqueue-only chain, in a pass of its own without profiling: good_features_enqueue(None)
                    then lk_track_enqueue reading the count on the device, one sync() per frame
-and the histogram of tracker iterations per (point, level) over all timed frames.  Prints one JSON line."""
+and the histogram of tracker iterations per (point, level) over all timed frames.  Prints one JSON line.
+
+    python tools/lk_probe.py --track [--points 2000] [--reps 30] [--rounds 3] [--sizes 1280x720,1920x1080]
+
+The tracker kernel alone, with and without cv2's `err`: one context per size in ONE process, the sizes taken in alternation `rounds`
+times, `reps` calls per visit and form on one frame pair with `points` points (the pair's corners, filled up with random points).
+Per form the HIP-event time of the class "lk_track" per call, median and minimum over all visits:
+  plain     mav_lk_track_dev                                  err_null  mav_lk_track_err_dev, flags 0, no err buffer
+  err       mav_lk_track_err_dev with an err buffer           min_eig   the same with OPTFLOW_LK_GET_MIN_EIGENVALS
+A library without the err form (an older build the script is pointed at) reports `plain` alone.  Prints one JSON line."""
 from __future__ import annotations
 
 import argparse
@@ -98,12 +107,64 @@ def probe(W: int, H: int, frames: int, warmup: int) -> dict:
     return out
 
 
+def track_probe(sizes, points: int, reps: int, rounds: int) -> list:
+    has_err = hasattr(_lib.Context, "lk_track_err_enqueue")
+    forms = ["plain"] + (["err_null", "err", "min_eig"] if has_err else [])
+    state = []
+    for W, H in sizes:
+        f0, f1 = synth.make_sequence(W, H, 2, seed=0)
+        c = _lib.Context(W, H, 1)
+        d0, d1 = c.alloc(W * H).upload(f0), c.alloc(W * H).upload(f1)
+        pts = c.good_features(f0, max_corners=points)
+        fill = (np.random.default_rng(5).random((points - len(pts), 2)) * (W - 1, H - 1)).astype(np.float32)
+        pts = np.concatenate([pts, fill])
+        d_pts, d_out, d_status, d_err = c.alloc(points * 8).upload(pts), c.alloc(points * 8), c.alloc(points), c.alloc(points * 4)
+        c.profile_enable(1)
+        state.append(dict(W=W, H=H, c=c, d0=d0, d1=d1, bufs=(d_pts, d_out, d_status, d_err), corners=int(points - len(fill)),
+                          ms={f: [] for f in forms}))
+
+    def call(st, form):
+        c, (d_pts, d_out, d_status, d_err) = st["c"], st["bufs"]
+        if form == "plain":
+            c.lk_track_dev(st["d0"].ptr, st["d1"].ptr, d_pts.ptr, points, d_out.ptr, d_status.ptr)
+        else:
+            c.lk_track_err_enqueue(st["d0"].ptr, st["d1"].ptr, d_pts.ptr, points, None, d_out.ptr, d_status.ptr,
+                                   None if form == "err_null" else d_err.ptr, flags=8 if form == "min_eig" else 0)
+        c.sync()
+
+    for r in range(rounds + 1):                               # round 0 warms up
+        for st in state:
+            for form in forms:
+                for i in range(reps):
+                    before = st["c"].profile_get()["lk_track"][0]
+                    call(st, form)
+                    if r:
+                        st["ms"][form].append(st["c"].profile_get()["lk_track"][0] - before)
+    res = []
+    for st in state:
+        row = dict(W=st["W"], H=st["H"], points=points, corners=st["corners"], calls=rounds * reps)
+        for f in forms:
+            row[f + "_ms"] = round(float(np.median(st["ms"][f])), 4)
+            row[f + "_min_ms"] = round(float(np.min(st["ms"][f])), 4)
+        res.append(row)
+        st["c"].close()
+    return res
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--sizes", default="1280x720,1920x1080")
+    ap.add_argument("--track", action="store_true", help="the tracker kernel with and without err (see the module text)")
+    ap.add_argument("--points", type=int, default=2000)
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()
+    if a.track:
+        sizes = [tuple(int(v) for v in s.split("x")) for s in a.sizes.split(",")]
+        print(json.dumps(dict(tool="lk_probe", mode="track", results=track_probe(sizes, a.points, a.reps, a.rounds))))
+        return
     res = [probe(*(int(v) for v in s.split("x")), a.frames, a.warmup) for s in a.sizes.split(",")]
     print(json.dumps(dict(tool="lk_probe", results=res)))
 
