@@ -1295,6 +1295,27 @@ static int check_launch(const char* what)
     if (e != hipSuccess) return fail(MAV_ERR_HIP, "launch of %s failed: %s", what, hipGetErrorString(e));
     return MAV_OK;
 }
+// The prologue of an entry point that takes a batch: a context, a batch it was created for, its device current.
+static int check_dev_call(mav_ctx* c, int batch, const char* fn)
+{
+    if (!c) return fail(MAV_ERR_ARG, "%s: NULL context", fn);
+    if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "%s: batch %d outside [1, %d]", fn, batch, c->max_batch);
+    HIPCHK(hipSetDevice(c->device));
+    return MAV_OK;
+}
+// The caller's parameters, or the defaults where it passed NULL.
+static mav_thr_params thr_or_defaults(const mav_thr_params* tp)
+{
+    mav_thr_params t;
+    if (tp) t = *tp; else mav_thr_defaults(&t);
+    return t;
+}
+static int foe_or_defaults(const mav_foe_params* fp, mav_foe_params* f)
+{
+    if (fp) *f = *fp; else mav_foe_defaults(f);
+    if (f->n_pairs < 1 || f->n_pairs > 4096) return fail(MAV_ERR_ARG, "n_pairs %d outside [1, 4096]", f->n_pairs);
+    return MAV_OK;
+}
 
 // ---- Farneback: the schedule of one group of pairs --------------------------------------------------------------------
 static BlurParams blur_of(const mav_ctx* c, const Layer& l)
@@ -1713,7 +1734,6 @@ static void snapshot_initial_flow(mav_ctx* c, const float* flow0, int n)
 template <typename T>
 static int farneback_run(mav_ctx* c, const T* prev, const T* next, int batch, const float* flow_init, float* flow)
 {
-    HIPCHK(hipSetDevice(c->device));
     CHK(ensure_workspace(c));
     // A frame SEQUENCE -- the caller's two batches are views of one run of batch + 1 consecutive frames, next = prev + one frame,
     // which is how a video goes through the reference's loop (src/farneback.py:76-80 with prevgray = the last call's frame) -- has
@@ -1754,21 +1774,27 @@ static int depth_esize(int depth)
 {
     return depth == MAV_DEPTH_8U ? 1 : depth == MAV_DEPTH_16U ? 2 : depth == MAV_DEPTH_32F ? 4 : 0;
 }
+// f(tag) with a null pointer to the pixel type of a MAV_DEPTH_* code the caller has checked (depth_esize): the one depth dispatch
+template <typename F>
+static auto with_depth(int depth, F&& f)
+{
+    if (depth == MAV_DEPTH_16U) return f((const uint16_t*)nullptr);
+    if (depth == MAV_DEPTH_32F) return f((const float*)nullptr);
+    return f((const uint8_t*)nullptr);
+}
 // The three device-pointer entry points: fn = the name their messages start with; need_init: flow_init may not be NULL.
 static int farneback_dev(mav_ctx* c, const char* fn, const void* prev, const void* next, int depth, int batch, const float* flow_init,
                          bool need_init, float* flow)
 {
     if (!c || !prev || !next || !flow || (need_init && !flow_init)) return fail(MAV_ERR_ARG, "%s: NULL argument", fn);
     if (!depth_esize(depth)) return fail(MAV_ERR_ARG, "%s: depth %d is none of MAV_DEPTH_8U / 16U / 32F", fn, depth);
-    if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "batch %d outside [1, %d]", batch, c->max_batch);
+    CHK(check_dev_call(c, batch, fn));
     if (flow_init) {
         const size_t n = (size_t)batch * 2 * c->n0;
         if (flow_init != flow && flow_init < flow + n && flow < flow_init + n)
             return fail(MAV_ERR_ARG, "%s: flow_init and flow overlap without being the same field", fn);
     }
-    if (depth == MAV_DEPTH_16U) return farneback_run(c, (const uint16_t*)prev, (const uint16_t*)next, batch, flow_init, flow);
-    if (depth == MAV_DEPTH_32F) return farneback_run(c, (const float*)prev, (const float*)next, batch, flow_init, flow);
-    return farneback_run(c, (const uint8_t*)prev, (const uint8_t*)next, batch, flow_init, flow);
+    return with_depth(depth, [&](auto* px) { return farneback_run(c, (decltype(px))prev, (decltype(px))next, batch, flow_init, flow); });
 }
 extern "C" int mav_farneback_dev(mav_ctx* c, const uint8_t* prev, const uint8_t* next, int batch, float* flow)
 {
@@ -1861,45 +1887,60 @@ static int upload_derot(mav_ctx* c, const double* omega, const double* dt, const
     return MAV_OK;
 }
 
-static int detect_dev(mav_ctx* c, const float* flow32, const double* flow64, const DerotParams* derot, const uint32_t* samples,
-                      const uint8_t* sky, int batch, const mav_foe_params* fp, const mav_thr_params* tp, const double* foe_in,
-                      double* phi, uint8_t* mask_fixed, uint8_t* mask_dyn, unsigned long long* max_phi_bits, double* foe_out,
-                      mav_result* results, int32_t* box_out)
+// What one detection call reads and writes, all device pointers; whatever stays NULL is not there / not wanted.
+struct DetectArgs {
+    const float* flow32 = nullptr;           // the flow field: this one (float32 arithmetic for frame-0 pairs, derot says which) ...
+    const double* flow64 = nullptr;          // ... or this one
+    const DerotParams* derot = nullptr;
+    const uint8_t* sky = nullptr;
+    const uint32_t* samples = nullptr;       // given: the FoE is estimated from them with foe_par (NULL: the defaults) and goes to foe_out
+    const mav_foe_params* foe_par = nullptr; // (NULL: the context's own buffer); not given: the phi / mask stage reads foe_in
+    const double* foe_in = nullptr;
+    double* foe_out = nullptr;
+    const mav_thr_params* thr = nullptr;     // given: the phi / mask stage runs even if none of its outputs below is wanted
+    double* phi = nullptr;
+    uint8_t *mask_fixed = nullptr, *mask_dyn = nullptr;
+    unsigned long long* max_phi_bits = nullptr;
+    mav_result* results = nullptr;
+    int32_t* box_out = nullptr;
+    void set_flow(const float* f) { flow32 = f; }
+    void set_flow(const double* f) { flow64 = f; }
+};
+static int detect_dev(mav_ctx* c, int batch, const DetectArgs& a)
 {
     const int W = c->W, H = c->H;
-    const double* foe = foe_in;
-    const bool want_phi = tp || phi || mask_fixed || mask_dyn || results || box_out || max_phi_bits;
-    if (samples) {
+    const double* foe = a.foe_in;
+    const bool want_phi = a.thr || a.phi || a.mask_fixed || a.mask_dyn || a.results || a.box_out || a.max_phi_bits;
+    if (a.samples) {
         mav_foe_params f;
-        if (fp) f = *fp; else mav_foe_defaults(&f);
-        if (f.n_pairs < 1 || f.n_pairs > 4096) return fail(MAV_ERR_ARG, "n_pairs %d outside [1, 4096]", f.n_pairs);
+        CHK(foe_or_defaults(a.foe_par, &f));
         CHK(ensure_foe_scratch(c, f.n_pairs));
-        double* fo = foe_out ? foe_out : c->foe_dev;
+        double* fo = a.foe_out ? a.foe_out : c->foe_dev;
         ProfScope ps(c, K_FOE);
         // the candidates kernel also initialises the pair's box accumulators and tickets, the vote's last workgroup writes the FoE:
         // two launches where round 2 had four (candidates, vote, FoE finalize, box init)
         int32_t* init_box = want_phi ? c->box_acc : nullptr;
-        if (flow32)
-            launch_foe_f32(c->stream, flow32, derot, samples, batch, W, H, f.n_pairs, sq_threshold(f.mag_threshold),
-                           sq_threshold_f32(f.mag_threshold), sq_threshold(f.ransac_threshold), c->foe_sc, fo, init_box, max_phi_bits);
+        if (a.flow32)
+            launch_foe_f32(c->stream, a.flow32, a.derot, a.samples, batch, W, H, f.n_pairs, sq_threshold(f.mag_threshold),
+                           sq_threshold_f32(f.mag_threshold), sq_threshold(f.ransac_threshold), c->foe_sc, fo, init_box, a.max_phi_bits);
         else
-            launch_foe_f64(c->stream, flow64, samples, batch, W, H, f.n_pairs, sq_threshold(f.mag_threshold),
-                           sq_threshold(f.ransac_threshold), c->foe_sc, fo, init_box, max_phi_bits);
+            launch_foe_f64(c->stream, a.flow64, a.samples, batch, W, H, f.n_pairs, sq_threshold(f.mag_threshold),
+                           sq_threshold(f.ransac_threshold), c->foe_sc, fo, init_box, a.max_phi_bits);
         foe = fo;
     }
     if (want_phi) {
         if (!foe) return fail(MAV_ERR_ARG, "phi/mask stage needs a FoE (samples or foe)");
-        mav_thr_params t;
-        if (tp) t = *tp; else mav_thr_defaults(&t);
-        if (!samples) { ProfScope ps(c, K_MISC); launch_box_init(c->stream, c->box_acc, max_phi_bits, c->foe_sc.done, batch); }
+        const mav_thr_params t = thr_or_defaults(a.thr);
+        if (!a.samples) { ProfScope ps(c, K_MISC); launch_box_init(c->stream, c->box_acc, a.max_phi_bits, c->foe_sc.done, batch); }
         // the pair's record (box, FoE) is written by the phi kernel's last workgroup of the pair: no finalize launch
         PhiLaunch pl;
-        pl.done = c->foe_sc.done; pl.results = results; pl.box_out = box_out; pl.screen = c->phi_screen; pl.yloop = c->phi_yloop;
+        pl.done = c->foe_sc.done; pl.results = a.results; pl.box_out = a.box_out; pl.screen = c->phi_screen; pl.yloop = c->phi_yloop;
         ProfScope ps(c, K_PHI);
-        if (flow32)
-            launch_phi_mask_f32(c->stream, flow32, derot, foe, sky, batch, W, H, t, phi, mask_fixed, mask_dyn, c->box_acc, max_phi_bits, pl);
+        if (a.flow32)
+            launch_phi_mask_f32(c->stream, a.flow32, a.derot, foe, a.sky, batch, W, H, t, a.phi, a.mask_fixed, a.mask_dyn, c->box_acc,
+                                a.max_phi_bits, pl);
         else
-            launch_phi_mask_f64(c->stream, flow64, foe, sky, batch, W, H, t, phi, mask_fixed, mask_dyn, c->box_acc, max_phi_bits, pl);
+            launch_phi_mask_f64(c->stream, a.flow64, foe, a.sky, batch, W, H, t, a.phi, a.mask_fixed, a.mask_dyn, c->box_acc, a.max_phi_bits, pl);
     }
     return check_launch("detection kernels");
 }
@@ -1908,17 +1949,16 @@ extern "C" int mav_detect_dev(mav_ctx* c, const float* flow, const uint32_t* sam
                               const uint8_t* frame0, const uint8_t* sky, int batch, const mav_foe_params* fp,
                               const mav_thr_params* tp, double* phi, uint8_t* mask_fixed, uint8_t* mask_dyn, mav_result* results)
 {
-    if (!c || !flow || !samples || !results) return fail(MAV_ERR_ARG, "mav_detect: NULL argument");
-    if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "batch %d outside [1, %d]", batch, c->max_batch);
-    HIPCHK(hipSetDevice(c->device));
-    const DerotParams* derot = nullptr;
-    CHK(upload_derot(c, omega, dt, frame0, batch, false, &derot));
-    mav_thr_params t;
-    if (tp) t = *tp; else mav_thr_defaults(&t);
-    CHK(detect_dev(c, flow, nullptr, derot, samples, sky, batch, fp, &t, nullptr, phi, mask_fixed, mask_dyn, nullptr, nullptr,
-                   results, nullptr));
-    // what mav_last_render reads: the FoE went to the context's own buffer (detect_dev with foe_out == NULL)
-    c->last_render.flow = flow; c->last_render.derot = derot; c->last_render.foe = c->foe_dev; c->last_render.sky = sky;
+    if (!c || !flow || !samples || !results) return fail(MAV_ERR_ARG, "mav_detect_dev: NULL argument");
+    CHK(check_dev_call(c, batch, "mav_detect_dev"));
+    const mav_thr_params t = thr_or_defaults(tp);
+    DetectArgs a;
+    a.flow32 = flow; a.samples = samples; a.sky = sky; a.foe_par = fp; a.thr = &t;
+    a.phi = phi; a.mask_fixed = mask_fixed; a.mask_dyn = mask_dyn; a.results = results;
+    CHK(upload_derot(c, omega, dt, frame0, batch, false, &a.derot));
+    CHK(detect_dev(c, batch, a));
+    // what mav_last_render reads: the FoE went to the context's own buffer (detect_dev without foe_out)
+    c->last_render.flow = flow; c->last_render.derot = a.derot; c->last_render.foe = c->foe_dev; c->last_render.sky = sky;
     c->last_render.thr = t; c->last_render.batch = batch; c->last_render.mask_fixed = mask_fixed;
     return MAV_OK;
 }
@@ -1929,8 +1969,7 @@ extern "C" int mav_process_batch_dev(mav_ctx* c, const uint8_t* prev, const uint
                                      uint8_t* mask_fixed, uint8_t* mask_dyn, mav_result* results)
 {
     if (!c || !prev || !next || !samples || !results) return fail(MAV_ERR_ARG, "mav_process_batch: NULL argument");
-    if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "batch %d outside [1, %d]", batch, c->max_batch);
-    HIPCHK(hipSetDevice(c->device));
+    CHK(check_dev_call(c, batch, "mav_process_batch_dev"));
     if (!flow) {
         CHK(ensure_flow_ws(c));
         flow = c->flow_ws;
@@ -2150,58 +2189,115 @@ extern "C" int mav_worker_drain(mav_ctx* c)
 }
 
 // ---- host-pointer wrappers -----------------------------------------------------------------------------------
-// A staging buffer of one host-pointer call.  It borrows the context's next scratch block (grown when too small, never
-// shrunk or freed before mav_destroy): once a call shape has been seen the staged path allocates nothing.  The host entry
-// points are synchronous (they end in mav_sync), so a block is idle again when the next call takes it.
-struct DevBuf {
-    void* p = nullptr;
-    int alloc(mav_ctx* c, size_t bytes)
-    {
-        if (c->scratch_next == c->scratch.size()) c->scratch.emplace_back();
-        mav_ctx::Block& b = c->scratch[c->scratch_next++];
-        CHK(grow_buffer(c, &b.p, &b.cap, bytes ? bytes : 1, MEM_OTHER, READ_ON_COMPUTE, RELEASE_FIRST, "staging block"));
-        p = b.p;
-        return MAV_OK;
-    }
-    int upload(mav_ctx* c, const void* src, size_t bytes)
-    {
-        CHK(alloc(c, bytes));
-        HIPCHK(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, c->stream));
-        return MAV_OK;
-    }
-    template <typename T> T* as() { return (T*)p; }
-};
-// The two frame batches of a host-pointer call -> device.  When the caller's batches are views of one run of batch + 1 frames
-// (next == prev + one frame) the run crosses PCIe once and keeps that layout on the device, which mav_farneback_dev recognises.
-// esize: bytes per pixel (the frame run is recognised in bytes, whatever the depth).
-static int upload_frames(mav_ctx* c, const void* prev, const void* next, int batch, int esize, DevBuf& dp, DevBuf& dn, const void** dprev,
-                         const void** dnext)
-{
-    const size_t fb = c->n0 * esize, n = fb * batch;
-    if ((const char*)next == (const char*)prev + fb) {
-        CHK(dp.upload(c, prev, n + fb));
-        CHK(dn.alloc(c, 1));                              // keeps the staging slots of the two call forms aligned
-        *dprev = dp.p; *dnext = dp.as<char>() + fb;
-        return MAV_OK;
-    }
-    CHK(dp.upload(c, prev, n)); CHK(dn.upload(c, next, n));
-    *dprev = dp.p; *dnext = dn.p;
-    return MAV_OK;
-}
 static int download(mav_ctx* c, void* dst, const void* src, size_t bytes)
 {
     HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
     return MAV_OK;
 }
-static int check_batch(mav_ctx* c, int batch, const char* fn)
+// One host-pointer call: its staging blocks and uploads, and the downloads and the one synchronisation it ends in.
+// A block is the context's next scratch block (grown when too small, never shrunk or freed before mav_destroy): once a call shape has
+// been seen the staged path allocates nothing.  The host entry points are synchronous (finish() ends in mav_sync), so a block is idle
+// again when the next call takes it.  Errors stick: after the first failure in() / out() / scratch() / fetch() do nothing and return
+// NULL, and staged() / finish() return its code -- a call site asks once, before it launches.
+struct HostCall {
+    mav_ctx* const c;
+    const char* const fn;            // the entry point, for messages
+    int rc = MAV_OK;
+    HostCall(mav_ctx* c_, const char* fn_) : c(c_), fn(fn_) {}
+    HostCall(const HostCall&) = delete;
+    ~HostCall() { if (appended) c->scratch_next = mark; }     // synchronous: an appending call's blocks are free again on return
+
+    // Two ways to begin.  A fresh call (of `batch` pairs or images, where it has a batch) starts again at block 0 ...
+    int fresh(int batch = 1)
+    {
+        if ((rc = check_dev_call(c, batch, fn)) != MAV_OK) return rc;
+        c->scratch_next = 0;
+        c->last_mf = c->last_md = nullptr; c->last_mask_batch = 0;     // ... and may overwrite the previous call's masks
+        c->last_render.batch = 0;                                       // ... and its flow, FoE and sky
+        return MAV_OK;
+    }
+    int fresh_layer(int k, const Layer** l)      // ... a stage hook on layer k
+    {
+        if (!c) return rc = fail(MAV_ERR_ARG, "%s: NULL context", fn);
+        if (k < 0 || k >= (int)c->layers.size()) return rc = fail(MAV_ERR_ARG, "%s: layer %d out of range", fn, k);
+        *l = &c->layers[k];
+        return fresh();
+    }
+    // A call that reads what the last call left resident takes the NEXT free blocks: the last call's blocks (its flow, sky and masks
+    // among them) and the last_* state stay untouched, and the blocks go back when this object does, whichever way the call ends.
+    int after_last()
+    {
+        if ((rc = check_dev_call(c, 1, fn)) != MAV_OK) return rc;
+        mark = c->scratch_next;
+        appended = true;
+        return MAV_OK;
+    }
+
+    // Staging, each returning the device pointer.  A NULL host pointer takes no block, registers nothing and returns NULL.
+    template <typename T> T* scratch(size_t bytes) { return (T*)block(bytes); }              // a block
+    template <typename T> T* in(const T* host, size_t bytes)                                 // a block, filled from the host now
+    {
+        T* d = host ? (T*)block(bytes) : nullptr;
+        if (d) rc = upload(d, host, bytes);
+        return rc == MAV_OK ? d : nullptr;
+    }
+    template <typename T> T* out(T* host, size_t bytes)                                      // a block, brought to the host by finish()
+    {
+        T* d = host ? (T*)block(bytes) : nullptr;
+        fetch(host, d, bytes);
+        return d;
+    }
+    void fetch(void* host, const void* dev, size_t bytes)       // any device memory, brought to the host by finish()
+    {
+        if (rc != MAV_OK || !host) return;
+        assert(n_down < MAX_DOWN);
+        down[n_down++] = {host, dev, bytes};
+    }
+    int staged() const { return rc; }
+    // the registered downloads, in the order they were registered, and the call's one synchronisation
+    int finish()
+    {
+        CHK(rc);
+        const int n = n_down;
+        n_down = 0;
+        for (int i = 0; i < n; i++) CHK(download(c, down[i].host, down[i].dev, down[i].bytes));
+        return mav_sync(c);
+    }
+
+private:
+    enum { MAX_DOWN = 6 };
+    struct Down { void* host; const void* dev; size_t bytes; } down[MAX_DOWN];
+    int n_down = 0;
+    size_t mark = 0;
+    bool appended = false;
+    void* block(size_t bytes)
+    {
+        if (rc != MAV_OK) return nullptr;
+        if (c->scratch_next == c->scratch.size()) c->scratch.emplace_back();
+        mav_ctx::Block& b = c->scratch[c->scratch_next++];
+        rc = grow_buffer(c, &b.p, &b.cap, bytes ? bytes : 1, MEM_OTHER, READ_ON_COMPUTE, RELEASE_FIRST, "staging block");
+        return rc == MAV_OK ? b.p : nullptr;
+    }
+    int upload(void* dst, const void* src, size_t bytes)
+    {
+        HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+        return MAV_OK;
+    }
+};
+// The two frame batches of a host-pointer call -> device.  When the caller's batches are views of one run of batch + 1 frames
+// (next == prev + one frame) the run crosses PCIe once and keeps that layout on the device, which mav_farneback_dev recognises.
+// esize: bytes per pixel (the frame run is recognised in bytes, whatever the depth).
+static void upload_frames(HostCall& h, const void* prev, const void* next, int batch, int esize, const void** dprev, const void** dnext)
 {
-    if (!c) return fail(MAV_ERR_ARG, "%s: NULL context", fn);
-    if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "%s: batch %d outside [1, %d]", fn, batch, c->max_batch);
-    HIPCHK(hipSetDevice(c->device));
-    c->scratch_next = 0;              // a new host-pointer call: its staging buffers start again at block 0
-    c->last_mf = c->last_md = nullptr; c->last_mask_batch = 0;     // ... and may overwrite the previous call's masks
-    c->last_render.batch = 0;                                       // ... and its flow, FoE and sky
-    return MAV_OK;
+    const size_t fb = h.c->n0 * esize, n = fb * batch;
+    if ((const char*)next == (const char*)prev + fb) {
+        *dprev = h.in(prev, n + fb);
+        h.scratch<void>(1);                               // keeps the staging slots of the two call forms aligned
+        *dnext = (const char*)*dprev + fb;
+        return;
+    }
+    *dprev = h.in(prev, n);
+    *dnext = h.in(next, n);
 }
 
 // The three host-pointer entry points: frames (and the initial flow, if any) up, farneback_dev in place on the device, flow down.
@@ -2209,17 +2305,17 @@ static int farneback_host(mav_ctx* c, const char* fn, const void* prev, const vo
                           bool need_init, float* flow)
 {
     if (c && !depth_esize(depth)) return fail(MAV_ERR_ARG, "%s: depth %d is none of MAV_DEPTH_8U / 16U / 32F", fn, depth);
-    CHK(check_batch(c, batch, fn));
+    HostCall h(c, fn);
+    CHK(h.fresh(batch));
     if (!prev || !next || !flow || (need_init && !flow_init)) return fail(MAV_ERR_ARG, "%s: NULL argument", fn);
-    const size_t n = c->n0 * batch;
-    DevBuf dp, dn, df;
+    const size_t bytes = c->n0 * batch * 2 * sizeof(float);
     const void *dprev, *dnext;
-    CHK(upload_frames(c, prev, next, batch, depth_esize(depth), dp, dn, &dprev, &dnext));
-    if (flow_init) CHK(df.upload(c, flow_init, n * 2 * sizeof(float)));
-    else CHK(df.alloc(c, n * 2 * sizeof(float)));
-    CHK(farneback_dev(c, fn, dprev, dnext, depth, batch, flow_init ? df.as<float>() : nullptr, false, df.as<float>()));
-    CHK(download(c, flow, df.p, n * 2 * sizeof(float)));
-    return mav_sync(c);
+    upload_frames(h, prev, next, batch, depth_esize(depth), &dprev, &dnext);
+    float* df = flow_init ? h.in(flow_init, bytes) : h.scratch<float>(bytes);
+    h.fetch(flow, df, bytes);
+    CHK(h.staged());
+    CHK(farneback_dev(c, fn, dprev, dnext, depth, batch, flow_init ? df : nullptr, false, df));
+    return h.finish();
 }
 extern "C" int mav_farneback(mav_ctx* c, const uint8_t* prev, const uint8_t* next, int batch, float* flow)
 {
@@ -2235,147 +2331,126 @@ extern "C" int mav_farneback_ex(mav_ctx* c, const void* prev, const void* next, 
 }
 extern "C" int mav_derotate(mav_ctx* c, const float* flow, const double* omega, const double* dt, int batch, double* flow_out)
 {
-    CHK(check_batch(c, batch, "mav_derotate"));
+    HostCall h(c, "mav_derotate");
+    CHK(h.fresh(batch));
     if (!flow || !omega || !flow_out) return fail(MAV_ERR_ARG, "mav_derotate: NULL argument");
     const size_t n = c->n0 * batch * 2;
-    DevBuf df, dout;
-    CHK(df.upload(c, flow, n * sizeof(float))); CHK(dout.alloc(c, n * sizeof(double)));
+    const float* df = h.in(flow, n * sizeof(float));
+    double* dout = h.out(flow_out, n * sizeof(double));
+    CHK(h.staged());
     const DerotParams* derot = nullptr;
     CHK(upload_derot(c, omega, dt, nullptr, batch, true, &derot));
-    launch_derotate(c->stream, df.as<float>(), derot, batch, c->W, c->H, dout.as<double>());
+    launch_derotate(c->stream, df, derot, batch, c->W, c->H, dout);
     CHK(check_launch("derotate"));
-    CHK(download(c, flow_out, dout.p, n * sizeof(double)));
-    return mav_sync(c);
+    return h.finish();
 }
 
-extern "C" int mav_foe_dense(mav_ctx* c, const double* flow, const uint32_t* samples, int batch, const mav_foe_params* fp, double* foe)
-{
-    CHK(check_batch(c, batch, "mav_foe_dense"));
-    if (!flow || !samples || !foe) return fail(MAV_ERR_ARG, "mav_foe_dense: NULL argument");
-    mav_foe_params f;
-    if (fp) f = *fp; else mav_foe_defaults(&f);
-    if (f.n_pairs < 1 || f.n_pairs > 4096) return fail(MAV_ERR_ARG, "n_pairs %d outside [1, 4096]", f.n_pairs);
-    DevBuf df, ds, dfoe;
-    CHK(df.upload(c, flow, c->n0 * batch * 2 * sizeof(double)));
-    CHK(ds.upload(c, samples, sizeof(uint32_t) * 4 * (size_t)f.n_pairs * batch));
-    CHK(dfoe.alloc(c, sizeof(double) * 2 * batch));
-    CHK(detect_dev(c, nullptr, df.as<double>(), nullptr, ds.as<uint32_t>(), nullptr, batch, &f, nullptr, nullptr, nullptr, nullptr,
-                   nullptr, nullptr, dfoe.as<double>(), nullptr, nullptr));
-    CHK(download(c, foe, dfoe.p, sizeof(double) * 2 * batch));
-    return mav_sync(c);
-}
-
-extern "C" int mav_phi_mask(mav_ctx* c, const double* flow, const double* foe, const uint8_t* sky, int batch, const mav_thr_params* tp,
-                            double* phi, uint8_t* mask_fixed, uint8_t* mask_dyn, double* max_phi)
-{
-    CHK(check_batch(c, batch, "mav_phi_mask"));
-    if (!flow || !foe) return fail(MAV_ERR_ARG, "mav_phi_mask: NULL argument");
-    const size_t n = c->n0 * batch;
-    mav_thr_params t;
-    if (tp) t = *tp; else mav_thr_defaults(&t);
-    DevBuf df, dfoe, dsky, dphi, dmf, dmd;
-    CHK(df.upload(c, flow, n * 2 * sizeof(double)));
-    CHK(dfoe.upload(c, foe, sizeof(double) * 2 * batch));
-    if (sky) CHK(dsky.upload(c, sky, n));
-    if (phi) CHK(dphi.alloc(c, n * sizeof(double)));
-    if (mask_fixed) CHK(dmf.alloc(c, n));
-    if (mask_dyn) CHK(dmd.alloc(c, n));
-    CHK(detect_dev(c, nullptr, df.as<double>(), nullptr, nullptr, dsky.as<uint8_t>(), batch, nullptr, &t, dfoe.as<double>(),
-                   dphi.as<double>(), dmf.as<uint8_t>(), dmd.as<uint8_t>(), max_phi ? c->u64_scratch : nullptr, nullptr, nullptr,
-                   nullptr));
-    c->last_mf = dmf.as<uint8_t>(); c->last_md = dmd.as<uint8_t>(); c->last_mask_batch = batch;
-    if (phi) CHK(download(c, phi, dphi.p, n * sizeof(double)));
-    if (mask_fixed) CHK(download(c, mask_fixed, dmf.p, n));
-    if (mask_dyn) CHK(download(c, mask_dyn, dmd.p, n));
-    if (max_phi) CHK(download(c, max_phi, c->u64_scratch, sizeof(double) * batch));  // same bits
-    return mav_sync(c);
-}
-
-// ---- the same two calls on a float32 flow array (the reference's frame index 0): float32 arithmetic ----------------
+// ---- FoE and phi / masks of a flow array: float64 (a derotated field), or float32 (the reference's frame index 0: float32 arithmetic) --
 static int frame0_params(mav_ctx* c, int batch, const DerotParams** out)
 {
     std::vector<uint8_t> all(batch, 1);
     return upload_derot(c, nullptr, nullptr, all.data(), batch, true, out);
 }
 
+template <typename T>                // double: mav_foe_dense; float: mav_foe_dense_f32
+static int foe_dense_host(mav_ctx* c, const char* fn, const T* flow, const uint32_t* samples, int batch, const mav_foe_params* fp, double* foe)
+{
+    HostCall h(c, fn);
+    CHK(h.fresh(batch));
+    if (!flow || !samples || !foe) return fail(MAV_ERR_ARG, "%s: NULL argument", fn);
+    mav_foe_params f;
+    CHK(foe_or_defaults(fp, &f));
+    DetectArgs a;
+    a.set_flow(h.in(flow, c->n0 * batch * 2 * sizeof(T)));
+    a.samples = h.in(samples, sizeof(uint32_t) * 4 * (size_t)f.n_pairs * batch);
+    a.foe_out = h.out(foe, sizeof(double) * 2 * batch);
+    a.foe_par = &f;
+    CHK(h.staged());
+    if constexpr (sizeof(T) == sizeof(float)) CHK(frame0_params(c, batch, &a.derot));
+    CHK(detect_dev(c, batch, a));
+    return h.finish();
+}
+extern "C" int mav_foe_dense(mav_ctx* c, const double* flow, const uint32_t* samples, int batch, const mav_foe_params* fp, double* foe)
+{
+    return foe_dense_host(c, "mav_foe_dense", flow, samples, batch, fp, foe);
+}
 extern "C" int mav_foe_dense_f32(mav_ctx* c, const float* flow, const uint32_t* samples, int batch, const mav_foe_params* fp, double* foe)
 {
-    CHK(check_batch(c, batch, "mav_foe_dense_f32"));
-    if (!flow || !samples || !foe) return fail(MAV_ERR_ARG, "mav_foe_dense_f32: NULL argument");
-    mav_foe_params f;
-    if (fp) f = *fp; else mav_foe_defaults(&f);
-    if (f.n_pairs < 1 || f.n_pairs > 4096) return fail(MAV_ERR_ARG, "n_pairs %d outside [1, 4096]", f.n_pairs);
-    DevBuf df, ds, dfoe;
-    CHK(df.upload(c, flow, c->n0 * batch * 2 * sizeof(float)));
-    CHK(ds.upload(c, samples, sizeof(uint32_t) * 4 * (size_t)f.n_pairs * batch));
-    CHK(dfoe.alloc(c, sizeof(double) * 2 * batch));
-    const DerotParams* mode = nullptr;
-    CHK(frame0_params(c, batch, &mode));
-    CHK(detect_dev(c, df.as<float>(), nullptr, mode, ds.as<uint32_t>(), nullptr, batch, &f, nullptr, nullptr, nullptr, nullptr,
-                   nullptr, nullptr, dfoe.as<double>(), nullptr, nullptr));
-    CHK(download(c, foe, dfoe.p, sizeof(double) * 2 * batch));
-    return mav_sync(c);
+    return foe_dense_host(c, "mav_foe_dense_f32", flow, samples, batch, fp, foe);
 }
 
+// T = double: mav_phi_mask.  T = float: mav_phi_mask_f32 -- the kernel stores the float32 angles widened to double (one phi layout
+// for both arithmetic types), so they come down as doubles and are narrowed back, exactly, once the call has finished.
+template <typename T>
+static int phi_mask_host(mav_ctx* c, const char* fn, const T* flow, const double* foe, const uint8_t* sky, int batch, const mav_thr_params* tp,
+                         T* phi, uint8_t* mask_fixed, uint8_t* mask_dyn, T* max_phi)
+{
+    constexpr bool f32 = sizeof(T) == sizeof(float);
+    HostCall h(c, fn);
+    CHK(h.fresh(batch));
+    if (!flow || !foe) return fail(MAV_ERR_ARG, "%s: NULL argument", fn);
+    const size_t n = c->n0 * batch;
+    const mav_thr_params t = thr_or_defaults(tp);
+    std::vector<double> wide(f32 && phi ? n : 0), mx(f32 && max_phi ? batch : 0);
+    double* const hphi = !f32 ? (double*)phi : phi ? wide.data() : nullptr;          // where the doubles land on the host
+    double* const hmax = !f32 ? (double*)max_phi : max_phi ? mx.data() : nullptr;
+    DetectArgs a;
+    a.set_flow(h.in(flow, n * 2 * sizeof(T)));
+    a.foe_in = h.in(foe, sizeof(double) * 2 * batch);
+    a.sky = h.in(sky, n);
+    a.phi = h.out(hphi, n * sizeof(double));
+    a.mask_fixed = h.out(mask_fixed, n);
+    a.mask_dyn = h.out(mask_dyn, n);
+    a.max_phi_bits = max_phi ? c->u64_scratch : nullptr;
+    h.fetch(hmax, c->u64_scratch, sizeof(double) * batch);       // same bits
+    a.thr = &t;
+    CHK(h.staged());
+    if constexpr (f32) CHK(frame0_params(c, batch, &a.derot));
+    CHK(detect_dev(c, batch, a));
+    c->last_mf = a.mask_fixed; c->last_md = a.mask_dyn; c->last_mask_batch = batch;
+    CHK(h.finish());
+    if (f32 && phi) for (size_t i = 0; i < n; i++) phi[i] = (T)wide[i];
+    if (f32 && max_phi) for (int b = 0; b < batch; b++) max_phi[b] = (T)mx[b];
+    return MAV_OK;
+}
+extern "C" int mav_phi_mask(mav_ctx* c, const double* flow, const double* foe, const uint8_t* sky, int batch, const mav_thr_params* tp,
+                            double* phi, uint8_t* mask_fixed, uint8_t* mask_dyn, double* max_phi)
+{
+    return phi_mask_host(c, "mav_phi_mask", flow, foe, sky, batch, tp, phi, mask_fixed, mask_dyn, max_phi);
+}
 extern "C" int mav_phi_mask_f32(mav_ctx* c, const float* flow, const double* foe, const uint8_t* sky, int batch,
                                 const mav_thr_params* tp, float* phi, uint8_t* mask_fixed, uint8_t* mask_dyn, float* max_phi)
 {
-    CHK(check_batch(c, batch, "mav_phi_mask_f32"));
-    if (!flow || !foe) return fail(MAV_ERR_ARG, "mav_phi_mask_f32: NULL argument");
-    const size_t n = c->n0 * batch;
-    mav_thr_params t;
-    if (tp) t = *tp; else mav_thr_defaults(&t);
-    DevBuf df, dfoe, dsky, dphi, dmf, dmd;
-    CHK(df.upload(c, flow, n * 2 * sizeof(float)));
-    CHK(dfoe.upload(c, foe, sizeof(double) * 2 * batch));
-    if (sky) CHK(dsky.upload(c, sky, n));
-    if (phi) CHK(dphi.alloc(c, n * sizeof(double)));
-    if (mask_fixed) CHK(dmf.alloc(c, n));
-    if (mask_dyn) CHK(dmd.alloc(c, n));
-    const DerotParams* mode = nullptr;
-    CHK(frame0_params(c, batch, &mode));
-    CHK(detect_dev(c, df.as<float>(), nullptr, mode, nullptr, dsky.as<uint8_t>(), batch, nullptr, &t, dfoe.as<double>(),
-                   dphi.as<double>(), dmf.as<uint8_t>(), dmd.as<uint8_t>(), max_phi ? c->u64_scratch : nullptr, nullptr, nullptr,
-                   nullptr));
-    c->last_mf = dmf.as<uint8_t>(); c->last_md = dmd.as<uint8_t>(); c->last_mask_batch = batch;
-    // the kernel stores the float32 angles widened to double (one phi layout for both arithmetic types): narrow them back, exactly
-    std::vector<double> wide;
-    if (phi) { wide.resize(n); CHK(download(c, wide.data(), dphi.p, n * sizeof(double))); }
-    if (mask_fixed) CHK(download(c, mask_fixed, dmf.p, n));
-    if (mask_dyn) CHK(download(c, mask_dyn, dmd.p, n));
-    std::vector<double> mx(max_phi ? batch : 0);
-    if (max_phi) CHK(download(c, mx.data(), c->u64_scratch, sizeof(double) * batch));
-    CHK(mav_sync(c));
-    if (phi) for (size_t i = 0; i < n; i++) phi[i] = (float)wide[i];
-    if (max_phi) for (int b = 0; b < batch; b++) max_phi[b] = (float)mx[b];
-    return MAV_OK;
+    return phi_mask_host(c, "mav_phi_mask_f32", flow, foe, sky, batch, tp, phi, mask_fixed, mask_dyn, max_phi);
 }
 
 extern "C" int mav_bbox(mav_ctx* c, const uint8_t* img, int batch, int32_t* box)
 {
-    CHK(check_batch(c, batch, "mav_bbox"));
+    HostCall h(c, "mav_bbox");
+    CHK(h.fresh(batch));
     if (!img || !box) return fail(MAV_ERR_ARG, "mav_bbox: NULL argument");
-    DevBuf di, db;
-    CHK(di.upload(c, img, c->n0 * batch)); CHK(db.alloc(c, sizeof(int32_t) * 4 * batch));
+    const uint8_t* di = h.in(img, c->n0 * batch);
+    int32_t* db = h.out(box, sizeof(int32_t) * 4 * batch);
+    CHK(h.staged());
     launch_box_init(c->stream, c->box_acc, nullptr, nullptr, batch);
-    launch_bbox_u8(c->stream, di.as<uint8_t>(), batch, c->W, c->H, c->i32_scratch, c->box_acc);
-    launch_box_finalize(c->stream, c->box_acc, batch, db.as<int32_t>());
+    launch_bbox_u8(c->stream, di, batch, c->W, c->H, c->i32_scratch, c->box_acc);
+    launch_box_finalize(c->stream, c->box_acc, batch, db);
     CHK(check_launch("bbox"));
-    CHK(download(c, box, db.p, sizeof(int32_t) * 4 * batch));
-    return mav_sync(c);
+    return h.finish();
 }
 
 extern "C" int mav_bgr2gray(mav_ctx* c, const uint8_t* bgr, int batch, uint8_t* gray)
 {
-    CHK(check_batch(c, batch, "mav_bgr2gray"));
+    HostCall h(c, "mav_bgr2gray");
+    CHK(h.fresh(batch));
     if (!bgr || !gray) return fail(MAV_ERR_ARG, "mav_bgr2gray: NULL argument");
     const size_t n = c->n0 * batch;
-    DevBuf di, dg;
-    CHK(di.upload(c, bgr, 3 * n)); CHK(dg.alloc(c, n));
-    launch_bgr2gray(c->stream, di.as<uint8_t>(), n, dg.as<uint8_t>());
+    const uint8_t* di = h.in(bgr, 3 * n);
+    uint8_t* dg = h.out(gray, n);
+    CHK(h.staged());
+    launch_bgr2gray(c->stream, di, n, dg);
     CHK(check_launch("bgr2gray"));
-    CHK(download(c, gray, dg.p, n));
-    return mav_sync(c);
+    return h.finish();
 }
 
 extern "C" int mav_bgr2gray_dev(mav_ctx* c, const uint8_t* bgr, int batch, uint8_t* gray)
@@ -2447,14 +2522,15 @@ extern "C" int mav_ransac(mav_ctx* c, const double* estimates, int count, double
 
 extern "C" int mav_window_max(mav_ctx* c, const uint8_t* img, int batch, int64_t* out)
 {
-    CHK(check_batch(c, batch, "mav_window_max"));
+    HostCall h(c, "mav_window_max");
+    CHK(h.fresh(batch));
     if (!img || !out) return fail(MAV_ERR_ARG, "mav_window_max: NULL argument");
-    DevBuf di, dout;
-    CHK(di.upload(c, img, c->n0 * batch)); CHK(dout.alloc(c, sizeof(int64_t) * 3 * batch));
-    launch_window_max(c->stream, di.as<uint8_t>(), batch, c->W, c->H, c->u64_scratch, dout.as<int64_t>());
+    const uint8_t* di = h.in(img, c->n0 * batch);
+    int64_t* dout = h.out(out, sizeof(int64_t) * 3 * batch);
+    CHK(h.staged());
+    launch_window_max(c->stream, di, batch, c->W, c->H, c->u64_scratch, dout);
     CHK(check_launch("window_max"));
-    CHK(download(c, out, dout.p, sizeof(int64_t) * 3 * batch));
-    return mav_sync(c);
+    return h.finish();
 }
 
 // ---- window search: analyze_pyramid / optimize_window -----------------------------------------------------------
@@ -2528,108 +2604,118 @@ extern "C" int mav_pyramid_dims(const mav_ctx* c, double scale, int level, int* 
 
 extern "C" int mav_analyze_pyramid(mav_ctx* c, const uint8_t* img, int batch, double scale, int64_t* out)
 {
-    CHK(check_batch(c, batch, "mav_analyze_pyramid"));
+    HostCall h(c, "mav_analyze_pyramid");
+    CHK(h.fresh(batch));
     if (!img || !out) return fail(MAV_ERR_ARG, "mav_analyze_pyramid: NULL argument");
     PyrPlan p;
     CHK(pyr_plan(c, scale, c->max_batch, &p));
     CHK(ensure_pyr_ws(c, p));
-    DevBuf di, dout;
-    CHK(di.upload(c, img, c->n0 * batch)); CHK(dout.alloc(c, sizeof(int64_t) * 6 * batch));
+    const uint8_t* di = h.in(img, c->n0 * batch);
+    int64_t* dout = h.out(out, sizeof(int64_t) * 6 * batch);
+    CHK(h.staged());
     HIPCHK(hipMemsetAsync(c->u64_scratch, 0, sizeof(unsigned long long) * batch, c->stream));
-    build_pyramid(c, p, di.as<uint8_t>(), batch, p.n - 1);
+    build_pyramid(c, p, di, batch, p.n - 1);
     for (int l = 0; l < p.n; l++)
-        launch_level_scan(c->stream, l == 0 ? di.as<uint8_t>() : c->pyr_ws + p.off[l], (size_t)p.w[l] * p.h[l], batch, p.w[l], p.h[l],
-                          p.base[l], c->u64_scratch);
-    launch_pyramid_finalize(c->stream, c->u64_scratch, p, di.as<uint8_t>(), c->pyr_ws, batch, dout.as<int64_t>());
+        launch_level_scan(c->stream, l == 0 ? di : c->pyr_ws + p.off[l], (size_t)p.w[l] * p.h[l], batch, p.w[l], p.h[l], p.base[l],
+                          c->u64_scratch);
+    launch_pyramid_finalize(c->stream, c->u64_scratch, p, di, c->pyr_ws, batch, dout);
     CHK(check_launch("analyze_pyramid"));
-    CHK(download(c, out, dout.p, sizeof(int64_t) * 6 * batch));
-    return mav_sync(c);
+    return h.finish();
 }
 
 extern "C" int mav_stage_pyramid_level(mav_ctx* c, const uint8_t* img, double scale, int level, uint8_t* out)
 {
-    CHK(check_batch(c, 1, "mav_stage_pyramid_level"));
+    HostCall h(c, "mav_stage_pyramid_level");
+    CHK(h.fresh());
     if (!img || !out) return fail(MAV_ERR_ARG, "mav_stage_pyramid_level: NULL argument");
     PyrPlan p;
     CHK(pyr_plan(c, scale, c->max_batch, &p));
     if (level < 0 || level >= p.n) return fail(MAV_ERR_ARG, "pyramid level %d outside [0, %d)", level, p.n);
     CHK(ensure_pyr_ws(c, p));
-    DevBuf di;
-    CHK(di.upload(c, img, c->n0));
-    build_pyramid(c, p, di.as<uint8_t>(), 1, level);
+    const uint8_t* di = h.in(img, c->n0);
+    CHK(h.staged());
+    build_pyramid(c, p, di, 1, level);
     CHK(check_launch("area_resize"));
-    CHK(download(c, out, level == 0 ? di.p : (void*)(c->pyr_ws + p.off[level]), (size_t)p.w[level] * p.h[level]));
-    return mav_sync(c);
+    h.fetch(out, level == 0 ? di : c->pyr_ws + p.off[level], (size_t)p.w[level] * p.h[level]);
+    return h.finish();
 }
 
 extern "C" int mav_optimize_window(mav_ctx* c, const uint8_t* img, int batch, const int32_t* window_in, int64_t* score,
                                    int32_t* window_out)
 {
-    CHK(check_batch(c, batch, "mav_optimize_window"));
+    HostCall h(c, "mav_optimize_window");
+    CHK(h.fresh(batch));
     if (!img || !window_in || !score || !window_out) return fail(MAV_ERR_ARG, "mav_optimize_window: NULL argument");
     if (!c->sat) CHK(c->mem.alloc(&c->sat, sizeof(unsigned long long) * (size_t)(c->W + 1) * (c->H + 1) * c->max_batch, MEM_OTHER, "summed-area tables"));
-    DevBuf di, dw, ds, dwo;
-    CHK(di.upload(c, img, c->n0 * batch)); CHK(dw.upload(c, window_in, sizeof(int32_t) * 4 * batch));
-    CHK(ds.alloc(c, sizeof(int64_t) * batch)); CHK(dwo.alloc(c, sizeof(int32_t) * 4 * batch));
-    launch_optimize_window(c->stream, di.as<uint8_t>(), batch, c->W, c->H, c->sat, dw.as<int32_t>(), ds.as<int64_t>(), dwo.as<int32_t>());
+    const uint8_t* di = h.in(img, c->n0 * batch);
+    const int32_t* dw = h.in(window_in, sizeof(int32_t) * 4 * batch);
+    int64_t* ds = h.out(score, sizeof(int64_t) * batch);
+    int32_t* dwo = h.out(window_out, sizeof(int32_t) * 4 * batch);
+    CHK(h.staged());
+    launch_optimize_window(c->stream, di, batch, c->W, c->H, c->sat, dw, ds, dwo);
     CHK(check_launch("optimize_window"));
-    CHK(download(c, score, ds.p, sizeof(int64_t) * batch));
-    CHK(download(c, window_out, dwo.p, sizeof(int32_t) * 4 * batch));
-    return mav_sync(c);
+    return h.finish();
 }
 
 extern "C" int mav_tpr_fpr_counts(mav_ctx* c, const uint8_t* gt, const uint8_t* mask, int mask_value, int batch, int64_t* counts)
 {
-    CHK(check_batch(c, batch, "mav_tpr_fpr_counts"));
+    HostCall h(c, "mav_tpr_fpr_counts");
+    CHK(h.fresh(batch));
     if (!gt || !mask || !counts) return fail(MAV_ERR_ARG, "mav_tpr_fpr_counts: NULL argument");
     if (mask_value < 1 || mask_value > 65535) return fail(MAV_ERR_ARG, "mav_tpr_fpr_counts: mask_value %d outside [1, 65535]", mask_value);
-    DevBuf dg, dm;
-    CHK(dg.upload(c, gt, c->n0 * batch)); CHK(dm.upload(c, mask, c->n0 * batch));
-    launch_tpr_fpr(c->stream, dg.as<uint8_t>(), dm.as<uint8_t>(), (unsigned)mask_value, batch, c->W, c->H, c->u64_scratch);
+    const uint8_t* dg = h.in(gt, c->n0 * batch);
+    const uint8_t* dm = h.in(mask, c->n0 * batch);
+    h.fetch(counts, c->u64_scratch, sizeof(int64_t) * 4 * batch);
+    CHK(h.staged());
+    launch_tpr_fpr(c->stream, dg, dm, (unsigned)mask_value, batch, c->W, c->H, c->u64_scratch);
     CHK(check_launch("tpr_fpr"));
-    CHK(download(c, counts, c->u64_scratch, sizeof(int64_t) * 4 * batch));
-    return mav_sync(c);
+    return h.finish();
 }
 
 // frames (mav_process_batch) or a float32 flow field (mav_detect) in, masks and records out: one body for both
-static int process_host(mav_ctx* c, const char* fn, const uint8_t* prev, const uint8_t* next, const float* flow_in,
-                        const uint32_t* samples, const double* omega, const double* dt, const uint8_t* frame0, const uint8_t* sky,
-                        int batch, const mav_foe_params* fp, const mav_thr_params* tp, float* flow_out, double* phi,
-                        uint8_t* mask_fixed, uint8_t* mask_dyn, mav_result* results)
+struct ProcessArgs {
+    const uint8_t *prev = nullptr, *next = nullptr;      // the frames ...
+    const float* flow_in = nullptr;                      // ... or their flow
+    const uint32_t* samples = nullptr;
+    const double *omega = nullptr, *dt = nullptr;
+    const uint8_t *frame0 = nullptr, *sky = nullptr;
+    const mav_foe_params* foe_par = nullptr;
+    const mav_thr_params* thr = nullptr;
+    float* flow_out = nullptr;                           // outputs: only the records are always wanted
+    double* phi = nullptr;
+    uint8_t *mask_fixed = nullptr, *mask_dyn = nullptr;
+    mav_result* results = nullptr;
+};
+static int process_host(mav_ctx* c, const char* fn, int batch, const ProcessArgs& a)
 {
-    CHK(check_batch(c, batch, fn));
-    if ((!flow_in && (!prev || !next)) || !samples || !results) return fail(MAV_ERR_ARG, "%s: NULL argument", fn);
+    HostCall h(c, fn);
+    CHK(h.fresh(batch));
+    if ((!a.flow_in && (!a.prev || !a.next)) || !a.samples || !a.results) return fail(MAV_ERR_ARG, "%s: NULL argument", fn);
     mav_foe_params f;
-    if (fp) f = *fp; else mav_foe_defaults(&f);
-    if (f.n_pairs < 1 || f.n_pairs > 4096) return fail(MAV_ERR_ARG, "n_pairs %d outside [1, 4096]", f.n_pairs);
-    const size_t n = c->n0 * batch;
-    DevBuf dp, dn, ds, dflow, dres, dmf, dmd, dsky, dom, ddt, df0, dphi;      // the always-present buffers take the first blocks
-    const uint8_t *dprev = nullptr, *dnext = nullptr;
-    if (flow_in) CHK(dflow.upload(c, flow_in, n * 2 * sizeof(float)));
+    CHK(foe_or_defaults(a.foe_par, &f));
+    const size_t n = c->n0 * batch, flow_bytes = n * 2 * sizeof(float);
+    const void *dprev = nullptr, *dnext = nullptr;
+    float* dflow;                                        // the always-present buffers take the first blocks
+    if (a.flow_in) dflow = h.in(a.flow_in, flow_bytes);
     else {
-        const void *vp, *vn;
-        CHK(upload_frames(c, prev, next, batch, 1, dp, dn, &vp, &vn)); CHK(dflow.alloc(c, n * 2 * sizeof(float)));
-        dprev = (const uint8_t*)vp; dnext = (const uint8_t*)vn;
+        upload_frames(h, a.prev, a.next, batch, 1, &dprev, &dnext);
+        dflow = h.scratch<float>(flow_bytes);
     }
-    CHK(ds.upload(c, samples, sizeof(uint32_t) * 4 * (size_t)f.n_pairs * batch));
-    CHK(dres.alloc(c, sizeof(mav_result) * batch));
-    if (mask_fixed) CHK(dmf.alloc(c, n));
-    if (mask_dyn) CHK(dmd.alloc(c, n));
-    if (sky) CHK(dsky.upload(c, sky, n));
-    if (omega) CHK(dom.upload(c, omega, sizeof(double) * 3 * batch));
-    if (omega && dt) CHK(ddt.upload(c, dt, sizeof(double) * batch));
-    if (frame0) CHK(df0.upload(c, frame0, batch));
-    if (phi) CHK(dphi.alloc(c, n * sizeof(double)));
-    if (!flow_in) CHK(mav_farneback_dev(c, dprev, dnext, batch, dflow.as<float>()));
-    CHK(mav_detect_dev(c, dflow.as<float>(), ds.as<uint32_t>(), dom.as<double>(), ddt.as<double>(), df0.as<uint8_t>(),
-                       dsky.as<uint8_t>(), batch, &f, tp, dphi.as<double>(), dmf.as<uint8_t>(), dmd.as<uint8_t>(), dres.as<mav_result>()));
-    c->last_mf = dmf.as<uint8_t>(); c->last_md = dmd.as<uint8_t>(); c->last_mask_batch = batch;
-    if (flow_out) CHK(download(c, flow_out, dflow.p, n * 2 * sizeof(float)));
-    if (phi) CHK(download(c, phi, dphi.p, n * sizeof(double)));
-    if (mask_fixed) CHK(download(c, mask_fixed, dmf.p, n));
-    if (mask_dyn) CHK(download(c, mask_dyn, dmd.p, n));
-    CHK(download(c, results, dres.p, sizeof(mav_result) * batch));
-    return mav_sync(c);
+    h.fetch(a.flow_out, dflow, flow_bytes);
+    const uint32_t* ds = h.in(a.samples, sizeof(uint32_t) * 4 * (size_t)f.n_pairs * batch);
+    mav_result* dres = h.out(a.results, sizeof(mav_result) * batch);
+    uint8_t* dmf = h.out(a.mask_fixed, n);
+    uint8_t* dmd = h.out(a.mask_dyn, n);
+    const uint8_t* dsky = h.in(a.sky, n);
+    const double* dom = h.in(a.omega, sizeof(double) * 3 * batch);
+    const double* ddt = h.in(a.omega ? a.dt : nullptr, sizeof(double) * batch);
+    const uint8_t* df0 = h.in(a.frame0, batch);
+    double* dphi = h.out(a.phi, n * sizeof(double));
+    CHK(h.staged());
+    if (!a.flow_in) CHK(mav_farneback_dev(c, (const uint8_t*)dprev, (const uint8_t*)dnext, batch, dflow));
+    CHK(mav_detect_dev(c, dflow, ds, dom, ddt, df0, dsky, batch, &f, a.thr, dphi, dmf, dmd, dres));
+    c->last_mf = dmf; c->last_md = dmd; c->last_mask_batch = batch;
+    return h.finish();
 }
 
 extern "C" int mav_last_masks_tpr_fpr(mav_ctx* c, const uint8_t* gt, int mask_value, int batch, int64_t* counts_fixed, int64_t* counts_dyn)
@@ -2638,23 +2724,20 @@ extern "C" int mav_last_masks_tpr_fpr(mav_ctx* c, const uint8_t* gt, int mask_va
     if (mask_value < 1 || mask_value > 65535) return fail(MAV_ERR_ARG, "mav_last_masks_tpr_fpr: mask_value %d outside [1, 65535]", mask_value);
     if (!c->last_mask_batch || batch != c->last_mask_batch || (counts_fixed && !c->last_mf) || (counts_dyn && !c->last_md))
         return fail(MAV_ERR_STATE, "mav_last_masks_tpr_fpr: no masks of a %d-pair detection call are resident", batch);
-    HIPCHK(hipSetDevice(c->device));
-    // the ground truth goes into the NEXT free staging block: the previous call's blocks (its masks among them) stay untouched
-    const uint8_t *mf = c->last_mf, *md = c->last_md;
-    const size_t mark = c->scratch_next;
-    DevBuf dg;
-    CHK(dg.upload(c, gt, c->n0 * batch));
-    c->scratch_next = mark;          // the call is synchronous: its block is free again on return, a repeated call re-uses it
+    HostCall h(c, "mav_last_masks_tpr_fpr");
+    CHK(h.after_last());
+    if (!counts_fixed && !counts_dyn) return MAV_OK;
+    const uint8_t* dg = h.in(gt, c->n0 * batch);
     // one pass over the ground truth for both masks
     unsigned long long *c0 = c->u64_scratch, *c1 = c->u64_scratch + 4 * (size_t)batch;
-    const uint8_t* m0 = counts_fixed ? mf : md;
-    const uint8_t* m1 = (counts_fixed && counts_dyn) ? md : nullptr;
-    if (!counts_fixed && !counts_dyn) return MAV_OK;
-    launch_tpr_fpr2(c->stream, dg.as<uint8_t>(), c->n0, m0, m1, (unsigned)mask_value, batch, c->W, c->H, c0, m1 ? c1 : nullptr);
+    const uint8_t* m0 = counts_fixed ? c->last_mf : c->last_md;
+    const uint8_t* m1 = (counts_fixed && counts_dyn) ? c->last_md : nullptr;
+    h.fetch(counts_fixed ? counts_fixed : counts_dyn, c0, sizeof(int64_t) * 4 * batch);
+    h.fetch(m1 ? counts_dyn : nullptr, c1, sizeof(int64_t) * 4 * batch);
+    CHK(h.staged());
+    launch_tpr_fpr2(c->stream, dg, c->n0, m0, m1, (unsigned)mask_value, batch, c->W, c->H, c0, m1 ? c1 : nullptr);
     CHK(check_launch("tpr_fpr"));
-    CHK(download(c, counts_fixed ? counts_fixed : counts_dyn, c0, sizeof(int64_t) * 4 * batch));
-    if (m1) CHK(download(c, counts_dyn, c1, sizeof(int64_t) * 4 * batch));
-    return mav_sync(c);
+    return h.finish();
 }
 
 // calculate_tpr_fpr of one or two device-resident masks against a device-resident ground truth, counts left on the device: the
@@ -2663,12 +2746,11 @@ extern "C" int mav_tpr_fpr_counts_dev(mav_ctx* c, const uint8_t* gt, int gt_imag
                                       int mask_value, int batch, int64_t* counts_fixed, int64_t* counts_dyn)
 {
     if (!c || !gt) return fail(MAV_ERR_ARG, "mav_tpr_fpr_counts_dev: NULL argument");
-    if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "batch %d outside [1, %d]", batch, c->max_batch);
+    CHK(check_dev_call(c, batch, "mav_tpr_fpr_counts_dev"));
     if (gt_images != 1 && gt_images != batch) return fail(MAV_ERR_ARG, "mav_tpr_fpr_counts_dev: gt_images must be 1 (shared) or batch (%d), got %d", batch, gt_images);
     if (mask_value < 1 || mask_value > 65535) return fail(MAV_ERR_ARG, "mav_tpr_fpr_counts_dev: mask_value %d outside [1, 65535]", mask_value);
     if ((mask_fixed && !counts_fixed) || (mask_dyn && !counts_dyn) || (!mask_fixed && !mask_dyn))
         return fail(MAV_ERR_ARG, "mav_tpr_fpr_counts_dev: every mask needs its counts buffer, and at least one mask");
-    HIPCHK(hipSetDevice(c->device));
     const size_t stride = gt_images == 1 && batch > 1 ? 0 : c->n0;
     const uint8_t* m0 = mask_fixed ? mask_fixed : mask_dyn;
     const uint8_t* m1 = (mask_fixed && mask_dyn) ? mask_dyn : nullptr;
@@ -2698,45 +2780,31 @@ extern "C" int mav_render_dev(mav_ctx* c, const float* flow, const double* foe, 
                               const uint8_t* sky, int batch, const mav_thr_params* tp, uint8_t* img_result, uint8_t* img_flow, uint8_t* img_phi)
 {
     if (!c || !flow || ((img_result || img_phi) && !foe)) return fail(MAV_ERR_ARG, "mav_render_dev: NULL argument");
-    if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "mav_render_dev: batch %d outside [1, %d]", batch, c->max_batch);
-    HIPCHK(hipSetDevice(c->device));
+    CHK(check_dev_call(c, batch, "mav_render_dev"));
     CHK(ensure_render(c));
     const DerotParams* derot = nullptr;
     CHK(upload_derot(c, omega, dt, frame0, batch, false, &derot, c->render_derot));
-    mav_thr_params t;
-    if (tp) t = *tp; else mav_thr_defaults(&t);
-    return render_enqueue(c, flow, derot, foe, sky, batch, t, img_result, img_flow, img_phi);
-}
-
-// device images -> host, each of (batch, H, W, 3) bytes
-static int download_images(mav_ctx* c, int batch, uint8_t* const dev[3], uint8_t* const host[3])
-{
-    for (int k = 0; k < 3; k++)
-        if (host[k]) CHK(download(c, host[k], dev[k], c->n0 * 3 * batch));
-    return mav_sync(c);
+    return render_enqueue(c, flow, derot, foe, sky, batch, thr_or_defaults(tp), img_result, img_flow, img_phi);
 }
 
 extern "C" int mav_render(mav_ctx* c, const float* flow, const double* foe, const double* omega, const double* dt, const uint8_t* frame0,
                           const uint8_t* sky, int batch, const mav_thr_params* tp, uint8_t* img_result, uint8_t* img_flow, uint8_t* img_phi)
 {
-    CHK(check_batch(c, batch, "mav_render"));
+    HostCall h(c, "mav_render");
+    CHK(h.fresh(batch));
     if (!flow || ((img_result || img_phi) && !foe)) return fail(MAV_ERR_ARG, "mav_render: NULL argument");
     if (!img_result && !img_flow && !img_phi) return MAV_OK;
     const size_t n = c->n0 * batch;
-    DevBuf df, dfoe, dsky, dom, ddt, df0, dimg[3];
-    CHK(df.upload(c, flow, n * 2 * sizeof(float)));
-    if (foe) CHK(dfoe.upload(c, foe, sizeof(double) * 2 * batch));
-    if (sky) CHK(dsky.upload(c, sky, n));
-    if (omega) CHK(dom.upload(c, omega, sizeof(double) * 3 * batch));
-    if (omega && dt) CHK(ddt.upload(c, dt, sizeof(double) * batch));
-    if (frame0) CHK(df0.upload(c, frame0, batch));
-    uint8_t* const host[3] = {img_result, img_flow, img_phi};
-    uint8_t* dev[3] = {nullptr, nullptr, nullptr};
-    for (int k = 0; k < 3; k++)
-        if (host[k]) { CHK(dimg[k].alloc(c, n * 3)); dev[k] = dimg[k].as<uint8_t>(); }
-    CHK(mav_render_dev(c, df.as<float>(), dfoe.as<double>(), dom.as<double>(), ddt.as<double>(), df0.as<uint8_t>(), dsky.as<uint8_t>(),
-                       batch, tp, dev[0], dev[1], dev[2]));
-    return download_images(c, batch, dev, host);
+    const float* df = h.in(flow, n * 2 * sizeof(float));
+    const double* dfoe = h.in(foe, sizeof(double) * 2 * batch);
+    const uint8_t* dsky = h.in(sky, n);
+    const double* dom = h.in(omega, sizeof(double) * 3 * batch);
+    const double* ddt = h.in(omega ? dt : nullptr, sizeof(double) * batch);
+    const uint8_t* df0 = h.in(frame0, batch);
+    uint8_t *dres = h.out(img_result, n * 3), *dfl = h.out(img_flow, n * 3), *dphi = h.out(img_phi, n * 3);   // each (batch, H, W, 3)
+    CHK(h.staged());
+    CHK(mav_render_dev(c, df, dfoe, dom, ddt, df0, dsky, batch, tp, dres, dfl, dphi));
+    return h.finish();
 }
 
 extern "C" int mav_last_render(mav_ctx* c, int batch, uint8_t* img_result, uint8_t* img_flow, uint8_t* img_phi)
@@ -2744,29 +2812,26 @@ extern "C" int mav_last_render(mav_ctx* c, int batch, uint8_t* img_result, uint8
     if (!c) return fail(MAV_ERR_ARG, "mav_last_render: NULL context");
     if (!c->last_render.batch || batch != c->last_render.batch)
         return fail(MAV_ERR_STATE, "mav_last_render: no flow of a %d-pair detection call is resident", batch);
-    HIPCHK(hipSetDevice(c->device));
+    HostCall h(c, "mav_last_render");
+    CHK(h.after_last());
     if (!img_result && !img_flow && !img_phi) return MAV_OK;
-    // the images go into the NEXT free staging blocks: the detection call's own blocks (flow, sky of a host-pointer call) stay untouched
-    const size_t mark = c->scratch_next;
-    DevBuf dimg[3];
-    uint8_t* const host[3] = {img_result, img_flow, img_phi};
-    uint8_t* dev[3] = {nullptr, nullptr, nullptr};
-    for (int k = 0; k < 3; k++)
-        if (host[k]) { CHK(dimg[k].alloc(c, c->n0 * 3 * batch)); dev[k] = dimg[k].as<uint8_t>(); }
-    c->scratch_next = mark;          // synchronous: the blocks are free again on return
+    const size_t bytes = c->n0 * 3 * batch;
+    uint8_t *dres = h.out(img_result, bytes), *dfl = h.out(img_flow, bytes), *dphi = h.out(img_phi, bytes);
+    CHK(h.staged());
     const mav_ctx::LastRender& r = c->last_render;
-    CHK(render_enqueue(c, r.flow, r.derot, r.foe, r.sky, batch, r.thr, dev[0], dev[1], dev[2]));
-    return download_images(c, batch, dev, host);
+    CHK(render_enqueue(c, r.flow, r.derot, r.foe, r.sky, batch, r.thr, dres, dfl, dphi));
+    return h.finish();
 }
 
 extern "C" int mav_flow_to_color(mav_ctx* c, const void* flow, int f64, int batch, uint8_t* img)
 {
-    CHK(check_batch(c, batch, "mav_flow_to_color"));
+    HostCall h(c, "mav_flow_to_color");
+    CHK(h.fresh(batch));
     if (!flow || !img) return fail(MAV_ERR_ARG, "mav_flow_to_color: NULL argument");
     const size_t n = c->n0 * batch;
-    DevBuf df, dimg;
-    CHK(df.upload(c, flow, n * 2 * (f64 ? sizeof(double) : sizeof(float))));
-    CHK(dimg.alloc(c, n * 3));
+    const void* df = h.in(flow, n * 2 * (f64 ? sizeof(double) : sizeof(float)));
+    uint8_t* dimg = h.out(img, n * 3);
+    CHK(h.staged());
     CHK(ensure_render(c));
     const DerotParams* derot = nullptr;
     if (!f64) {                      // a float32 field: numpy's float32 arithmetic, i.e. the frame-0 form
@@ -2775,29 +2840,26 @@ extern "C" int mav_flow_to_color(mav_ctx* c, const void* flow, int f64, int batc
     }
     {
         ProfScope ps(c, K_MISC);
-        if (f64) launch_render_f64(c->stream, df.as<double>(), batch, c->W, c->H, c->render_max, dimg.as<uint8_t>());
-        else launch_render_f32(c->stream, df.as<float>(), derot, nullptr, nullptr, batch, c->W, c->H, mav_thr_params{}, c->render_max, nullptr,
-                               dimg.as<uint8_t>(), nullptr);
+        if (f64) launch_render_f64(c->stream, (const double*)df, batch, c->W, c->H, c->render_max, dimg);
+        else launch_render_f32(c->stream, (const float*)df, derot, nullptr, nullptr, batch, c->W, c->H, mav_thr_params{}, c->render_max, nullptr,
+                               dimg, nullptr);
     }
     CHK(check_launch("render"));
-    CHK(download(c, img, dimg.p, n * 3));
-    return mav_sync(c);
+    return h.finish();
 }
 
 extern "C" int mav_colormap_jet(mav_ctx* c, const uint8_t* gray, size_t n, uint8_t* bgr)
 {
     if (!c || !gray || !bgr) return fail(MAV_ERR_ARG, "mav_colormap_jet: NULL argument");
-    HIPCHK(hipSetDevice(c->device));
-    c->scratch_next = 0;
-    c->last_mf = c->last_md = nullptr; c->last_mask_batch = 0;
-    c->last_render.batch = 0;
+    HostCall h(c, "mav_colormap_jet");
+    CHK(h.fresh());
     if (!n) return MAV_OK;
-    DevBuf dg, dout;
-    CHK(dg.upload(c, gray, n)); CHK(dout.alloc(c, n * 3));
-    launch_colormap_jet(c->stream, dg.as<uint8_t>(), n, dout.as<uint8_t>());
+    const uint8_t* dg = h.in(gray, n);
+    uint8_t* dout = h.out(bgr, n * 3);
+    CHK(h.staged());
+    launch_colormap_jet(c->stream, dg, n, dout);
     CHK(check_launch("colormap"));
-    CHK(download(c, bgr, dout.p, n * 3));
-    return mav_sync(c);
+    return h.finish();
 }
 
 // ---- the processed.mp4 frame (include/mavflow.h: mav_overlay) ---------------------------------------------------------------------
@@ -2818,63 +2880,53 @@ extern "C" int mav_overlay_dev(mav_ctx* c, const uint8_t* frames, const uint8_t*
                                int batch, int radius, uint8_t* overlay, uint8_t* written)
 {
     if (!c || !frames || !mask_fixed || !foe || !foe_gt || !overlay || !written) return fail(MAV_ERR_ARG, "mav_overlay_dev: NULL argument");
-    if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "mav_overlay_dev: batch %d outside [1, %d]", batch, c->max_batch);
+    CHK(check_dev_call(c, batch, "mav_overlay_dev"));
     CHK(check_radius(radius, "mav_overlay_dev"));
-    HIPCHK(hipSetDevice(c->device));
     ProfScope ps(c, K_MISC);
     launch_overlay(c->stream, frames, mask_fixed, foe, foe_gt, batch, c->W, c->H, radius, overlay, written);
     return check_launch("overlay");
 }
 
-// the overlay and the flags -> host, then the stream drained
-static int download_overlay(mav_ctx* c, int batch, const DevBuf& dout, const DevBuf& dw, uint8_t* overlay, uint8_t* written)
-{
-    CHK(download(c, overlay, dout.p, c->n0 * 3 * batch));
-    CHK(download(c, written, dw.p, batch));
-    return mav_sync(c);
-}
-
 extern "C" int mav_overlay(mav_ctx* c, const uint8_t* frames, const uint8_t* mask_fixed, const double* foe, const double* foe_gt, int batch,
                            int radius, uint8_t* overlay, uint8_t* written)
 {
-    CHK(check_batch(c, batch, "mav_overlay"));
+    HostCall h(c, "mav_overlay");
+    CHK(h.fresh(batch));
     if (!frames || !mask_fixed || !foe || !foe_gt || !overlay || !written) return fail(MAV_ERR_ARG, "mav_overlay: NULL argument");
     CHK(check_radius(radius, "mav_overlay"));
     CHK(check_foe_host(foe, batch, "foe", "mav_overlay"));
     CHK(check_foe_host(foe_gt, batch, "foe_gt", "mav_overlay"));
     const size_t n = c->n0 * batch;
-    DevBuf df, dm, dfoe, dgt, dout, dw;
-    CHK(df.upload(c, frames, n * 3));
-    CHK(dm.upload(c, mask_fixed, n));
-    CHK(dfoe.upload(c, foe, sizeof(double) * 2 * batch));
-    CHK(dgt.upload(c, foe_gt, sizeof(double) * 2 * batch));
-    CHK(dout.alloc(c, n * 3));
-    CHK(dw.alloc(c, batch));
-    CHK(mav_overlay_dev(c, df.as<uint8_t>(), dm.as<uint8_t>(), dfoe.as<double>(), dgt.as<double>(), batch, radius, dout.as<uint8_t>(),
-                        dw.as<uint8_t>()));
-    return download_overlay(c, batch, dout, dw, overlay, written);
+    const uint8_t* df = h.in(frames, n * 3);
+    const uint8_t* dm = h.in(mask_fixed, n);
+    const double* dfoe = h.in(foe, sizeof(double) * 2 * batch);
+    const double* dgt = h.in(foe_gt, sizeof(double) * 2 * batch);
+    uint8_t* dout = h.out(overlay, n * 3);
+    uint8_t* dw = h.out(written, batch);
+    CHK(h.staged());
+    CHK(mav_overlay_dev(c, df, dm, dfoe, dgt, batch, radius, dout, dw));
+    return h.finish();
 }
 
 extern "C" int mav_last_overlay(mav_ctx* c, const uint8_t* frames, const double* foe_gt, int batch, int radius, uint8_t* overlay, uint8_t* written)
 {
     if (!c || !frames || !foe_gt || !overlay || !written) return fail(MAV_ERR_ARG, "mav_last_overlay: NULL argument");
-    if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "mav_last_overlay: batch %d outside [1, %d]", batch, c->max_batch);
+    CHK(check_dev_call(c, batch, "mav_last_overlay"));
     if (!c->last_render.batch || batch != c->last_render.batch || !c->last_render.mask_fixed)
         return fail(MAV_ERR_STATE, "mav_last_overlay: no fixed mask of a %d-pair detection call is resident", batch);
     CHK(check_radius(radius, "mav_last_overlay"));
     CHK(check_foe_host(foe_gt, batch, "foe_gt", "mav_last_overlay"));
-    HIPCHK(hipSetDevice(c->device));
-    // frames and image go into the NEXT free staging blocks: the detection call's own blocks (the mask of a host-pointer call) stay untouched
-    const size_t n = c->n0 * batch, mark = c->scratch_next;
-    DevBuf df, dgt, dout, dw;
-    CHK(df.upload(c, frames, n * 3));
-    CHK(dgt.upload(c, foe_gt, sizeof(double) * 2 * batch));
-    CHK(dout.alloc(c, n * 3));
-    CHK(dw.alloc(c, batch));
-    c->scratch_next = mark;          // synchronous: the blocks are free again on return
+    HostCall h(c, "mav_last_overlay");
+    CHK(h.after_last());
+    const size_t n = c->n0 * batch;
+    const uint8_t* df = h.in(frames, n * 3);
+    const double* dgt = h.in(foe_gt, sizeof(double) * 2 * batch);
+    uint8_t* dout = h.out(overlay, n * 3);
+    uint8_t* dw = h.out(written, batch);
+    CHK(h.staged());
     const mav_ctx::LastRender& r = c->last_render;
-    CHK(mav_overlay_dev(c, df.as<uint8_t>(), r.mask_fixed, r.foe, dgt.as<double>(), batch, radius, dout.as<uint8_t>(), dw.as<uint8_t>()));
-    return download_overlay(c, batch, dout, dw, overlay, written);
+    CHK(mav_overlay_dev(c, df, r.mask_fixed, r.foe, dgt, batch, radius, dout, dw));
+    return h.finish();
 }
 
 // ---- PNG files of device-resident images (include/mavflow.h: mav_png_encode) -------------------------------------------------------
@@ -2917,32 +2969,30 @@ extern "C" int mav_png_encode_dev(mav_ctx* c, const uint8_t* imgs, int count, in
     }
     return check_launch("png_encode");
 }
-// the index, then the streams (packed from offset 0) of `count` encoded images -> host
-static int download_png(mav_ctx* c, const char* fn, int count, const DevBuf& dout, const DevBuf& didx, uint8_t* out_host, size_t out_bytes,
-                        uint64_t* index)
+// The tail of the PNG calls: the index -> host and the stream drained, so that the host knows how long the streams (packed from offset
+// 0) of the `count` encoded images are; then those.
+static int download_png(HostCall& h, int count, const uint8_t* dout, const uint64_t* didx, uint8_t* out_host, size_t out_bytes, uint64_t* index)
 {
-    CHK(download(c, index, didx.p, sizeof(uint64_t) * 2 * count));
-    CHK(mav_sync(c));
+    h.fetch(index, didx, sizeof(uint64_t) * 2 * count);
+    CHK(h.finish());
     const size_t total = (size_t)(index[2 * (count - 1)] + index[2 * (count - 1) + 1]);
-    if (total > out_bytes) return fail(MAV_ERR_ARG, "%s: out_bytes %zu, the %d streams take %zu", fn, out_bytes, count, total);
-    CHK(download(c, out_host, dout.p, total));
-    return mav_sync(c);
+    if (total > out_bytes) return fail(MAV_ERR_ARG, "%s: out_bytes %zu, the %d streams take %zu", h.fn, out_bytes, count, total);
+    h.fetch(out_host, dout, total);
+    return h.finish();
 }
 extern "C" int mav_png_encode(mav_ctx* c, const uint8_t* imgs, int count, int channels, uint8_t* out_host, size_t out_bytes, uint64_t* index)
 {
     CHK(check_png_args(c, "mav_png_encode", count, channels, out_bytes, false));
     if (!imgs || !out_host || !index) return fail(MAV_ERR_ARG, "mav_png_encode: NULL argument");
-    HIPCHK(hipSetDevice(c->device));
-    c->scratch_next = 0;
-    c->last_mf = c->last_md = nullptr; c->last_mask_batch = 0;
-    c->last_render.batch = 0;
+    HostCall h(c, "mav_png_encode");
+    CHK(h.fresh());
     const size_t bound = mav_png_bound(c->W, c->H, channels) * count;
-    DevBuf di, dout, didx;
-    CHK(di.upload(c, imgs, c->n0 * channels * count));
-    CHK(dout.alloc(c, bound));
-    CHK(didx.alloc(c, sizeof(uint64_t) * 2 * count));
-    CHK(mav_png_encode_dev(c, di.as<uint8_t>(), count, channels, dout.as<uint8_t>(), bound, didx.as<uint64_t>()));
-    return download_png(c, "mav_png_encode", count, dout, didx, out_host, out_bytes, index);
+    const uint8_t* di = h.in(imgs, c->n0 * channels * count);
+    uint8_t* dout = h.scratch<uint8_t>(bound);
+    uint64_t* didx = h.scratch<uint64_t>(sizeof(uint64_t) * 2 * count);
+    CHK(h.staged());
+    CHK(mav_png_encode_dev(c, di, count, channels, dout, bound, didx));
+    return download_png(h, count, dout, didx, out_host, out_bytes, index);
 }
 
 extern "C" int mav_last_render_png(mav_ctx* c, int batch, int want_result, int want_flow, int want_phi, uint8_t* out_host, size_t out_bytes,
@@ -2951,50 +3001,48 @@ extern "C" int mav_last_render_png(mav_ctx* c, int batch, int want_result, int w
     if (!c) return fail(MAV_ERR_ARG, "mav_last_render_png: NULL context");
     if (!c->last_render.batch || batch != c->last_render.batch)
         return fail(MAV_ERR_STATE, "mav_last_render_png: no flow of a %d-pair detection call is resident", batch);
-    HIPCHK(hipSetDevice(c->device));
+    HostCall h(c, "mav_last_render_png");
+    CHK(h.after_last());
     const int want[3] = {want_result != 0, want_flow != 0, want_phi != 0}, nimg = want[0] + want[1] + want[2];
     if (!nimg) return MAV_OK;
     if (!out_host || !index) return fail(MAV_ERR_ARG, "mav_last_render_png: NULL argument");
-    const size_t per = c->n0 * 3 * batch, bound = mav_png_bound(c->W, c->H, 3) * nimg * batch, mark = c->scratch_next;
-    // as mav_last_render: the NEXT free staging blocks, the detection call's own blocks stay untouched
-    DevBuf dimg, dout, didx;
-    CHK(dimg.alloc(c, per * nimg));
-    CHK(dout.alloc(c, bound));
-    CHK(didx.alloc(c, sizeof(uint64_t) * 2 * nimg * batch));
-    c->scratch_next = mark;
+    const size_t per = c->n0 * 3 * batch, bound = mav_png_bound(c->W, c->H, 3) * nimg * batch;
+    uint8_t* dimg = h.scratch<uint8_t>(per * nimg);
+    uint8_t* dout = h.scratch<uint8_t>(bound);
+    uint64_t* didx = h.scratch<uint64_t>(sizeof(uint64_t) * 2 * nimg * batch);
+    CHK(h.staged());
     uint8_t* dev[3] = {nullptr, nullptr, nullptr};
     for (int k = 0, j = 0; k < 3; k++)
-        if (want[k]) dev[k] = dimg.as<uint8_t>() + per * j++;
+        if (want[k]) dev[k] = dimg + per * j++;
     const mav_ctx::LastRender& r = c->last_render;
     CHK(render_enqueue(c, r.flow, r.derot, r.foe, r.sky, batch, r.thr, dev[0], dev[1], dev[2]));
-    CHK(mav_png_encode_dev(c, dimg.as<uint8_t>(), nimg * batch, 3, dout.as<uint8_t>(), bound, didx.as<uint64_t>()));
-    return download_png(c, "mav_last_render_png", nimg * batch, dout, didx, out_host, out_bytes, index);
+    CHK(mav_png_encode_dev(c, dimg, nimg * batch, 3, dout, bound, didx));
+    return download_png(h, nimg * batch, dout, didx, out_host, out_bytes, index);
 }
 
 extern "C" int mav_last_overlay_png(mav_ctx* c, const uint8_t* frames, const double* foe_gt, int batch, int radius, uint8_t* out_host,
                                     size_t out_bytes, uint64_t* index, uint8_t* written)
 {
     if (!c || !frames || !foe_gt || !out_host || !index || !written) return fail(MAV_ERR_ARG, "mav_last_overlay_png: NULL argument");
-    if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "mav_last_overlay_png: batch %d outside [1, %d]", batch, c->max_batch);
+    CHK(check_dev_call(c, batch, "mav_last_overlay_png"));
     if (!c->last_render.batch || batch != c->last_render.batch || !c->last_render.mask_fixed)
         return fail(MAV_ERR_STATE, "mav_last_overlay_png: no fixed mask of a %d-pair detection call is resident", batch);
     CHK(check_radius(radius, "mav_last_overlay_png"));
     CHK(check_foe_host(foe_gt, batch, "foe_gt", "mav_last_overlay_png"));
-    HIPCHK(hipSetDevice(c->device));
-    const size_t n = c->n0 * batch, bound = mav_png_bound(c->W, c->H, 3) * batch, mark = c->scratch_next;
-    DevBuf df, dgt, dimg, dw, dout, didx;
-    CHK(df.upload(c, frames, n * 3));
-    CHK(dgt.upload(c, foe_gt, sizeof(double) * 2 * batch));
-    CHK(dimg.alloc(c, n * 3));
-    CHK(dw.alloc(c, batch));
-    CHK(dout.alloc(c, bound));
-    CHK(didx.alloc(c, sizeof(uint64_t) * 2 * batch));
-    c->scratch_next = mark;
+    HostCall h(c, "mav_last_overlay_png");
+    CHK(h.after_last());
+    const size_t n = c->n0 * batch, bound = mav_png_bound(c->W, c->H, 3) * batch;
+    const uint8_t* df = h.in(frames, n * 3);
+    const double* dgt = h.in(foe_gt, sizeof(double) * 2 * batch);
+    uint8_t* dimg = h.scratch<uint8_t>(n * 3);
+    uint8_t* dw = h.out(written, batch);
+    uint8_t* dout = h.scratch<uint8_t>(bound);
+    uint64_t* didx = h.scratch<uint64_t>(sizeof(uint64_t) * 2 * batch);
+    CHK(h.staged());
     const mav_ctx::LastRender& r = c->last_render;
-    CHK(mav_overlay_dev(c, df.as<uint8_t>(), r.mask_fixed, r.foe, dgt.as<double>(), batch, radius, dimg.as<uint8_t>(), dw.as<uint8_t>()));
-    CHK(mav_png_encode_dev(c, dimg.as<uint8_t>(), batch, 3, dout.as<uint8_t>(), bound, didx.as<uint64_t>()));
-    CHK(download(c, written, dw.p, batch));
-    return download_png(c, "mav_last_overlay_png", batch, dout, didx, out_host, out_bytes, index);
+    CHK(mav_overlay_dev(c, df, r.mask_fixed, r.foe, dgt, batch, radius, dimg, dw));
+    CHK(mav_png_encode_dev(c, dimg, batch, 3, dout, bound, didx));
+    return download_png(h, batch, dout, didx, out_host, out_bytes, index);
 }
 
 extern "C" int mav_process_batch(mav_ctx* c, const uint8_t* prev, const uint8_t* next, const uint32_t* samples, const double* omega,
@@ -3002,8 +3050,10 @@ extern "C" int mav_process_batch(mav_ctx* c, const uint8_t* prev, const uint8_t*
                                  const mav_thr_params* tp, float* flow, double* phi, uint8_t* mask_fixed, uint8_t* mask_dyn,
                                  mav_result* results)
 {
-    return process_host(c, "mav_process_batch", prev, next, nullptr, samples, omega, dt, frame0, sky, batch, fp, tp, flow, phi,
-                        mask_fixed, mask_dyn, results);
+    ProcessArgs a;
+    a.prev = prev; a.next = next; a.samples = samples; a.omega = omega; a.dt = dt; a.frame0 = frame0; a.sky = sky; a.foe_par = fp; a.thr = tp;
+    a.flow_out = flow; a.phi = phi; a.mask_fixed = mask_fixed; a.mask_dyn = mask_dyn; a.results = results;
+    return process_host(c, "mav_process_batch", batch, a);
 }
 
 extern "C" int mav_detect(mav_ctx* c, const float* flow, const uint32_t* samples, const double* omega, const double* dt,
@@ -3011,48 +3061,35 @@ extern "C" int mav_detect(mav_ctx* c, const float* flow, const uint32_t* samples
                           double* phi, uint8_t* mask_fixed, uint8_t* mask_dyn, mav_result* results)
 {
     if (!flow) return fail(MAV_ERR_ARG, "mav_detect: NULL flow");
-    return process_host(c, "mav_detect", nullptr, nullptr, flow, samples, omega, dt, frame0, sky, batch, fp, tp, nullptr, phi,
-                        mask_fixed, mask_dyn, results);
+    ProcessArgs a;
+    a.flow_in = flow; a.samples = samples; a.omega = omega; a.dt = dt; a.frame0 = frame0; a.sky = sky; a.foe_par = fp; a.thr = tp;
+    a.phi = phi; a.mask_fixed = mask_fixed; a.mask_dyn = mask_dyn; a.results = results;
+    return process_host(c, "mav_detect", batch, a);
 }
 
 // ---- stage hooks -------------------------------------------------------------------------------------------------
-static int layer_of(mav_ctx* c, int k, const Layer** l)
-{
-    if (!c) return fail(MAV_ERR_ARG, "NULL context");
-    if (k < 0 || k >= (int)c->layers.size()) return fail(MAV_ERR_ARG, "layer %d out of range", k);
-    HIPCHK(hipSetDevice(c->device));
-    c->scratch_next = 0;
-    c->last_mf = c->last_md = nullptr; c->last_mask_batch = 0;
-    c->last_render.batch = 0;
-    *l = &c->layers[k];
-    return MAV_OK;
-}
 extern "C" int mav_stage_phi_mask(mav_ctx* c, const float* flow, const double* foe, const double* omega, const double* dt,
                                   const uint8_t* sky, int batch, const mav_thr_params* tp, double* phi, uint8_t* mask_fixed,
                                   uint8_t* mask_dyn, int32_t* box)
 {
-    CHK(check_batch(c, batch, "mav_stage_phi_mask"));
+    HostCall h(c, "mav_stage_phi_mask");
+    CHK(h.fresh(batch));
     if (!flow || !foe) return fail(MAV_ERR_ARG, "mav_stage_phi_mask: NULL argument");
     const size_t n = c->n0 * batch;
-    mav_thr_params t;
-    if (tp) t = *tp; else mav_thr_defaults(&t);
-    DevBuf df, dfoe, dsky, dphi, dmf, dmd, dbox;
-    CHK(df.upload(c, flow, n * 2 * sizeof(float)));
-    CHK(dfoe.upload(c, foe, sizeof(double) * 2 * batch));
-    if (sky) CHK(dsky.upload(c, sky, n));
-    if (phi) CHK(dphi.alloc(c, n * sizeof(double)));
-    if (mask_fixed) CHK(dmf.alloc(c, n));
-    if (mask_dyn) CHK(dmd.alloc(c, n));
-    if (box) CHK(dbox.alloc(c, sizeof(int32_t) * 4 * batch));
-    const DerotParams* derot = nullptr;
-    CHK(upload_derot(c, omega, dt, nullptr, batch, true, &derot));
-    CHK(detect_dev(c, df.as<float>(), nullptr, derot, nullptr, dsky.as<uint8_t>(), batch, nullptr, &t, dfoe.as<double>(),
-                   dphi.as<double>(), dmf.as<uint8_t>(), dmd.as<uint8_t>(), nullptr, nullptr, nullptr, dbox.as<int32_t>()));
-    if (phi) CHK(download(c, phi, dphi.p, n * sizeof(double)));
-    if (mask_fixed) CHK(download(c, mask_fixed, dmf.p, n));
-    if (mask_dyn) CHK(download(c, mask_dyn, dmd.p, n));
-    if (box) CHK(download(c, box, dbox.p, sizeof(int32_t) * 4 * batch));
-    return mav_sync(c);
+    const mav_thr_params t = thr_or_defaults(tp);
+    DetectArgs a;
+    a.flow32 = h.in(flow, n * 2 * sizeof(float));
+    a.foe_in = h.in(foe, sizeof(double) * 2 * batch);
+    a.sky = h.in(sky, n);
+    a.phi = h.out(phi, n * sizeof(double));
+    a.mask_fixed = h.out(mask_fixed, n);
+    a.mask_dyn = h.out(mask_dyn, n);
+    a.box_out = h.out(box, sizeof(int32_t) * 4 * batch);
+    a.thr = &t;
+    CHK(h.staged());
+    CHK(upload_derot(c, omega, dt, nullptr, batch, true, &a.derot));
+    CHK(detect_dev(c, batch, a));
+    return h.finish();
 }
 
 extern "C" int mav_stage_coefficients(mav_ctx* c, int k, float* g, float* xg, float* xxg, float* ig, float* blur_taps)
@@ -3066,8 +3103,9 @@ extern "C" int mav_stage_coefficients(mav_ctx* c, int k, float* g, float* xg, fl
     }
     if (ig) { ig[0] = c->pc.ig11; ig[1] = c->pc.ig03; ig[2] = c->pc.ig33; ig[3] = c->pc.ig55; }
     if (blur_taps) {
+        HostCall h(c, "mav_stage_coefficients");
         const Layer* l;
-        CHK(layer_of(c, k, &l));
+        CHK(h.fresh_layer(k, &l));
         HIPCHK(hipMemcpy(blur_taps, l->g, sizeof(float) * l->ksize, hipMemcpyDeviceToHost));   // what the kernels actually read
     }
     return MAV_OK;
@@ -3075,27 +3113,24 @@ extern "C" int mav_stage_coefficients(mav_ctx* c, int k, float* g, float* xg, fl
 
 static int stage_blur_resize(mav_ctx* c, const void* img, int depth, int k, bool two_pass, float* out)
 {
-    const Layer* l;
     if (c && !depth_esize(depth)) return fail(MAV_ERR_ARG, "mav_stage_blur_resize_ex: depth %d is none of MAV_DEPTH_8U / 16U / 32F", depth);
-    CHK(layer_of(c, k, &l));
+    HostCall h(c, "mav_stage_blur_resize");
+    const Layer* l;
+    CHK(h.fresh_layer(k, &l));
     if (!img || !out) return fail(MAV_ERR_ARG, "mav_stage_blur_resize: NULL argument");
     const size_t n = (size_t)l->w * l->h;
     // the two-pass form's H x w scratch (one frame: 4 bytes per pixel) is a staging block of this call: a diagnostic hook never
     // allocates the Farneback workspace (GBs at 1080p / 4K) nor freezes "deep_frac"
-    DevBuf di, dout, dtmp;
-    CHK(di.upload(c, img, c->n0 * depth_esize(depth))); CHK(dout.alloc(c, n * sizeof(float))); CHK(dtmp.alloc(c, c->htmp_stride * sizeof(float)));
-    if (depth == MAV_DEPTH_16U)
-        launch_blur_resize<uint16_t>(c->stream, di.as<uint16_t>(), nullptr, 0, c->n0, 1, c->W, c->H, l->w, l->h, blur_of(c, *l), dtmp.as<float>(),
-                           c->htmp_stride, dout.as<float>(), n, two_pass);
-    else if (depth == MAV_DEPTH_32F)
-        launch_blur_resize<float>(c->stream, di.as<float>(), nullptr, 0, c->n0, 1, c->W, c->H, l->w, l->h, blur_of(c, *l), dtmp.as<float>(),
-                           c->htmp_stride, dout.as<float>(), n, two_pass);
-    else
-        launch_blur_resize<uint8_t>(c->stream, di.as<uint8_t>(), nullptr, 0, c->n0, 1, c->W, c->H, l->w, l->h, blur_of(c, *l), dtmp.as<float>(),
-                           c->htmp_stride, dout.as<float>(), n, two_pass);
+    const void* di = h.in(img, c->n0 * depth_esize(depth));
+    float* dout = h.out(out, n * sizeof(float));
+    float* dtmp = h.scratch<float>(c->htmp_stride * sizeof(float));
+    CHK(h.staged());
+    with_depth(depth, [&](auto* px) {
+        launch_blur_resize(c->stream, (decltype(px))di, (decltype(px)) nullptr, 0, c->n0, 1, c->W, c->H, l->w, l->h, blur_of(c, *l), dtmp,
+                           c->htmp_stride, dout, n, two_pass);
+    });
     CHK(check_launch("blur_resize"));
-    CHK(download(c, out, dout.p, n * sizeof(float)));
-    return mav_sync(c);
+    return h.finish();
 }
 extern "C" int mav_stage_blur_resize(mav_ctx* c, const uint8_t* img, int k, float* out) { return stage_blur_resize(c, img, MAV_DEPTH_8U, k, false, out); }
 extern "C" int mav_stage_blur_resize_two_pass(mav_ctx* c, const uint8_t* img, int k, float* out) { return stage_blur_resize(c, img, MAV_DEPTH_8U, k, true, out); }
@@ -3105,37 +3140,41 @@ extern "C" int mav_stage_blur_resize_ex(mav_ctx* c, const void* img, int depth, 
 }
 extern "C" int mav_stage_polyexp(mav_ctx* c, const float* I, int k, float* R)
 {
+    HostCall h(c, "mav_stage_polyexp");
     const Layer* l;
-    CHK(layer_of(c, k, &l));
+    CHK(h.fresh_layer(k, &l));
     if (!I || !R) return fail(MAV_ERR_ARG, "mav_stage_polyexp: NULL argument");
     const size_t n = (size_t)l->w * l->h;
-    DevBuf di, dr;
-    CHK(di.upload(c, I, n * sizeof(float))); CHK(dr.alloc(c, 5 * n * sizeof(float)));
-    launch_polyexp(c->stream, di.as<float>(), n, 1, l->w, l->h, c->pc, dr.as<float>(), 5 * n);
+    const float* di = h.in(I, n * sizeof(float));
+    float* dr = h.out(R, 5 * n * sizeof(float));
+    CHK(h.staged());
+    launch_polyexp(c->stream, di, n, 1, l->w, l->h, c->pc, dr, 5 * n);
     CHK(check_launch("polyexp"));
-    CHK(download(c, R, dr.p, 5 * n * sizeof(float)));
-    return mav_sync(c);
+    return h.finish();
 }
 extern "C" int mav_stage_update_matrices(mav_ctx* c, const float* R0, const float* R1, const float* flow, int k, float* M)
 {
+    HostCall h(c, "mav_stage_update_matrices");
     const Layer* l;
-    CHK(layer_of(c, k, &l));
+    CHK(h.fresh_layer(k, &l));
     if (!R0 || !R1 || !flow || !M) return fail(MAV_ERR_ARG, "mav_stage_update_matrices: NULL argument");
     const size_t n = (size_t)l->w * l->h;
-    DevBuf d0, d1, df, dm;
-    CHK(d0.upload(c, R0, 5 * n * sizeof(float))); CHK(d1.upload(c, R1, 5 * n * sizeof(float)));
-    CHK(df.upload(c, flow, 2 * n * sizeof(float))); CHK(dm.alloc(c, 5 * n * sizeof(float)));
-    launch_update_matrices_flow(c->stream, d0.as<float>(), d1.as<float>(), 5 * n, df.as<float>(), 2 * n, 1, l->w, l->h, dm.as<float>(), 5 * n);
+    const float* d0 = h.in(R0, 5 * n * sizeof(float));
+    const float* d1 = h.in(R1, 5 * n * sizeof(float));
+    const float* df = h.in(flow, 2 * n * sizeof(float));
+    float* dm = h.out(M, 5 * n * sizeof(float));
+    CHK(h.staged());
+    launch_update_matrices_flow(c->stream, d0, d1, 5 * n, df, 2 * n, 1, l->w, l->h, dm, 5 * n);
     CHK(check_launch("update_matrices"));
-    CHK(download(c, M, dm.p, 5 * n * sizeof(float)));
-    return mav_sync(c);
+    return h.finish();
 }
 // The initial M as layer_sweeps builds it for layer k: from the coarser layer's flow (layer k + 1's size, upsampled and times
 // 1 / pyr_scale inside the kernel) or, flow_coarse == NULL, from a zero flow.
 extern "C" int mav_stage_update_matrices_from(mav_ctx* c, const float* R0, const float* R1, const float* flow_coarse, int k, float* M)
 {
+    HostCall h(c, "mav_stage_update_matrices_from");
     const Layer* l;
-    CHK(layer_of(c, k, &l));
+    CHK(h.fresh_layer(k, &l));
     if (!R0 || !R1 || !M) return fail(MAV_ERR_ARG, "mav_stage_update_matrices_from: NULL argument");
     if (flow_coarse && k + 1 >= (int)c->layers.size())
         return fail(MAV_ERR_ARG, "mav_stage_update_matrices_from: layer %d is the top layer, it has no coarser flow", k);
@@ -3143,48 +3182,51 @@ extern "C" int mav_stage_update_matrices_from(mav_ctx* c, const float* R0, const
     const int pw = flow_coarse ? c->layers[k + 1].w : 0, ph = flow_coarse ? c->layers[k + 1].h : 0;
     const size_t nc = (size_t)pw * ph;
     const float mul = (float)(1. / c->fb.pyr_scale);
-    DevBuf d0, d1, df, dm;
-    CHK(d0.upload(c, R0, 5 * n * sizeof(float))); CHK(d1.upload(c, R1, 5 * n * sizeof(float)));
-    if (flow_coarse) CHK(df.upload(c, flow_coarse, 2 * nc * sizeof(float)));
-    CHK(dm.alloc(c, 5 * n * sizeof(float)));
-    launch_update_matrices(c->stream, d0.as<float>(), d1.as<float>(), 5 * n, flow_coarse ? df.as<float>() : nullptr, 2 * nc, pw, ph, mul, 1,
-                           l->w, l->h, dm.as<float>(), 5 * n);
+    const float* d0 = h.in(R0, 5 * n * sizeof(float));
+    const float* d1 = h.in(R1, 5 * n * sizeof(float));
+    const float* df = h.in(flow_coarse, 2 * nc * sizeof(float));
+    float* dm = h.out(M, 5 * n * sizeof(float));
+    CHK(h.staged());
+    launch_update_matrices(c->stream, d0, d1, 5 * n, df, 2 * nc, pw, ph, mul, 1, l->w, l->h, dm, 5 * n);
     CHK(check_launch("update_matrices"));
-    CHK(download(c, M, dm.p, 5 * n * sizeof(float)));
-    return mav_sync(c);
+    return h.finish();
 }
 // The initial flow of layer k from a frame-size field as snapshot_initial_flow computes it for the top layer: INTER_AREA resize,
 // then times pyr_scale^k (the repeated product).
 extern "C" int mav_stage_initial_flow(mav_ctx* c, const float* flow0, int k, float* out)
 {
+    HostCall h(c, "mav_stage_initial_flow");
     const Layer* l;
-    CHK(layer_of(c, k, &l));
+    CHK(h.fresh_layer(k, &l));
     if (!flow0 || !out) return fail(MAV_ERR_ARG, "mav_stage_initial_flow: NULL argument");
     const size_t n = (size_t)l->w * l->h;
     double scale = 1;
     for (int i = 0; i < k; i++) scale *= c->fb.pyr_scale;
-    DevBuf di, dout;
-    CHK(di.upload(c, flow0, 2 * c->n0 * sizeof(float))); CHK(dout.alloc(c, 2 * n * sizeof(float)));
-    launch_area_resize_flow(c->stream, di.as<float>(), 2 * c->n0, c->W, c->H, dout.as<float>(), 2 * n, l->w, l->h, 1, scale);
+    const float* di = h.in(flow0, 2 * c->n0 * sizeof(float));
+    float* dout = h.out(out, 2 * n * sizeof(float));
+    CHK(h.staged());
+    launch_area_resize_flow(c->stream, di, 2 * c->n0, c->W, c->H, dout, 2 * n, l->w, l->h, 1, scale);
     CHK(check_launch("area_resize_flow"));
-    CHK(download(c, out, dout.p, 2 * n * sizeof(float)));
-    return mav_sync(c);
+    return h.finish();
 }
 extern "C" int mav_stage_blur_iter(mav_ctx* c, const float* R0, const float* R1, const float* M, int k, int update, float* flow, float* M_out)
 {
+    HostCall h(c, "mav_stage_blur_iter");
     const Layer* l;
-    CHK(layer_of(c, k, &l));
+    CHK(h.fresh_layer(k, &l));
     if (!R0 || !R1 || !M || !flow || (update && !M_out)) return fail(MAV_ERR_ARG, "mav_stage_blur_iter: NULL argument");
     const size_t n = (size_t)l->w * l->h;
-    DevBuf d0, d1, dm, dmo, df;
-    CHK(d0.upload(c, R0, 5 * n * sizeof(float))); CHK(d1.upload(c, R1, 5 * n * sizeof(float)));
-    CHK(dm.upload(c, M, 5 * n * sizeof(float))); CHK(dmo.alloc(c, 5 * n * sizeof(float))); CHK(df.alloc(c, 2 * n * sizeof(float)));
-    launch_blur_iter(c->stream, dm.as<float>(), dmo.as<float>(), 5 * n, d0.as<float>(), d1.as<float>(), 5 * n, 1, l->w, l->h,
-                     c->fb.winsize, update, 1, df.as<float>(), 2 * n, 0, -1, c->strip, false, window_taps(c));
+    const float* d0 = h.in(R0, 5 * n * sizeof(float));
+    const float* d1 = h.in(R1, 5 * n * sizeof(float));
+    const float* dm = h.in(M, 5 * n * sizeof(float));
+    float* dmo = h.scratch<float>(5 * n * sizeof(float));
+    float* df = h.out(flow, 2 * n * sizeof(float));
+    h.fetch(update ? M_out : nullptr, dmo, 5 * n * sizeof(float));
+    CHK(h.staged());
+    launch_blur_iter(c->stream, dm, dmo, 5 * n, d0, d1, 5 * n, 1, l->w, l->h, c->fb.winsize, update, 1, df, 2 * n, 0, -1, c->strip, false,
+                     window_taps(c));
     CHK(check_launch("blur_iter"));
-    CHK(download(c, flow, df.p, 2 * n * sizeof(float)));
-    if (update) CHK(download(c, M_out, dmo.p, 5 * n * sizeof(float)));
-    return mav_sync(c);
+    return h.finish();
 }
 
 // ---- RCCL (loaded lazily so the single-GPU path carries no collective library) ----------------------------------------
