@@ -10,6 +10,7 @@
 #include "mavflow_internal.h"
 
 #include <algorithm>
+#include <type_traits>
 
 static __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
@@ -135,213 +136,102 @@ static __device__ __forceinline__ void quad_px(typename QuadOf<T>::type q, float
     }
 }
 
-// Horizontal pass at destination column (s0, f) for the four source rows y0 .. y0 + 3 (clamped to the image): the ONE spelling of
-// this arithmetic, shared by the two-pass and the fused kernel so that both give the same bits.
-template <typename T>
-static __device__ __forceinline__ void blur_h4(const T* __restrict__ base, int W, int H, int y0, int s0, float f,
-                                               const BlurParams& bp, float out[4])
-{
-    const int r = bp.ksize >> 1;
-    const int s1 = s0 + 1 < W ? s0 + 1 : s0;
-    const T* rows[4];
+// ---- The separable passes: ONE body per pass, two compile-time policies --------------------------------------------------------
+// Along an axis the output is  out = fmaf(B[s0 + 1], f, B[s0] * (1 - f)).  Away from the border the two Gaussian sums share their
+// pixels: pixel j (0 .. ksize) of the run that starts at s0 - r contributes g[j] * p to B[s0] (j < ksize) and g[j - 1] * p to
+// B[s0 + 1] (j >= 1), and each sum is ONE chain of fused multiply-adds in increasing j.  That order is the whole bit contract: every
+// form below (fused == two-pass, u8 values == u8 bits at every depth) keeps it, whichever policies it picks.
+//   Px    where pixel j of the thread's four rows comes from: PxBytes (u8: aligned dwords re-aligned with v_alignbyte, from staged
+//         LDS rows or from global memory) or PxElems (one addressable element per pixel: uint16 / float staged rows, any depth from
+//         global memory)
+//   Taps  how a pixel is accumulated: TapsScalar (two scalar fmaf, g[] from the kernel argument) or TapsPairs (one packed fma of the
+//         pair (g[j], g[j - 1]) with (p, p); the pairs sit in LDS -- stage_tap_pairs -- or in registers -- TapPairs<KS>)
+// KS > 0: ksize known at compile time (the loops unroll: all loads of a thread issue together); KS == 0: a loop over ksize.
+typedef float mav_f2 __attribute__((ext_vector_type(2)));
+static __device__ __forceinline__ int tap_pairs_padded(int ksize) { return (ksize + 1 + 3) & ~3; }
+
+// word(k, i) = aligned dword i of the byte stream of the thread's k-th row; the row's pixel 0 is byte sh[k] of dword 0.  Pixels
+// 4c .. 4c + 3 need dwords c and c + 1, so the stream reads one dword past the last pixel's: staged rows carry a word of slack for
+// that (tile_columns, staged_pitch_words), and a word function over global memory returns 0 for dwords that hold no needed byte
+// instead of reading them.
+template <typename WordFn> struct PxBytes {
+    static constexpr int STEP = 4;                       // pixels per advance()
+    static constexpr bool whole_words = true;            // pixels past ksize are bytes like any other: finite, free to meet a zero tap
+    WordFn word;
+    unsigned sh[4];
+    uint32_t lo[4], cur[4];
+    __device__ __forceinline__ void begin()
+    {
 #pragma unroll
-    for (int k = 0; k < 4; k++) rows[k] = base + (size_t)min(y0 + k, H - 1) * W;
-    float b0[4] = {0.f, 0.f, 0.f, 0.f}, b1[4] = {0.f, 0.f, 0.f, 0.f};
-    if (s0 - r >= 0 && s0 + 1 + r < W) {               // interior: B[s0+1] re-uses B[s0]'s pixels shifted by one
-        float prev[4];
-        if (bp.ksize == 5) {                               // all 24 pixels of the thread requested before any is used
-            T px[4][6];
+        for (int k = 0; k < 4; k++) lo[k] = word(k, 0);
+    }
+    __device__ __forceinline__ void advance(int c)
+    {
 #pragma unroll
-            for (int k = 0; k < 4; k++)
-#pragma unroll
-                for (int t = 0; t < 6; t++) px[k][t] = rows[k][s0 - 2 + t];
-#pragma unroll
-            for (int t = 0; t < 5; t++) {
-                const float g = bp.g[t];
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    b0[k] = fmaf(g, (float)px[k][t], b0[k]);
-                    b1[k] = fmaf(g, (float)px[k][t + 1], b1[k]);
-                }
-            }
-        } else if constexpr (sizeof(T) > 1) {              // wider pixels: one aligned element load each, same order as below
-#pragma unroll
-            for (int k = 0; k < 4; k++) prev[k] = (float)rows[k][s0 - r];
-            for (int j = 1; j <= bp.ksize; j++) {
-                const float g = bp.g[j - 1];
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const float nxt = (float)rows[k][s0 - r + j];
-                    b0[k] = fmaf(g, prev[k], b0[k]);
-                    b1[k] = fmaf(g, nxt, b1[k]);
-                    prev[k] = nxt;
-                }
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; k++) prev[k] = (float)rows[k][s0 - r];
-            // long kernels (the 4K / 5-layer preset has 13-, 37- and 95-tap layers): the ksize + 1 consecutive bytes of a row
-            // come as ALIGNED dwords and are re-aligned with v_alignbyte -- a quarter of the load instructions.  Only words
-            // that hold a needed byte are read (an aligned dword never crosses a page, so nothing unmapped is touched).
-            // Same products in the same order as the byte loop: identical results.
-            const uint32_t* wp[4];
-            unsigned sh[4];
-            uint32_t lo[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const uintptr_t a = (uintptr_t)(rows[k] + (s0 - r));
-                wp[k] = (const uint32_t*)(a & ~(uintptr_t)3);
-                sh[k] = (unsigned)(a & 3);
-                lo[k] = wp[k][0];
-            }
-            const int nbytes = bp.ksize + 1;                 // byte 0 = prev, byte j = tap j - 1's "next"
-            for (int c = 0; 4 * c < nbytes; c++) {
-                uint32_t cur[4];
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    // the needed bytes sit at positions sh .. sh + nbytes - 1 of the word stream
-                    const uint32_t hi = c + 1 <= ((int)sh[k] + nbytes - 1) / 4 ? wp[k][c + 1] : 0u;
-                    cur[k] = __builtin_amdgcn_alignbyte(hi, lo[k], sh[k]);
-                    lo[k] = hi;
-                }
-#pragma unroll
-                for (int b = 0; b < 4; b++) {
-                    const int j = 4 * c + b;
-                    if (j >= nbytes) break;
-                    if (j > 0) {
-                        const float g = bp.g[j - 1];
-#pragma unroll
-                        for (int k = 0; k < 4; k++) {
-                            const float nxt = (float)((cur[k] >> (8 * b)) & 0xffu);
-                            b0[k] = fmaf(g, prev[k], b0[k]);
-                            b1[k] = fmaf(g, nxt, b1[k]);
-                            prev[k] = nxt;
-                        }
-                    }
-                }
-            }
-        }
-    } else {
-        for (int t = 0; t < bp.ksize; t++) {
-            const float g = bp.g[t];
-            const int c0 = reflect101d(s0 - r + t, W), c1 = reflect101d(s1 - r + t, W);
-#pragma unroll
-            for (int k = 0; k < 4; k++) { b0[k] = fmaf(g, (float)rows[k][c0], b0[k]); b1[k] = fmaf(g, (float)rows[k][c1], b1[k]); }
+        for (int k = 0; k < 4; k++) {
+            const uint32_t hi = word(k, c + 1);
+            cur[k] = __builtin_amdgcn_alignbyte(hi, lo[k], sh[k]);
+            lo[k] = hi;
         }
     }
-    const float a0 = 1.f - f;
-#pragma unroll
-    for (int k = 0; k < 4; k++) out[k] = fmaf(b1[k], f, b0[k] * a0);
+    __device__ __forceinline__ float get(int k, int c, int b) const { return (float)((cur[k] >> (8 * b)) & 0xffu); }
+};
+template <typename WordFn>
+static __device__ __forceinline__ PxBytes<WordFn> px_bytes(WordFn word, unsigned s0, unsigned s1, unsigned s2, unsigned s3)
+{
+    return PxBytes<WordFn>{word, {s0, s1, s2, s3}, {}, {}};
 }
-
-// The same horizontal pass for four rows of a source region STAGED IN LDS (stage_rows: columns outside the image already hold their
-// BORDER_REFLECT_101 pixels, so one code path serves interior and border tiles).  rd(k, wi) = aligned dword wi of the thread's k-th
-// row; the thread's first tap is byte `off` of that stream; tap t multiplies byte off + t for B[s0] and byte off + t + 1 for
-// B[s0 + 1] (when s0 is the last column resize_coord gives f = 0 and B[s0 + 1] drops out exactly).  The bytes come as dwords
-// re-aligned with v_alignbyte.  Same products in the same order with the same fused roundings as blur_h4: identical bits.
-template <int KS, typename WordFn>      // KS > 0: ksize known at compile time (the loops unroll: all LDS reads of a thread issue together)
-static __device__ __forceinline__ void blur_h4_stream_t(WordFn rd, int off, float f, const BlurParams& bp, float out[4])
+// four rows staged in LDS by stage_rows (or the fast tile's own loop): row(k) = first dword of the thread's k-th row, off = byte
+// offset of the thread's pixel 0 in it
+template <typename RowFn>
+static __device__ __forceinline__ auto px_staged_bytes(RowFn row, int off)
 {
     const int w0 = off >> 2;
     const unsigned sh = (unsigned)(off & 3);
-    const int nbytes = (KS > 0 ? KS : bp.ksize) + 1;          // byte 0 = the first "prev", byte j = tap j - 1's "next"
-    float b0[4] = {0.f, 0.f, 0.f, 0.f}, b1[4] = {0.f, 0.f, 0.f, 0.f}, prev[4] = {0.f, 0.f, 0.f, 0.f};
-    uint32_t lo[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) lo[k] = rd(k, w0);
-    auto step = [&](int c) {
-        uint32_t cur[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const uint32_t hi = rd(k, w0 + c + 1);              // (one word of slack behind every staged row)
-            cur[k] = __builtin_amdgcn_alignbyte(hi, lo[k], sh);
-            lo[k] = hi;
-        }
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const int j = 4 * c + b;
-            if (j >= nbytes) break;
-            if (j == 0) {
-#pragma unroll
-                for (int k = 0; k < 4; k++) prev[k] = (float)(cur[k] & 0xffu);
-            } else {
-                const float g = bp.g[j - 1];
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const float nxt = (float)((cur[k] >> (8 * b)) & 0xffu);
-                    b0[k] = fmaf(g, prev[k], b0[k]);
-                    b1[k] = fmaf(g, nxt, b1[k]);
-                    prev[k] = nxt;
-                }
-            }
-        }
-        };
-    if constexpr (KS > 0) {
-#pragma unroll
-        for (int c = 0; 4 * c < KS + 1; c++) step(c);
-    } else {
-        for (int c = 0; 4 * c < nbytes; c++) step(c);
-    }
-    const float a0 = 1.f - f;
-#pragma unroll
-    for (int k = 0; k < 4; k++) out[k] = fmaf(b1[k], f, b0[k] * a0);
+    return px_bytes([=](int k, int i) { return row(k)[w0 + i]; }, sh, sh, sh, sh);
 }
-template <typename WordFn>
-static __device__ __forceinline__ void blur_h4_stream(WordFn rd, int off, float f, const BlurParams& bp, float out[4])
-{
-    if (bp.ksize == 5) blur_h4_stream_t<5>(rd, off, f, bp, out);          // the reference's preset: layer 1 (scale 0.4, sigma 0.75)
-    else if (bp.ksize == 13) blur_h4_stream_t<13>(rd, off, f, bp, out);
-    else blur_h4_stream_t<0>(rd, off, f, bp, out);
-}
-// blur_h4_stream_t for the wider depths: px(k, j) = pixel j (0 .. ksize) of the thread's k-th staged row, already a float.  The same
-// products in the same order: prev = pixel j - 1, nxt = pixel j for tap j - 1.
-template <int KS, typename PxFn>
-static __device__ __forceinline__ void blur_h4_stream_px(PxFn px, float f, const BlurParams& bp, float out[4])
-{
-    float b0[4] = {0.f, 0.f, 0.f, 0.f}, b1[4] = {0.f, 0.f, 0.f, 0.f}, prev[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) prev[k] = px(k, 0);
-    auto step = [&](int j) {
-        const float g = bp.g[j - 1];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const float nxt = px(k, j);
-            b0[k] = fmaf(g, prev[k], b0[k]);
-            b1[k] = fmaf(g, nxt, b1[k]);
-            prev[k] = nxt;
-        }
-    };
-    if constexpr (KS > 0) {
-#pragma unroll
-        for (int j = 1; j <= KS; j++) step(j);
-    } else {
-        for (int j = 1; j <= bp.ksize; j++) step(j);
-    }
-    const float a0 = 1.f - f;
-#pragma unroll
-    for (int k = 0; k < 4; k++) out[k] = fmaf(b1[k], f, b0[k] * a0);
-}
-template <typename PxFn>
-static __device__ __forceinline__ void blur_h4_stream_px(PxFn px, float f, const BlurParams& bp, float out[4])
-{
-    if (bp.ksize == 5) blur_h4_stream_px<5>(px, f, bp, out);
-    else if (bp.ksize == 13) blur_h4_stream_px<13>(px, f, bp, out);
-    else blur_h4_stream_px<0>(px, f, bp, out);
-}
+// elem(k, j) = pixel j of the thread's k-th row, already a float.  Nothing past pixel ksize is ever read (a float frame's staging
+// slack is unwritten LDS and may hold NaN).
+template <typename ElemFn> struct PxElems {
+    static constexpr int STEP = 1;
+    static constexpr bool whole_words = false;
+    ElemFn elem;
+    __device__ __forceinline__ void begin() {}
+    __device__ __forceinline__ void advance(int) {}
+    __device__ __forceinline__ float get(int k, int c, int) const { return elem(k, c); }
+};
+template <typename ElemFn> static __device__ __forceinline__ PxElems<ElemFn> px_elems(ElemFn elem) { return PxElems<ElemFn>{elem}; }
 
-// The horizontal pass once more, for LONG Gaussians (the two-pass kernels: 37 and 95 taps at 3840 x 2160 / 5 layers), on tap PAIRS
-// kept in LDS.  blur_h4_stream's generic loop fetched every tap with a vector load from global memory and waited for it -- one
-// memory round trip per tap (the taps sit behind a pointer the compiler cannot prove constant next to the kernel's own stores) --
-// and shuffled registers to pack two rows into one v_pk_fma_f32.  Here the (b0, b1) accumulators of ONE row are the packed pair:
-// source byte t of the row contributes  g[t] * p  to B[s0]  and  g[t - 1] * p  to B[s0 + 1], i.e. one packed FMA of the pair
-// G2[t] = (g[t], g[t - 1]) (LDS, one broadcast ds_read_b64 per tap for all four rows) with the splat (p, p):
-//     B[s0]     accumulates g[0] p[0], g[1] p[1], ...            -- the order of blur_h4 / blur_h4_stream
-//     B[s0 + 1] accumulates g[0] p[1], g[1] p[2], ...            -- likewise
-// G2[0] = (g[0], 0), G2[ksize] = (0, g[ksize - 1]) and the padding up to a multiple of four taps is (0, 0): a fused multiply-add
-// with a zero tap returns its accumulator unchanged (pixels are finite, the accumulators start at +0), so the bits are those of the
-// other forms (tests/test_gpu_flow.py: fused == two-pass == oracle).
-typedef float mav_f2 __attribute__((ext_vector_type(2)));
-static __device__ __forceinline__ int tap_pairs_padded(int ksize) { return (ksize + 1 + 3) & ~3; }
+// g[] behind the kernel argument: wave-uniform scalar loads, a tap serves both sums (B[s0] with the pixel before, B[s0 + 1] with this one)
+struct TapsScalar {
+    static constexpr bool zero_padded = false;
+    struct Acc { float b0, b1, prev; };
+    typedef float Tap;
+    const float* g;
+    __device__ __forceinline__ Tap tap(int j) const { return j > 0 ? g[j - 1] : 0.f; }
+    __device__ __forceinline__ void add(Acc& a, Tap t, int j, float p) const
+    {
+        if (j > 0) { a.b0 = fmaf(t, a.prev, a.b0); a.b1 = fmaf(t, p, a.b1); }
+        a.prev = p;
+    }
+    static __device__ __forceinline__ float b0(const Acc& a) { return a.b0; }
+    static __device__ __forceinline__ float b1(const Acc& a) { return a.b1; }
+};
+// The (B[s0], B[s0 + 1]) accumulators of ONE row as a packed pair: pixel j costs one conversion and one v_pk_fma_f32 with
+// pair(j) = (g[j], g[j - 1]), where pair(0) = (g[0], 0) and pair(ksize) = (0, g[ksize - 1]).  ZERO_PADDED: pair(j) is (0, 0) from
+// ksize + 1 up to tap_pairs_padded(ksize), so a byte stream may run to the end of its last word -- a fused multiply-add with a zero
+// tap returns its accumulator unchanged (pixels are finite, the accumulators start at +0).
+template <typename PairFn, bool ZERO_PADDED> struct TapsPairs {
+    static constexpr bool zero_padded = ZERO_PADDED;
+    typedef mav_f2 Acc;
+    typedef mav_f2 Tap;
+    PairFn pair;
+    __device__ __forceinline__ Tap tap(int j) const { return pair(j); }
+    __device__ __forceinline__ void add(Acc& a, Tap t, int, float p) const { a = __builtin_elementwise_fma(t, (mav_f2)(p, p), a); }
+    static __device__ __forceinline__ float b0(const Acc& a) { return a.x; }
+    static __device__ __forceinline__ float b1(const Acc& a) { return a.y; }
+};
+// the pairs in LDS (the two-pass kernel: long Gaussians, one broadcast ds_read_b64 per tap for all four rows), padded with zeros
 static __device__ __forceinline__ void stage_tap_pairs(const BlurParams& bp, mav_f2* __restrict__ G2)
 {
     const int n = tap_pairs_padded(bp.ksize);
@@ -352,64 +242,110 @@ static __device__ __forceinline__ void stage_tap_pairs(const BlurParams& bp, mav
         G2[t] = v;
     }
 }
-template <typename WordFn>
-static __device__ __forceinline__ void blur_h4_pairs(WordFn rd, int off, float f, int ksize, const mav_f2* __restrict__ G2, float out[4])
+static __device__ __forceinline__ auto taps_lds_pairs(const mav_f2* __restrict__ G2)
 {
-    const int w0 = off >> 2;
-    const unsigned sh = (unsigned)(off & 3);
-    const int n_words = tap_pairs_padded(ksize) >> 2;
-    mav_f2 acc[4];
-    uint32_t lo[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) { acc[k] = (mav_f2)(0.f, 0.f); lo[k] = rd(k, w0); }
-    for (int c = 0; c < n_words; c++) {
-        uint32_t cur[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const uint32_t hi = rd(k, w0 + c + 1);              // (one word of slack behind every staged row)
-            cur[k] = __builtin_amdgcn_alignbyte(hi, lo[k], sh);
-            lo[k] = hi;
-        }
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const mav_f2 G = G2[4 * c + b];
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const float p = (float)((cur[k] >> (8 * b)) & 0xffu);
-                acc[k] = __builtin_elementwise_fma(G, (mav_f2)(p, p), acc[k]);
-            }
-        }
-    }
-    const float a0 = 1.f - f;
-#pragma unroll
-    for (int k = 0; k < 4; k++) out[k] = fmaf(acc[k].y, f, acc[k].x * a0);
+    auto pair = [=](int j) { return G2[j]; };
+    return TapsPairs<decltype(pair), true>{pair};
 }
-// The pair form for the wider depths: px(k, t) = pixel t of the thread's k-th staged row as a float, G(t) = tap pair t.  Pixels
-// 0 .. ksize only: the u8 form's padding pairs are (0, 0), whose fused multiply-adds leave the accumulators as they are, so stopping at
-// ksize gives the same bits -- and a float frame's staging slack (not written) is never multiplied.  KS > 0: ksize at compile time.
-template <int KS, typename PxFn, typename PairFn>
-static __device__ __forceinline__ void blur_h4_pairs_px(PxFn px, float f, int ksize, PairFn G, float out[4])
+// the pairs in registers, for a Gaussian whose length is a template argument (the fused fast tile: 13 taps)
+template <int KS> struct TapPairs {
+    mav_f2 G[KS + 1];
+    __device__ __forceinline__ void load(const BlurParams& bp)
+    {
+#pragma unroll
+        for (int t = 0; t <= KS; t++) { G[t].x = t < KS ? bp.g[t] : 0.f; G[t].y = t >= 1 ? bp.g[t - 1] : 0.f; }
+    }
+    __device__ __forceinline__ auto taps() const
+    {
+        auto pair = [this](int j) { return G[j]; };
+        return TapsPairs<decltype(pair), false>{pair};
+    }
+};
+
+// Horizontal pass of the thread's four rows, interior form (the rows' ksize + 1 pixels are all there: inside the image, or staged
+// with their BORDER_REFLECT_101 pixels in place).
+template <int KS, class Px, class Taps>
+static __device__ __forceinline__ void blur_h4_run(Px px, const Taps& taps, int ksize, float f, float out[4])
 {
-    mav_f2 acc[4];
+    // pixels to visit: 0 .. ksize, or whole words of them where both policies allow it (no bounds test per byte in the long loops)
+    const int n = KS > 0 ? KS + 1 : (Px::whole_words && Taps::zero_padded ? tap_pairs_padded(ksize) : ksize + 1);
+    typename Taps::Acc acc[4] = {};
+    px.begin();
+    auto step = [&](int c) {
+        px.advance(c);
 #pragma unroll
-    for (int k = 0; k < 4; k++) acc[k] = (mav_f2)(0.f, 0.f);
-    auto step = [&](int t) {
-        const mav_f2 g = G(t);
+        for (int b = 0; b < Px::STEP; b++) {
+            const int j = Px::STEP * c + b;
+            if (!(Px::whole_words && Taps::zero_padded) && j >= n) break;       // (n is whole words where both hold)
+            const typename Taps::Tap t = taps.tap(j);
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const float p = px(k, t);
-            acc[k] = __builtin_elementwise_fma(g, (mav_f2)(p, p), acc[k]);
+            for (int k = 0; k < 4; k++) taps.add(acc[k], t, j, px.get(k, c, b));
         }
     };
     if constexpr (KS > 0) {
 #pragma unroll
-        for (int t = 0; t <= KS; t++) step(t);
+        for (int c = 0; Px::STEP * c < KS + 1; c++) step(c);
     } else {
-        for (int t = 0; t <= ksize; t++) step(t);
+        for (int c = 0; Px::STEP * c < n; c++) step(c);
     }
     const float a0 = 1.f - f;
 #pragma unroll
-    for (int k = 0; k < 4; k++) out[k] = fmaf(acc[k].y, f, acc[k].x * a0);
+    for (int k = 0; k < 4; k++) out[k] = fmaf(Taps::b1(acc[k]), f, Taps::b0(acc[k]) * a0);
+}
+// scalar taps, ksize dispatched at run time: 5 (the reference's preset: layer 1, scale 0.4, sigma 0.75) and 13 unroll
+template <class Px>
+static __device__ __forceinline__ void blur_h4_scalar(Px px, float f, const BlurParams& bp, float out[4])
+{
+    const TapsScalar taps{bp.g};
+    if (bp.ksize == 5) blur_h4_run<5>(px, taps, 5, f, out);
+    else if (bp.ksize == 13) blur_h4_run<13>(px, taps, 13, f, out);
+    else blur_h4_run<0>(px, taps, bp.ksize, f, out);
+}
+
+// Horizontal pass at destination column (s0, f) for the four source rows y0 .. y0 + 3 (clamped to the image) read from GLOBAL memory:
+// the unstaged fused tile (u8 frames whose rows are not quad-addressable behind 13 taps) and the direct kernel (ksize >= 123).
+template <typename T>
+static __device__ __forceinline__ void blur_h4(const T* __restrict__ base, int W, int H, int y0, int s0, float f,
+                                               const BlurParams& bp, float out[4])
+{
+    const int r = bp.ksize >> 1;
+    const T* rows[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) rows[k] = base + (size_t)min(y0 + k, H - 1) * W;
+    if (s0 - r >= 0 && s0 + 1 + r < W) {               // interior: B[s0+1] re-uses B[s0]'s pixels shifted by one
+        const TapsScalar taps{bp.g};
+        if constexpr (sizeof(T) > 1) {                     // one aligned element load per pixel
+            blur_h4_run<0>(px_elems([&](int k, int j) { return (float)rows[k][s0 - r + j]; }), taps, bp.ksize, f, out);
+        } else {
+            // the ksize + 1 consecutive bytes of a row come as ALIGNED dwords -- a quarter of the load instructions.  Only words
+            // that hold a needed byte are read (an aligned dword never crosses a page, so nothing unmapped is touched).
+            const uint32_t* wp[4];
+            unsigned sh[4];
+            int last[4];                                     // the needed bytes sit at positions sh .. sh + ksize of the word stream
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const uintptr_t a = (uintptr_t)(rows[k] + (s0 - r));
+                wp[k] = (const uint32_t*)(a & ~(uintptr_t)3);
+                sh[k] = (unsigned)(a & 3);
+                last[k] = ((int)sh[k] + bp.ksize) / 4;
+            }
+            blur_h4_run<0>(px_bytes([&](int k, int i) { return i <= last[k] ? wp[k][i] : 0u; }, sh[0], sh[1], sh[2], sh[3]), taps,
+                           bp.ksize, f, out);
+        }
+        return;
+    }
+    // border: the columns of B[s0] and of B[s0 + 1] reflect separately and share no pixels
+    const int s1 = s0 + 1 < W ? s0 + 1 : s0;
+    float b0[4] = {0.f, 0.f, 0.f, 0.f}, b1[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < bp.ksize; t++) {
+        const float g = bp.g[t];
+        const int c0 = reflect101d(s0 - r + t, W), c1 = reflect101d(s1 - r + t, W);
+#pragma unroll
+        for (int k = 0; k < 4; k++) { b0[k] = fmaf(g, (float)rows[k][c0], b0[k]); b1[k] = fmaf(g, (float)rows[k][c1], b1[k]); }
+    }
+    const float a0 = 1.f - f;
+#pragma unroll
+    for (int k = 0; k < 4; k++) out[k] = fmaf(b1[k], f, b0[k] * a0);
 }
 
 // Source rows [y0, y0 + n_rows) (row index clamped to the image), pixel columns [xb, xb + 4 words) of one image -> LDS, row pitch
@@ -471,40 +407,44 @@ static __device__ __forceinline__ void tile_columns(int s0, const BlurParams& bp
     const int c0 = __builtin_amdgcn_readlane(s0, 0), c1 = __builtin_amdgcn_readlane(s0, 63);
     const int r = bp.ksize >> 1;
     *xb = (c0 - r) & ~3;
-    *words = ((c1 + 1 + r - *xb) >> 2) + 2;                  // + 1: blur_h4_stream reads one word ahead
+    *words = ((c1 + 1 + r - *xb) >> 2) + 2;                  // + 1: PxBytes reads one word ahead
 }
 
+// Vertical pass, interior form, of one column: row(j) = the horizontal pass's value at source row (s0 - r) + j of this thread's
+// column, j = 0 .. ksize.  The same chains in the same order as blur_h4_run, with the same Taps policies.
+template <int KS, typename RowFn, class Taps>
+static __device__ __forceinline__ float blur_v1_run(RowFn row, const Taps& taps, int ksize, float f)
+{
+    typename Taps::Acc acc = {};
+    if constexpr (KS > 0) {                                // the KS + 1 rows of the thread requested together
+        float px[KS + 1];
+#pragma unroll
+        for (int j = 0; j <= KS; j++) px[j] = row(j);
+#pragma unroll
+        for (int j = 0; j <= KS; j++) taps.add(acc, taps.tap(j), j, px[j]);
+    } else {
+#pragma unroll 8
+        for (int j = 0; j <= ksize; j++) taps.add(acc, taps.tap(j), j, row(j));
+    }
+    return fmaf(Taps::b1(acc), f, Taps::b0(acc) * (1.f - f));
+}
 // Vertical pass at destination row (s0, f): row(y) = the horizontal pass's value at source row y of this thread's column.
 template <typename RowFn>
 static __device__ __forceinline__ float blur_v1(RowFn row, int H, int s0, float f, const BlurParams& bp)
 {
     const int r = bp.ksize >> 1;
+    if (s0 - r >= 0 && s0 + 1 + r < H) {
+        const TapsScalar taps{bp.g};
+        auto at = [&](int j) { return row(s0 - r + j); };
+        return bp.ksize == 5 ? blur_v1_run<5>(at, taps, 5, f) : blur_v1_run<0>(at, taps, bp.ksize, f);
+    }
+    // border: the rows of B[s0] and of B[s0 + 1] reflect separately
     const int s1 = s0 + 1 < H ? s0 + 1 : s0;
     float b0 = 0.f, b1 = 0.f;
-    if (s0 - r >= 0 && s0 + 1 + r < H) {
-        if (bp.ksize == 5) {                               // the six rows of the thread requested together
-            float px[6];
-#pragma unroll
-            for (int t = 0; t < 6; t++) px[t] = row(s0 - 2 + t);
-#pragma unroll
-            for (int t = 0; t < 5; t++) { b0 = fmaf(bp.g[t], px[t], b0); b1 = fmaf(bp.g[t], px[t + 1], b1); }
-        } else {
-            float prev = row(s0 - r);
-#pragma unroll 8
-            for (int t = 0; t < bp.ksize; t++) {
-                const float g = bp.g[t];
-                const float nxt = row(s0 - r + t + 1);
-                b0 = fmaf(g, prev, b0);
-                b1 = fmaf(g, nxt, b1);
-                prev = nxt;
-            }
-        }
-    } else {
-        for (int t = 0; t < bp.ksize; t++) {
-            const float g = bp.g[t];
-            b0 = fmaf(g, row(reflect101d(s0 - r + t, H)), b0);
-            b1 = fmaf(g, row(reflect101d(s1 - r + t, H)), b1);
-        }
+    for (int t = 0; t < bp.ksize; t++) {
+        const float g = bp.g[t];
+        b0 = fmaf(g, row(reflect101d(s0 - r + t, H)), b0);
+        b1 = fmaf(g, row(reflect101d(s1 - r + t, H)), b1);
     }
     return fmaf(b1, f, b0 * (1.f - f));
 }
@@ -560,11 +500,13 @@ __global__ __launch_bounds__(256) void k_blur_resize_h(const T* __restrict__ img
         __syncthreads();
         for (int i = wv * 4; i < n_rows; i += 16) {
             float o[4];
+            // (rows past n_rows clamp to the last one; their results are not stored)
             if constexpr (sizeof(T) == 1)
-                blur_h4_pairs([&](int k, int wi) { return srows[min(i + k, n_rows - 1) * pitch_w + wi]; }, off, f, bp.ksize, G2, o);
+                blur_h4_run<0>(px_staged_bytes([&](int k) { return srows + min(i + k, n_rows - 1) * pitch_w; }, off), taps_lds_pairs(G2),
+                               bp.ksize, f, o);
             else
-                blur_h4_pairs_px<0>([&](int k, int t) { return (float)((const T*)srows)[(min(i + k, n_rows - 1) * pitch_w) * 4 + off + t]; },
-                                    f, bp.ksize, [&](int t) { return G2[t]; }, o);
+                blur_h4_run<0>(px_elems([&](int k, int j) { return (float)((const T*)srows)[(min(i + k, n_rows - 1) * pitch_w) * 4 + off + j]; }),
+                               taps_lds_pairs(G2), bp.ksize, f, o);
             if (dx < w) {
 #pragma unroll
                 for (int k = 0; k < 4; k++)
@@ -630,9 +572,9 @@ static __device__ __forceinline__ void blur_fused_tile(const T* __restrict__ bas
         for (int i = wv * 4; i < n_rows; i += 16) {
             float o[4];
             if constexpr (sizeof(T) == 1)
-                blur_h4_stream([&](int k, int wi) { return sw[min(i + k, n_rows - 1) * pitch_w + wi]; }, off, f, bp, o);
+                blur_h4_scalar(px_staged_bytes([&](int k) { return sw + min(i + k, n_rows - 1) * pitch_w; }, off), f, bp, o);
             else
-                blur_h4_stream_px([&](int k, int t) { return (float)((const T*)sw)[(min(i + k, n_rows - 1) * pitch_w) * 4 + off + t]; }, f, bp, o);
+                blur_h4_scalar(px_elems([&](int k, int j) { return (float)((const T*)sw)[(min(i + k, n_rows - 1) * pitch_w) * 4 + off + j]; }), f, bp, o);
 #pragma unroll
             for (int k = 0; k < 4; k++)
                 if (i + k < n_rows) hrows[(i + k) * 64 + lane] = o[k];
@@ -669,69 +611,9 @@ static __device__ __forceinline__ void blur_fused_tile(const T* __restrict__ bas
 //     loads in flight; every staged row lies inside the image (ylo + row <= yhi <= H - 1), so no clamping;
 //   * the H pass does not clamp its row index: rows past n_rows (at most 3, LDS the launch allocates) are computed and not stored;
 //   * interior tiles (every row's taps inside the image) take a V pass without the reflect-101 tests.
-// The (b0, b1)-pair form of blur_h4_pairs for a Gaussian whose length is a template argument (the fused tile: 5 and 13 taps): the
-// KS + 1 tap pairs (g[t], g[t - 1]) are wave-uniform values the caller builds once per thread (TapPairs), byte t of a row costs one
-// conversion and one packed FMA.  Same accumulation order as blur_h4_stream: same bits.
-template <int KS> struct TapPairs {
-    mav_f2 G[KS + 1];
-    __device__ __forceinline__ void load(const BlurParams& bp)
-    {
-#pragma unroll
-        for (int t = 0; t <= KS; t++) { G[t].x = t < KS ? bp.g[t] : 0.f; G[t].y = t >= 1 ? bp.g[t - 1] : 0.f; }
-    }
-};
-template <int KS, typename WordFn>
-static __device__ __forceinline__ void blur_h4_pairs_t(WordFn rd, int off, float f, const TapPairs<KS>& tp, float out[4])
-{
-    const int w0 = off >> 2;
-    const unsigned sh = (unsigned)(off & 3);
-    constexpr int NW = (KS + 1 + 3) / 4;
-    mav_f2 acc[4];
-    uint32_t lo[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) { acc[k] = (mav_f2)(0.f, 0.f); lo[k] = rd(k, w0); }
-#pragma unroll
-    for (int c = 0; c < NW; c++) {
-        uint32_t cur[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const uint32_t hi = rd(k, w0 + c + 1);
-            cur[k] = __builtin_amdgcn_alignbyte(hi, lo[k], sh);
-            lo[k] = hi;
-        }
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            if (4 * c + b > KS) break;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const float p = (float)((cur[k] >> (8 * b)) & 0xffu);
-                acc[k] = __builtin_elementwise_fma(tp.G[4 * c + b], (mav_f2)(p, p), acc[k]);
-            }
-        }
-    }
-    const float a0 = 1.f - f;
-#pragma unroll
-    for (int k = 0; k < 4; k++) out[k] = fmaf(acc[k].y, f, acc[k].x * a0);
-}
-template <int KS>
-static __device__ __forceinline__ float blur_v1_interior(const float* __restrict__ col, int s0, float f, const TapPairs<KS>& tp, const BlurParams& bp)
-{
-    constexpr int r = KS >> 1;
-    float px[KS + 1];
-#pragma unroll
-    for (int t = 0; t <= KS; t++) px[t] = col[(s0 - r + t) * 64];
-    if constexpr (KS >= 13) {
-        mav_f2 acc = (mav_f2)(0.f, 0.f);                                     // (b0, b1): row t feeds b0 with g[t] and b1 with g[t - 1]
-#pragma unroll
-        for (int t = 0; t <= KS; t++) acc = __builtin_elementwise_fma(tp.G[t], (mav_f2)(px[t], px[t]), acc);
-        return fmaf(acc.y, f, acc.x * (1.f - f));
-    } else {
-        float b0 = 0.f, b1 = 0.f;
-#pragma unroll
-        for (int t = 0; t < KS; t++) { const float g = bp.g[t]; b0 = fmaf(g, px[t], b0); b1 = fmaf(g, px[t + 1], b1); }
-        return fmaf(b1, f, b0 * (1.f - f));
-    }
-}
+// Taps: scalar for 5, register pairs for 13 -- the pair form pays for 13 taps (184 vs 194 us per launch for layer 2 of the 4K preset)
+// and costs for 5 (64 vs 53 us per launch for layer 1 at 1080p, where the compiler's own mix of scalar-tap FMAs is shorter).
+// 13 taps: u8 frames only (fused_fast_ok).
 template <typename T, int KS, int TH>
 static __device__ __forceinline__ void blur_fused_tile_fast(const T* __restrict__ base, float* __restrict__ out, int W, int H, int w, int h,
                                                             const BlurParams& bp, int rows_cap, int pitch_w, int tile_x, int tile_y,
@@ -739,8 +621,10 @@ static __device__ __forceinline__ void blur_fused_tile_fast(const T* __restrict_
 {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     constexpr int r = KS >> 1;
+    static_assert(KS == 5 || (KS == 13 && sizeof(T) == 1), "the fast tiles the dispatch selects");
     TapPairs<KS> tp;
-    if constexpr (KS >= 13) tp.load(bp);                                   // (the pair form: 13 taps only, see below)
+    if constexpr (KS >= 13) tp.load(bp);
+    const auto taps = [&] { if constexpr (KS >= 13) return tp.taps(); else return TapsScalar{bp.g}; }();
     const int dx = tile_x * 64 + lane, dxc = min(dx, w - 1);
     const int dy0 = tile_y * TH, dy1 = min(dy0 + TH, h) - 1;
     const int dyc = min(dy0 + (lane & (TH - 1)), h - 1);
@@ -797,16 +681,13 @@ static __device__ __forceinline__ void blur_fused_tile_fast(const T* __restrict_
     // ---- horizontal pass: staged bytes -> hrows (n_rows x 64 f32)
     for (int i = wv * 4; i < n_rows; i += 16) {
         float o[4];
-        const uint32_t* rw = sw + i * pitch_w;
-        // (the pair form pays for 13 taps -- 184 vs 194 us per launch for layer 2 of the 4K preset -- and costs for 5: 64 vs 53 us per
-        // launch for layer 1 at 1080p, where the compiler's own mix of scalar-tap FMAs is shorter)
         if constexpr (sizeof(T) > 1) {
             const T* re = (const T*)sw + i * pitch_w * 4 + off;
-            if constexpr (KS >= 13)
-                blur_h4_pairs_px<KS>([&](int k, int t) { return (float)re[k * pitch_w * 4 + t]; }, f, KS, [&](int t) { return tp.G[t]; }, o);
-            else blur_h4_stream_px<KS>([&](int k, int t) { return (float)re[k * pitch_w * 4 + t]; }, f, bp, o);
-        } else if constexpr (KS >= 13) blur_h4_pairs_t<KS>([&](int k, int wi) { return rw[k * pitch_w + wi]; }, off, f, tp, o);
-        else blur_h4_stream_t<KS>([&](int k, int wi) { return rw[k * pitch_w + wi]; }, off, f, bp, o);
+            blur_h4_run<KS>(px_elems([&](int k, int j) { return (float)re[k * pitch_w * 4 + j]; }), taps, KS, f, o);
+        } else {
+            const uint32_t* rw = sw + i * pitch_w;
+            blur_h4_run<KS>(px_staged_bytes([&](int k) { return rw + k * pitch_w; }, off), taps, KS, f, o);
+        }
 #pragma unroll
         for (int k = 0; k < 4; k++)
             if (i + k < n_rows) hrows[(i + k) * 64 + lane] = o[k];
@@ -821,39 +702,57 @@ static __device__ __forceinline__ void blur_fused_tile_fast(const T* __restrict_
         if (dy > dy1) break;
         const int t0 = __builtin_amdgcn_readlane(row_s, j * 4 + wv);
         const float tf = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(row_f), j * 4 + wv));
-        const float v = interior ? blur_v1_interior<KS>(col, t0, tf, tp, bp) : blur_v1([&](int y) { return col[y * 64]; }, H, t0, tf, bp);
+        const float v = interior ? blur_v1_run<KS>([&](int t) { return col[(t0 - r + t) * 64]; }, taps, KS, tf)
+                                 : blur_v1([&](int y) { return col[y * 64]; }, H, t0, tf, bp);
         if (dx < w) out[(size_t)dy * w + dx] = v;
     }
 }
-// does a fused layer take the fast tile?  (dword-addressable frames, staged form, tables, ksize 5 or 13)
-static __host__ __device__ __forceinline__ bool fused_fast_ok(const BlurParams& bp, int pitch_w, int dword_ok)
+// does a fused layer take the fast tile?  Quad-addressable frames, staged form, tables, and 5 taps (any depth) or 13 taps (u8 only:
+// blur_resize_is_fused refuses every 13-tap layer of wider pixels, whose staged 64 x 16 region is past 64 KB from 1 / scale = 5.6 on)
+static __host__ __device__ __forceinline__ bool fused_fast_ok(const BlurParams& bp, int pitch_w, int dword_ok, int esize)
 {
-    return dword_ok && pitch_w > 0 && bp.xs != nullptr && (bp.ksize == 5 || bp.ksize == 13);
+    return dword_ok && pitch_w > 0 && bp.xs != nullptr && (bp.ksize == 5 || (bp.ksize == 13 && esize == 1));
 }
 // Which tile code a fused launch carries.  One kernel per PATH: the paths differ a lot in registers (the generic tile and the 13-tap
 // pair form want ~80 VGPRs, the 5-tap fast tile 44), and a kernel that contained them all ran the 5-tap layers at the occupancy of
 // the hungriest (66 vs 53 us per launch for layer 1 at 1080p).
 enum { FP_GENERIC = 0, FP_FAST5 = 1, FP_FAST13 = 2, FP_ANY = 3 };
-static int fused_path_of(const BlurParams& bp, int pitch_w, int dword_ok)
+static int fused_path_of(const BlurParams& bp, int pitch_w, int dword_ok, int esize)
 {
-    return !fused_fast_ok(bp, pitch_w, dword_ok) ? FP_GENERIC : (bp.ksize == 5 ? FP_FAST5 : FP_FAST13);
+    return !fused_fast_ok(bp, pitch_w, dword_ok, esize) ? FP_GENERIC : (bp.ksize == 5 ? FP_FAST5 : FP_FAST13);
+}
+// go(integral_constant<int, PATH>) for a run-time path: the one place that turns a path into a kernel instantiation.  FP_FAST13
+// exists for u8 frames only (fused_path_of never names it for another depth); path < 0 (a launch without a fused job): any kernel.
+template <typename T, typename Go>
+static void with_fused_path(int path, Go go)
+{
+    switch (path) {
+    case FP_GENERIC: go(std::integral_constant<int, FP_GENERIC>()); break;
+    case FP_ANY: go(std::integral_constant<int, FP_ANY>()); break;
+    case FP_FAST13:
+        if constexpr (sizeof(T) == 1) go(std::integral_constant<int, FP_FAST13>());
+        break;
+    default: go(std::integral_constant<int, FP_FAST5>()); break;
+    }
 }
 template <typename T, int PATH>
 static __device__ __forceinline__ void blur_fused_any(const T* __restrict__ base, float* __restrict__ out, int W, int H, int w, int h,
                                                       const BlurParams& bp, int rows_cap, int pitch_w, int dword_ok, int th, int tile_x, int tile_y,
                                                       float* __restrict__ hrows)
 {
-    // th = tile height chosen by the host (fused_plan): 16, or 8 where 16 rows' source region does not fit LDS (fast tile only)
-    const bool fast = PATH == FP_FAST5 || PATH == FP_FAST13 || (PATH == FP_ANY && fused_fast_ok(bp, pitch_w, dword_ok));
+    // th = tile height chosen by the host (fused_plan): 16, or 8 where 16 rows' source region does not fit LDS (13 taps only)
+    static_assert(PATH != FP_FAST13 || sizeof(T) == 1, "the 13-tap fast tile is a u8 form");
+    const bool fast = PATH == FP_FAST5 || PATH == FP_FAST13 || (PATH == FP_ANY && fused_fast_ok(bp, pitch_w, dword_ok, (int)sizeof(T)));
     if ((PATH == FP_FAST5 || PATH == FP_ANY) && fast && bp.ksize == 5) {
-        if (th == 16) blur_fused_tile_fast<T, 5, 16>(base, out, W, H, w, h, bp, rows_cap, pitch_w, tile_x, tile_y, hrows);
-        else blur_fused_tile_fast<T, 5, 8>(base, out, W, H, w, h, bp, rows_cap, pitch_w, tile_x, tile_y, hrows);
+        blur_fused_tile_fast<T, 5, 16>(base, out, W, H, w, h, bp, rows_cap, pitch_w, tile_x, tile_y, hrows);
         return;
     }
-    if ((PATH == FP_FAST13 || PATH == FP_ANY) && fast && bp.ksize == 13) {
-        if (th == 16) blur_fused_tile_fast<T, 13, 16>(base, out, W, H, w, h, bp, rows_cap, pitch_w, tile_x, tile_y, hrows);
-        else blur_fused_tile_fast<T, 13, 8>(base, out, W, H, w, h, bp, rows_cap, pitch_w, tile_x, tile_y, hrows);
-        return;
+    if constexpr (sizeof(T) == 1 && (PATH == FP_FAST13 || PATH == FP_ANY)) {
+        if (fast && bp.ksize == 13) {
+            if (th == 16) blur_fused_tile_fast<T, 13, 16>(base, out, W, H, w, h, bp, rows_cap, pitch_w, tile_x, tile_y, hrows);
+            else blur_fused_tile_fast<T, 13, 8>(base, out, W, H, w, h, bp, rows_cap, pitch_w, tile_x, tile_y, hrows);
+            return;
+        }
     }
     if (PATH == FP_GENERIC || PATH == FP_ANY)
         blur_fused_tile(base, out, W, H, w, h, bp, rows_cap, pitch_w, dword_ok, tile_x, tile_y, hrows);
@@ -873,12 +772,12 @@ static int fused_blur_rows(int H, int h, int ksize, int th = FB_TH) { return (in
 // fast tile's horizontal pass works on whole groups of four rows)
 static size_t fused_lds_bytes(int rows, int pitch_w, int esize = 1) { return (size_t)rows * 256 + (size_t)(rows + 3) * 4 * pitch_w * esize; }
 // quads per staged source row: the columns 64 destination pixels need (63 scale + 1 + ksize), the 4-alignment slack and the quad
-// blur_h4_stream reads ahead
+// PxBytes reads ahead
 static int staged_pitch_words(int W, int w, int ksize) { return ((int)(63 * ((double)W / w)) + (ksize | 1) + 2 + 3) / 4 + 3; }
-// How a fused layer's tiles are cut: 64 x 16 with the source region staged in LDS when that fits 64 KB; else, for the fast tile
-// (fused_fast_ok), 64 x 8 staged (layer 2 of the 4K / 5-layer preset: 13 taps at scale 6.25 -- 110 source rows of 420 bytes for 16
-// destination rows); else 64 x 16 unstaged (every thread reads its bytes from global memory).  Wider pixels (esize 2 / 4) take the
-// fused form only where a staged 64 x 16 tile fits (blur_resize_is_fused), so for them the plan is always that one.
+// How a fused layer's tiles are cut: 64 x 16 with the source region staged in LDS when that fits 64 KB; else, for the 13-tap fast
+// tile, 64 x 8 staged (layer 2 of the 4K / 5-layer preset: 13 taps at scale 6.25 -- 110 source rows of 420 bytes for 16 destination
+// rows); else 64 x 16 unstaged (every thread reads its bytes from global memory).  Only u8 frames get past the first plan: a 5-tap
+// layer (1 / scale < 3.2) fits it, and wider pixels (esize 2 / 4) take the fused form only where it fits (blur_resize_is_fused).
 struct FusedPlan { int th, rows, pitch_w; size_t lds; };
 static FusedPlan fused_plan(int W, int H, int w, int h, const BlurParams& bp, int dword_ok, int esize = 1)
 {
@@ -886,7 +785,7 @@ static FusedPlan fused_plan(int W, int H, int w, int h, const BlurParams& bp, in
     FusedPlan p{FB_TH, fused_blur_rows(H, h, bp.ksize), pitch, 0};
     if (fused_lds_bytes(p.rows, pitch, esize) > 64 * 1024) {
         const int rows8 = fused_blur_rows(H, h, bp.ksize, 8);
-        if (fused_fast_ok(bp, pitch, dword_ok) && fused_lds_bytes(rows8, pitch, esize) <= 64 * 1024) { p.th = 8; p.rows = rows8; }
+        if (bp.ksize == 13 && fused_fast_ok(bp, pitch, dword_ok, esize) && fused_lds_bytes(rows8, pitch, esize) <= 64 * 1024) { p.th = 8; p.rows = rows8; }
         else p.pitch_w = 0;
     }
     p.lds = fused_lds_bytes(p.rows, p.pitch_w, esize);
@@ -1015,7 +914,7 @@ void launch_blur_multi(hipStream_t st, const T* img, const T* img2, int split, s
             auto path_of = [&](const BlurJob& J) {
                 if (J.w == W && J.h == H) return -1;
                 const FusedPlan fp = fused_plan(W, H, J.w, J.h, J.bp, dword_ok, esize);
-                return fused_path_of(J.bp, fp.pitch_w, dword_ok);
+                return fused_path_of(J.bp, fp.pitch_w, dword_ok, esize);
             };
             const int p = path_of(jobs.j[i]);
             BlurJobs sub{0, 0, {}};
@@ -1045,15 +944,12 @@ void launch_blur_multi(hipStream_t st, const T* img, const T* img2, int split, s
     int path = -1;                                                          // one tile code for all fused jobs, or FP_ANY
     for (int i = 0; i < jobs.n; i++)
         if (jobs.j[i].fused) {
-            const int p = fused_path_of(jobs.j[i].bp, jobs.j[i].pitch_w, dword_ok);
+            const int p = fused_path_of(jobs.j[i].bp, jobs.j[i].pitch_w, dword_ok, esize);
             path = path < 0 ? p : (path == p ? p : FP_ANY);
         }
-    switch (path) {
-    case FP_FAST13: hipLaunchKernelGGL((k_blur_multi<T, FP_FAST13>), dim3(blocks), dim3(256), lds, st, img, img2, split, img_stride, W, H, dword_ok, jobs); break;
-    case FP_GENERIC: hipLaunchKernelGGL((k_blur_multi<T, FP_GENERIC>), dim3(blocks), dim3(256), lds, st, img, img2, split, img_stride, W, H, dword_ok, jobs); break;
-    case FP_ANY: hipLaunchKernelGGL((k_blur_multi<T, FP_ANY>), dim3(blocks), dim3(256), lds, st, img, img2, split, img_stride, W, H, dword_ok, jobs); break;
-    default: hipLaunchKernelGGL((k_blur_multi<T, FP_FAST5>), dim3(blocks), dim3(256), lds, st, img, img2, split, img_stride, W, H, dword_ok, jobs); break;   // (also: no fused job)
-    }
+    with_fused_path<T>(path, [&](auto P) {
+        hipLaunchKernelGGL((k_blur_multi<T, decltype(P)::value>), dim3(blocks), dim3(256), lds, st, img, img2, split, img_stride, W, H, dword_ok, jobs);
+    });
 }
 
 // G images: the first `split` from run img, the rest from run img2 (both with stride img_stride); split >= G: one run.
@@ -1096,11 +992,11 @@ void launch_blur_resize(hipStream_t st, const T* img, const T* img2, int split, 
     if (!two_pass && blur_resize_is_fused(W, H, w, h, bp.ksize, esize)) {
         const FusedPlan fp = fused_plan(W, H, w, h, bp, dword_ok, esize);
         const dim3 grid((w + 63) / 64, (h + fp.th - 1) / fp.th, G);
-        switch (fused_path_of(bp, fp.pitch_w, dword_ok)) {
-        case FP_FAST5: hipLaunchKernelGGL((k_blur_resize_fused<T, FP_FAST5>), grid, dim3(256), fp.lds, st, img, img2, split, img_stride, W, H, w, h, bp, out, out_stride, fp.rows, fp.pitch_w, dword_ok, fp.th); break;
-        case FP_FAST13: hipLaunchKernelGGL((k_blur_resize_fused<T, FP_FAST13>), grid, dim3(256), fp.lds, st, img, img2, split, img_stride, W, H, w, h, bp, out, out_stride, fp.rows, fp.pitch_w, dword_ok, fp.th); break;
-        default: hipLaunchKernelGGL((k_blur_resize_fused<T, FP_GENERIC>), grid, dim3(256), fp.lds, st, img, img2, split, img_stride, W, H, w, h, bp, out, out_stride, fp.rows, fp.pitch_w, dword_ok, fp.th); break;
-        }
+        with_fused_path<T>(fused_path_of(bp, fp.pitch_w, dword_ok, esize), [&](auto P) {
+            if constexpr (decltype(P)::value != FP_ANY)                     // (one layer has one tile code)
+                hipLaunchKernelGGL((k_blur_resize_fused<T, decltype(P)::value>), grid, dim3(256), fp.lds, st, img, img2, split, img_stride, W, H, w, h, bp,
+                                   out, out_stride, fp.rows, fp.pitch_w, dword_ok, fp.th);
+        });
         return;
     }
     // the staged row block: rows_blk rows of pitch_w quads of esize-byte pixels

@@ -15,15 +15,15 @@ import pytest
 
 import stage_ref64 as ref
 from initial_flow_ref import smooth_initial_flow, top_layer_flow
-from stage_cases import (CASES, CASE_IDS, FORMS, REF64_MAX_PIXELS, UNTESTED, blur0_form, crafted_flow, images,
-                         initial_flow_form, polyexp_form, smooth_flow, sweep_form)
+from stage_cases import (BLUR_ATOL, BLUR_CASES, CASES, CASE_IDS, DEPTH_DTYPES, FORMS, REF64_MAX_PIXELS, UNTESTED, blur0_form,
+                         blur_case_forms, blur_coarse_name, crafted_flow, images, initial_flow_form, polyexp_form, smooth_flow,
+                         sweep_form)
 
 pytestmark = pytest.mark.gpu
 EPS = ref.EPS32
 TINY = 2.0 ** -126 * 16
 
 # ---- bounds: at most 4x the worst value measured over every case, layer and input of the matrix on an MI355X --------------------
-BLUR_ATOL = 1.6e-4          # layers k >= 1, |GPU - oracle|: measured 7.6e-5 (3840x2160); was 2e-4
 POLY_ATOL = 1.1e-4          # |GPU - oracle|: measured 2.8e-5 (1000x562, poly_n 5); was 2e-4
 POLY_REL = 0.62             # |GPU - oracle| / ((4 n + 4) 2^-24 magnitude), per pixel: measured 0.156 (1000x562)
 UPDATE_REL = 2.2            # |GPU - oracle| / (16 x 2^-24 magnitude), per pixel: measured 0.569 (1000x562)
@@ -251,6 +251,17 @@ def test_every_kernel_form_is_reached(mav):
             reached[s].add(f)
         names = {f for _, f in got}
         assert case.expects <= names, (case.name, sorted(case.expects - names))
+    for case in BLUR_CASES:                                       # the layer images' finer forms, at frames of their own
+        forms = blur_case_forms(case)
+        with _lib.Context(case.W, case.H, 1, case.fb()) as ctx:
+            for depth in case.depths:
+                info = ctx.schedule_info(1, DEPTH_DTYPES[depth])["layers"]
+                for f, k, forced in forms:
+                    if k and not forced and f.startswith(depth + ":"):
+                        assert info[k]["blur"] == blur_coarse_name(f.split(":")[1]), (case.name, k, f, info[k])
+        names = {f for f, _, _ in forms}
+        assert case.expects <= names, (case.name, sorted(case.expects - names))
+        reached["blur_form"] |= names
     for s, forms in FORMS.items():
         assert forms <= reached[s], (s, sorted(forms - reached[s]))
         assert not (UNTESTED.get(s, set()) & reached[s])
