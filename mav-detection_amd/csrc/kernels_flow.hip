@@ -882,48 +882,30 @@ __global__ __launch_bounds__(256) void k_blur_multi(const T* __restrict__ img, c
 // rows are quad-addressable (aligned dword / dwordx2 / dwordx4 loads) when W, the image stride (pixels) and both bases are multiples of
 // four pixels
 template <typename T>
-static int quad_ok(const T* img, const T* img2, size_t img_stride, int W)
+static int quad_ok(const FrameRun<T>& f)
 {
     const uintptr_t m = 4 * sizeof(T) - 1;
-    return (W % 4 == 0 && img_stride % 4 == 0 && ((uintptr_t)img & m) == 0 && ((uintptr_t)img2 & m) == 0) ? 1 : 0;
+    return (f.W % 4 == 0 && f.img_stride % 4 == 0 && ((uintptr_t)f.img & m) == 0 && ((uintptr_t)f.img2 & m) == 0) ? 1 : 0;
 }
-// Layer images of several layers of G frames in ONE launch.  jobs[i]: layer size, BlurParams, out / out_stride filled by the caller; a
-// layer qualifies when blur_multi_ok says so (3x3 form or fused form).  Grid bookkeeping and the LDS size are filled here.
+// does the layer take the 3x3 form (blur3_block)?  f: two runs spelled out (FrameRun::runs)
 template <typename T>
-static bool blur3_fast_ok(const T* img, const T* img2, size_t img_stride, int W, int H, int w, int h, const BlurParams& bp,
-                          const float* out, size_t out_stride);
-template <typename T>
-bool blur_multi_ok(const T* img, const T* img2, size_t img_stride, int W, int H, int w, int h, BlurParams bp, const float* out,
-                   size_t out_stride)
+static bool blur3_fast_ok(const FrameRun<T>& f, const LayerTarget& t)
 {
-    return blur3_fast_ok(img, img2 ? img2 : img, img_stride, W, H, w, h, bp, out, out_stride) ||
-           blur_resize_is_fused(W, H, w, h, bp.ksize, (int)sizeof(T));
+    return t.w == f.W && t.h == f.H && t.bp.fixed3 && f.W >= 8 && f.H >= 2 && quad_ok(f) && t.out_stride % 4 == 0 &&
+           ((uintptr_t)t.out & 15) == 0;
 }
+// Layer images of several layers of G frames in ONE launch.  jobs[i]: the LayerTarget filled by the caller; a layer qualifies when
+// blur_multi_ok says so (3x3 form or fused form).  Grid bookkeeping and the LDS size are filled here.
 template <typename T>
-void launch_blur_multi(hipStream_t st, const T* img, const T* img2, int split, size_t img_stride, int G, int W, int H, BlurJobs jobs,
-                       bool split_by_path)
+bool blur_multi_ok(const FrameRun<T>& f, const LayerTarget& t)
 {
-    if (!img2) { img2 = img; split = G; }
-    const int dword_ok = quad_ok(img, img2, img_stride, W);
-    const int esize = (int)sizeof(T);
-    if (split_by_path) {      // many frames per layer (the deep layers of a whole call): one launch per tile code -- a launch that mixes
-                              // them runs every layer at the occupancy of the hungriest path -- instead of one launch in all
-        bool done[MAV_MAX_JOBS] = {false};
-        for (int i = 0; i < jobs.n; i++) {
-            if (done[i]) continue;
-            auto path_of = [&](const BlurJob& J) {
-                if (J.w == W && J.h == H) return -1;
-                const FusedPlan fp = fused_plan(W, H, J.w, J.h, J.bp, dword_ok, esize);
-                return fused_path_of(J.bp, fp.pitch_w, dword_ok, esize);
-            };
-            const int p = path_of(jobs.j[i]);
-            BlurJobs sub{0, 0, {}};
-            for (int k = i; k < jobs.n; k++)
-                if (!done[k] && path_of(jobs.j[k]) == p) { sub.j[sub.n++] = jobs.j[k]; done[k] = true; }
-            launch_blur_multi(st, img, img2, split, img_stride, G, W, H, sub, false);
-        }
-        return;
-    }
+    return blur3_fast_ok(f.runs(), t) || blur_resize_is_fused(f.W, f.H, t.w, t.h, t.bp.ksize, (int)sizeof(T));
+}
+// one launch for all jobs; f: two runs spelled out
+template <typename T>
+static void blur_multi_launch(hipStream_t st, const FrameRun<T>& f, int dword_ok, BlurJobs jobs)
+{
+    const int esize = (int)sizeof(T), W = f.W, H = f.H;
     int blocks = 0;
     size_t lds = 0;
     for (int i = 0; i < jobs.n; i++) {
@@ -939,7 +921,7 @@ void launch_blur_multi(hipStream_t st, const T* img, const T* img2, int split, s
             J.gx = (W / 4 + 63) / 64; J.gy = ((H + 3) / 4 + 3) / 4;
         }
         J.first_block = blocks;
-        blocks += J.gx * J.gy * G;
+        blocks += J.gx * J.gy * f.G;
     }
     int path = -1;                                                          // one tile code for all fused jobs, or FP_ANY
     for (int i = 0; i < jobs.n; i++)
@@ -948,12 +930,36 @@ void launch_blur_multi(hipStream_t st, const T* img, const T* img2, int split, s
             path = path < 0 ? p : (path == p ? p : FP_ANY);
         }
     with_fused_path<T>(path, [&](auto P) {
-        hipLaunchKernelGGL((k_blur_multi<T, decltype(P)::value>), dim3(blocks), dim3(256), lds, st, img, img2, split, img_stride, W, H, dword_ok, jobs);
+        hipLaunchKernelGGL((k_blur_multi<T, decltype(P)::value>), dim3(blocks), dim3(256), lds, st, f.img, f.img2, f.split, f.img_stride, W, H,
+                           dword_ok, jobs);
     });
+}
+template <typename T>
+void launch_blur_multi(hipStream_t st, const FrameRun<T>& frames, BlurJobs jobs)
+{
+    const FrameRun<T> f = frames.runs();
+    const int dword_ok = quad_ok(f);
+    const int esize = (int)sizeof(T);
+    if (f.G <= 8) return blur_multi_launch(st, f, dword_ok, jobs);
+    // many frames per layer (the deep layers of a whole call): one launch per tile code -- a launch that mixes them runs every layer at
+    // the occupancy of the hungriest path -- instead of one launch in all
+    bool done[MAV_MAX_JOBS] = {false};
+    for (int i = 0; i < jobs.n; i++) {
+        if (done[i]) continue;
+        auto path_of = [&](const BlurJob& J) {
+            if (J.w == f.W && J.h == f.H) return -1;
+            const FusedPlan fp = fused_plan(f.W, f.H, J.w, J.h, J.bp, dword_ok, esize);
+            return fused_path_of(J.bp, fp.pitch_w, dword_ok, esize);
+        };
+        const int p = path_of(jobs.j[i]);
+        BlurJobs sub{0, 0, {}};
+        for (int k = i; k < jobs.n; k++)
+            if (!done[k] && path_of(jobs.j[k]) == p) { sub.j[sub.n++] = jobs.j[k]; done[k] = true; }
+        blur_multi_launch(st, f, dword_ok, sub);
+    }
 }
 
 // G images: the first `split` from run img, the rest from run img2 (both with stride img_stride); split >= G: one run.
-// two_pass: force the separable two-pass form through the tmp scratch (the stage hook compares the two forms).
 template <typename T>
 __global__ __launch_bounds__(256) void k_blur3(const T* __restrict__ img, const T* __restrict__ img2, int split,
                                                size_t img_stride, int W, int H, float* __restrict__ out, size_t out_stride)
@@ -961,41 +967,33 @@ __global__ __launch_bounds__(256) void k_blur3(const T* __restrict__ img, const 
     blur3_block(image_of(img, img2, split, img_stride, blockIdx.z), out + (size_t)blockIdx.z * out_stride, W, H, blockIdx.x, blockIdx.y);
 }
 
+// true when launch_blur_resize (scratch.two_pass = false) will go through the tmp scratch for these operands
 template <typename T>
-static bool blur3_fast_ok(const T* img, const T* img2, size_t img_stride, int W, int H, int w, int h, const BlurParams& bp,
-                          const float* out, size_t out_stride)
+bool blur_resize_needs_tmp(const FrameRun<T>& f, const LayerTarget& t)
 {
-    return w == W && h == H && bp.fixed3 && W >= 8 && H >= 2 && quad_ok(img, img2, img_stride, W) && out_stride % 4 == 0 &&
-           ((uintptr_t)out & 15) == 0;
-}
-// true when launch_blur_resize (two_pass = false) will go through the tmp scratch for these operands
-template <typename T>
-bool blur_resize_needs_tmp(const T* img, const T* img2, size_t img_stride, int W, int H, int w, int h, BlurParams bp,
-                           const float* out, size_t out_stride)
-{
-    return !blur3_fast_ok(img, img2 ? img2 : img, img_stride, W, H, w, h, bp, out, out_stride) &&
-           !blur_resize_is_fused(W, H, w, h, bp.ksize, (int)sizeof(T));
+    return !blur3_fast_ok(f.runs(), t) && !blur_resize_is_fused(f.W, f.H, t.w, t.h, t.bp.ksize, (int)sizeof(T));
 }
 template <typename T>
-void launch_blur_resize(hipStream_t st, const T* img, const T* img2, int split, size_t img_stride, int G, int W, int H, int w,
-                        int h, BlurParams bp, float* tmp, size_t tmp_stride, float* out, size_t out_stride, bool two_pass)
+void launch_blur_resize(hipStream_t st, const FrameRun<T>& frames, const LayerTarget& t, const BlurScratch& scratch)
 {
-    if (!img2) { img2 = img; split = G; }
-    if (blur3_fast_ok(img, img2, img_stride, W, H, w, h, bp, out, out_stride)) {
+    const FrameRun<T> f = frames.runs();
+    const int G = f.G, W = f.W, H = f.H, w = t.w, h = t.h;
+    const BlurParams& bp = t.bp;
+    if (blur3_fast_ok(f, t)) {
         dim3 grid((W / 4 + 63) / 64, ((H + 3) / 4 + 3) / 4, G);
-        hipLaunchKernelGGL(k_blur3<T>, grid, dim3(256), 0, st, img, img2, split, img_stride, W, H, out, out_stride);
+        hipLaunchKernelGGL(k_blur3<T>, grid, dim3(256), 0, st, f.img, f.img2, f.split, f.img_stride, W, H, t.out, t.out_stride);
         return;
     }
-    const int dword_ok = quad_ok(img, img2, img_stride, W);     // else the staging goes pixel by pixel
+    const int dword_ok = quad_ok(f);     // else the staging goes pixel by pixel
     const int esize = (int)sizeof(T);
     const int pitch_w = staged_pitch_words(W, w, bp.ksize);
-    if (!two_pass && blur_resize_is_fused(W, H, w, h, bp.ksize, esize)) {
+    if (!scratch.two_pass && blur_resize_is_fused(W, H, w, h, bp.ksize, esize)) {
         const FusedPlan fp = fused_plan(W, H, w, h, bp, dword_ok, esize);
         const dim3 grid((w + 63) / 64, (h + fp.th - 1) / fp.th, G);
         with_fused_path<T>(fused_path_of(bp, fp.pitch_w, dword_ok, esize), [&](auto P) {
             if constexpr (decltype(P)::value != FP_ANY)                     // (one layer has one tile code)
-                hipLaunchKernelGGL((k_blur_resize_fused<T, decltype(P)::value>), grid, dim3(256), fp.lds, st, img, img2, split, img_stride, W, H, w, h, bp,
-                                   out, out_stride, fp.rows, fp.pitch_w, dword_ok, fp.th);
+                hipLaunchKernelGGL((k_blur_resize_fused<T, decltype(P)::value>), grid, dim3(256), fp.lds, st, f.img, f.img2, f.split, f.img_stride,
+                                   W, H, w, h, bp, t.out, t.out_stride, fp.rows, fp.pitch_w, dword_ok, fp.th);
         });
         return;
     }
@@ -1007,22 +1005,21 @@ void launch_blur_resize(hipStream_t st, const T* img, const T* img2, int split, 
         const int gx = (w + 63) / 64, nby = (H + rows_blk - 1) / rows_blk;
         const int gy = nby;                                               // one row block per workgroup (walking several measured slower: 69 vs 47 us)
         const size_t lds_h = (size_t)((rows_blk * pitch_w * esize + 1) & ~1) * 4 + (size_t)((bp.ksize + 4) & ~3) * 8;    // staged rows + tap pairs
-        hipLaunchKernelGGL(k_blur_resize_h<T>, dim3(gx, gy, G), dim3(256), lds_h, st, img,
-                           img2, split, img_stride, W, H, w, bp, tmp, tmp_stride, rows_blk, pitch_w, dword_ok);
+        hipLaunchKernelGGL(k_blur_resize_h<T>, dim3(gx, gy, G), dim3(256), lds_h, st, f.img, f.img2, f.split, f.img_stride, W, H, w, bp,
+                           scratch.tmp, scratch.stride, rows_blk, pitch_w, dword_ok);
     }
     else
-        hipLaunchKernelGGL(k_blur_resize_h_direct<T>, dim3((w + 63) / 64, ((H + 3) / 4 + 3) / 4, G), dim3(256), 0, st, img, img2, split, img_stride,
-                           W, H, w, bp, tmp, tmp_stride);
-    hipLaunchKernelGGL(k_blur_resize_v, dim3((w + 63) / 64, (h + 3) / 4, G), dim3(256), 0, st, (const float*)tmp, tmp_stride, H, w, h,
-                       bp, out, out_stride);
+        hipLaunchKernelGGL(k_blur_resize_h_direct<T>, dim3((w + 63) / 64, ((H + 3) / 4 + 3) / 4, G), dim3(256), 0, st, f.img, f.img2, f.split,
+                           f.img_stride, W, H, w, bp, scratch.tmp, scratch.stride);
+    hipLaunchKernelGGL(k_blur_resize_v, dim3((w + 63) / 64, (h + 3) / 4, G), dim3(256), 0, st, (const float*)scratch.tmp, scratch.stride, H, w,
+                       h, bp, t.out, t.out_stride);
 }
 // the three source depths (mavflow_internal.h)
-#define MAV_BLUR_DEPTH(T)                                                                                                                    \
-    template bool blur_multi_ok<T>(const T*, const T*, size_t, int, int, int, int, BlurParams, const float*, size_t);                        \
-    template void launch_blur_multi<T>(hipStream_t, const T*, const T*, int, size_t, int, int, int, BlurJobs, bool);                          \
-    template bool blur_resize_needs_tmp<T>(const T*, const T*, size_t, int, int, int, int, BlurParams, const float*, size_t);                \
-    template void launch_blur_resize<T>(hipStream_t, const T*, const T*, int, size_t, int, int, int, int, int, BlurParams, float*, size_t,   \
-                                        float*, size_t, bool);
+#define MAV_BLUR_DEPTH(T)                                                                                     \
+    template bool blur_multi_ok<T>(const FrameRun<T>&, const LayerTarget&);                                   \
+    template void launch_blur_multi<T>(hipStream_t, const FrameRun<T>&, BlurJobs);                            \
+    template bool blur_resize_needs_tmp<T>(const FrameRun<T>&, const LayerTarget&);                           \
+    template void launch_blur_resize<T>(hipStream_t, const FrameRun<T>&, const LayerTarget&, const BlurScratch&);
 MAV_BLUR_DEPTH(uint8_t)
 MAV_BLUR_DEPTH(uint16_t)
 MAV_BLUR_DEPTH(float)
@@ -1182,28 +1179,64 @@ void launch_polyexp(hipStream_t st, const float* I, size_t I_stride, int G, int 
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// FarnebackUpdateMatrices for one pixel (A.5), register form: q[] = the 5 R0 values at (x, y), out[] = the 5 M values.
-static __device__ __forceinline__ void update_core(const float q[5], const float* __restrict__ R1p, size_t npx, int w, int h,
-                                                   int x, int y, float dx, float dy, float out[5])
+// FarnebackUpdateMatrices for one pixel (A.5): a GATHER of the 2x2 neighbourhood of the 5 R1 planes around (x + dx, y + dy), then ONE
+// body, update_finish, that turns (q[] = the 5 R0 values at (x, y), the taps, the flow) into the 5 M values.  Every kernel that builds
+// M calls that body; they differ only in how the taps arrive.
+struct GatherPx {
+    float p00[5], p01[5], p10[5], p11[5];
+    float fx, fy;
+    bool inside;
+};
+// the sweep's fast form: the loads are issued unconditionally, so that two pixels' gathers are in flight together; a neighbourhood that
+// is not inside the image reads the one at (0, 0) instead and discards it (on a layer of one row that read passes the plane's end)
+static __device__ __forceinline__ void gather_issue(const float* __restrict__ R1p, size_t npx, int w, int h, int x, int y, float dx,
+                                                    float dy, GatherPx& g)
+{
+    float fx = x + dx, fy = y + dy;
+    const int x1 = (int)floorf(fx), y1 = (int)floorf(fy);
+    g.fx = fx - x1; g.fy = fy - y1;
+    g.inside = (unsigned)x1 < (unsigned)(w - 1) && (unsigned)y1 < (unsigned)(h - 1);
+    const int xc = g.inside ? x1 : 0, yc = g.inside ? y1 : 0;
+    const float* p = R1p + (size_t)yc * w + xc;
+#pragma unroll
+    for (int c = 0; c < 5; c++) {
+        g.p00[c] = p[0]; g.p01[c] = p[1]; g.p10[c] = p[w]; g.p11[c] = p[w + 1];
+        p += npx;
+    }
+}
+// the memory form's gather: the taps are read only when the neighbourhood is inside the image
+static __device__ __forceinline__ void gather_inside(const float* __restrict__ R1p, size_t npx, int w, int h, int x, int y, float dx,
+                                                     float dy, GatherPx& g)
+{
+    float fx = x + dx, fy = y + dy;
+    const int x1 = (int)floorf(fx), y1 = (int)floorf(fy);
+    g.fx = fx - x1; g.fy = fy - y1;
+    g.inside = (unsigned)x1 < (unsigned)(w - 1) && (unsigned)y1 < (unsigned)(h - 1);
+    if (!g.inside) return;
+    const float* p = R1p + (size_t)y1 * w + x1;
+#pragma unroll
+    for (int c = 0; c < 5; c++) {
+        g.p00[c] = p[0]; g.p01[c] = p[1]; g.p10[c] = p[w]; g.p11[c] = p[w + 1];
+        p += npx;
+    }
+}
+static __device__ __forceinline__ void update_finish(const float q[5], const GatherPx& g, int w, int h, int x, int y, float dx,
+                                                     float dy, float out[5])
 {
     // Every multiply-add below is spelled out (fmaf) and contraction is off for the rest: the bits must not depend on which kernel
     // (or which template instantiation of one) the function is inlined into -- under -ffp-contract=fast (this file's setting until round 3) two
     // instantiations of the sweep kernel that differed in a store instruction fused `a*b + c*d` differently and their flows drifted
-    // apart by up to 8e-4 px over twenty sweeps.  update_finish() below is the same arithmetic on values already gathered.
+    // apart by up to 8e-4 px over twenty sweeps.
 #pragma clang fp contract(off)
-    float fx = x + dx, fy = y + dy;
-    const int x1 = (int)floorf(fx), y1 = (int)floorf(fy);
-    fx -= x1; fy -= y1;
     float r2, r3, r4, r5, r6;
-    if ((unsigned)x1 < (unsigned)(w - 1) && (unsigned)y1 < (unsigned)(h - 1)) {
-        const float gx = 1.f - fx, gy = 1.f - fy;
-        const float a00 = gx * gy, a01 = fx * gy, a10 = gx * fy, a11 = fx * fy;
-        const float* p = R1p + (size_t)y1 * w + x1;
-        r2 = fmaf(a11, p[w + 1], fmaf(a10, p[w], fmaf(a01, p[1], a00 * p[0]))); p += npx;
-        r3 = fmaf(a11, p[w + 1], fmaf(a10, p[w], fmaf(a01, p[1], a00 * p[0]))); p += npx;
-        r4 = fmaf(a11, p[w + 1], fmaf(a10, p[w], fmaf(a01, p[1], a00 * p[0]))); p += npx;
-        r5 = fmaf(a11, p[w + 1], fmaf(a10, p[w], fmaf(a01, p[1], a00 * p[0]))); p += npx;
-        r6 = fmaf(a11, p[w + 1], fmaf(a10, p[w], fmaf(a01, p[1], a00 * p[0])));
+    if (g.inside) {
+        const float gx = 1.f - g.fx, gy = 1.f - g.fy;
+        const float a00 = gx * gy, a01 = g.fx * gy, a10 = gx * g.fy, a11 = g.fx * g.fy;
+        r2 = fmaf(a11, g.p11[0], fmaf(a10, g.p10[0], fmaf(a01, g.p01[0], a00 * g.p00[0])));
+        r3 = fmaf(a11, g.p11[1], fmaf(a10, g.p10[1], fmaf(a01, g.p01[1], a00 * g.p00[1])));
+        r4 = fmaf(a11, g.p11[2], fmaf(a10, g.p10[2], fmaf(a01, g.p01[2], a00 * g.p00[2])));
+        r5 = fmaf(a11, g.p11[3], fmaf(a10, g.p10[3], fmaf(a01, g.p01[3], a00 * g.p00[3])));
+        r6 = fmaf(a11, g.p11[4], fmaf(a10, g.p10[4], fmaf(a01, g.p01[4], a00 * g.p00[4])));
         r4 = (q[2] + r4) * 0.5f;
         r5 = (q[3] + r5) * 0.5f;
         r6 = (q[4] + r6) * 0.25f;
@@ -1238,7 +1271,9 @@ static __device__ __forceinline__ void update_px(const float* __restrict__ R0p, 
     float q[5], o[5];
 #pragma unroll
     for (int c = 0; c < 5; c++) q[c] = R0p[c * npx + idx];
-    update_core(q, R1p, npx, w, h, x, y, dx, dy, o);
+    GatherPx g;
+    gather_inside(R1p, npx, w, h, x, y, dx, dy, g);
+    update_finish(q, g, w, h, x, y, dx, dy, o);
 #pragma unroll
     for (int c = 0; c < 5; c++) Mp[c * npx + idx] = o[c];
 }
@@ -1309,30 +1344,13 @@ __global__ __launch_bounds__(256) void k_update_matrices(const float* __restrict
               M + (size_t)s * M_stride);
 }
 
-void launch_update_matrices(hipStream_t st, const float* R0, const float* R1, size_t R_stride, const float* flow_prev,
-                            size_t fp_stride, int pw, int ph, float mul, int G, int w, int h, float* M, size_t M_stride, int y_begin, int y_end)
+void launch_initial_m(hipStream_t st, const InitialMArgs& a, const FlowSource& src)
 {
-    if (y_begin < 0) y_begin = 0;
-    if (y_end < 0 || y_end > h) y_end = h;
+    const int y_begin = a.y_begin < 0 ? 0 : a.y_begin, y_end = (a.y_end < 0 || a.y_end > a.h) ? a.h : a.y_end;
     if (y_end <= y_begin) return;
-    dim3 grid((w + 63) / 64, (y_end - y_begin + 3) / 4, G);
-    if (flow_prev)
-        hipLaunchKernelGGL(k_update_matrices<1>, grid, dim3(256), 0, st, R0, R1, R_stride, flow_prev, fp_stride, pw, ph, mul,
-                           (double)pw / w, (double)ph / h, w, h, M, M_stride, y_begin, y_end);
-    else
-        hipLaunchKernelGGL(k_update_matrices<0>, grid, dim3(256), 0, st, R0, R1, R_stride, (const float*)nullptr, (size_t)0,
-                           0, 0, 0.f, 0.0, 0.0, w, h, M, M_stride, y_begin, y_end);
-}
-
-void launch_update_matrices_flow(hipStream_t st, const float* R0, const float* R1, size_t R_stride, const float* flow,
-                                 size_t f_stride, int G, int w, int h, float* M, size_t M_stride, int y_begin, int y_end)
-{
-    if (y_begin < 0) y_begin = 0;
-    if (y_end < 0 || y_end > h) y_end = h;
-    if (y_end <= y_begin) return;
-    dim3 grid((w + 63) / 64, (y_end - y_begin + 3) / 4, G);
-    hipLaunchKernelGGL(k_update_matrices<2>, grid, dim3(256), 0, st, R0, R1, R_stride, flow, f_stride, 0, 0, 0.f, 0.0, 0.0,
-                       w, h, M, M_stride, y_begin, y_end);
+    const auto k = src.kind == FlowSource::COARSER ? k_update_matrices<1> : src.kind == FlowSource::FIELD ? k_update_matrices<2> : k_update_matrices<0>;
+    hipLaunchKernelGGL(k, dim3((a.w + 63) / 64, (y_end - y_begin + 3) / 4, a.G), dim3(256), 0, st, a.R0, a.R1, a.R_stride, src.flow, src.stride,
+                       src.pw, src.ph, src.mul, (double)src.pw / a.w, (double)src.ph / a.h, a.w, a.h, a.M, a.M_stride, y_begin, y_end);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1530,65 +1548,6 @@ __global__ __launch_bounds__(256) void k_blur_iter_generic(const float* __restri
 #define FT_X 64
 #define FT_Y 16
 
-struct GatherPx {
-    float p00[5], p01[5], p10[5], p11[5];
-    float fx, fy;
-    bool inside;
-};
-// request the 2x2 neighbourhood of the 5 R1 planes around (x + dx, y + dy); out-of-image taps read a clamped address
-static __device__ __forceinline__ void gather_issue(const float* __restrict__ R1p, size_t npx, int w, int h, int x, int y, float dx,
-                                                    float dy, GatherPx& g)
-{
-    float fx = x + dx, fy = y + dy;
-    const int x1 = (int)floorf(fx), y1 = (int)floorf(fy);
-    g.fx = fx - x1; g.fy = fy - y1;
-    g.inside = (unsigned)x1 < (unsigned)(w - 1) && (unsigned)y1 < (unsigned)(h - 1);
-    const int xc = g.inside ? x1 : 0, yc = g.inside ? y1 : 0;
-    const float* p = R1p + (size_t)yc * w + xc;
-#pragma unroll
-    for (int c = 0; c < 5; c++) {
-        g.p00[c] = p[0]; g.p01[c] = p[1]; g.p10[c] = p[w]; g.p11[c] = p[w + 1];
-        p += npx;
-    }
-}
-static __device__ __forceinline__ void update_finish(const float q[5], const GatherPx& g, int w, int h, int x, int y, float dx,
-                                                     float dy, float out[5])
-{
-#pragma clang fp contract(off)                       // explicit fmaf only: see update_core()
-    float r2, r3, r4, r5, r6;
-    if (g.inside) {
-        const float gx = 1.f - g.fx, gy = 1.f - g.fy;
-        const float a00 = gx * gy, a01 = g.fx * gy, a10 = gx * g.fy, a11 = g.fx * g.fy;
-        r2 = fmaf(a11, g.p11[0], fmaf(a10, g.p10[0], fmaf(a01, g.p01[0], a00 * g.p00[0])));
-        r3 = fmaf(a11, g.p11[1], fmaf(a10, g.p10[1], fmaf(a01, g.p01[1], a00 * g.p00[1])));
-        r4 = fmaf(a11, g.p11[2], fmaf(a10, g.p10[2], fmaf(a01, g.p01[2], a00 * g.p00[2])));
-        r5 = fmaf(a11, g.p11[3], fmaf(a10, g.p10[3], fmaf(a01, g.p01[3], a00 * g.p00[3])));
-        r6 = fmaf(a11, g.p11[4], fmaf(a10, g.p10[4], fmaf(a01, g.p01[4], a00 * g.p00[4])));
-        r4 = (q[2] + r4) * 0.5f;
-        r5 = (q[3] + r5) * 0.5f;
-        r6 = (q[4] + r6) * 0.25f;
-    } else {
-        r2 = r3 = 0.f;
-        r4 = q[2]; r5 = q[3]; r6 = q[4] * 0.5f;
-    }
-    r2 = (q[0] - r2) * 0.5f;
-    r3 = (q[1] - r3) * 0.5f;
-    r2 += fmaf(r4, dy, r6 * dx);
-    r3 += fmaf(r6, dy, r5 * dx);
-    const int BORDER = 5;
-    if ((unsigned)(x - BORDER) >= (unsigned)(w - BORDER * 2) || (unsigned)(y - BORDER) >= (unsigned)(h - BORDER * 2)) {
-        auto bw = [](int d) { return d < 2 ? 0.14f : 0.4472f; };
-        const float scale = (x < BORDER ? bw(x) : 1.f) * (x >= w - BORDER ? bw(w - x - 1) : 1.f) *
-                            (y < BORDER ? bw(y) : 1.f) * (y >= h - BORDER ? bw(h - y - 1) : 1.f);
-        r2 *= scale; r3 *= scale; r4 *= scale; r5 *= scale; r6 *= scale;
-    }
-    out[0] = fmaf(r4, r4, r6 * r6);
-    out[1] = (r4 + r5) * r6;
-    out[2] = fmaf(r5, r5, r6 * r6);
-    out[3] = fmaf(r4, r2, r6 * r3);
-    out[4] = fmaf(r6, r2, r5 * r3);
-}
-
 struct __attribute__((packed, aligned(4))) F2U { float x, y; };     // two adjacent floats at 4-byte alignment
 // AL = true: width a multiple of 4 and 16-byte aligned planes (vector loads / stores as written); AL = false: any width -- the
 // column pairs are read as two floats at 4-byte alignment and the flow is stored pixel by pixel.
@@ -1751,69 +1710,51 @@ __global__ __launch_bounds__(256) void k_blur_iter_fast(const float* __restrict_
 
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 int blur_iter_tile_rows(int h) { return (h + FT_Y - 1) / FT_Y; }
-static bool blur_iter_vec_ok(int w, size_t M_stride, size_t R_stride, size_t f_stride, const void* M_in, const void* M_out, const void* R0,
-                             const void* R1, const void* flow)
+static bool blur_iter_vec_ok(const SweepArgs& a)
 {
-    return (w % 4 == 0) && (M_stride % 4 == 0) && (R_stride % 4 == 0) && (f_stride % 4 == 0) && aligned16(M_in) && aligned16(M_out) &&
-           aligned16(R0) && aligned16(R1) && aligned16(flow);
+    return (a.w % 4 == 0) && (a.M_stride % 4 == 0) && (a.R_stride % 4 == 0) && (a.f_stride % 4 == 0) && aligned16(a.M_in) && aligned16(a.M_out) &&
+           aligned16(a.R0) && aligned16(a.R1) && aligned16(a.flow);
 }
-bool blur_iter_bands_ok(int w, int winsize, size_t M_stride, size_t R_stride, size_t f_stride, const void* M_in, const void* M_out,
-                        const void* R0, const void* R1, const void* flow)
-{
-    return winsize / 2 == 6 && blur_iter_vec_ok(w, M_stride, R_stride, f_stride, M_in, M_out, R0, R1, flow);
-}
+bool blur_iter_bands_ok(const SweepArgs& a) { return a.winsize / 2 == 6 && blur_iter_vec_ok(a); }
 
-// the fast form's launch; wt: M' through write-through stores
+// the fast form's launch
 template <typename Win, bool AL>
-static void launch_sweep_fast(hipStream_t st, const TileMap& tm, bool wt, const float* M_in, float* M_out, size_t M_stride, const float* R0,
-                              const float* R1, size_t R_stride, int w, int h, const Win& win, int do_update, int store_flow, float* flow,
-                              size_t f_stride)
+static void launch_sweep_fast(hipStream_t st, const TileMap& tm, const SweepArgs& a, const Win& win)
 {
+    const bool wt = a.write_through && a.do_update;      // M' through write-through stores
     const auto k = wt ? k_blur_iter_fast<Win, 6, AL, true> : k_blur_iter_fast<Win, 6, AL, false>;
-    hipLaunchKernelGGL(k, dim3(tile_grid(tm)), dim3(256), 0, st, M_in, M_out, M_stride, R0, R1, R_stride, w, h, tm, win, do_update,
-                       store_flow, flow, f_stride);
+    hipLaunchKernelGGL(k, dim3(tile_grid(tm)), dim3(256), 0, st, a.M_in, a.M_out, a.M_stride, a.R0, a.R1, a.R_stride, a.w, a.h, tm, win,
+                       a.do_update, a.store_flow, a.flow, a.f_stride);
 }
 
 // One sweep launch of either window, three tiers: the fast form as written (AL), its relaxed form for any width / alignment, the
 // generic form.
 template <typename Win>
-static void launch_sweep(hipStream_t st, const float* M_in, float* M_out, size_t M_stride, const float* R0, const float* R1,
-                         size_t R_stride, int G, int w, int h, int winsize, int do_update, int store_flow, float* flow, size_t f_stride,
-                         int ty0, int ty1, int strip, bool write_through, const Win& win)
+static void launch_sweep(hipStream_t st, const SweepArgs& a, const Win& win)
 {
-    const int m = winsize / 2;
-    const bool wt = write_through && do_update;
-    if (m == 6 && blur_iter_vec_ok(w, M_stride, R_stride, f_stride, M_in, M_out, R0, R1, flow)) {
-        const TileMap tm = make_tile_map(w, h, G, FT_X, FT_Y, ty0, ty1, strip);
+    const int m = a.winsize / 2;
+    if (m == 6 && blur_iter_vec_ok(a)) {
+        const TileMap tm = make_tile_map(a.w, a.h, a.G, FT_X, FT_Y, a.ty0, a.ty1, a.strip);
         if (tm.n_tiles == 0) return;
-        return launch_sweep_fast<Win, true>(st, tm, wt, M_in, M_out, M_stride, R0, R1, R_stride, w, h, win, do_update, store_flow, flow, f_stride);
+        return launch_sweep_fast<Win, true>(st, tm, a, win);
     }
-    if (m == 6 && f_stride % 2 == 0 && ((uintptr_t)flow & 7) == 0) {    // any width / alignment: relaxed form of the same kernel
-        const TileMap tm = make_tile_map(w, h, G, FT_X, FT_Y, 0, -1, strip);
-        return launch_sweep_fast<Win, false>(st, tm, wt, M_in, M_out, M_stride, R0, R1, R_stride, w, h, win, do_update, store_flow, flow, f_stride);
-    }
+    if (m == 6 && a.f_stride % 2 == 0 && ((uintptr_t)a.flow & 7) == 0)      // any width / alignment: relaxed form of the same kernel
+        return launch_sweep_fast<Win, false>(st, make_tile_map(a.w, a.h, a.G, FT_X, FT_Y, 0, -1, a.strip), a, win);
     int ext, pitch, plane;
     iter_geometry(m, &ext, &pitch, &plane);
     const size_t lds = sizeof(float) * 5 * (size_t)plane;
-    const dim3 grid((w + MAV_TILE - 1) / MAV_TILE, (h + MAV_TILE - 1) / MAV_TILE, G);
+    const dim3 grid((a.w + MAV_TILE - 1) / MAV_TILE, (a.h + MAV_TILE - 1) / MAV_TILE, a.G);
     // m != 6: dynamic LDS above the default limit was granted by blur_iter_prepare() when the context was created
     const auto k = m == 6 ? k_blur_iter_generic<Win, 6> : k_blur_iter_generic<Win, 0>;
-    hipLaunchKernelGGL(k, grid, dim3(256), lds, st, M_in, M_out, M_stride, R0, R1, R_stride, w, h, m, pitch, plane, win, do_update, flow,
-                       f_stride);
+    hipLaunchKernelGGL(k, grid, dim3(256), lds, st, a.M_in, a.M_out, a.M_stride, a.R0, a.R1, a.R_stride, a.w, a.h, m, pitch, plane, win,
+                       a.do_update, a.flow, a.f_stride);
 }
 
-// tile rows [ty0, ty1) only (ty1 < 0: the whole layer).  Band launches exist for the fast form only (blur_iter_bands_ok).
-// gauss: the taps of the Gaussian window, or nullptr for the box window.
-void launch_blur_iter(hipStream_t st, const float* M_in, float* M_out, size_t M_stride, const float* R0, const float* R1,
-                      size_t R_stride, int G, int w, int h, int winsize, int do_update, int store_flow, float* flow, size_t f_stride,
-                      int ty0, int ty1, int strip, bool write_through, const GaussTaps* gauss)
+// tile rows [a.ty0, a.ty1) only (ty1 < 0: the whole layer).  Band launches exist for the fast form only (blur_iter_bands_ok).
+void launch_blur_iter(hipStream_t st, const SweepArgs& a)
 {
-    if (gauss)
-        launch_sweep(st, M_in, M_out, M_stride, R0, R1, R_stride, G, w, h, winsize, do_update, store_flow, flow, f_stride, ty0, ty1, strip,
-                     write_through, GaussWindow{*gauss});
-    else
-        launch_sweep(st, M_in, M_out, M_stride, R0, R1, R_stride, G, w, h, winsize, do_update, store_flow, flow, f_stride, ty0, ty1, strip,
-                     write_through, BoxWindow{(float)(1.0 / ((double)winsize * winsize))});
+    if (a.gauss) launch_sweep(st, a, GaussWindow{*a.gauss});
+    else launch_sweep(st, a, BoxWindow{(float)(1.0 / ((double)a.winsize * a.winsize))});
 }
 
 // The general-winsize sweep needs 5 x (32 + 2m)^2 floats of dynamic LDS; above the 64 KB default a kernel must be granted

@@ -1423,15 +1423,9 @@ static SweepPlan plan_sweeps(const mav_ctx* c, int k, int g, bool bands_ok)
 // first sweep: pixel rows [16 a0 - 8, 16 a1 + 8) -- what that sweep reads (6-pixel halo) -- which lie below everything the bands
 // above have written into Ma (their odd sweeps end one whole tile row higher); the rows two neighbouring bands both need are
 // simply built twice, to the same values.
-struct BandUpdate { const float* flow_prev; size_t fc_stride; int pw, ph; float mul; bool exact; };
-// The initial M of pixel rows [y0, y1) of gs pairs from the source `u` names: zero (flow_prev == nullptr), the coarser layer's flow
-// upsampled (pw x ph, times mul) or -- exact: the top layer of a call with an initial flow -- a field of the layer's own size.
-static void initial_m(hipStream_t st, const BandUpdate& u, const float* r0, const float* r1, size_t rs, int gs, int w, int h, float* M, size_t ms,
-                      int y0 = 0, int y1 = -1)
-{
-    if (u.exact) launch_update_matrices_flow(st, r0, r1, rs, u.flow_prev, u.fc_stride, gs, w, h, M, ms, y0, y1);
-    else launch_update_matrices(st, r0, r1, rs, u.flow_prev, u.fc_stride, u.pw, u.ph, u.mul, gs, w, h, M, ms, y0, y1);
-}
+// a: the operands every sweep of the run shares; M_in / M_out (the ping-pong through Ma / Mb), do_update, store_flow, ty0 and ty1 are
+// set per launch here.
+struct BandRun { float *Ma, *Mb; int kid /* profile class of the sweeps */, J, phase; };
 // phase = 1 (the pairs of the second stream, option "band_phase", off by default): the partition is shifted by half a band -- J + 1 bands,
 // the first and the last of half size.  Two streams that start a group together with the same partition stay in lockstep: both build a
 // band's initial M (HBM-bound) at the same moments and both sweep (cache-bound) at the same moments -- untraced at 3840x2160: 1.3 ms per
@@ -1441,10 +1435,10 @@ static void initial_m(hipStream_t st, const BandUpdate& u, const float* r0, cons
 // of the Infinity Cache (sweep launches 37.1 vs 34.6 ms summed).  The lockstep is worth keeping.  The band arguments above hold for any
 // monotone sequence of boundaries (a band whose rows have all moved above the image top at a late sweep is empty and skipped; its
 // successor then starts at row 0): bit-identical (tests/test_gpu_flow.py).
-static void sweeps_band_major(mav_ctx* c, hipStream_t st, int kid, float* Ma, float* Mb, size_t ms, const float* r0, const float* r1, size_t rs, int gs,
-                              int lw, int lh, int T, int J, float* fo, size_t fstride, const BandUpdate* upd, bool wt, int phase)
+static void sweeps_band_major(mav_ctx* c, hipStream_t st, SweepArgs a, const BandRun& run, const FlowSource* upd)
 {
-    const int I = c->fb.iterations;
+    const int I = c->fb.iterations, T = blur_iter_tile_rows(a.h), phase = run.phase;
+    int J = run.J;
     const int NBands = phase ? J + 1 : J;
     auto bound = [&](int j) -> int {                      // first tile row of band j; bound(NBands) = T
         if (j <= 0) return 0;
@@ -1463,35 +1457,37 @@ static void sweeps_band_major(mav_ctx* c, hipStream_t st, int kid, float* Ma, fl
         if (a1 <= a0) continue;
         if (upd) {
             ProfScope ps(c, K_UPDATE, st);
-            initial_m(st, *upd, r0, r1, rs, gs, lw, lh, Ma, ms, a0 == 0 ? 0 : a0 * 16 - 8, j == J - 1 ? lh : a1 * 16 + 8);
+            launch_initial_m(st, {a, run.Ma, a.M_stride, a0 == 0 ? 0 : a0 * 16 - 8, j == J - 1 ? a.h : a1 * 16 + 8}, *upd);
         }
         for (int it = 0; it < I; it++) {
             const int update = it < I - 1;
             int ty0 = a0 - it, ty1 = j == J - 1 ? T : a1 - it;
             if (ty0 < 0) ty0 = 0;
             if (ty1 <= ty0) continue;
-            ProfScope ps(c, kid, st);
-            launch_blur_iter(st, (it & 1) ? Mb : Ma, (it & 1) ? Ma : Mb, ms, r0, r1, rs, gs, lw, lh, c->fb.winsize, update, !update, fo,
-                             fstride, ty0, ty1, c->strip, wt, window_taps(c));
+            ProfScope ps(c, run.kid, st);
+            a.M_in = (it & 1) ? run.Mb : run.Ma; a.M_out = (it & 1) ? run.Ma : run.Mb;
+            a.do_update = update; a.store_flow = !update; a.ty0 = ty0; a.ty1 = ty1;
+            launch_blur_iter(st, a);
         }
     }
 }
 
-// Initial M and the `iterations` sweeps of layer k for g pairs whose expansions lie at r0 / r1 (slot stride rs), starting on
-// stream st.  flow_prev = the coarser layer's flow (pw x ph, slot stride fc_stride; nullptr at the top layer); the layer's flow goes to
-// fdst (slot stride fstride).  M ping-pongs through Ma / Mb (slot stride ms).  On return everything has been joined back into st.
-// flow_init (top layer of a call with an initial flow only): the layer's initial flow itself, l.w x l.h, slot stride fi_stride.
-static int layer_sweeps(mav_ctx* c, hipStream_t st, int k, int g, const float* r0g, const float* r1g, size_t rs, const float* flow_prev,
-                        size_t fc_stride, int pw, int ph, float* fdst, size_t fstride, float* Ma, float* Mb, size_t ms,
-                        const float* flow_init = nullptr, size_t fi_stride = 0)
+// Where layer k of a walk of g pairs finds its expansions (pair 0's two; slot stride rs) and puts its flow (slot stride fstride), and
+// the slot stride ms of the M buffers at that layer.
+struct LayerIO { int k, g; const float *r0, *r1; size_t rs; float* flow; size_t fstride, ms; };
+struct MBuffers { float *a, *b; };               // M ping-pongs through them
+// Initial M and the `iterations` sweeps of layer io.k for io.g pairs, starting on stream st; the initial flow comes from `src` (the
+// coarser layer's flow; zero or the call's initial flow at the top layer).  On return everything has been joined back into st.
+static int layer_sweeps(mav_ctx* c, hipStream_t st, const LayerIO& io, const FlowSource& src, const MBuffers& m)
 {
+    const int k = io.k, g = io.g;
     const Layer& l = c->layers[k];
-    const float mul = (float)(1. / c->fb.pyr_scale);
-    const BandUpdate src = flow_init ? BandUpdate{flow_init, fi_stride, 0, 0, 0.f, true} : BandUpdate{flow_prev, fc_stride, pw, ph, mul, false};
-    auto src_at = [&](int s0) { BandUpdate u = src; if (u.flow_prev) u.flow_prev += (size_t)s0 * u.fc_stride; return u; };   // from pair s0 on
-    const SweepPlan p = plan_sweeps(c, k, g, blur_iter_bands_ok(l.w, c->fb.winsize, ms, rs, fstride, Ma, Mb, r0g, r1g, fdst));
-    const int kid = k == 0 ? K_ITER : K_ITER_COARSE;
-    const int T = blur_iter_tile_rows(l.h);
+    const size_t ms = io.ms, rs = io.rs;
+    const PairOperands group{io.r0, io.r1, rs, g, l.w, l.h};
+    SweepArgs sa{group, m.a, m.b, ms, c->fb.winsize, io.flow, io.fstride, 1, 0};
+    sa.strip = c->strip; sa.gauss = window_taps(c);
+    const SweepPlan p = plan_sweeps(c, k, g, blur_iter_bands_ok(sa));
+    sa.write_through = p.write_through;
     if (p.streams == 2) {
         CHK(ensure_pair_stream(c));
         HIPCHK(hipEventRecord(c->pif_fork, st));
@@ -1499,7 +1495,7 @@ static int layer_sweeps(mav_ctx* c, hipStream_t st, int k, int g, const float* r
     }
     if (p.m_build == M_GROUP) {
         ProfScope ps(c, K_UPDATE, st);
-        initial_m(st, src, r0g, r1g, rs, g, l.w, l.h, Ma, ms);
+        launch_initial_m(st, {group, m.a, ms}, src);
     }
     // With two streams the host alternates between them sub-group by sub-group, and within a pair band by band (a band's initial M, then
     // all its sweeps): the two streams never wait for each other inside the group.
@@ -1508,14 +1504,15 @@ static int layer_sweeps(mav_ctx* c, hipStream_t st, int k, int g, const float* r
         const bool second = p.streams == 2 && (i & 1);
         const hipStream_t ss = second ? c->pair_stream : st;
         const size_t m_off = p.m_slot == SLOT_OWN ? (size_t)s0 * ms : p.m_slot == SLOT_FIRST ? 0 : (size_t)(i & 1) * p.per_launch * ms;
-        const float *r0 = r0g + (size_t)s0 * rs, *r1 = r1g + (size_t)s0 * rs;
-        const BandUpdate bu = src_at(s0);
+        sa.R0 = io.r0 + (size_t)s0 * rs; sa.R1 = io.r1 + (size_t)s0 * rs; sa.G = gs;
+        sa.flow = io.flow + (size_t)s0 * io.fstride;
+        const FlowSource bu = src.from_pair(s0);
         if (p.m_build == M_SUB) {
             ProfScope ps(c, K_UPDATE, ss);
-            initial_m(ss, bu, r0, r1, rs, gs, l.w, l.h, Ma + m_off, ms);
+            launch_initial_m(ss, {sa, m.a + m_off, ms}, bu);
         }
-        sweeps_band_major(c, ss, kid, Ma + m_off, Mb + m_off, ms, r0, r1, rs, gs, l.w, l.h, T, p.J, fdst + (size_t)s0 * fstride, fstride,
-                          p.m_build == M_BAND ? &bu : nullptr, p.write_through, p.shift_second && second);
+        sweeps_band_major(c, ss, sa, {m.a + m_off, m.b + m_off, k == 0 ? K_ITER : K_ITER_COARSE, p.J, p.shift_second && second},
+                          p.m_build == M_BAND ? &bu : nullptr);
     }
     if (p.streams == 2) {
         prof_close_stream(c, c->pair_stream); prof_close_stream(c, st);
@@ -1537,9 +1534,12 @@ static void layer_expansions(mav_ctx* c, hipStream_t st, int k, const T* prev, c
     mav_ctx::WorkSet& w = c->ws;
     const size_t n0 = c->n0;
     const Layer& l = c->layers[k];
+    const LayerTarget target{I, n0, blur_of(c, l), l.w, l.h};
+    const BlurScratch scratch{w.Htmp, c->htmp_stride};
+    auto frames = [&](const T* a, const T* b, int split, int G) { return FrameRun<T>{a, b, split, n0, G, c->W, c->H}; };
     if (seq) {
         { ProfScope ps(c, K_BLUR_RESIZE, st);
-          launch_blur_resize<T>(st, prev, nullptr, 0, n0, g + 1, c->W, c->H, l.w, l.h, blur_of(c, l), w.Htmp, c->htmp_stride, I, n0); }
+          launch_blur_resize(st, frames(prev, nullptr, 0, g + 1), target, scratch); }
         { ProfScope ps(c, K_POLYEXP, st);
           launch_polyexp(st, I, n0, g + 1, l.w, l.h, c->pc, R, 5 * n0); }
         *r0 = R; *r1 = R + 5 * n0;
@@ -1548,11 +1548,11 @@ static void layer_expansions(mav_ctx* c, hipStream_t st, int k, const T* prev, c
     float* R1 = R + 5 * n0 * (size_t)g;
     *r0 = R; *r1 = R1;
     // (the two-pass blur's scratch holds g + 1 frames)
-    const bool no_tmp = !blur_resize_needs_tmp(prev, next, n0, c->W, c->H, l.w, l.h, blur_of(c, l), I, n0);
+    const bool no_tmp = !blur_resize_needs_tmp(frames(prev, next, g, 2 * g), target);
     const bool merge_frames = (no_tmp || 2 * g <= g + 1) && (size_t)2 * g * l.w * l.h * sizeof(float) <= ((size_t)48 << 20);
     if (merge_frames) {
         { ProfScope ps(c, K_BLUR_RESIZE, st);
-          launch_blur_resize(st, prev, next, g, n0, 2 * g, c->W, c->H, l.w, l.h, blur_of(c, l), w.Htmp, c->htmp_stride, I, n0); }
+          launch_blur_resize(st, frames(prev, next, g, 2 * g), target, scratch); }
         { ProfScope ps(c, K_POLYEXP, st);
           launch_polyexp(st, I, n0, 2 * g, l.w, l.h, c->pc, R, 5 * n0); }
         return;
@@ -1561,7 +1561,7 @@ static void layer_expansions(mav_ctx* c, hipStream_t st, int k, const T* prev, c
     float* Rs[2] = {R, R1};
     for (int i = 0; i < 2; i++) {
         { ProfScope ps(c, K_BLUR_RESIZE, st);
-          launch_blur_resize<T>(st, img[i], nullptr, 0, n0, g, c->W, c->H, l.w, l.h, blur_of(c, l), w.Htmp, c->htmp_stride, I, n0); }
+          launch_blur_resize(st, frames(img[i], nullptr, 0, g), target, scratch); }
         { ProfScope ps(c, K_POLYEXP, st);
           launch_polyexp(st, I, n0, g, l.w, l.h, c->pc, Rs[i], 5 * n0); }
     }
@@ -1574,25 +1574,24 @@ static bool is_small_group(const mav_ctx* c, int g)
            (size_t)g * c->n0 * 80 <= ((size_t)c->small_batch_mb << 20);
 }
 
-// The layer images of layers k_lo .. k_hi for F frames (the first `split` from run prev, the rest from run img2; img2 == nullptr: one
-// run) into regions Ik(k) with slot stride sk(k): every layer blur_multi_ok accepts through ONE launch, the others (long Gaussians)
+// The layer images of layers k_lo .. k_hi for the frames f into regions Ik(k) with slot stride sk(k): every layer blur_multi_ok accepts through ONE launch, the others (long Gaussians)
 // through the two-pass kernels in chunks the H x w scratch holds; then ALL their expansions through one launch (per MAV_MAX_JOBS layers).
 template <typename T, typename IkFn, typename RkFn, typename SkFn>
-static void pyramid_multi(mav_ctx* c, hipStream_t st, const T* prev, const T* img2, int split, int F, int k_lo, int k_hi, IkFn Ik,
-                          RkFn Rk, SkFn sk)
+static void pyramid_multi(mav_ctx* c, hipStream_t st, const FrameRun<T>& f, int k_lo, int k_hi, IkFn Ik, RkFn Rk, SkFn sk)
 {
     mav_ctx::WorkSet& w = c->ws;
     const size_t n0 = c->n0;
+    const int F = f.G;
     BlurJobs bj{0, 0, {}};
     PolyJobs pj{0, 0, {}};
-    auto flush_blur = [&]() { if (bj.n) { ProfScope ps(c, K_BLUR_RESIZE, st); launch_blur_multi(st, prev, img2, split, n0, F, c->W, c->H, bj, F > 8); bj.n = 0; } };
+    auto flush_blur = [&]() { if (bj.n) { ProfScope ps(c, K_BLUR_RESIZE, st); launch_blur_multi(st, f, bj); bj.n = 0; } };
     auto flush_poly = [&]() { if (pj.n) { ProfScope ps(c, K_POLYEXP, st); launch_polyexp_multi(st, pj, F, c->pc); pj.n = 0; } };
     for (int k = k_lo; k <= k_hi; k++) {
         const Layer& l = c->layers[k];
-        if (blur_multi_ok(prev, img2, n0, c->W, c->H, l.w, l.h, blur_of(c, l), Ik(k), sk(k))) {
+        const LayerTarget target{Ik(k), sk(k), blur_of(c, l), l.w, l.h};
+        if (blur_multi_ok(f, target)) {
             if (bj.n == MAV_MAX_JOBS) flush_blur();
-            BlurJob& J = bj.j[bj.n++];
-            J.out = Ik(k); J.out_stride = sk(k); J.bp = blur_of(c, l); J.w = l.w; J.h = l.h;
+            static_cast<LayerTarget&>(bj.j[bj.n++]) = target;
         } else {
             // a long Gaussian (or an unaligned finest layer): launches of its own.  The two-pass scratch holds (group + 1) H x W floats;
             // a frame needs H x w of it
@@ -1601,10 +1600,11 @@ static void pyramid_multi(mav_ctx* c, hipStream_t st, const T* prev, const T* im
             const int chunk = (int)(cap_frames < (size_t)F ? cap_frames : (size_t)F);
             for (int f0 = 0; f0 < F; f0 += chunk) {
                 const int n = F - f0 < chunk ? F - f0 : chunk;
-                const bool from2 = img2 && f0 >= split;
-                const T* a = from2 ? img2 + (size_t)(f0 - split) * n0 : prev + (size_t)f0 * n0;
-                launch_blur_resize(st, a, from2 ? nullptr : img2, from2 ? 0 : split - f0, n0, n, c->W, c->H, l.w, l.h, blur_of(c, l), w.Htmp, per,
-                                   Ik(k) + (size_t)f0 * sk(k), sk(k));
+                const bool from2 = f.img2 && f0 >= f.split;
+                const T* a = from2 ? f.img2 + (size_t)(f0 - f.split) * n0 : f.img + (size_t)f0 * n0;
+                LayerTarget chunk_target = target;
+                chunk_target.out += (size_t)f0 * sk(k);
+                launch_blur_resize(st, FrameRun<T>{a, from2 ? nullptr : f.img2, from2 ? 0 : f.split - f0, n0, n, c->W, c->H}, chunk_target, {w.Htmp, per});
             }
         }
         if (pj.n == MAV_MAX_JOBS) { flush_blur(); flush_poly(); }
@@ -1615,23 +1615,23 @@ static void pyramid_multi(mav_ctx* c, hipStream_t st, const T* prev, const T* im
     flush_poly();
 }
 
-// Where layer k of a walk finds its expansions (pair 0's two; slot stride rs) and puts its flow (slot stride fstride), and the slot
-// stride ms of the M buffers at that layer.
-struct LayerIO { const float *r0, *r1; size_t rs; float* flow; size_t fstride, ms; };
-// Layers k_hi .. k_lo of g pairs, top-down: `at(k)` makes layer k's expansions (unless they exist already) and says where they and the
-// layer's flow lie; then the layer's initial M and sweeps (layer_sweeps), from the flow of the layer above.  flow_prev / fp_stride:
-// the flow of layer k_hi + 1, or nullptr when the walk starts at the top of the pyramid; flow_init: the top layer's initial flow or nullptr.
-template <typename AtFn>
-static int walk_layers(mav_ctx* c, hipStream_t st, int k_hi, int k_lo, int g, AtFn at, float* Ma, float* Mb, const float* flow_prev,
-                       size_t fp_stride, const float* flow_init)
+// Layers k_hi .. k_lo, top-down: `at(k)` makes layer k's expansions (unless they exist already) and says where they and the layer's
+// flow lie; then the layer's initial M and sweeps (layer_sweeps), from the flow of the layer above.  src: where layer k_hi's initial
+// flow comes from (top_flow at the top of the pyramid, else the flow of layer k_hi + 1: coarser_flow).
+static FlowSource coarser_flow(const mav_ctx* c, int k_coarser, const float* flow, size_t stride)
 {
-    const int L = (int)c->layers.size();
-    int pw = flow_prev ? c->layers[k_hi + 1].w : 0, ph = flow_prev ? c->layers[k_hi + 1].h : 0;
+    const Layer& l = c->layers[k_coarser];
+    return FlowSource::coarser(flow, stride, l.w, l.h, (float)(1. / c->fb.pyr_scale));
+}
+// the top layer's: the call's initial flow (init_snap, the layer's own size) or zero
+static FlowSource top_flow(const mav_ctx* c, const float* flow_init) { return flow_init ? FlowSource::field(flow_init, c->init_stride) : FlowSource{}; }
+template <typename AtFn>
+static int walk_layers(mav_ctx* c, hipStream_t st, int k_hi, int k_lo, AtFn at, const MBuffers& m, FlowSource src)
+{
     for (int k = k_hi; k >= k_lo; k--) {
         const LayerIO io = at(k);
-        CHK(layer_sweeps(c, st, k, g, io.r0, io.r1, io.rs, flow_prev, fp_stride, pw, ph, io.flow, io.fstride, Ma, Mb, io.ms,
-                         k == L - 1 ? flow_init : nullptr, c->init_stride));
-        flow_prev = io.flow; fp_stride = io.fstride; pw = c->layers[k].w; ph = c->layers[k].h;
+        CHK(layer_sweeps(c, st, io, src, m));
+        src = coarser_flow(c, k, io.flow, io.fstride);
     }
     return MAV_OK;
 }
@@ -1644,17 +1644,16 @@ static int deep_layers(mav_ctx* c, hipStream_t st, const T* prev, const T* next,
 {
     const int L = (int)c->layers.size(), kd = c->kd;
     const int F = seq ? D + 1 : 2 * D;
-    const T* img2 = seq ? nullptr : next;
     const size_t base = c->c_off[kd];
     auto Ik = [&](int k) { return c->deep.I + (size_t)F * (c->c_off[k] - base); };
     auto Rk = [&](int k) { return c->deep.R + 5 * (size_t)F * (c->c_off[k] - base); };
     auto sk = [&](int k) { return c->c_stride[k]; };
-    pyramid_multi(c, st, prev, img2, D, F, kd, L - 1, Ik, Rk, sk);
+    pyramid_multi(c, st, FrameRun<T>{prev, seq ? nullptr : next, D, c->n0, F, c->W, c->H}, kd, L - 1, Ik, Rk, sk);
     auto at = [&](int k) {
         const size_t rs = 5 * sk(k);
-        return LayerIO{Rk(k), Rk(k) + (seq ? rs : rs * (size_t)D), rs, c->deep.f[k & 1], 2 * sk(k), rs};
+        return LayerIO{k, D, Rk(k), Rk(k) + (seq ? rs : rs * (size_t)D), rs, c->deep.f[k & 1], 2 * sk(k), rs};
     };
-    return walk_layers(c, st, L - 1, kd, D, at, c->deep.Ma, c->deep.Mb, nullptr, 0, flow_init);
+    return walk_layers(c, st, L - 1, kd, at, {c->deep.Ma, c->deep.Mb}, top_flow(c, flow_init));
 }
 
 // One group of g pairs: every coarse layer completely (top layer first: images, expansions, initial M, sweeps), then the finest layer.
@@ -1683,23 +1682,23 @@ static int flow_group(mav_ctx* c, const T* prev, const T* next, int g, bool seq,
     auto fstride_of = [&](int k) { return k ? fc_stride : 2 * n0; };
     if (!deep_flow && is_small_group(c, g)) {
         const int F = seq ? g + 1 : 2 * g;                                // frames: one run of g + 1, or the prev run and the next run
-        const T* img2 = seq ? nullptr : next;
         auto Ik = [&](int k) { return k ? w.Ic + (size_t)F * c->c_off[k] : w.I; };
         auto Rk = [&](int k) { return k ? w.Rc + 5 * (size_t)F * c->c_off[k] : w.R; };
         auto sk = [&](int k) { return k ? c->c_stride[k] : n0; };
-        pyramid_multi(c, st, prev, img2, g, F, 0, L - 1, Ik, Rk, sk);
+        pyramid_multi(c, st, FrameRun<T>{prev, seq ? nullptr : next, g, n0, F, c->W, c->H}, 0, L - 1, Ik, Rk, sk);
         auto at = [&](int k) {
             const size_t rs = 5 * sk(k);
-            return LayerIO{Rk(k), Rk(k) + (seq ? rs : rs * (size_t)g), rs, flow_of(k), fstride_of(k), 5 * n0};
+            return LayerIO{k, g, Rk(k), Rk(k) + (seq ? rs : rs * (size_t)g), rs, flow_of(k), fstride_of(k), 5 * n0};
         };
-        return walk_layers(c, st, L - 1, 0, g, at, w.Ma, w.Mb, nullptr, fc_stride, flow_init);
+        return walk_layers(c, st, L - 1, 0, at, {w.Ma, w.Mb}, top_flow(c, flow_init));
     }
     auto at = [&](int k) {
         const float *r0 = nullptr, *r1 = nullptr;
         layer_expansions(c, st, k, prev, next, g, seq, w.I, w.R, &r0, &r1);
-        return LayerIO{r0, r1, 5 * n0, flow_of(k), fstride_of(k), 5 * n0};
+        return LayerIO{k, g, r0, r1, 5 * n0, flow_of(k), fstride_of(k), 5 * n0};
     };
-    return walk_layers(c, st, deep_flow ? c->kd - 1 : L - 1, 0, g, at, w.Ma, w.Mb, deep_flow, deep_flow ? deep_stride : fc_stride, flow_init);
+    if (deep_flow) return walk_layers(c, st, c->kd - 1, 0, at, {w.Ma, w.Mb}, coarser_flow(c, c->kd, deep_flow, deep_stride));
+    return walk_layers(c, st, L - 1, 0, at, {w.Ma, w.Mb}, top_flow(c, flow_init));
 }
 
 // does a call of `batch` pairs run its deep layers once for the whole call (deep_layers) instead of once per group?
@@ -3126,8 +3125,9 @@ static int stage_blur_resize(mav_ctx* c, const void* img, int depth, int k, bool
     float* dtmp = h.scratch<float>(c->htmp_stride * sizeof(float));
     CHK(h.staged());
     with_depth(depth, [&](auto* px) {
-        launch_blur_resize(c->stream, (decltype(px))di, (decltype(px)) nullptr, 0, c->n0, 1, c->W, c->H, l->w, l->h, blur_of(c, *l), dtmp,
-                           c->htmp_stride, dout, n, two_pass);
+        typedef std::remove_const_t<std::remove_pointer_t<decltype(px)>> T;
+        launch_blur_resize(c->stream, FrameRun<T>{(const T*)di, nullptr, 0, c->n0, 1, c->W, c->H}, {dout, n, blur_of(c, *l), l->w, l->h},
+                           {dtmp, c->htmp_stride, two_pass});
     });
     CHK(check_launch("blur_resize"));
     return h.finish();
@@ -3164,7 +3164,7 @@ extern "C" int mav_stage_update_matrices(mav_ctx* c, const float* R0, const floa
     const float* df = h.in(flow, 2 * n * sizeof(float));
     float* dm = h.out(M, 5 * n * sizeof(float));
     CHK(h.staged());
-    launch_update_matrices_flow(c->stream, d0, d1, 5 * n, df, 2 * n, 1, l->w, l->h, dm, 5 * n);
+    launch_initial_m(c->stream, {{d0, d1, 5 * n, 1, l->w, l->h}, dm, 5 * n}, FlowSource::field(df, 2 * n));
     CHK(check_launch("update_matrices"));
     return h.finish();
 }
@@ -3179,15 +3179,13 @@ extern "C" int mav_stage_update_matrices_from(mav_ctx* c, const float* R0, const
     if (flow_coarse && k + 1 >= (int)c->layers.size())
         return fail(MAV_ERR_ARG, "mav_stage_update_matrices_from: layer %d is the top layer, it has no coarser flow", k);
     const size_t n = (size_t)l->w * l->h;
-    const int pw = flow_coarse ? c->layers[k + 1].w : 0, ph = flow_coarse ? c->layers[k + 1].h : 0;
-    const size_t nc = (size_t)pw * ph;
-    const float mul = (float)(1. / c->fb.pyr_scale);
+    const size_t nc = flow_coarse ? (size_t)c->layers[k + 1].w * c->layers[k + 1].h : 0;
     const float* d0 = h.in(R0, 5 * n * sizeof(float));
     const float* d1 = h.in(R1, 5 * n * sizeof(float));
     const float* df = h.in(flow_coarse, 2 * nc * sizeof(float));
     float* dm = h.out(M, 5 * n * sizeof(float));
     CHK(h.staged());
-    launch_update_matrices(c->stream, d0, d1, 5 * n, df, 2 * nc, pw, ph, mul, 1, l->w, l->h, dm, 5 * n);
+    launch_initial_m(c->stream, {{d0, d1, 5 * n, 1, l->w, l->h}, dm, 5 * n}, flow_coarse ? coarser_flow(c, k + 1, df, 2 * nc) : FlowSource{});
     CHK(check_launch("update_matrices"));
     return h.finish();
 }
@@ -3223,8 +3221,9 @@ extern "C" int mav_stage_blur_iter(mav_ctx* c, const float* R0, const float* R1,
     float* df = h.out(flow, 2 * n * sizeof(float));
     h.fetch(update ? M_out : nullptr, dmo, 5 * n * sizeof(float));
     CHK(h.staged());
-    launch_blur_iter(c->stream, dm, dmo, 5 * n, d0, d1, 5 * n, 1, l->w, l->h, c->fb.winsize, update, 1, df, 2 * n, 0, -1, c->strip, false,
-                     window_taps(c));
+    SweepArgs a{{d0, d1, 5 * n, 1, l->w, l->h}, dm, dmo, 5 * n, c->fb.winsize, df, 2 * n, update, 1};
+    a.strip = c->strip; a.gauss = window_taps(c);
+    launch_blur_iter(c->stream, a);
     CHK(check_launch("blur_iter"));
     return h.finish();
 }

@@ -44,57 +44,91 @@ struct DerotParams {  // one pair; Detector.derotate
 #define MAV_MAX_JOBS 6
 struct PolyJob { const float* I; float* R; size_t I_stride, R_stride; int w, h, tiles_x, per_img, first_block, pad; };
 struct PolyJobs { int n, pad; PolyJob j[MAV_MAX_JOBS]; };
-struct BlurJob { float* out; size_t out_stride; BlurParams bp; int w, h, fused, gx, gy, first_block, rows_cap, pitch_w, th, pad; };
-struct BlurJobs { int n, pad; BlurJob j[MAV_MAX_JOBS]; };
 
 // ---- flow kernels (kernels_flow.hip) ----------------------------------------------------------------------
 // All take G slots; slot s reads/writes base + s*stride (strides in elements).
-// G images from two runs: the first `split` from img, the rest from img2 (same stride); img2 == nullptr: one run.  Layers with a
-// short Gaussian (blur_resize_is_fused) go through one fused kernel and never touch tmp unless two_pass is set.
-// The layer-image functions take frames of one of three depths, T = uint8_t, uint16_t or float (instantiated in kernels_flow.hip);
-// esize = sizeof(T).
+// The frames of a layer-image launch: G images of W x H from two runs, the first `split` from img, the rest from img2 (same stride);
+// img2 == nullptr: one run.  T = uint8_t, uint16_t or float (the three source depths, instantiated in kernels_flow.hip; esize = sizeof(T)).
 template <typename T>
-void launch_blur_resize(hipStream_t st, const T* img, const T* img2, int split, size_t img_stride, int G, int W, int H, int w,
-                        int h, BlurParams bp, float* tmp /* G x H x w scratch for the separable passes */, size_t tmp_stride, float* out,
-                        size_t out_stride, bool two_pass = false);
+struct FrameRun {
+    const T *img, *img2;
+    int split;
+    size_t img_stride;
+    int G, W, H;
+    FrameRun runs() const { return img2 ? *this : FrameRun{img, img, G, img_stride, G, W, H}; }   // "one run" spelled as two: what the kernels take
+};
+// One layer's image of those frames: w x h, slot s at out + s * out_stride.  (The head of a BlurJob: the kernel argument's layout.)
+struct LayerTarget { float* out; size_t out_stride; BlurParams bp; int w, h; };
+struct BlurJob : LayerTarget { int fused, gx, gy, first_block, rows_cap, pitch_w, th, pad; };
+struct BlurJobs { int n, pad; BlurJob j[MAV_MAX_JOBS]; };
+// the separable two-pass form's scratch (G x H x w floats, slot stride `stride`); two_pass: take that form even for a layer that would be
+// fused (the stage hook compares the two forms).  Layers with a short Gaussian (blur_resize_is_fused) never touch tmp otherwise.
+struct BlurScratch { float* tmp; size_t stride; bool two_pass = false; };
+template <typename T>
+void launch_blur_resize(hipStream_t st, const FrameRun<T>& f, const LayerTarget& t, const BlurScratch& scratch);
 bool blur_resize_is_fused(int W, int H, int w, int h, int ksize, int esize = 1);
 template <typename T>
-bool blur_resize_needs_tmp(const T* img, const T* img2, size_t img_stride, int W, int H, int w, int h, BlurParams bp,
-                           const float* out, size_t out_stride);
+bool blur_resize_needs_tmp(const FrameRun<T>& f, const LayerTarget& t);
 void launch_polyexp(hipStream_t st, const float* I, size_t I_stride, int G, int w, int h, const PolyCoef& pc, float* R,
                     size_t R_stride);
 // jobs.j[i]: I, R, I_stride, R_stride, w, h filled by the caller; G images per job
 void launch_polyexp_multi(hipStream_t st, PolyJobs jobs, int G, const PolyCoef& pc);
-// jobs.j[i]: out, out_stride, bp, w, h filled by the caller, for layers blur_multi_ok accepts
 template <typename T>
-bool blur_multi_ok(const T* img, const T* img2, size_t img_stride, int W, int H, int w, int h, BlurParams bp, const float* out,
-                   size_t out_stride);
+bool blur_multi_ok(const FrameRun<T>& f, const LayerTarget& t);
+// jobs.j[i]: the LayerTarget filled by the caller, for layers blur_multi_ok accepts.  More than 8 frames (the deep layers of a whole
+// call): one launch per tile code (fused_path_of) instead of one for all jobs.
 template <typename T>
-void launch_blur_multi(hipStream_t st, const T* img, const T* img2, int split, size_t img_stride, int G, int W, int H, BlurJobs jobs,
-                       bool split_by_path = false /* one launch per tile code (fused_path_of) instead of one for all jobs */);
-// flow_prev == nullptr: zero initial flow. Otherwise flow = resize(prev (ph x pw x 2))*mul, evaluated inline.
-void launch_update_matrices(hipStream_t st, const float* R0, const float* R1, size_t R_stride, const float* flow_prev,
-                            size_t fp_stride, int pw, int ph, float mul, int G, int w, int h, float* M, size_t M_stride,
-                            int y_begin = 0, int y_end = -1 /* pixel rows [y_begin, y_end) only; -1 = to the bottom */);
-// explicit per-pixel flow (h x w x 2): the stage hook, and the top layer of a call with an initial flow (OPTFLOW_USE_INITIAL_FLOW)
-void launch_update_matrices_flow(hipStream_t st, const float* R0, const float* R1, size_t R_stride, const float* flow,
-                                 size_t f_stride, int G, int w, int h, float* M, size_t M_stride,
-                                 int y_begin = 0, int y_end = -1 /* pixel rows [y_begin, y_end) only; -1 = to the bottom */);
+void launch_blur_multi(hipStream_t st, const FrameRun<T>& f, BlurJobs jobs);
+
+// G pairs of one w x h layer: their expansions R0 / R1, five planes each.
+struct PairOperands { const float *R0, *R1; size_t R_stride; int G, w, h; };
+// Where a layer's initial flow comes from: nowhere (zero flow: the top layer), the coarser layer's field (pw x ph; resize(INTER_LINEAR)
+// to the layer's size times mul, evaluated inside the kernel and never written) or a field of the layer's own size (the stage hook; the
+// top layer of a call with OPTFLOW_USE_INITIAL_FLOW).  kind = k_update_matrices' MODE.
+struct FlowSource {
+    enum Kind { ZERO = 0, COARSER = 1, FIELD = 2 };
+    Kind kind = ZERO;
+    const float* flow = nullptr;
+    size_t stride = 0;
+    int pw = 0, ph = 0;
+    float mul = 0.f;
+    static FlowSource coarser(const float* flow, size_t stride, int pw, int ph, float mul)      // flow == nullptr: zero
+    {
+        return flow ? FlowSource{COARSER, flow, stride, pw, ph, mul} : FlowSource{};
+    }
+    static FlowSource field(const float* flow, size_t stride) { return FlowSource{FIELD, flow, stride}; }
+    FlowSource from_pair(int s0) const { FlowSource u = *this; if (u.flow) u.flow += (size_t)s0 * stride; return u; }
+};
+// The initial M (FarnebackUpdateMatrices on the source's flow) of pixel rows [y_begin, y_end) of the pairs; y_end < 0 = to the bottom.
+struct InitialMArgs : PairOperands {
+    float* M;
+    size_t M_stride;
+    int y_begin = 0, y_end = -1;
+};
+void launch_initial_m(hipStream_t st, const InitialMArgs& a, const FlowSource& src);
 // The Gaussian window of the sweep (OPTFLOW_FARNEBACK_GAUSSIAN): taps k[0..m], m = winsize / 2, as gauss_taps() computes them on the host.
 #define MAV_MAX_WIN_HALF 32                     // winsize <= 64 (mav_create)
 struct GaussTaps { float k[MAV_MAX_WIN_HALF + 1]; };
 void gauss_taps(int winsize, GaussTaps* out);
-void launch_blur_iter(hipStream_t st, const float* M_in, float* M_out, size_t M_stride, const float* R0, const float* R1,
-                      size_t R_stride, int G, int w, int h, int winsize, int do_update, int store_flow, float* flow, size_t f_stride,
-                      int ty0 = 0, int ty1 = -1 /* tile rows [ty0, ty1) of 16 pixel rows; ty1 < 0 = the whole layer */,
-                      int strip = 0 /* width in tiles of the tile order's column strips; 0 = automatic */,
-                      bool write_through = false /* M' through sc1 stores: see k_blur_iter_fast */,
-                      const GaussTaps* gauss = nullptr /* OPTFLOW_FARNEBACK_GAUSSIAN: the window's taps; nullptr = box window */);
+// One sweep launch (k_blur_iter_*): M_in -> flow and, with do_update, M_out.  launch_blur_iter and blur_iter_bands_ok take the same
+// object, so the predicate answers for the operands that are launched.
+struct SweepArgs : PairOperands {
+    const float* M_in;
+    float* M_out;
+    size_t M_stride;
+    int winsize;
+    float* flow;
+    size_t f_stride;
+    int do_update, store_flow;            // store_flow == 0: the sweep's flow is consumed inside the kernel only (valid when do_update != 0)
+    int ty0 = 0, ty1 = -1;                // tile rows [ty0, ty1) of 16 pixel rows; ty1 < 0 = the whole layer
+    int strip = 0;                        // width in tiles of the tile order's column strips; 0 = automatic
+    bool write_through = false;           // M' through sc1 stores: see k_blur_iter_fast
+    const GaussTaps* gauss = nullptr;     // OPTFLOW_FARNEBACK_GAUSSIAN: the window's taps; nullptr = box window
+};
+void launch_blur_iter(hipStream_t st, const SweepArgs& a);
 int blur_iter_tile_rows(int h);                 // 16-pixel tile rows of a layer of height h
 // band launches (ty0 / ty1) are honoured only by the fast sweep kernel: true when launch_blur_iter will take it for these operands
-bool blur_iter_bands_ok(int w, int winsize, size_t M_stride, size_t R_stride, size_t f_stride, const void* M_in, const void* M_out,
-                        const void* R0, const void* R1, const void* flow);
-// store_flow == 0: the sweep's flow is consumed inside the kernel only (valid when do_update != 0)
+bool blur_iter_bands_ok(const SweepArgs& a);
 size_t blur_iter_lds_bytes(int winsize);
 const char* blur_iter_prepare(int winsize);   // grants the general sweep kernels (both windows) their dynamic LDS on the current device
 

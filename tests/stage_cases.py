@@ -3,8 +3,8 @@ to the float64 restatement (tests/test_gpu_stages.py, tests/test_stage_ref64_cpu
 
 The library dispatches a stage to one of several kernels on the layer's width, the parameters and the area ratio of the initial
 flow.  Each case below names the forms it is there to reach; tests/test_gpu_stages.py::test_every_kernel_form_is_reached derives the
-forms from the same predicates the dispatch uses (kernels_flow.hip launch_blur_iter / launch_polyexp / launch_blur_resize,
-kernels_window.hip launch_area_resize_flow) and fails when a form of FORMS is no longer reached.
+forms from the same predicates the dispatch uses (kernels_flow.hip launch_blur_iter / launch_polyexp / launch_blur_resize /
+launch_initial_m, kernels_window.hip launch_area_resize_flow) and fails when a form of FORMS is no longer reached.
 
 The sibling tables: tests/detect_cases.py (detection path, kernels_detect.hip), tests/sparse_cases.py (sparse path, kernels_lk.hip)
 and tests/window_cases.py (window search, kernels_window.hip).
@@ -21,7 +21,7 @@ from initial_flow_ref import area_ratio
 FORMS = {
     "sweep": {"fast<6>", "fast<6,false>", "generic<0>", "generic<0>+lds>64K"},
     "polyexp": {"polyexp<8>", "polyexp<7>", "polyexp<5>", "polyexp<0>"},
-    "initial_m": {"mode0", "mode1", "mode2"},
+    "initial_m": {"mode0", "mode1", "mode2"},      # launch_initial_m: k_update_matrices<FlowSource::kind> -- ZERO, COARSER, FIELD
     "initial_flow": {"copy", "fast", "fast+remainder", "general"},
     "blur0": {"blur3_u8", "two-pass"},
     "blur": {"fused", "two-pass"},

@@ -134,7 +134,7 @@ def _flows(w, h):
 @pytest.mark.parametrize("case", CASES, ids=CASE_IDS)
 def test_update_matrices(contexts, fb_oracle, case):
     """MODE 2 (explicit flow) against the oracle per pixel; MODE 0 == MODE 2 with a zero field; MODE 1 (the coarser flow upsampled
-    inside the kernel) == MODE 2 fed fb_oracle.resize_flow of it -- both share update_px, so this isolates the fused upsample."""
+    inside the kernel) == MODE 2 fed fb_oracle.resize_flow of it -- both share update_px (launch_initial_m picks the mode from its FlowSource), so this isolates the fused upsample."""
     d = _case_data(contexts, fb_oracle, case)
     rel = ratio = 0.0
     for k in range(d["L"]):

@@ -40,8 +40,8 @@ def region_lines(src):
     r["col_edge"] = (find("// tiles touching the left/right image edge", k), find("STAMP(ts1);", k) - 1)
     r["row_solve"] = (find("STAMP(ts1);", k), find("STAMP(ts3);", k))
     r["update"] = (find("STAMP(ts3);", k) + 1, find("STAMP_ADD(0, ts0, ts1)", k))
-    r["gather_issue"] = (find("void gather_issue("), find("void update_finish(") - 1)
-    r["update_finish"] = (find("void update_finish("), find("struct __attribute__((packed, aligned(4))) F2U") - 1)
+    r["gather_issue"] = (find("void gather_issue("), find("// the memory form's gather") - 1)
+    r["update_finish"] = (find("void update_finish("), find("// memory form: R0p/R1p/Mp point at plane 0") - 1)
     r["solve_px"] = (find("void solve_px("), find("float2 upsample_flow(") - 1)
     r["window"] = (find("struct BoxWindow {"), find("void iter_geometry(") - 1)
     r["solve_gauss_px"] = (find("void solve_gauss_px("), find("struct GaussWindow {") - 1)

@@ -1,11 +1,13 @@
-"""The bits of the sweep kernels of one BUILD of libmavflow, one CRC32 per line: run it on two builds and diff the outputs.
+"""The bits of the sweep kernels and of the initial M of one BUILD of libmavflow, one CRC32 per line: run it on two builds and diff the outputs.
 
     python tools/sweep_bits.py <libmavflow.so> > bits.txt
 
 The box window has no bit-exact reference (its CPU original sums in double), so a change that must not move it is held to the
 build before it.  Stage lines: mav_stage_blur_iter's flow and M', update true and false, both windows, on every layer of the small
 cases of tests/stage_cases.py with smooth_flow and crafted_flow as the flow M is built from (R0, R1 and M come from the library's own
-expansion and UpdateMatrices stages).  Schedule lines: Context.farneback at 640x480, 3 levels, batch 3, both windows, bands 1 / 2 / 3 x
+expansion and UpdateMatrices stages); each also carries the CRC of that M (k_update_matrices MODE 2) and of the zero-flow initial M
+(MODE 0).  Initial-M lines: stage_update_matrices_from on a smooth_flow of the coarser layer's size (MODE 1), for every layer that has
+a coarser one.  Schedule lines: Context.farneback at 640x480, 3 levels, batch 3, both windows, bands 1 / 2 / 3 x
 pairs_in_flight 1 / 2 (the write-through instantiations run in the two-stream schedules)."""
 import os
 import sys
@@ -32,6 +34,11 @@ for case in CASES:
         for k in range(ctx.num_layers()):
             w, h = ctx.layer_dims(k)[:2]
             R0, R1 = (ctx.stage_polyexp(ctx.stage_blur_resize(img, k), k) for img in images(case))
+            zero = crc(ctx.stage_update_matrices_from(R0, R1, None, k))
+            if k + 1 < ctx.num_layers():
+                pw, ph = ctx.layer_dims(k + 1)[:2]
+                print(f"initial M {case.name} layer {k} {w}x{h} from {pw}x{ph}: "
+                      f"{crc(ctx.stage_update_matrices_from(R0, R1, smooth_flow(pw, ph), k))}")
             for tag, flow in (("smooth", smooth_flow(w, h)), ("crafted", crafted_flow(w, h))):
                 M = ctx.stage_update_matrices(R0, R1, flow, k)
                 for window in ("box", "gaussian"):
@@ -39,7 +46,7 @@ for case in CASES:
                     f1, M1 = ctx.stage_blur_iter(R0, R1, M, k, True)
                     f0, _ = ctx.stage_blur_iter(R0, R1, M, k, False)
                     print(f"stage {case.name} layer {k} {w}x{h} {sweep_form(w, case.winsize)} {tag} {window}: "
-                          f"flow {crc(f1)} M' {crc(M1)} flow(no update) {crc(f0)}")
+                          f"flow {crc(f1)} M' {crc(M1)} flow(no update) {crc(f0)} M {crc(M)} M(zero flow) {zero}")
                 ctx.set_window("box")
 
 W, H, B = 640, 480, 3
