@@ -1432,18 +1432,19 @@ struct BandRun { float *Ma, *Mb; int kid /* profile class of the sweeps */, J, p
 // step with two initial-M launches running and no sweep, 1.0 ms with one (tools/untraced_anatomy.py).  Shifted by half a band, one
 // stream's initial M does fall into the other's sweeps (3.6 ms per step) -- and the step gets SLOWER: 581 vs 602 pairs/s at 4K, 2 320 vs
 // 2 630 at 1080p (profiles/r04/ab_band_phase.log): the 66 MB a band's initial M streams in from HBM push the sweeping pair's band out
-// of the Infinity Cache (sweep launches 37.1 vs 34.6 ms summed).  The lockstep is worth keeping.  The band arguments above hold for any
+// of the Infinity Cache (sweep launches 37.1 vs 34.6 ms summed).  The lockstep is worth keeping.  (Those figures were taken while bound()
+// divided by 2 (J + 1) instead of 2 J -- a first band of half a band's size and a last one of one and a half; tests/test_gpu_schedule_forms.py
+// now holds the partition to the one described here.)  The band arguments above hold for any
 // monotone sequence of boundaries (a band whose rows have all moved above the image top at a late sweep is empty and skipped; its
 // successor then starts at row 0): bit-identical (tests/test_gpu_flow.py).
 static void sweeps_band_major(mav_ctx* c, hipStream_t st, SweepArgs a, const BandRun& run, const FlowSource* upd)
 {
     const int I = c->fb.iterations, T = blur_iter_tile_rows(a.h), phase = run.phase;
-    int J = run.J;
-    const int NBands = phase ? J + 1 : J;
+    const int J = run.J, NBands = phase ? J + 1 : J;
     auto bound = [&](int j) -> int {                      // first tile row of band j; bound(NBands) = T
         if (j <= 0) return 0;
         if (j >= NBands) return T;
-        if (phase) return (int)((long long)T * (2 * j - 1) / (2 * J));
+        if (phase) return (int)((long long)T * (2 * j - 1) / (2 * J));      // (J = the unshifted partition's count: half a band of ITS size)
         // Sweep `it` shifts every boundary up by `it` tile rows: over a band's sweeps the first band loses (I - 1) / 2 rows on average
         // and the last one gains as many.  Boundaries moved down by that amount give every band the same AVERAGE size -- launches and
         // cache footprints stay even (option "band_skew"; 1080p: first band 38 of 68 tile rows instead of 34; equal split: 0).
@@ -1451,17 +1452,16 @@ static void sweeps_band_major(mav_ctx* c, hipStream_t st, SweepArgs a, const Ban
         const int lo = j, hi = T - (NBands - j);             // at least one tile row per band
         return b < lo ? lo : (b > hi ? hi : b);
     };
-    J = NBands;
-    for (int j = 0; j < J; j++) {
+    for (int j = 0; j < NBands; j++) {
         const int a0 = bound(j), a1 = bound(j + 1);
         if (a1 <= a0) continue;
         if (upd) {
             ProfScope ps(c, K_UPDATE, st);
-            launch_initial_m(st, {a, run.Ma, a.M_stride, a0 == 0 ? 0 : a0 * 16 - 8, j == J - 1 ? a.h : a1 * 16 + 8}, *upd);
+            launch_initial_m(st, {a, run.Ma, a.M_stride, a0 == 0 ? 0 : a0 * 16 - 8, j == NBands - 1 ? a.h : a1 * 16 + 8}, *upd);
         }
         for (int it = 0; it < I; it++) {
             const int update = it < I - 1;
-            int ty0 = a0 - it, ty1 = j == J - 1 ? T : a1 - it;
+            int ty0 = a0 - it, ty1 = j == NBands - 1 ? T : a1 - it;
             if (ty0 < 0) ty0 = 0;
             if (ty1 <= ty0) continue;
             ProfScope ps(c, run.kid, st);

@@ -6,8 +6,9 @@ flow.  Each case below names the forms it is there to reach; tests/test_gpu_stag
 forms from the same predicates the dispatch uses (kernels_flow.hip launch_blur_iter / launch_polyexp / launch_blur_resize /
 launch_initial_m, kernels_window.hip launch_area_resize_flow) and fails when a form of FORMS is no longer reached.
 
-The sibling tables: tests/detect_cases.py (detection path, kernels_detect.hip), tests/sparse_cases.py (sparse path, kernels_lk.hip)
-and tests/window_cases.py (window search, kernels_window.hip).
+The sibling tables: tests/detect_cases.py (detection path, kernels_detect.hip), tests/sparse_cases.py (sparse path, kernels_lk.hip),
+tests/window_cases.py (window search, kernels_window.hip) and tests/schedule_cases.py (the host scheduler's band, stream, strip and
+M-slot forms, mavflow.cpp).
 """
 from __future__ import annotations
 

@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+import schedule_cases as sc
 from mavflow import synth
 from oracle.tolerances import check_flow
 
@@ -336,22 +337,32 @@ def test_double_buffered_uploads_with_different_content(mav):
 def test_band_major_sweeps_are_bit_identical(mav, size):
     """Option "bands": the finest layer's sweeps of a pair in band-major order over skewed horizontal bands (how frames beyond
     the Infinity Cache are swept).  Same tiles, same arithmetic: the flow must equal the sweep-major schedule bit for bit, for
-    one pair per call and for per-pair sweeps inside a batch."""
+    one pair per call and for per-pair sweeps inside a batch.  Every compared call runs on buffers another picture has just gone
+    through (schedule_cases.dirty), and the bands a call really takes are the restated plan's: at 640x480 (30 tile rows, ten sweeps)
+    `bands` = 3 is one band on one stream and two on two streams."""
     from mavflow import _lib
     W, H = size
     prev, nxt = synth.make_batch(W, H, 3, distinct=3)
+    restated = {b: sc.Case(f"{W}x{H}", W, H, b, 10, [], set(), levels=1) for b in (1, 3)}
     with _lib.Context(W, H, 3) as c:
         c.set_option("pairs_in_flight", 1)
         c.set_option("bands", 1)
-        ref = c.farneback(prev, nxt)
-        one = c.farneback(prev[:1], nxt[:1])
+        ref = c.farneback(prev, nxt).copy()
+        one = c.farneback(prev[:1], nxt[:1]).copy()
         for pif in (1, 2):                               # one stream, and two pairs in flight on two streams
             c.set_option("pairs_in_flight", pif)
             for bands in (1, 2, 3):
                 c.set_option("bands", bands)
+                for b in (1, 3):
+                    want = sc.schedule_layers(restated[b], {"pairs_in_flight": pif, "bands": bands})[0][2]
+                    assert c.schedule_info(b)["layers"][0]["bands"] == want, (pif, bands, b, want)
+                    assert want == (bands if H >= 1080 or bands < 3 else 2 if (pif, b) == (2, 3) else 1)
+                sc.dirty(c, W, H, 3)
                 assert np.array_equal(c.farneback(prev, nxt), ref), (pif, bands)
+                sc.dirty(c, W, H, 1)
                 assert np.array_equal(c.farneback(prev[:1], nxt[:1]), one), (pif, bands)
         c.set_option("group", 2)                       # a group of 2 + a group of 1
+        sc.dirty(c, W, H, 3)
         assert np.array_equal(c.farneback(prev, nxt), ref)
 
 
@@ -504,16 +515,21 @@ def test_two_pairs_in_flight_give_the_same_flow(mav, size, batch, group):
         chain = c.process_batch(prev, nxt, smp)
         c.set_option("pairs_in_flight", 2)
         for rep in range(3):
+            sc.dirty(c, W, H, batch)                   # (every compared call on buffers another picture has just gone through)
             out = c.farneback(prev, nxt)
             assert np.array_equal(out, ref), (rep, int((out != ref).sum()))
+        sc.dirty(c, W, H, 3)
         assert np.array_equal(c.farneback(prev[:3], nxt[:3]), ref[:3])
+        sc.dirty(c, W, H, 1)
         assert np.array_equal(c.farneback(prev[:1], nxt[:1]), ref[:1])
+        sc.dirty(c, W, H, batch)
         two = c.process_batch(prev, nxt, smp)
         for key in ("flow", "mask_fixed", "mask_dyn"):
             assert np.array_equal(two[key], chain[key]), key
         assert two["results"].tobytes() == chain["results"].tobytes()
         for wt in (0, 1, -1):                        # the sweeps' M' through plain or write-through (sc1) stores: the same values either way
             c.set_option("sweep_write_through", wt)
+            sc.dirty(c, W, H, batch)
             assert np.array_equal(c.farneback(prev, nxt), ref), wt
         # the profile's interval union: launches of one class overlap, the busy time stays below their sum
         c.profile_enable(True)
@@ -565,10 +581,14 @@ def test_deep_layers_once_per_call_and_banded_coarse_layers_are_bit_identical(ma
             if cb and big:
                 assert info["layers"][1]["sweeps"].startswith("two pairs in flight") and info["layers"][1]["bands"] >= 2, info["layers"][1]
             for rep in range(2):
+                sc.dirty(c, W, H, batch)               # (every compared call on buffers another picture has just gone through)
                 out = c.farneback(prev, nxt)
                 assert np.array_equal(out, ref), (deep, cb, rep, int((out != ref).sum()))
+            sc.dirty(c, W, H, batch)
             assert np.array_equal(c.farneback_sequence(seq), seq_ref), (deep, cb)
+            sc.dirty(c, W, H, 1)
             assert np.array_equal(c.farneback(prev[:1], nxt[:1]), ref[:1])
+            sc.dirty(c, W, H, group + 1)
             assert np.array_equal(c.farneback(prev[:group + 1], nxt[:group + 1]), ref[:group + 1])
         # "band_phase": the second stream's pairs on a partition shifted by half a band (J + 1 bands, the outer two of half size), so that
         # one stream's initial-M launches fall into the other's sweeps; with band_mb = 8 the finest layer has up to 5 bands of 12 tile rows
@@ -576,6 +596,7 @@ def test_deep_layers_once_per_call_and_banded_coarse_layers_are_bit_identical(ma
             c.set_option("band_phase", bp)
             c.set_option("band_mb", mb)
             for rep in range(2):
+                sc.dirty(c, W, H, batch)
                 out = c.farneback(prev, nxt)
                 assert np.array_equal(out, ref), ("band_phase", bp, mb, rep, int((out != ref).sum()))
         c.set_option("band_mb", band_mb)
@@ -584,9 +605,11 @@ def test_deep_layers_once_per_call_and_banded_coarse_layers_are_bit_identical(ma
         # its sweeps; 0 = equal bands, other shifts for the test -- any monotone partition gives the same flow
         for bs in (0, 2, 7, -1):
             c.set_option("band_skew", bs)
+            sc.dirty(c, W, H, batch)
             out = c.farneback(prev, nxt)
             assert np.array_equal(out, ref), ("band_skew", bs, int((out != ref).sum()))
         c.set_option("band_phase", 1)
+        sc.dirty(c, W, H, batch)
         two = c.process_batch(prev, nxt, smp)
         for key in ("flow", "mask_fixed", "mask_dyn"):
             assert np.array_equal(two[key], chain[key]), key

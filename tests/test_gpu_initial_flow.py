@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import initial_flow_ref as ref
+import schedule_cases as sc
 from mavflow import synth
 from oracle import fb_oracle as fbo
 from oracle.tolerances import check_flow
@@ -79,14 +80,21 @@ def test_schedule_options_are_bit_identical_with_an_initial_flow(mav, size, batc
     W, H = size
     prev, nxt = synth.make_batch(W, H, batch, distinct=batch)
     init = _inits(W, H, batch)
+    other = -0.5 * _inits(W, H, batch, seed=40)                      # the start of the picture that dirties the buffers
+
+    def dirty(c, n):                                                   # every compared call on buffers another picture has just gone through
+        sc.dirty(c, W, H, n, call=lambda p, q: c.farneback(p, q, initial_flow=other[:n]))
+
     with _lib.Context(W, H, batch) as c:
         c.set_option("pairs_in_flight", 1)
         c.set_option("group", 1)
         c.set_option("small_batch", 0)
         want = c.farneback(prev, nxt, initial_flow=init).copy()
         c.set_option("small_batch", 1)
+        dirty(c, batch)
         assert np.array_equal(c.farneback(prev, nxt, initial_flow=init), want), "small_batch"
         for b in range(batch):                                         # one pair per call
+            dirty(c, 1)
             assert np.array_equal(c.farneback(prev[b], nxt[b], initial_flow=init[b])[0], want[b]), b
         variants = [dict(group=g, pairs_in_flight=pif) for g in (2, batch) for pif in (1, 2)]
         variants += [dict(group=batch, group_fine=0), dict(group=batch, share_m=0), dict(group=2, deep_batch=0),
@@ -96,6 +104,7 @@ def test_schedule_options_are_bit_identical_with_an_initial_flow(mav, size, batc
         for v in variants:
             for k, val in v.items():
                 c.set_option(k, val)
+            dirty(c, batch)
             got = c.farneback(prev, nxt, initial_flow=init)
             assert np.array_equal(got, want), (v, int((got != want).sum()))
             for k in v:

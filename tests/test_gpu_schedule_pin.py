@@ -1,8 +1,9 @@
 """The host scheduler's launch sequence, pinned: for every case of tests/schedule_pin_cases.py the `mav_schedule_info` string (byte
 for byte) and the (kernel class, stream) of every launch of one `farneback` call in host enqueue order must equal
 tests/golden/schedule_pin.json.  Bit-identical flow (tests/test_gpu_flow.py) cannot see a launch that moved to the other stream or
-changed places with a neighbour; this can.  What it cannot see: which M slot a launch uses, and a band launch's tile-row range (the
-bit-identity tests cover the second).
+changed places with a neighbour; this can.  What it cannot see: which M slot a launch uses, and a band launch's tile-row range.
+tests/test_gpu_schedule_forms.py covers both: the tile-row ranges at every band edge of tests/schedule_cases.py, the M slots under
+buffers another picture has dirtied.
 
 The fixture is a recording (tools/gen_schedule_pin.py).  A change that alters the schedule ON PURPOSE regenerates it with that tool and
 says so; any other difference is a regression.  Timestamps are not compared."""
