@@ -694,6 +694,55 @@ int mav_stage_corner_response(mav_ctx*, const uint8_t* img, int block_size, cons
  * any order, n <= MAV_GFTT_MAX_CANDIDATES.  quality_level and block_size are not used.  The resident frame stays. */
 int mav_stage_corner_pick(mav_ctx*, const uint64_t* keys, int n, const mav_gftt_params*, float* corners, int* count);
 
+/* ---- global-motion subtraction: the homography branch of Processor.run_detection [src/processor.py:286-303] ------------------------
+ * Detector.get_transformation_matrix [src/detector.py:119-151, HOMOGRAPHY] and Detector.flow_vec_subtract [:153-202].
+ *
+ * The fit follows cv2.findHomography(src, dst) with method 0 in structure -- a normalised DLT over all pairs (the eigenvector of the
+ * smallest eigenvalue of the 9x9 LtL by cyclic Jacobi), then at most MAV_HOMOGRAPHY_LM_ITERATIONS Levenberg-Marquardt evaluations on the
+ * reprojection error, H scaled to H[2][2] == 1 -- in float64 with every sum over the pairs taken in index order, so that
+ * tests/global_motion_ref.py reproduces its bytes.  It is NOT pinned against cv2.  ok[b] == 0 and H[b] all zero when
+ * the pairs of item b do not determine a homography (a coordinate without spread, collinear or repeated points) or an entry is not
+ * finite.  n >= 4 pairs per item, the same n for every item; src / dst (batch, n, 2) float64 (x, y); H (batch, 9) float64 row-major. */
+#define MAV_HOMOGRAPHY_LM_ITERATIONS 10
+#define MAV_HOMOGRAPHY_MAX_PAIRS 65536
+int mav_find_homography(mav_ctx*, const double* src, const double* dst, int n, int batch, double* H, int32_t* ok);
+int mav_find_homography_dev(mav_ctx*, const double* src, const double* dst, int n, int batch, double* H, int32_t* ok);   /* enqueue only */
+/* The pairs of [:126-128] from a flow field, then the fit: src = coords, dst = coords + flow[y, x].  flow (batch, H, W, 2) float32;
+ * coords (n, 2) int32 (x, y) inside the frame (host memory in both forms: they are range-checked), shared by the items.
+ * pairs_dst: NULL, or (batch, n, 2) float64 receiving dst (the reference's coords_new). */
+int mav_flow_homography(mav_ctx*, const float* flow, const int32_t* coords, int n, int batch, double* H, int32_t* ok, double* pairs_dst);
+int mav_flow_homography_dev(mav_ctx*, const float* flow, const int32_t* coords, int n, int batch, double* H, int32_t* ok);  /* flow, H, ok: device */
+/* One item of mav_global_motion: the largest residual magnitude and its first position [:180-181], analyze_pyramid's record of the
+ * normalised image (as mav_analyze_pyramid's out) and the window after optimize_window (optimize == 0: analyze_pyramid's own window
+ * x, y, 64, 64 -- all zero when no window scored -- and opt_score 0). */
+typedef struct {
+    float max_mag;
+    int32_t max_row, max_col;
+    int32_t reserved;
+    int64_t window[6];        /* score, x, y, level, argmax_row, argmax_col */
+    int64_t opt_score;
+    int32_t opt_window[4];    /* x, y, w, h */
+} mav_motion_result;
+/* flow_vec_subtract without its renderings.  M (batch, 6) float64 = rows 0 and 1 of the homography, or the 2x3 affine matrix.  Per pixel
+ * global_motion = float32(((m00 x + m01 y) + m02) - x) (float64 inside), warped = global_motion - flow, mag = sqrt(w0 w0 + w1 w1) in
+ * float32; gray = one channel of im_helpers.to_rgb(mag): around((|mag| * 255) / max(mag)) in float32, half to even, all zero when the
+ * maximum is 0; then analyze_pyramid(scale) and, with optimize != 0, optimize_window from its window, on the device image.
+ * warped (batch, H, W, 2) float32, mag (batch, H, W) float32, gray (batch, H, W) u8: optional (NULL).  results (batch).
+ * MAV_ERR_ARG as mav_analyze_pyramid for scale <= 1 or an integer-ratio pyramid level. */
+int mav_global_motion(mav_ctx*, const float* flow, const double* M, int batch, double scale, int optimize, float* warped, float* mag,
+                      uint8_t* gray, mav_motion_result* results);
+int mav_global_motion_dev(mav_ctx*, const float* flow, const double* M, int batch, double scale, int optimize, float* warped, float* mag,
+                          uint8_t* gray, mav_motion_result* results);                                           /* enqueue only */
+/* One iteration of the branch for device-resident flow, enqueue only: gather, fit, subtract, window search; the matrix never visits
+ * the host.  coords: host (n, 2) int32.  H (batch, 9), ok (batch), gray (batch, H, W): optional device outputs; results (batch): device.
+ * An item whose fit failed (ok == 0) gets an all-zero record. */
+int mav_global_motion_step_dev(mav_ctx*, const float* flow, const int32_t* coords, int n, int batch, double scale, int optimize, double* H,
+                               int32_t* ok, uint8_t* gray, mav_motion_result* results);
+/* get_flow_vis of flow_uv_warped and of global_motion [:179,202] for the most recent mav_global_motion(_dev) / mav_global_motion_step_dev
+ * on this context, from its resident flow and matrix: (batch, H, W, 3) u8 BGR each, either may be NULL.  Host outputs, synchronous.
+ * MAV_ERR_STATE under mav_last_render's rules: no such call precedes, its batch differs, or a later call may have overwritten its flow. */
+int mav_last_global_motion_render(mav_ctx*, int batch, uint8_t* img_warped, uint8_t* img_global);
+
 #ifdef __cplusplus
 }
 #endif

@@ -466,6 +466,17 @@ struct mav_ctx {
     uint8_t* pyr_ws = nullptr;                  // analyze_pyramid level images (lazily, max_batch)
     size_t pyr_ws_cap = 0;
     unsigned long long* sat = nullptr;          // optimize_window summed-area tables (lazily, max_batch)
+    // global-motion subtraction (mav_global_motion*, mav_find_homography*): per-item scratch (lazily, max_batch), the pair buffers
+    // (grow-only, pairs_cap = pairs per item they hold) and what the latest call left resident for mav_last_global_motion_render
+    struct Motion {
+        double* H = nullptr; int* ok = nullptr; int64_t* pyr = nullptr; int32_t* win = nullptr; int32_t* opt_win = nullptr;
+        int64_t* opt_score = nullptr; unsigned long long* key = nullptr;      // key: [2 * max_batch] the residual maximum | the window scan
+        uint8_t* gray = nullptr;                                              // the normalised image of a call whose caller does not want it
+        double *src = nullptr, *dst = nullptr, *work = nullptr;
+        int32_t* coords = nullptr;
+        size_t pairs_cap = 0;
+        struct Last { const float* flow = nullptr; const double* M = nullptr; int m_stride = 0; int batch = 0; } last;
+    } gm;
     hipEvent_t t0 = nullptr, t1 = nullptr;
     int profiling = 0;               // 0 off; 1 = HIP events around every launch; 2 = around every RUN of launches of one class on a stream
     struct OpenRun { hipStream_t st; int kid; hipEvent_t a; };
@@ -1766,6 +1777,7 @@ static int farneback_run(mav_ctx* c, const T* prev, const T* next, int batch, co
     }
     c->last_flow = flow;
     c->last_render.batch = 0;        // the flow a previous detection call read may have been overwritten
+    c->gm.last.batch = 0;
     return MAV_OK;
 }
 // bytes per pixel of a MAV_DEPTH_* code; 0 for any other code
@@ -2213,6 +2225,7 @@ struct HostCall {
         c->scratch_next = 0;
         c->last_mf = c->last_md = nullptr; c->last_mask_batch = 0;     // ... and may overwrite the previous call's masks
         c->last_render.batch = 0;                                       // ... and its flow, FoE and sky
+        c->gm.last.batch = 0;                                           // ... and the flow and matrix of a global-motion call
         return MAV_OK;
     }
     int fresh_layer(int k, const Layer** l)      // ... a stage hook on layer k
@@ -2653,6 +2666,191 @@ extern "C" int mav_optimize_window(mav_ctx* c, const uint8_t* img, int batch, co
     CHK(h.staged());
     launch_optimize_window(c->stream, di, batch, c->W, c->H, c->sat, dw, ds, dwo);
     CHK(check_launch("optimize_window"));
+    return h.finish();
+}
+
+// ---- global-motion subtraction: get_transformation_matrix / flow_vec_subtract (include/mavflow.h) ------------------------------------
+static int ensure_render(mav_ctx* c);
+static int ensure_motion(mav_ctx* c)
+{
+    if (c->gm.H) return MAV_OK;
+    const size_t B = (size_t)c->max_batch;
+    return c->mem.alloc_set({{&c->gm.H, sizeof(double) * 9 * B}, {&c->gm.ok, sizeof(int) * B}, {&c->gm.pyr, sizeof(int64_t) * 6 * B},
+                             {&c->gm.win, sizeof(int32_t) * 4 * B}, {&c->gm.opt_win, sizeof(int32_t) * 4 * B},
+                             {&c->gm.opt_score, sizeof(int64_t) * B}, {&c->gm.key, sizeof(unsigned long long) * 2 * B}},
+                            MEM_OTHER, "global-motion scratch");
+}
+// the pair buffers for n pairs per item
+static int ensure_pairs(mav_ctx* c, int n)
+{
+    CHK(ensure_motion(c));
+    if ((size_t)n <= c->gm.pairs_cap) return MAV_OK;
+    c->gm.pairs_cap = 0;
+    const size_t items = (size_t)n * c->max_batch;
+    CHK(grow_buffer(c, &c->gm.src, nullptr, sizeof(double) * 2 * items, MEM_OTHER, READ_ON_COMPUTE, RELEASE_FIRST, "homography pairs"));
+    CHK(grow_buffer(c, &c->gm.dst, nullptr, sizeof(double) * 2 * items, MEM_OTHER, READ_ON_COMPUTE, RELEASE_FIRST, "homography pairs"));
+    CHK(grow_buffer(c, &c->gm.work, nullptr, sizeof(double) * homography_work_doubles(n) * c->max_batch, MEM_OTHER, READ_ON_COMPUTE, RELEASE_FIRST,
+                    "homography workspace"));
+    CHK(grow_buffer(c, &c->gm.coords, nullptr, sizeof(int32_t) * 2 * (size_t)n, MEM_OTHER, READ_ON_COMPUTE, RELEASE_FIRST, "sample coordinates"));
+    c->gm.pairs_cap = (size_t)n;
+    return MAV_OK;
+}
+static int check_pairs(const char* fn, int n)
+{
+    if (n < 4 || n > MAV_HOMOGRAPHY_MAX_PAIRS) return fail(MAV_ERR_ARG, "%s: %d pairs outside [4, %d]", fn, n, MAV_HOMOGRAPHY_MAX_PAIRS);
+    return MAV_OK;
+}
+extern "C" int mav_find_homography_dev(mav_ctx* c, const double* src, const double* dst, int n, int batch, double* H, int32_t* ok)
+{
+    CHK(check_dev_call(c, batch, "mav_find_homography_dev"));
+    if (!src || !dst || !H || !ok) return fail(MAV_ERR_ARG, "mav_find_homography_dev: NULL argument");
+    CHK(check_pairs("mav_find_homography_dev", n));
+    CHK(ensure_pairs(c, n));
+    launch_homography_fit(c->stream, src, dst, n, batch, c->gm.work, H, ok);
+    return check_launch("homography_fit");
+}
+extern "C" int mav_find_homography(mav_ctx* c, const double* src, const double* dst, int n, int batch, double* H, int32_t* ok)
+{
+    HostCall h(c, "mav_find_homography");
+    CHK(h.fresh(batch));
+    if (!src || !dst || !H || !ok) return fail(MAV_ERR_ARG, "mav_find_homography: NULL argument");
+    CHK(check_pairs("mav_find_homography", n));
+    const size_t bytes = sizeof(double) * 2 * (size_t)n * batch;
+    const double *ds = h.in(src, bytes), *dd = h.in(dst, bytes);
+    double* dH = h.out(H, sizeof(double) * 9 * batch);
+    int32_t* dok = h.out(ok, sizeof(int32_t) * batch);
+    CHK(h.staged());
+    CHK(mav_find_homography_dev(c, ds, dd, n, batch, dH, dok));
+    return h.finish();
+}
+// coords (host) range-checked and brought to the context's buffer, then the pairs of `flow` gathered into the context's pair buffers
+static int gather_pairs(mav_ctx* c, const char* fn, const float* flow, const int32_t* coords, int n, int batch)
+{
+    CHK(check_pairs(fn, n));
+    for (int i = 0; i < n; i++)
+        if (coords[2 * i] < 0 || coords[2 * i] >= c->W || coords[2 * i + 1] < 0 || coords[2 * i + 1] >= c->H)
+            return fail(MAV_ERR_ARG, "%s: sample %d = (%d, %d) lies outside the %dx%d frame", fn, i, coords[2 * i], coords[2 * i + 1], c->W, c->H);
+    CHK(ensure_pairs(c, n));
+    HIPCHK(hipMemcpyAsync(c->gm.coords, coords, sizeof(int32_t) * 2 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    launch_pair_gather(c->stream, flow, c->gm.coords, n, batch, c->W, c->H, c->gm.src, c->gm.dst);
+    return check_launch("pair_gather");
+}
+extern "C" int mav_flow_homography_dev(mav_ctx* c, const float* flow, const int32_t* coords, int n, int batch, double* H, int32_t* ok)
+{
+    CHK(check_dev_call(c, batch, "mav_flow_homography_dev"));
+    if (!flow || !coords || !H || !ok) return fail(MAV_ERR_ARG, "mav_flow_homography_dev: NULL argument");
+    CHK(gather_pairs(c, "mav_flow_homography_dev", flow, coords, n, batch));
+    launch_homography_fit(c->stream, c->gm.src, c->gm.dst, n, batch, c->gm.work, H, ok);
+    return check_launch("homography_fit");
+}
+extern "C" int mav_flow_homography(mav_ctx* c, const float* flow, const int32_t* coords, int n, int batch, double* H, int32_t* ok, double* pairs_dst)
+{
+    HostCall h(c, "mav_flow_homography");
+    CHK(h.fresh(batch));
+    if (!flow || !coords || !H || !ok) return fail(MAV_ERR_ARG, "mav_flow_homography: NULL argument");
+    CHK(check_pairs("mav_flow_homography", n));
+    CHK(ensure_pairs(c, n));
+    const float* df = h.in(flow, c->n0 * batch * 2 * sizeof(float));
+    double* dH = h.out(H, sizeof(double) * 9 * batch);
+    int32_t* dok = h.out(ok, sizeof(int32_t) * batch);
+    h.fetch(pairs_dst, c->gm.dst, sizeof(double) * 2 * (size_t)n * batch);
+    CHK(h.staged());
+    CHK(mav_flow_homography_dev(c, df, coords, n, batch, dH, dok));
+    return h.finish();
+}
+// passes A and B, the window search and the records, all on the compute stream.  M: item b's matrix at M + b * m_stride; ok: null, or
+// the fit's flags (a failed item's record is zeroed).
+static int global_motion_enqueue(mav_ctx* c, const char* fn, const float* flow, const double* M, int m_stride, const int* ok, int batch, double scale,
+                                 int optimize, float* warped, float* mag, uint8_t* gray, mav_motion_result* results)
+{
+    if (!flow || !M || !results) return fail(MAV_ERR_ARG, "%s: NULL argument", fn);
+    PyrPlan p;
+    CHK(pyr_plan(c, scale, c->max_batch, &p));
+    CHK(ensure_pyr_ws(c, p));
+    CHK(ensure_motion(c));
+    if (optimize && !c->sat) CHK(c->mem.alloc(&c->sat, sizeof(unsigned long long) * (size_t)(c->W + 1) * (c->H + 1) * c->max_batch, MEM_OTHER, "summed-area tables"));
+    if (!gray) {
+        if (!c->gm.gray) CHK(c->mem.alloc(&c->gm.gray, c->n0 * c->max_batch, MEM_OTHER, "global-motion image"));
+        gray = c->gm.gray;
+    }
+    unsigned long long *kmax = c->gm.key, *kwin = c->gm.key + batch;
+    HIPCHK(hipMemsetAsync(c->gm.key, 0, sizeof(unsigned long long) * 2 * batch, c->stream));
+    launch_motion_pass_a(c->stream, flow, M, m_stride, batch, c->W, c->H, warped, mag, nullptr, kmax);
+    launch_motion_pass_b(c->stream, flow, M, m_stride, batch, c->W, c->H, kmax, gray);
+    build_pyramid(c, p, gray, batch, p.n - 1);
+    for (int l = 0; l < p.n; l++)
+        launch_level_scan(c->stream, l == 0 ? gray : c->pyr_ws + p.off[l], (size_t)p.w[l] * p.h[l], batch, p.w[l], p.h[l], p.base[l], kwin);
+    launch_pyramid_finalize(c->stream, kwin, p, gray, c->pyr_ws, batch, c->gm.pyr);
+    launch_motion_window(c->stream, c->gm.pyr, batch, c->gm.win);
+    if (optimize) launch_optimize_window(c->stream, gray, batch, c->W, c->H, c->sat, c->gm.win, c->gm.opt_score, c->gm.opt_win);
+    launch_motion_pack(c->stream, kmax, c->gm.pyr, c->gm.win, optimize ? c->gm.opt_score : nullptr, optimize ? c->gm.opt_win : nullptr, ok, batch,
+                       c->W, results);
+    CHK(check_launch("global_motion"));
+    c->gm.last.flow = flow; c->gm.last.M = M; c->gm.last.m_stride = m_stride; c->gm.last.batch = batch;
+    return MAV_OK;
+}
+extern "C" int mav_global_motion_dev(mav_ctx* c, const float* flow, const double* M, int batch, double scale, int optimize, float* warped,
+                                     float* mag, uint8_t* gray, mav_motion_result* results)
+{
+    CHK(check_dev_call(c, batch, "mav_global_motion_dev"));
+    return global_motion_enqueue(c, "mav_global_motion_dev", flow, M, 6, nullptr, batch, scale, optimize, warped, mag, gray, results);
+}
+extern "C" int mav_global_motion(mav_ctx* c, const float* flow, const double* M, int batch, double scale, int optimize, float* warped, float* mag,
+                                 uint8_t* gray, mav_motion_result* results)
+{
+    HostCall h(c, "mav_global_motion");
+    CHK(h.fresh(batch));
+    if (!flow || !M || !results) return fail(MAV_ERR_ARG, "mav_global_motion: NULL argument");
+    PyrPlan p;
+    CHK(pyr_plan(c, scale, c->max_batch, &p));           // (before anything is staged)
+    const size_t n = c->n0 * batch;
+    const float* df = h.in(flow, n * 2 * sizeof(float));
+    const double* dM = h.in(M, sizeof(double) * 6 * batch);
+    mav_motion_result* dres = h.out(results, sizeof(mav_motion_result) * batch);
+    float* dw = h.out(warped, n * 2 * sizeof(float));
+    float* dm = h.out(mag, n * sizeof(float));
+    uint8_t* dg = h.out(gray, n);
+    CHK(h.staged());
+    CHK(global_motion_enqueue(c, "mav_global_motion", df, dM, 6, nullptr, batch, scale, optimize, dw, dm, dg, dres));
+    return h.finish();
+}
+extern "C" int mav_global_motion_step_dev(mav_ctx* c, const float* flow, const int32_t* coords, int n, int batch, double scale, int optimize,
+                                          double* H, int32_t* ok, uint8_t* gray, mav_motion_result* results)
+{
+    CHK(check_dev_call(c, batch, "mav_global_motion_step_dev"));
+    if (!flow || !coords || !results) return fail(MAV_ERR_ARG, "mav_global_motion_step_dev: NULL argument");
+    PyrPlan p;
+    CHK(pyr_plan(c, scale, c->max_batch, &p));           // (before anything is enqueued)
+    CHK(gather_pairs(c, "mav_global_motion_step_dev", flow, coords, n, batch));
+    if (!H) H = c->gm.H;
+    if (!ok) ok = c->gm.ok;
+    launch_homography_fit(c->stream, c->gm.src, c->gm.dst, n, batch, c->gm.work, H, ok);
+    return global_motion_enqueue(c, "mav_global_motion_step_dev", flow, H, 9, ok, batch, scale, optimize, nullptr, nullptr, gray, results);
+}
+extern "C" int mav_last_global_motion_render(mav_ctx* c, int batch, uint8_t* img_warped, uint8_t* img_global)
+{
+    if (!c) return fail(MAV_ERR_ARG, "mav_last_global_motion_render: NULL context");
+    if (!c->gm.last.batch || batch != c->gm.last.batch)
+        return fail(MAV_ERR_STATE, "mav_last_global_motion_render: no flow of a %d-item global-motion call is resident", batch);
+    HostCall h(c, "mav_last_global_motion_render");
+    CHK(h.after_last());
+    if (!img_warped && !img_global) return MAV_OK;
+    const size_t n = c->n0 * batch;
+    float* field = h.scratch<float>(n * 2 * sizeof(float));
+    uint8_t *dw = h.out(img_warped, n * 3), *dg = h.out(img_global, n * 3);
+    CHK(h.staged());
+    CHK(ensure_render(c));
+    const DerotParams* derot = nullptr;                  // float32 fields: numpy's float32 arithmetic, i.e. the frame-0 form
+    std::vector<uint8_t> all(batch, 1);
+    CHK(upload_derot(c, nullptr, nullptr, all.data(), batch, true, &derot, c->render_derot));
+    const mav_ctx::Motion::Last& l = c->gm.last;
+    for (int k = 0; k < 2; k++) {
+        uint8_t* img = k == 0 ? dw : dg;
+        if (!img) continue;
+        launch_motion_pass_a(c->stream, l.flow, l.M, l.m_stride, batch, c->W, c->H, k == 0 ? field : nullptr, nullptr, k == 1 ? field : nullptr, nullptr);
+        launch_render_f32(c->stream, field, derot, nullptr, nullptr, batch, c->W, c->H, mav_thr_params{}, c->render_max, nullptr, img, nullptr);
+    }
+    CHK(check_launch("global_motion render"));
     return h.finish();
 }
 

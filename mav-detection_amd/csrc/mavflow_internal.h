@@ -280,3 +280,19 @@ void launch_lk_scharr(hipStream_t st, const uint8_t* pyr, const LkLevels& lv, in
 size_t lk_track_lds_bytes(int win_w, int win_h);
 void launch_lk_track(hipStream_t st, const LkTrackArgs& a);
 void launch_lk_track_err(hipStream_t st, const LkTrackErrArgs& a);
+
+// ---- global-motion subtraction (kernels_motion.hip, compiled with -ffp-contract=off) ----------------------------------------------------
+// src[b][i] = coords[i], dst[b][i] = coords[i] + flow[b][y_i][x_i], (B, n, 2) float64 each; coords (n, 2) int32 (x, y) on the device
+void launch_pair_gather(hipStream_t st, const float* flow, const int32_t* coords, int n, int B, int W, int H, double* src, double* dst);
+// the fit of B items of n pairs: work = homography_work_doubles(n) doubles per item; H (B, 9), ok (B)
+size_t homography_work_doubles(int n);
+void launch_homography_fit(hipStream_t st, const double* src, const double* dst, int n, int B, double* work, double* H, int* ok);
+// M: item b's six entries at M + b * m_stride.  Pass A: key[b] (zeroed by the caller, or null) = (float bits of the largest residual
+// magnitude << 32) | ~(its first pixel index); warped / gm (B, H, W, 2) and mag (B, H, W) float32, each nullable.  Pass B: gray (B, H, W).
+void launch_motion_pass_a(hipStream_t st, const float* flow, const double* M, int m_stride, int B, int W, int H, float* warped, float* mag,
+                          float* gm, unsigned long long* key);
+void launch_motion_pass_b(hipStream_t st, const float* flow, const double* M, int m_stride, int B, int W, int H, const unsigned long long* key,
+                          uint8_t* gray);
+void launch_motion_window(hipStream_t st, const int64_t* pyr, int B, int32_t* win);
+void launch_motion_pack(hipStream_t st, const unsigned long long* key, const int64_t* pyr, const int32_t* win, const int64_t* opt_score,
+                        const int32_t* opt_win, const int* ok, int B, int W, mav_motion_result* out);

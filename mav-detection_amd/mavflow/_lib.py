@@ -57,6 +57,17 @@ class Result(C.Structure):
 RESULT_DTYPE = np.dtype([("box", np.int32, (4,)), ("foe", np.float64, (2,))])
 assert RESULT_DTYPE.itemsize == C.sizeof(Result) == 32
 
+class MotionResult(C.Structure):
+    """mav_motion_result: one item of mav_global_motion."""
+    _fields_ = [("max_mag", C.c_float), ("max_row", C.c_int32), ("max_col", C.c_int32), ("reserved", C.c_int32),
+                ("window", C.c_int64 * 6), ("opt_score", C.c_int64), ("opt_window", C.c_int32 * 4)]
+
+
+MOTION_DTYPE = np.dtype([("max_mag", np.float32), ("max_row", np.int32), ("max_col", np.int32), ("reserved", np.int32),
+                         ("window", np.int64, (6,)), ("opt_score", np.int64), ("opt_window", np.int32, (4,))])
+assert MOTION_DTYPE.itemsize == C.sizeof(MotionResult) == 88
+HOMOGRAPHY_MAX_PAIRS = 65536
+
 # every symbol include/mavflow.h declares (tests check the library exports each of them)
 EXPORTS = [
     "mav_fb_defaults", "mav_foe_defaults", "mav_thr_defaults", "mav_create", "mav_destroy", "mav_last_error",
@@ -84,6 +95,8 @@ EXPORTS = [
     "mav_set_window", "mav_get_window",
     "mav_lk_track_err", "mav_lk_track_err_dev", "mav_corner_score_defaults", "mav_good_features_score", "mav_good_features_score_dev",
     "mav_stage_corner_response",
+    "mav_find_homography", "mav_find_homography_dev", "mav_flow_homography", "mav_flow_homography_dev", "mav_global_motion",
+    "mav_global_motion_dev", "mav_global_motion_step_dev", "mav_last_global_motion_render",
 ]
 
 # Frame depths of the _ex entry points (cv2's depth codes) by numpy dtype.  uint8 frames keep going through the u8 symbols.
@@ -285,6 +298,19 @@ def load(path: str | None = None) -> C.CDLL:
     lib.mav_good_features_score.argtypes = [vp, vp, vp, C.POINTER(GfttParams), C.POINTER(CornerScore), vp, C.POINTER(C.c_int)]
     lib.mav_good_features_score_dev.argtypes = [vp, vp, vp, C.POINTER(GfttParams), C.POINTER(CornerScore), vp, vp]
     lib.mav_stage_corner_response.argtypes = [vp, vp, C.c_int, C.POINTER(CornerScore), vp]
+    # ctx, src, dst, n, batch, H, ok
+    lib.mav_find_homography.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp]
+    lib.mav_find_homography_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp]
+    # ctx, flow, coords, n, batch, H, ok (, pairs_dst)
+    lib.mav_flow_homography.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
+    lib.mav_flow_homography_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp]
+    # ctx, flow, M, batch, scale, optimize, warped, mag, gray, results
+    gm = [vp, vp, vp, C.c_int, C.c_double, C.c_int, vp, vp, vp, vp]
+    lib.mav_global_motion.argtypes = gm
+    lib.mav_global_motion_dev.argtypes = gm
+    # ctx, flow, coords, n, batch, scale, optimize, H, ok, gray, results
+    lib.mav_global_motion_step_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp, vp, vp]
+    lib.mav_last_global_motion_render.argtypes = [vp, C.c_int, vp, vp]
     _lib = lib
     return lib
 
@@ -1004,6 +1030,90 @@ class Context:
         out = np.empty((B, self.H, self.W, 3), np.uint8)
         check(self.lib.mav_flow_to_color(self.h, _ptr(flow), int(f64), B, _ptr(out)))
         return out
+
+    # -- global-motion subtraction (detector.py:119-202) ----------------------------------------------------------------------------
+    def find_homography(self, src, dst):
+        """The fit of cv2.findHomography(src, dst) with method 0 as include/mavflow.h describes it (not pinned against cv2): src, dst
+        (n, 2) or (batch, n, 2) (x, y) -> (H (batch, 3, 3) float64 with H[2, 2] == 1, ok (batch) int32).  ok == 0: the pairs do not
+        determine a homography, H is zero."""
+        src, dst = np.asarray(src, np.float64), np.asarray(dst, np.float64)
+        if src.ndim == 2:
+            src, dst = src[None], dst[None]
+        if src.ndim != 3 or src.shape[2] != 2 or src.shape != dst.shape:
+            raise ValueError(f"find_homography: expected two (batch, n, 2) arrays, got {src.shape} and {dst.shape}")
+        B, n = src.shape[:2]
+        src, dst = np.ascontiguousarray(src), np.ascontiguousarray(dst)
+        H, ok = np.empty((B, 3, 3), np.float64), np.empty(B, np.int32)
+        check(self.lib.mav_find_homography(self.h, _ptr(src), _ptr(dst), n, B, _ptr(H), _ptr(ok)))
+        return H, ok
+
+    @staticmethod
+    def _coords(coords) -> np.ndarray:
+        c = np.asarray(coords)
+        if c.ndim != 2 or c.shape[1] != 2 or not np.issubdtype(c.dtype, np.integer):
+            raise ValueError(f"coords: expected (n, 2) integers (x, y), got {c.dtype} {c.shape}")
+        return np.ascontiguousarray(c, dtype=np.int32)
+
+    def flow_homography(self, flow, coords, want_pairs: bool = False):
+        """Detector.get_transformation_matrix for HOMOGRAPHY (detector.py:126-139): the pairs coords -> coords + flow[y, x] of
+        float32 fields (B, H, W, 2), then find_homography.  -> (H, ok), and with want_pairs the (B, n, 2) float64 coords_new."""
+        flow = np.asarray(flow)
+        flow = flow[None] if flow.ndim == 3 else flow
+        flow = self._flows(flow, flow.shape[0], "flow")
+        coords = self._coords(coords)
+        B, n = flow.shape[0], coords.shape[0]
+        H, ok = np.empty((B, 3, 3), np.float64), np.empty(B, np.int32)
+        pairs = np.empty((B, n, 2), np.float64) if want_pairs else None
+        check(self.lib.mav_flow_homography(self.h, _ptr(flow), _ptr(coords), n, B, _ptr(H), _ptr(ok), _ptr(pairs)))
+        return (H, ok, pairs) if want_pairs else (H, ok)
+
+    MOTION_OUTPUTS = ("warped", "mag", "gray")
+
+    def global_motion(self, flow, M, optimize: bool = False, outputs=("gray",), scale: float = 1.5) -> dict:
+        """Detector.flow_vec_subtract without its renderings (detector.py:164-192) for float32 fields (B, H, W, 2) and matrices M
+        (B, 2 or 3, 3) float64 (rows 0 and 1 are read): dict(results = (B,) MOTION_DTYPE records, and of `outputs` "warped" (B, H, W, 2)
+        float32, "mag" (B, H, W) float32, "gray" (B, H, W) u8 -- one channel of cluster_vis)."""
+        bad = set(outputs) - set(self.MOTION_OUTPUTS)
+        if bad:
+            raise ValueError(f"unknown output(s) {sorted(bad)}; choose from {self.MOTION_OUTPUTS}")
+        flow = np.asarray(flow)
+        flow = flow[None] if flow.ndim == 3 else flow
+        B = flow.shape[0]
+        flow = self._flows(flow, B, "flow")
+        M = np.asarray(M, np.float64)
+        M = M[None] if M.ndim == 2 else M
+        if M.ndim != 3 or M.shape[0] != B or M.shape[1] not in (2, 3) or M.shape[2] != 3:
+            raise ValueError(f"M: expected ({B}, 2 or 3, 3) float64, got {M.shape}")
+        M6 = np.ascontiguousarray(M[:, :2, :])
+        res = np.empty(B, MOTION_DTYPE)
+        out = dict(warped=np.empty((B, self.H, self.W, 2), np.float32) if "warped" in outputs else None,
+                   mag=np.empty((B, self.H, self.W), np.float32) if "mag" in outputs else None,
+                   gray=np.empty((B, self.H, self.W), np.uint8) if "gray" in outputs else None)
+        check(self.lib.mav_global_motion(self.h, _ptr(flow), _ptr(M6), B, scale, int(bool(optimize)), _ptr(out["warped"]), _ptr(out["mag"]),
+                                         _ptr(out["gray"]), _ptr(res)))
+        got = {k: v for k, v in out.items() if v is not None}
+        got["results"] = res
+        return got
+
+    def global_motion_step(self, flow_ptr, coords, batch: int, results_ptr, optimize: bool = False, H_ptr=None, ok_ptr=None, gray_ptr=None,
+                           scale: float = 1.5):
+        """mav_global_motion_step_dev: gather, fit, subtract and window search of device-resident flow, enqueue only.  coords: host
+        (n, 2) integers; the other arguments are device pointers (results: batch MOTION_DTYPE records)."""
+        coords = self._coords(coords)
+        check(self.lib.mav_global_motion_step_dev(self.h, flow_ptr, _ptr(coords), coords.shape[0], int(batch), scale, int(bool(optimize)),
+                                                  H_ptr, ok_ptr, gray_ptr, results_ptr))
+
+    MOTION_IMAGES = ("warped", "global")
+
+    def render_last_global_motion(self, batch: int, images=MOTION_IMAGES) -> dict:
+        """get_flow_vis of flow_uv_warped ("warped") and of global_motion ("global") for the most recent global_motion /
+        global_motion_step call, from its resident flow and matrix: (batch, H, W, 3) u8 BGR each."""
+        bad = set(images) - set(self.MOTION_IMAGES)
+        if bad:
+            raise ValueError(f"unknown image(s) {sorted(bad)}; choose from {self.MOTION_IMAGES}")
+        out = {k: (np.empty((batch, self.H, self.W, 3), np.uint8) if k in images else None) for k in self.MOTION_IMAGES}
+        check(self.lib.mav_last_global_motion_render(self.h, int(batch), _ptr(out["warped"]), _ptr(out["global"])))
+        return {k: v for k, v in out.items() if v is not None}
 
     def colormap_jet(self, gray) -> np.ndarray:
         """cv2.applyColorMap(gray, COLORMAP_JET) of a u8 array of any shape -> shape + (3,) BGR."""

@@ -1,6 +1,7 @@
-"""Detector -- the Algorithm switch, IMU derotation and the window search (analyze_pyramid, optimize_window) of the
-reference's Detector (/root/reference/src/detector.py:14-117,280-358,430-433) on libmavflow.  The homography / affine / essential-matrix
-branches (cv2 RANSAC estimators, dead in run_detection) are not part of the hot path."""
+"""Detector -- the Algorithm switch, IMU derotation, the window search (analyze_pyramid, optimize_window) and the global-motion
+branch (get_transformation_matrix for HOMOGRAPHY, flow_vec_subtract) of the reference's Detector (src/detector.py:14-202,280-358,
+430-433) on libmavflow.  The affine / fundamental / essential-matrix estimators (cv2 RANSAC with a private RNG, unreachable from
+run_detection) are not reproduced: get_transformation_matrix says so; flow_vec_subtract takes a user-set .aff as the reference does."""
 from __future__ import annotations
 
 from enum import Enum
@@ -9,7 +10,10 @@ from typing import Any, Tuple
 import numpy as np
 
 from . import im_helpers, utils
+from ._lib import MOTION_DTYPE as _MOTION_DTYPE, check as _lib_check
 from .frame_result import FrameResult
+
+_MOTION_BYTES = _MOTION_DTYPE.itemsize
 
 
 class LucasKanade:
@@ -97,6 +101,12 @@ class Detector:
         self.fov = 90
         self.focal_length = 1 / np.tan(np.deg2rad(self.fov) / 2)
         self.frame_result = FrameResult()
+        self.use_optimization = False
+        self._gm_dev = None              # (context, device buffers) of the calls that take a device-resident flow field
+
+    def get_gradient_and_magnitude(self, frame: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """Polar form of a cartesian flow field (detector.py:53-63): (magnitude, angle)."""
+        return np.sqrt(frame[..., 0] ** 2.0 + frame[..., 1] ** 2.0), np.arctan2(frame[..., 1], frame[..., 0])
 
     def derotate(self, previous_frame_index: int, current_frame_index: int, flow_uv: np.ndarray) -> np.ndarray:
         """Subtract the rotational flow predicted from the IMU rates; float64 out.  Frame 0 is returned untouched."""
@@ -143,6 +153,19 @@ class Detector:
             return a, np.ascontiguousarray(a[..., 0]), 1
         return a, a, 3
 
+    @staticmethod
+    def _window_tuple(ctx, record, gray: np.ndarray, three: bool) -> Tuple[float, utils.Rectangle, np.ndarray, Any]:
+        """analyze_pyramid's 4-tuple from the device's record (score, x, y, level, argmax row, argmax col) of the u8 image `gray`;
+        three: the image handed in had three (equal) channels."""
+        score, x, y, level, ay, ax = (int(v) for v in record)
+        if score == 0:
+            return (0, utils.Rectangle((0, 0), (0, 0)), np.zeros(0), 0)
+        lv = gray if level == 0 else ctx.pyramid_level(gray, level)
+        window = lv[y:y + 64, x:x + 64]
+        if three:
+            window = np.repeat(window[..., None], 3, axis=2)
+        return (score // (1 if three else 3), utils.Rectangle((x, y), (64, 64)), window, (ay, ax, 0) if three else (ay, ax))
+
     def analyze_pyramid(self, img: np.ndarray) -> Tuple[float, utils.Rectangle, np.ndarray, Any]:
         """Highest-sum 64x64 window (stride 16, first maximum wins) over every pyramid level (scale 1.5, INTER_AREA).
         Returns (score, Rectangle, window, argmax inside the window) like the reference (detector.py:280-312): the
@@ -150,14 +173,7 @@ class Detector:
         a, gray, mult = self._gray_of(img, "analyze_pyramid")
         H, W = gray.shape
         ctx = im_helpers._ctx(W, H)
-        score, x, y, level, ay, ax = (int(v) for v in ctx.analyze_pyramid(gray)[0])
-        if score == 0:
-            return (0, utils.Rectangle((0, 0), (0, 0)), np.zeros(0), 0)
-        lv = gray if level == 0 else ctx.pyramid_level(gray, level)
-        window = lv[y:y + 64, x:x + 64]
-        if a.ndim == 3:
-            window = np.repeat(window[..., None], 3, axis=2)
-        return (score // mult, utils.Rectangle((x, y), (64, 64)), window, (ay, ax, 0) if a.ndim == 3 else (ay, ax))
+        return self._window_tuple(ctx, ctx.analyze_pyramid(gray)[0], gray, a.ndim == 3)
 
     def optimize_window(self, mag_img: np.ndarray, window: utils.Rectangle) -> Tuple[float, utils.Rectangle]:
         """Greedy corner walk of detector.py:314-358 (the window grows / shrinks while the enclosed sum rises)."""
@@ -170,6 +186,141 @@ class Detector:
             return (0.0, window)
         x, y, w, h = (int(v) for v in out[0])
         return (float(int(score[0]) // mult), utils.Rectangle.from_points((x, y), (x + w, y + h)))
+
+    # -- global-motion subtraction (detector.py:119-202) ----------------------------------------------------------------------------
+    def _device_flow(self, flow_uv):
+        """(context, device pointer) of a float32 flow handle from the flow seam that is still on the device, else None."""
+        from . import pipeline
+        if not (isinstance(flow_uv, pipeline.DeviceArray) and flow_uv.on_device and flow_uv.dtype == np.float32 and flow_uv.ctx.alive):
+            return None
+        if flow_uv._deferred is not None:              # the flow stage has not enqueued it yet
+            flow_uv._deferred.flush()
+        return flow_uv.ctx, flow_uv.ptr
+
+    def _dev_buffers(self, ctx) -> dict:
+        """Device buffers (on the flow's context) of the calls that take a device-resident field: allocated once per context."""
+        if self._gm_dev is None or self._gm_dev[0] is not ctx:
+            self._free_dev_buffers()
+            n0 = ctx.W * ctx.H
+            sizes = dict(H=72, ok=4, M=48, res=_MOTION_BYTES, gray=n0, warped=8 * n0, mag=4 * n0)
+            self._gm_dev = (ctx, {k: ctx.alloc(v) for k, v in sizes.items()})
+        return self._gm_dev[1]
+
+    def _free_dev_buffers(self) -> None:
+        if self._gm_dev is not None:
+            ctx, bufs = self._gm_dev
+            self._gm_dev = None
+            if ctx.alive:
+                for b in bufs.values():
+                    b.free()
+
+    def get_transformation_matrix(self, orig_frame: np.ndarray, flow_uv: np.ndarray) -> None:
+        """The homography of detector.py:119-139: 1000 sampled pairs coords -> coords + flow[y, x] (or, with use_sparse_of, the
+        Lucas-Kanade tracks of orig_frame when there are any), fitted on the device in the structure of cv2.findHomography's method 0
+        (Context.find_homography: not pinned against cv2).  Sets .homography (3x3 float64) and .confidence (the all-ones inlier mask,
+        (n, 1) uint8); RuntimeError when the pairs determine no homography.  flow_uv: a host array or the flow seam's device handle."""
+        A = Detector.Algorithm
+        if self.algorithm in (A.AFFINE, A.FUNDAMENTAL, A.ESSENTIAL):
+            raise NotImplementedError(
+                f"{self.algorithm.name}: cv2.estimateAffine2D / findFundamentalMat / findEssentialMat are RANSAC estimators driven by "
+                "OpenCV's private RNG; they are not reproduced (run_detection reaches HOMOGRAPHY only)")
+        if self.algorithm != A.HOMOGRAPHY:
+            return
+        W, H = self.dataset.capture_size[0], self.dataset.capture_size[1]
+        pairs = None
+        if self.use_sparse_of:
+            old, new, _ = self.lucas_kanade.get_features(orig_frame)
+            if len(old) > 0 and len(new) > 0:
+                pairs = (np.asarray(old, np.float64), np.asarray(new, np.float64))
+                logger = getattr(self.dataset, "logger", None)
+                if logger is not None:
+                    logger.info(f"features: {len(new)}")
+        dev = None if pairs is not None else self._device_flow(flow_uv)
+        if pairs is not None:
+            Hm, ok = im_helpers._ctx(W, H).find_homography(*pairs)
+            n = len(pairs[0])
+        elif dev is not None:
+            ctx, ptr = dev
+            b = self._dev_buffers(ctx)
+            coords = ctx._coords(self.coords)
+            _lib_check(ctx.lib.mav_flow_homography_dev(ctx.h, ptr, coords.ctypes.data, coords.shape[0], 1, b["H"].ptr, b["ok"].ptr))
+            Hm, ok = b["H"].download(np.float64, (1, 3, 3)), b["ok"].download(np.int32, (1,))
+            n = coords.shape[0]
+        else:
+            flow = np.asarray(flow_uv)
+            n = self.coords.shape[0]
+            if flow.dtype == np.float32:
+                Hm, ok = im_helpers._ctx(W, H).flow_homography(flow, self.coords)
+            else:                                       # a float64 field keeps its precision: the reference's own pair arithmetic
+                new = self.coords.astype(np.float64) + flow[self.sample_y, self.sample_x]
+                Hm, ok = im_helpers._ctx(W, H).find_homography(self.coords.astype(np.float64), new)
+        if not int(ok[0]):
+            raise RuntimeError("get_transformation_matrix: the point pairs do not determine a homography")
+        self.homography = np.array(Hm[0])
+        self.confidence = np.ones((n, 1), np.uint8)
+
+    def flow_vec_subtract(self, orig_frame: np.ndarray, flow_uv: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """detector.py:153-202: the motion the matrix predicts (.homography for HOMOGRAPHY, else a user-set .aff) is subtracted from
+        the field, the residual's magnitude becomes cluster_vis and the window search runs on it (optimize_window too with
+        .use_optimization).  A float32 field -- host array or the flow seam's device handle -- goes through mav_global_motion; any other
+        dtype takes the reference's numpy arithmetic on the host, as derotate does.  Returns (get_flow_vis(flow_uv_warped),
+        cluster_vis, to_rgb(magnitude), get_flow_vis(global_motion)) and sets flow_uv_warped, flow_uv_warped_mag, flow_max, cluster_vis,
+        opt_window, iou, flow_uv_warped_vis, prev_frame, frame_result."""
+        self.frame_result = FrameResult()
+        M = np.asarray(self.homography if self.algorithm == Detector.Algorithm.HOMOGRAPHY else self.aff, np.float64)
+        W, H = self.dataset.capture_size[0], self.dataset.capture_size[1]
+        dev = self._device_flow(flow_uv)
+        host = None if dev is not None else np.asarray(flow_uv)
+        if dev is None and host.dtype != np.float32:
+            x_coords = np.tile(np.arange(W), (H, 1))
+            y_coords = np.tile(np.arange(H), (W, 1)).T
+            global_motion = np.zeros_like(host)
+            global_motion[..., 0] = M[0, 0] * x_coords + M[0, 1] * y_coords + M[0, 2] - x_coords
+            global_motion[..., 1] = M[1, 0] * x_coords + M[1, 1] * y_coords + M[1, 2] - y_coords
+            self.flow_uv_warped = global_motion - host
+            flow_uv_warped_vis = im_helpers.get_flow_vis(self.flow_uv_warped)
+            self.flow_uv_warped_mag = np.sqrt(self.flow_uv_warped[..., 0] ** 2.0 + self.flow_uv_warped[..., 1] ** 2.0)
+            self.flow_max = np.unravel_index(self.flow_uv_warped_mag.argmax(), self.flow_uv_warped_mag.shape)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                self.cluster_vis = im_helpers.to_rgb(self.flow_uv_warped_mag)
+            self.opt_window = self.analyze_pyramid(self.cluster_vis)
+            window_optimized = self.opt_window[1]
+            if self.use_optimization:
+                window_optimized = self.optimize_window(self.cluster_vis, self.opt_window[1])[1]
+            global_motion_vis = im_helpers.get_flow_vis(global_motion)
+        else:
+            if dev is not None:
+                ctx, ptr = dev
+                b = self._dev_buffers(ctx)
+                b["M"].upload(np.ascontiguousarray(M[:2, :]))
+                _lib_check(ctx.lib.mav_global_motion_dev(ctx.h, ptr, b["M"].ptr, 1, 1.5, int(bool(self.use_optimization)), b["warped"].ptr,
+                                                         b["mag"].ptr, b["gray"].ptr, b["res"].ptr))
+                imgs = ctx.render_last_global_motion(1)
+                rec = b["res"].download(_MOTION_DTYPE, (1,))[0]
+                gray = b["gray"].download(np.uint8, (H, W))
+                self.flow_uv_warped = b["warped"].download(np.float32, (H, W, 2))
+                self.flow_uv_warped_mag = b["mag"].download(np.float32, (H, W))
+            else:
+                ctx = im_helpers._ctx(W, H)
+                out = ctx.global_motion(host, M, optimize=self.use_optimization, outputs=("warped", "mag", "gray"))
+                imgs = ctx.render_last_global_motion(1)
+                rec, gray = out["results"][0], out["gray"][0]
+                self.flow_uv_warped, self.flow_uv_warped_mag = out["warped"][0], out["mag"][0]
+            flow_uv_warped_vis, global_motion_vis = imgs["warped"][0], imgs["global"][0]
+            self.flow_max = (int(rec["max_row"]), int(rec["max_col"]))
+            self.cluster_vis = np.repeat(gray[..., None], 3, axis=2)
+            self.opt_window = self._window_tuple(ctx, rec["window"], gray, True)
+            x, y, w, h = (int(v) for v in rec["opt_window"])
+            window_optimized = utils.Rectangle.from_points((x, y), (x + w, y + h)) if self.use_optimization else self.opt_window[1]
+        if self.use_optimization:
+            opt_window_list = list(self.opt_window)
+            opt_window_list[1] = window_optimized
+            self.opt_window = tuple(opt_window_list)
+        for gt in getattr(self.dataset, "ground_truth", []):
+            self.iou = utils.Rectangle.calculate_iou(window_optimized, gt)
+        self.flow_uv_warped_vis = flow_uv_warped_vis
+        self.prev_frame = orig_frame
+        return flow_uv_warped_vis, self.cluster_vis, self.cluster_vis.copy(), global_motion_vis
 
     def is_homography_based(self) -> bool:
         return self.algorithm in [Detector.Algorithm.HOMOGRAPHY]

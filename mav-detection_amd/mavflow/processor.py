@@ -1,4 +1,5 @@
-"""Processor -- the detection loop of /root/reference/src/processor.py:277-396 (FoE branch) on libmavflow.
+"""Processor -- the detection loop of /root/reference/src/processor.py:277-396 on libmavflow: the FoE branch (:304-394) and, with
+Processor(algorithm=Detector.Algorithm.HOMOGRAPHY), the global-motion branch (:286-303, see run_detection).
 
 run_detection() keeps the reference's shape: one frame index at a time, the same order of operations
 (:305-341), the same FrameResult fields (:353-362); run_detection_staged() is that loop through the reference-named
@@ -21,7 +22,8 @@ the same pixels, their bytes differ.  The staged loop always encodes on the host
 FoE discs on the frame, the fixed mask painted purple, blended 0.2 / 0.8) as `{processed_path}/image_{i:05d}.png` for every frame the
 reference would write (np.sum(result_img) > 0); the fast loops render it on the device from the resident mask and FoE
 (mav_last_overlay), the staged loop composes it from draw_FoE, the painted mask and add_weighted.  No video container is encoded: the
-reference's etc/bash/pngs_to_mp4.sh turns the sequence into the mp4.  The homography branch is not reproduced."""
+reference's etc/bash/pngs_to_mp4.sh turns the sequence into the mp4.  The global-motion branch writes cluster_vis there instead
+(:303), encoded on the host, and neither JSON nor result images, as the reference's does outside debug mode."""
 from __future__ import annotations
 
 import json
@@ -157,6 +159,15 @@ class SyntheticDataset:
     def get_angular_difference(self, a: int, b: int) -> np.ndarray:
         return self.dangle
 
+    @property
+    def ground_truth(self):
+        """The moving patch's rectangle (dataset.py: ground_truth, what get_annotation fills in): one box for every frame."""
+        W, H = self.capture_size
+        return [utils.Rectangle((W // 4, H // 4), (24, 24))]
+
+    def get_annotation(self, i: int) -> None:
+        """Nothing to read: ground_truth is constant."""
+
     def release(self) -> None:
         if self._stage is not None:
             self._stage.close()
@@ -179,7 +190,7 @@ def _write_stream(path: str, stream) -> None:
 
 class Processor:
     def __init__(self, config: RunConfig, results_path: Optional[str] = None, images_path: Optional[str] = None,
-                 processed_path: Optional[str] = None, png_encoder: str = "host") -> None:
+                 processed_path: Optional[str] = None, png_encoder: str = "host", algorithm: Optional["Detector.Algorithm"] = None) -> None:
         if png_encoder not in ("host", "device"):
             raise ValueError(f"png_encoder must be 'host' or 'device', got {png_encoder!r}")
         self.png_encoder = png_encoder
@@ -189,8 +200,12 @@ class Processor:
         self.debug_mode = config.debug
         self.headless = config.headless
         self.dataset = config.get_dataset()
-        self.detector = Detector(self.dataset)
+        self.detector = Detector(self.dataset, algorithm)           # None: the reference's default, which takes the FoE branch
         self.detection_results: Dict[int, FrameResult] = dict()
+        # extras of the global-motion branch: every frame's (optimised) window and its IoU with the last ground-truth box
+        self.detection_windows: Dict[int, utils.Rectangle] = dict()
+        self.detection_iou: Dict[int, float] = dict()
+        self._gm_bufs = None                             # (context, device buffers) of the global-motion step
         # extra: get_simple_bounding_box of every frame's fixed mask, which the device records with the FoE (the reference derives no
         # box in this loop; FrameResult and its JSON stay exactly the reference's)
         self.detection_boxes: Dict[int, utils.Rectangle] = dict()
@@ -409,6 +424,8 @@ class Processor:
         pipeline has lanes (pipeline.auto_lanes: 3 - 4 contexts taken in turn for frames up to 1080p, whose one-pair chains of launches
         then interleave on the GPU) -- have been enqueued; results, files and their order are those of the plain loop."""
         from collections import deque
+        if self.detector.is_homography_based():
+            return self._run_global_motion()
         pending = deque()
 
         def finish(n_keep: int) -> None:
@@ -454,6 +471,91 @@ class Processor:
         self._flush_images()
         return self.detection_results
 
+    # -- the global-motion branch (processor.py:286-303) ----------------------------------------------------------------------------
+    def _run_global_motion(self) -> Dict[int, FrameResult]:
+        """processor.py:286-303 outside debug mode, one frame at a time: the flow from the dataset's seam, then
+        get_transformation_matrix -> flow_vec_subtract as ONE enqueue (mav_global_motion_step_dev: pair gather, homography fit,
+        subtraction, normalised image, window search, optimize_window with detector.use_optimization) on the context that holds the
+        flow -- a device handle is not moved, a host field crosses PCIe once, the matrix never visits the host before the record does.
+        Back come the 88-byte record, the matrix and, with a processed_path, the u8 image: cluster_vis is written there as
+        image_{i:05d}.png, the reference's write(cluster_vis).  Sets detector.homography / confidence / flow_max / iou (and
+        cluster_vis when it is fetched) per frame, detection_windows[i] and detection_iou[i]; the returned dict is empty, as the reference's is outside debug
+        mode.  A field that is not float32 goes through the Detector's two calls (host float64 arithmetic).  flow_vis (:288) is formed
+        in debug mode only, which this branch does not reproduce."""
+        if self.debug_mode:
+            raise NotImplementedError("debug_mode in the global-motion branch draws with cv2.rectangle and writes a six-image mosaic "
+                                      "(processor.py:295-301): not reproduced")
+        det = self.detector
+        W, H = self.dataset.capture_size
+        while self.is_active():
+            i = self.frame_index
+            orig_frame = self.dataset.get_frame()
+            self.flow_uv = self.dataset.get_flow_uv(i)
+            if self.flow_uv is None:
+                raise ValueError("Could not load flow field.")
+            self.dataset.get_annotation(i)
+            dev = det._device_flow(self.flow_uv)
+            if dev is None and np.asarray(self.flow_uv).dtype != np.float32:
+                det.get_transformation_matrix(orig_frame, self.flow_uv)
+                _, cluster_vis, _, _ = det.flow_vec_subtract(orig_frame, self.flow_uv)
+                window = det.opt_window[1]
+            else:
+                ctx, ptr = dev if dev is not None else (self._own_ctxs(1, 1)[0], None)
+                b = self._global_motion_buffers(ctx)
+                if ptr is None:
+                    ptr = b["flow"].upload(np.ascontiguousarray(self.flow_uv, dtype=np.float32)).ptr
+                if det.use_sparse_of:                    # the pairs come from the tracker (host), the rest stays one call
+                    det.get_transformation_matrix(orig_frame, self.flow_uv)
+                    b["M"].upload(np.ascontiguousarray(det.homography[:2, :]))
+                    _lib.check(ctx.lib.mav_global_motion_dev(ctx.h, ptr, b["M"].ptr, 1, 1.5, int(bool(det.use_optimization)), None, None,
+                                                             b["gray"].ptr, b["res"].ptr))
+                else:
+                    ctx.global_motion_step(ptr, det.coords, 1, b["res"].ptr, optimize=det.use_optimization, H_ptr=b["H"].ptr,
+                                           ok_ptr=b["ok"].ptr, gray_ptr=b["gray"].ptr)
+                    if not int(b["ok"].download(np.int32, (1,))[0]):
+                        raise RuntimeError(f"frame {i}: the sampled flow vectors do not determine a homography")
+                    det.homography = b["H"].download(np.float64, (3, 3))
+                    det.confidence = np.ones((det.coords.shape[0], 1), np.uint8)
+                rec = b["res"].download(_lib.MOTION_DTYPE, (1,))[0]
+                det.flow_max = (int(rec["max_row"]), int(rec["max_col"]))
+                x, y, w, h = (int(v) for v in rec["opt_window"])
+                window = utils.Rectangle.from_points((x, y), (x + w, y + h))
+                cluster_vis = None
+                if self.processed_path is not None:
+                    cluster_vis = np.repeat(b["gray"].download(np.uint8, (H, W))[..., None], 3, axis=2)
+                    det.cluster_vis = cluster_vis
+                for gt in self.dataset.ground_truth:
+                    det.iou = utils.Rectangle.calculate_iou(window, gt)
+                det.prev_frame = orig_frame
+            self.detection_windows[i] = window
+            if hasattr(det, "iou"):
+                self.detection_iou[i] = det.iou
+            if self.processed_path is not None:
+                self._queue_png(self.processed_path, i, cluster_vis)
+            self.frame_index += 1
+        self._flush_images()
+        return self.detection_results
+
+    def _global_motion_buffers(self, ctx) -> dict:
+        if self._gm_bufs is None or self._gm_bufs[0] is not ctx:
+            self._free_global_motion_buffers()
+            n0 = ctx.W * ctx.H
+            sizes = dict(res=_lib.MOTION_DTYPE.itemsize, H=72, ok=4, M=48, gray=n0, flow=8 * n0)
+            self._gm_bufs = (ctx, {k: ctx.alloc(v) for k, v in sizes.items()})
+        return self._gm_bufs[1]
+
+    def _free_global_motion_buffers(self) -> None:
+        if self._gm_bufs is not None:
+            ctx, bufs = self._gm_bufs
+            self._gm_bufs = None
+            if ctx.alive:
+                for buf in bufs.values():
+                    buf.free()
+
+    def _no_global_motion(self, what: str) -> None:
+        if self.detector.is_homography_based():
+            raise NotImplementedError(f"{what} runs the FoE branch only; the global-motion branch (algorithm HOMOGRAPHY) is run_detection()")
+
     @property
     def _renders(self) -> bool:
         """Images or processed frames are rendered from what a step left resident: the loops finish each step before the next."""
@@ -477,6 +579,7 @@ class Processor:
         """The same loop through the reference-named calls one by one (Detector.derotate, get_FOE_dense, the masks): every call
         ships its arrays across PCIe, as a maintainer who only swaps the imports would get.  Kept as the parity check of
         those shims; run_detection() is the fast form."""
+        self._no_global_motion("run_detection_staged")
         while self.is_active():
             i = self.frame_index
             orig_frame = self.dataset.get_frame()
@@ -523,6 +626,7 @@ class Processor:
         dataset's arrays and cross PCIe, and batch k - 1's FrameResults are filled in.  Needs a dataset that hands out frame pairs
         (frame_pair(i)).  The sample coordinates are drawn per frame in frame order, as get_FOE_dense draws them."""
         from collections import deque
+        self._no_global_motion("run_detection_batched")
         W, H = self.dataset.capture_size
         idx = list(range(self.frame_index, self.dataset.N - 1))
         # small batches (one pair at 720p / 1080p ...) are spread over 2 - 3 contexts taken in turn; a big batch keeps two pairs in
@@ -578,6 +682,8 @@ class Processor:
         if self._png_pool is not None:
             self._png_pool.shutdown()
             self._png_pool = None
+        self._free_global_motion_buffers()
+        self.detector._free_dev_buffers()
         self._close_pipes()
         for c in self._ctxs:
             c.close()
