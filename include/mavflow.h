@@ -738,8 +738,18 @@ int mav_global_motion_dev(mav_ctx*, const float* flow, const double* M, int batc
  * An item whose fit failed (ok == 0) gets an all-zero record. */
 int mav_global_motion_step_dev(mav_ctx*, const float* flow, const int32_t* coords, int n, int batch, double scale, int optimize, double* H,
                                int32_t* ok, uint8_t* gray, mav_motion_result* results);
-/* get_flow_vis of flow_uv_warped and of global_motion [:179,202] for the most recent mav_global_motion(_dev) / mav_global_motion_step_dev
- * on this context, from its resident flow and matrix: (batch, H, W, 3) u8 BGR each, either may be NULL.  Host outputs, synchronous.
+/* processor.py:286-303 for `batch` frame pairs as one call: Farneback(prev, next) -> pairs at coords -> homography fit ->
+ * subtraction -> normalised image -> analyze_pyramid (-> optimize_window).  prev / next as in mav_farneback (the frame-sequence
+ * layout next == prev + W*H is recognised; the context's window is followed); coords (n, 2) int32 host, range-checked, shared
+ * by the items; scale / optimize / results / gray / H / ok as in mav_global_motion_step_dev.  flow: optional (batch, H, W, 2)
+ * float32 output (NULL: the context's own flow buffer, mav_last_flow_dev reports it).  Every argument is checked before anything
+ * is enqueued.  mav_last_global_motion_render works after it as after the step. */
+int mav_global_motion_batch(mav_ctx*, const uint8_t* prev, const uint8_t* next, const int32_t* coords, int n, int batch, double scale,
+                            int optimize, float* flow, double* H, int32_t* ok, uint8_t* gray, mav_motion_result* results);      /* host pointers, synchronous */
+int mav_global_motion_batch_dev(mav_ctx*, const uint8_t* prev, const uint8_t* next, const int32_t* coords, int n, int batch, double scale,
+                                int optimize, float* flow, double* H, int32_t* ok, uint8_t* gray, mav_motion_result* results);  /* device pointers except coords; enqueue only */
+/* get_flow_vis of flow_uv_warped and of global_motion [:179,202] for the most recent mav_global_motion(_dev) / mav_global_motion_step_dev /
+ * mav_global_motion_batch(_dev) on this context, from its resident flow and matrix: (batch, H, W, 3) u8 BGR each, either may be NULL.  Host outputs, synchronous.
  * MAV_ERR_STATE under mav_last_render's rules: no such call precedes, its batch differs, or a later call may have overwritten its flow. */
 int mav_last_global_motion_render(mav_ctx*, int batch, uint8_t* img_warped, uint8_t* img_global);
 

@@ -29,17 +29,31 @@ void launch_pair_gather(hipStream_t st, const float* flow, const int32_t* coords
 // ---- homography fit ----------------------------------------------------------------------------------------------------------
 // One workgroup per batch item.  Sums over the points run in plain index order with one accumulator per matrix entry (a thread
 // per entry); the per-point terms they add are computed by all threads into `work` (global memory: n is not bounded by the LDS).
-// The 9x9 / 8x8 eigen-decompositions are serial (thread 0).  Every loop has a fixed bound.
+// The 9x9 / 8x8 eigen-decompositions run on wave 0 alone, a rotation's element updates spread over lanes 0 .. n - 1 (jacobi_eigen); the
+// other waves wait at the next workgroup barrier.  Every loop has a fixed bound.
 #define FIT_THREADS 256
 #define JACOBI_SWEEPS 30
 #define LM_ITERATIONS 10
 #define RANK_RATIO 1e-12
 
-// Cyclic Jacobi on the symmetric n x n matrix A (row stride 9): eigenvalues on the diagonal, eigenvectors as columns of V.
-__device__ static void jacobi_eigen(double* A, double* V, int n)
+// Wave-scope ordering point between LDS writes of some lanes and LDS reads of others.  One wavefront issues its LDS instructions in
+// order, so what is needed is that the compiler neither moves an access across this point nor keeps an LDS value in a register over it.
+__device__ __forceinline__ void wave_sync()
 {
-    for (int i = 0; i < n; i++)
-        for (int j = 0; j < n; j++) V[i * 9 + j] = i == j ? 1.0 : 0.0;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// Cyclic Jacobi on the symmetric n x n matrix A (row stride 9): eigenvalues on the diagonal, eigenvectors as columns of V.  Called by
+// every lane of ONE wavefront (lane = 0 .. 63), A and V in LDS.  Every lane evaluates the off-diagonal sum and a rotation's apq, theta,
+// t, c, s from the same LDS values (broadcast reads), so every decision is wave-uniform; lane k < n then carries the element updates:
+// row k of the column update and row k of V (independent of each other), and, after an ordering point, column k of the row update,
+// which reads what the column update wrote.  Every expression is the serial loop's: tests/global_motion_ref.py, same bytes.
+__device__ static void jacobi_eigen(double* A, double* V, int n, int lane)
+{
+    if (lane < n)
+        for (int j = 0; j < n; j++) V[lane * 9 + j] = lane == j ? 1.0 : 0.0;
+    wave_sync();
     for (int sweep = 0; sweep < JACOBI_SWEEPS; sweep++) {
         double off = 0.0;
         for (int p = 0; p < n - 1; p++)
@@ -51,25 +65,29 @@ __device__ static void jacobi_eigen(double* A, double* V, int n)
                 if (apq == 0.0) continue;
                 const double g = 100.0 * fabs(apq), app = A[p * 9 + p], aqq = A[q * 9 + q];
                 if (sweep > 3 && fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq)) {
-                    A[p * 9 + q] = 0.0; A[q * 9 + p] = 0.0;
+                    wave_sync();                                       // (every lane has read apq, app, aqq)
+                    if (lane == 0) { A[p * 9 + q] = 0.0; A[q * 9 + p] = 0.0; }
+                    wave_sync();
                     continue;
                 }
                 const double theta = (aqq - app) / (2.0 * apq);
                 double t = isfinite(theta) ? 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0)) : 0.0;
                 if (theta < 0.0) t = -t;
                 const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                for (int k = 0; k < n; k++) {
-                    const double akp = A[k * 9 + p], akq = A[k * 9 + q];
+                wave_sync();                                           // (every lane has read apq, app, aqq)
+                if (lane < n) {
+                    const int k = lane;
+                    const double akp = A[k * 9 + p], akq = A[k * 9 + q], vkp = V[k * 9 + p], vkq = V[k * 9 + q];
                     A[k * 9 + p] = c * akp - s * akq; A[k * 9 + q] = s * akp + c * akq;
+                    V[k * 9 + p] = c * vkp - s * vkq; V[k * 9 + q] = s * vkp + c * vkq;
                 }
-                for (int k = 0; k < n; k++) {
+                wave_sync();
+                if (lane < n) {
+                    const int k = lane;
                     const double apk = A[p * 9 + k], aqk = A[q * 9 + k];
                     A[p * 9 + k] = c * apk - s * aqk; A[q * 9 + k] = s * apk + c * aqk;
                 }
-                for (int k = 0; k < n; k++) {
-                    const double vkp = V[k * 9 + p], vkq = V[k * 9 + q];
-                    V[k * 9 + p] = c * vkp - s * vkq; V[k * 9 + q] = s * vkp + c * vkq;
-                }
+                wave_sync();
             }
     }
 }
@@ -89,14 +107,16 @@ __device__ __forceinline__ double dlt_ly(int j, double X, double Y, double y)
 {
     switch (j) { case 3: return X; case 4: return Y; case 5: return 1.0; case 6: return -y * X; case 7: return -y * Y; case 8: return -y; default: return 0.0; }
 }
-// element j of the Jacobian rows from a point's stored terms P = a, b, ww, -a xi, -b xi, -a yi, -b yi
-__device__ __forceinline__ double lm_jx(int j, const double* P, size_t n, int i)
+// Element j of the Jacobian rows from a point's stored terms P = a, b, ww, -a xi, -b xi, -a yi, -b yi: which of the seven arrays it is
+// (lm_jx_term / lm_jy_term, -1: the element is 0), and its value.  The array is chosen once per matrix entry, outside the sum over the
+// points, so that the lanes of a wavefront -- one entry each -- issue the same loads side by side instead of one switch case after the
+// other; the value is the one the switch returned.
+__device__ __forceinline__ int lm_jx_term(int j) { return j < 3 ? j : j == 6 ? 3 : j == 7 ? 4 : -1; }
+__device__ __forceinline__ int lm_jy_term(int j) { return j >= 3 && j < 6 ? j - 3 : j == 6 ? 5 : j == 7 ? 6 : -1; }
+__device__ __forceinline__ double lm_term(const double* P, size_t n, int a, int i)
 {
-    switch (j) { case 0: return P[i]; case 1: return P[n + i]; case 2: return P[2 * n + i]; case 6: return P[3 * n + i]; case 7: return P[4 * n + i]; default: return 0.0; }
-}
-__device__ __forceinline__ double lm_jy(int j, const double* P, size_t n, int i)
-{
-    switch (j) { case 3: return P[i]; case 4: return P[n + i]; case 5: return P[2 * n + i]; case 6: return P[5 * n + i]; case 7: return P[6 * n + i]; default: return 0.0; }
+    const double v = P[(size_t)(a < 0 ? 0 : a) * n + i];
+    return a < 0 ? 0.0 : v;
 }
 // projection of (X, Y) by h (8 parameters, h[8] = 1): ww, xi, yi
 __device__ __forceinline__ void lm_project(const double* h, double X, double Y, double* ww, double* xi, double* yi)
@@ -109,7 +129,7 @@ __device__ __forceinline__ void lm_project(const double* h, double X, double Y, 
 
 // sum of term(0) .. term(n - 1) in index order with one accumulator.  The terms of 16 consecutive points are fetched before they are
 // added, so that the loads of a block are in flight together; the order of the additions -- and so every bit of the sum -- is that
-// of the plain loop.  (Measured: the fit's time did not change with it; the serial Jacobi is what the fit costs)
+// of the plain loop.  (Measured: the fit's time did not change with it; where the time was and is: DESIGN.md 4d.)
 template <typename F>
 __device__ __forceinline__ double seq_sum(int n, F term)
 {
@@ -175,8 +195,8 @@ __global__ __launch_bounds__(FIT_THREADS) void k_homography_fit(const double* __
         A[j * 9 + k] = acc; A[k * 9 + j] = acc;
     }
     __syncthreads();
+    if (state && tid < 64) jacobi_eigen(A, V, 9, tid); // wave 0, no workgroup barrier inside: the other waves wait at the next one
     if (state && tid == 0) {
-        jacobi_eigen(A, V, 9);
         int kmin = 0;
         double wmax = fabs(A[0]);
         for (int k = 1; k < 9; k++) {
@@ -248,18 +268,23 @@ __global__ __launch_bounds__(FIT_THREADS) void k_homography_fit(const double* __
         if (run && tid < 36) {
             int j, k;
             upper_entry(tid, 8, &j, &k);
+            const int xj = lm_jx_term(j), xk = lm_jx_term(k), yj = lm_jy_term(j), yk = lm_jy_term(k);
             const double acc = seq_sum(n, [&](int i) {
-                return lm_jx(j, work, N, i) * lm_jx(k, work, N, i) + lm_jy(j, work, N, i) * lm_jy(k, work, N, i);
+                return lm_term(work, N, xj, i) * lm_term(work, N, xk, i) + lm_term(work, N, yj, i) * lm_term(work, N, yk, i);
             });
             A[j * 9 + k] = acc; A[k * 9 + j] = acc;
         } else if (run && tid >= 64 && tid < 72) {      // (a second wave: the gradient)
             const int j = tid - 64;
-            grad[j] = seq_sum(n, [&](int i) { return lm_jx(j, work, N, i) * work[7 * N + i] + lm_jy(j, work, N, i) * work[8 * N + i]; });
+            const int xj = lm_jx_term(j), yj = lm_jy_term(j);
+            grad[j] = seq_sum(n, [&](int i) { return lm_term(work, N, xj, i) * work[7 * N + i] + lm_term(work, N, yj, i) * work[8 * N + i]; });
         }
         __syncthreads();
+        if (run && tid < 64) {                         // wave 0, as above
+            if (tid < 8) A[tid * 9 + tid] = A[tid * 9 + tid] + lambda * A[tid * 9 + tid];
+            wave_sync();
+            jacobi_eigen(A, V, 8, tid);
+        }
         if (run && tid == 0) {
-            for (int j = 0; j < 8; j++) A[j * 9 + j] = A[j * 9 + j] + lambda * A[j * 9 + j];
-            jacobi_eigen(A, V, 8);
             double wmax = 0.0;
             for (int k = 0; k < 8; k++)
                 if (fabs(A[k * 9 + k]) > wmax) wmax = fabs(A[k * 9 + k]);

@@ -2723,13 +2723,19 @@ extern "C" int mav_find_homography(mav_ctx* c, const double* src, const double* 
     CHK(mav_find_homography_dev(c, ds, dd, n, batch, dH, dok));
     return h.finish();
 }
-// coords (host) range-checked and brought to the context's buffer, then the pairs of `flow` gathered into the context's pair buffers
-static int gather_pairs(mav_ctx* c, const char* fn, const float* flow, const int32_t* coords, int n, int batch)
+// n and the coords (host) of a call that samples a flow field: the pair count, every sample inside the frame
+static int check_coords(const mav_ctx* c, const char* fn, const int32_t* coords, int n)
 {
     CHK(check_pairs(fn, n));
     for (int i = 0; i < n; i++)
         if (coords[2 * i] < 0 || coords[2 * i] >= c->W || coords[2 * i + 1] < 0 || coords[2 * i + 1] >= c->H)
             return fail(MAV_ERR_ARG, "%s: sample %d = (%d, %d) lies outside the %dx%d frame", fn, i, coords[2 * i], coords[2 * i + 1], c->W, c->H);
+    return MAV_OK;
+}
+// coords (host) range-checked and brought to the context's buffer, then the pairs of `flow` gathered into the context's pair buffers
+static int gather_pairs(mav_ctx* c, const char* fn, const float* flow, const int32_t* coords, int n, int batch)
+{
+    CHK(check_coords(c, fn, coords, n));
     CHK(ensure_pairs(c, n));
     HIPCHK(hipMemcpyAsync(c->gm.coords, coords, sizeof(int32_t) * 2 * (size_t)n, hipMemcpyHostToDevice, c->stream));
     launch_pair_gather(c->stream, flow, c->gm.coords, n, batch, c->W, c->H, c->gm.src, c->gm.dst);
@@ -2826,6 +2832,46 @@ extern "C" int mav_global_motion_step_dev(mav_ctx* c, const float* flow, const i
     if (!ok) ok = c->gm.ok;
     launch_homography_fit(c->stream, c->gm.src, c->gm.dst, n, batch, c->gm.work, H, ok);
     return global_motion_enqueue(c, "mav_global_motion_step_dev", flow, H, 9, ok, batch, scale, optimize, nullptr, nullptr, gray, results);
+}
+// The fused call of the branch: everything mav_farneback_dev and the step would refuse is refused here, before either enqueues anything.
+static int check_motion_batch(mav_ctx* c, const char* fn, const void* prev, const void* next, const int32_t* coords, int n, double scale,
+                              const void* results)
+{
+    if (!prev || !next || !coords || !results) return fail(MAV_ERR_ARG, "%s: NULL argument", fn);
+    CHK(check_coords(c, fn, coords, n));
+    PyrPlan p;
+    return pyr_plan(c, scale, c->max_batch, &p);
+}
+extern "C" int mav_global_motion_batch_dev(mav_ctx* c, const uint8_t* prev, const uint8_t* next, const int32_t* coords, int n, int batch,
+                                           double scale, int optimize, float* flow, double* H, int32_t* ok, uint8_t* gray,
+                                           mav_motion_result* results)
+{
+    CHK(check_dev_call(c, batch, "mav_global_motion_batch_dev"));
+    CHK(check_motion_batch(c, "mav_global_motion_batch_dev", prev, next, coords, n, scale, results));
+    if (!flow) {
+        CHK(ensure_flow_ws(c));
+        flow = c->flow_ws;
+    }
+    CHK(mav_farneback_dev(c, prev, next, batch, flow));
+    return mav_global_motion_step_dev(c, flow, coords, n, batch, scale, optimize, H, ok, gray, results);
+}
+extern "C" int mav_global_motion_batch(mav_ctx* c, const uint8_t* prev, const uint8_t* next, const int32_t* coords, int n, int batch, double scale,
+                                       int optimize, float* flow, double* H, int32_t* ok, uint8_t* gray, mav_motion_result* results)
+{
+    HostCall h(c, "mav_global_motion_batch");
+    CHK(h.fresh(batch));
+    CHK(check_motion_batch(c, "mav_global_motion_batch", prev, next, coords, n, scale, results));     // (before anything is staged)
+    const size_t px = c->n0 * batch;
+    const void *dprev, *dnext;
+    upload_frames(h, prev, next, batch, 1, &dprev, &dnext);
+    float* df = h.out(flow, px * 2 * sizeof(float));
+    double* dH = h.out(H, sizeof(double) * 9 * batch);
+    int32_t* dok = h.out(ok, sizeof(int32_t) * batch);
+    uint8_t* dg = h.out(gray, px);
+    mav_motion_result* dres = h.out(results, sizeof(mav_motion_result) * batch);
+    CHK(h.staged());
+    CHK(mav_global_motion_batch_dev(c, (const uint8_t*)dprev, (const uint8_t*)dnext, coords, n, batch, scale, optimize, df, dH, dok, dg, dres));
+    return h.finish();
 }
 extern "C" int mav_last_global_motion_render(mav_ctx* c, int batch, uint8_t* img_warped, uint8_t* img_global)
 {

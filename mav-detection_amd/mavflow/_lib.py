@@ -96,7 +96,8 @@ EXPORTS = [
     "mav_lk_track_err", "mav_lk_track_err_dev", "mav_corner_score_defaults", "mav_good_features_score", "mav_good_features_score_dev",
     "mav_stage_corner_response",
     "mav_find_homography", "mav_find_homography_dev", "mav_flow_homography", "mav_flow_homography_dev", "mav_global_motion",
-    "mav_global_motion_dev", "mav_global_motion_step_dev", "mav_last_global_motion_render",
+    "mav_global_motion_dev", "mav_global_motion_step_dev", "mav_last_global_motion_render", "mav_global_motion_batch",
+    "mav_global_motion_batch_dev",
 ]
 
 # Frame depths of the _ex entry points (cv2's depth codes) by numpy dtype.  uint8 frames keep going through the u8 symbols.
@@ -311,6 +312,10 @@ def load(path: str | None = None) -> C.CDLL:
     # ctx, flow, coords, n, batch, scale, optimize, H, ok, gray, results
     lib.mav_global_motion_step_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp, vp, vp]
     lib.mav_last_global_motion_render.argtypes = [vp, C.c_int, vp, vp]
+    # ctx, prev, next, coords, n, batch, scale, optimize, flow, H, ok, gray, results
+    gmb = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp, vp, vp, vp]
+    lib.mav_global_motion_batch.argtypes = gmb
+    lib.mav_global_motion_batch_dev.argtypes = gmb
     _lib = lib
     return lib
 
@@ -1103,11 +1108,46 @@ class Context:
         check(self.lib.mav_global_motion_step_dev(self.h, flow_ptr, _ptr(coords), coords.shape[0], int(batch), scale, int(bool(optimize)),
                                                   H_ptr, ok_ptr, gray_ptr, results_ptr))
 
+    MOTION_BATCH_OUTPUTS = ("flow", "gray")
+
+    def global_motion_batch(self, prev, nxt, coords, optimize: bool = False, outputs=(), scale: float = 1.5) -> dict:
+        """processor.py:286-303 for a batch of u8 frame pairs (B, H, W) as one call (mav_global_motion_batch): Farneback, the pairs at
+        coords (n, 2) integers (x, y), the homography fit, the subtraction, the normalised image and the window search.  Views of one
+        run of frames (prev = f[:-1], nxt = f[1:]) are recognised as in farneback_sequence.  -> dict(results = (B,) MOTION_DTYPE
+        records -- all zero for an item whose fit failed --, H (B, 3, 3) float64, ok (B,) int32, and of `outputs` "flow" (B, H, W, 2)
+        float32 and "gray" (B, H, W) u8)."""
+        bad = set(outputs) - set(self.MOTION_BATCH_OUTPUTS)
+        if bad:
+            raise ValueError(f"unknown output(s) {sorted(bad)}; choose from {self.MOTION_BATCH_OUTPUTS}")
+        prev, nxt = self._imgs(prev, "prev"), self._imgs(nxt, "next")
+        if prev.shape != nxt.shape:
+            raise ValueError("prev and next differ in shape")
+        coords = self._coords(coords)
+        B = prev.shape[0]
+        got = dict(results=np.empty(B, MOTION_DTYPE), H=np.empty((B, 3, 3), np.float64), ok=np.empty(B, np.int32))
+        flow = np.empty((B, self.H, self.W, 2), np.float32) if "flow" in outputs else None
+        gray = np.empty((B, self.H, self.W), np.uint8) if "gray" in outputs else None
+        check(self.lib.mav_global_motion_batch(self.h, _ptr(prev), _ptr(nxt), _ptr(coords), coords.shape[0], B, scale, int(bool(optimize)),
+                                               _ptr(flow), _ptr(got["H"]), _ptr(got["ok"]), _ptr(gray), _ptr(got["results"])))
+        if flow is not None:
+            got["flow"] = flow
+        if gray is not None:
+            got["gray"] = gray
+        return got
+
+    def global_motion_batch_dev(self, prev_ptr, next_ptr, coords, batch: int, results_ptr, optimize: bool = False, flow_ptr=None, H_ptr=None,
+                                ok_ptr=None, gray_ptr=None, scale: float = 1.5):
+        """mav_global_motion_batch_dev: the same for device-resident frames, enqueue only.  coords: host (n, 2) integers; the other
+        arguments are device pointers (flow_ptr None: the context's own flow buffer, last_flow() reads it)."""
+        coords = self._coords(coords)
+        check(self.lib.mav_global_motion_batch_dev(self.h, prev_ptr, next_ptr, _ptr(coords), coords.shape[0], int(batch), scale,
+                                                   int(bool(optimize)), flow_ptr, H_ptr, ok_ptr, gray_ptr, results_ptr))
+
     MOTION_IMAGES = ("warped", "global")
 
     def render_last_global_motion(self, batch: int, images=MOTION_IMAGES) -> dict:
         """get_flow_vis of flow_uv_warped ("warped") and of global_motion ("global") for the most recent global_motion /
-        global_motion_step call, from its resident flow and matrix: (batch, H, W, 3) u8 BGR each."""
+        global_motion_step / global_motion_batch call, from its resident flow and matrix: (batch, H, W, 3) u8 BGR each."""
         bad = set(images) - set(self.MOTION_IMAGES)
         if bad:
             raise ValueError(f"unknown image(s) {sorted(bad)}; choose from {self.MOTION_IMAGES}")

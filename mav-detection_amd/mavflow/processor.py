@@ -23,7 +23,8 @@ FoE discs on the frame, the fixed mask painted purple, blended 0.2 / 0.8) as `{p
 reference would write (np.sum(result_img) > 0); the fast loops render it on the device from the resident mask and FoE
 (mav_last_overlay), the staged loop composes it from draw_FoE, the painted mask and add_weighted.  No video container is encoded: the
 reference's etc/bash/pngs_to_mp4.sh turns the sequence into the mp4.  The global-motion branch writes cluster_vis there instead
-(:303), encoded on the host, and neither JSON nor result images, as the reference's does outside debug mode."""
+(:303) and neither JSON nor result images, as the reference's does outside debug mode; its one-frame loop encodes on the host, its
+batched loop (run_detection_batched with algorithm HOMOGRAPHY: _run_global_motion_batched) where png_encoder says."""
 from __future__ import annotations
 
 import json
@@ -206,6 +207,7 @@ class Processor:
         self.detection_windows: Dict[int, utils.Rectangle] = dict()
         self.detection_iou: Dict[int, float] = dict()
         self._gm_bufs = None                             # (context, device buffers) of the global-motion step
+        self._gm_slots = None                            # (key, the two buffer sets) of the batched global-motion loop
         # extra: get_simple_bounding_box of every frame's fixed mask, which the device records with the FoE (the reference derives no
         # box in this loop; FrameResult and its JSON stay exactly the reference's)
         self.detection_boxes: Dict[int, utils.Rectangle] = dict()
@@ -258,6 +260,7 @@ class Processor:
         ok = len(self._ctxs) >= lanes and all(c.alive and c.max_batch >= batch and (c.W, c.H) == (W, H) for c in self._ctxs[:lanes])
         if not ok:
             self._close_pipes()
+            self._free_global_motion_slots()
             for c in self._ctxs:
                 c.close()
             self._ctxs = [_lib.Context(W, H, batch) for _ in range(lanes)]
@@ -513,7 +516,7 @@ class Processor:
                     ctx.global_motion_step(ptr, det.coords, 1, b["res"].ptr, optimize=det.use_optimization, H_ptr=b["H"].ptr,
                                            ok_ptr=b["ok"].ptr, gray_ptr=b["gray"].ptr)
                     if not int(b["ok"].download(np.int32, (1,))[0]):
-                        raise RuntimeError(f"frame {i}: the sampled flow vectors do not determine a homography")
+                        raise RuntimeError(self.GM_MESSAGE.format(i))
                     det.homography = b["H"].download(np.float64, (3, 3))
                     det.confidence = np.ones((det.coords.shape[0], 1), np.uint8)
                 rec = b["res"].download(_lib.MOTION_DTYPE, (1,))[0]
@@ -554,7 +557,166 @@ class Processor:
 
     def _no_global_motion(self, what: str) -> None:
         if self.detector.is_homography_based():
-            raise NotImplementedError(f"{what} runs the FoE branch only; the global-motion branch (algorithm HOMOGRAPHY) is run_detection()")
+            raise NotImplementedError(f"{what} runs the FoE branch only; the global-motion branch (algorithm HOMOGRAPHY) is run_detection() "
+                                      "or run_detection_batched(batch)")
+
+    # -- the global-motion branch, `batch` frames per enqueue ---------------------------------------------------------------------------
+    GM_MESSAGE = "frame {}: the sampled flow vectors do not determine a homography"
+
+    def _run_global_motion_batched(self, batch: int) -> Dict[int, FrameResult]:
+        """_run_global_motion with the frame indices taken `batch` at a time, two buffer sets: batch k + 1's upload and step are enqueued
+        before the host waits for batch k's records (one marker per set, recorded behind the set's downloads).  A dataset that hands out
+        frame pairs and whose flow seam is Farneback on them (frame_pair(i); attribute use_farneback true or absent) goes through the
+        fused call, frames in and records out (mav_global_motion_batch_dev; consecutive pairs that share their frame objects are sent as
+        one run of frames).  Any other dataset hands the host float32 fields of get_flow_uv(i) to one gather upload in front of
+        mav_global_motion_step_dev; a device handle of the flow seam is read back and sent with them; a field of another dtype is a
+        ValueError (run_detection() serves it).  Per-frame state as the one-frame loop leaves it, in frame order: get_annotation(i),
+        detection_windows[i], detection_iou[i], detector.homography / confidence / flow_max / iou, cluster_vis files with a
+        processed_path (png_encoder="device": deflated from the gray planes where they are, one channel; they decode to the same
+        pixels, and detector.cluster_vis, which only the host encoder brings back, stays as it was).  A frame whose fit fails ends the
+        loop as it ends the one-frame loop: every earlier frame is stored and written,
+        frame_index is the failing index, nothing of later frames is stored."""
+        det = self.detector
+        if self.debug_mode:
+            raise NotImplementedError("debug_mode in the global-motion branch draws with cv2.rectangle and writes a six-image mosaic "
+                                      "(processor.py:295-301): not reproduced")
+        if det.use_sparse_of:
+            raise NotImplementedError("run_detection_batched takes the pairs from the flow field at detector.coords; use_sparse_of (pairs from "
+                                      "the sequential tracker, frame after frame) is served by run_detection()")
+        batch = int(batch)
+        if batch < 1:
+            raise ValueError(f"batch must be >= 1, got {batch}")
+        idx = list(range(self.frame_index, self.dataset.N - 1))
+        if not idx:
+            return self.detection_results
+        fused = hasattr(self.dataset, "frame_pair") and bool(getattr(self.dataset, "use_farneback", True))
+        ctx = self._own_ctxs(batch, 1)[0]
+        slots = self._global_motion_slots(ctx, batch, fused)
+        pending = deque()
+        try:
+            for k, b0 in enumerate(range(0, len(idx), batch)):
+                pending.append(self._submit_global_motion(ctx, slots[k % 2], idx[b0:b0 + batch], fused))
+                while len(pending) > 1:
+                    self._collect_global_motion(ctx, *pending.popleft())
+            while pending:
+                self._collect_global_motion(ctx, *pending.popleft())
+        finally:
+            for slot, _, _ in pending:                       # a failed frame: what is in flight behind it finishes, nothing of it is kept
+                slot["fence"].wait()
+            self._flush_images()
+        return self.detection_results
+
+    def _global_motion_slots(self, ctx, batch: int, fused: bool) -> list:
+        """The two buffer sets of the batched loop on `ctx` (kept until release() or until the loop moves to another context)."""
+        key = (ctx, batch, fused, self.png_encoder, self.processed_path is not None)
+        cur = self._gm_slots
+        if cur is not None and cur[0][0] is ctx and cur[0][1:] == key[1:]:
+            return cur[1]
+        self._free_global_motion_slots()
+        n0, B = ctx.W * ctx.H, batch
+        pin = lambda shape, dtype: _lib._pinned.empty(ctx, shape, dtype)
+        slots = []
+        for _ in range(2):
+            # fused: prev frames then next frames, or a run of B + 1 frames; else the B flow fields
+            s = dict(dev=dict(src=ctx.alloc(2 * B * n0 if fused else 8 * B * n0), H=ctx.alloc(72 * B), ok=ctx.alloc(4 * B), gray=ctx.alloc(B * n0),
+                              res=ctx.alloc(_lib.MOTION_DTYPE.itemsize * B)),
+                     res=pin((B,), _lib.MOTION_DTYPE), H=pin((B, 3, 3), np.float64), ok=pin((B,), np.int32), fence=pipeline._Fence(ctx))
+            if self.processed_path is not None and self.png_encoder == "device":
+                s["dev"]["png"] = ctx.alloc(ctx.lib.mav_png_bound(ctx.W, ctx.H, 1) * B)
+                s["dev"]["index"] = ctx.alloc(16 * B)
+                s["index"] = pin((B, 2), np.uint64)
+            elif self.processed_path is not None:
+                s["gray"] = pin((B, ctx.H, ctx.W), np.uint8)
+            slots.append(s)
+        self._gm_slots = (key, slots)
+        return slots
+
+    def _free_global_motion_slots(self) -> None:
+        if self._gm_slots is not None:
+            (ctx, *_), slots = self._gm_slots
+            self._gm_slots = None
+            for s in slots:
+                if ctx.alive:
+                    s["fence"].wait()
+                    for buf in s["dev"].values():
+                        buf.free()
+                s["fence"].destroy()
+
+    def _submit_global_motion(self, ctx, slot, ids, fused: bool):
+        """Upload and step of frames `ids` on buffer set `slot` (idle: its last batch has been collected), the downloads of what the host
+        reads, the set's marker.  -> (slot, ids, frames)."""
+        det, dev, n, n0 = self.detector, slot["dev"], len(ids), ctx.W * ctx.H
+        lib, h = ctx.lib, ctx.h
+        # the frames the reference's loop draws on, one get_frame() per frame index as it calls it (only when they are drawn)
+        frames = [self.dataset.get_frame() for _ in ids] if self.processed_path is not None else None
+        optimize = bool(det.use_optimization)
+        if fused:
+            pairs = [self.dataset.frame_pair(i) for i in ids]
+            prev = pipeline._as_frames([p[0] for p in pairs], ctx.H, ctx.W, "prev")
+            nxt = pipeline._as_frames([p[1] for p in pairs], ctx.H, ctx.W, "next")
+            run = all(pairs[k][1] is pairs[k + 1][0] for k in range(n - 1))        # one run of n + 1 frames (a video)
+            arrs = prev + nxt[-1:] if run else prev + nxt
+            _lib.check(lib.mav_upload_gather(h, dev["src"].ptr, pipeline._ptr_array(arrs), len(arrs), n0, 0))
+            _lib.check(lib.mav_upload_fence(h))
+            ctx.global_motion_batch_dev(dev["src"].ptr, dev["src"].ptr + (1 if run else n) * n0, det.coords, n, dev["res"].ptr, optimize=optimize,
+                                        H_ptr=dev["H"].ptr, ok_ptr=dev["ok"].ptr, gray_ptr=dev["gray"].ptr)
+        else:
+            fields = []
+            for i in ids:
+                f = self.dataset.get_flow_uv(i)
+                if f is None:
+                    raise ValueError("Could not load flow field.")
+                if f.dtype != np.float32:
+                    raise ValueError(f"frame {i}: run_detection_batched() takes float32 flow fields, got {f.dtype}; run_detection() serves "
+                                     "a field of another dtype (host float64 arithmetic)")
+                a = np.ascontiguousarray(np.asarray(f))                            # (a device handle of the flow seam is read back here)
+                if a.shape != (ctx.H, ctx.W, 2):
+                    raise ValueError(f"frame {i}: expected a ({ctx.H}, {ctx.W}, 2) flow field, got {a.shape}")
+                fields.append(a)
+            _lib.check(lib.mav_upload_gather(h, dev["src"].ptr, pipeline._ptr_array(fields), n, 8 * n0, 0))
+            _lib.check(lib.mav_upload_fence(h))
+            ctx.global_motion_step(dev["src"].ptr, det.coords, n, dev["res"].ptr, optimize=optimize, H_ptr=dev["H"].ptr, ok_ptr=dev["ok"].ptr,
+                                   gray_ptr=dev["gray"].ptr)
+        if "index" in slot:
+            _lib.check(lib.mav_png_encode_dev(h, dev["gray"].ptr, n, 1, dev["png"].ptr, dev["png"].nbytes, dev["index"].ptr))
+        for name in ("res", "H", "ok", "gray", "index"):
+            if name in slot:
+                host = slot[name][:n]
+                _lib.check(lib.mav_download_async(h, _lib._ptr(host), dev[name].ptr, host.nbytes))
+        slot["fence"].record()
+        return slot, ids, frames
+
+    def _collect_global_motion(self, ctx, slot, ids, frames) -> None:
+        """Batch `ids` on `slot` has finished: its frames in frame order, as the one-frame loop leaves them."""
+        det = self.detector
+        slot["fence"].wait()
+        for k, i in enumerate(ids):
+            self.dataset.get_annotation(i)
+            if not int(slot["ok"][k]):
+                self.frame_index = i
+                raise RuntimeError(self.GM_MESSAGE.format(i))
+            det.homography = np.array(slot["H"][k])
+            det.confidence = np.ones((det.coords.shape[0], 1), np.uint8)
+            rec = slot["res"][k]
+            det.flow_max = (int(rec["max_row"]), int(rec["max_col"]))
+            x, y, w, h = (int(v) for v in rec["opt_window"])
+            window = utils.Rectangle.from_points((x, y), (x + w, y + h))
+            for gt in self.dataset.ground_truth:
+                det.iou = utils.Rectangle.calculate_iou(window, gt)
+            self.detection_windows[i] = window
+            if hasattr(det, "iou"):
+                self.detection_iou[i] = det.iou
+            if self.processed_path is not None:
+                det.prev_frame = frames[k]
+                if "index" in slot:                          # the stream alone crosses PCIe; the pool adds the chunk framing
+                    off, size = (int(v) for v in slot["index"][k])
+                    z = np.empty(size, np.uint8)
+                    _lib.check(ctx.lib.mav_memcpy_d2h(ctx.h, _lib._ptr(z), slot["dev"]["png"].ptr + off, size))
+                    self._queue_png(self.processed_path, i, (ctx.W, ctx.H, 1, z.tobytes()))
+                else:
+                    det.cluster_vis = np.repeat(slot["gray"][k][..., None], 3, axis=2)
+                    self._queue_png(self.processed_path, i, det.cluster_vis)
+            self.frame_index = i + 1
 
     @property
     def _renders(self) -> bool:
@@ -620,13 +782,20 @@ class Processor:
             self._write_processed([i], [mask_vis], [np.sum(result_img) > 0])
         self.frame_index += 1
 
-    def run_detection_batched(self, batch: int = 8) -> Dict[int, FrameResult]:
+    def run_detection_batched(self, batch: Optional[int] = None) -> Dict[int, FrameResult]:
         """The same loop with frame pairs in flight `batch` at a time through the fused entry point (frames -> flow -> derotation ->
         FoE -> masks -> box -> counts), two batches in flight: while batch k computes, batch k + 1's frames are gathered from the
         dataset's arrays and cross PCIe, and batch k - 1's FrameResults are filled in.  Needs a dataset that hands out frame pairs
-        (frame_pair(i)).  The sample coordinates are drawn per frame in frame order, as get_FOE_dense draws them."""
+        (frame_pair(i)).  The sample coordinates are drawn per frame in frame order, as get_FOE_dense draws them.
+        batch None: 8 pairs.  With algorithm HOMOGRAPHY and a batch given: the global-motion branch `batch` frames at a time
+        (_run_global_motion_batched); without one the call refuses that algorithm as it always has -- the branch's buffer sets and its
+        context are sized by the batch, and no default is chosen for the caller."""
         from collections import deque
-        self._no_global_motion("run_detection_batched")
+        if self.detector.is_homography_based():
+            if batch is None:
+                self._no_global_motion("run_detection_batched() without a batch")
+            return self._run_global_motion_batched(batch)
+        batch = 8 if batch is None else batch
         W, H = self.dataset.capture_size
         idx = list(range(self.frame_index, self.dataset.N - 1))
         # small batches (one pair at 720p / 1080p ...) are spread over 2 - 3 contexts taken in turn; a big batch keeps two pairs in
@@ -683,6 +852,7 @@ class Processor:
             self._png_pool.shutdown()
             self._png_pool = None
         self._free_global_motion_buffers()
+        self._free_global_motion_slots()
         self.detector._free_dev_buffers()
         self._close_pipes()
         for c in self._ctxs:
