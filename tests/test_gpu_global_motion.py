@@ -1,7 +1,8 @@
 """The global-motion branch on the GPU (csrc/kernels_motion.hip and the calls around it) against the numpy restatement
 tests/global_motion_ref.py and, for the window search on the normalised image, oracle/pyramid_oracle.py.  Equal bytes everywhere:
 no tolerance appears in this file.  The restatement's full-frame half is pinned to the reference by tests/golden/global_motion.npz
-(tests/test_global_motion_ref_cpu.py); the fit is pinned to nothing but the restatement."""
+(tests/test_global_motion_ref_cpu.py); the fit's restatement is held to an independent least-squares minimiser by
+tests/test_homography_lsq_cpu.py and is not pinned against cv2."""
 import logging
 import os
 
