@@ -137,6 +137,8 @@ int mav_device_count(void);       /* <= 0 when no GPU is visible */
  *                      The runtime keeps a pool of hardware queues per priority class and hands a new stream the least-used queue of its
  *                      class: which queue a lane gets otherwise depends on every stream the process has ever made (one idle context created
  *                      before three lanes: 0.31 instead of 0.215 ms per 1280x720 frame).  Lanes take a class of their own
+ *   "cc_workspace_mb"  default 256: the most scratch mav_components* holds; a batch is labelled in sub-batches of as many images as fit
+ *                      (at least one: 0 = one image at a time)
  * None of them changes a result bit (tests/test_gpu_flow.py, tests/test_gpu_screen.py; "phi_yloop" and "phi_screen":
  * tests/test_gpu_detect_forms.py). */
 int mav_set_option(mav_ctx*, const char* name, long value);
@@ -388,6 +390,49 @@ int mav_marker_wait(mav_ctx* /* may be NULL */, void* marker);
 int mav_marker_query(mav_ctx* /* may be NULL */, void* marker, int* done);
 int mav_marker_destroy(mav_ctx* /* may be NULL */, void* marker);
 
+/* ---- blob detections: connected components of u8 masks, on the device ----------------------------------------------------------------
+ * The step from a mask to objects that the reference left commented out [src/detector.py:189, src/validator.py:116:
+ * frame_result.add_box('MAV', 1.0, window)]: where mav_result.box is the hull of EVERY set pixel, this is one record per connected
+ * component.  mask: (batch, H, W) u8, any non-zero byte is set.  connectivity 4 or 8.
+ *   labels  optional (NULL), (batch, H, W) int32: 0 on background, components numbered 1 .. n in raster order of their FIRST pixel
+ *           (top-most row, then left-most column).  That is scipy.ndimage.label's numbering.  It is NOT promised to be cv2's:
+ *           cv2.connectedComponents' block-based default algorithms create labels in 2x2-block order (unpinned against cv2, like the
+ *           Farneback caveats above).
+ *   counts  (batch): n_components = the exact number of components; n_blobs = the exact number with area >= min_area -- it may exceed
+ *           max_blobs, which is how a caller sees that the table is truncated.
+ *   blobs   (batch, max_blobs) records of 40 bytes: the first min(n_blobs, max_blobs) components with area >= min_area in label order;
+ *           x, y, w, h as cv2's CC_STAT_LEFT / TOP / WIDTH / HEIGHT; sum_x, sum_y the integer coordinate sums (sum / area in float64 on
+ *           the host is the exact centroid).  Unused records are all-zero bytes: whole tables compare equal.
+ * Parameters (mav_cc_defaults: 8, 1, 256; NULL = defaults): connectivity 4 | 8, min_area >= 1, max_blobs 1 .. MAV_CC_MAX_BLOBS; anything
+ * else is MAV_ERR_ARG and nothing is enqueued.  All results are integers and functions of the partition into components alone: the same
+ * call gives the same bytes every time (tests/test_gpu_components.py compares them with tests/components_ref.py bit for bit).
+ * Scratch: two int32 planes + a few counters, 8.03 bytes per pixel, from the context's memory ledger (mav_mem_info counts it); a batch
+ * is walked in sub-batches of as many images as fit option "cc_workspace_mb" (default 256; at least one image), so the workspace is
+ * bounded whatever max_batch is.  The tile of the first pass is MAV_CC_TILE_W x MAV_CC_TILE_H pixels. */
+#define MAV_CC_TILE_W 64
+#define MAV_CC_TILE_H 16
+#define MAV_CC_MAX_BLOBS 65535
+typedef struct {
+    int connectivity, min_area, max_blobs;
+} mav_cc_params;
+typedef struct {
+    int32_t n_components, n_blobs;
+} mav_cc_counts;
+typedef struct {
+    int32_t label, x, y, w, h, area;
+    int64_t sum_x, sum_y;
+} mav_blob;
+void mav_cc_defaults(mav_cc_params*);
+int mav_components(mav_ctx*, const uint8_t* mask, int batch, const mav_cc_params*, int32_t* labels, mav_cc_counts* counts,
+                   mav_blob* blobs);                                                      /* host pointers, synchronous */
+int mav_components_dev(mav_ctx*, const uint8_t* mask, int batch, const mav_cc_params*, int32_t* labels, mav_cc_counts* counts,
+                       mav_blob* blobs);                                                  /* device pointers, enqueue only */
+/* The same for the fixed (which = 0) or dynamic (which = 1) mask that the most recent mav_detect / mav_process_batch /
+ * mav_phi_mask(_f32) call on this context left resident: host outputs, the mask is not moved again.  MAV_ERR_STATE exactly as
+ * mav_last_masks_tpr_fpr (no such call precedes, its batch differs, or it kept no such mask). */
+int mav_last_masks_components(mav_ctx*, int which, int batch, const mav_cc_params*, int32_t* labels, mav_cc_counts* counts,
+                              mav_blob* blobs);
+
 /* ---- one iteration of the reference's loop as ONE call ---------------------------------------------------------------------------
  * Processor.run_detection's body [src/processor.py:283-362] is, per frame: read a frame, get the flow (Farneback here), derotate,
  * FoE, phi, masks, TPR / FPR counts against the segmentation, store a record.  Through the entry points above that is a dozen calls
@@ -404,6 +449,7 @@ int mav_marker_destroy(mav_ctx* /* may be NULL */, void* marker);
  *      recognised), then the `record_after_flow` markers ("the frame buffers have been read"),
  *   5. detection on flow_dev (mav_detect_dev): samples / omega / dt / frame0 at their offsets inside par_dev, sky_dev, masks,
  *      n records to out_dev; with gt_dev the TPR / FPR counts of both masks (mav_tpr_fpr_counts_dev) to out_dev + off_counts_*,
+ *      with cc.max_blobs != 0 the connected components of mask_fixed_dev (mav_components_dev) to out_dev + off_cc_*,
  *   6. out_dev[0 : out_bytes] -> out_host (page-locked), then `record_done`.
  * The library copies the struct and the pointer arrays it refers to (gather[i].src_host, wait_before, record_after_flow) when the
  * step is posted; the HOST BUFFERS themselves (frames, par_host, out_host) must stay valid and unchanged until the step's
@@ -456,6 +502,11 @@ typedef struct mav_frame_step {
     void* out_host;
     size_t out_bytes;
     void* record_done;
+    /* 5, behind the counts: connected components of mask_fixed_dev (mav_components_dev), n mav_cc_counts at out_dev + off_cc_counts and
+     * n x cc.max_blobs mav_blob records at out_dev + off_cc_blobs (a multiple of 8), so that part 6's one copy carries them.
+     * cc.max_blobs == 0 (a zeroed struct): off, not one launch more. */
+    mav_cc_params cc;
+    size_t off_cc_counts, off_cc_blobs;
 } mav_frame_step;
 int mav_frame_step_dev(mav_ctx*, const mav_frame_step*);
 /* Post the step to the context's worker thread.  From the first post on until mav_worker_drain (or mav_destroy) the worker is the

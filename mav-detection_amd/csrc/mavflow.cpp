@@ -327,9 +327,9 @@ struct Stager {
         }
     }
 };
-enum KernelId { K_BLUR_RESIZE, K_POLYEXP, K_UPDATE, K_ITER, K_ITER_COARSE, K_FOE, K_PHI, K_MISC, K_LK_CORNERS, K_LK_PYRAMID, K_LK_TRACK, K_LK_PICK, K_COUNT };
+enum KernelId { K_BLUR_RESIZE, K_POLYEXP, K_UPDATE, K_ITER, K_ITER_COARSE, K_FOE, K_PHI, K_MISC, K_LK_CORNERS, K_LK_PYRAMID, K_LK_TRACK, K_LK_PICK, K_COMPONENTS, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"blur_resize", "polyexp", "update_matrices", "blur_iter", "blur_iter_coarse",
-                                                  "foe_ransac", "phi_mask_box", "misc", "lk_corners", "lk_pyramid", "lk_track", "lk_pick"};
+                                                  "foe_ransac", "phi_mask_box", "misc", "lk_corners", "lk_pyramid", "lk_track", "lk_pick", "components"};
 struct ProfRec { int kid; hipEvent_t a, b; int stream; };
 struct ProfInterval { int kid; float t0, t1; int stream; };      // ms since the profile was switched on
 
@@ -466,6 +466,9 @@ struct mav_ctx {
     uint8_t* pyr_ws = nullptr;                  // analyze_pyramid level images (lazily, max_batch)
     size_t pyr_ws_cap = 0;
     unsigned long long* sat = nullptr;          // optimize_window summed-area tables (lazily, max_batch)
+    uint8_t* cc_ws = nullptr;                   // connected components: label planes + chunk counters of one sub-batch (first call, grow-only
+    size_t cc_ws_cap = 0;                       // up to "cc_workspace_mb", or one image's)
+    int cc_workspace_mb = 256;                  // option "cc_workspace_mb"
     // global-motion subtraction (mav_global_motion*, mav_find_homography*): per-item scratch (lazily, max_batch), the pair buffers
     // (grow-only, pairs_cap = pairs per item they hold) and what the latest call left resident for mav_last_global_motion_render
     struct Motion {
@@ -859,6 +862,7 @@ static const Option kOptions[] = {
     {"upload_threads", 1, 64, &mav_ctx::upload_threads, nullptr, false, set_upload_threads},
     {"inline_uploads", -kAny, kAny, nullptr, &mav_ctx::inline_uploads, false, set_inline_uploads},
     {"stream_priority", -kAny, kAny, &mav_ctx::stream_priority, nullptr, false, set_stream_priority},
+    {"cc_workspace_mb", 0, 1 << 20, &mav_ctx::cc_workspace_mb, nullptr, false, nullptr},
 };
 static const Option* find_option(const char* name)
 {
@@ -1989,6 +1993,48 @@ extern "C" int mav_process_batch_dev(mav_ctx* c, const uint8_t* prev, const uint
     return mav_detect_dev(c, flow, samples, omega, dt, frame0, sky, batch, fp, tp, phi, mask_fixed, mask_dyn, results);
 }
 
+// ---- connected components (include/mavflow.h: mav_components) -----------------------------------------------------------------------
+extern "C" void mav_cc_defaults(mav_cc_params* p)
+{
+    if (p) { p->connectivity = 8; p->min_area = 1; p->max_blobs = 256; }
+}
+// The caller's parameters (NULL = defaults), refused before anything is enqueued.
+static int cc_params_checked(const mav_cc_params* pp, mav_cc_params* p, const char* fn)
+{
+    if (pp) *p = *pp; else mav_cc_defaults(p);
+    if (p->connectivity != 4 && p->connectivity != 8) return fail(MAV_ERR_ARG, "%s: connectivity must be 4 or 8, got %d", fn, p->connectivity);
+    if (p->min_area < 1) return fail(MAV_ERR_ARG, "%s: min_area must be at least 1, got %d", fn, p->min_area);
+    if (p->max_blobs < 1 || p->max_blobs > MAV_CC_MAX_BLOBS) return fail(MAV_ERR_ARG, "%s: max_blobs %d outside [1, %d]", fn, p->max_blobs, (int)MAV_CC_MAX_BLOBS);
+    return MAV_OK;
+}
+// Device pointers, checked parameters: the tables zeroed, then the passes over sub-batches of as many images as the workspace cap holds
+// (at least one).  The workspace grows to that size once and is never sized by max_batch.
+static int components_enqueue(mav_ctx* c, const uint8_t* mask, int batch, const mav_cc_params& p, int32_t* labels, mav_cc_counts* counts,
+                              mav_blob* blobs)
+{
+    const size_t per = cc_workspace_per_image(c->W, c->H);
+    size_t sub = ((size_t)c->cc_workspace_mb << 20) / per;
+    sub = sub < 1 ? 1 : sub > (size_t)batch ? (size_t)batch : sub;
+    CHK(grow_buffer(c, &c->cc_ws, &c->cc_ws_cap, per * sub, MEM_OTHER, READ_ON_COMPUTE, RELEASE_FIRST, "components workspace"));
+    HIPCHK(hipMemsetAsync(blobs, 0, sizeof(mav_blob) * (size_t)p.max_blobs * batch, c->stream));
+    ProfScope ps(c, K_COMPONENTS);
+    for (size_t b0 = 0; b0 < (size_t)batch; b0 += sub) {
+        const int g = (int)((size_t)batch - b0 < sub ? (size_t)batch - b0 : sub);
+        launch_components(c->stream, CcArgs{mask + b0 * c->n0, g, c->W, c->H, p.connectivity, p.min_area, p.max_blobs, c->cc_ws,
+                                            labels ? labels + b0 * c->n0 : nullptr, counts + b0, blobs + b0 * (size_t)p.max_blobs});
+    }
+    return check_launch("components");
+}
+extern "C" int mav_components_dev(mav_ctx* c, const uint8_t* mask, int batch, const mav_cc_params* pp, int32_t* labels, mav_cc_counts* counts,
+                                  mav_blob* blobs)
+{
+    if (!c || !mask || !counts || !blobs) return fail(MAV_ERR_ARG, "mav_components_dev: NULL argument");
+    mav_cc_params p;
+    CHK(cc_params_checked(pp, &p, "mav_components_dev"));
+    CHK(check_dev_call(c, batch, "mav_components_dev"));
+    return components_enqueue(c, mask, batch, p, labels, counts, blobs);
+}
+
 // ---- one iteration of the reference's loop as one call (include/mavflow.h: mav_frame_step) ---------------------------------------
 static int frame_step_body(mav_ctx* c, const mav_frame_step* s, bool* started);
 static int frame_step_enqueue(mav_ctx* c, const mav_frame_step* s)
@@ -2021,6 +2067,13 @@ static int frame_step_body(mav_ctx* c, const mav_frame_step* s, bool* started)
     if (s->n_bgr && (!s->bgr_dev || !s->gray_dev)) return fail(MAV_ERR_ARG, "mav_frame_step: n_bgr without bgr_dev / gray_dev");
     if (s->out_bytes && (!s->out_host || !s->out_dev)) return fail(MAV_ERR_ARG, "mav_frame_step: out_bytes without out_host / out_dev");
     if (s->par_bytes && (!s->par_host || !s->par_dev)) return fail(MAV_ERR_ARG, "mav_frame_step: par_bytes without par_host / par_dev");
+    mav_cc_params cc{};
+    if (s->cc.max_blobs) {
+        if (!s->detect || !s->mask_fixed_dev || !s->out_dev) return fail(MAV_ERR_ARG, "mav_frame_step: cc needs detect, mask_fixed_dev and out_dev");
+        if (s->off_cc_counts % alignof(mav_cc_counts) || s->off_cc_blobs % alignof(mav_blob))
+            return fail(MAV_ERR_ARG, "mav_frame_step: off_cc_counts must be a multiple of 4 and off_cc_blobs of 8");
+        CHK(cc_params_checked(&s->cc, &cc, "mav_frame_step"));
+    }
     HIPCHK(hipSetDevice(c->device));
     for (int i = 0; i < s->n_wait_before; i++)
         if (s->wait_before[i]) HIPCHK(hipEventSynchronize((hipEvent_t)s->wait_before[i]));
@@ -2050,6 +2103,9 @@ static int frame_step_body(mav_ctx* c, const mav_frame_step* s, bool* started)
         if (s->gt_dev)
             CHK(mav_tpr_fpr_counts_dev(c, s->gt_dev, s->gt_images, s->mask_fixed_dev, s->mask_dyn_dev, 255, s->n,
                                        (int64_t*)((char*)s->out_dev + s->off_counts_fixed), (int64_t*)((char*)s->out_dev + s->off_counts_dyn)));
+        if (cc.max_blobs)
+            CHK(components_enqueue(c, s->mask_fixed_dev, s->n, cc, nullptr, (mav_cc_counts*)((char*)s->out_dev + s->off_cc_counts),
+                                   (mav_blob*)((char*)s->out_dev + s->off_cc_blobs)));
     }
     if (s->out_bytes) CHK(mav_download_async(c, s->out_host, s->out_dev, s->out_bytes));
     if (s->record_done) HIPCHK(hipEventRecord((hipEvent_t)s->record_done, c->stream));
@@ -2981,6 +3037,40 @@ extern "C" int mav_last_masks_tpr_fpr(mav_ctx* c, const uint8_t* gt, int mask_va
     launch_tpr_fpr2(c->stream, dg, c->n0, m0, m1, (unsigned)mask_value, batch, c->W, c->H, c0, m1 ? c1 : nullptr);
     CHK(check_launch("tpr_fpr"));
     return h.finish();
+}
+
+// mask == NULL: the resident mask `resident` of the last detection call (the call appends its blocks behind that call's)
+static int components_host(mav_ctx* c, const char* fn, const uint8_t* mask, const uint8_t* resident, int batch, const mav_cc_params* pp,
+                           int32_t* labels, mav_cc_counts* counts, mav_blob* blobs)
+{
+    mav_cc_params p;
+    CHK(cc_params_checked(pp, &p, fn));
+    HostCall h(c, fn);
+    if (resident) CHK(h.after_last()); else CHK(h.fresh(batch));
+    const size_t n = c->n0 * batch;
+    const uint8_t* dm = resident ? resident : h.in(mask, n);
+    int32_t* dl = h.out(labels, n * sizeof(int32_t));
+    mav_cc_counts* dc = h.out(counts, sizeof(mav_cc_counts) * batch);
+    mav_blob* db = h.out(blobs, sizeof(mav_blob) * (size_t)p.max_blobs * batch);
+    CHK(h.staged());
+    CHK(components_enqueue(c, dm, batch, p, dl, dc, db));
+    return h.finish();
+}
+extern "C" int mav_components(mav_ctx* c, const uint8_t* mask, int batch, const mav_cc_params* pp, int32_t* labels, mav_cc_counts* counts,
+                              mav_blob* blobs)
+{
+    if (!c || !mask || !counts || !blobs) return fail(MAV_ERR_ARG, "mav_components: NULL argument");
+    return components_host(c, "mav_components", mask, nullptr, batch, pp, labels, counts, blobs);
+}
+extern "C" int mav_last_masks_components(mav_ctx* c, int which, int batch, const mav_cc_params* pp, int32_t* labels, mav_cc_counts* counts,
+                                         mav_blob* blobs)
+{
+    if (!c || !counts || !blobs) return fail(MAV_ERR_ARG, "mav_last_masks_components: NULL argument");
+    if (which != 0 && which != 1) return fail(MAV_ERR_ARG, "mav_last_masks_components: which must be 0 (fixed) or 1 (dynamic), got %d", which);
+    const uint8_t* m = which == 0 ? c->last_mf : c->last_md;
+    if (!c->last_mask_batch || batch != c->last_mask_batch || !m)
+        return fail(MAV_ERR_STATE, "mav_last_masks_components: no %s mask of a %d-pair detection call is resident", which ? "dynamic" : "fixed", batch);
+    return components_host(c, "mav_last_masks_components", nullptr, m, batch, pp, labels, counts, blobs);
 }
 
 // calculate_tpr_fpr of one or two device-resident masks against a device-resident ground truth, counts left on the device: the

@@ -296,3 +296,16 @@ void launch_motion_pass_b(hipStream_t st, const float* flow, const double* M, in
 void launch_motion_window(hipStream_t st, const int64_t* pyr, int B, int32_t* win);
 void launch_motion_pack(hipStream_t st, const unsigned long long* key, const int64_t* pyr, const int32_t* win, const int64_t* opt_score,
                         const int32_t* opt_win, const int* ok, int B, int W, mav_motion_result* out);
+
+// ---- connected components (kernels_components.hip, integer arithmetic only) -----------------------------------------------------------
+// B images of W x H from `mask`; ws: B * cc_workspace_per_image bytes; labels nullable; counts (B), blobs (B, max_blobs: zeroed by the caller).
+struct CcArgs {
+    const uint8_t* mask;
+    int B, W, H, connectivity, min_area, max_blobs;
+    void* ws;
+    int32_t* labels;
+    mav_cc_counts* counts;
+    mav_blob* blobs;
+};
+size_t cc_workspace_per_image(int W, int H);
+void launch_components(hipStream_t st, const CcArgs& a);

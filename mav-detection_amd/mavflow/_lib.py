@@ -68,6 +68,28 @@ MOTION_DTYPE = np.dtype([("max_mag", np.float32), ("max_row", np.int32), ("max_c
 assert MOTION_DTYPE.itemsize == C.sizeof(MotionResult) == 88
 HOMOGRAPHY_MAX_PAIRS = 65536
 
+
+class CcParams(C.Structure):
+    """mav_cc_params: connectivity (4 | 8), min_area (>= 1), max_blobs (1 .. CC_MAX_BLOBS)."""
+    _fields_ = [("connectivity", C.c_int), ("min_area", C.c_int), ("max_blobs", C.c_int)]
+
+
+class CcCounts(C.Structure):
+    _fields_ = [("n_components", C.c_int32), ("n_blobs", C.c_int32)]
+
+
+class Blob(C.Structure):
+    """mav_blob: one connected component (x, y, w, h as cv2's CC_STAT_LEFT / TOP / WIDTH / HEIGHT; integer coordinate sums)."""
+    _fields_ = [("label", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("area", C.c_int32),
+                ("sum_x", C.c_int64), ("sum_y", C.c_int64)]
+
+
+CC_COUNTS_DTYPE = np.dtype([("n_components", np.int32), ("n_blobs", np.int32)])
+BLOB_DTYPE = np.dtype([("label", np.int32), ("x", np.int32), ("y", np.int32), ("w", np.int32), ("h", np.int32), ("area", np.int32),
+                       ("sum_x", np.int64), ("sum_y", np.int64)])
+assert BLOB_DTYPE.itemsize == C.sizeof(Blob) == 40 and CC_COUNTS_DTYPE.itemsize == C.sizeof(CcCounts) == 8
+CC_TILE_W, CC_TILE_H, CC_MAX_BLOBS = 64, 16, 65535      # MAV_CC_TILE_W / _H (the first pass's tile), MAV_CC_MAX_BLOBS
+
 # every symbol include/mavflow.h declares (tests check the library exports each of them)
 EXPORTS = [
     "mav_fb_defaults", "mav_foe_defaults", "mav_thr_defaults", "mav_create", "mav_destroy", "mav_last_error",
@@ -98,6 +120,7 @@ EXPORTS = [
     "mav_find_homography", "mav_find_homography_dev", "mav_flow_homography", "mav_flow_homography_dev", "mav_global_motion",
     "mav_global_motion_dev", "mav_global_motion_step_dev", "mav_last_global_motion_render", "mav_global_motion_batch",
     "mav_global_motion_batch_dev",
+    "mav_cc_defaults", "mav_components", "mav_components_dev", "mav_last_masks_components",
 ]
 
 # Frame depths of the _ex entry points (cv2's depth codes) by numpy dtype.  uint8 frames keep going through the u8 symbols.
@@ -137,7 +160,8 @@ class FrameStep(C.Structure):
                 ("foe", FoeParams), ("thr", ThrParams),
                 ("mask_fixed_dev", C.c_void_p), ("mask_dyn_dev", C.c_void_p), ("out_dev", C.c_void_p),
                 ("off_counts_fixed", C.c_size_t), ("off_counts_dyn", C.c_size_t),
-                ("out_host", C.c_void_p), ("out_bytes", C.c_size_t), ("record_done", C.c_void_p)]
+                ("out_host", C.c_void_p), ("out_bytes", C.c_size_t), ("record_done", C.c_void_p),
+                ("cc", CcParams), ("off_cc_counts", C.c_size_t), ("off_cc_blobs", C.c_size_t)]
 
 _lib = None
 
@@ -161,7 +185,7 @@ def load(path: str | None = None) -> C.CDLL:
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("mav_last_error", "mav_stream", "mav_fb_defaults", "mav_foe_defaults", "mav_thr_defaults", "mav_last_flow_dev", "mav_png_bound",
-                        "mav_gftt_defaults", "mav_lk_defaults", "mav_corner_score_defaults"):
+                        "mav_gftt_defaults", "mav_lk_defaults", "mav_corner_score_defaults", "mav_cc_defaults"):
             fn.restype = C.c_int
     lib.mav_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FbParams)]
     lib.mav_destroy.argtypes = [C.c_void_p]
@@ -316,6 +340,11 @@ def load(path: str | None = None) -> C.CDLL:
     gmb = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp, vp, vp, vp]
     lib.mav_global_motion_batch.argtypes = gmb
     lib.mav_global_motion_batch_dev.argtypes = gmb
+    lib.mav_cc_defaults.argtypes = [C.POINTER(CcParams)]
+    lib.mav_cc_defaults.restype = None
+    lib.mav_components.argtypes = [vp, vp, C.c_int, C.POINTER(CcParams), vp, vp, vp]
+    lib.mav_components_dev.argtypes = [vp, vp, C.c_int, C.POINTER(CcParams), vp, vp, vp]
+    lib.mav_last_masks_components.argtypes = [vp, C.c_int, C.c_int, C.POINTER(CcParams), vp, vp, vp]
     _lib = lib
     return lib
 
@@ -349,6 +378,17 @@ def foe_defaults() -> FoeParams:
 def thr_defaults() -> ThrParams:
     p = ThrParams()
     load().mav_thr_defaults(C.byref(p))
+    return p
+
+
+def cc_defaults(**kw) -> CcParams:
+    """mav_cc_defaults (8, 1, 256) with the given fields replaced: connectivity, min_area, max_blobs."""
+    p = CcParams()
+    load().mav_cc_defaults(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(CcParams._fields_):
+            raise ValueError(f"unknown connected-components parameter {k!r}")
+        setattr(p, k, int(v))
     return p
 
 
@@ -917,6 +957,49 @@ class Context:
         out = np.empty((gt.shape[0], 4), np.int64)
         check(self.lib.mav_tpr_fpr_counts(self.h, _ptr(gt), _ptr(mask), int(mask_value), gt.shape[0], _ptr(out)))
         return out
+
+    # -- blob detections: connected components of masks (include/mavflow.h: mav_components) ----------------------
+    @staticmethod
+    def _cc_result(B, p, labels, counts, table):
+        """The call's arrays as the dict the three forms return: the table trimmed per image to min(n_blobs, max_blobs) records."""
+        out = dict(n_components=counts["n_components"].copy(), n_blobs=counts["n_blobs"].copy(),
+                   blobs=[table[b, :min(int(counts["n_blobs"][b]), p.max_blobs)] for b in range(B)])
+        if labels is not None:
+            out["labels"] = labels
+        return out
+
+    def components(self, mask, connectivity: int = 8, min_area: int = 1, max_blobs: int = 256, labels: bool = False) -> dict:
+        """Connected components of (batch, H, W) masks (bool or u8; any non-zero byte is set): n_components, n_blobs (batch) int32,
+        blobs = per image the records (BLOB_DTYPE) of the first min(n_blobs, max_blobs) components with area >= min_area in label
+        order, and with labels=True the (batch, H, W) int32 label image, numbered as scipy.ndimage.label does (not as cv2 does)."""
+        mask = np.asarray(mask)
+        mask = self._imgs(mask.view(np.uint8) if mask.dtype == np.bool_ else mask, "mask")
+        B = mask.shape[0]
+        p = cc_defaults(connectivity=connectivity, min_area=min_area, max_blobs=max_blobs)
+        lab = np.empty((B, self.H, self.W), np.int32) if labels else None
+        counts, table = np.empty(B, CC_COUNTS_DTYPE), np.empty((B, max(1, p.max_blobs)), BLOB_DTYPE)
+        check(self.lib.mav_components(self.h, _ptr(mask), B, C.byref(p), _ptr(lab), _ptr(counts), _ptr(table)))
+        return self._cc_result(B, p, lab, counts, table)
+
+    def components_last(self, batch: int, which: str = "fixed", connectivity: int = 8, min_area: int = 1, max_blobs: int = 256,
+                        labels: bool = False) -> dict:
+        """components() of the fixed or dynamic mask the most recent detect / process_batch / phi_mask call left on the device."""
+        if which not in ("fixed", "dynamic"):
+            raise ValueError(f"which must be 'fixed' or 'dynamic', got {which!r}")
+        B = int(batch)
+        p = cc_defaults(connectivity=connectivity, min_area=min_area, max_blobs=max_blobs)
+        lab = np.empty((B, self.H, self.W), np.int32) if labels else None
+        counts, table = np.empty(max(B, 1), CC_COUNTS_DTYPE), np.empty((max(B, 1), max(1, p.max_blobs)), BLOB_DTYPE)
+        check(self.lib.mav_last_masks_components(self.h, int(which == "dynamic"), B, C.byref(p), _ptr(lab), _ptr(counts), _ptr(table)))
+        return self._cc_result(B, p, lab, counts, table)
+
+    def components_dev(self, mask_ptr, batch: int, counts_ptr, blobs_ptr, labels_ptr=None, connectivity: int = 8, min_area: int = 1,
+                       max_blobs: int = 256) -> None:
+        """mav_components_dev: enqueue only, device pointers (ints, or objects with a .ptr such as DeviceBuffer / DeviceArray);
+        counts (batch) CC_COUNTS_DTYPE, blobs (batch, max_blobs) BLOB_DTYPE, labels (batch, H, W) int32 or None."""
+        p = cc_defaults(connectivity=connectivity, min_area=min_area, max_blobs=max_blobs)
+        raw = [getattr(x, "ptr", x) for x in (mask_ptr, labels_ptr, counts_ptr, blobs_ptr)]
+        check(self.lib.mav_components_dev(self.h, raw[0], int(batch), C.byref(p), raw[1], raw[2], raw[3]))
 
     def _detect_args(self, B, samples, omega, dt, frame0, sky, fp):
         samples = _arr(np.asarray(samples).reshape(B, 2 * fp.n_pairs, 2), np.uint32)

@@ -4,7 +4,7 @@ get_flow_vis / apply_colormap (:103-135, the result images' renderers), pyramid 
 parity unpinned at the cv2 boundary -- DESIGN.md section 2)."""
 from __future__ import annotations
 
-from typing import Iterator, Tuple
+from typing import Iterator, List, Tuple
 
 import numpy as np
 
@@ -52,6 +52,31 @@ def get_simple_bounding_box(img: np.ndarray) -> Rectangle:
         raise TypeError("get_simple_bounding_box: u8 or bool image expected (the reference applies it to segmentation masks)")
     H, W = a.shape
     return Rectangle.from_box(_ctx(W, H).bbox(a)[0])
+
+
+def blob_rectangle(blob) -> Rectangle:
+    """A mav_blob record (x, y, w, h as cv2's CC_STAT_*) as a Rectangle in get_simple_bounding_box's inclusive-ends convention
+    (Rectangle.from_points: size = extent - 1)."""
+    x, y, w, h = (int(blob[k]) for k in ("x", "y", "w", "h"))
+    return Rectangle.from_points((x, y), (x + w - 1, y + h - 1))
+
+
+def get_bounding_boxes(img: np.ndarray, connectivity: int = 8, min_area: int = 1, max_blobs: int = 256) -> List[Rectangle]:
+    """The many-object sibling of get_simple_bounding_box: one box per connected component of the pixels above 0.1 * max(img)
+    (the same threshold, the same inclusive-ends Rectangle.from_points convention), components in raster order of their first
+    pixel, those of fewer than min_area pixels dropped, at most max_blobs boxes; an empty mask gives an empty list.  The hull of
+    all boxes (min_area 1, no truncation) is get_simple_bounding_box's.  Labelled on the device (mav_components)."""
+    a = np.asarray(img)
+    if a.ndim == 3:
+        a = a.max(axis=2)
+    if a.dtype == np.bool_:
+        a = a.view(np.uint8)
+    if a.dtype != np.uint8:
+        raise TypeError("get_bounding_boxes: u8 or bool image expected")
+    H, W = a.shape
+    mask = (a > 0.1 * int(a.max())).view(np.uint8)
+    out = _ctx(W, H).components(mask, connectivity=connectivity, min_area=min_area, max_blobs=max_blobs)
+    return [blob_rectangle(b) for b in out["blobs"][0]]
 
 
 def calculate_tpr_fpr(gt_img: np.ndarray, img: np.ndarray) -> Tuple[float, float]:

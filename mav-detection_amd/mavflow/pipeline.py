@@ -524,6 +524,35 @@ class DetectPipeline:
         self._sky_any = None                                  # (shared sky array, does it mask anything)
         self.foe_params = _lib.foe_defaults()
         self.thr_params = _lib.thr_defaults()
+        self.cc_params = None                                 # connected components of the fixed mask inside the step: off
+
+    def set_params(self, foe_params=None, thr_params=None, cc_params=False) -> None:
+        """cc_params: a _lib.CcParams or a dict(connectivity=, min_area=, max_blobs=) switches the step's connected components of the
+        fixed mask on (collect() then also returns "cc_counts" and "blobs"), None switches them off; False leaves them as they are.
+        The slots' result blocks grow by the counts and tables (batch x max_blobs records of 40 bytes): busy slots are waited for."""
+        if foe_params is not None:
+            self.foe_params = foe_params
+        if thr_params is not None:
+            self.thr_params = thr_params
+        if cc_params is False:
+            return
+        if isinstance(cc_params, dict):
+            cc_params = _lib.cc_defaults(**cc_params)
+        ctx, B = self.ctx, self.B
+        cc_bytes = 0 if cc_params is None else B * 8 + B * cc_params.max_blobs * 40
+        if cc_params is not None and (cc_params.connectivity not in (4, 8) or cc_params.min_area < 1
+                                      or not 1 <= cc_params.max_blobs <= _lib.CC_MAX_BLOBS):     # (the step would refuse them; the blocks are sized first)
+            raise ValueError(f"cc_params: connectivity 4 | 8, min_area >= 1, max_blobs 1 .. {_lib.CC_MAX_BLOBS} expected")
+        for s in self.slots:
+            if s.busy:
+                self._wait_slot(s)
+        ctx.sync()
+        self.cc_params = cc_params
+        self._out_bytes = B * 96 + cc_bytes
+        for s in self.slots:
+            s.out.free()
+            s.out = ctx.alloc(self._out_bytes)
+            s.h_out = _lib._pinned.empty(ctx, (self._out_bytes,), np.uint8)
 
     # -- shared images (a segmentation / sky mask that is the same for every frame of the run) ---------------------------------
     def _shared_image(self, kind: str, img: np.ndarray, replicate: int) -> "_lib.DeviceBuffer":
@@ -703,7 +732,10 @@ class DetectPipeline:
         step.mask_fixed_dev, step.mask_dyn_dev, step.out_dev = s.mf.ptr, s.md.ptr, s.out.ptr
         step.off_counts_fixed, step.off_counts_dyn = self.B * 32, 2 * self.B * 32
         s.has_counts = gt_ptr is not None
-        step.out_host, step.out_bytes = s.h_out.ctypes.data, (self._out_bytes if s.has_counts else n * 32)
+        s.cc = self.cc_params
+        if s.cc is not None:                                  # behind the counts: the fixed mask's components, inside the same block
+            step.cc, step.off_cc_counts, step.off_cc_blobs = s.cc, self.B * 96, self.B * 96 + self.B * 8
+        step.out_host, step.out_bytes = s.h_out.ctypes.data, (self._out_bytes if s.has_counts or s.cc is not None else n * 32)
         step.record_done = s.marker
         if self.worker:
             s.ticket = ctx.post_step(step)
@@ -758,7 +790,14 @@ class DetectPipeline:
             flow = [DeviceArray(ctx, s.flow_handle[0] + k * 8 * n0, (ctx.H, ctx.W, 2), np.float32) for k in range(n)]
         for h in mf + md + (flow or []):
             s.handles.append(weakref.ref(h))
-        return dict(results=res, counts_fixed=cf, counts_dyn=cd, mask_fixed=mf, mask_dyn=md, flow=flow)
+        out = dict(results=res, counts_fixed=cf, counts_dyn=cd, mask_fixed=mf, mask_dyn=md, flow=flow)
+        if s.cc is not None:
+            mb = s.cc.max_blobs
+            cc = s.h_out[B * 96:B * 96 + n * 8].view(_lib.CC_COUNTS_DTYPE).copy()
+            table = s.h_out[B * 104:B * 104 + B * mb * 40].view(_lib.BLOB_DTYPE).reshape(B, mb)
+            out["cc_counts"] = cc
+            out["blobs"] = [table[k, :min(int(cc["n_blobs"][k]), mb)].copy() for k in range(n)]
+        return out
 
     def close(self):
         ctx = self.ctx
@@ -873,12 +912,9 @@ class LanedPipeline:
     def ctxs(self):
         return [p.ctx for p in self.pipes]
 
-    def set_params(self, foe_params=None, thr_params=None) -> None:
+    def set_params(self, foe_params=None, thr_params=None, cc_params=False) -> None:
         for p in self.pipes:
-            if foe_params is not None:
-                p.foe_params = foe_params
-            if thr_params is not None:
-                p.thr_params = thr_params
+            p.set_params(foe_params, thr_params, cc_params)
 
     def submit(self, samples, flow=None, **kw):
         if isinstance(flow, DeviceArray) and flow.on_device:

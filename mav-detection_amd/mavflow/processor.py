@@ -191,9 +191,16 @@ def _write_stream(path: str, stream) -> None:
 
 class Processor:
     def __init__(self, config: RunConfig, results_path: Optional[str] = None, images_path: Optional[str] = None,
-                 processed_path: Optional[str] = None, png_encoder: str = "host", algorithm: Optional["Detector.Algorithm"] = None) -> None:
+                 processed_path: Optional[str] = None, png_encoder: str = "host", algorithm: Optional["Detector.Algorithm"] = None,
+                 blobs: Optional[dict] = None) -> None:
         if png_encoder not in ("host", "device"):
             raise ValueError(f"png_encoder must be 'host' or 'device', got {png_encoder!r}")
+        # extra: blobs=dict(connectivity=, min_area=, max_blobs=) (any subset; {} = the defaults 8, 1, 256) labels every frame's fixed mask
+        # on the device, inside the frame's own step, and fills detection_blobs[i] = [(Rectangle, area, (cx, cy)), ...] in label order --
+        # one entry per connected component where detection_boxes[i] is the hull of them all.  None (default): not one launch more.
+        # FrameResult, its JSON and every file the loops write are the same either way.
+        self.blobs = None if blobs is None else _lib.cc_defaults(**blobs)
+        self.detection_blobs: Dict[int, list] = dict()
         self.png_encoder = png_encoder
         self.config = config
         self.logger = config.logger
@@ -250,7 +257,7 @@ class Processor:
             for k in [k for k in self._pipes if k[1] == batch and k != key and set(k[0]) < mine]:
                 self._stale_pipes.append(self._pipes.pop(k))
             pipe = pipeline.LanedPipeline(ctxs, batch)
-            pipe.set_params(foe_params=self.focus_of_expansion._foe_params(1000))
+            pipe.set_params(foe_params=self.focus_of_expansion._foe_params(1000), **({} if self.blobs is None else {"cc_params": self.blobs}))
             self._pipes[key] = pipe
         return pipe
 
@@ -485,6 +492,7 @@ class Processor:
         cluster_vis when it is fetched) per frame, detection_windows[i] and detection_iou[i]; the returned dict is empty, as the reference's is outside debug
         mode.  A field that is not float32 goes through the Detector's two calls (host float64 arithmetic).  flow_vis (:288) is formed
         in debug mode only, which this branch does not reproduce."""
+        self._no_blobs_here()
         if self.debug_mode:
             raise NotImplementedError("debug_mode in the global-motion branch draws with cv2.rectangle and writes a six-image mosaic "
                                       "(processor.py:295-301): not reproduced")
@@ -577,6 +585,7 @@ class Processor:
         loop as it ends the one-frame loop: every earlier frame is stored and written,
         frame_index is the failing index, nothing of later frames is stored."""
         det = self.detector
+        self._no_blobs_here()
         if self.debug_mode:
             raise NotImplementedError("debug_mode in the global-motion branch draws with cv2.rectangle and writes a six-image mosaic "
                                       "(processor.py:295-301): not reproduced")
@@ -723,8 +732,20 @@ class Processor:
         """Images or processed frames are rendered from what a step left resident: the loops finish each step before the next."""
         return self.images_path is not None or self.processed_path is not None
 
+    @staticmethod
+    def _blob_list(records) -> list:
+        """mav_blob records -> [(Rectangle, area, (cx, cy))]: the box in get_simple_bounding_box's convention, the exact centroid."""
+        return [(im_helpers.blob_rectangle(b), int(b["area"]), (int(b["sum_x"]) / int(b["area"]), int(b["sum_y"]) / int(b["area"])))
+                for b in records]
+
+    def _no_blobs_here(self) -> None:
+        if self.blobs is not None:
+            raise NotImplementedError("blobs= labels the FoE branch's fixed mask; the global-motion branch (algorithm HOMOGRAPHY) has no mask")
+
     def _finish_frame(self, pipe, i: int, ticket, sky, orig_frame) -> None:
         out = pipe.collect(ticket)
+        if self.blobs is not None:
+            self.detection_blobs[i] = self._blob_list(out["blobs"][0])
         rec = out["results"][0]
         self.estimate_fixed, self.total_mask = out["mask_fixed"][0], out["mask_dyn"][0]
         r = self._fill_result(i, (float(rec["foe"][0]), float(rec["foe"][1])), sky, out["counts_fixed"][0], out["counts_dyn"][0])
@@ -761,6 +782,10 @@ class Processor:
         foe = self.focus_of_expansion.get_FOE_dense(self.flow_uv_derotated)
         fixed, total = self.focus_of_expansion.get_masks(self.flow_uv_derotated, foe, self.sky_mask)
         self.estimate_fixed, self.total_mask = fixed, total
+        if self.blobs is not None:                            # the fixed mask get_masks left on the helpers' context: not moved again
+            b = self.blobs
+            out = im_helpers._ctx(fixed.shape[1], fixed.shape[0]).components_last(1, "fixed", b.connectivity, b.min_area, b.max_blobs)
+            self.detection_blobs[i] = self._blob_list(out["blobs"][0])
         r = self._fill_result(i, foe, sky, estimate_fixed=fixed, total_mask=total)
         self._store(i, r)
         if self.images_path is not None:                      # the reference-named helpers, as processor.py:364-374 reads
@@ -835,6 +860,8 @@ class Processor:
             rec = out["results"][k]
             r = self._fill_result(i, (float(rec["foe"][0]), float(rec["foe"][1])), sky_scores[k], out["counts_fixed"][k], out["counts_dyn"][k])
             self.detection_boxes[i] = utils.Rectangle.from_box(rec["box"])
+            if self.blobs is not None:
+                self.detection_blobs[i] = self._blob_list(out["blobs"][k])
             self._store(i, r)
             gts.append(r.foe_gt)
         ctx = pipe.pipes[ticket[0]].ctx
