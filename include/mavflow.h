@@ -526,6 +526,60 @@ int mav_worker_drain(mav_ctx*);
  * failure of the step stays for its wait and for the next drain.  MAV_OK at once for ticket 0 or a context that never posted. */
 int mav_worker_wait_enqueued(mav_ctx*, uint64_t ticket);
 
+/* ---- threshold sweep: the TPR / FPR counts of every (angle, magnitude) pair in one pass ---------------------------------------------
+ * The detector's one decision is the fixed mask [src/processor.py:340-341], phi * (mag > fixed_min_mag) * ~sky > fixed_deg, and
+ * mav_result / mav_tpr_fpr_counts report it at one operating point.  The sweep evaluates it at every pair of two lists in ONE pass over
+ * flow, sky and ground truth.
+ *   angles[0 .. n_angles), mags[0 .. n_mags): HOST arrays (copied by the call), each strictly increasing, finite and >= 0;
+ *   1 <= n_angles <= MAV_ROC_MAX_ANGLES, 1 <= n_mags <= MAV_ROC_MAX_MAGS.  Anything else is MAV_ERR_ARG: nothing is enqueued, nothing
+ *   is written.
+ * Per pair of the batch one table of MAV_ROC_TABLE_WORDS(n_angles, n_mags) int64 words:
+ *   pos, neg, then for i in angles, for j in mags: tp[i][j], fp[i][j]
+ * pos / neg are mav_tpr_fpr_counts' first two counts; tp[i][j] / fp[i][j] are its last two for the fixed mask that the detection stage
+ * produces with thr.fixed_deg = angles[i], thr.fixed_min_mag = mags[j] and everything else the same (sky, derotation, frame-0 pairs),
+ * at mask_value 255 -- where a set pixel is a true positive iff gt >= 1 and a false positive iff gt <= 254.
+ * Why >= 0: phi is never NaN (angle_diff[isnan] = 0) and never negative, so for a threshold t >= 0 the reference's product form
+ * phi * gate > t equals gate && phi > t (a closed gate gives 0 > t, false); the mask is then monotone in both thresholds, a pixel
+ * with ia = #{angles < phi} and im = #{mags < mag} (strict comparisons, as the mask's) is set in exactly the cells (i < ia, j < im),
+ * and one histogram of the exact bins gives every cell by a suffix sum.  A negative threshold would set every gated-off and sky pixel.
+ * A NaN magnitude passes no gate.  A frame-0 pair compares as the detection stage does: float32 phi and magnitude against the thresholds
+ * ROUNDED TO FLOAT32 -- two thresholds that collapse to one float32 value give equal cells for such a pair.
+ * Of `thr` only the dynamic mask's fields (dyn_min_mag, dyn_a, dyn_b, dyn_c) are ignored, and fixed_deg / fixed_min_mag are replaced by
+ * the lists: nothing of it is read today, the parameter is there so that the argument list is mav_render's (NULL is fine).  phi and the magnitude are the exact path's bits (no single-precision screen), the counts are integers:
+ * the same call gives the same bytes every time.  No scratch beyond the table. */
+#define MAV_ROC_MAX_ANGLES 64
+#define MAV_ROC_MAX_MAGS 16
+#define MAV_ROC_TABLE_WORDS(ka, km) (2 + 2 * (size_t)(ka) * (km))
+typedef struct {
+    int n_angles, n_mags;
+    const double* angles; /* HOST arrays, copied by the call */
+    const double* mags;
+} mav_roc_params;
+/* flow / foe / omega / dt / frame0 / sky as in mav_render; gt (gt_images, H, W) u8 with gt_images = batch, or 1 = one image shared by
+ * every pair (as mav_tpr_fpr_counts_dev); table (batch, MAV_ROC_TABLE_WORDS).  Host pointers, synchronous. */
+int mav_roc_sweep(mav_ctx*, const float* flow, const double* foe, const double* omega, const double* dt, const uint8_t* frame0,
+                  const uint8_t* sky, const uint8_t* gt, int gt_images, int batch, const mav_thr_params*, const mav_roc_params*,
+                  int64_t* table);
+/* The same on device pointers (all but the parameters' arrays); enqueue only. */
+int mav_roc_sweep_dev(mav_ctx*, const float* flow, const double* foe, const double* omega, const double* dt, const uint8_t* frame0,
+                      const uint8_t* sky, const uint8_t* gt, int gt_images, int batch, const mav_thr_params*, const mav_roc_params*,
+                      int64_t* table);
+/* The same on what the most recent mav_detect / mav_process_batch(_dev) / mav_detect_dev / frame step left resident (flow, derotation
+ * constants, FoE, sky): gt is a host array, the table a host output, synchronous.  MAV_ERR_STATE exactly as mav_last_render.  A
+ * mav_phi_mask / mav_phi_mask_f32 call leaves its field (float64, already derotated; or float32, a frame-0 pair), FoE and sky resident
+ * for this call too -- the staged loop's route -- though not for mav_last_render. */
+int mav_last_roc_sweep(mav_ctx*, const uint8_t* gt, int gt_images, int batch, const mav_roc_params*, int64_t* table);
+/* The loop hook.  mav_frame_step is a frozen layout, so the sweep is armed on the context instead: while armed, every frame step whose
+ * part 5 runs with gt_dev also enqueues the sweep behind the counts and the components -- on the step's own flow_dev, FoE, derotation
+ * block, sky_dev, gt_dev / gt_images and thr -- and writes n tables at out_dev + off_table, so that part 6's one copy carries them.
+ * off_table must be a multiple of 8 (MAV_ERR_ARG here otherwise).  A step with out_host whose out_bytes is smaller than
+ * off_table + n tables is refused with MAV_ERR_ARG before anything of it is enqueued (its markers are still recorded).
+ * params == NULL disarms; disarmed is the default, and then not one launch or byte of a step differs.  The call drains the worker
+ * itself (as mav_frame_step_dev does: it returns a failed step's code that nothing has reported yet, and then changes nothing); it
+ * must still not run concurrently with a thread that posts steps.  The armed state belongs to the CONTEXT: whoever runs steps of
+ * different shapes on one context arms before each (the Python pipelines do). */
+int mav_roc_arm(mav_ctx*, const mav_roc_params* /* NULL: disarm */, size_t off_table);
+
 /* Frame decode in front of the path [src/datasets/dataset.py:57,223-230: cv2.VideoCapture over image_%05d.png; src/farneback.py:17-21]:
  * the un-filtering pass of a PNG image, host memory, no context.  raw = the inflated IDAT stream of a non-interlaced image (per row a
  * filter-type byte + stride bytes), bpp = bytes per complete pixel (1 for bit depths below 8), out = rows x stride bytes.  Filters 0 - 4 of

@@ -782,6 +782,156 @@ void launch_tpr_fpr(hipStream_t st, const uint8_t* gt, const uint8_t* mask, unsi
     launch_tpr_fpr2(st, gt, (size_t)W * H, mask, nullptr, mask_value, B, W, H, counts, nullptr);
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// Threshold sweep (include/mavflow.h: mav_roc_sweep): the tp / fp counts of the fixed mask for every (angle, magnitude) pair of two
+// sorted lists in one pass over flow, sky and ground truth.  The fixed mask  phi * (mag > m) * ~sky > t  is, for t >= 0 and a phi
+// that is never NaN,  ~sky && mag > m && phi > t : monotone in both thresholds.  A pixel with ia = #{angles < phi} and
+// im = #{mags < mag} (strict, as the mask's comparisons) is set in exactly the cells (i < ia, j < im); the kernel counts it once, in
+// the exact bin (ia - 1, im - 1) of a per-workgroup LDS histogram (tp and fp separately: gt >= 1 / gt <= 254 at mask value 255), and
+// k_roc_suffix turns the bins into cells.  phi and the magnitude come from derot_apply / phi_exact (float64 pairs) and phi_pixel_f32
+// (frame-0 pairs, against the thresholds rounded to float32): the bits of k_phi_mask's exact path.  Sky pixels and pixels below the
+// smallest magnitude never reach the arccos; a float64 pair below it skips the square root too (a frame-0 pair always takes sqrtf).  Integer counts: the result does not depend on the order of the additions.
+// Workgroup = 1024 consecutive pixels per step (four per thread, 256 apart: every load is lane-contiguous), grid-strided.
+// A wave whose set pixels all fall into ONE bin (a strong uniform field: every pixel in the top bin) adds its ballot counts once
+// instead of serialising 64 same-address LDS atomics.  FlowT = double: an already derotated float64 field (mav_phi_mask's input).
+template <typename FlowT>
+__global__ __launch_bounds__(256) void k_roc_sweep(const FlowT* __restrict__ flow, const DerotParams* __restrict__ derot,
+                                                   const double* __restrict__ foe, const uint8_t* __restrict__ sky,
+                                                   const uint8_t* __restrict__ gt, size_t gt_stride, int W, int H, RocThr thr,
+                                                   unsigned long long* __restrict__ table)
+{
+    __shared__ unsigned hist[MAV_ROC_MAX_ANGLES * MAV_ROC_MAX_MAGS * 2];
+    __shared__ unsigned part[4][2];
+    const int b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const unsigned npx = (unsigned)W * (unsigned)H;
+    const int ka = thr.ka, km = thr.km, cells2 = ka * km * 2;
+    for (int i = tid; i < cells2; i += 256) hist[i] = 0u;
+    __syncthreads();
+    const FlowT* fl = flow + (size_t)b * npx * 2;
+    const uint8_t* sk = sky ? sky + (size_t)b * npx : nullptr;
+    const uint8_t* g = gt + (size_t)b * gt_stride;
+    const DerotParams* dp = derot ? derot + b : nullptr;
+    const bool f32_pair = std::is_same<FlowT, float>::value && dp && dp->mode == MAV_PAIR_FRAME0;
+    const double foex = foe[2 * b], foey = foe[2 * b + 1];
+    unsigned pos = 0u, neg = 0u;
+    for (unsigned base = blockIdx.x * 1024u; base < npx; base += gridDim.x * 1024u) {
+        decltype(flow_raw(fl, W, 0, 0)) raw[4];
+        unsigned skv[4], gv[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const unsigned p = base + k * 256u + tid;
+            const unsigned q = p < npx ? p : npx - 1u;        // past the end: re-read the last pixel, never counted
+            raw[k] = flow_raw(fl, (int)npx, 0, (int)q);          // pixel q of the image, as one row
+            skv[k] = sk ? sk[q] : 0u;
+            gv[k] = g[q];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const unsigned p = base + k * 256u + tid;
+            const bool valid = p < npx;
+            pos += (valid && gv[k] > 127u) ? 1u : 0u;
+            neg += (valid && (255u - gv[k]) > 127u) ? 1u : 0u;
+            int key = -1;
+            if (valid && skv[k] == 0u) {
+                const int y = (int)(p / (unsigned)W), x = (int)(p - (unsigned)y * (unsigned)W);
+                const double d2x = (double)x - foex, d2y = (double)y - foey;
+                int ia = 0, im = 0;
+                if (f32_pair) {
+                    const float u = (float)raw[k].x, v = (float)raw[k].y;
+                    const float fm = sqrtf(u * u + v * v);                 // phi_pixel_f32's magnitude
+                    for (int j = 0; j < km; j++) im += thr.mag32[j] < fm ? 1 : 0;
+                    if (im) {
+                        const PhiVerdict pv = phi_pixel_f32(u, v, (float)d2x, (float)d2y, 1, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f);
+                        const float ph = (float)pv.ph;                     // the float32 value, widened and back
+                        for (int i = 0; i < ka; i++) ia += thr.ang32[i] < ph ? 1 : 0;
+                    }
+                } else {
+                    double u, v;
+                    derot_apply(raw[k], dp, W, H, y, x, &u, &v);
+                    const double m2 = u * u + v * v;
+                    if (!(m2 < thr.mag0_sq_lo)) {                          // below: sqrt(m2) <= mag[0], no gate passes (NaN goes on)
+                        double fm = sqrt(m2);
+                        for (int j = 0; j < km; j++) im += thr.mag[j] < fm ? 1 : 0;
+                        if (im) {
+                            const double ph = phi_exact(u, v, d2x, d2y, &fm);
+                            for (int i = 0; i < ka; i++) ia += thr.ang[i] < ph ? 1 : 0;
+                        }
+                    }
+                }
+                if (ia > 0 && im > 0) key = (ia - 1) * km + (im - 1);
+            }
+            // every lane of the wave arrives here (the loops above have wave-uniform bounds)
+            const bool tp = key >= 0 && gv[k] >= 1u, fp = key >= 0 && gv[k] <= 254u;
+            const unsigned long long any = __ballot(key >= 0);
+            if (any) {
+                const int first = __shfl(key, __ffsll((long long)any) - 1);
+                if (__ballot(key >= 0 && key != first) == 0ull) {
+                    const unsigned ntp = (unsigned)__popcll(__ballot(tp)), nfp = (unsigned)__popcll(__ballot(fp));
+                    if (lane == 0) {
+                        if (ntp) atomicAdd(&hist[2 * first], ntp);
+                        if (nfp) atomicAdd(&hist[2 * first + 1], nfp);
+                    }
+                } else {
+                    if (tp) atomicAdd(&hist[2 * key], 1u);
+                    if (fp) atomicAdd(&hist[2 * key + 1], 1u);
+                }
+            }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) { pos += __shfl_xor(pos, o); neg += __shfl_xor(neg, o); }
+    if (lane == 0) { part[wv][0] = pos; part[wv][1] = neg; }
+    __syncthreads();                                                       // ... and every wave's histogram updates
+    unsigned long long* tab = table + (size_t)b * MAV_ROC_TABLE_WORDS(ka, km);
+    if (tid < 2) {
+        const unsigned long long v = (unsigned long long)part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid];
+        if (v) atomicAdd(&tab[tid], v);
+    }
+    for (int i = tid; i < cells2; i += 256) {
+        const unsigned v = hist[i];
+        if (v) atomicAdd(&tab[2 + i], (unsigned long long)v);
+    }
+}
+// Exact bins -> cells, in place, one workgroup per pair: cell[i][j] = sum of the bins (a >= i, b >= j), a suffix sum along the
+// magnitudes and then along the angles.
+__global__ __launch_bounds__(256) void k_roc_suffix(unsigned long long* __restrict__ table, int ka, int km)
+{
+    __shared__ unsigned long long s[MAV_ROC_MAX_ANGLES * MAV_ROC_MAX_MAGS * 2];
+    unsigned long long* t = table + (size_t)blockIdx.x * MAV_ROC_TABLE_WORDS(ka, km) + 2;
+    const int tid = threadIdx.x, cells2 = ka * km * 2;
+    for (int i = tid; i < cells2; i += 256) s[i] = t[i];
+    __syncthreads();
+    for (int r = tid; r < ka * 2; r += 256) {
+        const int i = r >> 1, k = r & 1;
+        unsigned long long acc = 0ull;
+        for (int j = km - 1; j >= 0; j--) { acc += s[(i * km + j) * 2 + k]; s[(i * km + j) * 2 + k] = acc; }
+    }
+    __syncthreads();
+    for (int r = tid; r < km * 2; r += 256) {
+        const int j = r >> 1, k = r & 1;
+        unsigned long long acc = 0ull;
+        for (int i = ka - 1; i >= 0; i--) { acc += s[(i * km + j) * 2 + k]; s[(i * km + j) * 2 + k] = acc; }
+    }
+    __syncthreads();
+    for (int i = tid; i < cells2; i += 256) t[i] = s[i];
+}
+hipError_t launch_roc_sweep(hipStream_t st, const void* flow, bool f64, const DerotParams* derot, const double* foe, const uint8_t* sky,
+                      const uint8_t* gt, size_t gt_stride, int B, int W, int H, const RocThr& thr, unsigned long long* table)
+{
+    const size_t npx = (size_t)W * H;
+    const hipError_t e = hipMemsetAsync(table, 0, sizeof(unsigned long long) * MAV_ROC_TABLE_WORDS(thr.ka, thr.km) * B, st);
+    if (e != hipSuccess) return e;                           // bins would be added to whatever the table held
+    // about 1024 workgroups in all: each flushes its non-zero bins with 64-bit atomics, so fewer, longer-lived workgroups per pair
+    const int nblk = (int)((npx + 1023) / 1024), cap = 1024 / B > 0 ? 1024 / B : 1;
+    const dim3 grid(nblk < cap ? nblk : cap, 1, B);
+    if (f64)
+        hipLaunchKernelGGL(k_roc_sweep<double>, grid, dim3(256), 0, st, (const double*)flow, (const DerotParams*)nullptr, foe, sky, gt, gt_stride,
+                           W, H, thr, table);
+    else
+        hipLaunchKernelGGL(k_roc_sweep<float>, grid, dim3(256), 0, st, (const float*)flow, derot, foe, sky, gt, gt_stride, W, H, thr, table);
+    hipLaunchKernelGGL(k_roc_suffix, dim3(B), dim3(256), 0, st, table, thr.ka, thr.km);
+    return hipSuccess;
+}
+
 // cv2.cvtColor(COLOR_BGR2GRAY) on u8 (farneback.py:21,74): fixed point, (B*1868 + G*9617 + R*4899 + 8192) >> 14  (SURVEY A.7).
 __global__ __launch_bounds__(256) void k_bgr2gray(const uint8_t* __restrict__ bgr, size_t n, uint8_t* __restrict__ gray)
 {

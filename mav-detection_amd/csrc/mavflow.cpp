@@ -455,6 +455,12 @@ struct mav_ctx {
         mav_thr_params thr{};
         int batch = 0;
     } last_render;
+    // what mav_last_roc_sweep reads: last_render's fields after a detection call, or the field (float32 or float64), FoE and sky a
+    // mav_phi_mask(_f32) call left in its staging blocks (batch 0: nothing)
+    struct LastRoc {
+        const void* flow = nullptr; bool f64 = false; const DerotParams* derot = nullptr; const double* foe = nullptr; const uint8_t* sky = nullptr;
+        int batch = 0;
+    } last_roc;
     // staging buffers of the host-pointer entry points: slot i of a call re-uses the block slot i of the previous call
     // left behind (grow-only), so the staged path performs no hipMalloc / hipFree once warm
     struct Block { void* p = nullptr; size_t cap = 0; };
@@ -469,6 +475,10 @@ struct mav_ctx {
     uint8_t* cc_ws = nullptr;                   // connected components: label planes + chunk counters of one sub-batch (first call, grow-only
     size_t cc_ws_cap = 0;                       // up to "cc_workspace_mb", or one image's)
     int cc_workspace_mb = 256;                  // option "cc_workspace_mb"
+    // threshold sweep armed for the frame steps (mav_roc_arm): the checked lists and where a step's tables go inside its out block
+    bool roc_armed = false;
+    RocThr roc_thr{};
+    size_t roc_off = 0;
     // global-motion subtraction (mav_global_motion*, mav_find_homography*): per-item scratch (lazily, max_batch), the pair buffers
     // (grow-only, pairs_cap = pairs per item they hold) and what the latest call left resident for mav_last_global_motion_render
     struct Motion {
@@ -1781,6 +1791,7 @@ static int farneback_run(mav_ctx* c, const T* prev, const T* next, int batch, co
     }
     c->last_flow = flow;
     c->last_render.batch = 0;        // the flow a previous detection call read may have been overwritten
+    c->last_roc.batch = 0;
     c->gm.last.batch = 0;
     return MAV_OK;
 }
@@ -1975,6 +1986,7 @@ extern "C" int mav_detect_dev(mav_ctx* c, const float* flow, const uint32_t* sam
     // what mav_last_render reads: the FoE went to the context's own buffer (detect_dev without foe_out)
     c->last_render.flow = flow; c->last_render.derot = a.derot; c->last_render.foe = c->foe_dev; c->last_render.sky = sky;
     c->last_render.thr = t; c->last_render.batch = batch; c->last_render.mask_fixed = mask_fixed;
+    c->last_roc = mav_ctx::LastRoc{flow, false, a.derot, c->foe_dev, sky, batch};
     return MAV_OK;
 }
 
@@ -2035,6 +2047,44 @@ extern "C" int mav_components_dev(mav_ctx* c, const uint8_t* mask, int batch, co
     return components_enqueue(c, mask, batch, p, labels, counts, blobs);
 }
 
+// ---- threshold sweep (include/mavflow.h: mav_roc_sweep) ---------------------------------------------------------------------------
+// The caller's lists, refused before anything is enqueued or written: each 1 .. max entries, finite, >= 0, strictly increasing.
+static int roc_list_checked(const double* v, int n, int max, const char* what, const char* fn)
+{
+    if (n < 1 || n > max) return fail(MAV_ERR_ARG, "%s: %d %s outside [1, %d]", fn, n, what, max);
+    if (!v) return fail(MAV_ERR_ARG, "%s: NULL %s", fn, what);
+    for (int i = 0; i < n; i++) {
+        if (!(v[i] >= 0.0) || !std::isfinite(v[i])) return fail(MAV_ERR_ARG, "%s: %s[%d] = %g is not a finite value >= 0", fn, what, i, v[i]);
+        if (i && !(v[i] > v[i - 1])) return fail(MAV_ERR_ARG, "%s: %s must be strictly increasing (entry %d)", fn, what, i);
+    }
+    return MAV_OK;
+}
+// Every entry point calls this BEFORE it looks at the context, so that a refused list is refused whatever the context is: the order is
+// load-bearing for tests/test_abi_roc.py, which passes refused lists with a handle that must never be dereferenced.
+static int roc_params_checked(const mav_roc_params* p, RocThr* t, const char* fn)
+{
+    if (!p) return fail(MAV_ERR_ARG, "%s: NULL parameters", fn);
+    CHK(roc_list_checked(p->angles, p->n_angles, MAV_ROC_MAX_ANGLES, "angles", fn));
+    CHK(roc_list_checked(p->mags, p->n_mags, MAV_ROC_MAX_MAGS, "mags", fn));
+    *t = RocThr{};
+    t->ka = p->n_angles; t->km = p->n_mags;
+    for (int i = 0; i < t->ka; i++) { t->ang[i] = p->angles[i]; t->ang32[i] = (float)p->angles[i]; }
+    for (int j = 0; j < t->km; j++) { t->mag[j] = p->mags[j]; t->mag32[j] = (float)p->mags[j]; }
+    // a lower bound of mag[0]^2: the product is within half an ulp of it, so one step towards zero is below or on it
+    const double sq = t->mag[0] * t->mag[0];
+    t->mag0_sq_lo = std::isfinite(sq) ? nextafter(sq, 0.0) : 0.0;
+    return MAV_OK;
+}
+// Device pointers, checked lists.  Of the thresholds nothing is read: the lists replace the fixed mask's two, the dynamic ones are ignored.
+static int roc_enqueue(mav_ctx* c, const void* flow, bool f64, const DerotParams* derot, const double* foe, const uint8_t* sky, const uint8_t* gt,
+                       int gt_images, int batch, const RocThr& t, int64_t* table)
+{
+    const size_t stride = gt_images == 1 && batch > 1 ? 0 : c->n0;
+    ProfScope ps(c, K_MISC);
+    HIPCHK(launch_roc_sweep(c->stream, flow, f64, derot, foe, sky, gt, stride, batch, c->W, c->H, t, (unsigned long long*)table));
+    return check_launch("roc sweep");
+}
+
 // ---- one iteration of the reference's loop as one call (include/mavflow.h: mav_frame_step) ---------------------------------------
 static int frame_step_body(mav_ctx* c, const mav_frame_step* s, bool* started);
 static int frame_step_enqueue(mav_ctx* c, const mav_frame_step* s)
@@ -2078,6 +2128,11 @@ static int frame_step_body(mav_ctx* c, const mav_frame_step* s, bool* started)
     for (int i = 0; i < s->n_wait_before; i++)
         if (s->wait_before[i]) HIPCHK(hipEventSynchronize((hipEvent_t)s->wait_before[i]));
     *started = true;                             // from here on a failure may leave work of this step enqueued
+    const bool roc = c->roc_armed && s->detect && s->gt_dev;
+    const size_t roc_bytes = roc ? sizeof(int64_t) * MAV_ROC_TABLE_WORDS(c->roc_thr.ka, c->roc_thr.km) * (size_t)s->n : 0;
+    if (roc && s->out_host && s->out_bytes < c->roc_off + roc_bytes)      // refused like any parameter; the step's markers still fire
+        return fail(MAV_ERR_ARG, "mav_frame_step: out_bytes %zu does not hold the armed sweep's tables (%zu bytes at offset %zu)", s->out_bytes,
+                    roc_bytes, c->roc_off);
     if (s->par_bytes) {
         CHK(mav_upload_async_unordered(c, s->par_dev, s->par_host, s->par_bytes));
     }
@@ -2106,6 +2161,10 @@ static int frame_step_body(mav_ctx* c, const mav_frame_step* s, bool* started)
         if (cc.max_blobs)
             CHK(components_enqueue(c, s->mask_fixed_dev, s->n, cc, nullptr, (mav_cc_counts*)((char*)s->out_dev + s->off_cc_counts),
                                    (mav_blob*)((char*)s->out_dev + s->off_cc_blobs)));
+        if (roc) {                               // on what the detection above read: its flow, derotation block, FoE, sky and thresholds
+            const mav_ctx::LastRender& r = c->last_render;
+            CHK(roc_enqueue(c, r.flow, false, r.derot, r.foe, r.sky, s->gt_dev, s->gt_images, s->n, c->roc_thr, (int64_t*)((char*)s->out_dev + c->roc_off)));
+        }
     }
     if (s->out_bytes) CHK(mav_download_async(c, s->out_host, s->out_dev, s->out_bytes));
     if (s->record_done) HIPCHK(hipEventRecord((hipEvent_t)s->record_done, c->stream));
@@ -2281,6 +2340,7 @@ struct HostCall {
         c->scratch_next = 0;
         c->last_mf = c->last_md = nullptr; c->last_mask_batch = 0;     // ... and may overwrite the previous call's masks
         c->last_render.batch = 0;                                       // ... and its flow, FoE and sky
+        c->last_roc.batch = 0;
         c->gm.last.batch = 0;                                           // ... and the flow and matrix of a global-motion call
         return MAV_OK;
     }
@@ -2476,6 +2536,7 @@ static int phi_mask_host(mav_ctx* c, const char* fn, const T* flow, const double
     if constexpr (f32) CHK(frame0_params(c, batch, &a.derot));
     CHK(detect_dev(c, batch, a));
     c->last_mf = a.mask_fixed; c->last_md = a.mask_dyn; c->last_mask_batch = batch;
+    c->last_roc = mav_ctx::LastRoc{f32 ? (const void*)a.flow32 : (const void*)a.flow64, !f32, a.derot, a.foe_in, a.sky, batch};
     CHK(h.finish());
     if (f32 && phi) for (size_t i = 0; i < n; i++) phi[i] = (T)wide[i];
     if (f32 && max_phi) for (int b = 0; b < batch; b++) max_phi[b] = (T)mx[b];
@@ -3154,6 +3215,79 @@ extern "C" int mav_last_render(mav_ctx* c, int batch, uint8_t* img_result, uint8
     const mav_ctx::LastRender& r = c->last_render;
     CHK(render_enqueue(c, r.flow, r.derot, r.foe, r.sky, batch, r.thr, dres, dfl, dphi));
     return h.finish();
+}
+
+// ---- threshold sweep: the entry points (the core is in front of the frame step) -------------------------------------------------------
+static int roc_gt_images_checked(int gt_images, int batch, const char* fn)
+{
+    if (gt_images != 1 && gt_images != batch) return fail(MAV_ERR_ARG, "%s: gt_images must be 1 (shared) or batch (%d), got %d", fn, batch, gt_images);
+    return MAV_OK;
+}
+extern "C" int mav_roc_sweep_dev(mav_ctx* c, const float* flow, const double* foe, const double* omega, const double* dt, const uint8_t* frame0,
+                                 const uint8_t* sky, const uint8_t* gt, int gt_images, int batch, const mav_thr_params* tp,
+                                 const mav_roc_params* rp, int64_t* table)
+{
+    (void)tp;                                    // nothing of it is read: the lists replace its fixed fields, the dynamic ones are ignored
+    if (!c || !flow || !foe || !gt || !table) return fail(MAV_ERR_ARG, "mav_roc_sweep_dev: NULL argument");
+    RocThr t;
+    CHK(roc_params_checked(rp, &t, "mav_roc_sweep_dev"));
+    CHK(check_dev_call(c, batch, "mav_roc_sweep_dev"));
+    CHK(roc_gt_images_checked(gt_images, batch, "mav_roc_sweep_dev"));
+    CHK(ensure_render(c));
+    const DerotParams* derot = nullptr;
+    CHK(upload_derot(c, omega, dt, frame0, batch, false, &derot, c->render_derot));
+    return roc_enqueue(c, flow, false, derot, foe, sky, gt, gt_images, batch, t, table);
+}
+extern "C" int mav_roc_sweep(mav_ctx* c, const float* flow, const double* foe, const double* omega, const double* dt, const uint8_t* frame0,
+                             const uint8_t* sky, const uint8_t* gt, int gt_images, int batch, const mav_thr_params* tp,
+                             const mav_roc_params* rp, int64_t* table)
+{
+    if (!c || !flow || !foe || !gt || !table) return fail(MAV_ERR_ARG, "mav_roc_sweep: NULL argument");
+    RocThr t;
+    CHK(roc_params_checked(rp, &t, "mav_roc_sweep"));
+    HostCall h(c, "mav_roc_sweep");
+    CHK(h.fresh(batch));
+    CHK(roc_gt_images_checked(gt_images, batch, "mav_roc_sweep"));
+    const size_t n = c->n0 * batch;
+    const float* df = h.in(flow, n * 2 * sizeof(float));
+    const double* dfoe = h.in(foe, sizeof(double) * 2 * batch);
+    const uint8_t* dsky = h.in(sky, n);
+    const uint8_t* dgt = h.in(gt, c->n0 * gt_images);
+    const double* dom = h.in(omega, sizeof(double) * 3 * batch);
+    const double* ddt = h.in(omega ? dt : nullptr, sizeof(double) * batch);
+    const uint8_t* df0 = h.in(frame0, batch);
+    int64_t* dtab = h.out(table, sizeof(int64_t) * MAV_ROC_TABLE_WORDS(t.ka, t.km) * batch);
+    CHK(h.staged());
+    CHK(mav_roc_sweep_dev(c, df, dfoe, dom, ddt, df0, dsky, dgt, gt_images, batch, tp, rp, dtab));
+    return h.finish();
+}
+extern "C" int mav_last_roc_sweep(mav_ctx* c, const uint8_t* gt, int gt_images, int batch, const mav_roc_params* rp, int64_t* table)
+{
+    if (!c || !gt || !table) return fail(MAV_ERR_ARG, "mav_last_roc_sweep: NULL argument");
+    RocThr t;
+    CHK(roc_params_checked(rp, &t, "mav_last_roc_sweep"));
+    if (!c->last_roc.batch || batch != c->last_roc.batch)
+        return fail(MAV_ERR_STATE, "mav_last_roc_sweep: no flow of a %d-pair detection call is resident", batch);
+    CHK(roc_gt_images_checked(gt_images, batch, "mav_last_roc_sweep"));
+    HostCall h(c, "mav_last_roc_sweep");
+    CHK(h.after_last());
+    const uint8_t* dgt = h.in(gt, c->n0 * gt_images);
+    int64_t* dtab = h.out(table, sizeof(int64_t) * MAV_ROC_TABLE_WORDS(t.ka, t.km) * batch);
+    CHK(h.staged());
+    const mav_ctx::LastRoc& r = c->last_roc;
+    CHK(roc_enqueue(c, r.flow, r.f64, r.derot, r.foe, r.sky, dgt, gt_images, batch, t, dtab));
+    return h.finish();
+}
+extern "C" int mav_roc_arm(mav_ctx* c, const mav_roc_params* rp, size_t off_table)
+{
+    if (!c) return fail(MAV_ERR_ARG, "mav_roc_arm: NULL context");
+    RocThr t;
+    if (rp) CHK(roc_params_checked(rp, &t, "mav_roc_arm"));
+    if (rp && off_table % 8) return fail(MAV_ERR_ARG, "mav_roc_arm: off_table %zu is not a multiple of 8", off_table);
+    CHK(mav_worker_drain(c));                    // the worker reads this state while it enqueues posted steps (as mav_frame_step_dev drains)
+    if (!rp) { c->roc_armed = false; return MAV_OK; }
+    c->roc_thr = t; c->roc_off = off_table; c->roc_armed = true;
+    return MAV_OK;
 }
 
 extern "C" int mav_flow_to_color(mav_ctx* c, const void* flow, int f64, int batch, uint8_t* img)

@@ -174,6 +174,20 @@ void launch_tpr_fpr(hipStream_t st, const uint8_t* gt, const uint8_t* mask, unsi
 // one pass over gt for one mask (mask1 = counts1 = nullptr) or two; gt_stride = 0: one ground-truth image for every pair
 void launch_tpr_fpr2(hipStream_t st, const uint8_t* gt, size_t gt_stride, const uint8_t* mask0, const uint8_t* mask1, unsigned mask_value, int B,
                      int W, int H, unsigned long long* counts0 /*[B][4]*/, unsigned long long* counts1 /*[B][4]*/);
+// Threshold sweep (mav_roc_sweep): the checked lists of one call, passed to the kernel by value.  ang32 / mag32: the thresholds rounded
+// to float32 (what a frame-0 pair compares against); mag0_sq_lo <= mag[0]^2 (rounded down on the host): a double pair with
+// u*u + v*v below it passes no magnitude gate and needs no square root.
+struct RocThr {
+    int ka, km;
+    double mag0_sq_lo;
+    double ang[MAV_ROC_MAX_ANGLES], mag[MAV_ROC_MAX_MAGS];
+    float ang32[MAV_ROC_MAX_ANGLES], mag32[MAV_ROC_MAX_MAGS];
+};
+// table: B x MAV_ROC_TABLE_WORDS(ka, km) int64 (zeroed here); gt_stride = 0: one ground-truth image for every pair
+// flow: float32 (derot says how each pair is treated) or, with f64, an already derotated float64 field (derot is not read)
+// returns the table fill's error, if any (nothing is launched then)
+hipError_t launch_roc_sweep(hipStream_t st, const void* flow, bool f64, const DerotParams* derot /*dev, [B] or null*/, const double* foe,
+                      const uint8_t* sky, const uint8_t* gt, size_t gt_stride, int B, int W, int H, const RocThr& thr, unsigned long long* table);
 void launch_bgr2gray(hipStream_t st, const uint8_t* bgr, size_t n, uint8_t* gray);
 void launch_ransac_only(hipStream_t st, FoeScratch s, int M, int N, double dist2_thr, double* foe);
 void launch_make_derot(hipStream_t st, const double* omega /*null: no rotation*/, const double* dt, const uint8_t* frame0, int B,

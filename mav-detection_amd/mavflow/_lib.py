@@ -90,6 +90,38 @@ BLOB_DTYPE = np.dtype([("label", np.int32), ("x", np.int32), ("y", np.int32), ("
 assert BLOB_DTYPE.itemsize == C.sizeof(Blob) == 40 and CC_COUNTS_DTYPE.itemsize == C.sizeof(CcCounts) == 8
 CC_TILE_W, CC_TILE_H, CC_MAX_BLOBS = 64, 16, 65535      # MAV_CC_TILE_W / _H (the first pass's tile), MAV_CC_MAX_BLOBS
 
+
+class RocParams(C.Structure):
+    """mav_roc_params: the two threshold lists of a sweep (host arrays, copied by each call)."""
+    _fields_ = [("n_angles", C.c_int), ("n_mags", C.c_int), ("angles", C.POINTER(C.c_double)), ("mags", C.POINTER(C.c_double))]
+
+
+ROC_MAX_ANGLES, ROC_MAX_MAGS = 64, 16                    # MAV_ROC_MAX_ANGLES / MAV_ROC_MAX_MAGS
+
+
+def roc_table_words(ka: int, km: int) -> int:
+    """MAV_ROC_TABLE_WORDS: pos, neg, then (tp, fp) per (angle, magnitude) cell."""
+    return 2 + 2 * int(ka) * int(km)
+
+
+def roc_params(angles, mags):
+    """(RocParams, angles, mags): the lists as contiguous float64 arrays (which the struct points into: keep them alive with it).
+    The library checks them (strictly increasing, finite, >= 0, 1 .. 64 angles and 1 .. 16 magnitudes)."""
+    a = np.ascontiguousarray(np.asarray(angles, np.float64).reshape(-1))
+    m = np.ascontiguousarray(np.asarray(mags, np.float64).reshape(-1))
+    p = RocParams(a.size, m.size, a.ctypes.data_as(C.POINTER(C.c_double)), m.ctypes.data_as(C.POINTER(C.c_double)))
+    return p, a, m
+
+
+def roc_expand(table: np.ndarray, ka: int, km: int) -> np.ndarray:
+    """(B, words) int64 tables -> (B, ka, km, 4) = pos, neg, tp, fp per cell, as tpr_fpr_counts orders them."""
+    table = np.asarray(table, np.int64).reshape(-1, roc_table_words(ka, km))
+    out = np.empty((table.shape[0], ka, km, 4), np.int64)
+    out[..., 0] = table[:, 0, None, None]
+    out[..., 1] = table[:, 1, None, None]
+    out[..., 2:] = table[:, 2:].reshape(-1, ka, km, 2)
+    return out
+
 # every symbol include/mavflow.h declares (tests check the library exports each of them)
 EXPORTS = [
     "mav_fb_defaults", "mav_foe_defaults", "mav_thr_defaults", "mav_create", "mav_destroy", "mav_last_error",
@@ -121,6 +153,7 @@ EXPORTS = [
     "mav_global_motion_dev", "mav_global_motion_step_dev", "mav_last_global_motion_render", "mav_global_motion_batch",
     "mav_global_motion_batch_dev",
     "mav_cc_defaults", "mav_components", "mav_components_dev", "mav_last_masks_components",
+    "mav_roc_sweep", "mav_roc_sweep_dev", "mav_last_roc_sweep", "mav_roc_arm",
 ]
 
 # Frame depths of the _ex entry points (cv2's depth codes) by numpy dtype.  uint8 frames keep going through the u8 symbols.
@@ -345,6 +378,11 @@ def load(path: str | None = None) -> C.CDLL:
     lib.mav_components.argtypes = [vp, vp, C.c_int, C.POINTER(CcParams), vp, vp, vp]
     lib.mav_components_dev.argtypes = [vp, vp, C.c_int, C.POINTER(CcParams), vp, vp, vp]
     lib.mav_last_masks_components.argtypes = [vp, C.c_int, C.c_int, C.POINTER(CcParams), vp, vp, vp]
+    rp = C.POINTER(RocParams)
+    lib.mav_roc_sweep.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(ThrParams), rp, vp]
+    lib.mav_roc_sweep_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(ThrParams), rp, vp]
+    lib.mav_last_roc_sweep.argtypes = [vp, vp, C.c_int, C.c_int, rp, vp]
+    lib.mav_roc_arm.argtypes = [vp, rp, C.c_size_t]
     _lib = lib
     return lib
 
@@ -1106,6 +1144,71 @@ class Context:
         out = self._image_outs(batch, images)
         check(self.lib.mav_last_render(self.h, int(batch), _ptr(out["result"]), _ptr(out["flow"]), _ptr(out["phi"])))
         return {k: v for k, v in out.items() if v is not None}
+
+    # -- threshold sweep (include/mavflow.h: mav_roc_sweep) ------------------------------------------------------
+    def _roc_gt(self, gt, B):
+        """(gt array (gt_images, H, W) u8, gt_images): one image per pair, or one 2-D image shared by every pair"""
+        gt = np.asarray(gt)
+        shared = gt.ndim == 2
+        gt = self._imgs(gt, "gt")
+        if not shared and gt.shape[0] != B:
+            raise ValueError(f"gt: {gt.shape[0]} images for {B} pairs (a 2-D image is shared by every pair)")
+        return gt, (1 if shared else B)
+
+    def roc_sweep(self, flow, foe, gt, angles, mags, omega=None, dt=None, sky=None, frame0=None, thr_params=None) -> dict:
+        """The fixed mask's TPR / FPR counts at every (angle, magnitude) pair in one pass: counts (B, Ka, Km, 4) int64 = pos, neg, tp,
+        fp, where counts[b, i, j] is tpr_fpr_counts(gt, fixed mask at fixed_deg = angles[i], fixed_min_mag = mags[j])[b].  flow / foe /
+        omega / dt / sky / frame0 as for render(); gt (B, H, W) u8, or (H, W) = one image shared by every pair."""
+        flow = np.asarray(flow)
+        if flow.dtype != np.float32:
+            raise TypeError(f"roc_sweep() takes a float32 flow field, got {flow.dtype}")
+        flow = flow[None] if flow.ndim == 3 else flow
+        B = flow.shape[0]
+        flow = _arr(flow, np.float32, (B, self.H, self.W, 2), "flow")
+        foe = _arr(np.asarray(foe, np.float64).reshape(B, 2), np.float64)
+        omega = None if omega is None else _arr(np.asarray(omega, np.float64).reshape(B, 3), np.float64)
+        dt = None if dt is None else _arr(np.asarray(dt, np.float64).reshape(B), np.float64)
+        frame0 = None if frame0 is None else _arr(np.asarray(frame0).reshape(B).astype(np.uint8), np.uint8)
+        sky = None if sky is None else _arr(np.asarray(sky).reshape(B, self.H, self.W).astype(np.uint8), np.uint8)
+        gt, gt_images = self._roc_gt(gt, B)
+        tp = thr_params or thr_defaults()
+        p, a, m = roc_params(angles, mags)
+        table = np.empty((B, roc_table_words(a.size, m.size)), np.int64)
+        check(self.lib.mav_roc_sweep(self.h, _ptr(flow), _ptr(foe), _ptr(omega), _ptr(dt), _ptr(frame0), _ptr(sky), _ptr(gt), gt_images, B,
+                                     C.byref(tp), C.byref(p), _ptr(table)))
+        return dict(counts=roc_expand(table, a.size, m.size), angles=a, mags=m)
+
+    def roc_sweep_last(self, batch: int, gt, angles, mags) -> dict:
+        """roc_sweep() of what the most recent detect / process_batch(_dev) / frame step left on the device (flow, FoE, sky,
+        derotation): only the ground truth goes up and the tables come down."""
+        B = int(batch)
+        gt, gt_images = self._roc_gt(gt, B)
+        p, a, m = roc_params(angles, mags)
+        table = np.empty((max(B, 1), roc_table_words(a.size, m.size)), np.int64)
+        check(self.lib.mav_last_roc_sweep(self.h, _ptr(gt), gt_images, B, C.byref(p), _ptr(table)))
+        return dict(counts=roc_expand(table[:B], a.size, m.size), angles=a, mags=m)
+
+    def roc_sweep_dev(self, flow_ptr, foe_ptr, gt_ptr, gt_images: int, batch: int, angles, mags, table_ptr, omega_ptr=None, dt_ptr=None,
+                      frame0_ptr=None, sky_ptr=None, thr_params=None) -> None:
+        """mav_roc_sweep_dev: enqueue only, device pointers (ints, or objects with a .ptr); table (batch, roc_table_words) int64."""
+        tp = thr_params or thr_defaults()
+        p, a, m = roc_params(angles, mags)
+        raw = [getattr(x, "ptr", x) for x in (flow_ptr, foe_ptr, omega_ptr, dt_ptr, frame0_ptr, sky_ptr, gt_ptr, table_ptr)]
+        check(self.lib.mav_roc_sweep_dev(self.h, *raw[:7], int(gt_images), int(batch), C.byref(tp), C.byref(p), raw[7]))
+
+    def roc_arm(self, angles, mags=None, off_table: int = 0) -> None:
+        """mav_roc_arm: while armed, every frame step with a ground truth also writes its pairs' sweep tables at out_dev + off_table.
+        roc_arm(None) disarms.  The state is the context's, one for all its users: roc_state is what this binding last armed
+        (angles bytes, mags bytes, off_table; None = disarmed), by which the pipelines that share a context see whose it is."""
+        if angles is None:
+            check(self.lib.mav_roc_arm(self.h, None, 0))
+            self.roc_state = None
+            return
+        p, a, m = roc_params(angles, mags)
+        check(self.lib.mav_roc_arm(self.h, C.byref(p), int(off_table)))
+        self.roc_state = (a.tobytes(), m.tobytes(), int(off_table))
+
+    roc_state = None
 
     def flow_to_color(self, flow) -> np.ndarray:
         """flow_vis.flow_to_color(flow, convert_to_bgr=True) of (B, H, W, 2) fields in their own float type -> (B, H, W, 3) u8."""

@@ -525,17 +525,25 @@ class DetectPipeline:
         self.foe_params = _lib.foe_defaults()
         self.thr_params = _lib.thr_defaults()
         self.cc_params = None                                 # connected components of the fixed mask inside the step: off
+        self.roc = None                                       # threshold sweep inside the step (angles, mags): the context is not armed
+        self._roc_off = 0
 
-    def set_params(self, foe_params=None, thr_params=None, cc_params=False) -> None:
+    def set_params(self, foe_params=None, thr_params=None, cc_params=False, roc=False) -> None:
         """cc_params: a _lib.CcParams or a dict(connectivity=, min_area=, max_blobs=) switches the step's connected components of the
         fixed mask on (collect() then also returns "cc_counts" and "blobs"), None switches them off; False leaves them as they are.
-        The slots' result blocks grow by the counts and tables (batch x max_blobs records of 40 bytes): busy slots are waited for."""
+        roc: a dict(angles=, mags=) arms the context's threshold sweep (mav_roc_arm): every batch submitted with a ground truth then
+        also returns "roc", the (n, Ka, Km, 4) int64 counts (pos, neg, tp, fp) of the fixed mask at every threshold pair; None disarms;
+        False leaves it as it is.
+        The slots' result blocks grow by the counts and tables (batch x max_blobs records of 40 bytes, then batch sweep tables): busy
+        slots are waited for."""
         if foe_params is not None:
             self.foe_params = foe_params
         if thr_params is not None:
             self.thr_params = thr_params
-        if cc_params is False:
+        if cc_params is False and roc is False:
             return
+        if cc_params is False:
+            cc_params = self.cc_params
         if isinstance(cc_params, dict):
             cc_params = _lib.cc_defaults(**cc_params)
         ctx, B = self.ctx, self.B
@@ -543,16 +551,48 @@ class DetectPipeline:
         if cc_params is not None and (cc_params.connectivity not in (4, 8) or cc_params.min_area < 1
                                       or not 1 <= cc_params.max_blobs <= _lib.CC_MAX_BLOBS):     # (the step would refuse them; the blocks are sized first)
             raise ValueError(f"cc_params: connectivity 4 | 8, min_area >= 1, max_blobs 1 .. {_lib.CC_MAX_BLOBS} expected")
+        if roc is False:
+            roc = self.roc
+        elif roc is not None:
+            if not isinstance(roc, dict) or set(roc) != {"angles", "mags"}:
+                raise ValueError("roc: dict(angles=, mags=) or None expected")
+            _, a, m = _lib.roc_params(roc["angles"], roc["mags"])
+            for name, v, cap in (("angles", a, _lib.ROC_MAX_ANGLES), ("mags", m, _lib.ROC_MAX_MAGS)):   # (mav_roc_arm refuses them too; the blocks are sized first)
+                if not 1 <= v.size <= cap or not np.all(np.isfinite(v)) or np.any(v < 0) or np.any(np.diff(v) <= 0):
+                    raise ValueError(f"roc: {name} must be 1 .. {cap} finite values >= 0, strictly increasing")
+            roc = (a, m)
         for s in self.slots:
             if s.busy:
                 self._wait_slot(s)
         ctx.sync()
-        self.cc_params = cc_params
-        self._out_bytes = B * 96 + cc_bytes
+        self._release_roc()                                  # the tables' offset moves with the blocks: armed again by the next submit
+        self.cc_params, self.roc = cc_params, roc
+        self._roc_off = B * 96 + cc_bytes                    # a multiple of 8
+        self._out_bytes = self._roc_off + (0 if roc is None else B * 8 * _lib.roc_table_words(roc[0].size, roc[1].size))
         for s in self.slots:
             s.out.free()
             s.out = ctx.alloc(self._out_bytes)
             s.h_out = _lib._pinned.empty(ctx, (self._out_bytes,), np.uint8)
+
+    # The sweep is armed on the CONTEXT, which several pipelines may share (the loops keep pipelines of different batches, and of
+    # growing lane sets, alive on the same contexts) and whose tables' offset depends on the pipeline's blocks: the armed state follows
+    # the pipeline that is about to run.  A change drains the context's worker first (Context.h), so steps already posted are enqueued
+    # under the state they were submitted under.
+    def _roc_want(self):
+        return None if self.roc is None else (self.roc[0].tobytes(), self.roc[1].tobytes(), self._roc_off)
+
+    def _claim_roc(self) -> None:
+        """before a step is submitted: the context armed with this pipeline's lists at this pipeline's offset, or disarmed"""
+        if self.ctx.roc_state != self._roc_want():
+            if self.roc is None:
+                self.ctx.roc_arm(None)
+            else:
+                self.ctx.roc_arm(self.roc[0], self.roc[1], self._roc_off)
+
+    def _release_roc(self) -> None:
+        """disarm the context if it is this pipeline's arming that it carries (never another pipeline's)"""
+        if self.roc is not None and self.ctx.roc_state == self._roc_want():
+            self.ctx.roc_arm(None)
 
     # -- shared images (a segmentation / sky mask that is the same for every frame of the run) ---------------------------------
     def _shared_image(self, kind: str, img: np.ndarray, replicate: int) -> "_lib.DeviceBuffer":
@@ -732,11 +772,13 @@ class DetectPipeline:
         step.mask_fixed_dev, step.mask_dyn_dev, step.out_dev = s.mf.ptr, s.md.ptr, s.out.ptr
         step.off_counts_fixed, step.off_counts_dyn = self.B * 32, 2 * self.B * 32
         s.has_counts = gt_ptr is not None
+        s.roc = self.roc if s.has_counts else None            # the armed context sweeps every step that has a ground truth
         s.cc = self.cc_params
         if s.cc is not None:                                  # behind the counts: the fixed mask's components, inside the same block
             step.cc, step.off_cc_counts, step.off_cc_blobs = s.cc, self.B * 96, self.B * 96 + self.B * 8
         step.out_host, step.out_bytes = s.h_out.ctypes.data, (self._out_bytes if s.has_counts or s.cc is not None else n * 32)
         step.record_done = s.marker
+        self._claim_roc()
         if self.worker:
             s.ticket = ctx.post_step(step)
         else:
@@ -797,6 +839,10 @@ class DetectPipeline:
             table = s.h_out[B * 104:B * 104 + B * mb * 40].view(_lib.BLOB_DTYPE).reshape(B, mb)
             out["cc_counts"] = cc
             out["blobs"] = [table[k, :min(int(cc["n_blobs"][k]), mb)].copy() for k in range(n)]
+        if s.roc is not None:
+            ka, km = s.roc[0].size, s.roc[1].size
+            words = _lib.roc_table_words(ka, km)
+            out["roc"] = _lib.roc_expand(s.h_out[self._roc_off:self._roc_off + n * words * 8].view(np.int64), ka, km)
         return out
 
     def close(self):
@@ -811,6 +857,8 @@ class DetectPipeline:
                     s.busy = False
             _retire_all(s.handles)
         ctx.sync()
+        self._release_roc()                                   # the context outlives the pipeline; another pipeline's arming stays
+        self.roc = None
         for s in self.slots:
             for b in (s.frames, s.flow_in, s.flow_out, s.mf, s.md, s.par, s.out, s.sky, s.gt):
                 if b is not None:
@@ -912,9 +960,9 @@ class LanedPipeline:
     def ctxs(self):
         return [p.ctx for p in self.pipes]
 
-    def set_params(self, foe_params=None, thr_params=None, cc_params=False) -> None:
+    def set_params(self, foe_params=None, thr_params=None, cc_params=False, roc=False) -> None:
         for p in self.pipes:
-            p.set_params(foe_params, thr_params, cc_params)
+            p.set_params(foe_params, thr_params, cc_params, roc)
 
     def submit(self, samples, flow=None, **kw):
         if isinstance(flow, DeviceArray) and flow.on_device:

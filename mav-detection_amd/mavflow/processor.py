@@ -192,7 +192,7 @@ def _write_stream(path: str, stream) -> None:
 class Processor:
     def __init__(self, config: RunConfig, results_path: Optional[str] = None, images_path: Optional[str] = None,
                  processed_path: Optional[str] = None, png_encoder: str = "host", algorithm: Optional["Detector.Algorithm"] = None,
-                 blobs: Optional[dict] = None) -> None:
+                 blobs: Optional[dict] = None, roc: Optional[dict] = None) -> None:
         if png_encoder not in ("host", "device"):
             raise ValueError(f"png_encoder must be 'host' or 'device', got {png_encoder!r}")
         # extra: blobs=dict(connectivity=, min_area=, max_blobs=) (any subset; {} = the defaults 8, 1, 256) labels every frame's fixed mask
@@ -201,6 +201,16 @@ class Processor:
         # FrameResult, its JSON and every file the loops write are the same either way.
         self.blobs = None if blobs is None else _lib.cc_defaults(**blobs)
         self.detection_blobs: Dict[int, list] = dict()
+        # extra: roc=dict(angles=[...], mags=[...]) sweeps the fixed mask's two thresholds (processor.py:340-341: 15 degrees, 1.0 px) over
+        # both lists in the frame's own step and fills roc_counts[i], a (Ka, Km, 4) int64 array of calculate_tpr_fpr's sums (pos, neg, tp,
+        # fp) per threshold pair; roc_rates() divides them.  None (default): not one launch more; results and files are the same either way.
+        self.roc = None
+        if roc is not None:
+            if set(roc) != {"angles", "mags"}:
+                raise ValueError("roc: dict(angles=[...], mags=[...]) expected")
+            _, a, m = _lib.roc_params(roc["angles"], roc["mags"])
+            self.roc = dict(angles=a, mags=m)
+        self.roc_counts: Dict[int, np.ndarray] = dict()
         self.png_encoder = png_encoder
         self.config = config
         self.logger = config.logger
@@ -257,7 +267,8 @@ class Processor:
             for k in [k for k in self._pipes if k[1] == batch and k != key and set(k[0]) < mine]:
                 self._stale_pipes.append(self._pipes.pop(k))
             pipe = pipeline.LanedPipeline(ctxs, batch)
-            pipe.set_params(foe_params=self.focus_of_expansion._foe_params(1000), **({} if self.blobs is None else {"cc_params": self.blobs}))
+            pipe.set_params(foe_params=self.focus_of_expansion._foe_params(1000), **({} if self.blobs is None else {"cc_params": self.blobs}),
+                            **({} if self.roc is None else {"roc": self.roc}))
             self._pipes[key] = pipe
         return pipe
 
@@ -493,6 +504,7 @@ class Processor:
         mode.  A field that is not float32 goes through the Detector's two calls (host float64 arithmetic).  flow_vis (:288) is formed
         in debug mode only, which this branch does not reproduce."""
         self._no_blobs_here()
+        self._no_roc_here()
         if self.debug_mode:
             raise NotImplementedError("debug_mode in the global-motion branch draws with cv2.rectangle and writes a six-image mosaic "
                                       "(processor.py:295-301): not reproduced")
@@ -586,6 +598,7 @@ class Processor:
         frame_index is the failing index, nothing of later frames is stored."""
         det = self.detector
         self._no_blobs_here()
+        self._no_roc_here()
         if self.debug_mode:
             raise NotImplementedError("debug_mode in the global-motion branch draws with cv2.rectangle and writes a six-image mosaic "
                                       "(processor.py:295-301): not reproduced")
@@ -742,8 +755,27 @@ class Processor:
         if self.blobs is not None:
             raise NotImplementedError("blobs= labels the FoE branch's fixed mask; the global-motion branch (algorithm HOMOGRAPHY) has no mask")
 
+    def _no_roc_here(self) -> None:
+        if self.roc is not None:
+            raise NotImplementedError("roc= sweeps the FoE branch's fixed mask; the global-motion branch (algorithm HOMOGRAPHY) has no mask")
+
+    def roc_rates(self) -> dict:
+        """The sweep's rates: tpr / fpr per frame (n, Ka, Km) float64 = tp / pos and fp / neg as calculate_tpr_fpr divides (NaN where a
+        frame has no positives / negatives), frames in index order; tpr_pooled / fpr_pooled (Ka, Km): the sums over the frames, then
+        one division."""
+        if self.roc is None:
+            raise ValueError("roc_rates() needs Processor(roc=dict(angles=, mags=))")
+        ka, km = self.roc["angles"].size, self.roc["mags"].size
+        c = (np.stack([self.roc_counts[i] for i in sorted(self.roc_counts)]) if self.roc_counts else np.zeros((0, ka, km, 4), np.int64)).astype(np.float64)
+        tot = c.sum(axis=0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return dict(angles=self.roc["angles"], mags=self.roc["mags"], tpr=c[..., 2] / c[..., 0], fpr=c[..., 3] / c[..., 1],
+                        tpr_pooled=tot[..., 2] / tot[..., 0], fpr_pooled=tot[..., 3] / tot[..., 1])
+
     def _finish_frame(self, pipe, i: int, ticket, sky, orig_frame) -> None:
         out = pipe.collect(ticket)
+        if self.roc is not None:
+            self.roc_counts[i] = out["roc"][0]
         if self.blobs is not None:
             self.detection_blobs[i] = self._blob_list(out["blobs"][0])
         rec = out["results"][0]
@@ -786,6 +818,9 @@ class Processor:
             b = self.blobs
             out = im_helpers._ctx(fixed.shape[1], fixed.shape[0]).components_last(1, "fixed", b.connectivity, b.min_area, b.max_blobs)
             self.detection_blobs[i] = self._blob_list(out["blobs"][0])
+        if self.roc is not None:                              # the field, FoE and sky get_masks left on the helpers' context: not moved again
+            out = im_helpers._ctx(fixed.shape[1], fixed.shape[0]).roc_sweep_last(1, self._segmentation(i)[0], self.roc["angles"], self.roc["mags"])
+            self.roc_counts[i] = out["counts"][0]
         r = self._fill_result(i, foe, sky, estimate_fixed=fixed, total_mask=total)
         self._store(i, r)
         if self.images_path is not None:                      # the reference-named helpers, as processor.py:364-374 reads
@@ -862,6 +897,8 @@ class Processor:
             self.detection_boxes[i] = utils.Rectangle.from_box(rec["box"])
             if self.blobs is not None:
                 self.detection_blobs[i] = self._blob_list(out["blobs"][k])
+            if self.roc is not None:
+                self.roc_counts[i] = out["roc"][k]
             self._store(i, r)
             gts.append(r.foe_gt)
         ctx = pipe.pipes[ticket[0]].ctx
