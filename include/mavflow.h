@@ -41,6 +41,7 @@ extern "C" {
 #define MAV_DEPTH_8U 0
 #define MAV_DEPTH_16U 2
 #define MAV_DEPTH_32F 5
+#define MAV_DEPTH_64F 6 /* the flow history's fields and ring only (mav_history_*, mav_stage_remap_linear): never a frame depth */
 
 typedef struct mav_ctx mav_ctx;
 
@@ -579,6 +580,66 @@ int mav_last_roc_sweep(mav_ctx*, const uint8_t* gt, int gt_images, int batch, co
  * must still not run concurrently with a thread that posts steps.  The armed state belongs to the CONTEXT: whoever runs steps of
  * different shapes on one context arms before each (the Python pipelines do). */
 int mav_roc_arm(mav_ctx*, const mav_roc_params* /* NULL: disarm */, size_t off_table);
+
+/* ---- flow history: every pixel's trajectory through the last fields [src/detector.py:365-388, Detector.get_history] ------------------
+ * The reference's one temporal operator.  A ring keeps the last `length` flow fields; a push stores a field and returns, for every
+ * pixel, the displacement accumulated along the trajectory that starts there and is followed through the ring's fields by chained
+ * cv2.remap(field, map_x, map_y, INTER_LINEAR) calls.  On the device that is one kernel per push: a pixel walks its own chain of
+ * dependent bilinear gathers, nothing intermediate is written.
+ *
+ * ONE REMAP (restated from OpenCV 4.x and NOT pinned against a cv2 build: DESIGN.md section 4g lists what to re-check first).
+ * src (H, W, 2) float32 or float64, float32 maps, BORDER_CONSTANT with value 0; per output element:
+ *   1. qx = round_half_even(map_x * 32.0f) as int32, the product in float32; qy likewise.  A coordinate that is NaN, infinite or whose
+ *      product does not fit int32 samples as wholly outside: +0.0 in both channels.
+ *   2. sx = clamp(qx >> 5, -32768, 32767) (arithmetic shift), ax = qx & 31; sy, ay likewise.
+ *   3. fx = ax / 32, fy = ay / 32 in float32; w00 = (1-fy)(1-fx), w01 = (1-fy) fx, w10 = fy (1-fx), w11 = fy fx: exact multiples of 1/1024.
+ *   4. sx >= W or sx + 1 < 0 or sy >= H or sy + 1 < 0: wholly outside, +0.0.
+ *   5. otherwise, with T(r, c) the source value widened to double, or 0.0 when (r, c) is out of range, per channel
+ *      ((T(sy,sx) w00 + T(sy,sx+1) w01) + T(sy+1,sx) w10) + T(sy+1,sx+1) w11 in double, every product and sum rounded on its own (no
+ *      FMA).  All four products are always formed: an in-range NaN tap under a zero weight gives NaN.
+ * A float32 ring that holds the same values as a float64 ring therefore gives identical bits.  A NaN result is stored as the quiet NaN
+ * 0x7FF8000000000000 (float32: 0x7FC00000): whether a result is a NaN is arithmetic, its sign and payload are the machine's.
+ *
+ * ONE PUSH, ring of length L at index h (slots zero at creation):  ring[h] = flow;  slots = mav_history_schedule(L, h);  every pixel
+ * (y, x) starts from r = y, c = x in double and does, for each s of slots in turn, (u, v) = remap(ring[s], (float)c, (float)r) (the casts
+ * round to nearest even), r += u, c += v -- the reference's channel order, lookup_map[..., 0] is the row and the flow's x component is
+ * added to it, kept as it is; MAV_HISTORY_AXES_XY: r += v, c += u, the geometrically consistent order --; the result is (r - y, c - x);
+ * then h = (h + 1) % L.  The schedule is the reference's loop taken literally: k = (h + 1) % (L - 1); while k != h % (L - 1): emit k,
+ * k = (k + 1) % L.  For L = 20: h <= 17 walks h+1 .. 19, 0 .. h-1 (19 steps, the field just stored is not read), h = 18 walks 0 .. 17
+ * (18 steps), h = 19 walks 1 .. 19 (the field just stored is read).
+ *
+ * length 3 .. MAV_HISTORY_MAX_LENGTH; depth MAV_DEPTH_32F or MAV_DEPTH_64F, the ring's element; flags 0 or MAV_HISTORY_AXES_XY.  The
+ * ring is length * W * H * 2 * sizeof(element) bytes of the context's device memory (mav_mem_info counts it; 332 MB for 20 float32
+ * fields at 1080p), freed by mav_history_destroy or mav_destroy; a failed allocation is MAV_ERR_OOM and leaves nothing behind.  A context
+ * may own several histories; a history is used with the context that created it only (MAV_ERR_ARG otherwise). */
+#define MAV_HISTORY_MAX_LENGTH 64
+#define MAV_HISTORY_AXES_XY 1           /* mav_history_params.flags */
+#define MAV_HISTORY_OUT_REFERENCE 0     /* out_form: float64 (H, W, 2) = (r - y, c - x), the reference's return value */
+#define MAV_HISTORY_OUT_FLOW_F32 1      /* out_form: float32 (H, W, 2) = (c - x, r - y), each rounded once from the double: the (u, v)
+                                           layout mav_detect / mav_render / mav_roc_sweep take */
+typedef struct mav_history mav_history; /* opaque; owned by its context */
+typedef struct {
+    int length, depth, flags;
+} mav_history_params;                   /* mav_history_defaults: 20, MAV_DEPTH_32F, 0 */
+void mav_history_defaults(mav_history_params*);
+/* Pure host, no context: the slots a push at `index` of a ring of `length` walks, in order, into slots[0 .. *n); slots holds
+ * length - 1 entries.  MAV_ERR_ARG for a length outside 3 .. MAV_HISTORY_MAX_LENGTH, an index outside 0 .. length - 1 or a NULL pointer. */
+int mav_history_schedule(int length, int index, int* slots, int* n);
+int mav_history_create(mav_ctx*, const mav_history_params* /* NULL = defaults */, mav_history** out);   /* ring zeroed, index 0 */
+int mav_history_destroy(mav_ctx*, mav_history*);   /* waits for the context's stream, then frees the ring */
+int mav_history_reset(mav_ctx*, mav_history*);     /* ring zeroed, index 0, pushes 0; enqueue only */
+int mav_history_info(mav_ctx*, const mav_history*, int* index, long* pushes, size_t* ring_bytes);   /* any output may be NULL */
+/* `count` >= 1 consecutive fields, flow (count, H, W, 2) of flow_depth (MAV_DEPTH_32F, or MAV_DEPTH_64F into a float64 ring: a float32
+ * field into a float64 ring is widened, a float64 field into a float32 ring would round and is MAV_ERR_ARG), pushed and traced in order:
+ * out (count, H, W, 2) in out_form.  count * W * H <= MAV_MAX_BATCH_PIXELS.  flow and out are aligned to their elements and do not
+ * overlap.  Bad arguments are refused before anything is enqueued, the ring, the index and out as they were; mav_last_error names
+ * the argument.  mav_history_push: host pointers, synchronous.  mav_history_push_dev: device pointers, enqueue only -- stream order keeps
+ * field t's reads ahead of field t + 1's write of the oldest slot. */
+int mav_history_push(mav_ctx*, mav_history*, const void* flow, int flow_depth, int count, int out_form, void* out);
+int mav_history_push_dev(mav_ctx*, mav_history*, const void* flow, int flow_depth, int count, int out_form, void* out);
+/* One remap, as defined above, of a W x H field: src (H, W, 2) of `depth`, map_x / map_y (H, W) float32, out (H, W, 2) float64.  Host
+ * pointers, synchronous: the stage-level pin of the trajectory kernel's one body (tests/test_gpu_history.py). */
+int mav_stage_remap_linear(mav_ctx*, const void* src, int depth, const float* map_x, const float* map_y, double* out);
 
 /* Frame decode in front of the path [src/datasets/dataset.py:57,223-230: cv2.VideoCapture over image_%05d.png; src/farneback.py:17-21]:
  * the un-filtering pass of a PNG image, host memory, no context.  raw = the inflated IDAT stream of a non-interlaced image (per row a

@@ -327,9 +327,9 @@ struct Stager {
         }
     }
 };
-enum KernelId { K_BLUR_RESIZE, K_POLYEXP, K_UPDATE, K_ITER, K_ITER_COARSE, K_FOE, K_PHI, K_MISC, K_LK_CORNERS, K_LK_PYRAMID, K_LK_TRACK, K_LK_PICK, K_COMPONENTS, K_COUNT };
+enum KernelId { K_BLUR_RESIZE, K_POLYEXP, K_UPDATE, K_ITER, K_ITER_COARSE, K_FOE, K_PHI, K_MISC, K_LK_CORNERS, K_LK_PYRAMID, K_LK_TRACK, K_LK_PICK, K_COMPONENTS, K_HISTORY_PUT, K_HISTORY_TRACE, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"blur_resize", "polyexp", "update_matrices", "blur_iter", "blur_iter_coarse",
-                                                  "foe_ransac", "phi_mask_box", "misc", "lk_corners", "lk_pyramid", "lk_track", "lk_pick", "components"};
+                                                  "foe_ransac", "phi_mask_box", "misc", "lk_corners", "lk_pyramid", "lk_track", "lk_pick", "components", "history_put", "history_trace"};
 struct ProfRec { int kid; hipEvent_t a, b; int stream; };
 struct ProfInterval { int kid; float t0, t1; int stream; };      // ms since the profile was switched on
 
@@ -351,6 +351,14 @@ struct LkState {
     uint8_t* status = nullptr;       // MAV_LK_MAX_POINTS
     bool hist_valid = false;
     std::vector<float> fetch;        // host staging of the host forms' corners: kept, so a call allocates nothing
+};
+
+// A flow history (include/mavflow.h: mav_history_*): the ring and where the next field goes.
+struct mav_history {
+    int length = 0, depth = 0, flags = 0, index = 0;
+    long pushes = 0;
+    void* ring = nullptr;            // length slots of W * H pairs of `depth`, from the owning context's ledger
+    size_t ring_bytes = 0;
 };
 
 struct mav_ctx {
@@ -490,6 +498,7 @@ struct mav_ctx {
         size_t pairs_cap = 0;
         struct Last { const float* flow = nullptr; const double* M = nullptr; int m_stride = 0; int batch = 0; } last;
     } gm;
+    std::vector<mav_history*> histories;       // flow histories (mav_history_create): the objects are the context's, their rings are in `mem`
     hipEvent_t t0 = nullptr, t1 = nullptr;
     int profiling = 0;               // 0 off; 1 = HIP events around every launch; 2 = around every RUN of launches of one class on a stream
     struct OpenRun { hipStream_t st; int kid; hipEvent_t a; };
@@ -649,6 +658,7 @@ extern "C" int mav_destroy(mav_ctx* c)
     if (c->copy_stream) hipStreamSynchronize(c->copy_stream);
     if (c->stager) { c->stager->shutdown(); delete c->stager; c->stager = nullptr; }
     c->mem.release_all();
+    for (mav_history* h : c->histories) delete h;
     for (auto& r : c->prof) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
     if (c->prof_base) hipEventDestroy(c->prof_base);
     for (hipEvent_t e : {c->t0, c->t1, c->copy_done, c->compute_mark, c->gather_done, c->pif_fork, c->pif_join}) if (e) hipEventDestroy(e);
@@ -3288,6 +3298,156 @@ extern "C" int mav_roc_arm(mav_ctx* c, const mav_roc_params* rp, size_t off_tabl
     if (!rp) { c->roc_armed = false; return MAV_OK; }
     c->roc_thr = t; c->roc_off = off_table; c->roc_armed = true;
     return MAV_OK;
+}
+
+// ---- flow history (include/mavflow.h: mav_history_*) -------------------------------------------------------------------------------------
+extern "C" void mav_history_defaults(mav_history_params* p) { *p = mav_history_params{20, MAV_DEPTH_32F, 0}; }
+// Detector.get_history's loop (detector.py:376-385) taken literally.  k moves through 0 .. L - 1 cyclically and the target is one of
+// those values, so the walk ends within L - 1 steps for every L >= 3.
+extern "C" int mav_history_schedule(int length, int index, int* slots, int* n)
+{
+    if (length < 3 || length > MAV_HISTORY_MAX_LENGTH) return fail(MAV_ERR_ARG, "mav_history_schedule: length %d outside [3, %d]", length, MAV_HISTORY_MAX_LENGTH);
+    if (index < 0 || index >= length) return fail(MAV_ERR_ARG, "mav_history_schedule: index %d outside [0, %d]", index, length - 1);
+    if (!slots || !n) return fail(MAV_ERR_ARG, "mav_history_schedule: NULL slots or n");
+    int cnt = 0;
+    for (int k = (index + 1) % (length - 1); k != index % (length - 1); k = (k + 1) % length) slots[cnt++] = k;
+    *n = cnt;
+    return MAV_OK;
+}
+static size_t depth_bytes(int depth) { return depth == MAV_DEPTH_64F ? sizeof(double) : sizeof(float); }
+static int history_owned(mav_ctx* c, const mav_history* h, const char* fn)
+{
+    if (!c) return fail(MAV_ERR_ARG, "%s: NULL context", fn);
+    if (!h) return fail(MAV_ERR_ARG, "%s: NULL history", fn);
+    if (std::find(c->histories.begin(), c->histories.end(), h) == c->histories.end())
+        return fail(MAV_ERR_ARG, "%s: history is not one of this context's", fn);
+    return MAV_OK;
+}
+extern "C" int mav_history_create(mav_ctx* c, const mav_history_params* pp, mav_history** out)
+{
+    if (!c || !out) return fail(MAV_ERR_ARG, "mav_history_create: NULL %s", !c ? "context" : "out");
+    mav_history_params p;
+    if (pp) p = *pp; else mav_history_defaults(&p);
+    if (p.length < 3 || p.length > MAV_HISTORY_MAX_LENGTH) return fail(MAV_ERR_ARG, "mav_history_create: length %d outside [3, %d]", p.length, MAV_HISTORY_MAX_LENGTH);
+    if (p.depth != MAV_DEPTH_32F && p.depth != MAV_DEPTH_64F) return fail(MAV_ERR_ARG, "mav_history_create: depth %d is neither MAV_DEPTH_32F nor MAV_DEPTH_64F", p.depth);
+    if (p.flags & ~MAV_HISTORY_AXES_XY) return fail(MAV_ERR_ARG, "mav_history_create: unknown flags 0x%x", p.flags);
+    HIPCHK(hipSetDevice(c->device));
+    mav_history* h = new mav_history;
+    h->length = p.length; h->depth = p.depth; h->flags = p.flags;
+    h->ring_bytes = (size_t)p.length * c->n0 * 2 * depth_bytes(p.depth);
+    int rc = c->mem.alloc(&h->ring, h->ring_bytes, MEM_OTHER, "flow history ring");
+    if (rc == MAV_OK && hipMemsetAsync(h->ring, 0, h->ring_bytes, c->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        c->mem.release(h->ring);
+        rc = fail(MAV_ERR_HIP, "mav_history_create: zeroing the ring failed");
+    }
+    if (rc != MAV_OK) { delete h; return rc; }
+    c->histories.push_back(h);
+    *out = h;
+    return MAV_OK;
+}
+extern "C" int mav_history_destroy(mav_ctx* c, mav_history* h)
+{
+    CHK(history_owned(c, h, "mav_history_destroy"));
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));       // enqueued pushes may still read the ring
+    c->mem.release(h->ring);
+    c->histories.erase(std::find(c->histories.begin(), c->histories.end(), h));
+    delete h;
+    return MAV_OK;
+}
+extern "C" int mav_history_reset(mav_ctx* c, mav_history* h)
+{
+    CHK(history_owned(c, h, "mav_history_reset"));
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemsetAsync(h->ring, 0, h->ring_bytes, c->stream));
+    h->index = 0;
+    h->pushes = 0;
+    return MAV_OK;
+}
+extern "C" int mav_history_info(mav_ctx* c, const mav_history* h, int* index, long* pushes, size_t* ring_bytes)
+{
+    CHK(history_owned(c, h, "mav_history_info"));
+    if (index) *index = h->index;
+    if (pushes) *pushes = h->pushes;
+    if (ring_bytes) *ring_bytes = h->ring_bytes;
+    return MAV_OK;
+}
+// Everything a push can be refused for, host or device pointers alike: nothing has been enqueued or changed when this fails.  What can
+// be judged from the arguments alone comes before the context or the history is looked at (tests/test_abi_history.py passes handles
+// that must never be dereferenced).
+static int history_push_checked(mav_ctx* c, const mav_history* h, const void* flow, int flow_depth, int count, int out_form, const void* out,
+                                const char* fn)
+{
+    if (!c) return fail(MAV_ERR_ARG, "%s: NULL context", fn);
+    if (!h) return fail(MAV_ERR_ARG, "%s: NULL history", fn);
+    if (!flow) return fail(MAV_ERR_ARG, "%s: NULL flow", fn);
+    if (!out) return fail(MAV_ERR_ARG, "%s: NULL out", fn);
+    if (flow_depth != MAV_DEPTH_32F && flow_depth != MAV_DEPTH_64F) return fail(MAV_ERR_ARG, "%s: flow_depth %d is neither MAV_DEPTH_32F nor MAV_DEPTH_64F", fn, flow_depth);
+    if (out_form != MAV_HISTORY_OUT_REFERENCE && out_form != MAV_HISTORY_OUT_FLOW_F32) return fail(MAV_ERR_ARG, "%s: unknown out_form %d", fn, out_form);
+    if (count < 1) return fail(MAV_ERR_ARG, "%s: count %d is less than 1", fn, count);
+    const size_t fe = depth_bytes(flow_depth), oe = out_form == MAV_HISTORY_OUT_FLOW_F32 ? sizeof(float) : sizeof(double);
+    if ((uintptr_t)flow % fe) return fail(MAV_ERR_ARG, "%s: flow is not aligned to its %zu-byte elements", fn, fe);
+    if ((uintptr_t)out % oe) return fail(MAV_ERR_ARG, "%s: out is not aligned to its %zu-byte elements", fn, oe);
+    CHK(history_owned(c, h, fn));
+    if (flow_depth == MAV_DEPTH_64F && h->depth == MAV_DEPTH_32F)
+        return fail(MAV_ERR_ARG, "%s: flow_depth: a float64 field would be rounded into this float32 ring", fn);
+    if ((size_t)count * c->n0 > MAV_MAX_BATCH_PIXELS) return fail(MAV_ERR_ARG, "%s: count %d above %zu fields of this size", fn, count, MAV_MAX_BATCH_PIXELS / c->n0);
+    const uintptr_t f0 = (uintptr_t)flow, f1 = f0 + (size_t)count * c->n0 * 2 * fe, o0 = (uintptr_t)out, o1 = o0 + (size_t)count * c->n0 * 2 * oe;
+    if (f0 < o1 && o0 < f1) return fail(MAV_ERR_ARG, "%s: flow and out overlap", fn);
+    return MAV_OK;
+}
+extern "C" int mav_history_push_dev(mav_ctx* c, mav_history* h, const void* flow, int flow_depth, int count, int out_form, void* out)
+{
+    CHK(history_push_checked(c, h, flow, flow_depth, count, out_form, out, "mav_history_push_dev"));
+    HIPCHK(hipSetDevice(c->device));
+    const bool ring64 = h->depth == MAV_DEPTH_64F, flow64 = flow_depth == MAV_DEPTH_64F, out32 = out_form == MAV_HISTORY_OUT_FLOW_F32;
+    const size_t field = c->n0 * 2, slot_bytes = field * depth_bytes(h->depth);
+    for (int t = 0; t < count; t++) {
+        int slots[MAV_HISTORY_MAX_LENGTH], n = 0;
+        CHK(mav_history_schedule(h->length, h->index, slots, &n));
+        HistSlots hs{};
+        hs.n = n;
+        for (int i = 0; i < n; i++) hs.w[i >> 2] |= (unsigned)slots[i] << ((i & 3) * 8);
+        {
+            ProfScope ps(c, K_HISTORY_PUT);
+            launch_history_put(c->stream, (const char*)flow + (size_t)t * field * depth_bytes(flow_depth), flow64, (char*)h->ring + h->index * slot_bytes, ring64, c->W, c->H);
+        }
+        {
+            ProfScope ps(c, K_HISTORY_TRACE);
+            launch_history_trace(c->stream, h->ring, ring64, hs, c->W, c->H, (h->flags & MAV_HISTORY_AXES_XY) != 0, out32,
+                                 (char*)out + (size_t)t * field * (out32 ? sizeof(float) : sizeof(double)));
+        }
+        h->index = (h->index + 1) % h->length;
+        h->pushes++;
+    }
+    return check_launch("flow history");
+}
+extern "C" int mav_history_push(mav_ctx* c, mav_history* hist, const void* flow, int flow_depth, int count, int out_form, void* out)
+{
+    CHK(history_push_checked(c, hist, flow, flow_depth, count, out_form, out, "mav_history_push"));
+    HostCall h(c, "mav_history_push");
+    CHK(h.fresh());
+    const size_t field = c->n0 * 2 * (size_t)count;
+    const char* dflow = h.in((const char*)flow, field * depth_bytes(flow_depth));
+    char* dout = h.out((char*)out, field * (out_form == MAV_HISTORY_OUT_FLOW_F32 ? sizeof(float) : sizeof(double)));
+    CHK(h.staged());
+    CHK(mav_history_push_dev(c, hist, dflow, flow_depth, count, out_form, dout));
+    return h.finish();
+}
+extern "C" int mav_stage_remap_linear(mav_ctx* c, const void* src, int depth, const float* map_x, const float* map_y, double* out)
+{
+    if (!c || !src || !map_x || !map_y || !out) return fail(MAV_ERR_ARG, "mav_stage_remap_linear: NULL argument");
+    if (depth != MAV_DEPTH_32F && depth != MAV_DEPTH_64F) return fail(MAV_ERR_ARG, "mav_stage_remap_linear: depth %d is neither MAV_DEPTH_32F nor MAV_DEPTH_64F", depth);
+    HostCall h(c, "mav_stage_remap_linear");
+    CHK(h.fresh());
+    const char* dsrc = h.in((const char*)src, c->n0 * 2 * depth_bytes(depth));
+    const float *dmx = h.in(map_x, c->n0 * sizeof(float)), *dmy = h.in(map_y, c->n0 * sizeof(float));
+    double* dout = h.out(out, c->n0 * 2 * sizeof(double));
+    CHK(h.staged());
+    launch_remap_linear(c->stream, dsrc, depth == MAV_DEPTH_64F, dmx, dmy, c->W, c->H, dout);
+    CHK(check_launch("remap"));
+    return h.finish();
 }
 
 extern "C" int mav_flow_to_color(mav_ctx* c, const void* flow, int f64, int batch, uint8_t* img)

@@ -323,3 +323,15 @@ struct CcArgs {
 };
 size_t cc_workspace_per_image(int W, int H);
 void launch_components(hipStream_t st, const CcArgs& a);
+
+// ---- flow history (kernels_history.hip, compiled with -ffp-contract=off) ----------------------------------------------------------------
+// The slots a push walks, in order (mav_history_schedule): at most MAV_HISTORY_MAX_LENGTH - 1 entries of one byte, four to a word, passed
+// to the kernel by value.
+struct HistSlots { int n; unsigned w[(MAV_HISTORY_MAX_LENGTH + 3) / 4]; };
+// one remap of a W x H field of pairs (float32 or, with f64, float64) at the float32 maps: out (H, W, 2) float64
+void launch_remap_linear(hipStream_t st, const void* src, bool f64, const float* map_x, const float* map_y, int W, int H, double* out);
+// a caller's field (aligned to its element) -> a ring slot, copied or widened (float64 into a float32 slot does not exist)
+void launch_history_put(hipStream_t st, const void* src, bool src_f64, void* slot, bool ring_f64, int W, int H);
+// every pixel's trajectory through the listed slots of the ring (slot s at ring + s * W * H pairs): out (H, W, 2) float64 (r - y, c - x),
+// or with out_f32 float32 (c - x, r - y); out is aligned to its element
+void launch_history_trace(hipStream_t st, const void* ring, bool ring_f64, const HistSlots& slots, int W, int H, bool axes_xy, bool out_f32, void* out);

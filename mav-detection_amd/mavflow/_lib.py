@@ -122,6 +122,25 @@ def roc_expand(table: np.ndarray, ka: int, km: int) -> np.ndarray:
     out[..., 2:] = table[:, 2:].reshape(-1, ka, km, 2)
     return out
 
+class HistoryParams(C.Structure):
+    """mav_history_params: ring length (3 .. 64), element depth (DEPTH_32F / DEPTH_64F), flags (HISTORY_AXES_XY)."""
+    _fields_ = [("length", C.c_int), ("depth", C.c_int), ("flags", C.c_int)]
+
+
+HISTORY_MAX_LENGTH = 64                                  # MAV_HISTORY_MAX_LENGTH
+HISTORY_AXES_XY = 1                                      # MAV_HISTORY_AXES_XY
+HISTORY_OUT_REFERENCE, HISTORY_OUT_FLOW_F32 = 0, 1       # MAV_HISTORY_OUT_*
+HISTORY_AXES = {"reference": 0, "xy": HISTORY_AXES_XY}
+HISTORY_OUTS = {"reference": (HISTORY_OUT_REFERENCE, np.dtype(np.float64)), "flow": (HISTORY_OUT_FLOW_F32, np.dtype(np.float32))}
+
+
+def history_schedule(length: int, index: int) -> list:
+    """mav_history_schedule: the ring slots a push at `index` walks, in order (Detector.get_history's loop, detector.py:376-385)."""
+    slots, n = (C.c_int * HISTORY_MAX_LENGTH)(), C.c_int()
+    check(load().mav_history_schedule(int(length), int(index), slots, C.byref(n)))
+    return list(slots[:n.value])
+
+
 # every symbol include/mavflow.h declares (tests check the library exports each of them)
 EXPORTS = [
     "mav_fb_defaults", "mav_foe_defaults", "mav_thr_defaults", "mav_create", "mav_destroy", "mav_last_error",
@@ -154,10 +173,14 @@ EXPORTS = [
     "mav_global_motion_batch_dev",
     "mav_cc_defaults", "mav_components", "mav_components_dev", "mav_last_masks_components",
     "mav_roc_sweep", "mav_roc_sweep_dev", "mav_last_roc_sweep", "mav_roc_arm",
+    "mav_history_defaults", "mav_history_schedule", "mav_history_create", "mav_history_destroy", "mav_history_reset", "mav_history_info",
+    "mav_history_push", "mav_history_push_dev", "mav_stage_remap_linear",
 ]
 
 # Frame depths of the _ex entry points (cv2's depth codes) by numpy dtype.  uint8 frames keep going through the u8 symbols.
 DEPTH_8U, DEPTH_16U, DEPTH_32F = 0, 2, 5
+DEPTH_64F = 6                                   # the flow history's fields and ring only: never a frame depth
+HISTORY_DEPTHS = {np.dtype(np.float32): DEPTH_32F, np.dtype(np.float64): DEPTH_64F}
 DEPTHS = {np.dtype(np.uint8): DEPTH_8U, np.dtype(np.uint16): DEPTH_16U, np.dtype(np.float32): DEPTH_32F}
 
 OPTFLOW_USE_INITIAL_FLOW = 4                    # FbParams.flags bit (cv2.OPTFLOW_USE_INITIAL_FLOW): see Context.farneback(initial_flow=);
@@ -218,7 +241,7 @@ def load(path: str | None = None) -> C.CDLL:
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("mav_last_error", "mav_stream", "mav_fb_defaults", "mav_foe_defaults", "mav_thr_defaults", "mav_last_flow_dev", "mav_png_bound",
-                        "mav_gftt_defaults", "mav_lk_defaults", "mav_corner_score_defaults", "mav_cc_defaults"):
+                        "mav_gftt_defaults", "mav_lk_defaults", "mav_corner_score_defaults", "mav_cc_defaults", "mav_history_defaults"):
             fn.restype = C.c_int
     lib.mav_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FbParams)]
     lib.mav_destroy.argtypes = [C.c_void_p]
@@ -383,6 +406,17 @@ def load(path: str | None = None) -> C.CDLL:
     lib.mav_roc_sweep_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(ThrParams), rp, vp]
     lib.mav_last_roc_sweep.argtypes = [vp, vp, C.c_int, C.c_int, rp, vp]
     lib.mav_roc_arm.argtypes = [vp, rp, C.c_size_t]
+    lib.mav_history_defaults.argtypes = [C.POINTER(HistoryParams)]
+    lib.mav_history_defaults.restype = None
+    lib.mav_history_schedule.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.mav_history_create.argtypes = [vp, C.POINTER(HistoryParams), C.POINTER(C.c_void_p)]
+    lib.mav_history_destroy.argtypes = [vp, vp]
+    lib.mav_history_reset.argtypes = [vp, vp]
+    lib.mav_history_info.argtypes = [vp, vp, C.POINTER(C.c_int), C.POINTER(C.c_long), C.POINTER(C.c_size_t)]
+    # ctx, history, flow, flow_depth, count, out_form, out
+    lib.mav_history_push.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
+    lib.mav_history_push_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
+    lib.mav_stage_remap_linear.argtypes = [vp, vp, C.c_int, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -617,6 +651,106 @@ class DeviceBuffer:
         if self.ptr:
             self.ctx.lib.mav_dev_free(self.ctx.h, self.ptr)
             self.ptr = None
+
+
+def _dev_ptr(p) -> int:
+    """A device pointer: an int, or an object with a .ptr (DeviceBuffer, pipeline.DeviceArray)."""
+    return int(getattr(p, "ptr", p))
+
+
+class FlowHistory:
+    """One mav_history of a context (Context.flow_history): a ring of the last `length` flow fields on the device and, per push, every
+    pixel's accumulated displacement along its trajectory through them (the reference's Detector.get_history, detector.py:365-388)."""
+
+    def __init__(self, ctx: "Context", length: int = 20, dtype=np.float32, axes: str = "reference"):
+        if np.dtype(dtype) not in HISTORY_DEPTHS:
+            raise ValueError(f"flow_history: dtype must be float32 or float64, got {np.dtype(dtype)}")
+        if axes not in HISTORY_AXES:
+            raise ValueError(f"flow_history: axes must be 'reference' or 'xy', got {axes!r}")
+        self.ctx, self.length, self.dtype, self.axes = ctx, int(length), np.dtype(dtype), axes
+        p = HistoryParams(self.length, HISTORY_DEPTHS[self.dtype], HISTORY_AXES[axes])
+        h = C.c_void_p()
+        check(ctx.lib.mav_history_create(ctx.h, C.byref(p), C.byref(h)))
+        self._h = h
+
+    def _info(self):
+        i, n, b = C.c_int(), C.c_long(), C.c_size_t()
+        check(self.ctx.lib.mav_history_info(self.ctx.h, self._h, C.byref(i), C.byref(n), C.byref(b)))
+        return i.value, n.value, b.value
+
+    @property
+    def index(self) -> int:
+        """The slot the next field goes to (the reference's history_index)."""
+        return self._info()[0]
+
+    @property
+    def pushes(self) -> int:
+        return self._info()[1]
+
+    @property
+    def ring_bytes(self) -> int:
+        return self._info()[2]
+
+    @staticmethod
+    def _out_form(out: str):
+        if out not in HISTORY_OUTS:
+            raise ValueError(f"push: out must be 'reference' or 'flow', got {out!r}")
+        return HISTORY_OUTS[out]
+
+    def push(self, flow, out: str = "reference") -> np.ndarray:
+        """Store the field(s) and return the accumulated displacement(s).  flow: (H, W, 2) -> (H, W, 2), or (n, H, W, 2) -> (n, H, W, 2),
+        float32 or (into a float64 ring) float64; a host array, or a device handle with .ptr / .shape / .dtype (pipeline.DeviceArray)
+        of this context, which is read where it is.  out="reference": float64 (r - y, c - x), the reference's return value;
+        out="flow": float32 (c - x, r - y), the (u, v) layout Context.detect takes."""
+        form, odt = self._out_form(out)
+        ctx = self.ctx
+        on_dev = hasattr(flow, "ptr") and getattr(flow, "on_device", True) and getattr(flow, "ctx", ctx) is ctx
+        if on_dev and getattr(flow, "_deferred", None) is not None:        # a flow the flow stage has not enqueued yet
+            flow._deferred.flush()
+        a = flow if on_dev else np.asarray(flow)
+        shape, dt = tuple(a.shape), np.dtype(a.dtype)
+        if dt not in HISTORY_DEPTHS:
+            raise ValueError(f"push: expected a float32 or float64 field, got {dt}")
+        single = len(shape) == 3
+        if (shape[1:] if not single else shape) != (ctx.H, ctx.W, 2) or len(shape) not in (3, 4) or (not single and shape[0] < 1):
+            raise ValueError(f"push: expected ({ctx.H}, {ctx.W}, 2) or (n, {ctx.H}, {ctx.W}, 2), got {shape}")
+        n = 1 if single else shape[0]
+        res = np.empty((n, ctx.H, ctx.W, 2), odt)
+        if on_dev:
+            buf = ctx.alloc(res.nbytes)
+            try:
+                check(ctx.lib.mav_history_push_dev(ctx.h, self._h, flow.ptr, HISTORY_DEPTHS[dt], n, form, buf.ptr))
+                res = buf.download(odt, res.shape)
+            finally:
+                buf.free()
+        else:
+            a = np.ascontiguousarray(a)
+            check(ctx.lib.mav_history_push(ctx.h, self._h, _ptr(a), HISTORY_DEPTHS[dt], n, form, _ptr(res)))
+        return res[0] if single else res
+
+    def push_enqueue(self, flow_ptr, out_ptr, count: int = 1, dtype=np.float32, out: str = "reference") -> None:
+        """mav_history_push_dev: enqueue only, device pointers (ints, or objects with a .ptr); `count` fields of `dtype` at flow_ptr,
+        `count` results in the `out` form at out_ptr."""
+        form, _ = self._out_form(out)
+        if np.dtype(dtype) not in HISTORY_DEPTHS:
+            raise ValueError(f"push_enqueue: dtype must be float32 or float64, got {np.dtype(dtype)}")
+        check(self.ctx.lib.mav_history_push_dev(self.ctx.h, self._h, _dev_ptr(flow_ptr), HISTORY_DEPTHS[np.dtype(dtype)], int(count), form,
+                                                _dev_ptr(out_ptr)))
+
+    def reset(self) -> None:
+        """Zero ring, index 0 (enqueue only)."""
+        check(self.ctx.lib.mav_history_reset(self.ctx.h, self._h))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) and self.ctx.alive:
+            check(self.ctx.lib.mav_history_destroy(self.ctx.h, self._h))
+        self._h = None                     # (a closed context has freed the ring already)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Context:
@@ -1209,6 +1343,22 @@ class Context:
         self.roc_state = (a.tobytes(), m.tobytes(), int(off_table))
 
     roc_state = None
+
+    def flow_history(self, length: int = 20, dtype=np.float32, axes: str = "reference") -> FlowHistory:
+        """A flow history on this context (mav_history_create): ring of `length` fields (3 .. 64) of `dtype` (float32 / float64), zeroed;
+        axes="reference" keeps the reference's channel order (the flow's x component is added to the row), "xy" the geometric one."""
+        return FlowHistory(self, length, dtype, axes)
+
+    def stage_remap_linear(self, src, map_x, map_y) -> np.ndarray:
+        """mav_stage_remap_linear: cv2.remap(src, map_x, map_y, INTER_LINEAR) as the library restates it, of one (H, W, 2) float32 or
+        float64 field at (H, W) float32 maps -> (H, W, 2) float64."""
+        src = np.ascontiguousarray(src)
+        if src.dtype not in HISTORY_DEPTHS or src.shape != (self.H, self.W, 2):
+            raise ValueError(f"stage_remap_linear: expected ({self.H}, {self.W}, 2) float32 or float64, got {src.shape} {src.dtype}")
+        mx, my = _arr(map_x, np.float32, (self.H, self.W), "map_x"), _arr(map_y, np.float32, (self.H, self.W), "map_y")
+        out = np.empty((self.H, self.W, 2), np.float64)
+        check(self.lib.mav_stage_remap_linear(self.h, _ptr(src), HISTORY_DEPTHS[src.dtype], _ptr(mx), _ptr(my), _ptr(out)))
+        return out
 
     def flow_to_color(self, flow) -> np.ndarray:
         """flow_vis.flow_to_color(flow, convert_to_bgr=True) of (B, H, W, 2) fields in their own float type -> (B, H, W, 3) u8."""

@@ -103,6 +103,10 @@ class Detector:
         self.frame_result = FrameResult()
         self.use_optimization = False
         self._gm_dev = None              # (context, device buffers) of the calls that take a device-resident flow field
+        # get_history (detector.py:30-36): the reference allocates two (20, H, W, 2) host arrays here; the ring lives on the device and
+        # is made by the first get_history call
+        self.history_length = 20
+        self._history = None
 
     def get_gradient_and_magnitude(self, frame: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
         """Polar form of a cartesian flow field (detector.py:53-63): (magnitude, angle)."""
@@ -321,6 +325,35 @@ class Detector:
         self.flow_uv_warped_vis = flow_uv_warped_vis
         self.prev_frame = orig_frame
         return flow_uv_warped_vis, self.cluster_vis, self.cluster_vis.copy(), global_motion_vis
+
+    # -- flow history (detector.py:365-388) -----------------------------------------------------------------------------------------
+    @property
+    def history_index(self) -> int:
+        """The ring slot the next field goes to (0 before the first call)."""
+        return self._history.index if self._history is not None else 0
+
+    def get_history(self, flow_uv: np.ndarray) -> np.ndarray:
+        """detector.py:365-388: the field is stored in the ring of the last history_length fields and every pixel's trajectory is
+        followed through them by chained bilinear lookups (Context.flow_history: cv2.remap restated, not pinned against cv2).
+        Returns the accumulated displacement, float64 (H, W, 2) in the reference's channel order.  flow_uv: a host array or the flow
+        seam's device handle.  The ring is made by the first call, on the handle's context or the shared one of this frame size, with
+        the element type of that first field (float32, or float64 for a float64 array) and kept until history_length changes or its
+        context is closed (then a new, zero ring starts); a float64 field into a float32 ring would round and is a ValueError."""
+        W, H = self.dataset.capture_size[0], self.dataset.capture_size[1]
+        hist = self._history
+        if hist is not None and (hist.length != int(self.history_length) or not hist.ctx.alive):
+            hist.close()
+            hist = self._history = None
+        dev = self._device_flow(flow_uv)
+        if dev is None or (hist is not None and dev[0] is not hist.ctx):      # a handle of another context is read through the host
+            flow_uv = np.asarray(flow_uv)
+            if flow_uv.dtype not in (np.float32, np.float64):
+                flow_uv = flow_uv.astype(np.float64)
+            dev = None
+        if hist is None:
+            ctx = dev[0] if dev is not None else im_helpers._ctx(W, H)
+            hist = self._history = ctx.flow_history(int(self.history_length), flow_uv.dtype, "reference")
+        return hist.push(flow_uv, out="reference")
 
     def is_homography_based(self) -> bool:
         return self.algorithm in [Detector.Algorithm.HOMOGRAPHY]
