@@ -773,7 +773,9 @@ extern "C" int mav_create(mav_ctx** out, int device, int W, int H, int max_batch
     c->group = group;                                   // the workspace itself comes with the first call that computes flow (ensure_workspace)
     c->small_g = small_group_cap(c, group);
     const size_t B = (size_t)max_batch;
-    CHK(c->mem.alloc_set({{&c->foe_dev, sizeof(double) * 2 * B}, {&c->box_acc, sizeof(int32_t) * 4 * B},
+    // foe_dev: a FoE per pair, which last_render / last_roc point at, and behind them the one of mav_ransac -- a vote on caller-supplied
+    // estimates is no detection call and must not write what those records read
+    CHK(c->mem.alloc_set({{&c->foe_dev, sizeof(double) * 2 * (B + 1)}, {&c->box_acc, sizeof(int32_t) * 4 * B},
                           {&c->u64_scratch, sizeof(unsigned long long) * 8 * B},       // two count blocks of 4 per pair
                           {&c->i32_scratch, sizeof(int) * B}, {&c->derot_dev, sizeof(DerotParams) * B}, {&c->foe_sc.count, sizeof(int) * B},
                           {&c->foe_sc.best_key, sizeof(unsigned long long) * B}, {&c->foe_sc.done, sizeof(unsigned) * 2 * B}},
@@ -1895,6 +1897,14 @@ static int ensure_foe_scratch(mav_ctx* c, int N)
     c->foe_sc_n = N;
     return MAV_OK;
 }
+// The caller's FoE parameters (NULL: the defaults) judged, and the candidates' scratch there for them: what every call that estimates
+// a FoE does once, before it enqueues anything.  A call refused here leaves the derotation block, the FoEs and the tickets that
+// last_render / last_roc read as they were.
+static int foe_checked(mav_ctx* c, const mav_foe_params* fp, mav_foe_params* f)
+{
+    CHK(foe_or_defaults(fp, f));
+    return ensure_foe_scratch(c, f->n_pairs);
+}
 
 // Per-pair derotation constants.  Device pointers stay on the device (a tiny kernel packs them: no host round trip, the
 // stream never drains); host pointers are packed here and copied.
@@ -1930,9 +1940,9 @@ struct DetectArgs {
     const DerotParams* derot = nullptr;
     const uint8_t* sky = nullptr;
     const uint32_t* samples = nullptr;       // given: the FoE is estimated from them with foe_par (NULL: the defaults) and goes to foe_out
-    const mav_foe_params* foe_par = nullptr; // (NULL: the context's own buffer); not given: the phi / mask stage reads foe_in
-    const double* foe_in = nullptr;
-    double* foe_out = nullptr;
+    const mav_foe_params* foe_par = nullptr; // (what foe_checked filled in: detect_dev judges nothing); not given: the phi / mask stage reads
+    const double* foe_in = nullptr;          // foe_in
+    double* foe_out = nullptr;               // (NULL: the context's own buffer)
     const mav_thr_params* thr = nullptr;     // given: the phi / mask stage runs even if none of its outputs below is wanted
     double* phi = nullptr;
     uint8_t *mask_fixed = nullptr, *mask_dyn = nullptr;
@@ -1948,9 +1958,7 @@ static int detect_dev(mav_ctx* c, int batch, const DetectArgs& a)
     const double* foe = a.foe_in;
     const bool want_phi = a.thr || a.phi || a.mask_fixed || a.mask_dyn || a.results || a.box_out || a.max_phi_bits;
     if (a.samples) {
-        mav_foe_params f;
-        CHK(foe_or_defaults(a.foe_par, &f));
-        CHK(ensure_foe_scratch(c, f.n_pairs));
+        const mav_foe_params& f = *a.foe_par;
         double* fo = a.foe_out ? a.foe_out : c->foe_dev;
         ProfScope ps(c, K_FOE);
         // the candidates kernel also initialises the pair's box accumulators and tickets, the vote's last workgroup writes the FoE:
@@ -1981,15 +1989,14 @@ static int detect_dev(mav_ctx* c, int batch, const DetectArgs& a)
     return check_launch("detection kernels");
 }
 
-extern "C" int mav_detect_dev(mav_ctx* c, const float* flow, const uint32_t* samples, const double* omega, const double* dt,
-                              const uint8_t* frame0, const uint8_t* sky, int batch, const mav_foe_params* fp,
-                              const mav_thr_params* tp, double* phi, uint8_t* mask_fixed, uint8_t* mask_dyn, mav_result* results)
+// mav_detect_dev behind its checks (f: from foe_checked): the derotation block, the detection, the records of the readers
+static int detect_checked(mav_ctx* c, const float* flow, const uint32_t* samples, const double* omega, const double* dt,
+                          const uint8_t* frame0, const uint8_t* sky, int batch, const mav_foe_params& f,
+                          const mav_thr_params* tp, double* phi, uint8_t* mask_fixed, uint8_t* mask_dyn, mav_result* results)
 {
-    if (!c || !flow || !samples || !results) return fail(MAV_ERR_ARG, "mav_detect_dev: NULL argument");
-    CHK(check_dev_call(c, batch, "mav_detect_dev"));
     const mav_thr_params t = thr_or_defaults(tp);
     DetectArgs a;
-    a.flow32 = flow; a.samples = samples; a.sky = sky; a.foe_par = fp; a.thr = &t;
+    a.flow32 = flow; a.samples = samples; a.sky = sky; a.foe_par = &f; a.thr = &t;
     a.phi = phi; a.mask_fixed = mask_fixed; a.mask_dyn = mask_dyn; a.results = results;
     CHK(upload_derot(c, omega, dt, frame0, batch, false, &a.derot));
     CHK(detect_dev(c, batch, a));
@@ -1999,6 +2006,16 @@ extern "C" int mav_detect_dev(mav_ctx* c, const float* flow, const uint32_t* sam
     c->last_roc = mav_ctx::LastRoc{flow, false, a.derot, c->foe_dev, sky, batch};
     return MAV_OK;
 }
+extern "C" int mav_detect_dev(mav_ctx* c, const float* flow, const uint32_t* samples, const double* omega, const double* dt,
+                              const uint8_t* frame0, const uint8_t* sky, int batch, const mav_foe_params* fp,
+                              const mav_thr_params* tp, double* phi, uint8_t* mask_fixed, uint8_t* mask_dyn, mav_result* results)
+{
+    if (!c || !flow || !samples || !results) return fail(MAV_ERR_ARG, "mav_detect_dev: NULL argument");
+    CHK(check_dev_call(c, batch, "mav_detect_dev"));
+    mav_foe_params f;
+    CHK(foe_checked(c, fp, &f));                 // every argument is judged before anything is enqueued
+    return detect_checked(c, flow, samples, omega, dt, frame0, sky, batch, f, tp, phi, mask_fixed, mask_dyn, results);
+}
 
 extern "C" int mav_process_batch_dev(mav_ctx* c, const uint8_t* prev, const uint8_t* next, const uint32_t* samples,
                                      const double* omega, const double* dt, const uint8_t* frame0, const uint8_t* sky, int batch,
@@ -2007,12 +2024,14 @@ extern "C" int mav_process_batch_dev(mav_ctx* c, const uint8_t* prev, const uint
 {
     if (!c || !prev || !next || !samples || !results) return fail(MAV_ERR_ARG, "mav_process_batch: NULL argument");
     CHK(check_dev_call(c, batch, "mav_process_batch_dev"));
+    mav_foe_params f;
+    CHK(foe_checked(c, fp, &f));                 // (before the flow is enqueued: a refused call changes nothing)
     if (!flow) {
         CHK(ensure_flow_ws(c));
         flow = c->flow_ws;
     }
     CHK(mav_farneback_dev(c, prev, next, batch, flow));
-    return mav_detect_dev(c, flow, samples, omega, dt, frame0, sky, batch, fp, tp, phi, mask_fixed, mask_dyn, results);
+    return detect_checked(c, flow, samples, omega, dt, frame0, sky, batch, f, tp, phi, mask_fixed, mask_dyn, results);
 }
 
 // ---- connected components (include/mavflow.h: mav_components) -----------------------------------------------------------------------
@@ -2497,7 +2516,7 @@ static int foe_dense_host(mav_ctx* c, const char* fn, const T* flow, const uint3
     CHK(h.fresh(batch));
     if (!flow || !samples || !foe) return fail(MAV_ERR_ARG, "%s: NULL argument", fn);
     mav_foe_params f;
-    CHK(foe_or_defaults(fp, &f));
+    CHK(foe_checked(c, fp, &f));
     DetectArgs a;
     a.set_flow(h.in(flow, c->n0 * batch * 2 * sizeof(T)));
     a.samples = h.in(samples, sizeof(uint32_t) * 4 * (size_t)f.n_pairs * batch);
@@ -2653,9 +2672,10 @@ extern "C" int mav_ransac(mav_ctx* c, const double* estimates, int count, double
     const int N = count > 0 ? count : 1;
     CHK(ensure_foe_scratch(c, N));
     if (count > 0) HIPCHK(hipMemcpyAsync(c->foe_sc.cand, estimates, sizeof(double) * 2 * count, hipMemcpyHostToDevice, c->stream));
-    launch_ransac_only(c->stream, c->foe_sc, count, c->foe_sc_n, sq_threshold(ransac_threshold), c->foe_dev);
+    double* const vote = c->foe_dev + 2 * (size_t)c->max_batch;       // its own two doubles: the pairs' FoEs stay resident
+    launch_ransac_only(c->stream, c->foe_sc, count, c->foe_sc_n, sq_threshold(ransac_threshold), vote);
     CHK(check_launch("ransac"));
-    CHK(download(c, foe, c->foe_dev, sizeof(double) * 2));
+    CHK(download(c, foe, vote, sizeof(double) * 2));
     return mav_sync(c);
 }
 
@@ -3062,7 +3082,7 @@ static int process_host(mav_ctx* c, const char* fn, int batch, const ProcessArgs
     CHK(h.fresh(batch));
     if ((!a.flow_in && (!a.prev || !a.next)) || !a.samples || !a.results) return fail(MAV_ERR_ARG, "%s: NULL argument", fn);
     mav_foe_params f;
-    CHK(foe_or_defaults(a.foe_par, &f));
+    CHK(foe_checked(c, a.foe_par, &f));
     const size_t n = c->n0 * batch, flow_bytes = n * 2 * sizeof(float);
     const void *dprev = nullptr, *dnext = nullptr;
     float* dflow;                                        // the always-present buffers take the first blocks
@@ -3083,7 +3103,7 @@ static int process_host(mav_ctx* c, const char* fn, int batch, const ProcessArgs
     double* dphi = h.out(a.phi, n * sizeof(double));
     CHK(h.staged());
     if (!a.flow_in) CHK(mav_farneback_dev(c, (const uint8_t*)dprev, (const uint8_t*)dnext, batch, dflow));
-    CHK(mav_detect_dev(c, dflow, ds, dom, ddt, df0, dsky, batch, &f, a.thr, dphi, dmf, dmd, dres));
+    CHK(detect_checked(c, dflow, ds, dom, ddt, df0, dsky, batch, f, a.thr, dphi, dmf, dmd, dres));
     c->last_mf = dmf; c->last_md = dmd; c->last_mask_batch = batch;
     return h.finish();
 }
