@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "mavflow_internal.h"
+#include "../../include/mavflow_truth.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const char* fmt, ...)
@@ -499,6 +500,8 @@ struct mav_ctx {
         struct Last { const float* flow = nullptr; const double* M = nullptr; int m_stride = 0; int batch = 0; } last;
     } gm;
     std::vector<mav_history*> histories;       // flow histories (mav_history_create): the objects are the context's, their rings are in `mem`
+    double* radial_edges = nullptr;            // mav_radial_error_hist: the two edge lists of the call in hand (first call; 2 * MAV_RADIAL_MAX_EDGES doubles)
+    RadialEdges radial_mag{}, radial_err{};    // ... and what the stream's last call put there (n = 0: nothing): a sequence sends its lists once
     hipEvent_t t0 = nullptr, t1 = nullptr;
     int profiling = 0;               // 0 off; 1 = HIP events around every launch; 2 = around every RUN of launches of one class on a stream
     struct OpenRun { hipStream_t st; int kid; hipEvent_t a; };
@@ -2385,6 +2388,16 @@ struct HostCall {
     int after_last()
     {
         if ((rc = check_dev_call(c, 1, fn)) != MAV_OK) return rc;
+        mark = c->scratch_next;
+        appended = true;
+        return MAV_OK;
+    }
+
+    // A call that neither reads nor replaces anything resident (include/mavflow_truth.h), of `batch` pairs: the next free blocks as well,
+    // given back in the same way.
+    int beside(int batch)
+    {
+        if ((rc = check_dev_call(c, batch, fn)) != MAV_OK) return rc;
         mark = c->scratch_next;
         appended = true;
         return MAV_OK;
@@ -4407,4 +4420,126 @@ extern "C" int mav_stage_corner_pick(mav_ctx* c, const uint64_t* keys, int n, co
     if (n) HIPCHK(hipMemcpyAsync(k.cand, cand.data(), (size_t)n * sizeof(uint2), hipMemcpyHostToDevice, c->stream));
     CHK(corner_pick_enqueue(c, p, k.out, reinterpret_cast<int*>(k.counters + LK_CNT_PICKED)));
     return corner_pick_fetch(c, p, corners, count, "mav_stage_corner_pick");
+}
+
+// ---- ground truth and radial error (include/mavflow_truth.h) ----------------------------------------------------------------------------
+// These four keep every kind of resident state: the context's stream, staging blocks behind the last call's (HostCall::beside), the
+// caller's outputs and radial_edges -- no last_* record is touched and no buffer one points at is written.
+// Everything a ground-truth call can be refused for from its arguments alone, before the context is looked at.
+static int gt_flow_checked(mav_ctx* c, const float* depth, const mav_gt_flow_params* params, int batch, int out_depth, const void* flow, bool dev,
+                           const char* fn)
+{
+    if (!c) return fail(MAV_ERR_ARG, "%s: NULL context", fn);
+    if (!depth) return fail(MAV_ERR_ARG, "%s: NULL depth", fn);
+    if (!params) return fail(MAV_ERR_ARG, "%s: NULL params", fn);
+    if (!flow) return fail(MAV_ERR_ARG, "%s: NULL flow", fn);
+    if (out_depth != MAV_DEPTH_32F && out_depth != MAV_DEPTH_64F) return fail(MAV_ERR_ARG, "%s: out_depth %d is neither MAV_DEPTH_32F nor MAV_DEPTH_64F", fn, out_depth);
+    if (batch < 1) return fail(MAV_ERR_ARG, "%s: batch %d is less than 1", fn, batch);
+    if (dev) {
+        const size_t pair = 2 * depth_bytes(out_depth);
+        if ((uintptr_t)depth % sizeof(float)) return fail(MAV_ERR_ARG, "%s: depth is not aligned to its 4-byte elements", fn);
+        if ((uintptr_t)params % sizeof(double)) return fail(MAV_ERR_ARG, "%s: params is not aligned to 8 bytes", fn);
+        if ((uintptr_t)flow % pair) return fail(MAV_ERR_ARG, "%s: flow is not aligned to its %zu-byte pairs", fn, pair);
+    } else {
+        for (int b = 0; b < batch; b++)
+            if (params[b].flags != 0) return fail(MAV_ERR_ARG, "%s: params[%d].flags 0x%x: no flag is defined", fn, b, params[b].flags);
+    }
+    return MAV_OK;
+}
+extern "C" int mav_gt_flow_dev(mav_ctx* c, const float* depth, const uint8_t* seg, const mav_gt_flow_params* params, int batch, int out_depth, void* flow)
+{
+    CHK(gt_flow_checked(c, depth, params, batch, out_depth, flow, true, "mav_gt_flow_dev"));
+    CHK(check_dev_call(c, batch, "mav_gt_flow_dev"));
+    {
+        ProfScope ps(c, K_MISC);
+        launch_gt_flow(c->stream, depth, seg, params, batch, c->W, c->H, out_depth == MAV_DEPTH_64F, flow);
+    }
+    return check_launch("ground-truth flow");
+}
+extern "C" int mav_gt_flow(mav_ctx* c, const float* depth, const uint8_t* seg, const mav_gt_flow_params* params, int batch, int out_depth, void* flow)
+{
+    CHK(gt_flow_checked(c, depth, params, batch, out_depth, flow, false, "mav_gt_flow"));
+    HostCall h(c, "mav_gt_flow");
+    CHK(h.beside(batch));
+    const size_t n = c->n0 * batch;
+    const float* dd = h.in(depth, n * sizeof(float));
+    const uint8_t* ds = h.in(seg, n);
+    const mav_gt_flow_params* dp = h.in(params, sizeof(mav_gt_flow_params) * batch);
+    char* df = h.out((char*)flow, n * 2 * depth_bytes(out_depth));
+    CHK(h.staged());
+    CHK(mav_gt_flow_dev(c, dd, ds, dp, batch, out_depth, df));
+    return h.finish();
+}
+
+static int radial_edges_checked(const double* e, int n, const char* what, RadialEdges* out, const char* fn)
+{
+    if (!e) return fail(MAV_ERR_ARG, "%s: NULL %s_edges", fn, what);
+    if (n < 2 || n > MAV_RADIAL_MAX_EDGES) return fail(MAV_ERR_ARG, "%s: %d %s_edges outside [2, %d]", fn, n, what, MAV_RADIAL_MAX_EDGES);
+    for (int i = 0; i < n; i++) {
+        if (!std::isfinite(e[i])) return fail(MAV_ERR_ARG, "%s: %s_edges[%d] is not finite", fn, what, i);
+        if (i && !(e[i - 1] < e[i])) return fail(MAV_ERR_ARG, "%s: %s_edges are not strictly increasing at [%d]", fn, what, i);
+    }
+    out->n = n;
+    out->pad = 0;
+    memcpy(out->e, e, sizeof(double) * n);
+    memset(out->e + n, 0, sizeof(double) * (MAV_RADIAL_MAX_EDGES - n));
+    return MAV_OK;
+}
+static int radial_hist_checked(mav_ctx* c, const float* flow, const float* gt_flow, int batch, const double* mag_edges, int n_mag_edges,
+                               const double* err_edges, int n_err_edges, const int64_t* table, bool dev, RadialEdges* em, RadialEdges* ee, const char* fn)
+{
+    if (!c) return fail(MAV_ERR_ARG, "%s: NULL context", fn);
+    if (!flow) return fail(MAV_ERR_ARG, "%s: NULL flow", fn);
+    if (!gt_flow) return fail(MAV_ERR_ARG, "%s: NULL gt_flow", fn);
+    if (!table) return fail(MAV_ERR_ARG, "%s: NULL table", fn);
+    if (batch < 1) return fail(MAV_ERR_ARG, "%s: batch %d is less than 1", fn, batch);
+    CHK(radial_edges_checked(mag_edges, n_mag_edges, "mag", em, fn));
+    CHK(radial_edges_checked(err_edges, n_err_edges, "err", ee, fn));
+    if ((n_mag_edges - 1) * (n_err_edges - 1) > MAV_RADIAL_MAX_CELLS)
+        return fail(MAV_ERR_ARG, "%s: %d x %d bins are more than %d cells", fn, n_mag_edges - 1, n_err_edges - 1, MAV_RADIAL_MAX_CELLS);
+    if (dev) {
+        if ((uintptr_t)flow % 8) return fail(MAV_ERR_ARG, "%s: flow is not aligned to its 8-byte pairs", fn);
+        if ((uintptr_t)gt_flow % 8) return fail(MAV_ERR_ARG, "%s: gt_flow is not aligned to its 8-byte pairs", fn);
+        if ((uintptr_t)table % 8) return fail(MAV_ERR_ARG, "%s: table is not aligned to its 8-byte words", fn);
+    }
+    return MAV_OK;
+}
+static int radial_hist_enqueue(mav_ctx* c, const float* flow, const float* gt_flow, const uint8_t* sky, int batch, const RadialEdges& em,
+                               const RadialEdges& ee, int64_t* table)
+{
+    if (!c->radial_edges) CHK(c->mem.alloc(&c->radial_edges, sizeof(double) * 2 * MAV_RADIAL_MAX_EDGES, MEM_OTHER, "radial-error edge lists"));
+    const bool resident = c->radial_mag.n == em.n && c->radial_err.n == ee.n && !memcmp(c->radial_mag.e, em.e, sizeof(double) * em.n) &&
+                          !memcmp(c->radial_err.e, ee.e, sizeof(double) * ee.n);
+    c->radial_mag.n = c->radial_err.n = 0;                              // whatever goes wrong below, the lists are sent again
+    ProfScope ps(c, K_MISC);
+    const hipError_t e = launch_radial_hist(c->stream, flow, gt_flow, sky, batch, c->W, c->H, em, ee, c->radial_edges, resident, (unsigned long long*)table);
+    if (e != hipSuccess) return fail(MAV_ERR_HIP, "radial-error histogram: granting the counters' LDS failed: %s", hipGetErrorString(e));
+    CHK(check_launch("radial-error histogram"));
+    c->radial_mag = em; c->radial_err = ee;
+    return MAV_OK;
+}
+extern "C" int mav_radial_error_hist_dev(mav_ctx* c, const float* flow, const float* gt_flow, const uint8_t* sky, int batch, const double* mag_edges,
+                                         int n_mag_edges, const double* err_edges, int n_err_edges, int64_t* table)
+{
+    RadialEdges em, ee;
+    CHK(radial_hist_checked(c, flow, gt_flow, batch, mag_edges, n_mag_edges, err_edges, n_err_edges, table, true, &em, &ee, "mav_radial_error_hist_dev"));
+    CHK(check_dev_call(c, batch, "mav_radial_error_hist_dev"));
+    return radial_hist_enqueue(c, flow, gt_flow, sky, batch, em, ee, table);
+}
+extern "C" int mav_radial_error_hist(mav_ctx* c, const float* flow, const float* gt_flow, const uint8_t* sky, int batch, const double* mag_edges,
+                                     int n_mag_edges, const double* err_edges, int n_err_edges, int64_t* table)
+{
+    RadialEdges em, ee;
+    CHK(radial_hist_checked(c, flow, gt_flow, batch, mag_edges, n_mag_edges, err_edges, n_err_edges, table, false, &em, &ee, "mav_radial_error_hist"));
+    HostCall h(c, "mav_radial_error_hist");
+    CHK(h.beside(batch));
+    const size_t n = c->n0 * batch, words = MAV_RADIAL_TABLE_WORDS((size_t)(n_mag_edges - 1), (size_t)(n_err_edges - 1));
+    const float* df = h.in(flow, n * 2 * sizeof(float));
+    const float* dg = h.in(gt_flow, n * 2 * sizeof(float));
+    const uint8_t* ds = h.in(sky, n);
+    int64_t* dt = h.in(table, words * sizeof(int64_t));             // the caller's counts so far: the kernel adds to them
+    h.fetch(table, dt, words * sizeof(int64_t));
+    CHK(h.staged());
+    CHK(radial_hist_enqueue(c, df, dg, ds, batch, em, ee, dt));
+    return h.finish();
 }

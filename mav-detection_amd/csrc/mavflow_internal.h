@@ -335,3 +335,21 @@ void launch_history_put(hipStream_t st, const void* src, bool src_f64, void* slo
 // every pixel's trajectory through the listed slots of the ring (slot s at ring + s * W * H pairs): out (H, W, 2) float64 (r - y, c - x),
 // or with out_f32 float32 (c - x, r - y); out is aligned to its element
 void launch_history_trace(hipStream_t st, const void* ring, bool ring_f64, const HistSlots& slots, int W, int H, bool axes_xy, bool out_f32, void* out);
+
+// ---- ground truth and radial error (kernels_truth.hip, compiled with -ffp-contract=off; include/mavflow_truth.h) -------------------------
+#define MAV_GT_FLOW_GRID_CAP 1024u     // workgroups of 256 pixels per pair; larger frames loop
+// depth (B, H, W) float32, seg (B, H, W) u8 or null, params: B blocks on the device; out (B, H, W, 2) float32 or, with out_f64, float64,
+// aligned to one pair
+void launch_gt_flow(hipStream_t st, const float* depth, const uint8_t* seg, const void* params /* mav_gt_flow_params[B] */, int B, int W, int H,
+                    bool out_f64, void* out);
+// One checked edge list of a histogram call, passed to a kernel by value (the same bound as MAV_RADIAL_MAX_EDGES).
+struct RadialEdges { int n, pad; double e[257]; };
+#define MAV_RADIAL_LDS_CELLS 32768     // cells a workgroup can count in LDS (128 KiB of the CU's 160 beside the edge lists): more go to the table directly
+#define MAV_RADIAL_GRID_CAP 256        // workgroups of 1024 threads in all pairs of a call: one per CU, which is what the LDS form's counters leave room for
+bool radial_hist_lds_counts(int nm, int ne);
+int radial_hist_grid(size_t npx, int B);
+// flow, gt (B, H, W, 2) float32 aligned to 8, sky (B, H, W) u8 or null; edges_dev: 2 * 257 doubles of the context's, written here first
+// unless edges_resident (the stream's last call left these very lists there); table: 2 + cells words, ADDED into.  Returns the error
+// of granting the LDS, if any (nothing is launched then).
+hipError_t launch_radial_hist(hipStream_t st, const float* flow, const float* gt, const uint8_t* sky, int B, int W, int H, const RadialEdges& mag,
+                              const RadialEdges& err, double* edges_dev, bool edges_resident, unsigned long long* table);

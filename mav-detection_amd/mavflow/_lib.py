@@ -1952,3 +1952,8 @@ def runtime_info() -> dict:
 
 def device_count() -> int:
     return load().mav_device_count()
+
+
+# include/mavflow_truth.h (Context.gt_flow, .radial_error_hist, .radial_error_accumulator): a binding module of its own, attached here so
+# that every Context has the methods
+from . import _truth  # noqa: E402,F401

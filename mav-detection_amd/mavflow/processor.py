@@ -252,6 +252,28 @@ class Processor:
     def is_active(self) -> bool:
         return self.frame_index < self.dataset.N - 1 and not self.is_exiting
 
+    def analyze_radial_error(self) -> None:
+        """Compare the angular error in flow to the magnitude of the flow (processor.py:267-275): the current frame's flow_uv against
+        gt_flow_uv over the non-sky pixels.  Where the reference saves two full-frame arrays per frame and bins them afterwards
+        (plot_radial_error.py:38-39), the histogram over those bins builds up on the device: self.radial_error is the accumulator
+        (Context.radial_error_accumulator; .counts() -> counts, non_sky, in_range).  Nothing calls it inside the loops, as in the reference."""
+        if self.flow_uv is None:
+            raise ValueError("analyze_radial_error: no flow_uv of a current frame")
+        i = self.frame_index
+        gt = self.gt_flow_uv if self.gt_flow_uv is not None else utils.assert_type(self.dataset.get_gt_of(i))     # (processor.py:309)
+        sky = getattr(self, "sky_mask", None)
+        sky = sky if sky is not None else self.dataset.get_sky_segmentation(i)
+        on_dev = isinstance(self.flow_uv, pipeline.DeviceArray) and self.flow_uv.on_device
+        ctx = self.flow_uv.ctx if on_dev else self._own_ctxs(1, 1)[0]
+        if self.radial_error is None or self.radial_error.ctx is not ctx or not ctx.alive:
+            if self.radial_error is not None:
+                self.radial_error.close()
+            self.radial_error = ctx.radial_error_accumulator()
+        self.radial_error.add(self.flow_uv, gt, sky)
+
+    radial_error = None
+    gt_flow_uv = None
+
     # -- device plumbing --------------------------------------------------------------------------------------------------------
     def _pipeline(self, ctxs, batch: int) -> "pipeline.LanedPipeline":
         """The (cached) pipeline over these contexts for `batch` pairs per submit."""
@@ -918,6 +940,9 @@ class Processor:
         self._free_global_motion_buffers()
         self._free_global_motion_slots()
         self.detector._free_dev_buffers()
+        if self.radial_error is not None:
+            self.radial_error.close()
+            self.radial_error = None
         self._close_pipes()
         for c in self._ctxs:
             c.close()
