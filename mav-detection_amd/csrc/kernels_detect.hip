@@ -16,28 +16,7 @@
 
 #include <type_traits>
 
-// Derotated flow vector at pixel (col, row) in double, reference operation order (detector.py:92-114).
-static __device__ __forceinline__ void derot_apply(float2 f, const DerotParams* __restrict__ dp, int W, int H, int row, int col,
-                                                   double* fu, double* fv)
-{
-    double u = (double)f.x, v = (double)f.y;
-    if (dp && dp->mode == MAV_PAIR_DEROTATE) {
-        const double x = -((double)col / (double)W - 0.5) * 2.0;
-        const double y = -((double)row / (double)H - 0.5) * 2.0;
-        const double o0 = dp->o0, o1 = dp->o1, o2 = dp->o2;
-        double du = (((o0 * x) * y - o1 * (x * x)) - o1) + o2 * y;
-        double dv = ((((-o2) * x + o0) + o0 * (y * y))) - (o1 * x) * y;
-        du = du * dp->sx;
-        dv = dv * dp->sy;
-        u = u - du;
-        v = v - dv;
-    }
-    *fu = u; *fv = v;
-}
-static __device__ __forceinline__ void derot_apply(double2 f, const DerotParams*, int, int, int, int, double* fu, double* fv)
-{
-    *fu = f.x; *fv = f.y;
-}
+// derot_apply (the derotated flow vector at a pixel, reference operation order) is in mavflow_internal.h: kernels_validation.hip uses it too.
 static __device__ __forceinline__ float2 flow_raw(const float* __restrict__ flow, int W, int row, int col)
 {
     return *(const float2*)(flow + ((size_t)row * W + col) * 2);

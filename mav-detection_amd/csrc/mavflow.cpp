@@ -22,6 +22,7 @@
 
 #include "mavflow_internal.h"
 #include "../../include/mavflow_truth.h"
+#include "../../include/mavflow_validation.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const char* fmt, ...)
@@ -328,9 +329,10 @@ struct Stager {
         }
     }
 };
-enum KernelId { K_BLUR_RESIZE, K_POLYEXP, K_UPDATE, K_ITER, K_ITER_COARSE, K_FOE, K_PHI, K_MISC, K_LK_CORNERS, K_LK_PYRAMID, K_LK_TRACK, K_LK_PICK, K_COMPONENTS, K_HISTORY_PUT, K_HISTORY_TRACE, K_COUNT };
+enum KernelId { K_BLUR_RESIZE, K_POLYEXP, K_UPDATE, K_ITER, K_ITER_COARSE, K_FOE, K_PHI, K_MISC, K_LK_CORNERS, K_LK_PYRAMID, K_LK_TRACK, K_LK_PICK, K_COMPONENTS, K_HISTORY_PUT, K_HISTORY_TRACE, K_GTS_MAX, K_GTS_COUNT, K_GTS_LIST, K_GTS_SUM, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"blur_resize", "polyexp", "update_matrices", "blur_iter", "blur_iter_coarse",
-                                                  "foe_ransac", "phi_mask_box", "misc", "lk_corners", "lk_pyramid", "lk_track", "lk_pick", "components", "history_put", "history_trace"};
+                                                  "foe_ransac", "phi_mask_box", "misc", "lk_corners", "lk_pyramid", "lk_track", "lk_pick", "components", "history_put", "history_trace",
+                                                  "gt_stats_max", "gt_stats_count", "gt_stats_list", "gt_stats_sum"};
 struct ProfRec { int kid; hipEvent_t a, b; int stream; };
 struct ProfInterval { int kid; float t0, t1; int stream; };      // ms since the profile was switched on
 
@@ -502,6 +504,8 @@ struct mav_ctx {
     std::vector<mav_history*> histories;       // flow histories (mav_history_create): the objects are the context's, their rings are in `mem`
     double* radial_edges = nullptr;            // mav_radial_error_hist: the two edge lists of the call in hand (first call; 2 * MAV_RADIAL_MAX_EDGES doubles)
     RadialEdges radial_mag{}, radial_err{};    // ... and what the stream's last call put there (n = 0: nothing): a sequence sends its lists once
+    void* gts_scratch = nullptr;               // mav_gt_stats: accumulators, row counts and (without a caller's index list) the list of the call in hand
+    size_t gts_cap = 0;
     hipEvent_t t0 = nullptr, t1 = nullptr;
     int profiling = 0;               // 0 off; 1 = HIP events around every launch; 2 = around every RUN of launches of one class on a stream
     struct OpenRun { hipStream_t st; int kid; hipEvent_t a; };
@@ -4541,5 +4545,81 @@ extern "C" int mav_radial_error_hist(mav_ctx* c, const float* flow, const float*
     h.fetch(table, dt, words * sizeof(int64_t));
     CHK(h.staged());
     CHK(radial_hist_enqueue(c, df, dg, ds, batch, em, ee, dt));
+    return h.finish();
+}
+
+// ---- validation tail (include/mavflow_validation.h) --------------------------------------------------------------------------------------
+// Like the ground-truth calls these keep every kind of resident state: the context's stream, staging blocks behind the last call's
+// (HostCall::beside), the caller's outputs and gts_scratch -- no last_* record is touched and no buffer one points at is written.
+extern "C" void mav_gt_stats_defaults(mav_gt_stats_params* p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->dt = 1.0;
+    p->box_fraction = 0.1;
+    p->depth_fraction = 0.8f;
+    p->seg_threshold = 127;
+}
+// Everything a call can be refused for from its arguments alone, before the context is looked at.
+static int gt_stats_checked(mav_ctx* c, const uint8_t* seg, const float* gt_flow, const float* depth, const mav_gt_stats_params* params, int batch,
+                            int max_pixels, const mav_gt_stats_record* records, const int32_t* indices, bool dev, const char* fn)
+{
+    if (!c) return fail(MAV_ERR_ARG, "%s: NULL context", fn);
+    if (!seg) return fail(MAV_ERR_ARG, "%s: NULL seg", fn);
+    if (!params) return fail(MAV_ERR_ARG, "%s: NULL params", fn);
+    if (!records) return fail(MAV_ERR_ARG, "%s: NULL records", fn);
+    if (batch < 1) return fail(MAV_ERR_ARG, "%s: batch %d is less than 1", fn, batch);
+    if (max_pixels < 1 || max_pixels > MAV_GT_STATS_MAX_PIXELS)
+        return fail(MAV_ERR_ARG, "%s: max_pixels %d outside [1, %d]", fn, max_pixels, MAV_GT_STATS_MAX_PIXELS);
+    if (dev) {
+        if ((uintptr_t)depth % 4) return fail(MAV_ERR_ARG, "%s: depth is not aligned to its 4-byte elements", fn);
+        if ((uintptr_t)gt_flow % 8) return fail(MAV_ERR_ARG, "%s: gt_flow is not aligned to its 8-byte pairs", fn);
+        if ((uintptr_t)params % 8) return fail(MAV_ERR_ARG, "%s: params is not aligned to 8 bytes", fn);
+        if ((uintptr_t)records % 16) return fail(MAV_ERR_ARG, "%s: records is not aligned to 16 bytes", fn);
+        if ((uintptr_t)indices % 4) return fail(MAV_ERR_ARG, "%s: indices is not aligned to its 4-byte elements", fn);
+    } else {
+        for (int b = 0; b < batch; b++) {
+            const mav_gt_stats_params& p = params[b];
+            if (p.flags & ~(MAV_GT_STATS_FRAME0 | MAV_GT_STATS_THR_F64)) return fail(MAV_ERR_ARG, "%s: params[%d].flags 0x%x has unknown bits", fn, b, p.flags);
+            for (int k = 0; k < 3; k++)
+                if (!std::isfinite(p.omega[k])) return fail(MAV_ERR_ARG, "%s: params[%d].omega[%d] is not finite", fn, b, k);
+            if (!std::isfinite(p.dt)) return fail(MAV_ERR_ARG, "%s: params[%d].dt is not finite", fn, b);
+            if (p.dt == 0.0 && !(p.flags & MAV_GT_STATS_FRAME0)) return fail(MAV_ERR_ARG, "%s: params[%d].dt is 0 without MAV_GT_STATS_FRAME0", fn, b);
+        }
+    }
+    return MAV_OK;
+}
+extern "C" int mav_gt_stats_dev(mav_ctx* c, const uint8_t* seg, const float* gt_flow, const uint8_t* sky, const float* depth,
+                                const mav_gt_stats_params* params, int batch, int max_pixels, mav_gt_stats_record* records, int32_t* indices)
+{
+    const char* fn = "mav_gt_stats_dev";
+    CHK(gt_stats_checked(c, seg, gt_flow, depth, params, batch, max_pixels, records, indices, true, fn));
+    CHK(check_dev_call(c, batch, fn));
+    CHK(grow_buffer(c, &c->gts_scratch, &c->gts_cap, gt_stats_scratch_bytes(batch, c->H, max_pixels, gt_flow && !indices), MEM_OTHER, READ_ON_COMPUTE,
+                    ALLOC_FIRST, "validation scratch"));
+    const GtStatsCall k{seg, sky, gt_flow, depth, params, batch, c->W, c->H, max_pixels, c->gts_scratch, records, indices};
+    static const int kid[GTS_PHASES] = {K_GTS_MAX, K_GTS_COUNT, K_GTS_LIST, K_GTS_SUM};
+    for (int ph = 0; ph < GTS_PHASES; ph++) {
+        ProfScope ps(c, kid[ph]);
+        launch_gt_stats_phase(c->stream, ph, k);
+    }
+    return check_launch("validation statistics");
+}
+extern "C" int mav_gt_stats(mav_ctx* c, const uint8_t* seg, const float* gt_flow, const uint8_t* sky, const float* depth, const mav_gt_stats_params* params,
+                            int batch, int max_pixels, mav_gt_stats_record* records, int32_t* indices)
+{
+    CHK(gt_stats_checked(c, seg, gt_flow, depth, params, batch, max_pixels, records, indices, false, "mav_gt_stats"));
+    HostCall h(c, "mav_gt_stats");
+    CHK(h.beside(batch));
+    const size_t n = c->n0 * batch;
+    const uint8_t* ds = h.in(seg, n);
+    const float* dg = h.in(gt_flow, n * 2 * sizeof(float));
+    const uint8_t* dk = h.in(sky, n);
+    const float* dd = h.in(depth, n * sizeof(float));
+    const mav_gt_stats_params* dp = h.in(params, sizeof(mav_gt_stats_params) * batch);
+    mav_gt_stats_record* dr = h.out(records, sizeof(mav_gt_stats_record) * batch);
+    int32_t* di = h.out(indices, sizeof(int32_t) * (size_t)batch * max_pixels);
+    CHK(h.staged());
+    CHK(mav_gt_stats_dev(c, ds, dg, dk, dd, dp, batch, max_pixels, dr, di));
     return h.finish();
 }

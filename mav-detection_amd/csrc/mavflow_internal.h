@@ -40,6 +40,29 @@ struct DerotParams {  // one pair; Detector.derotate
     int mode;                   // MAV_PAIR_*
 };
 
+// Derotated flow vector at pixel (col, row) in double, reference operation order (detector.py:92-114).
+static __device__ __forceinline__ void derot_apply(float2 f, const DerotParams* __restrict__ dp, int W, int H, int row, int col,
+                                                   double* fu, double* fv)
+{
+    double u = (double)f.x, v = (double)f.y;
+    if (dp && dp->mode == MAV_PAIR_DEROTATE) {
+        const double x = -((double)col / (double)W - 0.5) * 2.0;
+        const double y = -((double)row / (double)H - 0.5) * 2.0;
+        const double o0 = dp->o0, o1 = dp->o1, o2 = dp->o2;
+        double du = (((o0 * x) * y - o1 * (x * x)) - o1) + o2 * y;
+        double dv = ((((-o2) * x + o0) + o0 * (y * y))) - (o1 * x) * y;
+        du = du * dp->sx;
+        dv = dv * dp->sy;
+        u = u - du;
+        v = v - dv;
+    }
+    *fu = u; *fv = v;
+}
+static __device__ __forceinline__ void derot_apply(double2 f, const DerotParams*, int, int, int, int, double* fu, double* fv)
+{
+    *fu = f.x; *fv = f.y;
+}
+
 // Several layers in one launch (a small group's whole pyramid): job tables passed by value in the kernel arguments.
 #define MAV_MAX_JOBS 6
 struct PolyJob { const float* I; float* R; size_t I_stride, R_stride; int w, h, tiles_x, per_img, first_block, pad; };
@@ -353,3 +376,22 @@ int radial_hist_grid(size_t npx, int B);
 // of granting the LDS, if any (nothing is launched then).
 hipError_t launch_radial_hist(hipStream_t st, const float* flow, const float* gt, const uint8_t* sky, int B, int W, int H, const RadialEdges& mag,
                               const RadialEdges& err, double* edges_dev, bool edges_resident, unsigned long long* table);
+
+// ---- validation tail (kernels_validation.hip, compiled with -ffp-contract=off; include/mavflow_validation.h) -----------------------------
+#define MAV_GT_STATS_GRID_CAP 2048u    // workgroups of 256 pixels per image in the maxima's launch; larger frames loop
+// One image's accumulators between the phases: the head of the call's scratch, B of them; then (B, H) int32 row counts; then, when
+// the caller wants the flow sum but no index list, the (B, max_pixels) list of the call's own.
+struct GtsAcc { unsigned long long drone, pos, tp, fp; int seg_max; unsigned depth_key, nan; int pad; int box[4]; };
+static_assert(sizeof(GtsAcc) == 64, "GtsAcc");
+inline size_t gts_rows_offset(int B) { return sizeof(GtsAcc) * (size_t)B; }
+inline size_t gts_list_offset(int B, int H) { return gts_rows_offset(B) + ((sizeof(int) * (size_t)B * H + 15) & ~(size_t)15); }
+size_t gt_stats_scratch_bytes(int B, int H, int max_pixels, bool own_list);
+// What one call reads and writes, all device pointers: seg, sky (B, H, W) u8, depth (B, H, W) float32 aligned to 4, gt_flow (B, H, W, 2)
+// float32 aligned to 8 (sky, depth, gt_flow may be null), params: B mav_gt_stats_params, records: B mav_gt_stats_record, indices
+// (B, max_pixels) int32 or null, scratch: gt_stats_scratch_bytes(B, H, max_pixels, gt_flow && !indices) bytes aligned to 16.
+struct GtStatsCall {
+    const uint8_t *seg, *sky; const float *gt_flow, *depth; const void* params; int B, W, H, max_pixels; void* scratch; void* records; int32_t* indices;
+};
+enum { GTS_PHASE_MAX, GTS_PHASE_COUNT, GTS_PHASE_LIST, GTS_PHASE_SUM, GTS_PHASES };
+// one phase's launches (the phases of a call in this order, on one stream)
+void launch_gt_stats_phase(hipStream_t st, int phase, const GtStatsCall& k);

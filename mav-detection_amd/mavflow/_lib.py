@@ -1682,10 +1682,10 @@ class Context:
         check(self.lib.mav_profile_enable(self.h, int(on)))
 
     def profile_get(self) -> dict:
-        n = C.c_int(16)
-        names = (C.c_char_p * 16)()
-        ms = (C.c_double * 16)()
-        cnt = (C.c_long * 16)()
+        n = C.c_int(32)
+        names = (C.c_char_p * 32)()
+        ms = (C.c_double * 32)()
+        cnt = (C.c_long * 32)()
         check(self.lib.mav_profile_get(self.h, C.byref(n), names, ms, cnt))
         return {names[i].decode(): (ms[i], cnt[i]) for i in range(n.value)}
 
@@ -1957,3 +1957,7 @@ def device_count() -> int:
 # include/mavflow_truth.h (Context.gt_flow, .radial_error_hist, .radial_error_accumulator): a binding module of its own, attached here so
 # that every Context has the methods
 from . import _truth  # noqa: E402,F401
+
+
+# include/mavflow_validation.h (Context.gt_stats, .gt_stats_enqueue): likewise
+from . import _validation  # noqa: E402,F401

@@ -192,9 +192,23 @@ def _write_stream(path: str, stream) -> None:
 class Processor:
     def __init__(self, config: RunConfig, results_path: Optional[str] = None, images_path: Optional[str] = None,
                  processed_path: Optional[str] = None, png_encoder: str = "host", algorithm: Optional["Detector.Algorithm"] = None,
-                 blobs: Optional[dict] = None, roc: Optional[dict] = None) -> None:
+                 blobs: Optional[dict] = None, roc: Optional[dict] = None, validation: str = "host") -> None:
+        if validation not in ("host", "device"):
+            raise ValueError(f"validation must be 'host' or 'device', got {validation!r}")
         if png_encoder not in ("host", "device"):
             raise ValueError(f"png_encoder must be 'host' or 'device', got {png_encoder!r}")
+        # extra: validation="device" takes the validation tail of the FoE loops (processor.py:315-317, 343-347, 360) -- drone_size_pixels,
+        # the box centre behind center_phi, sky_tpr / sky_fpr and drone_flow_pixels -- from ONE Context.gt_stats call per batch on the
+        # loop's own context (include/mavflow_validation.h) instead of full-frame numpy on the host: no np.nonzero, no
+        # get_simple_bounding_box upload, no dataset.validate_sky_segment.  The sky scores then follow the reference's
+        # Dataset.validate_sky_segment rule (depth > 0.80 * max(depth), calculate_tpr_fpr) WHATEVER the dataset overrides, and the depth
+        # buffer has to be float32 (as the reference's .pfm reader returns it).  A ground-truth flow the dataset hands out as a device
+        # handle of the loop's context is summed where it is; a host array is not uploaded: it is gathered at the listed pixels and
+        # averaged as today.  A frame whose drone has more than validation_max_pixels pixels takes today's host path for its pixel list.
+        # FrameResult, its JSON and every file are the same either way; the global-motion branch has no validation tail and ignores it.
+        self.validation = validation
+        self.validation_max_pixels = _lib._validation.DEFAULT_MAX_PIXELS
+        self._tails: Dict[int, dict] = dict()
         # extra: blobs=dict(connectivity=, min_area=, max_blobs=) (any subset; {} = the defaults 8, 1, 256) labels every frame's fixed mask
         # on the device, inside the frame's own step, and fills detection_blobs[i] = [(Rectangle, area, (cx, cy)), ...] in label order --
         # one entry per connected component where detection_boxes[i] is the hull of them all.  None (default): not one launch more.
@@ -338,12 +352,17 @@ class Processor:
         r = FrameResult()
         r.foe_dense = foe_dense
         r.foe_gt = utils.assert_type(self.dataset.get_gt_foe(i))
-        segmentation, rows, cols = self._segmentation(i)
-        # ground-truth flow of the drone: derotated at the drone's pixels only (pointwise, same values as derotating the frame)
-        gt = utils.assert_type(self.dataset.get_gt_of(i))
-        with np.errstate(all="ignore"):
-            drone_flow_avg_gt = np.average(self.detector.derotate_at(i - self.frame_step_size, i, gt[rows, cols], rows, cols), axis=0)
-        center = self._gt_center(segmentation)
+        tail = self._tails.pop(i, None)                        # validation="device": what the batch's gt_stats call found for this frame
+        if tail is not None:
+            segmentation, center, drone_flow_avg_gt, size = tail["seg"], tail["center"], tail["flow_avg"], tail["size"]
+        else:
+            segmentation, rows, cols = self._segmentation(i)
+            # ground-truth flow of the drone: derotated at the drone's pixels only (pointwise, same values as derotating the frame)
+            gt = utils.assert_type(self.dataset.get_gt_of(i))
+            with np.errstate(all="ignore"):
+                drone_flow_avg_gt = np.average(self.detector.derotate_at(i - self.frame_step_size, i, gt[rows, cols], rows, cols), axis=0)
+            center = self._gt_center(segmentation)
+            size = np.int64(rows.size)                         # == np.sum(segmentation > 127), a numpy integer as in the reference
         r.center_phi = np.rad2deg(np.arctan2(center[1] - r.foe_gt[1], center[0] - r.foe_gt[0]))
         if counts_fixed is not None:
             r.tpr_fixed, r.fpr_fixed = im_helpers._rates(counts_fixed)
@@ -353,7 +372,7 @@ class Processor:
             r.tpr, r.fpr = im_helpers.calculate_tpr_fpr(segmentation, 255 * total_mask)
         r.sky_tpr, r.sky_fpr = sky_scores
         r.drone_flow_pixels = (drone_flow_avg_gt[0], drone_flow_avg_gt[1])
-        r.drone_size_pixels = np.int64(rows.size)              # == np.sum(segmentation > 127), a numpy integer as in the reference
+        r.drone_size_pixels = size
         r.time = self.dataset.get_time(i)
         return r
 
@@ -440,21 +459,73 @@ class Processor:
         dt = self.dataset.get_delta_time(i)
         return np.asarray(self.dataset.get_angular_difference(i - self.frame_step_size, i), np.float64) / dt, dt
 
-    def _sky_and_gt(self, ids):
-        """(submit() keywords for the sky masks and the ground truth of these frames, their segmentation tuples).  A dataset that declares
-        an image constant has it uploaded once for the run; otherwise one image per frame travels with the batch."""
+    def _sky_and_gt(self, ids, segs=None):
+        """(submit() keywords for the sky masks and the ground truth of these frames, their sky masks).  A dataset that declares
+        an image constant has it uploaded once for the run; otherwise one image per frame travels with the batch.  segs: the frames'
+        segmentation images (channel 0) where the caller has them already (validation="device": no drone pixels are derived here)."""
         kw = {}
         skies = [self.dataset.get_sky_segmentation(i) for i in ids]
         if getattr(self.dataset, "constant_sky_segmentation", False):
             kw["sky_shared"] = skies[0]
         else:
             kw["sky"] = skies
-        segs = [self._segmentation(i) for i in ids]
+        if segs is None:
+            segs = [self._segmentation(i)[0] for i in ids]
         if getattr(self.dataset, "constant_segmentation", False):
-            kw["gt_shared"] = segs[0][0]
+            kw["gt_shared"] = segs[0]
         else:
-            kw["gt"] = [sg[0] for sg in segs]
+            kw["gt"] = list(segs)
         return kw, skies
+
+    def _seg_plane(self, i: int) -> np.ndarray:
+        """Channel 0 of the dataset's segmentation image, contiguous (once for a dataset that declares it constant): no pixel list."""
+        seg3 = self.dataset.get_segmentation(i)
+        if getattr(self.dataset, "constant_segmentation", False):
+            if self._seg_plane_val is None:
+                self._seg_plane_val = np.ascontiguousarray(seg3[..., 0])
+            return self._seg_plane_val
+        return np.ascontiguousarray(seg3[..., 0])
+
+    _seg_plane_val = None
+
+    def _validation_tail(self, ctxs, ids):
+        """validation="device": ONE Context.gt_stats call for frames `ids` on one of the loop's contexts `ctxs`, at the point where the
+        host path runs _sky_and_gt and dataset.validate_sky_segment.  Returns what those give -- (submit() keywords, sky masks, sky
+        scores per frame) -- and leaves every frame's tail (segmentation, drone size, box centre, average ground-truth flow of the
+        drone) in self._tails for _fill_result.
+        The ground-truth flow: device handles of one of these contexts that follow each other in memory (one frame always does) are
+        summed on the device (the record's flow_sum); anything else is read as host arrays, gathered at the listed pixels and averaged
+        as the host path does (Detector.derotate_at, np.average).  A frame with more drone pixels than validation_max_pixels takes
+        the host path's np.nonzero for its list."""
+        W, H = self.dataset.capture_size
+        n = len(ids)
+        segs = [self._seg_plane(i) for i in ids]
+        kw, skies = self._sky_and_gt(ids, segs)
+        depths = [utils.assert_type(self.dataset.get_depth(i)) for i in ids]
+        gts = [utils.assert_type(self.dataset.get_gt_of(i)) for i in ids]
+        ctx = ctxs[0]
+        on_dev = all(isinstance(g, pipeline.DeviceArray) and g.on_device and np.dtype(g.dtype) == np.float32 and tuple(g.shape) == (H, W, 2) for g in gts)
+        if on_dev:
+            ctx = next((c for c in ctxs if c is gts[0].ctx), None)
+            on_dev = ctx is not None and all(g.ctx is ctx for g in gts) and all(gts[k + 1].ptr == gts[k].ptr + gts[k].nbytes for k in range(n - 1))
+            ctx = ctx if on_dev else ctxs[0]
+        gt_arg = pipeline.DeviceArray(ctx, gts[0].ptr, (n, H, W, 2), np.float32) if on_dev else None
+        rates = [self._rates(i) if i >= 1 else (np.zeros(3), 1.0) for i in ids]
+        out = ctx.gt_stats(np.stack(segs), gt_flow=gt_arg, sky=np.stack([np.asarray(sk) for sk in skies]), depth=np.stack(depths),
+                           omega=np.stack([r[0] for r in rates]), dt=[r[1] for r in rates], frame0=[i < 1 for i in ids],
+                           max_pixels=self.validation_max_pixels, indices=True)
+        for k, i in enumerate(ids):
+            avg = out["drone_flow_avg"][k] if on_dev else None
+            if avg is None:
+                if out["truncated"][k]:
+                    rows, cols = np.nonzero(segs[k] > 127)
+                else:
+                    rows, cols = np.divmod(out["indices"][k].astype(np.intp), W)
+                gt = np.asarray(gts[k])
+                with np.errstate(all="ignore"):
+                    avg = np.average(self.detector.derotate_at(i - self.frame_step_size, i, gt[rows, cols], rows, cols), axis=0)
+            self._tails[i] = dict(seg=segs[k], size=out["drone_size_pixels"][k], center=out["box"][k].get_center(), flow_avg=avg)
+        return kw, skies, out["sky_tpr_fpr"]
 
     def run_detection(self) -> Dict[int, FrameResult]:
         """The reference's loop (processor.py:283-341): one frame index at a time, flow from the dataset's seam (get_flow_uv: a
@@ -465,7 +536,10 @@ class Processor:
         (detector.py:80-81).  The sample coordinates are drawn from np.random exactly where get_FOE_dense draws them.
         Software-pipelined: frame i's FrameResult is filled in (and its JSON written) after the following frames -- as many as the
         pipeline has lanes (pipeline.auto_lanes: 3 - 4 contexts taken in turn for frames up to 1080p, whose one-pair chains of launches
-        then interleave on the GPU) -- have been enqueued; results, files and their order are those of the plain loop."""
+        then interleave on the GPU) -- have been enqueued; results, files and their order are those of the plain loop.
+        With Processor(validation="device") the frame's drone size, box centre, sky scores and average ground-truth flow come from one
+        Context.gt_stats call (_validation_tail); the sky scores then follow the reference's Dataset.validate_sky_segment rule whatever
+        the dataset overrides.  The same holds for run_detection_batched() (one call per batch) and run_detection_staged()."""
         from collections import deque
         if self.detector.is_homography_based():
             return self._run_global_motion()
@@ -498,9 +572,13 @@ class Processor:
                 finish(0)
                 self._drop_stale_pipes()
                 pipe = now
-            kw, skies = self._sky_and_gt([i])
-            self.sky_mask = skies[0]
-            sky = self.dataset.validate_sky_segment(self.sky_mask, utils.assert_type(self.dataset.get_depth(i)))
+            if self.validation == "device":
+                kw, skies, scores = self._validation_tail(ctxs, [i])
+                self.sky_mask, sky = skies[0], scores[0]
+            else:
+                kw, skies = self._sky_and_gt([i])
+                self.sky_mask = skies[0]
+                sky = self.dataset.validate_sky_segment(self.sky_mask, utils.assert_type(self.dataset.get_depth(i)))
             rand1 = np.empty((2000, 2), dtype=np.uint32)                 # focus_of_expansion.py:69-71
             rand1[..., 0] = np.random.randint(0, self.flow_uv.shape[0], 2000)
             rand1[..., 1] = np.random.randint(0, self.flow_uv.shape[1], 2000)
@@ -831,8 +909,12 @@ class Processor:
         """One frame through the reference-named calls (processor.py:306-341), flow already in self.flow_uv."""
         self._derot_frame = i
         self.flow_uv_derotated = self.detector.derotate(i - self.frame_step_size, i, np.asarray(self.flow_uv))
-        self.sky_mask = self.dataset.get_sky_segmentation(i)
-        sky = self.dataset.validate_sky_segment(self.sky_mask, utils.assert_type(self.dataset.get_depth(i)))
+        if self.validation == "device":
+            _, skies, scores = self._validation_tail(self._own_ctxs(1, 1), [i])
+            self.sky_mask, sky = skies[0], scores[0]
+        else:
+            self.sky_mask = self.dataset.get_sky_segmentation(i)
+            sky = self.dataset.validate_sky_segment(self.sky_mask, utils.assert_type(self.dataset.get_depth(i)))
         foe = self.focus_of_expansion.get_FOE_dense(self.flow_uv_derotated)
         fixed, total = self.focus_of_expansion.get_masks(self.flow_uv_derotated, foe, self.sky_mask)
         self.estimate_fixed, self.total_mask = fixed, total
@@ -841,7 +923,8 @@ class Processor:
             out = im_helpers._ctx(fixed.shape[1], fixed.shape[0]).components_last(1, "fixed", b.connectivity, b.min_area, b.max_blobs)
             self.detection_blobs[i] = self._blob_list(out["blobs"][0])
         if self.roc is not None:                              # the field, FoE and sky get_masks left on the helpers' context: not moved again
-            out = im_helpers._ctx(fixed.shape[1], fixed.shape[0]).roc_sweep_last(1, self._segmentation(i)[0], self.roc["angles"], self.roc["mags"])
+            seg = self._tails[i]["seg"] if i in self._tails else self._segmentation(i)[0]
+            out = im_helpers._ctx(fixed.shape[1], fixed.shape[0]).roc_sweep_last(1, seg, self.roc["angles"], self.roc["mags"])
             self.roc_counts[i] = out["counts"][0]
         r = self._fill_result(i, foe, sky, estimate_fixed=fixed, total_mask=total)
         self._store(i, r)
@@ -897,8 +980,11 @@ class Processor:
             # frame 0 is never derotated and runs in float32 (detector.py:80-81): flagged per pair
             omega = np.stack([np.asarray(self.dataset.get_angular_difference(i - self.frame_step_size, i), np.float64) / dt
                               for i, dt in zip(ids, dts)])
-            kw, skies = self._sky_and_gt(ids)
-            sky_scores = [self.dataset.validate_sky_segment(sk, utils.assert_type(self.dataset.get_depth(i))) for i, sk in zip(ids, skies)]
+            if self.validation == "device":
+                kw, skies, sky_scores = self._validation_tail(pipe.ctxs, ids)
+            else:
+                kw, skies = self._sky_and_gt(ids)
+                sky_scores = [self.dataset.validate_sky_segment(sk, utils.assert_type(self.dataset.get_depth(i))) for i, sk in zip(ids, skies)]
             ticket = pipe.submit(samples, prev=[p[0] for p in pairs], nxt=[p[1] for p in pairs], omega=omega, dt=dts,
                                  frame0=[i < 1 for i in ids], **kw)
             pending.append((ids, ticket, sky_scores, frames))
