@@ -4623,3 +4623,153 @@ extern "C" int mav_gt_stats(mav_ctx* c, const uint8_t* seg, const float* gt_flow
     CHK(mav_gt_stats_dev(c, ds, dg, dk, dd, dp, batch, max_pixels, dr, di));
     return h.finish();
 }
+
+// ---- k-means clustering (include/mavflow_cluster.h) ---------------------------------------------------------------------------------------
+// Like the validation tail these keep every kind of resident state, and they hold no device memory of the context's at all: the _dev form
+// works in the caller's workspace, the host form in staging blocks behind the last call's (HostCall::beside).
+#include "../../include/mavflow_cluster.h"
+
+extern "C" void mav_kmeans_defaults(mav_kmeans_params* p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->K = 8;
+    p->attempts = 10;
+    p->max_iter = 10;
+    p->dims = 3;
+    p->depth = MAV_KMEANS_F32;
+    p->eps = 1.0;
+}
+static int kmeans_shape_checked(int n, int K, int dims, const char* fn)
+{
+    if (K < 1 || K > MAV_KMEANS_MAX_K) return fail(MAV_ERR_ARG, "%s: K %d outside [1, %d]", fn, K, MAV_KMEANS_MAX_K);
+    if (dims < 1 || dims > MAV_KMEANS_MAX_DIMS) return fail(MAV_ERR_ARG, "%s: dims %d outside [1, %d]", fn, dims, MAV_KMEANS_MAX_DIMS);
+    if (n < K || n > MAV_KMEANS_MAX_N) return fail(MAV_ERR_ARG, "%s: n %d outside [K = %d, %d]", fn, n, K, MAV_KMEANS_MAX_N);
+    return MAV_OK;
+}
+static int kmeans_params_checked(int n, const mav_kmeans_params* p, const char* fn)
+{
+    if (!p) return fail(MAV_ERR_ARG, "%s: NULL params", fn);
+    if (p->attempts < 1 || p->attempts > MAV_KMEANS_MAX_ATTEMPTS) return fail(MAV_ERR_ARG, "%s: attempts %d outside [1, %d]", fn, p->attempts, MAV_KMEANS_MAX_ATTEMPTS);
+    if (p->depth != MAV_KMEANS_F32 && p->depth != MAV_KMEANS_U8) return fail(MAV_ERR_ARG, "%s: depth %d is neither MAV_KMEANS_F32 nor MAV_KMEANS_U8", fn, p->depth);
+    if (p->max_iter < 1) return fail(MAV_ERR_ARG, "%s: max_iter %d is less than 1", fn, p->max_iter);
+    if (p->flags != 0) return fail(MAV_ERR_ARG, "%s: flags 0x%x: no flag is defined", fn, p->flags);
+    if (!std::isfinite(p->eps)) return fail(MAV_ERR_ARG, "%s: eps is not finite", fn);
+    return kmeans_shape_checked(n, p->K, p->dims, fn);
+}
+extern "C" size_t mav_kmeans_workspace_bytes(int n, int batch, const mav_kmeans_params* p)
+{
+    if (batch < 1 || kmeans_params_checked(n, p, "mav_kmeans_workspace_bytes") != MAV_OK) return 0;
+    return km_image_bytes(n, p->attempts, p->K, p->dims) * (size_t)batch;
+}
+// Everything a call can be refused for from its arguments alone, before the context is looked at.
+static int kmeans_checked(mav_ctx* c, const void* samples, int n, int batch, const mav_kmeans_params* p, const float* init, const int32_t* labels,
+                          const float* centers, const mav_kmeans_record* records, const char* fn)
+{
+    if (!c) return fail(MAV_ERR_ARG, "%s: NULL context", fn);
+    if (!samples) return fail(MAV_ERR_ARG, "%s: NULL samples", fn);
+    if (!init) return fail(MAV_ERR_ARG, "%s: NULL init", fn);
+    if (!labels) return fail(MAV_ERR_ARG, "%s: NULL labels", fn);
+    if (!centers) return fail(MAV_ERR_ARG, "%s: NULL centers", fn);
+    if (!records) return fail(MAV_ERR_ARG, "%s: NULL records", fn);
+    if (batch < 1) return fail(MAV_ERR_ARG, "%s: batch %d is less than 1", fn, batch);
+    return kmeans_params_checked(n, p, fn);
+}
+static int kmeans_staging_checked(mav_ctx* c, int n, int batch, int dims, const char* fn)
+{
+    const size_t cap = (size_t)c->max_batch * c->n0 * 4;
+    if ((size_t)batch * n * dims > cap) return fail(MAV_ERR_ARG, "%s: batch * n * dims = %zu is more than max_batch * W * H * 4 = %zu", fn, (size_t)batch * n * dims, cap);
+    return MAV_OK;
+}
+extern "C" int mav_kmeans_dev(mav_ctx* c, const void* samples, int n, int batch, const mav_kmeans_params* p, const float* init, int32_t* labels, float* centers,
+                              mav_kmeans_record* records, void* workspace, size_t workspace_bytes)
+{
+    const char* fn = "mav_kmeans_dev";
+    CHK(kmeans_checked(c, samples, n, batch, p, init, labels, centers, records, fn));
+    if (!workspace) return fail(MAV_ERR_ARG, "%s: NULL workspace", fn);
+    if (p->depth == MAV_KMEANS_F32 && (uintptr_t)samples % 4) return fail(MAV_ERR_ARG, "%s: samples is not aligned to its 4-byte elements", fn);
+    if ((uintptr_t)init % 4) return fail(MAV_ERR_ARG, "%s: init is not aligned to its 4-byte elements", fn);
+    if ((uintptr_t)labels % 4) return fail(MAV_ERR_ARG, "%s: labels is not aligned to its 4-byte elements", fn);
+    if ((uintptr_t)centers % 4) return fail(MAV_ERR_ARG, "%s: centers is not aligned to its 4-byte elements", fn);
+    if ((uintptr_t)records % 16) return fail(MAV_ERR_ARG, "%s: records is not aligned to 16 bytes", fn);
+    if ((uintptr_t)workspace % 16) return fail(MAV_ERR_ARG, "%s: workspace is not aligned to 16 bytes", fn);
+    const size_t need = km_image_bytes(n, p->attempts, p->K, p->dims) * (size_t)batch;
+    if (workspace_bytes < need) return fail(MAV_ERR_ARG, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, need);
+    CHK(check_dev_call(c, batch, fn));
+    KmCall k;
+    k.samples = samples; k.init = init; k.labels = labels; k.centers = centers; k.records = records; k.ws = (char*)workspace;
+    k.n = n; k.B = batch; k.A = p->attempts; k.K = p->K; k.D = p->dims; k.u8 = p->depth == MAV_KMEANS_U8;
+    k.max_iter = p->max_iter < 2 ? 2 : p->max_iter > 100 ? 100 : p->max_iter;
+    k.eps2 = p->eps > 0.0 ? p->eps * p->eps : 0.0;
+    {
+        ProfScope ps(c, K_MISC);
+        launch_kmeans(c->stream, k);
+    }
+    return check_launch("k-means");
+}
+extern "C" int mav_kmeans(mav_ctx* c, const void* samples, int n, int batch, const mav_kmeans_params* p, const float* init, int32_t* labels, float* centers,
+                          mav_kmeans_record* records)
+{
+    const char* fn = "mav_kmeans";
+    CHK(kmeans_checked(c, samples, n, batch, p, init, labels, centers, records, fn));
+    if (batch > c->max_batch) return fail(MAV_ERR_ARG, "%s: batch %d outside [1, %d]", fn, batch, c->max_batch);
+    CHK(kmeans_staging_checked(c, n, batch, p->dims, fn));
+    const size_t items = (size_t)batch * n * p->dims, seeds = (size_t)batch * p->attempts * p->K * p->dims;
+    if (p->depth == MAV_KMEANS_F32) {
+        const float* x = (const float*)samples;
+        for (size_t i = 0; i < items; i++)
+            if (!std::isfinite(x[i])) return fail(MAV_ERR_ARG, "%s: samples[%zu] is not finite", fn, i);
+    }
+    for (size_t i = 0; i < seeds; i++)
+        if (!std::isfinite(init[i])) return fail(MAV_ERR_ARG, "%s: init[%zu] is not finite", fn, i);
+    HostCall h(c, fn);
+    CHK(h.beside(batch));
+    const size_t wsb = km_image_bytes(n, p->attempts, p->K, p->dims) * (size_t)batch;
+    const char* dx = h.in((const char*)samples, items * (p->depth == MAV_KMEANS_U8 ? 1 : sizeof(float)));
+    const float* di = h.in(init, seeds * sizeof(float));
+    char* dw = h.scratch<char>(wsb);
+    int32_t* dl = h.out(labels, sizeof(int32_t) * (size_t)batch * n);
+    float* dc = h.out(centers, sizeof(float) * (size_t)batch * p->K * p->dims);
+    mav_kmeans_record* dr = h.out(records, sizeof(mav_kmeans_record) * batch);
+    CHK(h.staged());
+    CHK(mav_kmeans_dev(c, dx, n, batch, p, di, dl, dc, dr, dw, wsb));
+    return h.finish();
+}
+static int kmeans_paint_checked(mav_ctx* c, const int32_t* labels, const float* centers, int n, int batch, int K, int dims, const uint8_t* res, const char* fn)
+{
+    if (!c) return fail(MAV_ERR_ARG, "%s: NULL context", fn);
+    if (!labels) return fail(MAV_ERR_ARG, "%s: NULL labels", fn);
+    if (!centers) return fail(MAV_ERR_ARG, "%s: NULL centers", fn);
+    if (!res) return fail(MAV_ERR_ARG, "%s: NULL res", fn);
+    if (batch < 1) return fail(MAV_ERR_ARG, "%s: batch %d is less than 1", fn, batch);
+    return kmeans_shape_checked(n, K, dims, fn);
+}
+extern "C" int mav_kmeans_paint_dev(mav_ctx* c, const int32_t* labels, const float* centers, int n, int batch, int K, int dims, uint8_t* res, uint8_t* mask)
+{
+    const char* fn = "mav_kmeans_paint_dev";
+    CHK(kmeans_paint_checked(c, labels, centers, n, batch, K, dims, res, fn));
+    if ((uintptr_t)labels % 4) return fail(MAV_ERR_ARG, "%s: labels is not aligned to its 4-byte elements", fn);
+    if ((uintptr_t)centers % 4) return fail(MAV_ERR_ARG, "%s: centers is not aligned to its 4-byte elements", fn);
+    CHK(check_dev_call(c, batch, fn));
+    {
+        ProfScope ps(c, K_MISC);
+        launch_kmeans_paint(c->stream, labels, centers, n, batch, K, dims, res, mask);
+    }
+    return check_launch("k-means paint");
+}
+extern "C" int mav_kmeans_paint(mav_ctx* c, const int32_t* labels, const float* centers, int n, int batch, int K, int dims, uint8_t* res, uint8_t* mask)
+{
+    const char* fn = "mav_kmeans_paint";
+    CHK(kmeans_paint_checked(c, labels, centers, n, batch, K, dims, res, fn));
+    if (batch > c->max_batch) return fail(MAV_ERR_ARG, "%s: batch %d outside [1, %d]", fn, batch, c->max_batch);
+    CHK(kmeans_staging_checked(c, n, batch, dims, fn));
+    HostCall h(c, fn);
+    CHK(h.beside(batch));
+    const int32_t* dl = h.in(labels, sizeof(int32_t) * (size_t)batch * n);
+    const float* dc = h.in(centers, sizeof(float) * (size_t)batch * K * dims);
+    uint8_t* dr = h.out(res, (size_t)batch * n * dims);
+    uint8_t* dm = h.out(mask, (size_t)batch * n);
+    CHK(h.staged());
+    CHK(mav_kmeans_paint_dev(c, dl, dc, n, batch, K, dims, dr, dm));
+    return h.finish();
+}

@@ -395,3 +395,32 @@ struct GtStatsCall {
 enum { GTS_PHASE_MAX, GTS_PHASE_COUNT, GTS_PHASE_LIST, GTS_PHASE_SUM, GTS_PHASES };
 // one phase's launches (the phases of a call in this order, on one stream)
 void launch_gt_stats_phase(hipStream_t st, int phase, const GtStatsCall& k);
+
+// ---- k-means clustering (kernels_cluster.hip, compiled with -ffp-contract=off; include/mavflow_cluster.h) --------------------------------
+#define KM_THREADS 256
+#define KM_PER_THREAD 16                // KM_THREADS * KM_PER_THREAD = MAV_KMEANS_CHUNK
+#define KM_GRID_CAP 1024u               // workgroups per image in the full-frame launches; more chunks are strode over
+// One image's control block at the head of its part of the workspace: everything the launches decide lives here.
+struct KmState {
+    double S[16][16][4];                // [attempt][cluster][component]
+    double shift[16], compact[16];
+    unsigned long long key[16];         // the repair's argmax: dist bits << 32 | sample index
+    float c[16][16][4];
+    float mean[16][4];                  // the donor's mean of the repair in hand
+    int n[16][16];
+    int done[16], iters[16], repairs[16], pending[16], donor[16];   // pending: the empty cluster being repaired, or -1
+    int live, any_pending, best, skipped;
+};
+// What one call works on, all device pointers; the workspace layout follows from (n, B, A, K, D) alone.
+struct KmCall {
+    const void* samples; const float* init; int32_t* labels; float* centers; void* records; char* ws;
+    int n, B, A, K, D, u8, max_iter; double eps2;
+};
+inline size_t km_chunks(int n) { return ((size_t)n + KM_THREADS * KM_PER_THREAD - 1) / (KM_THREADS * KM_PER_THREAD); }
+inline size_t km_state_bytes() { return (sizeof(KmState) + 255) & ~(size_t)255; }
+inline size_t km_labels_bytes(int n, int A) { return ((size_t)A * n + 255) & ~(size_t)255; }            // uint8 (A, n)
+inline size_t km_slab_bytes(int n, int A, int K, int D) { return sizeof(double) * km_chunks(n) * A * K * (D + 1); }
+inline size_t km_image_bytes(int n, int A, int K, int D) { return km_state_bytes() + km_labels_bytes(n, A) + ((km_slab_bytes(n, A, K, D) + 255) & ~(size_t)255); }
+// the whole launch sequence of a call
+void launch_kmeans(hipStream_t st, const KmCall& k);
+void launch_kmeans_paint(hipStream_t st, const int32_t* labels, const float* centers, int n, int B, int K, int D, uint8_t* res, uint8_t* mask);

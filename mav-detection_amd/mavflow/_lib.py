@@ -1961,3 +1961,7 @@ from . import _truth  # noqa: E402,F401
 
 # include/mavflow_validation.h (Context.gt_stats, .gt_stats_enqueue): likewise
 from . import _validation  # noqa: E402,F401
+
+
+# include/mavflow_cluster.h (Context.kmeans, .kmeans_enqueue, .kmeans_workspace_bytes, .kmeans_paint): likewise
+from . import clustering  # noqa: E402,F401

@@ -107,6 +107,10 @@ class Detector:
         # is made by the first get_history call
         self.history_length = 20
         self._history = None
+        # clustering (detector.py:396-428): off in flow_vec_subtract, as the reference's commented-out line leaves it
+        self.use_clustering = False
+        self.cluster_rng = None          # the generator of clustering's initial centres (None: np.random)
+        self.mag_handle = self.gray_handle = None    # flow_uv_warped_mag / one channel of to_rgb(magnitude) on the device, after a flow_vec_subtract of a device flow
 
     def get_gradient_and_magnitude(self, frame: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
         """Polar form of a cartesian flow field (detector.py:53-63): (magnitude, angle)."""
@@ -269,7 +273,8 @@ class Detector:
         .use_optimization).  A float32 field -- host array or the flow seam's device handle -- goes through mav_global_motion; any other
         dtype takes the reference's numpy arithmetic on the host, as derotate does.  Returns (get_flow_vis(flow_uv_warped),
         cluster_vis, to_rgb(magnitude), get_flow_vis(global_motion)) and sets flow_uv_warped, flow_uv_warped_mag, flow_max, cluster_vis,
-        opt_window, iou, flow_uv_warped_vis, prev_frame, frame_result."""
+        opt_window, iou, flow_uv_warped_vis, prev_frame, frame_result.  With .use_clustering (an extra, off by default) cluster_vis and
+        the second return are clustering(flow_uv_warped_mag)'s image instead."""
         self.frame_result = FrameResult()
         M = np.asarray(self.homography if self.algorithm == Detector.Algorithm.HOMOGRAPHY else self.aff, np.float64)
         W, H = self.dataset.capture_size[0], self.dataset.capture_size[1]
@@ -304,6 +309,8 @@ class Detector:
                 gray = b["gray"].download(np.uint8, (H, W))
                 self.flow_uv_warped = b["warped"].download(np.float32, (H, W, 2))
                 self.flow_uv_warped_mag = b["mag"].download(np.float32, (H, W))
+                from .clustering import DeviceSamples
+                self.mag_handle, self.gray_handle = DeviceSamples(ctx, b["mag"].ptr, (H, W), np.float32), DeviceSamples(ctx, b["gray"].ptr, (H, W), np.uint8)
             else:
                 ctx = im_helpers._ctx(W, H)
                 out = ctx.global_motion(host, M, optimize=self.use_optimization, outputs=("warped", "mag", "gray"))
@@ -324,6 +331,14 @@ class Detector:
             self.iou = utils.Rectangle.calculate_iou(window_optimized, gt)
         self.flow_uv_warped_vis = flow_uv_warped_vis
         self.prev_frame = orig_frame
+        if dev is None:
+            self.mag_handle = self.gray_handle = None
+        if self.use_clustering:
+            # the reference's commented-out line (detector.py:182): cluster_vis is clustering's image of the residual magnitude.  The
+            # window search above stays on the magnitude's grey image (clustering's rgb is no grey replica: channel 1 is cleared under its mask)
+            magnitude_vis = self.cluster_vis
+            self.cluster_vis, _ = self.clustering(self.mag_handle if dev is not None else self.flow_uv_warped_mag)
+            return flow_uv_warped_vis, self.cluster_vis, magnitude_vis.copy(), global_motion_vis
         return flow_uv_warped_vis, self.cluster_vis, self.cluster_vis.copy(), global_motion_vis
 
     # -- flow history (detector.py:365-388) -----------------------------------------------------------------------------------------
@@ -354,6 +369,38 @@ class Detector:
             ctx = dev[0] if dev is not None else im_helpers._ctx(W, H)
             hist = self._history = ctx.flow_history(int(self.history_length), flow_uv.dtype, "reference")
         return hist.push(flow_uv, out="reference")
+
+    # -- clustering (detector.py:396-428) -------------------------------------------------------------------------------------------
+    def clustering(self, img: np.ndarray, enable_raw: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """detector.py:396-428: k-means (K = 8, 10 attempts, criteria (EPS | MAX_ITER, 10, 1.0), random centres) of the image's values
+        taken three at a time -- the reference's reshape((-1, 3)); a size not divisible by 3 is numpy's ValueError --, every value
+        replaced by its centre scaled to 0..255.  Returns (res, zeros(0)) with enable_raw, else (rgb, mask): res repeated to three channels
+        with channel 1 cleared where res >= 225.  img: a host array (float32 and uint8 as they are, anything else as float32, the
+        reference's astype) or a device handle with .ptr, .shape, .dtype and .ctx (the mag / gray of a global-motion call on the flow's
+        context: .mag_handle, .gray_handle), clustered where it is.  The centres are drawn from .cluster_rng (None: np.random, the global
+        generator the reference's other draws use) by clustering.random_centers, not by OpenCV's private generator: the result equals no
+        cv2 run sample for sample (include/mavflow_cluster.h)."""
+        from . import clustering as _cl
+        if hasattr(img, "ptr") and getattr(img, "on_device", True) and getattr(getattr(img, "ctx", None), "alive", False):
+            shape = tuple(img.shape)
+            np.empty(shape, np.uint8).reshape((-1, 3))                    # numpy's ValueError for a size not divisible by 3
+            n = int(np.prod(shape)) // 3
+            ctx = img.ctx
+            samples = _cl.DeviceSamples(ctx, img.ptr, (n, 3), img.dtype)
+        else:
+            a = np.asarray(img)
+            shape = a.shape
+            z = a.reshape((-1, 3))
+            samples = np.ascontiguousarray(z if z.dtype in (np.float32, np.uint8) else z.astype(np.float32))
+            ctx = _cl.context_for(z.size)
+        out = ctx.kmeans(samples, K=8, attempts=10, max_iter=10, eps=1.0, rng=np.random if self.cluster_rng is None else self.cluster_rng)
+        res = ctx.kmeans_paint(out["labels"], out["centers"])[0].reshape(shape)
+        if enable_raw:
+            return res, np.zeros(0)
+        rgb = np.repeat(res[..., None], 3, axis=-1)
+        mask = rgb[..., 0] >= 225
+        rgb[mask, 1] = 0
+        return rgb, mask
 
     def is_homography_based(self) -> bool:
         return self.algorithm in [Detector.Algorithm.HOMOGRAPHY]
