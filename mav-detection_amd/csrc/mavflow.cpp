@@ -4773,3 +4773,187 @@ extern "C" int mav_kmeans_paint(mav_ctx* c, const int32_t* labels, const float* 
     CHK(mav_kmeans_paint_dev(c, dl, dc, n, batch, K, dims, dr, dm));
     return h.finish();
 }
+
+// ---- image warps (include/mavflow_warp.h) ---------------------------------------------------------------------------------------------------
+// Like the clustering calls these keep every kind of resident state and hold no device memory of the context's: the _dev forms work on the
+// caller's blocks alone, the host forms in staging blocks behind the last call's (HostCall::beside).
+#include "../../include/mavflow_warp.h"
+
+static size_t warp_px_bytes(int format)     // bytes of one pixel; 0: no such format
+{
+    switch (format) {
+    case MAV_WARP_U8C1: return 1;
+    case MAV_WARP_U8C3: return 3;
+    case MAV_WARP_F32C1: return 4;
+    case MAV_WARP_F32C2: return 8;
+    }
+    return 0;
+}
+// Everything a warp can be refused for from its arguments alone, before the context is looked at.  ops: the policy's operands, by name.
+static int warp_checked(mav_ctx* c, const void* src, int format, const void* a, const char* a_name, const void* b, const char* b_name, int flags, int batch,
+                        const void* dst, bool dev, const char* fn)
+{
+    if (!c) return fail(MAV_ERR_ARG, "%s: NULL context", fn);
+    if (!src) return fail(MAV_ERR_ARG, "%s: NULL src", fn);
+    if (!a) return fail(MAV_ERR_ARG, "%s: NULL %s", fn, a_name);
+    if (b_name && !b) return fail(MAV_ERR_ARG, "%s: NULL %s", fn, b_name);
+    if (!dst) return fail(MAV_ERR_ARG, "%s: NULL dst", fn);
+    if (!warp_px_bytes(format)) return fail(MAV_ERR_ARG, "%s: format %d is none of MAV_WARP_U8C1, _U8C3, _F32C1, _F32C2", fn, format);
+    if (flags != 0 && flags != MAV_WARP_INVERSE_MAP) return fail(MAV_ERR_ARG, "%s: flags 0x%x: 0 or MAV_WARP_INVERSE_MAP", fn, flags);
+    if (batch < 1) return fail(MAV_ERR_ARG, "%s: batch %d is less than 1", fn, batch);
+    if (dev) {
+        const bool f32 = format == MAV_WARP_F32C1 || format == MAV_WARP_F32C2;
+        const bool matrix = a_name[0] == 'M';
+        if (f32 && (uintptr_t)src % 4) return fail(MAV_ERR_ARG, "%s: src is not aligned to its 4-byte elements", fn);
+        if (f32 && (uintptr_t)dst % 4) return fail(MAV_ERR_ARG, "%s: dst is not aligned to its 4-byte elements", fn);
+        if ((uintptr_t)a % (matrix ? 8 : 4)) return fail(MAV_ERR_ARG, "%s: %s is not aligned to its %d-byte elements", fn, a_name, matrix ? 8 : 4);
+        if (b_name && (uintptr_t)b % 4) return fail(MAV_ERR_ARG, "%s: %s is not aligned to its 4-byte elements", fn, b_name);
+    }
+    return MAV_OK;
+}
+// The host forms' look at the matrices: finite, and invertible where the call inverts (the determinant as the device takes it).
+static int warp_matrices_checked(const double* M, int n, int batch, bool inverts, const char* fn)
+{
+    for (int b = 0; b < batch; b++) {
+        const double* m = M + (size_t)b * n;
+        for (int i = 0; i < n; i++)
+            if (!std::isfinite(m[i])) return fail(MAV_ERR_ARG, "%s: M[%d][%d] is not finite", fn, b, i);
+        if (!inverts) continue;
+        const double d = n == 6 ? m[0] * m[4] - m[1] * m[3]
+                                : (m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6])) + m[2] * (m[3] * m[7] - m[4] * m[6]);
+        if (d == 0 || !std::isfinite(d)) return fail(MAV_ERR_ARG, "%s: M[%d] is singular (determinant %g)", fn, b, d);
+    }
+    return MAV_OK;
+}
+static int warp_enqueue(mav_ctx* c, int policy, const void* src, int format, const void* a, const void* b, int flags, int batch, void* dst, const char* fn)
+{
+    CHK(check_dev_call(c, batch, fn));
+    {
+        ProfScope ps(c, K_MISC);
+        launch_warp(c->stream, policy, format, src, a, b, flags, c->W, c->H, batch, dst);
+    }
+    return check_launch("warp");
+}
+// One host-form warp: a and b are host blocks of a_bytes / b_bytes per call.
+static int warp_host(mav_ctx* c, int policy, const void* src, int format, const void* a, size_t a_bytes, const void* b, size_t b_bytes, int flags, int batch,
+                     void* dst, const char* fn)
+{
+    if (batch > c->max_batch) return fail(MAV_ERR_ARG, "%s: batch %d outside [1, %d]", fn, batch, c->max_batch);
+    HostCall h(c, fn);
+    CHK(h.beside(batch));
+    const size_t img = (size_t)batch * c->n0 * warp_px_bytes(format);
+    const char* ds = h.in((const char*)src, img);
+    const char* da = h.in((const char*)a, a_bytes);
+    const char* db = h.in((const char*)b, b_bytes);
+    char* dd = h.out((char*)dst, img);
+    CHK(h.staged());
+    CHK(warp_enqueue(c, policy, ds, format, da, db, flags, batch, dd, fn));
+    return h.finish();
+}
+extern "C" int mav_remap_dev(mav_ctx* c, const void* src, int format, const float* map_xy, int batch, void* dst)
+{
+    const char* fn = "mav_remap_dev";
+    CHK(warp_checked(c, src, format, map_xy, "map_xy", nullptr, nullptr, 0, batch, dst, true, fn));
+    return warp_enqueue(c, WARP_POLICY_MAP, src, format, map_xy, nullptr, 0, batch, dst, fn);
+}
+extern "C" int mav_remap(mav_ctx* c, const void* src, int format, const float* map_xy, int batch, void* dst)
+{
+    const char* fn = "mav_remap";
+    CHK(warp_checked(c, src, format, map_xy, "map_xy", nullptr, nullptr, 0, batch, dst, false, fn));
+    return warp_host(c, WARP_POLICY_MAP, src, format, map_xy, sizeof(float) * 2 * batch * c->n0, nullptr, 0, 0, batch, dst, fn);
+}
+extern "C" int mav_remap_planes_dev(mav_ctx* c, const void* src, int format, const float* map_x, const float* map_y, int batch, void* dst)
+{
+    const char* fn = "mav_remap_planes_dev";
+    CHK(warp_checked(c, src, format, map_x, "map_x", map_y, "map_y", 0, batch, dst, true, fn));
+    return warp_enqueue(c, WARP_POLICY_PLANES, src, format, map_x, map_y, 0, batch, dst, fn);
+}
+extern "C" int mav_remap_planes(mav_ctx* c, const void* src, int format, const float* map_x, const float* map_y, int batch, void* dst)
+{
+    const char* fn = "mav_remap_planes";
+    CHK(warp_checked(c, src, format, map_x, "map_x", map_y, "map_y", 0, batch, dst, false, fn));
+    const size_t plane = sizeof(float) * batch * c->n0;
+    return warp_host(c, WARP_POLICY_PLANES, src, format, map_x, plane, map_y, plane, 0, batch, dst, fn);
+}
+extern "C" int mav_warp_flow_dev(mav_ctx* c, const void* img, int format, const float* flow, int batch, void* dst)
+{
+    const char* fn = "mav_warp_flow_dev";
+    CHK(warp_checked(c, img, format, flow, "flow", nullptr, nullptr, 0, batch, dst, true, fn));
+    return warp_enqueue(c, WARP_POLICY_FLOW, img, format, flow, nullptr, 0, batch, dst, fn);
+}
+extern "C" int mav_warp_flow(mav_ctx* c, const void* img, int format, const float* flow, int batch, void* dst)
+{
+    const char* fn = "mav_warp_flow";
+    CHK(warp_checked(c, img, format, flow, "flow", nullptr, nullptr, 0, batch, dst, false, fn));
+    return warp_host(c, WARP_POLICY_FLOW, img, format, flow, sizeof(float) * 2 * batch * c->n0, nullptr, 0, 0, batch, dst, fn);
+}
+extern "C" int mav_warp_affine_dev(mav_ctx* c, const void* src, int format, const double* M, int flags, int batch, void* dst)
+{
+    const char* fn = "mav_warp_affine_dev";
+    CHK(warp_checked(c, src, format, M, "M", nullptr, nullptr, flags, batch, dst, true, fn));
+    return warp_enqueue(c, WARP_POLICY_AFFINE, src, format, M, nullptr, flags, batch, dst, fn);
+}
+extern "C" int mav_warp_affine(mav_ctx* c, const void* src, int format, const double* M, int flags, int batch, void* dst)
+{
+    const char* fn = "mav_warp_affine";
+    CHK(warp_checked(c, src, format, M, "M", nullptr, nullptr, flags, batch, dst, false, fn));
+    CHK(warp_matrices_checked(M, 6, batch, !(flags & MAV_WARP_INVERSE_MAP), fn));
+    return warp_host(c, WARP_POLICY_AFFINE, src, format, M, sizeof(double) * 6 * batch, nullptr, 0, flags, batch, dst, fn);
+}
+extern "C" int mav_warp_perspective_dev(mav_ctx* c, const void* src, int format, const double* M, int flags, int batch, void* dst)
+{
+    const char* fn = "mav_warp_perspective_dev";
+    CHK(warp_checked(c, src, format, M, "M", nullptr, nullptr, flags, batch, dst, true, fn));
+    return warp_enqueue(c, WARP_POLICY_PERSPECTIVE, src, format, M, nullptr, flags, batch, dst, fn);
+}
+extern "C" int mav_warp_perspective(mav_ctx* c, const void* src, int format, const double* M, int flags, int batch, void* dst)
+{
+    const char* fn = "mav_warp_perspective";
+    CHK(warp_checked(c, src, format, M, "M", nullptr, nullptr, flags, batch, dst, false, fn));
+    CHK(warp_matrices_checked(M, 9, batch, !(flags & MAV_WARP_INVERSE_MAP), fn));
+    return warp_host(c, WARP_POLICY_PERSPECTIVE, src, format, M, sizeof(double) * 9 * batch, nullptr, 0, flags, batch, dst, fn);
+}
+static int warp_method_checked(mav_ctx* c, const float* flow, const double* M, int kind, int batch, const mav_warp_record* records, const char* fn)
+{
+    if (!c) return fail(MAV_ERR_ARG, "%s: NULL context", fn);
+    if (!flow) return fail(MAV_ERR_ARG, "%s: NULL flow", fn);
+    if (!M) return fail(MAV_ERR_ARG, "%s: NULL M", fn);
+    if (!records) return fail(MAV_ERR_ARG, "%s: NULL records", fn);
+    if (kind != MAV_WARP_AFFINE && kind != MAV_WARP_PERSPECTIVE) return fail(MAV_ERR_ARG, "%s: kind %d is neither MAV_WARP_AFFINE nor MAV_WARP_PERSPECTIVE", fn, kind);
+    if (batch < 1) return fail(MAV_ERR_ARG, "%s: batch %d is less than 1", fn, batch);
+    return MAV_OK;
+}
+extern "C" int mav_warp_method_dev(mav_ctx* c, const float* flow, const double* M, int kind, int batch, float* diff, float* mag, mav_warp_record* records)
+{
+    const char* fn = "mav_warp_method_dev";
+    CHK(warp_method_checked(c, flow, M, kind, batch, records, fn));
+    if ((uintptr_t)flow % 4) return fail(MAV_ERR_ARG, "%s: flow is not aligned to its 4-byte elements", fn);
+    if ((uintptr_t)M % 8) return fail(MAV_ERR_ARG, "%s: M is not aligned to its 8-byte elements", fn);
+    if ((uintptr_t)diff % 4) return fail(MAV_ERR_ARG, "%s: diff is not aligned to its 4-byte elements", fn);
+    if ((uintptr_t)mag % 4) return fail(MAV_ERR_ARG, "%s: mag is not aligned to its 4-byte elements", fn);
+    if ((uintptr_t)records % 16) return fail(MAV_ERR_ARG, "%s: records is not aligned to 16 bytes", fn);
+    CHK(check_dev_call(c, batch, fn));
+    {
+        ProfScope ps(c, K_MISC);
+        launch_warp_method(c->stream, kind == MAV_WARP_AFFINE ? WARP_POLICY_AFFINE : WARP_POLICY_PERSPECTIVE, flow, M, c->W, c->H, batch, diff, mag, records);
+    }
+    return check_launch("warp method");
+}
+extern "C" int mav_warp_method(mav_ctx* c, const float* flow, const double* M, int kind, int batch, float* diff, float* mag, mav_warp_record* records)
+{
+    const char* fn = "mav_warp_method";
+    CHK(warp_method_checked(c, flow, M, kind, batch, records, fn));
+    const int n = kind == MAV_WARP_AFFINE ? 6 : 9;
+    CHK(warp_matrices_checked(M, n, batch, true, fn));
+    if (batch > c->max_batch) return fail(MAV_ERR_ARG, "%s: batch %d outside [1, %d]", fn, batch, c->max_batch);
+    HostCall h(c, fn);
+    CHK(h.beside(batch));
+    const float* df = h.in(flow, sizeof(float) * 2 * batch * c->n0);
+    const double* dm = h.in(M, sizeof(double) * n * batch);
+    float* dd = h.out(diff, sizeof(float) * 2 * batch * c->n0);
+    float* dg = h.out(mag, sizeof(float) * batch * c->n0);
+    mav_warp_record* dr = h.out(records, sizeof(mav_warp_record) * batch);
+    CHK(h.staged());
+    CHK(mav_warp_method_dev(c, df, dm, kind, batch, dd, dg, dr));
+    return h.finish();
+}

@@ -424,3 +424,11 @@ inline size_t km_image_bytes(int n, int A, int K, int D) { return km_state_bytes
 // the whole launch sequence of a call
 void launch_kmeans(hipStream_t st, const KmCall& k);
 void launch_kmeans_paint(hipStream_t st, const int32_t* labels, const float* centers, int n, int B, int K, int D, uint8_t* res, uint8_t* mask);
+
+// ---- image warps (kernels_warp.hip, compiled with -ffp-contract=off; include/mavflow_warp.h) ---------------------------------------------
+// the coordinate policies of the one sampling body
+enum { WARP_POLICY_MAP, WARP_POLICY_PLANES, WARP_POLICY_FLOW, WARP_POLICY_AFFINE, WARP_POLICY_PERSPECTIVE };
+// a, b: the policy's operands (map_xy | map_x, map_y | flow | M); B images of W x H in `format` (MAV_WARP_*), one launch
+void launch_warp(hipStream_t st, int policy, int format, const void* src, const void* a, const void* b, int flags, int W, int H, int B, void* dst);
+// Detector.warp_method: records' initialisation, the pass and the records' final form, three launches; diff and mag may be NULL
+void launch_warp_method(hipStream_t st, int policy, const float* flow, const double* M, int W, int H, int B, float* diff, float* mag, void* records);

@@ -1965,3 +1965,7 @@ from . import _validation  # noqa: E402,F401
 
 # include/mavflow_cluster.h (Context.kmeans, .kmeans_enqueue, .kmeans_workspace_bytes, .kmeans_paint): likewise
 from . import clustering  # noqa: E402,F401
+
+
+# include/mavflow_warp.h (Context.remap, .warp_flow, .warp_affine, .warp_perspective, .warp_method and their *_enqueue twins): likewise
+from . import warp  # noqa: E402,F401

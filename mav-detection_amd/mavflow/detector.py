@@ -402,5 +402,40 @@ class Detector:
         rgb[mask, 1] = 0
         return rgb, mask
 
+    # -- warp method (detector.py:204-240) --------------------------------------------------------------------------------------------
+    def warp_method(self, flow_uv: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """detector.py:204-240, the reference's second way of removing global motion: the field warped by the matrix (.homography for
+        HOMOGRAPHY through warpPerspective, else a user-set .aff through warpAffine), subtracted from the field -- elements whose warped
+        value is 0 count as equal --, the difference's magnitude.  Returns (get_flow_vis(flow_diff), to_rgb(flow_diff_mag)) and sets
+        .flow_diff_mag (and .flow_diff, .flow_diff_max = (row, col) of the largest magnitude, which the reference computes and drops).
+        flow_uv: a host array or the flow seam's device handle, on whose context the call then runs.  A float32 field goes through
+        mav_warp_method; any other dtype takes the reference's arithmetic on the host with mavflow.warp.warpPerspective / warpAffine
+        on a float32 COPY of the field -- which rounds it: the warp is built for float32 alone.  The reference hard-codes
+        dsize = (752, 480), its dataset's frame, and fails at any other size; this warps at the field's own size.  The `blocks`
+        arithmetic of :229-237 is dead code there and is not reproduced."""
+        from . import warp as _warp
+        homography = self.algorithm == Detector.Algorithm.HOMOGRAPHY
+        M = np.asarray(self.homography if homography else self.aff, np.float64)
+        M = M if homography else M[:2, :]
+        dev = self._device_flow(flow_uv)
+        host = None if dev is not None else np.asarray(flow_uv)
+        if dev is None and host.dtype != np.float32:
+            H, W = host.shape[:2]
+            stable = (_warp.warpPerspective if homography else _warp.warpAffine)(host.astype(np.float32), M, (W, H))
+            flow = np.where(stable == 0, stable.astype(host.dtype), host)      # elements whose warped value is 0 count as equal
+            self.flow_diff = flow - stable
+            self.flow_diff_mag = np.sqrt(self.flow_diff[..., 0] ** 2.0 + self.flow_diff[..., 1] ** 2.0)
+            self.flow_diff_max = tuple(int(v) for v in np.unravel_index(self.flow_diff_mag.argmax(), self.flow_diff_mag.shape))
+        else:
+            if dev is not None:
+                ctx = dev[0]
+                out = ctx.warp_method(flow_uv, M)
+            else:
+                ctx = im_helpers._ctx(host.shape[1], host.shape[0])
+                out = ctx.warp_method(host, M)
+            self.flow_diff, self.flow_diff_mag, self.flow_diff_max = out["diff"], out["mag"], out["flow_max"]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return im_helpers.get_flow_vis(self.flow_diff), im_helpers.to_rgb(self.flow_diff_mag)
+
     def is_homography_based(self) -> bool:
         return self.algorithm in [Detector.Algorithm.HOMOGRAPHY]

@@ -122,6 +122,16 @@ class Farneback:
     def _gray(self, img: np.ndarray) -> np.ndarray:
         return self.ctx.bgr2gray(img)[0] if img.ndim == 3 else np.ascontiguousarray(img, np.uint8)
 
+    def warp_flow(self, img: np.ndarray, flow: np.ndarray) -> np.ndarray:
+        """farneback.py:63-69: img (a BGR frame, or any image Context.remap takes) sampled at grid - flow by cv2.remap(INTER_LINEAR) --
+        the motion-compensated frame --, the map generated on the device (mav_warp_flow).  flow (H, W, 2) float32, or anything numpy
+        converts to it; the caller's array is not negated in place.  Runs on this object's context when the frame is its size, else on a
+        cached context of the frame's size."""
+        from . import im_helpers, warp  # noqa: F401
+        h, w = np.shape(flow)[:2]
+        ctx = self.ctx if (w, h) == (self.ctx.W, self.ctx.H) else im_helpers._ctx(w, h)
+        return ctx.warp_flow(img, np.asarray(flow, np.float32))
+
     def process(self) -> np.ndarray:
         _, img = self.capture.read()
         gray = self._gray(img)

@@ -1,0 +1,197 @@
+"""TEST INFRASTRUCTURE -- the case table of the image warps (include/mavflow_warp.h, csrc/kernels_warp.hip): for every frame every
+(coordinate policy x pixel format) instance, and for every policy the inputs it is run on, each with a note of what it is there to reach.
+tests/test_warp_cases_cpu.py holds the table to the instantiations the kernel file names and computes from the restatement
+(tests/warp_ref.py) that every noted feature is reached; tests/test_gpu_warp.py runs the device on every case."""
+from __future__ import annotations
+
+import os
+import re
+from collections import namedtuple
+
+import numpy as np
+
+import warp_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+KERNELS = os.path.join(ROOT, "mav-detection_amd", "csrc", "kernels_warp.hip")
+FRAMES = [(1, 1), (2, 3), (5, 3), (37, 23), (131, 67)]     # (W, H): no multiple of a tile; the last two span more than one workgroup of 256
+B = 3                                                      # max_batch of every context here; calls run at batch 1 and 3
+POLICIES = {"map": "CoordMap", "planes": "CoordPlanes", "flow": "CoordFlow", "affine": "CoordAffine", "perspective": "CoordPerspective"}
+FORMATS = {"U8C1": R.U8C1, "U8C3": R.U8C3, "F32C1": R.F32C1, "F32C2": R.F32C2}
+INSTANCES = [(p, f) for p in POLICIES for f in FORMATS]
+FEATURE_FRAME = 15          # pixels from which a frame has room for what an input is noted for (the smaller frames run the same inputs)
+
+
+def source_forms() -> dict:
+    """what kernels_warp.hip names, read as text: the policies (struct Coord*), the ones dispatched, the formats of the dispatch"""
+    with open(KERNELS) as f:
+        src = f.read()
+    return dict(structs=set(re.findall(r"^struct (Coord\w+)", src, re.M)), dispatched=set(re.findall(r"launch_policy<(Coord\w+)>", src)),
+                formats=set(re.findall(r"k_warp<P, MAV_WARP_(\w+)>", src)), fmt_structs=set(re.findall(r"struct WarpFmt<MAV_WARP_(\w+)>", src)),
+                method=set(re.findall(r"k_warp_method<(Coord\w+)>", src)), text=src)
+
+
+# ---- images --------------------------------------------------------------------------------------------------------------------------------
+def images(fmt: int, W: int, H: int, nan: bool = True) -> np.ndarray:
+    """(B, H, W[, C]): item 0 a 0 / 255 checkerboard (uint8) or noise with one NaN planted mid-frame (float32), items 1.. noise"""
+    dt, ch = R.FORMATS[fmt]
+    rng = np.random.default_rng(1000 * fmt + 7 * W + H)
+    shape = (B,) + R.image_shape(fmt, H, W)
+    if dt == np.uint8:
+        a = rng.integers(0, 256, shape, dtype=np.uint8)
+        board = ((np.arange(H)[:, None] + np.arange(W)[None, :]) % 2 * 255).astype(np.uint8)
+        a[0] = board if ch == 1 else np.repeat(board[..., None], ch, axis=2)
+        return a
+    a = rng.normal(0, 40, shape).astype(np.float32)
+    if nan:
+        a[0].reshape(H, W, ch)[H // 2, W // 2, 0] = np.nan
+    return a
+
+
+def nan_pixel(W: int, H: int) -> tuple:
+    return H // 2, W // 2
+
+
+# ---- maps ----------------------------------------------------------------------------------------------------------------------------------
+def smooth_map(W: int, H: int, k: int = 0) -> np.ndarray:
+    """(H, W, 2) float32: the identity plus a smooth displacement of a few pixels -- most elements inside, the rim partly outside"""
+    y, x = np.mgrid[0:H, 0:W].astype(np.float64)
+    mx = x + 2.3 * np.sin(0.21 * y + 0.4 * k) + 0.37
+    my = y + 1.7 * np.cos(0.17 * x + 0.3 * k) - 0.61
+    return np.stack([mx, my], axis=-1).astype(np.float32)
+
+
+def special_coords(W: int, H: int) -> list:
+    """[(mx, my, note)]: every coordinate the issue lists, on x with a benign y and on y with a benign x"""
+    out = []
+    for axis, n in (("x", W), ("y", H)):
+        other = np.float32(0.25 * ((H if axis == "x" else W) - 1))
+        vals = [(-1.0, "-1"), (-1 / 32, "-1/32"), (0.0, "0"), (n - 1.0, "n-1"), (n - 1 / 32, "n-1/32"), (float(n), "n"),
+                (16 / 32 + 1 / 64, "tie +"), (3 / 32 + 1 / 64, "tie +"), (-16 / 32 + 1 / 64, "tie -"), (-2 / 32 - 1 / 64, "tie -"),
+                (np.nan, "NaN"), (np.inf, "+inf"), (-np.inf, "-inf"), (3e9, "+3e9"), (-3e9, "-3e9"), (40000.0, "past int16"), (-40000.0, "past int16"),
+                (6e7, "past int16")]
+        for v, note in vals:
+            out.append((np.float32(v), other, f"{axis} {note}") if axis == "x" else (other, np.float32(v), f"{axis} {note}"))
+    # the tap right of / below the coordinate is the image's NaN pixel, under a zero weight
+    ny, nx = nan_pixel(W, H)
+    out.append((np.float32(nx - 1), np.float32(ny), "NaN tap under zero weight"))
+    out.append((np.float32(nx), np.float32(ny - 1), "NaN tap under zero weight"))
+    return out
+
+
+def map_fields(W: int, H: int) -> list:
+    """[(name, (H, W, 2) float32 map)]: the smooth map, then as many maps as it takes to place every special coordinate once, each over
+    the smooth map's first pixels in raster order"""
+    sp = special_coords(W, H)
+    n0 = W * H
+    out = [("smooth", smooth_map(W, H))]
+    for k in range(-(-len(sp) // n0)):
+        m = smooth_map(W, H, k + 1).reshape(n0, 2)
+        part = sp[k * n0:(k + 1) * n0]
+        for p, (mx, my, _) in enumerate(part):
+            m[p] = (mx, my)
+        out.append((f"special {k}", m.reshape(H, W, 2)))
+    return out
+
+
+def flow_fields(W: int, H: int) -> list:
+    """the fields whose grid - flow IS the maps above where the float32 subtraction is exact, and noise"""
+    y, x = np.mgrid[0:H, 0:W].astype(np.float32)
+    grid = np.stack([x, y], axis=-1)
+    out = []
+    with np.errstate(all="ignore"):
+        for name, m in map_fields(W, H):
+            out.append((name, (grid - m).astype(np.float32)))
+    out.append(("noise", np.random.default_rng(W * 31 + H).normal(0, 2.5, (H, W, 2)).astype(np.float32)))
+    return out
+
+
+# ---- matrices ------------------------------------------------------------------------------------------------------------------------------
+Matrix = namedtuple("Matrix", "name M note")
+
+
+def affine_matrices(W: int, H: int) -> list:
+    cx, cy = (W - 1) / 2, (H - 1) / 2
+    a, s = np.deg2rad(30.0), 1.1
+    c_, s_ = s * np.cos(a), s * np.sin(a)
+    return [Matrix("identity", [[1, 0, 0], [0, 1, 0]], "exact"),
+            Matrix("shift (1, -1)", [[1, 0, 1], [0, 1, -1]], "exact; integer translation"),
+            Matrix("shift (-2, 1)", [[1, 0, -2], [0, 1, 1]], "exact; integer translation"),
+            Matrix("half pixel", [[1, 0, 0.5], [0, 1, 0.5]], "ax = ay = 16"),
+            Matrix("rotation with scale", [[c_, s_, (1 - c_) * cx - s_ * cy], [-s_, c_, s_ * cx + (1 - c_) * cy]], "general"),
+            Matrix("reflection", [[-1, 0, W - 1], [0, 1, 0]], "negative determinant"),
+            Matrix("scale 2", [[2, 0, 0], [0, 2, 0]], "power of two: exact inverse"),
+            Matrix("zero determinant", [[1, 2, 0], [2, 4, 1]], "D = 0 -> the zero matrix"),
+            Matrix("huge", [[1e7, 0, 3e7], [0, 1e7, -3e7]], "rint(... * 1024) saturates as given"),
+            Matrix("tiny", [[1e-8, 0, 3.0], [0, 1e-8, -3.0]], "rint(... * 1024) saturates once inverted")]
+
+
+def perspective_matrices(W: int, H: int) -> list:
+    out = [Matrix(m.name, [list(m.M[0]), list(m.M[1]), [0, 0, 1]], m.note) for m in affine_matrices(W, H)]
+    out += [Matrix("tilt, W crosses zero", [[1, 0, 0], [0, 1, 0], [1, 0.125, -(W / 2 - 0.3)]], "W changes sign inside the frame"),
+            Matrix("W zero on a pixel", [[1, 0, 0], [0, 1, 0], [1, 0, -(W // 2)]], "W == 0 exactly at x = W // 2 (as given)"),
+            Matrix("mild tilt", [[1.02, 0.01, -0.4], [-0.02, 0.98, 0.3], [1e-3, -2e-3, 1.0]], "general"),
+            Matrix("zero matrix", [[0, 0, 0], [0, 0, 0], [0, 0, 0]], "d = 0; W = 0 everywhere")]
+    return out
+
+
+def matrices(policy: str, W: int, H: int) -> list:
+    return affine_matrices(W, H) if policy == "affine" else perspective_matrices(W, H)
+
+
+def host_refuses(M, flags: int) -> bool:
+    """what the host forms refuse: non-finite elements; where the call inverts, a determinant that is 0 or not finite"""
+    M = np.asarray(M, np.float64)
+    if not np.isfinite(M).all():
+        return True
+    d = R.determinant(M)
+    return not (flags & R.INVERSE_MAP) and (d == 0 or not np.isfinite(d))
+
+
+# ---- the operands of one policy at one frame, as a list of named single-image operands -------------------------------------------------------
+def operands(policy: str, W: int, H: int) -> list:
+    """[(name, operand, flags)]: operand is the map (H, W, 2) | the flow (H, W, 2) | the matrix"""
+    if policy in ("map", "planes"):
+        return [(n, m, 0) for n, m in map_fields(W, H)]
+    if policy == "flow":
+        return [(n, f, 0) for n, f in flow_fields(W, H)]
+    return [(f"{m.name}, flags {fl}", np.array(m.M, np.float64), fl) for m in matrices(policy, W, H) for fl in (0, R.INVERSE_MAP)]
+
+
+def reference(policy: str, img: np.ndarray, op: np.ndarray, flags: int, trace=None) -> np.ndarray:
+    if policy == "map":
+        return R.remap(img, op, trace)
+    if policy == "planes":
+        return R.remap_planes(img, op[..., 0], op[..., 1], trace)
+    if policy == "flow":
+        return R.warp_flow(img, op, trace)
+    if policy == "affine":
+        return R.warp_affine(img, op, flags, trace)
+    return R.warp_perspective(img, op, flags, trace)
+
+
+def groups(items: list, n: int = B) -> list:
+    """the operands in groups of n (one call of batch n each), the last group filled up by repeating its last item"""
+    out = []
+    for i in range(0, len(items), n):
+        g = items[i:i + n]
+        out.append(g + [g[-1]] * (n - len(g)))
+    return out
+
+
+# ---- warp_method's fields --------------------------------------------------------------------------------------------------------------------
+def method_flow(W: int, H: int) -> np.ndarray:
+    """(B, H, W, 2) float32: noise; item 1 with a block of exact zeros (stable == 0 inside the frame) and one large vector; item 2 with
+    its largest magnitude twice (the first position wins)"""
+    f = np.random.default_rng(W + 100 * H).normal(0, 3, (B, H, W, 2)).astype(np.float32)
+    f[1, :max(1, H // 2), :max(1, W // 2)] = 0
+    f[1, H - 1, W - 1] = (300.0, -400.0)
+    f[2, H // 2, W // 3] = (600.0, 800.0)
+    f[2, H - 1, W - 1] = (600.0, 800.0)
+    return f
+
+
+def method_matrices(kind: int, W: int, H: int) -> list:
+    names = ("identity", "shift (1, -1)", "half pixel", "rotation with scale", "reflection", "scale 2")
+    ms = [m for m in (affine_matrices(W, H) if kind == R.AFFINE else perspective_matrices(W, H)) if m.name in names + ("mild tilt",)]
+    return ms
