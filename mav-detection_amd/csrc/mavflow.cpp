@@ -4957,3 +4957,176 @@ extern "C" int mav_warp_method(mav_ctx* c, const float* flow, const double* M, i
     CHK(mav_warp_method_dev(c, df, dm, kind, batch, dd, dg, dr));
     return h.finish();
 }
+
+// ---- robust affine fit (include/mavflow_affine.h) -------------------------------------------------------------------------------------------
+// Like the warps these keep every kind of resident state and hold no device memory of the context's: the _dev forms work in the caller's
+// workspace (the flow form's gathered pairs included), the host forms in staging blocks behind the last call's (HostCall::beside).
+#include "../../include/mavflow_affine.h"
+#include <cfloat>
+
+extern "C" void mav_affine_defaults(mav_affine_params* p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->threshold = 3.0;
+    p->confidence = 0.99;
+    p->max_iters = 2000;
+    p->refine = 1;
+}
+static int affine_params_checked(int n, const mav_affine_params* p, const char* fn)
+{
+    if (!p) return fail(MAV_ERR_ARG, "%s: NULL params", fn);
+    if (n < 3 || n > MAV_AFFINE_MAX_PAIRS) return fail(MAV_ERR_ARG, "%s: n %d outside [3, %d]", fn, n, MAV_AFFINE_MAX_PAIRS);
+    if (p->max_iters < 1 || p->max_iters > MAV_AFFINE_MAX_ITERS) return fail(MAV_ERR_ARG, "%s: max_iters %d outside [1, %d]", fn, p->max_iters, MAV_AFFINE_MAX_ITERS);
+    if (!std::isfinite(p->threshold) || p->threshold < 0.0) return fail(MAV_ERR_ARG, "%s: threshold %g is negative or not finite", fn, p->threshold);
+    if (!(p->confidence > 0.0 && p->confidence < 1.0)) return fail(MAV_ERR_ARG, "%s: confidence %g outside (0, 1)", fn, p->confidence);
+    if (p->flags != 0) return fail(MAV_ERR_ARG, "%s: flags 0x%x: no flag is defined", fn, p->flags);
+    return MAV_OK;
+}
+extern "C" size_t mav_estimate_affine_workspace_bytes(int n, int batch, const mav_affine_params* p)
+{
+    if (batch < 1) { fail(MAV_ERR_ARG, "mav_estimate_affine_workspace_bytes: batch %d is less than 1", batch); return 0; }
+    if (affine_params_checked(n, p, "mav_estimate_affine_workspace_bytes") != MAV_OK) return 0;
+    return aff_workspace_bytes(n, batch, p->max_iters);
+}
+// need[g], g = 0 .. n: RANSACUpdateNumIters(confidence, (n - g) / n, 3, max_iters) as the header writes it out
+static void affine_need_table(int n, double confidence, int max_iters, int32_t* need)
+{
+    const double ln = log(1.0 - confidence);
+    for (int g = 0; g <= n; g++) {
+        if (g < 3) { need[g] = max_iters; continue; }
+        const double w = (double)g / (double)n;
+        const double den = 1.0 - (w * w) * w;
+        if (den < DBL_MIN) { need[g] = 0; continue; }
+        const double ld = log(den);
+        need[g] = ld >= 0.0 || -ln >= max_iters * (-ld) ? max_iters : (int32_t)nearbyint(ln / ld);
+    }
+}
+// Everything a call can be refused for from its arguments alone, before the context is looked at.  a, b: src and dst, or flow and coords.
+static int affine_checked(mav_ctx* c, const void* a, const char* a_name, const void* b, const char* b_name, int n, int batch, const mav_affine_params* p,
+                          const int32_t* triples, const double* M, const uint8_t* inliers, const mav_affine_record* records, const char* fn)
+{
+    if (!c) return fail(MAV_ERR_ARG, "%s: NULL context", fn);
+    if (!a) return fail(MAV_ERR_ARG, "%s: NULL %s", fn, a_name);
+    if (!b) return fail(MAV_ERR_ARG, "%s: NULL %s", fn, b_name);
+    if (!triples) return fail(MAV_ERR_ARG, "%s: NULL triples", fn);
+    if (!M) return fail(MAV_ERR_ARG, "%s: NULL M", fn);
+    if (!inliers) return fail(MAV_ERR_ARG, "%s: NULL inliers", fn);
+    if (!records) return fail(MAV_ERR_ARG, "%s: NULL records", fn);
+    if (batch < 1) return fail(MAV_ERR_ARG, "%s: batch %d is less than 1", fn, batch);
+    return affine_params_checked(n, p, fn);
+}
+// what the _dev forms refuse beyond that: a's alignment is `a_align`, b's is checked where b is a device pointer (b_align != 0)
+static int affine_dev_checked(const void* a, const char* a_name, size_t a_align, const void* b, const char* b_name, size_t b_align, int n, int batch,
+                              const mav_affine_params* p, const int32_t* triples, const double* M, const mav_affine_record* records, const void* workspace,
+                              size_t workspace_bytes, const char* fn)
+{
+    if (!workspace) return fail(MAV_ERR_ARG, "%s: NULL workspace", fn);
+    if ((uintptr_t)a % a_align) return fail(MAV_ERR_ARG, "%s: %s is not aligned to %zu bytes", fn, a_name, a_align);
+    if (b_align && (uintptr_t)b % b_align) return fail(MAV_ERR_ARG, "%s: %s is not aligned to %zu bytes", fn, b_name, b_align);
+    if ((uintptr_t)triples % 4) return fail(MAV_ERR_ARG, "%s: triples is not aligned to its 4-byte elements", fn);
+    if ((uintptr_t)M % 8) return fail(MAV_ERR_ARG, "%s: M is not aligned to its 8-byte elements", fn);
+    if ((uintptr_t)records % 16) return fail(MAV_ERR_ARG, "%s: records is not aligned to 16 bytes", fn);
+    if ((uintptr_t)workspace % 16) return fail(MAV_ERR_ARG, "%s: workspace is not aligned to 16 bytes", fn);
+    const size_t need = aff_workspace_bytes(n, batch, p->max_iters);
+    if (workspace_bytes < need) return fail(MAV_ERR_ARG, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, need);
+    return MAV_OK;
+}
+// the host forms' triples: every index inside [0, n), no index twice
+static int affine_triples_checked(const int32_t* t, int n, int batch, int max_iters, const char* fn)
+{
+    for (size_t i = 0; i < (size_t)batch * max_iters; i++) {
+        const int32_t *q = t + 3 * i;
+        for (int j = 0; j < 3; j++)
+            if (q[j] < 0 || q[j] >= n) return fail(MAV_ERR_ARG, "%s: triples[%zu][%d] = %d outside [0, %d)", fn, i, j, q[j], n);
+        if (q[0] == q[1] || q[0] == q[2] || q[1] == q[2]) return fail(MAV_ERR_ARG, "%s: triples[%zu] = (%d, %d, %d) repeats an index", fn, i, q[0], q[1], q[2]);
+    }
+    return MAV_OK;
+}
+static int affine_coords_checked(const mav_ctx* c, const int32_t* coords, int n, const char* fn)
+{
+    for (int i = 0; i < n; i++)
+        if (coords[2 * i] < 0 || coords[2 * i] >= c->W || coords[2 * i + 1] < 0 || coords[2 * i + 1] >= c->H)
+            return fail(MAV_ERR_ARG, "%s: sample %d = (%d, %d) lies outside the %dx%d frame", fn, i, coords[2 * i], coords[2 * i + 1], c->W, c->H);
+    return MAV_OK;
+}
+// the table's copy and the three launches
+static int affine_enqueue(mav_ctx* c, const double* src, const double* dst, int n, int batch, const mav_affine_params* p, const int32_t* triples, double* M,
+                          uint8_t* inliers, mav_affine_record* records, void* workspace)
+{
+    std::vector<int32_t> need((size_t)n + 1);             // this call's own block: the copy below has taken its bytes when it returns
+    affine_need_table(n, p->confidence, p->max_iters, need.data());
+    HIPCHK(hipMemcpyAsync(workspace, need.data(), sizeof(int32_t) * need.size(), hipMemcpyHostToDevice, c->stream));
+    AffCall a;
+    a.src = src; a.dst = dst; a.triples = triples; a.M = M; a.inliers = inliers; a.records = records; a.ws = (char*)workspace;
+    a.n = n; a.B = batch; a.max_iters = p->max_iters; a.refine = p->refine != 0; a.t2 = p->threshold * p->threshold;
+    { ProfScope ps(c, K_MISC); launch_affine_score(c->stream, a); }
+    { ProfScope ps(c, K_MISC); launch_affine_choose(c->stream, a); }
+    { ProfScope ps(c, K_MISC); launch_affine_finish(c->stream, a); }
+    return check_launch("affine fit");
+}
+extern "C" int mav_estimate_affine_dev(mav_ctx* c, const double* src, const double* dst, int n, int batch, const mav_affine_params* p, const int32_t* triples,
+                                       double* M, uint8_t* inliers, mav_affine_record* records, void* workspace, size_t workspace_bytes)
+{
+    const char* fn = "mav_estimate_affine_dev";
+    CHK(affine_checked(c, src, "src", dst, "dst", n, batch, p, triples, M, inliers, records, fn));
+    CHK(affine_dev_checked(src, "src", 8, dst, "dst", 8, n, batch, p, triples, M, records, workspace, workspace_bytes, fn));
+    CHK(check_dev_call(c, batch, fn));
+    return affine_enqueue(c, src, dst, n, batch, p, triples, M, inliers, records, workspace);
+}
+extern "C" int mav_estimate_affine(mav_ctx* c, const double* src, const double* dst, int n, int batch, const mav_affine_params* p, const int32_t* triples,
+                                   double* M, uint8_t* inliers, mav_affine_record* records)
+{
+    const char* fn = "mav_estimate_affine";
+    CHK(affine_checked(c, src, "src", dst, "dst", n, batch, p, triples, M, inliers, records, fn));
+    CHK(affine_triples_checked(triples, n, batch, p->max_iters, fn));
+    HostCall h(c, fn);
+    CHK(h.beside(batch));
+    const size_t pairs = sizeof(double) * 2 * (size_t)n * batch, wsb = aff_workspace_bytes(n, batch, p->max_iters);
+    const double *ds = h.in(src, pairs), *dd = h.in(dst, pairs);
+    const int32_t* dt = h.in(triples, sizeof(int32_t) * 3 * (size_t)batch * p->max_iters);
+    char* dw = h.scratch<char>(wsb);
+    double* dM = h.out(M, sizeof(double) * 6 * batch);
+    uint8_t* di = h.out(inliers, (size_t)batch * n);
+    mav_affine_record* dr = h.out(records, sizeof(mav_affine_record) * batch);
+    CHK(h.staged());
+    CHK(mav_estimate_affine_dev(c, ds, dd, n, batch, p, dt, dM, di, dr, dw, wsb));
+    return h.finish();
+}
+extern "C" int mav_flow_affine_dev(mav_ctx* c, const float* flow, const int32_t* coords, int n, int batch, const mav_affine_params* p, const int32_t* triples,
+                                   double* M, uint8_t* inliers, mav_affine_record* records, void* workspace, size_t workspace_bytes)
+{
+    const char* fn = "mav_flow_affine_dev";
+    CHK(affine_checked(c, flow, "flow", coords, "coords", n, batch, p, triples, M, inliers, records, fn));
+    CHK(affine_dev_checked(flow, "flow", 8, coords, "coords", 0, n, batch, p, triples, M, records, workspace, workspace_bytes, fn));
+    CHK(check_dev_call(c, batch, fn));
+    CHK(affine_coords_checked(c, coords, n, fn));
+    char* ws = (char*)workspace;
+    int32_t* dcoords = (int32_t*)(ws + aff_coords_offset(n, batch, p->max_iters));
+    double *ps = (double*)(ws + aff_src_offset(n, batch, p->max_iters)), *pd = (double*)(ws + aff_dst_offset(n, batch, p->max_iters));
+    HIPCHK(hipMemcpyAsync(dcoords, coords, sizeof(int32_t) * 2 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    { ProfScope ps_(c, K_MISC); launch_pair_gather(c->stream, flow, dcoords, n, batch, c->W, c->H, ps, pd); }
+    CHK(check_launch("pair_gather"));
+    return affine_enqueue(c, ps, pd, n, batch, p, triples, M, inliers, records, workspace);
+}
+extern "C" int mav_flow_affine(mav_ctx* c, const float* flow, const int32_t* coords, int n, int batch, const mav_affine_params* p, const int32_t* triples,
+                               double* M, uint8_t* inliers, mav_affine_record* records, double* pairs_dst)
+{
+    const char* fn = "mav_flow_affine";
+    CHK(affine_checked(c, flow, "flow", coords, "coords", n, batch, p, triples, M, inliers, records, fn));
+    CHK(affine_triples_checked(triples, n, batch, p->max_iters, fn));
+    HostCall h(c, fn);
+    CHK(h.beside(batch));
+    CHK(affine_coords_checked(c, coords, n, fn));
+    const size_t wsb = aff_workspace_bytes(n, batch, p->max_iters);
+    const float* df = h.in(flow, c->n0 * batch * 2 * sizeof(float));
+    const int32_t* dt = h.in(triples, sizeof(int32_t) * 3 * (size_t)batch * p->max_iters);
+    char* dw = h.scratch<char>(wsb);
+    double* dM = h.out(M, sizeof(double) * 6 * batch);
+    uint8_t* di = h.out(inliers, (size_t)batch * n);
+    mav_affine_record* dr = h.out(records, sizeof(mav_affine_record) * batch);
+    if (dw) h.fetch(pairs_dst, dw + aff_dst_offset(n, batch, p->max_iters), sizeof(double) * 2 * (size_t)n * batch);
+    CHK(h.staged());
+    CHK(mav_flow_affine_dev(c, df, coords, n, batch, p, dt, dM, di, dr, dw, wsb));
+    return h.finish();
+}

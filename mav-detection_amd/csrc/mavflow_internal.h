@@ -432,3 +432,23 @@ enum { WARP_POLICY_MAP, WARP_POLICY_PLANES, WARP_POLICY_FLOW, WARP_POLICY_AFFINE
 void launch_warp(hipStream_t st, int policy, int format, const void* src, const void* a, const void* b, int flags, int W, int H, int B, void* dst);
 // Detector.warp_method: records' initialisation, the pass and the records' final form, three launches; diff and mag may be NULL
 void launch_warp_method(hipStream_t st, int policy, const float* flow, const double* M, int W, int H, int B, float* diff, float* mag, void* records);
+
+// ---- robust affine fit (kernels_affine.hip, compiled with -ffp-contract=off; include/mavflow_affine.h) ------------------------------------
+// What one call works on, all device pointers.  The workspace layout follows from (n, B, max_iters) alone: need[] (n + 1 int32, filled by
+// the host's copy), the counts (B, max_iters) int32 (-1: an invalid hypothesis), the choice (B, 4) int32, then the flow form's coords
+// (n, 2) int32 and its gathered pairs, src and dst (B, n, 2) float64 each.
+struct AffCall {
+    const double *src, *dst; const int32_t* triples; double* M; uint8_t* inliers; void* records; char* ws;
+    int n, B, max_iters, refine; double t2;
+};
+__host__ __device__ inline size_t aff_round(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+__host__ __device__ inline size_t aff_counts_offset(int n) { return aff_round(sizeof(int32_t) * ((size_t)n + 1)); }
+__host__ __device__ inline size_t aff_choice_offset(int n, int B, int max_iters) { return aff_counts_offset(n) + aff_round(sizeof(int32_t) * (size_t)B * max_iters); }
+__host__ __device__ inline size_t aff_coords_offset(int n, int B, int max_iters) { return aff_choice_offset(n, B, max_iters) + aff_round(sizeof(int32_t) * 4 * (size_t)B); }
+__host__ __device__ inline size_t aff_src_offset(int n, int B, int max_iters) { return aff_coords_offset(n, B, max_iters) + aff_round(sizeof(int32_t) * 2 * (size_t)n); }
+__host__ __device__ inline size_t aff_dst_offset(int n, int B, int max_iters) { return aff_src_offset(n, B, max_iters) + aff_round(sizeof(double) * 2 * (size_t)n * B); }
+__host__ __device__ inline size_t aff_workspace_bytes(int n, int B, int max_iters) { return aff_dst_offset(n, B, max_iters) + aff_round(sizeof(double) * 2 * (size_t)n * B); }
+// the three launches of a call, in this order on one stream
+void launch_affine_score(hipStream_t st, const AffCall& a);
+void launch_affine_choose(hipStream_t st, const AffCall& a);
+void launch_affine_finish(hipStream_t st, const AffCall& a);

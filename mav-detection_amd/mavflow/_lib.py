@@ -1969,3 +1969,7 @@ from . import clustering  # noqa: E402,F401
 
 # include/mavflow_warp.h (Context.remap, .warp_flow, .warp_affine, .warp_perspective, .warp_method and their *_enqueue twins): likewise
 from . import warp  # noqa: E402,F401
+
+
+# include/mavflow_affine.h (Context.estimate_affine, .flow_affine, their *_enqueue twins and .estimate_affine_workspace_bytes): likewise
+from . import affine  # noqa: E402,F401

@@ -1,7 +1,8 @@
 """Detector -- the Algorithm switch, IMU derotation, the window search (analyze_pyramid, optimize_window) and the global-motion
 branch (get_transformation_matrix for HOMOGRAPHY, flow_vec_subtract) of the reference's Detector (src/detector.py:14-202,280-358,
-430-433) on libmavflow.  The affine / fundamental / essential-matrix estimators (cv2 RANSAC with a private RNG, unreachable from
-run_detection) are not reproduced: get_transformation_matrix says so; flow_vec_subtract takes a user-set .aff as the reference does."""
+430-433) on libmavflow.  The fundamental / essential-matrix estimators (cv2 RANSAC with a private RNG, unreachable from
+run_detection) are not reproduced: get_transformation_matrix says so.  The affine estimator runs with the caller's generator in
+.affine_rng (an extra; None: refused as before); flow_vec_subtract takes .aff, user-set as in the reference or set by that fit."""
 from __future__ import annotations
 
 from enum import Enum
@@ -110,6 +111,9 @@ class Detector:
         # clustering (detector.py:396-428): off in flow_vec_subtract, as the reference's commented-out line leaves it
         self.use_clustering = False
         self.cluster_rng = None          # the generator of clustering's initial centres (None: np.random)
+        # an extra: the generator of the AFFINE fit's sample triples (a seed, a Generator or np.random).  None: get_transformation_matrix
+        # refuses AFFINE as before
+        self.affine_rng = None
         self.mag_handle = self.gray_handle = None    # flow_uv_warped_mag / one channel of to_rgb(magnitude) on the device, after a flow_vec_subtract of a device flow
 
     def get_gradient_and_magnitude(self, frame: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
@@ -226,12 +230,17 @@ class Detector:
         """The homography of detector.py:119-139: 1000 sampled pairs coords -> coords + flow[y, x] (or, with use_sparse_of, the
         Lucas-Kanade tracks of orig_frame when there are any), fitted on the device in the structure of cv2.findHomography's method 0
         (Context.find_homography: not pinned against cv2).  Sets .homography (3x3 float64) and .confidence (the all-ones inlier mask,
-        (n, 1) uint8); RuntimeError when the pairs determine no homography.  flow_uv: a host array or the flow seam's device handle."""
+        (n, 1) uint8); RuntimeError when the pairs determine no homography.  flow_uv: a host array or the flow seam's device handle.
+        AFFINE with .affine_rng set: _affine_matrix (sets .aff and .aff_inliers); with .affine_rng None it raises, as FUNDAMENTAL and
+        ESSENTIAL do."""
         A = Detector.Algorithm
-        if self.algorithm in (A.AFFINE, A.FUNDAMENTAL, A.ESSENTIAL):
+        affine = self.algorithm == A.AFFINE and self.affine_rng is not None
+        if self.algorithm in (A.AFFINE, A.FUNDAMENTAL, A.ESSENTIAL) and not affine:
             raise NotImplementedError(
                 f"{self.algorithm.name}: cv2.estimateAffine2D / findFundamentalMat / findEssentialMat are RANSAC estimators driven by "
                 "OpenCV's private RNG; they are not reproduced (run_detection reaches HOMOGRAPHY only)")
+        if affine:
+            return self._affine_matrix(orig_frame, flow_uv)
         if self.algorithm != A.HOMOGRAPHY:
             return
         W, H = self.dataset.capture_size[0], self.dataset.capture_size[1]
@@ -266,6 +275,34 @@ class Detector:
             raise RuntimeError("get_transformation_matrix: the point pairs do not determine a homography")
         self.homography = np.array(Hm[0])
         self.confidence = np.ones((n, 1), np.uint8)
+
+    def _affine_matrix(self, orig_frame: np.ndarray, flow_uv: np.ndarray) -> None:
+        """detector.py:141-143 with .affine_rng set (an extra): cv2.estimateAffine2D(coords_old, coords_new)'s RANSAC fit on the device
+        (include/mavflow_affine.h: not pinned against cv2), the sample triples drawn from .affine_rng by affine.sample_triples, on the
+        same three pair sources as HOMOGRAPHY.  Sets .aff (2x3 float64) and .aff_inliers ((n, 1) uint8); RuntimeError when no valid
+        hypothesis had more than two inliers."""
+        W, H = self.dataset.capture_size[0], self.dataset.capture_size[1]
+        pairs = None
+        if self.use_sparse_of:
+            old, new, _ = self.lucas_kanade.get_features(orig_frame)
+            if len(old) > 0 and len(new) > 0:
+                pairs = (np.asarray(old, np.float64), np.asarray(new, np.float64))
+        dev = None if pairs is not None else self._device_flow(flow_uv)
+        if pairs is not None:
+            out = im_helpers._ctx(W, H).estimate_affine(*pairs, rng=self.affine_rng)
+        elif dev is not None:
+            out = dev[0].flow_affine(flow_uv, self.coords, rng=self.affine_rng)           # the field is read where it is
+        else:
+            flow = np.asarray(flow_uv)
+            if flow.dtype == np.float32:
+                out = im_helpers._ctx(W, H).flow_affine(flow, self.coords, rng=self.affine_rng)
+            else:                                       # a float64 field keeps its precision: the reference's own pair arithmetic
+                new = self.coords.astype(np.float64) + flow[self.sample_y, self.sample_x]
+                out = im_helpers._ctx(W, H).estimate_affine(self.coords.astype(np.float64), new, rng=self.affine_rng)
+        if not out["ok"]:
+            raise RuntimeError("get_transformation_matrix: the point pairs do not determine an affine map")
+        self.aff = np.array(out["M"])
+        self.aff_inliers = np.array(out["inliers"]).reshape(-1, 1)
 
     def flow_vec_subtract(self, orig_frame: np.ndarray, flow_uv: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         """detector.py:153-202: the motion the matrix predicts (.homography for HOMOGRAPHY, else a user-set .aff) is subtracted from
