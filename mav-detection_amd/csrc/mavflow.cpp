@@ -5130,3 +5130,218 @@ extern "C" int mav_flow_affine(mav_ctx* c, const float* flow, const int32_t* coo
     CHK(mav_flow_affine_dev(c, df, coords, n, batch, p, dt, dM, di, dr, dw, wsb));
     return h.finish();
 }
+
+// ---- robust fundamental-matrix fit and dense epipolar residual (include/mavflow_fundamental.h) ---------------------------------------------
+// As the affine fit: every kind of resident state is kept, no device memory of the context's is held; the _dev forms work in the caller's
+// workspace (the flow form's gathered pairs included), the host forms in staging blocks behind the last call's (HostCall::beside).
+#include "../../include/mavflow_fundamental.h"
+
+extern "C" void mav_fundamental_defaults(mav_fundamental_params* p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->threshold = 3.0;
+    p->confidence = 0.99;
+    p->max_iters = 1000;
+}
+static int fundamental_params_checked(int n, const mav_fundamental_params* p, const char* fn)
+{
+    if (!p) return fail(MAV_ERR_ARG, "%s: NULL params", fn);
+    if (n < 7 || n > MAV_FUNDAMENTAL_MAX_PAIRS) return fail(MAV_ERR_ARG, "%s: n %d outside [7, %d]", fn, n, MAV_FUNDAMENTAL_MAX_PAIRS);
+    if (p->max_iters < 1 || p->max_iters > MAV_FUNDAMENTAL_MAX_ITERS)
+        return fail(MAV_ERR_ARG, "%s: max_iters %d outside [1, %d]", fn, p->max_iters, MAV_FUNDAMENTAL_MAX_ITERS);
+    if (!std::isfinite(p->threshold) || p->threshold < 0.0) return fail(MAV_ERR_ARG, "%s: threshold %g is negative or not finite", fn, p->threshold);
+    if (!(p->confidence > 0.0 && p->confidence < 1.0)) return fail(MAV_ERR_ARG, "%s: confidence %g outside (0, 1)", fn, p->confidence);
+    if (p->flags != 0) return fail(MAV_ERR_ARG, "%s: flags 0x%x: no flag is defined", fn, p->flags);
+    return MAV_OK;
+}
+extern "C" size_t mav_find_fundamental_workspace_bytes(int n, int batch, const mav_fundamental_params* p)
+{
+    if (batch < 1) { fail(MAV_ERR_ARG, "mav_find_fundamental_workspace_bytes: batch %d is less than 1", batch); return 0; }
+    if (fundamental_params_checked(n, p, "mav_find_fundamental_workspace_bytes") != MAV_OK) return 0;
+    return fm_workspace_bytes(n, batch, p->max_iters);
+}
+// need[g], g = 0 .. n: RANSACUpdateNumIters(confidence, (n - g) / n, 7, max_iters) as the header writes it out
+static void fundamental_need_table(int n, double confidence, int max_iters, int32_t* need)
+{
+    const double ln = log(1.0 - confidence);
+    for (int g = 0; g <= n; g++) {
+        if (g < 7) { need[g] = max_iters; continue; }
+        const double w = (double)g / (double)n;
+        const double w2 = w * w;
+        const double w4 = w2 * w2;
+        const double den = 1.0 - (w4 * w2) * w;
+        if (den < DBL_MIN) { need[g] = 0; continue; }
+        const double ld = log(den);
+        need[g] = ld >= 0.0 || -ln >= max_iters * (-ld) ? max_iters : (int32_t)nearbyint(ln / ld);
+    }
+}
+// Everything a call can be refused for from its arguments alone, before the context is looked at.  a, b: src and dst, or flow and coords.
+static int fundamental_checked(mav_ctx* c, const void* a, const char* a_name, const void* b, const char* b_name, int n, int batch,
+                               const mav_fundamental_params* p, const int32_t* subsets, const double* F, const uint8_t* inliers,
+                               const mav_fundamental_record* records, const char* fn)
+{
+    if (!c) return fail(MAV_ERR_ARG, "%s: NULL context", fn);
+    if (!a) return fail(MAV_ERR_ARG, "%s: NULL %s", fn, a_name);
+    if (!b) return fail(MAV_ERR_ARG, "%s: NULL %s", fn, b_name);
+    if (!subsets) return fail(MAV_ERR_ARG, "%s: NULL subsets", fn);
+    if (!F) return fail(MAV_ERR_ARG, "%s: NULL F", fn);
+    if (!inliers) return fail(MAV_ERR_ARG, "%s: NULL inliers", fn);
+    if (!records) return fail(MAV_ERR_ARG, "%s: NULL records", fn);
+    if (batch < 1) return fail(MAV_ERR_ARG, "%s: batch %d is less than 1", fn, batch);
+    return fundamental_params_checked(n, p, fn);
+}
+// what the _dev forms refuse beyond that: a's alignment is `a_align`, b's is checked where b is a device pointer (b_align != 0)
+static int fundamental_dev_checked(const void* a, const char* a_name, size_t a_align, const void* b, const char* b_name, size_t b_align, int n, int batch,
+                                   const mav_fundamental_params* p, const int32_t* subsets, const double* F, const mav_fundamental_record* records,
+                                   const void* workspace, size_t workspace_bytes, const char* fn)
+{
+    if (!workspace) return fail(MAV_ERR_ARG, "%s: NULL workspace", fn);
+    if ((uintptr_t)a % a_align) return fail(MAV_ERR_ARG, "%s: %s is not aligned to %zu bytes", fn, a_name, a_align);
+    if (b_align && (uintptr_t)b % b_align) return fail(MAV_ERR_ARG, "%s: %s is not aligned to %zu bytes", fn, b_name, b_align);
+    if ((uintptr_t)subsets % 4) return fail(MAV_ERR_ARG, "%s: subsets is not aligned to its 4-byte elements", fn);
+    if ((uintptr_t)F % 8) return fail(MAV_ERR_ARG, "%s: F is not aligned to its 8-byte elements", fn);
+    if ((uintptr_t)records % 16) return fail(MAV_ERR_ARG, "%s: records is not aligned to 16 bytes", fn);
+    if ((uintptr_t)workspace % 16) return fail(MAV_ERR_ARG, "%s: workspace is not aligned to 16 bytes", fn);
+    const size_t need = fm_workspace_bytes(n, batch, p->max_iters);
+    if (workspace_bytes < need) return fail(MAV_ERR_ARG, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, need);
+    return MAV_OK;
+}
+// the host forms' subsets: every index inside [0, n), no index twice
+static int fundamental_subsets_checked(const int32_t* t, int n, int batch, int max_iters, const char* fn)
+{
+    for (size_t i = 0; i < (size_t)batch * max_iters; i++) {
+        const int32_t* q = t + 7 * i;
+        for (int j = 0; j < 7; j++) {
+            if (q[j] < 0 || q[j] >= n) return fail(MAV_ERR_ARG, "%s: subsets[%zu][%d] = %d outside [0, %d)", fn, i, j, q[j], n);
+            for (int k = 0; k < j; k++)
+                if (q[k] == q[j]) return fail(MAV_ERR_ARG, "%s: subsets[%zu] repeats the index %d", fn, i, q[j]);
+        }
+    }
+    return MAV_OK;
+}
+// the table's copy and the four launches
+static int fundamental_enqueue(mav_ctx* c, const double* src, const double* dst, int n, int batch, const mav_fundamental_params* p, const int32_t* subsets,
+                               double* F, uint8_t* inliers, mav_fundamental_record* records, void* workspace)
+{
+    std::vector<int32_t> need((size_t)n + 1);             // this call's own block: the copy below has taken its bytes when it returns
+    fundamental_need_table(n, p->confidence, p->max_iters, need.data());
+    HIPCHK(hipMemcpyAsync(workspace, need.data(), sizeof(int32_t) * need.size(), hipMemcpyHostToDevice, c->stream));
+    FmCall a;
+    a.src = src; a.dst = dst; a.subsets = subsets; a.F = F; a.inliers = inliers; a.records = records; a.ws = (char*)workspace;
+    a.n = n; a.B = batch; a.max_iters = p->max_iters; a.t2 = p->threshold * p->threshold;
+    { ProfScope ps(c, K_MISC); launch_fm_models(c->stream, a); }
+    { ProfScope ps(c, K_MISC); launch_fm_score(c->stream, a); }
+    { ProfScope ps(c, K_MISC); launch_fm_choose(c->stream, a); }
+    { ProfScope ps(c, K_MISC); launch_fm_finish(c->stream, a); }
+    return check_launch("fundamental fit");
+}
+extern "C" int mav_find_fundamental_dev(mav_ctx* c, const double* src, const double* dst, int n, int batch, const mav_fundamental_params* p,
+                                        const int32_t* subsets, double* F, uint8_t* inliers, mav_fundamental_record* records, void* workspace,
+                                        size_t workspace_bytes)
+{
+    const char* fn = "mav_find_fundamental_dev";
+    CHK(fundamental_checked(c, src, "src", dst, "dst", n, batch, p, subsets, F, inliers, records, fn));
+    CHK(fundamental_dev_checked(src, "src", 8, dst, "dst", 8, n, batch, p, subsets, F, records, workspace, workspace_bytes, fn));
+    CHK(check_dev_call(c, batch, fn));
+    return fundamental_enqueue(c, src, dst, n, batch, p, subsets, F, inliers, records, workspace);
+}
+extern "C" int mav_find_fundamental(mav_ctx* c, const double* src, const double* dst, int n, int batch, const mav_fundamental_params* p,
+                                    const int32_t* subsets, double* F, uint8_t* inliers, mav_fundamental_record* records)
+{
+    const char* fn = "mav_find_fundamental";
+    CHK(fundamental_checked(c, src, "src", dst, "dst", n, batch, p, subsets, F, inliers, records, fn));
+    CHK(fundamental_subsets_checked(subsets, n, batch, p->max_iters, fn));
+    HostCall h(c, fn);
+    CHK(h.beside(batch));
+    const size_t pairs = sizeof(double) * 2 * (size_t)n * batch, wsb = fm_workspace_bytes(n, batch, p->max_iters);
+    const double *ds = h.in(src, pairs), *dd = h.in(dst, pairs);
+    const int32_t* dt = h.in(subsets, sizeof(int32_t) * 7 * (size_t)batch * p->max_iters);
+    char* dw = h.scratch<char>(wsb);
+    double* dF = h.out(F, sizeof(double) * 9 * batch);
+    uint8_t* di = h.out(inliers, (size_t)batch * n);
+    mav_fundamental_record* dr = h.out(records, sizeof(mav_fundamental_record) * batch);
+    CHK(h.staged());
+    CHK(mav_find_fundamental_dev(c, ds, dd, n, batch, p, dt, dF, di, dr, dw, wsb));
+    return h.finish();
+}
+extern "C" int mav_flow_fundamental_dev(mav_ctx* c, const float* flow, const int32_t* coords, int n, int batch, const mav_fundamental_params* p,
+                                        const int32_t* subsets, double* F, uint8_t* inliers, mav_fundamental_record* records, void* workspace,
+                                        size_t workspace_bytes)
+{
+    const char* fn = "mav_flow_fundamental_dev";
+    CHK(fundamental_checked(c, flow, "flow", coords, "coords", n, batch, p, subsets, F, inliers, records, fn));
+    CHK(fundamental_dev_checked(flow, "flow", 8, coords, "coords", 0, n, batch, p, subsets, F, records, workspace, workspace_bytes, fn));
+    CHK(check_dev_call(c, batch, fn));
+    CHK(affine_coords_checked(c, coords, n, fn));         // the affine flow form's range check of the host coords
+    char* ws = (char*)workspace;
+    int32_t* dcoords = (int32_t*)(ws + fm_coords_offset(n, batch, p->max_iters));
+    double *ps = (double*)(ws + fm_src_offset(n, batch, p->max_iters)), *pd = (double*)(ws + fm_dst_offset(n, batch, p->max_iters));
+    HIPCHK(hipMemcpyAsync(dcoords, coords, sizeof(int32_t) * 2 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    { ProfScope ps_(c, K_MISC); launch_pair_gather(c->stream, flow, dcoords, n, batch, c->W, c->H, ps, pd); }
+    CHK(check_launch("pair_gather"));
+    return fundamental_enqueue(c, ps, pd, n, batch, p, subsets, F, inliers, records, workspace);
+}
+extern "C" int mav_flow_fundamental(mav_ctx* c, const float* flow, const int32_t* coords, int n, int batch, const mav_fundamental_params* p,
+                                    const int32_t* subsets, double* F, uint8_t* inliers, mav_fundamental_record* records, double* pairs_dst)
+{
+    const char* fn = "mav_flow_fundamental";
+    CHK(fundamental_checked(c, flow, "flow", coords, "coords", n, batch, p, subsets, F, inliers, records, fn));
+    CHK(fundamental_subsets_checked(subsets, n, batch, p->max_iters, fn));
+    HostCall h(c, fn);
+    CHK(h.beside(batch));
+    CHK(affine_coords_checked(c, coords, n, fn));
+    const size_t wsb = fm_workspace_bytes(n, batch, p->max_iters);
+    const float* df = h.in(flow, c->n0 * batch * 2 * sizeof(float));
+    const int32_t* dt = h.in(subsets, sizeof(int32_t) * 7 * (size_t)batch * p->max_iters);
+    char* dw = h.scratch<char>(wsb);
+    double* dF = h.out(F, sizeof(double) * 9 * batch);
+    uint8_t* di = h.out(inliers, (size_t)batch * n);
+    mav_fundamental_record* dr = h.out(records, sizeof(mav_fundamental_record) * batch);
+    if (dw) h.fetch(pairs_dst, dw + fm_dst_offset(n, batch, p->max_iters), sizeof(double) * 2 * (size_t)n * batch);
+    CHK(h.staged());
+    CHK(mav_flow_fundamental_dev(c, df, coords, n, batch, p, dt, dF, di, dr, dw, wsb));
+    return h.finish();
+}
+static int epipolar_checked(mav_ctx* c, const float* flow, const double* F, double threshold, int batch, const mav_epipolar_record* records, const char* fn)
+{
+    if (!c) return fail(MAV_ERR_ARG, "%s: NULL context", fn);
+    if (!flow) return fail(MAV_ERR_ARG, "%s: NULL flow", fn);
+    if (!F) return fail(MAV_ERR_ARG, "%s: NULL F", fn);
+    if (!records) return fail(MAV_ERR_ARG, "%s: NULL records", fn);
+    if (batch < 1) return fail(MAV_ERR_ARG, "%s: batch %d is less than 1", fn, batch);
+    if (!std::isfinite(threshold) || threshold < 0.0) return fail(MAV_ERR_ARG, "%s: threshold %g is negative or not finite", fn, threshold);
+    return MAV_OK;
+}
+extern "C" int mav_epipolar_residual_dev(mav_ctx* c, const float* flow, const double* F, double threshold, int batch, float* residual, uint8_t* mask,
+                                         mav_epipolar_record* records)
+{
+    const char* fn = "mav_epipolar_residual_dev";
+    CHK(epipolar_checked(c, flow, F, threshold, batch, records, fn));
+    if ((uintptr_t)flow % 4) return fail(MAV_ERR_ARG, "%s: flow is not aligned to its 4-byte elements", fn);
+    if ((uintptr_t)F % 8) return fail(MAV_ERR_ARG, "%s: F is not aligned to its 8-byte elements", fn);
+    if ((uintptr_t)residual % 4) return fail(MAV_ERR_ARG, "%s: residual is not aligned to its 4-byte elements", fn);
+    if ((uintptr_t)records % 16) return fail(MAV_ERR_ARG, "%s: records is not aligned to 16 bytes", fn);
+    CHK(check_dev_call(c, batch, fn));
+    {
+        ProfScope ps(c, K_MISC);
+        launch_epipolar_residual(c->stream, flow, F, threshold * threshold, c->W, c->H, batch, residual, mask, records);
+    }
+    return check_launch("epipolar residual");
+}
+extern "C" int mav_epipolar_residual(mav_ctx* c, const float* flow, const double* F, double threshold, int batch, float* residual, uint8_t* mask,
+                                     mav_epipolar_record* records)
+{
+    const char* fn = "mav_epipolar_residual";
+    CHK(epipolar_checked(c, flow, F, threshold, batch, records, fn));
+    HostCall h(c, fn);
+    CHK(h.beside(batch));
+    const float* df = h.in(flow, sizeof(float) * 2 * batch * c->n0);
+    const double* dF = h.in(F, sizeof(double) * 9 * batch);
+    float* dr = h.out(residual, sizeof(float) * batch * c->n0);
+    uint8_t* dm = h.out(mask, (size_t)batch * c->n0);
+    mav_epipolar_record* drec = h.out(records, sizeof(mav_epipolar_record) * batch);
+    CHK(h.staged());
+    CHK(mav_epipolar_residual_dev(c, df, dF, threshold, batch, dr, dm, drec));
+    return h.finish();
+}

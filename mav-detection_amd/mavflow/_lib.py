@@ -1973,3 +1973,7 @@ from . import warp  # noqa: E402,F401
 
 # include/mavflow_affine.h (Context.estimate_affine, .flow_affine, their *_enqueue twins and .estimate_affine_workspace_bytes): likewise
 from . import affine  # noqa: E402,F401
+
+# include/mavflow_fundamental.h (Context.find_fundamental, .flow_fundamental, .epipolar_residual, their *_enqueue twins and
+# .find_fundamental_workspace_bytes): likewise
+from . import fundamental  # noqa: E402,F401

@@ -1,8 +1,10 @@
 """Detector -- the Algorithm switch, IMU derotation, the window search (analyze_pyramid, optimize_window) and the global-motion
 branch (get_transformation_matrix for HOMOGRAPHY, flow_vec_subtract) of the reference's Detector (src/detector.py:14-202,280-358,
-430-433) on libmavflow.  The fundamental / essential-matrix estimators (cv2 RANSAC with a private RNG, unreachable from
-run_detection) are not reproduced: get_transformation_matrix says so.  The affine estimator runs with the caller's generator in
-.affine_rng (an extra; None: refused as before); flow_vec_subtract takes .aff, user-set as in the reference or set by that fit."""
+430-433) on libmavflow.  The affine, fundamental and essential-matrix estimators are cv2 RANSAC with a private RNG (unreachable
+from run_detection) and are refused by default: get_transformation_matrix says so.  The affine estimator runs with the caller's generator in
+.affine_rng (an extra; None: refused as before); flow_vec_subtract takes .aff, user-set as in the reference or set by that fit.  The
+fundamental-matrix estimator likewise runs with .fundamental_rng (an extra; None: refused as before) and gives epipolar_residual its
+matrix; the essential-matrix estimator (cv2's five-point solver, a different estimator) stays refused."""
 from __future__ import annotations
 
 from enum import Enum
@@ -114,6 +116,8 @@ class Detector:
         # an extra: the generator of the AFFINE fit's sample triples (a seed, a Generator or np.random).  None: get_transformation_matrix
         # refuses AFFINE as before
         self.affine_rng = None
+        # an extra: the generator of the FUNDAMENTAL fit's sample subsets, likewise.  None: FUNDAMENTAL is refused as before
+        self.fundamental_rng = None
         self.mag_handle = self.gray_handle = None    # flow_uv_warped_mag / one channel of to_rgb(magnitude) on the device, after a flow_vec_subtract of a device flow
 
     def get_gradient_and_magnitude(self, frame: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
@@ -231,10 +235,13 @@ class Detector:
         Lucas-Kanade tracks of orig_frame when there are any), fitted on the device in the structure of cv2.findHomography's method 0
         (Context.find_homography: not pinned against cv2).  Sets .homography (3x3 float64) and .confidence (the all-ones inlier mask,
         (n, 1) uint8); RuntimeError when the pairs determine no homography.  flow_uv: a host array or the flow seam's device handle.
-        AFFINE with .affine_rng set: _affine_matrix (sets .aff and .aff_inliers); with .affine_rng None it raises, as FUNDAMENTAL and
-        ESSENTIAL do."""
+        AFFINE with .affine_rng set: _affine_matrix (sets .aff and .aff_inliers); FUNDAMENTAL with .fundamental_rng set:
+        _fundamental_matrix (sets .fundamental and .fundamental_inliers); with the generator None either raises, as ESSENTIAL always
+        does."""
         A = Detector.Algorithm
         affine = self.algorithm == A.AFFINE and self.affine_rng is not None
+        if self.algorithm == A.FUNDAMENTAL and self.fundamental_rng is not None:
+            return self._fundamental_matrix(orig_frame, flow_uv)
         if self.algorithm in (A.AFFINE, A.FUNDAMENTAL, A.ESSENTIAL) and not affine:
             raise NotImplementedError(
                 f"{self.algorithm.name}: cv2.estimateAffine2D / findFundamentalMat / findEssentialMat are RANSAC estimators driven by "
@@ -303,6 +310,54 @@ class Detector:
             raise RuntimeError("get_transformation_matrix: the point pairs do not determine an affine map")
         self.aff = np.array(out["M"])
         self.aff_inliers = np.array(out["inliers"]).reshape(-1, 1)
+
+    def _fundamental_matrix(self, orig_frame: np.ndarray, flow_uv: np.ndarray) -> None:
+        """detector.py:144-146 with .fundamental_rng set (an extra): cv2.findFundamentalMat(coords_old, coords_new, cv2.FM_RANSAC, 0.999,
+        1.0)'s RANSAC fit on the device (include/mavflow_fundamental.h: not pinned against cv2), the sample subsets drawn from
+        .fundamental_rng by fundamental.sample_subsets, on the same three pair sources as HOMOGRAPHY and AFFINE.  The reference's literal
+        arguments are swapped -- cv2's order is (threshold, confidence) -- so the threshold is 0.999 pixels and the confidence 1.0, which
+        cv2's argument repair turns into 0.99; both are taken as cv2 would take them.  Sets .fundamental (3x3 float64, scaled to
+        F[2, 2] = 1 as cv2 returns it) and .fundamental_inliers ((n, 1) uint8); RuntimeError when no valid model had more than six
+        inliers."""
+        from . import fundamental as fm
+        W, H = self.dataset.capture_size[0], self.dataset.capture_size[1]
+        threshold, confidence = fm.repaired(0.999, 1.0)
+        kw = dict(threshold=threshold, confidence=confidence, rng=self.fundamental_rng)
+        pairs = None
+        if self.use_sparse_of:
+            old, new, _ = self.lucas_kanade.get_features(orig_frame)
+            if len(old) > 0 and len(new) > 0:
+                pairs = (np.asarray(old, np.float64), np.asarray(new, np.float64))
+        dev = None if pairs is not None else self._device_flow(flow_uv)
+        if pairs is not None:
+            out = im_helpers._ctx(W, H).find_fundamental(*pairs, **kw)
+        elif dev is not None:
+            out = dev[0].flow_fundamental(flow_uv, self.coords, **kw)                   # the field is read where it is
+        else:
+            flow = np.asarray(flow_uv)
+            if flow.dtype == np.float32:
+                out = im_helpers._ctx(W, H).flow_fundamental(flow, self.coords, **kw)
+            else:                                       # a float64 field keeps its precision: the reference's own pair arithmetic
+                new = self.coords.astype(np.float64) + flow[self.sample_y, self.sample_x]
+                out = im_helpers._ctx(W, H).find_fundamental(self.coords.astype(np.float64), new, **kw)
+        if not out["ok"]:
+            raise RuntimeError("get_transformation_matrix: the point pairs do not determine a fundamental matrix")
+        self.fundamental = fm.scaled(out["F"])
+        self.fundamental_inliers = np.array(out["inliers"]).reshape(-1, 1)
+
+    def epipolar_residual(self, flow_uv, threshold: float = 1.0) -> Tuple[np.ndarray, np.ndarray]:
+        """An extra: (residual (H, W) float32, mask (H, W) uint8 0/255) of the dense epipolar residual of flow_uv under .fundamental
+        (Context.epipolar_residual): per pixel the distance of p + flow(p) from the epipolar line of p; the mask marks what moves off its
+        line by more than `threshold` pixels -- an independent mover, whatever the scene's depth.  flow_uv: a float32 host array or the
+        flow seam's device handle, on whose context the pass runs."""
+        Fm = np.asarray(self.fundamental, np.float64)
+        dev = self._device_flow(flow_uv)
+        if dev is not None:
+            out = dev[0].epipolar_residual(flow_uv, Fm, threshold)
+        else:
+            W, H = self.dataset.capture_size[0], self.dataset.capture_size[1]
+            out = im_helpers._ctx(W, H).epipolar_residual(np.asarray(flow_uv, np.float32), Fm, threshold)
+        return out["residual"], out["mask"]
 
     def flow_vec_subtract(self, orig_frame: np.ndarray, flow_uv: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         """detector.py:153-202: the motion the matrix predicts (.homography for HOMOGRAPHY, else a user-set .aff) is subtracted from
