@@ -2,8 +2,8 @@
 // fused {box blur -> 2x2 solve -> UpdateMatrices} iteration of Farneback's algorithm.
 //
 // What they compute is cv2.calcOpticalFlowFarneback as called at /root/reference/src/farneback.py:76-80
-// (OpenCV modules/video/src/optflowgf.cpp).  How they compute it is new: R and M live
-// in HBM as 5 separate f32 planes per pair (coalesced 128-B row segments per wave), every stencil stage stages
+// (OpenCV modules/video/src/optflowgf.cpp).  How they compute it is new: M lives in HBM as 5
+// separate f32 planes per pair (coalesced 128-B row segments per wave), R as (h, w, 5), every stencil stage stages
 // its tile + halo through LDS once, box sums are separable sliding sums done in place in LDS, and the solve and
 // the next UpdateMatrices are fused behind the blur so M makes exactly one HBM round trip per iteration.
 // The path is HBM/LDS-bound stencil work: no MFMA.
@@ -1029,11 +1029,25 @@ MAV_BLUR_DEPTH(float)
 // FarnebackPolyExp (A.4).  64x16 output tile per workgroup; the (64+2n) x (16+2n) source tile (edge-clamped,
 // which is exactly OpenCV's row clamp + edge-triple replication) is staged in LDS, the vertical pass leaves
 // three (64+2n) x 16 planes in LDS and the horizontal pass reads those.  Coefficients sit in kernel arguments
-// (scalar loads).  Output: 5 planes.
+// (scalar loads).  Output: (h, w, 5), a wave's row of 64 pixels is 1 280 contiguous bytes.
 // ------------------------------------------------------------------------------------------------------------
 #define PX 64
 #define PY 16
-// one 64 x 16 tile of one image: src / dst = the image's layer plane and its five expansion planes
+// An expansion is (h, w, 5): the five values of a pixel lie together, 20 bytes at 4-byte alignment.  A pixel is
+// 16 + 4 bytes; the gather's row of two adjacent pixels is 16 + 16 + 8.
+struct __attribute__((packed, aligned(4))) F2U { float x, y; };           // two / four adjacent floats at 4-byte alignment
+struct __attribute__((packed, aligned(4))) F4U { float x, y, z, w; };
+static __device__ __forceinline__ void load5(const float* __restrict__ p, float v[5])
+{
+    const F4U a = *(const F4U*)p;
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = p[4];
+}
+static __device__ __forceinline__ void store5(float* __restrict__ p, const float v[5])
+{
+    *(F4U*)p = F4U{v[0], v[1], v[2], v[3]};
+    p[4] = v[4];
+}
+// one 64 x 16 tile of one image: src / dst = the image's layer plane and its expansion
 template <int N_T>
 static __device__ __forceinline__ void polyexp_tile(const float* __restrict__ src, float* __restrict__ dst, int w, int h, const PolyCoef& pc,
                                                     int tile_x, int tile_y, float* __restrict__ smem)
@@ -1087,7 +1101,6 @@ static __device__ __forceinline__ void polyexp_tile(const float* __restrict__ sr
         v0[i] = t0; v1[i] = t1; v2[i] = t2;
     }
     __syncthreads();
-    const size_t npx = (size_t)w * h;
     for (int i = tid; i < PY * PX; i += 256) {
         const int ly = i >> 6, lx = i & 63;
         const int gx = x0 + lx, gy = y0 + ly;
@@ -1107,12 +1120,10 @@ static __device__ __forceinline__ void polyexp_tile(const float* __restrict__ sr
             b6 = fmaf(c1 - a1, pc.xg[k], b6);
             b5 = fmaf(c2 + a2, pc.g[k], b5);
         }
-        const size_t o = (size_t)gy * w + gx;
-        dst[o] = b3 * pc.ig11;
-        dst[npx + o] = b2 * pc.ig11;
-        dst[2 * npx + o] = fmaf(b5, pc.ig33, b1 * pc.ig03);
-        dst[3 * npx + o] = fmaf(b4, pc.ig33, b1 * pc.ig03);
-        dst[4 * npx + o] = b6 * pc.ig55;
+        // the pixel's five values as 16 + 4 bytes, a wave's row 1 280 contiguous bytes.  (Measured, not kept: the row staged through LDS
+        // and stored as 16 bytes per consecutive lane -- k_polyexp<8> 231 us per launch against 217; HISTORY.md, "Expansion layout".)
+        const float r[5] = {b3 * pc.ig11, b2 * pc.ig11, fmaf(b5, pc.ig33, b1 * pc.ig03), fmaf(b4, pc.ig33, b1 * pc.ig03), b6 * pc.ig55};
+        store5(dst + 5 * ((size_t)gy * w + gx), r);
     }
 }
 
@@ -1179,7 +1190,7 @@ void launch_polyexp(hipStream_t st, const float* I, size_t I_stride, int G, int 
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// FarnebackUpdateMatrices for one pixel (A.5): a GATHER of the 2x2 neighbourhood of the 5 R1 planes around (x + dx, y + dy), then ONE
+// FarnebackUpdateMatrices for one pixel (A.5): a GATHER of the 2x2 neighbourhood of R1 around (x + dx, y + dy), then ONE
 // body, update_finish, that turns (q[] = the 5 R0 values at (x, y), the taps, the flow) into the 5 M values.  Every kernel that builds
 // M calls that body; they differ only in how the taps arrive.
 struct GatherPx {
@@ -1187,38 +1198,40 @@ struct GatherPx {
     float fx, fy;
     bool inside;
 };
+// one row of the neighbourhood: the pixels at p and p + 5, ten adjacent floats, as 16 + 16 + 8 bytes
+static __device__ __forceinline__ void gather_row(const float* __restrict__ p, float a[5], float b[5])
+{
+    const F4U t0 = *(const F4U*)p, t1 = *(const F4U*)(p + 4);
+    const F2U t2 = *(const F2U*)(p + 8);
+    a[0] = t0.x; a[1] = t0.y; a[2] = t0.z; a[3] = t0.w; a[4] = t1.x;
+    b[0] = t1.y; b[1] = t1.z; b[2] = t1.w; b[3] = t2.x; b[4] = t2.y;
+}
 // the sweep's fast form: the loads are issued unconditionally, so that two pixels' gathers are in flight together; a neighbourhood that
-// is not inside the image reads the one at (0, 0) instead and discards it (on a layer of one row that read passes the plane's end)
-static __device__ __forceinline__ void gather_issue(const float* __restrict__ R1p, size_t npx, int w, int h, int x, int y, float dx,
-                                                    float dy, GatherPx& g)
+// is not inside the image reads the one at (0, 0) instead and discards it.  On a layer of one row or one column no neighbourhood is
+// inside, and the second row of that read is the first one again: it stays inside the expansion (DESIGN.md has the one exception, 1 x 1)
+static __device__ __forceinline__ void gather_issue(const float* __restrict__ R1p, int w, int h, int x, int y, float dx, float dy, GatherPx& g)
 {
     float fx = x + dx, fy = y + dy;
     const int x1 = (int)floorf(fx), y1 = (int)floorf(fy);
     g.fx = fx - x1; g.fy = fy - y1;
     g.inside = (unsigned)x1 < (unsigned)(w - 1) && (unsigned)y1 < (unsigned)(h - 1);
     const int xc = g.inside ? x1 : 0, yc = g.inside ? y1 : 0;
-    const float* p = R1p + (size_t)yc * w + xc;
-#pragma unroll
-    for (int c = 0; c < 5; c++) {
-        g.p00[c] = p[0]; g.p01[c] = p[1]; g.p10[c] = p[w]; g.p11[c] = p[w + 1];
-        p += npx;
-    }
+    const float* p = R1p + 5 * ((size_t)yc * w + xc);
+    const size_t row = (w > 1 && h > 1) ? 5 * (size_t)w : 0;             // uniform
+    gather_row(p, g.p00, g.p01);
+    gather_row(p + row, g.p10, g.p11);
 }
 // the memory form's gather: the taps are read only when the neighbourhood is inside the image
-static __device__ __forceinline__ void gather_inside(const float* __restrict__ R1p, size_t npx, int w, int h, int x, int y, float dx,
-                                                     float dy, GatherPx& g)
+static __device__ __forceinline__ void gather_inside(const float* __restrict__ R1p, int w, int h, int x, int y, float dx, float dy, GatherPx& g)
 {
     float fx = x + dx, fy = y + dy;
     const int x1 = (int)floorf(fx), y1 = (int)floorf(fy);
     g.fx = fx - x1; g.fy = fy - y1;
     g.inside = (unsigned)x1 < (unsigned)(w - 1) && (unsigned)y1 < (unsigned)(h - 1);
     if (!g.inside) return;
-    const float* p = R1p + (size_t)y1 * w + x1;
-#pragma unroll
-    for (int c = 0; c < 5; c++) {
-        g.p00[c] = p[0]; g.p01[c] = p[1]; g.p10[c] = p[w]; g.p11[c] = p[w + 1];
-        p += npx;
-    }
+    const float* p = R1p + 5 * ((size_t)y1 * w + x1);
+    gather_row(p, g.p00, g.p01);
+    gather_row(p + 5 * (size_t)w, g.p10, g.p11);
 }
 static __device__ __forceinline__ void update_finish(const float q[5], const GatherPx& g, int w, int h, int x, int y, float dx,
                                                      float dy, float out[5])
@@ -1263,16 +1276,15 @@ static __device__ __forceinline__ void update_finish(const float q[5], const Gat
     out[4] = fmaf(r6, r2, r5 * r3);
 }
 
-// memory form: R0p/R1p/Mp point at plane 0 of the pair; planes are npx apart.
+// memory form: R0p/R1p point at the pair's two expansions (h, w, 5); Mp at plane 0 of its M, planes are npx apart.
 static __device__ __forceinline__ void update_px(const float* __restrict__ R0p, const float* __restrict__ R1p, size_t npx,
                                                  int w, int h, int x, int y, float dx, float dy, float* __restrict__ Mp)
 {
     const size_t idx = (size_t)y * w + x;
     float q[5], o[5];
-#pragma unroll
-    for (int c = 0; c < 5; c++) q[c] = R0p[c * npx + idx];
+    load5(R0p + 5 * idx, q);
     GatherPx g;
-    gather_inside(R1p, npx, w, h, x, y, dx, dy, g);
+    gather_inside(R1p, w, h, x, y, dx, dy, g);
     update_finish(q, g, w, h, x, y, dx, dy, o);
 #pragma unroll
     for (int c = 0; c < 5; c++) Mp[c * npx + idx] = o[c];
@@ -1321,7 +1333,9 @@ static __device__ __forceinline__ float2 upsample_flow(const float* __restrict__
 // explicit flow field (stage hook; the top layer of a call with an initial flow).  The upsampled flow is never written: the first blur sweep overwrites it.
 // One thread per pixel, 64 x 4 pixels per workgroup on a plain 2-D grid.  (Measured alternative, not kept: 64 x 16 tiles in the
 // XCD-aware order with two gathers in flight per thread -- L2 absorbed the gather rows, the kernel ran 5 % slower: its reads
-// that miss L2 are served by the Infinity Cache anyway, and the taller tile halves the number of workgroups in flight.)
+// that miss L2 are served by the Infinity Cache anyway, and the taller tile halves the number of workgroups in flight.  And with the
+// expansions interleaved: 64 x 8 per workgroup, a wave on two adjacent rows with both gathers in flight, fetched 8 % less than 64 x 4
+// (2 x FETCH_SIZE 6.36 vs 6.89 GB per step) and ran no faster: 3.69 vs 3.65 ms of class time; HISTORY.md, "Expansion layout".)
 template <int MODE>  // 0 zero, 1 upsample, 2 explicit
 __global__ __launch_bounds__(256) void k_update_matrices(const float* __restrict__ R0, const float* __restrict__ R1,
                                                          size_t R_stride, const float* __restrict__ fsrc, size_t f_stride,
@@ -1548,7 +1562,6 @@ __global__ __launch_bounds__(256) void k_blur_iter_generic(const float* __restri
 #define FT_X 64
 #define FT_Y 16
 
-struct __attribute__((packed, aligned(4))) F2U { float x, y; };     // two adjacent floats at 4-byte alignment
 // AL = true: width a multiple of 4 and 16-byte aligned planes (vector loads / stores as written); AL = false: any width -- the
 // column pairs are read as two floats at 4-byte alignment and the flow is stored pixel by pixel.
 // WT = true: M' leaves the kernel through write-through (agent-scope, sc1) stores instead of staying dirty in the XCD's L2 until the
@@ -1590,9 +1603,7 @@ __global__ __launch_bounds__(256) void k_blur_iter_fast(const float* __restrict_
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             gys[j] = min(y0 + wv * 4 + j, h - 1);
-            const size_t idx = (size_t)gys[j] * w + gxc;
-#pragma unroll
-            for (int c = 0; c < 5; c++) q[j][c] = R0p[c * npx + idx];
+            load5(R0p + 5 * ((size_t)gys[j] * w + gxc), q[j]);
         }
     }
 
@@ -1685,7 +1696,7 @@ __global__ __launch_bounds__(256) void k_blur_iter_fast(const float* __restrict_
             const int ly = wv * 4 + jb + jj;
             fu[jj] = vs[ly * PITCH + lane];
             fv[jj] = vs[PLANE + ly * PITCH + lane];
-            gather_issue(R1p, npx, w, h, gxc, gys[jb + jj], fu[jj], fv[jj], g[jj]);
+            gather_issue(R1p, w, h, gxc, gys[jb + jj], fu[jj], fv[jj], g[jj]);
         }
 #pragma unroll
         for (int jj = 0; jj < 2; jj++) {

@@ -3811,11 +3811,11 @@ extern "C" int mav_stage_polyexp(mav_ctx* c, const float* I, int k, float* R)
     if (!I || !R) return fail(MAV_ERR_ARG, "mav_stage_polyexp: NULL argument");
     const size_t n = (size_t)l->w * l->h;
     const float* di = h.in(I, n * sizeof(float));
-    float* dr = h.out(R, 5 * n * sizeof(float));
+    std::vector<float> e(5 * n); float* dr = h.out(e.data(), 5 * n * sizeof(float));      // (h, w, 5), as the kernel writes it
     CHK(h.staged());
     launch_polyexp(c->stream, di, n, 1, l->w, l->h, c->pc, dr, 5 * n);
     CHK(check_launch("polyexp"));
-    return h.finish();
+    return planes_of_expansion(h.finish(), e, n, R);      // R takes its planes
 }
 extern "C" int mav_stage_update_matrices(mav_ctx* c, const float* R0, const float* R1, const float* flow, int k, float* M)
 {
@@ -3824,8 +3824,8 @@ extern "C" int mav_stage_update_matrices(mav_ctx* c, const float* R0, const floa
     CHK(h.fresh_layer(k, &l));
     if (!R0 || !R1 || !flow || !M) return fail(MAV_ERR_ARG, "mav_stage_update_matrices: NULL argument");
     const size_t n = (size_t)l->w * l->h;
-    const float* d0 = h.in(R0, 5 * n * sizeof(float));
-    const float* d1 = h.in(R1, 5 * n * sizeof(float));
+    const std::vector<float> e0 = expansion_of_planes(R0, n), e1 = expansion_of_planes(R1, n);      // the caller's planes as (h, w, 5)
+    const float *d0 = h.in(e0.data(), 5 * n * sizeof(float)), *d1 = h.in(e1.data(), 5 * n * sizeof(float));
     const float* df = h.in(flow, 2 * n * sizeof(float));
     float* dm = h.out(M, 5 * n * sizeof(float));
     CHK(h.staged());
@@ -3845,8 +3845,8 @@ extern "C" int mav_stage_update_matrices_from(mav_ctx* c, const float* R0, const
         return fail(MAV_ERR_ARG, "mav_stage_update_matrices_from: layer %d is the top layer, it has no coarser flow", k);
     const size_t n = (size_t)l->w * l->h;
     const size_t nc = flow_coarse ? (size_t)c->layers[k + 1].w * c->layers[k + 1].h : 0;
-    const float* d0 = h.in(R0, 5 * n * sizeof(float));
-    const float* d1 = h.in(R1, 5 * n * sizeof(float));
+    const std::vector<float> e0 = expansion_of_planes(R0, n), e1 = expansion_of_planes(R1, n);      // the caller's planes as (h, w, 5)
+    const float *d0 = h.in(e0.data(), 5 * n * sizeof(float)), *d1 = h.in(e1.data(), 5 * n * sizeof(float));
     const float* df = h.in(flow_coarse, 2 * nc * sizeof(float));
     float* dm = h.out(M, 5 * n * sizeof(float));
     CHK(h.staged());
@@ -3879,8 +3879,8 @@ extern "C" int mav_stage_blur_iter(mav_ctx* c, const float* R0, const float* R1,
     CHK(h.fresh_layer(k, &l));
     if (!R0 || !R1 || !M || !flow || (update && !M_out)) return fail(MAV_ERR_ARG, "mav_stage_blur_iter: NULL argument");
     const size_t n = (size_t)l->w * l->h;
-    const float* d0 = h.in(R0, 5 * n * sizeof(float));
-    const float* d1 = h.in(R1, 5 * n * sizeof(float));
+    const std::vector<float> e0 = expansion_of_planes(R0, n), e1 = expansion_of_planes(R1, n);      // the caller's planes as (h, w, 5)
+    const float *d0 = h.in(e0.data(), 5 * n * sizeof(float)), *d1 = h.in(e1.data(), 5 * n * sizeof(float));
     const float* dm = h.in(M, 5 * n * sizeof(float));
     float* dmo = h.scratch<float>(5 * n * sizeof(float));
     float* df = h.out(flow, 2 * n * sizeof(float));

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <vector>
 
 #include "../../include/mavflow.h"
 
@@ -103,8 +104,24 @@ bool blur_multi_ok(const FrameRun<T>& f, const LayerTarget& t);
 template <typename T>
 void launch_blur_multi(hipStream_t st, const FrameRun<T>& f, BlurJobs jobs);
 
-// G pairs of one w x h layer: their expansions R0 / R1, five planes each.
+// G pairs of one w x h layer: their expansions R0 / R1, (h, w, 5) each -- the five values of a pixel lie together.
 struct PairOperands { const float *R0, *R1; size_t R_stride; int G, w, h; };
+// The stage hooks keep their host contract of five planes (include/mavflow.h) and transpose at the edge, on the host copy, so that no
+// launch is added.  The staged copy must live until the call's finish() has returned.
+inline std::vector<float> expansion_of_planes(const float* planes, size_t n)
+{
+    std::vector<float> e(planes ? 5 * n : 0);
+    for (size_t c = 0; c < 5 && planes; c++)
+        for (size_t i = 0; i < n; i++) e[5 * i + c] = planes[c * n + i];
+    return e;
+}
+// rc: what the call's finish() returned; the planes are written only when it succeeded
+inline int planes_of_expansion(int rc, const std::vector<float>& e, size_t n, float* planes)
+{
+    for (size_t c = 0; c < 5 && rc == MAV_OK; c++)
+        for (size_t i = 0; i < n; i++) planes[c * n + i] = e[5 * i + c];
+    return rc;
+}
 // Where a layer's initial flow comes from: nowhere (zero flow: the top layer), the coarser layer's field (pw x ph; resize(INTER_LINEAR)
 // to the layer's size times mul, evaluated inside the kernel and never written) or a field of the layer's own size (the stage hook; the
 // top layer of a call with OPTFLOW_USE_INITIAL_FLOW).  kind = k_update_matrices' MODE.
