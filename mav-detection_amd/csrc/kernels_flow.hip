@@ -1047,7 +1047,9 @@ static __device__ __forceinline__ void store5(float* __restrict__ p, const float
     *(F4U*)p = F4U{v[0], v[1], v[2], v[3]};
     p[4] = v[4];
 }
-// one 64 x 16 tile of one image: src / dst = the image's layer plane and its expansion
+// one 64 x 16 tile of one image: src / dst = the image's layer plane and its expansion.  This is the RELAXED form: any width, any
+// alignment, any poly_n (N_T == 0: n from the arguments).  polyexp_tile_fast below is the aligned form of the same arithmetic; the
+// launch chooses (polyexp_vec_ok), and tests/test_gpu_polyexp_forms.py holds the two to the same bits.
 template <int N_T>
 static __device__ __forceinline__ void polyexp_tile(const float* __restrict__ src, float* __restrict__ dst, int w, int h, const PolyCoef& pc,
                                                     int tile_x, int tile_y, float* __restrict__ smem)
@@ -1127,14 +1129,202 @@ static __device__ __forceinline__ void polyexp_tile(const float* __restrict__ sr
     }
 }
 
+// The aligned fast form of the same tile (N_T > 0, polyexp_vec_ok: width a multiple of 4, 16-byte aligned planes): the same values
+// bit for bit -- every output is the relaxed form's expression in the relaxed form's order, two adjacent pixels per packed
+// instruction -- with the taps carried in registers instead of re-read from LDS for every output.
+//   staging     the source tile as 16-byte quads, 20 per row: columns x0 - 8 .. x0 + 71 whatever n is, so that every quad is aligned;
+//               with w % 4 == 0 a quad lies wholly inside the image or wholly outside, where it is the edge pixel replicated
+//   vertical    one thread per (column pair, block of 4 rows): its 4 + 2n float2 values are read once and slide through registers
+//               for the 4 x 2 outputs of the three planes (plane column = tile column + 8)
+//   horizontal  one thread per 4 consecutive pixels of a row, lanes laid out by the hardware's ds_read_b128 lane groups as in the sweep
+//               kernel's phase B (16 consecutive quads of one row per group: every bank once at any pitch); per plane five 16-byte
+//               reads
+//   stores      a thread's 4 pixels are 80 contiguous bytes of the expansion, but stored from there a wave's store instruction would
+//               touch 40 cache lines at 16 bytes in every 80 (measured: 257 us per launch of k_polyexp<8> against the relaxed form's
+//               217).  The 16 lanes of a row exchange their quads through LDS that nobody reads any more -- the wave's own rows of
+//               the three planes and a row of the tile region -- and lane p stores quads p, 16 + p, .. 64 + p of the row's 80: 256
+//               contiguous bytes per row and instruction (169 us).  Same wave, LDS operations in program order: no barrier.
+// LDS: (16 + 2n) x 84 + 3 x 16 x 80 floats = 25.5 KB at n = 8.  The tile pitch of 84 puts the two row blocks that one half-wave of the
+// vertical pass can straddle (4 rows apart) on disjoint banks.  HISTORY.md, "Polynomial expansion: the aligned fast form".
+typedef float pk2 __attribute__((ext_vector_type(2)));
+#define PF_QX 20                // quads per staged row
+#define PF_TP 84                // tile pitch (floats)
+#define PF_PP 80                // plane pitch
+static __device__ __forceinline__ pk2 pk_fma(float s, pk2 x, pk2 acc) { return __builtin_elementwise_fma(pk2{s, s}, x, acc); }
+// A thread's 20 floats of one plane row as five 16-byte reads.  n < 8 leaves the outer 8 - n floats unused, and the compiler would then
+// re-form the reads from the pairs the arithmetic takes, at 4-byte alignment (ds_read2_b32 at a 16-byte lane stride: 4-way bank
+// conflicts, and floats read several times): there the quads pass through an empty asm statement, which it cannot look through.
+template <int N_T>
+static __device__ __forceinline__ void load_quads5(const float* __restrict__ p, float f[20])
+{
+    typedef float pk4 __attribute__((ext_vector_type(4)));
+    pk4 t[5];
+#pragma unroll
+    for (int k = 0; k < 5; k++) t[k] = ((const pk4*)p)[k];
+#pragma unroll
+    for (int k = 0; k < 5; k++) {
+        if constexpr (N_T < 8) asm volatile("" : "+v"(t[k]));
+        f[4 * k] = t[k].x; f[4 * k + 1] = t[k].y; f[4 * k + 2] = t[k].z; f[4 * k + 3] = t[k].w;
+    }
+}
+template <int N_T>
+static __device__ __forceinline__ void polyexp_tile_fast(const float* __restrict__ src, float* __restrict__ dst, int w, int h, const PolyCoef& pc,
+                                                         int tile_x, int tile_y, float* __restrict__ smem)
+{
+    constexpr int n = N_T, EY = PY + 2 * n, NV = 4 + 2 * n;
+    float* tile = smem;
+    float* v0 = tile + EY * PF_TP;
+    float* v1 = v0 + PY * PF_PP;
+    float* v2 = v1 + PY * PF_PP;
+    const int tid = threadIdx.x;
+    const int x0 = tile_x * PX, y0 = tile_y * PY;
+    {
+        // all of a thread's loads are issued before the first LDS store, as in the relaxed form
+        constexpr int TOT = PF_QX * EY, CNT = (TOT + 255) / 256;
+        // (straight-line loads -- a thread past the last quad re-reads that quad -- and selects afterwards: with the load or the edge
+        // replication under a branch the compiler splits the load and waits for its first part before it issues the next)
+        float4 q[CNT];
+#pragma unroll
+        for (int j = 0; j < CNT; j++) {
+            const int i = min(tid + 256 * j, TOT - 1);
+            const int ly = i / PF_QX, qx = i - ly * PF_QX;
+            const int gx = x0 - 8 + 4 * qx, gy = clampi(y0 - n + ly, 0, h - 1);
+            q[j] = *(const float4*)(src + (size_t)gy * w + clampi(gx, 0, w - 4));
+        }
+#pragma unroll
+        for (int j = 0; j < CNT; j++) {
+            const int i = tid + 256 * j;
+            const int ly = i / PF_QX, qx = i - ly * PF_QX;
+            const int gx = x0 - 8 + 4 * qx;
+            const bool lo = gx < 0, hi = gx >= w, out = lo || hi;
+            const float4 t = q[j];
+            const float e = lo ? t.x : t.w;
+            if (i < TOT) *(float4*)(tile + ly * PF_TP + 4 * qx) = make_float4(hi ? e : t.x, out ? e : t.y, out ? e : t.z, lo ? e : t.w);
+        }
+    }
+    __syncthreads();
+    if (tid < (PY / 4) * (PF_PP / 2)) {
+        const int rb = tid / (PF_PP / 2), cp = tid - rb * (PF_PP / 2);
+        const float* c = tile + rb * 4 * PF_TP + 2 * cp;
+        pk2 v[NV];
+#pragma unroll
+        for (int i = 0; i < NV; i++) v[i] = *(const pk2*)(c + i * PF_TP);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            pk2 t0 = v[j + n] * pc.g[0], t1 = pk2{0.f, 0.f}, t2 = pk2{0.f, 0.f};
+#pragma unroll
+            for (int k = 1; k <= n; k++) {
+                const pk2 a = v[j + n - k], b = v[j + n + k];
+                const pk2 p = a + b;
+                t0 = pk_fma(pc.g[k], p, t0);
+                t1 = pk_fma(pc.xg[k], b - a, t1);
+                t2 = pk_fma(pc.xxg[k], p, t2);
+            }
+            const int o = (rb * 4 + j) * PF_PP + 2 * cp;
+            *(pk2*)(v0 + o) = t0; *(pk2*)(v1 + o) = t1; *(pk2*)(v2 + o) = t2;
+        }
+    }
+    __syncthreads();
+    {
+        // hardware b128 lane group -> tile row, position inside the group -> the row's quad (k_blur_iter_fast, phase B)
+        const int lane = tid & 63, wv = tid >> 6;
+        const int quad = (lane & 31) >> 2;
+        const int grp = (lane >> 5) * 2 + ((quad == 1 || quad == 2 || quad == 4 || quad == 7) ? 1 : 0);
+        const int qpos = (quad == 0 || quad == 1) ? 0 : ((quad == 3 || quad == 2) ? 1 : ((quad == 5 || quad == 4) ? 2 : 3));
+        const int ly = wv * 4 + grp, lx0 = (qpos * 4 + (lane & 3)) * 4;
+        const int gy = y0 + ly;
+        const int o = ly * PF_PP + lx0;       // f[i] = plane column lx0 + i; pixel j of the thread sits at f[8 + j]
+        float f[20];
+        pk2 b1[2], b2[2], b3[2], b4[2], b5[2], b6[2];
+        load_quads5<N_T>(v0 + o, f);
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const int m = 8 + 2 * j;
+            b1[j] = pk2{f[m], f[m + 1]} * pc.g[0]; b2[j] = pk2{0.f, 0.f}; b4[j] = pk2{0.f, 0.f};
+#pragma unroll
+            for (int k = 1; k <= n; k++) {
+                const pk2 a0 = pk2{f[m - k], f[m + 1 - k]}, c0 = pk2{f[m + k], f[m + 1 + k]};
+                const pk2 tg = c0 + a0;
+                b1[j] = pk_fma(pc.g[k], tg, b1[j]);
+                b4[j] = pk_fma(pc.xxg[k], tg, b4[j]);
+                b2[j] = pk_fma(pc.xg[k], c0 - a0, b2[j]);
+            }
+        }
+        load_quads5<N_T>(v1 + o, f);
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const int m = 8 + 2 * j;
+            b3[j] = pk2{f[m], f[m + 1]} * pc.g[0]; b6[j] = pk2{0.f, 0.f};
+#pragma unroll
+            for (int k = 1; k <= n; k++) {
+                const pk2 a1 = pk2{f[m - k], f[m + 1 - k]}, c1 = pk2{f[m + k], f[m + 1 + k]};
+                b3[j] = pk_fma(pc.g[k], c1 + a1, b3[j]);
+                b6[j] = pk_fma(pc.xg[k], c1 - a1, b6[j]);
+            }
+        }
+        load_quads5<N_T>(v2 + o, f);
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const int m = 8 + 2 * j;
+            b5[j] = pk2{f[m], f[m + 1]} * pc.g[0];
+#pragma unroll
+            for (int k = 1; k <= n; k++) {
+                const pk2 a2 = pk2{f[m - k], f[m + 1 - k]}, c2 = pk2{f[m + k], f[m + 1 + k]};
+                b5[j] = pk_fma(pc.g[k], c2 + a2, b5[j]);
+            }
+        }
+        float r[20];
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const pk2 r0 = b3[j] * pc.ig11, r1 = b2[j] * pc.ig11, e = b1[j] * pc.ig03;
+            const pk2 r2 = pk_fma(pc.ig33, b5[j], e), r3 = pk_fma(pc.ig33, b4[j], e), r4 = b6[j] * pc.ig55;
+            float* q = r + 10 * j;
+            q[0] = r0.x; q[1] = r1.x; q[2] = r2.x; q[3] = r3.x; q[4] = r4.x;
+            q[5] = r0.y; q[6] = r1.y; q[7] = r2.y; q[8] = r3.y; q[9] = r4.y;
+        }
+        // the row's 80 quads through LDS (this wave's own rows of the three planes + a row of the tile region, 20 quads each): lane pos
+        // leaves quads 5 pos .. 5 pos + 4 and takes quads 16 k + pos, so that a store instruction covers 256 contiguous bytes per row
+        {
+            const int pos = lx0 >> 2;
+            auto chunk = [&](int c) { return smem + (c < 3 ? EY * PF_TP + c * PY * PF_PP : 0) + ly * PF_PP; };
+            float* wr = chunk(pos >> 2) + 4 * (5 * (pos & 3));
+#pragma unroll
+            for (int k = 0; k < 5; k++) *(float4*)(wr + 4 * k) = make_float4(r[4 * k], r[4 * k + 1], r[4 * k + 2], r[4 * k + 3]);
+            const int vq = 5 * (min(PX, w - x0) >> 2);          // valid quads of the row
+            float4* out = (float4*)(dst + 5 * ((size_t)gy * w + x0));
+            float4 t[5];
+#pragma unroll
+            for (int k = 0; k < 5; k++) {
+                const int idx = 16 * k + pos, c = idx / 20;
+                t[k] = *(const float4*)(chunk(c) + 4 * (idx - 20 * c));
+            }
+            if (gy < h) {
+#pragma unroll
+                for (int k = 0; k < 5; k++)
+                    if (16 * k + pos < vq) out[16 * k + pos] = t[k];
+            }
+        }
+    }
+}
+// one tile in the form the launch chose (`fast`: polyexp_vec_ok held on the host; uniform over the workgroup)
+template <int N_T>
+static __device__ __forceinline__ void polyexp_tile_any(bool fast, const float* __restrict__ src, float* __restrict__ dst, int w, int h,
+                                                        const PolyCoef& pc, int tile_x, int tile_y, float* __restrict__ smem)
+{
+    if constexpr (N_T > 0) {
+        if (fast) { polyexp_tile_fast<N_T>(src, dst, w, h, pc, tile_x, tile_y, smem); return; }
+    }
+    polyexp_tile<N_T>(src, dst, w, h, pc, tile_x, tile_y, smem);
+}
+
 template <int N_T>
 __global__ __launch_bounds__(256) void k_polyexp(const float* __restrict__ I, size_t I_stride, int w, int h, PolyCoef pc, TileMap tm,
-                                                 float* __restrict__ R, size_t R_stride)
+                                                 float* __restrict__ R, size_t R_stride, int fast)
 {
     int img_s, tile_x, tile_y;
     if (!tile_of_block(tm, &img_s, &tile_x, &tile_y)) return;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    polyexp_tile<N_T>(I + (size_t)img_s * I_stride, R + (size_t)img_s * R_stride, w, h, pc, tile_x, tile_y, smem);
+    polyexp_tile_any<N_T>(fast != 0, I + (size_t)img_s * I_stride, R + (size_t)img_s * R_stride, w, h, pc, tile_x, tile_y, smem);
 }
 
 // The expansions of SEVERAL layers in one launch (a small group's whole pyramid: launch_polyexp_multi): workgroup b belongs to the
@@ -1149,21 +1339,39 @@ __global__ __launch_bounds__(256) void k_polyexp_multi(PolyJobs jobs, PolyCoef p
     const int img_s = tile / J.per_img, rem = tile - img_s * J.per_img;
     const int tile_y = rem / J.tiles_x, tile_x = rem - tile_y * J.tiles_x;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    polyexp_tile<N_T>(J.I + (size_t)img_s * J.I_stride, J.R + (size_t)img_s * J.R_stride, J.w, J.h, pc, tile_x, tile_y, smem);
+    polyexp_tile_any<N_T>(J.fast != 0, J.I + (size_t)img_s * J.I_stride, J.R + (size_t)img_s * J.R_stride, J.w, J.h, pc, tile_x, tile_y, smem);
 }
-// jobs[i]: G images of a (w x h) layer at I (slot stride I_stride) -> R (slot stride R_stride); first_block / tiles_x / per_img are filled here
+// The fast form's predicate (the same kind as blur_iter_vec_ok): every quad of a row, of the source and of the expansion, is 16-byte
+// aligned in every slot.  poly_n 8, 7 and 5 have the form; every other n takes the relaxed one.
+static bool polyexp_vec_ok(const float* I, size_t I_stride, const float* R, size_t R_stride, int w, int n)
+{
+    return (n == 8 || n == 7 || n == 5) && w >= 4 && w % 4 == 0 && I_stride % 4 == 0 && R_stride % 4 == 0 && ((uintptr_t)I & 15) == 0 &&
+           ((uintptr_t)R & 15) == 0;
+}
+// dynamic LDS of a launch: the relaxed form's, or the larger of the two when a job takes the fast form
+static size_t polyexp_lds_bytes(int n, bool fast)
+{
+    const size_t relaxed = sizeof(float) * ((size_t)(PX + 2 * n) * (PY + 2 * n) + 3 * (size_t)PY * (PX + 2 * n));
+    const size_t vec = sizeof(float) * ((size_t)(PY + 2 * n) * PF_TP + 3 * (size_t)PY * PF_PP);
+    return fast && vec > relaxed ? vec : relaxed;
+}
+// jobs[i]: G images of a (w x h) layer at I (slot stride I_stride) -> R (slot stride R_stride); first_block / tiles_x / per_img / fast are
+// filled here
 void launch_polyexp_multi(hipStream_t st, PolyJobs jobs, int G, const PolyCoef& pc)
 {
     const int n = pc.n;
-    const size_t lds = sizeof(float) * ((size_t)(PX + 2 * n) * (PY + 2 * n) + 3 * (size_t)PY * (PX + 2 * n));
     int blocks = 0;
+    bool any_fast = false;
     for (int i = 0; i < jobs.n; i++) {
         PolyJob& J = jobs.j[i];
         J.tiles_x = (J.w + PX - 1) / PX;
         J.per_img = J.tiles_x * ((J.h + PY - 1) / PY);
         J.first_block = blocks;
+        J.fast = polyexp_vec_ok(J.I, J.I_stride, J.R, J.R_stride, J.w, n);
+        any_fast |= J.fast != 0;
         blocks += J.per_img * G;
     }
+    const size_t lds = polyexp_lds_bytes(n, any_fast);
     if (n == 8) hipLaunchKernelGGL(k_polyexp_multi<8>, dim3(blocks), dim3(256), lds, st, jobs, pc);
     else if (n == 7) hipLaunchKernelGGL(k_polyexp_multi<7>, dim3(blocks), dim3(256), lds, st, jobs, pc);
     else if (n == 5) hipLaunchKernelGGL(k_polyexp_multi<5>, dim3(blocks), dim3(256), lds, st, jobs, pc);
@@ -1174,19 +1382,20 @@ void launch_polyexp(hipStream_t st, const float* I, size_t I_stride, int G, int 
                     size_t R_stride)
 {
     const int n = pc.n;
-    const size_t lds = sizeof(float) * ((size_t)(PX + 2 * n) * (PY + 2 * n) + 3 * (size_t)PY * (PX + 2 * n));
+    const int fast = polyexp_vec_ok(I, I_stride, R, R_stride, w, n);
+    const size_t lds = polyexp_lds_bytes(n, fast != 0);
     TileMap tm = make_tile_map(w, h, G, PX, PY);
     tm.xcd = 0;        // plain row-major order: measured 3 % faster here than the XCD-banded order (the halo re-reads that miss
                        // L2 hit the Infinity Cache, which all XCDs share; the kernel is VALU / write bound, not read bound)
     const dim3 grid(tile_grid(tm));
     if (n == 8)
-        hipLaunchKernelGGL(k_polyexp<8>, grid, dim3(256), lds, st, I, I_stride, w, h, pc, tm, R, R_stride);
+        hipLaunchKernelGGL(k_polyexp<8>, grid, dim3(256), lds, st, I, I_stride, w, h, pc, tm, R, R_stride, fast);
     else if (n == 7)
-        hipLaunchKernelGGL(k_polyexp<7>, grid, dim3(256), lds, st, I, I_stride, w, h, pc, tm, R, R_stride);
+        hipLaunchKernelGGL(k_polyexp<7>, grid, dim3(256), lds, st, I, I_stride, w, h, pc, tm, R, R_stride, fast);
     else if (n == 5)
-        hipLaunchKernelGGL(k_polyexp<5>, grid, dim3(256), lds, st, I, I_stride, w, h, pc, tm, R, R_stride);
+        hipLaunchKernelGGL(k_polyexp<5>, grid, dim3(256), lds, st, I, I_stride, w, h, pc, tm, R, R_stride, fast);
     else
-        hipLaunchKernelGGL(k_polyexp<0>, grid, dim3(256), lds, st, I, I_stride, w, h, pc, tm, R, R_stride);
+        hipLaunchKernelGGL(k_polyexp<0>, grid, dim3(256), lds, st, I, I_stride, w, h, pc, tm, R, R_stride, fast);
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -66,7 +66,7 @@ static __device__ __forceinline__ void derot_apply(double2 f, const DerotParams*
 
 // Several layers in one launch (a small group's whole pyramid): job tables passed by value in the kernel arguments.
 #define MAV_MAX_JOBS 6
-struct PolyJob { const float* I; float* R; size_t I_stride, R_stride; int w, h, tiles_x, per_img, first_block, pad; };
+struct PolyJob { const float* I; float* R; size_t I_stride, R_stride; int w, h, tiles_x, per_img, first_block, fast; };
 struct PolyJobs { int n, pad; PolyJob j[MAV_MAX_JOBS]; };
 
 // ---- flow kernels (kernels_flow.hip) ----------------------------------------------------------------------
