@@ -5345,3 +5345,186 @@ extern "C" int mav_epipolar_residual(mav_ctx* c, const float* flow, const double
     CHK(mav_epipolar_residual_dev(c, df, dF, threshold, batch, dr, dm, drec));
     return h.finish();
 }
+
+// ---- robust essential-matrix fit (include/mavflow_essential.h) -----------------------------------------------------------------------------
+// As the fundamental fit: every kind of resident state is kept, no device memory of the context's is held; the _dev forms work in the
+// caller's workspace (the flow form's gathered pairs included), the host forms in staging blocks behind the last call's.
+#include "../../include/mavflow_essential.h"
+
+extern "C" void mav_essential_defaults(mav_essential_params* p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->threshold = 1.0;
+    p->confidence = 0.999;
+    p->fx = 1.0;
+    p->fy = 1.0;
+    p->max_iters = 1000;
+}
+static int essential_params_checked(int n, const mav_essential_params* p, const char* fn)
+{
+    if (!p) return fail(MAV_ERR_ARG, "%s: NULL params", fn);
+    if (n < 5 || n > MAV_ESSENTIAL_MAX_PAIRS) return fail(MAV_ERR_ARG, "%s: n %d outside [5, %d]", fn, n, MAV_ESSENTIAL_MAX_PAIRS);
+    if (p->max_iters < 1 || p->max_iters > MAV_ESSENTIAL_MAX_ITERS)
+        return fail(MAV_ERR_ARG, "%s: max_iters %d outside [1, %d]", fn, p->max_iters, MAV_ESSENTIAL_MAX_ITERS);
+    if (!std::isfinite(p->threshold) || p->threshold < 0.0) return fail(MAV_ERR_ARG, "%s: threshold %g is negative or not finite", fn, p->threshold);
+    if (!(p->confidence > 0.0 && p->confidence < 1.0)) return fail(MAV_ERR_ARG, "%s: confidence %g outside (0, 1)", fn, p->confidence);
+    if (!std::isfinite(p->fx) || !std::isfinite(p->fy) || !(p->fx > 0.0) || !(p->fy > 0.0))
+        return fail(MAV_ERR_ARG, "%s: camera fx %g, fy %g: not finite or not positive", fn, p->fx, p->fy);
+    if (!std::isfinite(p->cx) || !std::isfinite(p->cy)) return fail(MAV_ERR_ARG, "%s: camera cx %g, cy %g: not finite", fn, p->cx, p->cy);
+    if (p->flags != 0) return fail(MAV_ERR_ARG, "%s: flags 0x%x: no flag is defined", fn, p->flags);
+    return MAV_OK;
+}
+extern "C" size_t mav_find_essential_workspace_bytes(int n, int batch, const mav_essential_params* p)
+{
+    if (batch < 1) { fail(MAV_ERR_ARG, "mav_find_essential_workspace_bytes: batch %d is less than 1", batch); return 0; }
+    if (essential_params_checked(n, p, "mav_find_essential_workspace_bytes") != MAV_OK) return 0;
+    return em_workspace_bytes(n, batch, p->max_iters);
+}
+// need[g], g = 0 .. n: RANSACUpdateNumIters(confidence, (n - g) / n, 5, max_iters) as the header writes it out
+static void essential_need_table(int n, double confidence, int max_iters, int32_t* need)
+{
+    const double ln = log(1.0 - confidence);
+    for (int g = 0; g <= n; g++) {
+        if (g < 5) { need[g] = max_iters; continue; }
+        const double w = (double)g / (double)n;
+        const double w2 = w * w;
+        const double den = 1.0 - (w2 * w2) * w;
+        if (den < DBL_MIN) { need[g] = 0; continue; }
+        const double ld = log(den);
+        need[g] = ld >= 0.0 || -ln >= max_iters * (-ld) ? max_iters : (int32_t)nearbyint(ln / ld);
+    }
+}
+// Everything a call can be refused for from its arguments alone, before the context is looked at.  a, b: src and dst, or flow and coords.
+static int essential_checked(mav_ctx* c, const void* a, const char* a_name, const void* b, const char* b_name, int n, int batch,
+                             const mav_essential_params* p, const int32_t* subsets, const double* E, const double* F, const uint8_t* inliers,
+                             const mav_essential_record* records, const char* fn)
+{
+    if (!c) return fail(MAV_ERR_ARG, "%s: NULL context", fn);
+    if (!a) return fail(MAV_ERR_ARG, "%s: NULL %s", fn, a_name);
+    if (!b) return fail(MAV_ERR_ARG, "%s: NULL %s", fn, b_name);
+    if (!subsets) return fail(MAV_ERR_ARG, "%s: NULL subsets", fn);
+    if (!E) return fail(MAV_ERR_ARG, "%s: NULL E", fn);
+    if (!F) return fail(MAV_ERR_ARG, "%s: NULL F", fn);
+    if (!inliers) return fail(MAV_ERR_ARG, "%s: NULL inliers", fn);
+    if (!records) return fail(MAV_ERR_ARG, "%s: NULL records", fn);
+    if (batch < 1) return fail(MAV_ERR_ARG, "%s: batch %d is less than 1", fn, batch);
+    return essential_params_checked(n, p, fn);
+}
+// what the _dev forms refuse beyond that: a's alignment is `a_align`, b's is checked where b is a device pointer (b_align != 0)
+static int essential_dev_checked(const void* a, const char* a_name, size_t a_align, const void* b, const char* b_name, size_t b_align, int n, int batch,
+                                 const mav_essential_params* p, const int32_t* subsets, const double* E, const double* F,
+                                 const mav_essential_record* records, const void* workspace, size_t workspace_bytes, const char* fn)
+{
+    if (!workspace) return fail(MAV_ERR_ARG, "%s: NULL workspace", fn);
+    if ((uintptr_t)a % a_align) return fail(MAV_ERR_ARG, "%s: %s is not aligned to %zu bytes", fn, a_name, a_align);
+    if (b_align && (uintptr_t)b % b_align) return fail(MAV_ERR_ARG, "%s: %s is not aligned to %zu bytes", fn, b_name, b_align);
+    if ((uintptr_t)subsets % 4) return fail(MAV_ERR_ARG, "%s: subsets is not aligned to its 4-byte elements", fn);
+    if ((uintptr_t)E % 8) return fail(MAV_ERR_ARG, "%s: E is not aligned to its 8-byte elements", fn);
+    if ((uintptr_t)F % 8) return fail(MAV_ERR_ARG, "%s: F is not aligned to its 8-byte elements", fn);
+    if ((uintptr_t)records % 16) return fail(MAV_ERR_ARG, "%s: records is not aligned to 16 bytes", fn);
+    if ((uintptr_t)workspace % 16) return fail(MAV_ERR_ARG, "%s: workspace is not aligned to 16 bytes", fn);
+    const size_t need = em_workspace_bytes(n, batch, p->max_iters);
+    if (workspace_bytes < need) return fail(MAV_ERR_ARG, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, need);
+    return MAV_OK;
+}
+// the host forms' subsets: every index inside [0, n), no index twice
+static int essential_subsets_checked(const int32_t* t, int n, int batch, int max_iters, const char* fn)
+{
+    for (size_t i = 0; i < (size_t)batch * max_iters; i++) {
+        const int32_t* q = t + 5 * i;
+        for (int j = 0; j < 5; j++) {
+            if (q[j] < 0 || q[j] >= n) return fail(MAV_ERR_ARG, "%s: subsets[%zu][%d] = %d outside [0, %d)", fn, i, j, q[j], n);
+            for (int k = 0; k < j; k++)
+                if (q[k] == q[j]) return fail(MAV_ERR_ARG, "%s: subsets[%zu] repeats the index %d", fn, i, q[j]);
+        }
+    }
+    return MAV_OK;
+}
+// the table's copy and the four launches
+static int essential_enqueue(mav_ctx* c, const double* src, const double* dst, int n, int batch, const mav_essential_params* p, const int32_t* subsets,
+                             double* E, double* F, uint8_t* inliers, mav_essential_record* records, void* workspace)
+{
+    std::vector<int32_t> need((size_t)n + 1);             // this call's own block: the copy below has taken its bytes when it returns
+    essential_need_table(n, p->confidence, p->max_iters, need.data());
+    HIPCHK(hipMemcpyAsync(workspace, need.data(), sizeof(int32_t) * need.size(), hipMemcpyHostToDevice, c->stream));
+    EmCall a;
+    a.src = src; a.dst = dst; a.subsets = subsets; a.E = E; a.F = F; a.inliers = inliers; a.records = records; a.ws = (char*)workspace;
+    a.n = n; a.B = batch; a.max_iters = p->max_iters;
+    const double t = p->threshold / ((p->fx + p->fy) / 2.0);
+    a.t2 = t * t; a.fx = p->fx; a.fy = p->fy; a.cx = p->cx; a.cy = p->cy;
+    { ProfScope ps(c, K_MISC); launch_em_models(c->stream, a); }
+    { ProfScope ps(c, K_MISC); launch_em_score(c->stream, a); }
+    { ProfScope ps(c, K_MISC); launch_em_choose(c->stream, a); }
+    { ProfScope ps(c, K_MISC); launch_em_finish(c->stream, a); }
+    return check_launch("essential fit");
+}
+extern "C" int mav_find_essential_dev(mav_ctx* c, const double* src, const double* dst, int n, int batch, const mav_essential_params* p,
+                                      const int32_t* subsets, double* E, double* F, uint8_t* inliers, mav_essential_record* records, void* workspace,
+                                      size_t workspace_bytes)
+{
+    const char* fn = "mav_find_essential_dev";
+    CHK(essential_checked(c, src, "src", dst, "dst", n, batch, p, subsets, E, F, inliers, records, fn));
+    CHK(essential_dev_checked(src, "src", 8, dst, "dst", 8, n, batch, p, subsets, E, F, records, workspace, workspace_bytes, fn));
+    CHK(check_dev_call(c, batch, fn));
+    return essential_enqueue(c, src, dst, n, batch, p, subsets, E, F, inliers, records, workspace);
+}
+extern "C" int mav_find_essential(mav_ctx* c, const double* src, const double* dst, int n, int batch, const mav_essential_params* p,
+                                  const int32_t* subsets, double* E, double* F, uint8_t* inliers, mav_essential_record* records)
+{
+    const char* fn = "mav_find_essential";
+    CHK(essential_checked(c, src, "src", dst, "dst", n, batch, p, subsets, E, F, inliers, records, fn));
+    CHK(essential_subsets_checked(subsets, n, batch, p->max_iters, fn));
+    HostCall h(c, fn);
+    CHK(h.beside(batch));
+    const size_t pairs = sizeof(double) * 2 * (size_t)n * batch, wsb = em_workspace_bytes(n, batch, p->max_iters);
+    const double *ds = h.in(src, pairs), *dd = h.in(dst, pairs);
+    const int32_t* dt = h.in(subsets, sizeof(int32_t) * 5 * (size_t)batch * p->max_iters);
+    char* dw = h.scratch<char>(wsb);
+    double* dE = h.out(E, sizeof(double) * 9 * batch);
+    double* dF = h.out(F, sizeof(double) * 9 * batch);
+    uint8_t* di = h.out(inliers, (size_t)batch * n);
+    mav_essential_record* dr = h.out(records, sizeof(mav_essential_record) * batch);
+    CHK(h.staged());
+    CHK(mav_find_essential_dev(c, ds, dd, n, batch, p, dt, dE, dF, di, dr, dw, wsb));
+    return h.finish();
+}
+extern "C" int mav_flow_essential_dev(mav_ctx* c, const float* flow, const int32_t* coords, int n, int batch, const mav_essential_params* p,
+                                      const int32_t* subsets, double* E, double* F, uint8_t* inliers, mav_essential_record* records, void* workspace,
+                                      size_t workspace_bytes)
+{
+    const char* fn = "mav_flow_essential_dev";
+    CHK(essential_checked(c, flow, "flow", coords, "coords", n, batch, p, subsets, E, F, inliers, records, fn));
+    CHK(essential_dev_checked(flow, "flow", 8, coords, "coords", 0, n, batch, p, subsets, E, F, records, workspace, workspace_bytes, fn));
+    CHK(check_dev_call(c, batch, fn));
+    CHK(affine_coords_checked(c, coords, n, fn));         // the affine flow form's range check of the host coords
+    char* ws = (char*)workspace;
+    int32_t* dcoords = (int32_t*)(ws + em_coords_offset(n, batch, p->max_iters));
+    double *ps = (double*)(ws + em_src_offset(n, batch, p->max_iters)), *pd = (double*)(ws + em_dst_offset(n, batch, p->max_iters));
+    HIPCHK(hipMemcpyAsync(dcoords, coords, sizeof(int32_t) * 2 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    { ProfScope ps_(c, K_MISC); launch_pair_gather(c->stream, flow, dcoords, n, batch, c->W, c->H, ps, pd); }
+    CHK(check_launch("pair_gather"));
+    return essential_enqueue(c, ps, pd, n, batch, p, subsets, E, F, inliers, records, workspace);
+}
+extern "C" int mav_flow_essential(mav_ctx* c, const float* flow, const int32_t* coords, int n, int batch, const mav_essential_params* p,
+                                  const int32_t* subsets, double* E, double* F, uint8_t* inliers, mav_essential_record* records, double* pairs_dst)
+{
+    const char* fn = "mav_flow_essential";
+    CHK(essential_checked(c, flow, "flow", coords, "coords", n, batch, p, subsets, E, F, inliers, records, fn));
+    CHK(essential_subsets_checked(subsets, n, batch, p->max_iters, fn));
+    HostCall h(c, fn);
+    CHK(h.beside(batch));
+    CHK(affine_coords_checked(c, coords, n, fn));
+    const size_t wsb = em_workspace_bytes(n, batch, p->max_iters);
+    const float* df = h.in(flow, c->n0 * batch * 2 * sizeof(float));
+    const int32_t* dt = h.in(subsets, sizeof(int32_t) * 5 * (size_t)batch * p->max_iters);
+    char* dw = h.scratch<char>(wsb);
+    double* dE = h.out(E, sizeof(double) * 9 * batch);
+    double* dF = h.out(F, sizeof(double) * 9 * batch);
+    uint8_t* di = h.out(inliers, (size_t)batch * n);
+    mav_essential_record* dr = h.out(records, sizeof(mav_essential_record) * batch);
+    if (dw) h.fetch(pairs_dst, dw + em_dst_offset(n, batch, p->max_iters), sizeof(double) * 2 * (size_t)n * batch);
+    CHK(h.staged());
+    CHK(mav_flow_essential_dev(c, df, coords, n, batch, p, dt, dE, dF, di, dr, dw, wsb));
+    return h.finish();
+}

@@ -494,3 +494,28 @@ void launch_fm_choose(hipStream_t st, const FmCall& a);
 void launch_fm_finish(hipStream_t st, const FmCall& a);
 // the dense pass: records' initialisation, the pass and the records' final form, three launches; residual and mask may be NULL
 void launch_epipolar_residual(hipStream_t st, const float* flow, const double* F, double t2, int W, int H, int B, float* residual, uint8_t* mask, void* records);
+
+// ---- robust essential-matrix fit (kernels_essential.hip, -ffp-contract=off; include/mavflow_essential.h) ----------------------------------
+// What one call works on, all device pointers.  The workspace layout follows from (n, B, max_iters) alone: need[] (n + 1 int32, filled by
+// the host's copy), the models (B, max_iters, EM_STRIDE) float64 (ten slots of nine, then two int32: slots with a root, mask of the valid
+// ones), the counts (B, max_iters, 10) int32 (-1: an invalid slot), the choice (B, 4) int32, then the flow form's coords (n, 2) int32 and
+// its gathered pairs, src and dst (B, n, 2) float64 each.
+#define EM_SLOTS 10
+#define EM_STRIDE 92
+struct EmCall {
+    const double *src, *dst; const int32_t* subsets; double *E, *F; uint8_t* inliers; void* records; char* ws;
+    int n, B, max_iters; double t2, fx, fy, cx, cy;
+};
+__host__ __device__ inline size_t em_round(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+__host__ __device__ inline size_t em_models_offset(int n) { return em_round(sizeof(int32_t) * ((size_t)n + 1)); }
+__host__ __device__ inline size_t em_counts_offset(int n, int B, int max_iters) { return em_models_offset(n) + em_round(sizeof(double) * EM_STRIDE * (size_t)B * max_iters); }
+__host__ __device__ inline size_t em_choice_offset(int n, int B, int max_iters) { return em_counts_offset(n, B, max_iters) + em_round(sizeof(int32_t) * EM_SLOTS * (size_t)B * max_iters); }
+__host__ __device__ inline size_t em_coords_offset(int n, int B, int max_iters) { return em_choice_offset(n, B, max_iters) + em_round(sizeof(int32_t) * 4 * (size_t)B); }
+__host__ __device__ inline size_t em_src_offset(int n, int B, int max_iters) { return em_coords_offset(n, B, max_iters) + em_round(sizeof(int32_t) * 2 * (size_t)n); }
+__host__ __device__ inline size_t em_dst_offset(int n, int B, int max_iters) { return em_src_offset(n, B, max_iters) + em_round(sizeof(double) * 2 * (size_t)n * B); }
+__host__ __device__ inline size_t em_workspace_bytes(int n, int B, int max_iters) { return em_dst_offset(n, B, max_iters) + em_round(sizeof(double) * 2 * (size_t)n * B); }
+// the four launches of a fit, in this order on one stream
+void launch_em_models(hipStream_t st, const EmCall& a);
+void launch_em_score(hipStream_t st, const EmCall& a);
+void launch_em_choose(hipStream_t st, const EmCall& a);
+void launch_em_finish(hipStream_t st, const EmCall& a);

@@ -1977,3 +1977,7 @@ from . import affine  # noqa: E402,F401
 # include/mavflow_fundamental.h (Context.find_fundamental, .flow_fundamental, .epipolar_residual, their *_enqueue twins and
 # .find_fundamental_workspace_bytes): likewise
 from . import fundamental  # noqa: E402,F401
+
+# include/mavflow_essential.h (Context.find_essential, .flow_essential, their *_enqueue twins and .find_essential_workspace_bytes):
+# likewise
+from . import essential  # noqa: E402,F401

@@ -4,7 +4,8 @@ branch (get_transformation_matrix for HOMOGRAPHY, flow_vec_subtract) of the refe
 from run_detection) and are refused by default: get_transformation_matrix says so.  The affine estimator runs with the caller's generator in
 .affine_rng (an extra; None: refused as before); flow_vec_subtract takes .aff, user-set as in the reference or set by that fit.  The
 fundamental-matrix estimator likewise runs with .fundamental_rng (an extra; None: refused as before) and gives epipolar_residual its
-matrix; the essential-matrix estimator (cv2's five-point solver, a different estimator) stays refused."""
+matrix; the essential-matrix estimator -- the reference's default -- runs with .essential_rng (an extra; None: refused as before) on
+Nister's five-point solver (include/mavflow_essential.h), sets .essential for get_rotation and gives epipolar_residual its matrix too."""
 from __future__ import annotations
 
 from enum import Enum
@@ -118,6 +119,8 @@ class Detector:
         self.affine_rng = None
         # an extra: the generator of the FUNDAMENTAL fit's sample subsets, likewise.  None: FUNDAMENTAL is refused as before
         self.fundamental_rng = None
+        # an extra: the generator of the ESSENTIAL fit's sample subsets, likewise.  None: ESSENTIAL is refused as before
+        self.essential_rng = None
         self.mag_handle = self.gray_handle = None    # flow_uv_warped_mag / one channel of to_rgb(magnitude) on the device, after a flow_vec_subtract of a device flow
 
     def get_gradient_and_magnitude(self, frame: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
@@ -236,12 +239,14 @@ class Detector:
         (Context.find_homography: not pinned against cv2).  Sets .homography (3x3 float64) and .confidence (the all-ones inlier mask,
         (n, 1) uint8); RuntimeError when the pairs determine no homography.  flow_uv: a host array or the flow seam's device handle.
         AFFINE with .affine_rng set: _affine_matrix (sets .aff and .aff_inliers); FUNDAMENTAL with .fundamental_rng set:
-        _fundamental_matrix (sets .fundamental and .fundamental_inliers); with the generator None either raises, as ESSENTIAL always
-        does."""
+        _fundamental_matrix (sets .fundamental and .fundamental_inliers); ESSENTIAL with .essential_rng set: _essential_matrix (sets
+        .essential, .essential_inliers and .essential_F); with its generator None each of the three raises."""
         A = Detector.Algorithm
         affine = self.algorithm == A.AFFINE and self.affine_rng is not None
         if self.algorithm == A.FUNDAMENTAL and self.fundamental_rng is not None:
             return self._fundamental_matrix(orig_frame, flow_uv)
+        if self.algorithm == A.ESSENTIAL and self.essential_rng is not None:
+            return self._essential_matrix(orig_frame, flow_uv)
         if self.algorithm in (A.AFFINE, A.FUNDAMENTAL, A.ESSENTIAL) and not affine:
             raise NotImplementedError(
                 f"{self.algorithm.name}: cv2.estimateAffine2D / findFundamentalMat / findEssentialMat are RANSAC estimators driven by "
@@ -345,12 +350,53 @@ class Detector:
         self.fundamental = fm.scaled(out["F"])
         self.fundamental_inliers = np.array(out["inliers"]).reshape(-1, 1)
 
+    def _essential_matrix(self, orig_frame: np.ndarray, flow_uv: np.ndarray) -> None:
+        """detector.py:147-151 with .essential_rng set (an extra): cv2.findEssentialMat(coords_old, coords_new, self.focal_length,
+        (0, 0), cv2.FM_RANSAC, 0.999, 1.0)'s RANSAC fit on the device (include/mavflow_essential.h: Nister's five-point solver, not pinned
+        against cv2), the sample subsets drawn from .essential_rng by essential.sample_subsets, on the same pair sources as FUNDAMENTAL.
+        The reference's literal arguments are kept: the focal length 1 / tan(fov / 2) and the principal point (0, 0) on pixel
+        coordinates, prob 0.999, threshold 1.0.  Sets .essential (3x3 float64 of unit Frobenius norm), .essential_inliers ((n, 1) uint8)
+        and .essential_F (K^-T E K^-1, what epipolar_residual reads); RuntimeError when no valid model had more than four inliers."""
+        W, H = self.dataset.capture_size[0], self.dataset.capture_size[1]
+        f = float(self.focal_length)
+        kw = dict(threshold=1.0, confidence=0.999, rng=self.essential_rng, camera=(f, f, 0.0, 0.0))
+        pairs = None
+        if self.use_sparse_of:
+            old, new, _ = self.lucas_kanade.get_features(orig_frame)
+            if len(old) > 0 and len(new) > 0:
+                pairs = (np.asarray(old, np.float64), np.asarray(new, np.float64))
+        dev = None if pairs is not None else self._device_flow(flow_uv)
+        if pairs is not None:
+            out = im_helpers._ctx(W, H).find_essential(*pairs, **kw)
+        elif dev is not None:
+            out = dev[0].flow_essential(flow_uv, self.coords, **kw)                     # the field is read where it is
+        else:
+            flow = np.asarray(flow_uv)
+            if flow.dtype == np.float32:
+                out = im_helpers._ctx(W, H).flow_essential(flow, self.coords, **kw)
+            else:                                       # a float64 field keeps its precision: the reference's own pair arithmetic
+                new = self.coords.astype(np.float64) + flow[self.sample_y, self.sample_x]
+                out = im_helpers._ctx(W, H).find_essential(self.coords.astype(np.float64), new, **kw)
+        if not out["ok"]:
+            raise RuntimeError("get_transformation_matrix: the point pairs do not determine an essential matrix")
+        self.essential = np.array(out["E"])
+        self.essential_inliers = np.array(out["inliers"]).reshape(-1, 1)
+        self.essential_F = np.array(out["F"])
+
+    def get_rotation(self, flow_uv: np.ndarray, use_fundamental: bool = True) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """detector.py:65-68: (euler(R1), euler(R2), t) of .essential's decomposition (essential.decomposeEssentialMat on the host: R1's
+        and R2's order and t's sign are not pinned against cv2), the Euler angles in degrees by utils.rotation_matrix_to_euler; t is
+        (3, 1).  Both arguments are ignored, as in the reference."""
+        from . import essential as em
+        R1, R2, t = em.decomposeEssentialMat(self.essential)
+        return utils.rotation_matrix_to_euler(R1), utils.rotation_matrix_to_euler(R2), t
+
     def epipolar_residual(self, flow_uv, threshold: float = 1.0) -> Tuple[np.ndarray, np.ndarray]:
         """An extra: (residual (H, W) float32, mask (H, W) uint8 0/255) of the dense epipolar residual of flow_uv under .fundamental
-        (Context.epipolar_residual): per pixel the distance of p + flow(p) from the epipolar line of p; the mask marks what moves off its
+        (for ESSENTIAL: under .essential_F, the fitted essential matrix in pixel coordinates) (Context.epipolar_residual): per pixel the distance of p + flow(p) from the epipolar line of p; the mask marks what moves off its
         line by more than `threshold` pixels -- an independent mover, whatever the scene's depth.  flow_uv: a float32 host array or the
         flow seam's device handle, on whose context the pass runs."""
-        Fm = np.asarray(self.fundamental, np.float64)
+        Fm = np.asarray(self.essential_F if self.algorithm == Detector.Algorithm.ESSENTIAL else self.fundamental, np.float64)
         dev = self._device_flow(flow_uv)
         if dev is not None:
             out = dev[0].epipolar_residual(flow_uv, Fm, threshold)

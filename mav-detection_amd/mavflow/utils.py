@@ -135,6 +135,27 @@ def write_flow(filename: str, uv: np.ndarray, v: np.ndarray = None) -> None:
         np.stack([u, v], axis=-1).astype(np.float32).tofile(f)
 
 
+def is_rotation_matrix(R: np.ndarray) -> bool:
+    """utils.py:305-318: whether R^T R is within 1e-6 (Frobenius norm) of the identity; pinned to the reference bit for bit
+    (tests/golden/euler.npz)."""
+    R = np.asarray(R)
+    return bool(np.linalg.norm(np.identity(3, dtype=R.dtype) - np.dot(np.transpose(R), R)) < 1e-6)
+
+
+def rotation_matrix_to_euler(R: np.ndarray) -> np.ndarray:
+    """utils.py:321-347: the Euler angles (x, y, z) in degrees of a rotation matrix, z = 0 on the singular branch
+    (sqrt(R00^2 + R10^2) < 1e-6); AssertionError when R is no rotation matrix.  Pinned to the reference bit for bit
+    (tests/golden/euler.npz)."""
+    R = np.asarray(R)
+    assert is_rotation_matrix(R)
+    sy = np.sqrt(R[0, 0] * R[0, 0] + R[1, 0] * R[1, 0])
+    if sy < 1e-6:
+        angles = [np.arctan2(-R[1, 2], R[1, 1]), np.arctan2(-R[2, 0], sy), 0]
+    else:
+        angles = [np.arctan2(R[2, 1], R[2, 2]), np.arctan2(-R[2, 0], sy), np.arctan2(R[1, 0], R[0, 0])]
+    return np.rad2deg(np.array(angles))
+
+
 def get_json(obj: Dict[str, Any]) -> Dict[str, Any]:
     """JSON-safe dictionary; anything json cannot encode becomes its __dict__ or its str() (numpy ints -> strings)."""
     return json.loads(json.dumps(obj, default=lambda o: getattr(o, "__dict__", str(o))))
