@@ -9,48 +9,9 @@
 #include <cstdint>
 
 #include "mavflow_internal.h"
+#include "resize_area.h"
 
-// ---- cv2.resize(INTER_AREA), non-integer ratio: computeResizeAreaTab + resizeArea_<T, float> (resize.cpp) ------------
-// One destination index d of one axis covers source cells [d*scale, d*scale + scale): an optional partial first cell
-// (s1 - 1, weight wf), whole cells s1 .. s2-1 (weight wm each) and an optional partial last cell (s2, weight wl).
-struct AreaSpan { int s1, s2; float wf, wm, wl; bool first, last; };
-__device__ __forceinline__ AreaSpan area_span(int d, double scale, int ssize)
-{
-    AreaSpan a;
-    const double f1 = d * scale, f2 = f1 + scale;
-    const double cell = fmin(scale, (double)ssize - f1);
-    int s1 = (int)ceil(f1), s2 = (int)floor(f2);
-    s2 = s2 < ssize - 1 ? s2 : ssize - 1;
-    s1 = s1 < s2 ? s1 : s2;
-    a.s1 = s1; a.s2 = s2;
-    a.first = (double)s1 - f1 > 1e-3;
-    a.last = f2 - (double)s2 > 1e-3;
-    a.wf = (float)(((double)s1 - f1) / cell);
-    a.wm = (float)(1.0 / cell);
-    a.wl = (float)(fmin(fmin(f2 - (double)s2, 1.0), cell) / cell);
-    return a;
-}
-// channel c of one source row of CN interleaved channels (resizeArea_ keeps one float accumulator per channel: the same sum per channel)
-template <int CN, typename T>
-__device__ __forceinline__ float area_row(const T* __restrict__ S, const AreaSpan& x, int c = 0)
-{
-    float buf = 0.f;                                   // buf[dx] += S[si] * alpha, in tab order
-    if (x.first) buf = buf + (float)S[(size_t)(x.s1 - 1) * CN + c] * x.wf;
-    for (int sx = x.s1; sx < x.s2; sx++) buf = buf + (float)S[(size_t)sx * CN + c] * x.wm;
-    if (x.last) buf = buf + (float)S[(size_t)x.s2 * CN + c] * x.wl;
-    return buf;
-}
-// rows in tab order: sum[dx] += beta * buf[dx]; S = channel plane origin, row pitch sw * CN elements
-template <int CN, typename T>
-__device__ __forceinline__ float area_general(const T* __restrict__ S, int sw, const AreaSpan& x, const AreaSpan& y, int c = 0)
-{
-    const size_t pitch = (size_t)sw * CN;
-    float sum = 0.f;
-    if (y.first) sum = sum + y.wf * area_row<CN>(S + (size_t)(y.s1 - 1) * pitch, x, c);
-    for (int sy = y.s1; sy < y.s2; sy++) sum = sum + y.wm * area_row<CN>(S + (size_t)sy * pitch, x, c);
-    if (y.last) sum = sum + y.wl * area_row<CN>(S + (size_t)y.s2 * pitch, x, c);
-    return sum;
-}
+// ---- cv2.resize(INTER_AREA), non-integer ratio: area_span / area_row / area_general of resize_area.h (shared with kernels_resize.hip) ----
 __global__ __launch_bounds__(256) void k_area_resize(const uint8_t* __restrict__ src, size_t src_stride, int sw, int sh,
                                                      uint8_t* __restrict__ dst, size_t dst_stride, int dw, int dh,
                                                      double scale_x, double scale_y)
@@ -94,18 +55,9 @@ __global__ __launch_bounds__(256) void k_area_resize_flow(const float* __restric
         const float2 p = *(const float2*)(S + ((size_t)dy * sw + dx) * 2);
         v[0] = p.x; v[1] = p.y;
     } else if (FORM == AREA_FAST) {
-        const int area = ix * iy;
-        const float inv = 1.f / (float)area;
         const float* B = S + ((size_t)dy * iy * sw + (size_t)dx * ix) * 2;
-        auto at = [&](int k, int c) { return B[((size_t)(k / ix) * sw + (k % ix)) * 2 + c]; };
-#pragma unroll
-        for (int c = 0; c < 2; c++) {
-            float sum = 0.f;
-            int k = 0;
-            for (; k <= area - 4; k += 4) sum = sum + (((at(k, c) + at(k + 1, c)) + at(k + 2, c)) + at(k + 3, c));
-            for (; k < area; k++) sum = sum + at(k, c);
-            v[c] = sum * inv;
-        }
+        v[0] = area_fast_f32<2>(B, sw, ix, iy);
+        v[1] = area_fast_f32<2>(B + 1, sw, ix, iy);
     } else {
         const AreaSpan x = area_span(dx, scale_x, sw), y = area_span(dy, scale_y, sh);
         v[0] = area_general<2>(S, sw, x, y, 0);

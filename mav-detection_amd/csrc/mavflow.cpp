@@ -4958,6 +4958,106 @@ extern "C" int mav_warp_method(mav_ctx* c, const float* flow, const double* M, i
     return h.finish();
 }
 
+// ---- image resize (include/mavflow_resize.h) ------------------------------------------------------------------------------------------------
+// Like the warps these keep every kind of resident state and hold no device memory of the context's: the _dev forms work on the caller's
+// blocks alone and allocate nothing, the host forms in staging blocks behind the last call's (HostCall::beside).
+#include "../../include/mavflow_resize.h"
+
+// Everything a resize can be refused for from its arguments alone, before the context is looked at.  px_src / px_dst: bytes per pixel.
+static int resize_checked(mav_ctx* c, const void* src, const char* src_name, size_t px_src, int sw, int sh, int dw, int dh, int batch, const void* dst,
+                          const char* dst_name, size_t px_dst, const char* fn)
+{
+    if (!c) return fail(MAV_ERR_ARG, "%s: NULL context", fn);
+    if (!src) return fail(MAV_ERR_ARG, "%s: NULL %s", fn, src_name);
+    if (!dst) return fail(MAV_ERR_ARG, "%s: NULL %s", fn, dst_name);
+    const int sides[4] = {sw, sh, dw, dh};
+    const char* names[4] = {"sw", "sh", "dw", "dh"};
+    for (int i = 0; i < 4; i++)
+        if (sides[i] < 1 || sides[i] > MAV_RESIZE_MAX_SIDE) return fail(MAV_ERR_ARG, "%s: %s %d outside [1, %d]", fn, names[i], sides[i], MAV_RESIZE_MAX_SIDE);
+    if (batch < 1) return fail(MAV_ERR_ARG, "%s: batch %d is less than 1", fn, batch);
+    const uintptr_t s0 = (uintptr_t)src, s1 = s0 + (size_t)batch * sw * sh * px_src, d0 = (uintptr_t)dst, d1 = d0 + (size_t)batch * dw * dh * px_dst;
+    if (s0 < d1 && d0 < s1) return fail(MAV_ERR_ARG, "%s: %s and %s overlap", fn, src_name, dst_name);
+    return MAV_OK;
+}
+static int resize_call_checked(mav_ctx* c, const void* src, int format, int sw, int sh, int dw, int dh, int interpolation, int batch, const void* dst, bool dev,
+                               const char* fn)
+{
+    if (!c) return fail(MAV_ERR_ARG, "%s: NULL context", fn);
+    if (!warp_px_bytes(format)) return fail(MAV_ERR_ARG, "%s: format %d is none of MAV_WARP_U8C1, _U8C3, _F32C1, _F32C2", fn, format);
+    if (interpolation != MAV_INTER_NEAREST && interpolation != MAV_INTER_LINEAR && interpolation != MAV_INTER_AREA)
+        return fail(MAV_ERR_ARG, "%s: interpolation %d is none of MAV_INTER_NEAREST, _LINEAR, _AREA", fn, interpolation);
+    CHK(resize_checked(c, src, "src", warp_px_bytes(format), sw, sh, dw, dh, batch, dst, "dst", warp_px_bytes(format), fn));
+    if (interpolation == MAV_INTER_AREA && (dw > sw || dh > sh))
+        return fail(MAV_ERR_ARG, "%s: MAV_INTER_AREA enlarging (%d x %d -> %d x %d) is not built", fn, sw, sh, dw, dh);
+    if (dev && (format == MAV_WARP_F32C1 || format == MAV_WARP_F32C2)) {
+        if ((uintptr_t)src % 4) return fail(MAV_ERR_ARG, "%s: src is not aligned to its 4-byte elements", fn);
+        if ((uintptr_t)dst % 4) return fail(MAV_ERR_ARG, "%s: dst is not aligned to its 4-byte elements", fn);
+    }
+    return MAV_OK;
+}
+static int sky_mask_checked(mav_ctx* c, const uint8_t* pred_bgr, int sw, int sh, int dw, int dh, int key0, int key1, int batch, const uint8_t* sky, const char* fn)
+{
+    CHK(resize_checked(c, pred_bgr, "pred_bgr", 3, sw, sh, dw, dh, batch, sky, "sky", 1, fn));
+    if (key0 < 0 || key0 > 255) return fail(MAV_ERR_ARG, "%s: key0 %d outside [0, 255]", fn, key0);
+    if (key1 < 0 || key1 > 255) return fail(MAV_ERR_ARG, "%s: key1 %d outside [0, 255]", fn, key1);
+    return MAV_OK;
+}
+extern "C" int mav_resize_dev(mav_ctx* c, const void* src, int format, int sw, int sh, int dw, int dh, int interpolation, int batch, void* dst)
+{
+    const char* fn = "mav_resize_dev";
+    CHK(resize_call_checked(c, src, format, sw, sh, dw, dh, interpolation, batch, dst, true, fn));
+    CHK(check_dev_call(c, batch, fn));
+    {
+        ProfScope ps(c, K_MISC);
+        launch_resize(c->stream, format, src, sw, sh, dw, dh, interpolation, batch, dst);
+    }
+    return check_launch("resize");
+}
+extern "C" int mav_resize(mav_ctx* c, const void* src, int format, int sw, int sh, int dw, int dh, int interpolation, int batch, void* dst)
+{
+    const char* fn = "mav_resize";
+    CHK(resize_call_checked(c, src, format, sw, sh, dw, dh, interpolation, batch, dst, false, fn));
+    HostCall h(c, fn);
+    CHK(h.beside(batch));
+    const size_t px = warp_px_bytes(format);
+    const char* ds = h.in((const char*)src, (size_t)batch * sw * sh * px);
+    char* dd = h.out((char*)dst, (size_t)batch * dw * dh * px);
+    CHK(h.staged());
+    {
+        ProfScope ps(c, K_MISC);
+        launch_resize(c->stream, format, ds, sw, sh, dw, dh, interpolation, batch, dd);
+    }
+    CHK(check_launch("resize"));
+    return h.finish();
+}
+extern "C" int mav_sky_mask_dev(mav_ctx* c, const uint8_t* pred_bgr, int sw, int sh, int dw, int dh, int key0, int key1, int batch, uint8_t* sky)
+{
+    const char* fn = "mav_sky_mask_dev";
+    CHK(sky_mask_checked(c, pred_bgr, sw, sh, dw, dh, key0, key1, batch, sky, fn));
+    CHK(check_dev_call(c, batch, fn));
+    {
+        ProfScope ps(c, K_MISC);
+        launch_sky_mask(c->stream, pred_bgr, sw, sh, dw, dh, key0, key1, batch, sky);
+    }
+    return check_launch("sky mask");
+}
+extern "C" int mav_sky_mask(mav_ctx* c, const uint8_t* pred_bgr, int sw, int sh, int dw, int dh, int key0, int key1, int batch, uint8_t* sky)
+{
+    const char* fn = "mav_sky_mask";
+    CHK(sky_mask_checked(c, pred_bgr, sw, sh, dw, dh, key0, key1, batch, sky, fn));
+    HostCall h(c, fn);
+    CHK(h.beside(batch));
+    const uint8_t* dp = h.in(pred_bgr, (size_t)batch * sw * sh * 3);
+    uint8_t* dk = h.out(sky, (size_t)batch * dw * dh);
+    CHK(h.staged());
+    {
+        ProfScope ps(c, K_MISC);
+        launch_sky_mask(c->stream, dp, sw, sh, dw, dh, key0, key1, batch, dk);
+    }
+    CHK(check_launch("sky mask"));
+    return h.finish();
+}
+
 // ---- robust affine fit (include/mavflow_affine.h) -------------------------------------------------------------------------------------------
 // Like the warps these keep every kind of resident state and hold no device memory of the context's: the _dev forms work in the caller's
 // workspace (the flow form's gathered pairs included), the host forms in staging blocks behind the last call's (HostCall::beside).

@@ -450,6 +450,16 @@ void launch_warp(hipStream_t st, int policy, int format, const void* src, const 
 // Detector.warp_method: records' initialisation, the pass and the records' final form, three launches; diff and mag may be NULL
 void launch_warp_method(hipStream_t st, int policy, const float* flow, const double* M, int W, int H, int B, float* diff, float* mag, void* records);
 
+// ---- image resize (kernels_resize.hip, compiled with -ffp-contract=off; include/mavflow_resize.h) ------------------------------------------
+// the forms of the one body, as cv::resize's dispatch picks them (RS_AREA_2X2: uint8 alone)
+enum { RS_COPY, RS_NEAREST, RS_LINEAR, RS_AREA_2X2, RS_AREA_FAST, RS_AREA_GENERAL };
+int resize_form(int format, int sw, int sh, int dw, int dh, int interpolation, int* ix, int* iy);
+bool resize_vector_stores(int format, int dw, const void* dst, bool sky);
+// B images of sw x sh in `format` (MAV_WARP_*) -> dw x dh, one launch
+void launch_resize(hipStream_t st, int format, const void* src, int sw, int sh, int dw, int dh, int interpolation, int B, void* dst);
+// resize(U8C3, INTER_LINEAR) + key in one launch: sky (B, dh, dw) uint8, 1 where channels 0 and 1 equal the keys
+void launch_sky_mask(hipStream_t st, const uint8_t* pred_bgr, int sw, int sh, int dw, int dh, int key0, int key1, int B, uint8_t* sky);
+
 // ---- robust affine fit (kernels_affine.hip, compiled with -ffp-contract=off; include/mavflow_affine.h) ------------------------------------
 // What one call works on, all device pointers.  The workspace layout follows from (n, B, max_iters) alone: need[] (n + 1 int32, filled by
 // the host's copy), the counts (B, max_iters) int32 (-1: an invalid hypothesis), the choice (B, 4) int32, then the flow form's coords

@@ -184,7 +184,16 @@ def add_weighted(src1: np.ndarray, alpha: float, src2: np.ndarray, beta: float, 
     return np.clip(np.rint(a + np.float32(gamma)), 0, 255).astype(np.uint8)
 
 
-def pyramid(image: np.ndarray, scale: float = 1.5, minSize: Tuple[int, int] = (30, 30)) -> Iterator[np.ndarray]:
+def resize_percent(img: np.ndarray, scale_percent: float) -> np.ndarray:
+    """The reference's helper (:254-260): cv2.resize(img, (int(w * p / 100), int(h * p / 100)), interpolation=INTER_AREA) on the device
+    (mavflow.resize; include/mavflow_resize.h has the arithmetic).  The half-resolution images HRNet reads are resize_percent(img, 50)."""
+    from . import resize as _resize
+    width = int(img.shape[1] * scale_percent / 100)
+    height = int(img.shape[0] * scale_percent / 100)
+    return _resize.resize(img, (width, height), interpolation=_resize.INTER_AREA)
+
+
+def pyramid(image: np.ndarray, scale: float = 1.5,minSize: Tuple[int, int] = (30, 30)) -> Iterator[np.ndarray]:
     """Every level of the reference's generator (:12-35): the image itself, then imutils.resize(previous, width=int(w / scale))
     = cv2.resize(INTER_AREA) until a side drops below minSize.  Levels >= 1 come from the device (mav_stage_pyramid_level, the
     same cascade Detector.analyze_pyramid scans), so iterating pyramid() + sliding_window() as the reference does sees exactly
