@@ -5628,3 +5628,135 @@ extern "C" int mav_flow_essential(mav_ctx* c, const float* flow, const int32_t* 
     CHK(mav_flow_essential_dev(c, df, coords, n, batch, p, dt, dE, dF, di, dr, dw, wsb));
     return h.finish();
 }
+
+// ---- flow pictures (include/mavflow_vis.h) -------------------------------------------------------------------------------------------------
+// Like the warps and the resizes these keep every kind of resident state and hold no device memory of the context's: the _dev forms work
+// on the caller's blocks alone (the record block is the minimum / maximum pass's scratch) and allocate nothing, the host forms in staging
+// blocks behind the last call's (HostCall::beside).
+#include "../../include/mavflow_vis.h"
+
+extern "C" int mav_vis_form(int W, int H, int batch, const void* flow, const void* bgr, const void* hsv) { return vis_form(W, H, batch, flow, bgr, hsv); }
+
+// What every call of the family is refused for before the context's device is looked at; a, b: the two pointers every call needs.
+static int vis_checked(mav_ctx* c, const void* a, const char* a_name, const void* b, const char* b_name, int batch, const char* fn)
+{
+    if (!c) return fail(MAV_ERR_ARG, "%s: NULL context", fn);
+    if (!a) return fail(MAV_ERR_ARG, "%s: NULL %s", fn, a_name);
+    if (!b) return fail(MAV_ERR_ARG, "%s: NULL %s", fn, b_name);
+    if (batch < 1 || batch > c->max_batch) return fail(MAV_ERR_ARG, "%s: batch %d outside [1, %d]", fn, batch, c->max_batch);
+    if ((uint64_t)c->n0 * (uint64_t)batch > 0x7FFFFFFFull) return fail(MAV_ERR_ARG, "%s: %d images of %d x %d are more than 2^31 - 1 pixels", fn, batch, c->W, c->H);
+    return MAV_OK;
+}
+static int flow_hsv_checked(mav_ctx* c, const float* flow, int batch, int mode, const uint8_t* bgr, const mav_hsv_record* records, bool dev, const char* fn)
+{
+    CHK(vis_checked(c, flow, "flow", bgr, "bgr", batch, fn));
+    if (!records) return fail(MAV_ERR_ARG, "%s: NULL records", fn);
+    if (mode != MAV_HSV_PROCESS && mode != MAV_HSV_DRAW) return fail(MAV_ERR_ARG, "%s: mode %d is neither MAV_HSV_PROCESS nor MAV_HSV_DRAW", fn, mode);
+    if (dev && (uintptr_t)flow % 4) return fail(MAV_ERR_ARG, "%s: flow is not aligned to its 4-byte elements", fn);
+    if (dev && (uintptr_t)records % 4) return fail(MAV_ERR_ARG, "%s: records is not aligned to 4", fn);
+    return MAV_OK;
+}
+extern "C" int mav_flow_hsv_dev(mav_ctx* c, const float* flow, int batch, int mode, uint8_t* bgr, uint8_t* hsv, mav_hsv_record* records)
+{
+    const char* fn = "mav_flow_hsv_dev";
+    CHK(flow_hsv_checked(c, flow, batch, mode, bgr, records, true, fn));
+    CHK(check_dev_call(c, batch, fn));
+    {
+        ProfScope ps(c, K_MISC);
+        const hipError_t e = launch_flow_hsv(c->stream, flow, c->W, c->H, batch, mode, bgr, hsv, records);
+        if (e != hipSuccess) return fail(MAV_ERR_HIP, "%s: zeroing the records failed: %s", fn, hipGetErrorString(e));
+    }
+    return check_launch("flow_hsv");
+}
+extern "C" int mav_flow_hsv(mav_ctx* c, const float* flow, int batch, int mode, uint8_t* bgr, uint8_t* hsv, mav_hsv_record* records)
+{
+    const char* fn = "mav_flow_hsv";
+    CHK(flow_hsv_checked(c, flow, batch, mode, bgr, records, false, fn));
+    HostCall h(c, fn);
+    CHK(h.beside(batch));
+    const size_t n = c->n0 * batch;
+    const float* df = h.in(flow, n * 2 * sizeof(float));
+    uint8_t* db = h.out(bgr, n * 3);
+    uint8_t* dh = h.out(hsv, n * 3);
+    mav_hsv_record* dr = h.out(records, sizeof(mav_hsv_record) * batch);
+    CHK(h.staged());
+    {
+        ProfScope ps(c, K_MISC);
+        const hipError_t e = launch_flow_hsv(c->stream, df, c->W, c->H, batch, mode, db, dh, dr);
+        if (e != hipSuccess) return fail(MAV_ERR_HIP, "%s: zeroing the records failed: %s", fn, hipGetErrorString(e));
+    }
+    CHK(check_launch("flow_hsv"));
+    return h.finish();
+}
+static int cvt_color_checked(mav_ctx* c, const uint8_t* src, int code, int batch, const uint8_t* dst, const char* fn)
+{
+    CHK(vis_checked(c, src, "src", dst, "dst", batch, fn));
+    if (code != MAV_COLOR_HSV2BGR && code != MAV_COLOR_BGR2HSV && code != MAV_COLOR_BGR2RADIAL)
+        return fail(MAV_ERR_ARG, "%s: code %d is none of MAV_COLOR_HSV2BGR, MAV_COLOR_BGR2HSV, MAV_COLOR_BGR2RADIAL", fn, code);
+    return MAV_OK;
+}
+extern "C" int mav_cvt_color_dev(mav_ctx* c, const uint8_t* src, int code, int batch, uint8_t* dst)
+{
+    const char* fn = "mav_cvt_color_dev";
+    CHK(cvt_color_checked(c, src, code, batch, dst, fn));
+    CHK(check_dev_call(c, batch, fn));
+    {
+        ProfScope ps(c, K_MISC);
+        launch_cvt_color(c->stream, src, code, c->W, c->H, batch, dst);
+    }
+    return check_launch("cvt_color");
+}
+extern "C" int mav_cvt_color(mav_ctx* c, const uint8_t* src, int code, int batch, uint8_t* dst)
+{
+    const char* fn = "mav_cvt_color";
+    CHK(cvt_color_checked(c, src, code, batch, dst, fn));
+    HostCall h(c, fn);
+    CHK(h.beside(batch));
+    const size_t n = c->n0 * batch * 3;
+    const uint8_t* ds = h.in(src, n);
+    uint8_t* dd = h.out(dst, n);
+    CHK(h.staged());
+    {
+        ProfScope ps(c, K_MISC);
+        launch_cvt_color(c->stream, ds, code, c->W, c->H, batch, dd);
+    }
+    CHK(check_launch("cvt_color"));
+    return h.finish();
+}
+static int draw_flow_checked(mav_ctx* c, const uint8_t* img, const float* flow, int batch, int step, const uint8_t* colour, bool dev, const char* fn)
+{
+    CHK(vis_checked(c, img, "img", flow, "flow", batch, fn));
+    if (!colour) return fail(MAV_ERR_ARG, "%s: NULL bgr_colour", fn);
+    if (step < 1) return fail(MAV_ERR_ARG, "%s: step %d is less than 1", fn, step);
+    if (dev && (uintptr_t)flow % 4) return fail(MAV_ERR_ARG, "%s: flow is not aligned to its 4-byte elements", fn);
+    return MAV_OK;
+}
+extern "C" int mav_draw_flow_dev(mav_ctx* c, uint8_t* img, const float* flow, int batch, int step, float threshold, const uint8_t* bgr_colour)
+{
+    const char* fn = "mav_draw_flow_dev";
+    CHK(draw_flow_checked(c, img, flow, batch, step, bgr_colour, true, fn));
+    CHK(check_dev_call(c, batch, fn));
+    {
+        ProfScope ps(c, K_MISC);
+        launch_draw_flow(c->stream, img, flow, c->W, c->H, batch, step, threshold, bgr_colour);
+    }
+    return check_launch("draw_flow");
+}
+extern "C" int mav_draw_flow(mav_ctx* c, uint8_t* img, const float* flow, int batch, int step, float threshold, const uint8_t* bgr_colour)
+{
+    const char* fn = "mav_draw_flow";
+    CHK(draw_flow_checked(c, img, flow, batch, step, bgr_colour, false, fn));
+    HostCall h(c, fn);
+    CHK(h.beside(batch));
+    const size_t n = c->n0 * batch;
+    uint8_t* di = h.in(img, n * 3);                           // drawn into on the device, and brought back
+    const float* df = h.in(flow, n * 2 * sizeof(float));
+    h.fetch(img, di, n * 3);
+    CHK(h.staged());
+    {
+        ProfScope ps(c, K_MISC);
+        launch_draw_flow(c->stream, di, df, c->W, c->H, batch, step, threshold, bgr_colour);
+    }
+    CHK(check_launch("draw_flow"));
+    return h.finish();
+}

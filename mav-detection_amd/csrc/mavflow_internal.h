@@ -529,3 +529,17 @@ void launch_em_models(hipStream_t st, const EmCall& a);
 void launch_em_score(hipStream_t st, const EmCall& a);
 void launch_em_choose(hipStream_t st, const EmCall& a);
 void launch_em_finish(hipStream_t st, const EmCall& a);
+
+// ---- flow pictures (kernels_vis.hip, compiled with -ffp-contract=off; include/mavflow_vis.h) -----------------------------------------------
+// MAV_VIS_FORM_* of a call's sizes and pointers (NULL pointers constrain nothing); -1 for a size below 1
+int vis_form(int W, int H, int batch, const void* flow, const void* bgr, const void* hsv);
+// the grid points of draw_flow along each axis
+void vis_draw_grid(int W, int H, int step, int* nx, int* ny);
+// flow (B, H, W, 2) -> bgr and (unless NULL) hsv (B, H, W, 3); records: B mav_hsv_record, the call's only scratch.  MAV_HSV_PROCESS: the
+// records' initialisation, the minimum / maximum pass and the picture, three launches; MAV_HSV_DRAW: the records zeroed and one launch.
+// Returns the error of zeroing the records, if any (nothing is launched then).
+hipError_t launch_flow_hsv(hipStream_t st, const float* flow, int W, int H, int B, int mode, uint8_t* bgr, uint8_t* hsv, void* records);
+// src, dst (B, H, W, 3) uint8, code MAV_COLOR_*; one launch
+void launch_cvt_color(hipStream_t st, const uint8_t* src, int code, int W, int H, int B, uint8_t* dst);
+// img (B, H, W, 3) drawn into; colour: three bytes on the host; one launch (none where the grid is empty)
+void launch_draw_flow(hipStream_t st, uint8_t* img, const float* flow, int W, int H, int B, int step, float threshold, const uint8_t* colour);

@@ -92,7 +92,16 @@ def calcOpticalFlowFarneback(prev, next, flow, pyr_scale, levels, winsize, itera
 class Farneback:
     PARAMS = dict(pyr_scale=0.4, levels=1, winsize=12, iterations=10, poly_n=8, poly_sigma=1.2, flags=0)
 
-    def __init__(self, capture, output=None) -> None:
+    def __init__(self, capture, output=None, vis: str = "host") -> None:
+        """vis="host": the picture is composed in numpy (flow_to_hsv, hsv_to_bgr), the field comes to the host every frame.
+        vis="device": process() hands the frame to a pipeline.FlowStage of the context (gray conversion, prevgray and the flow stay on the
+        device) and mav_flow_hsv_dev builds the picture where the flow is: one frame goes up, the picture and its 16-byte record come down."""
+        if vis not in ("host", "device"):
+            raise ValueError(f"vis must be 'host' or 'device', got {vis!r}")
+        if vis == "device" and self.PARAMS["flags"] & _lib.OPTFLOW_USE_INITIAL_FLOW:
+            raise NotImplementedError("vis='device' with OPTFLOW_USE_INITIAL_FLOW in PARAMS['flags'] is not built: the device path's "
+                                      "pipeline.FlowStage has no warm start; use vis='host'")
+        self.vis = vis
         self.capture = capture
         self.output = output
         _, prev = self.capture.read()
@@ -108,16 +117,18 @@ class Farneback:
         self.flow = np.zeros((H, W, 2), np.float32)
         self.history_length = 1
         self.prev_result = np.zeros((H, W, 3), np.uint8)
+        if vis == "device":
+            self._device_init(prev)
 
     @classmethod
-    def from_png_sequence(cls, img_path: str, img_format: str = "image_%05d.png", output=None) -> "Farneback":
+    def from_png_sequence(cls, img_path: str, img_format: str = "image_%05d.png", output=None, vis: str = "host") -> "Farneback":
         """Farneback(cv2.VideoCapture(f'{img_path}/image_%05d.png'), output) with the capture this build provides for PNG sequences
         (frame_source.PngSequenceCapture; src/datasets/dataset.py:38,57)."""
         from .frame_source import PngSequenceCapture
         cap = PngSequenceCapture(f"{img_path}/{img_format}")
         if not cap.isOpened():
             raise OSError(f"no PNG sequence at {img_path}/{img_format}")
-        return cls(cap, output)
+        return cls(cap, output, vis)
 
     def _gray(self, img: np.ndarray) -> np.ndarray:
         return self.ctx.bgr2gray(img)[0] if img.ndim == 3 else np.ascontiguousarray(img, np.uint8)
@@ -132,7 +143,77 @@ class Farneback:
         ctx = self.ctx if (w, h) == (self.ctx.W, self.ctx.H) else im_helpers._ctx(w, h)
         return ctx.warp_flow(img, np.asarray(flow, np.float32))
 
+    # ---- vis="device" ----------------------------------------------------------------------------------------------------------------
+    def _device_init(self, prev: np.ndarray) -> None:
+        from . import vis as _vis                         # (attaches Context.flow_hsv_enqueue)
+        from .pipeline import FlowStage
+        n = self.ctx.W * self.ctx.H
+        self._stage = FlowStage(self.ctx, defer=False)    # the flow is enqueued at once: the picture is enqueued right behind it
+        self._stage.flow_next(prev)                       # frame 0: its gray image is the device's prevgray
+        self._pic = self.ctx.alloc(16 + (3 * n + 15) // 16 * 16 + 3 * n)     # the record, the BGR picture, the HSV picture (on demand)
+        self._hsv_of = None                               # the flow handle whose HSV picture self._hsv holds
+        self._hsv = None
+        self._record_dtype = _vis.RECORD_DTYPE
+
+    @property
+    def hsv(self) -> np.ndarray:
+        """The HSV picture of the last frame; in device mode it is rendered when somebody asks for it."""
+        if self.vis == "device" and self._hsv_of is not self.flow:
+            n = self.ctx.W * self.ctx.H
+            off = 16 + (3 * n + 15) // 16 * 16
+            if not getattr(self.flow, "on_device", False):
+                self._hsv = flow_to_hsv(np.asarray(self.flow))[0]      # the handle has been brought over (or no frame yet): the host's form
+            else:
+                self.ctx.flow_hsv_enqueue(self.flow, self._pic.ptr + 16, self._pic.ptr, "process", hsv_ptr=self._pic.ptr + off)
+                raw = self._pic.download(np.uint8, (self._pic.nbytes,))
+                self._hsv = raw[off:off + 3 * n].reshape(self.ctx.H, self.ctx.W, 3)
+            self._hsv_of = self.flow
+        return self._hsv
+
+    @hsv.setter
+    def hsv(self, value) -> None:
+        self._hsv = value
+
+    def _process_device(self) -> np.ndarray:
+        _, img = self.capture.read()
+        n = self.ctx.W * self.ctx.H
+        self.flow = self._stage.flow_next(np.asarray(img))            # the frame has been read when this returns
+        self.ctx.flow_hsv_enqueue(self.flow, self._pic.ptr + 16, self._pic.ptr, "process")
+        raw = self._pic.download(np.uint8, (16 + 3 * n,))              # the record and the BGR picture: all that comes back
+        record = raw[:16].view(self._record_dtype)[0]
+        result = raw[16:].reshape(self.ctx.H, self.ctx.W, 3)
+        if record["invalid"]:
+            result = self.prev_result
+        self.prev_result = result
+        return result
+
+    def close(self) -> None:
+        """Device mode: gives the stage's and the picture's device memory back (the context itself goes with the object)."""
+        if getattr(self, "_stage", None) is not None:
+            self._stage.close()
+            self._pic.free()
+            self._stage = None
+
+    def draw_hsv(self, flow: np.ndarray) -> np.ndarray:
+        """farneback.py:50-60: hue from atan2(fy, fx) + pi, value min(4 |flow|, 255), saturation 255, COLOR_HSV2BGR -- on the device
+        (MAV_HSV_DRAW).  flow (H, W, 2) float32; a float64 field is a TypeError (it would round).  Runs on this object's context when
+        the field is its size, else on a cached context of the field's size."""
+        from . import im_helpers, vis as _vis  # noqa: F401
+        h, w = np.shape(flow)[:2]
+        ctx = self.ctx if (w, h) == (self.ctx.W, self.ctx.H) else im_helpers._ctx(w, h)
+        return ctx.flow_hsv(flow, mode="draw")["bgr"]
+
+    def draw_flow(self, img: np.ndarray, flow: np.ndarray, step: int = 8) -> np.ndarray:
+        """farneback.py:28-48: green lines from every step-th pixel whose flow is longer than 1 to where it points, and a dot at the
+        pixel; img is drawn into and returned, as cv2.polylines does.  On the device (mav_draw_flow)."""
+        from . import im_helpers, vis as _vis  # noqa: F401
+        h, w = np.shape(img)[:2]
+        ctx = self.ctx if (w, h) == (self.ctx.W, self.ctx.H) else im_helpers._ctx(w, h)
+        return ctx.draw_flow(img, flow, step=step, threshold=1.0, color=(0, 255, 0))
+
     def process(self) -> np.ndarray:
+        if self.vis == "device":
+            return self._process_device()
         _, img = self.capture.read()
         gray = self._gray(img)
         # with cv2.OPTFLOW_USE_INITIAL_FLOW in PARAMS["flags"] the call (:76-80) hands cv2 the previous result as its starting flow

@@ -154,6 +154,17 @@ def get_flow_vis(frame: np.ndarray, magnitude_factor: float = 1.0) -> np.ndarray
     return _ctx(f.shape[1], f.shape[0]).flow_to_color(f)[0]
 
 
+def get_flow_radial(frame: np.ndarray) -> np.ndarray:
+    """The reference's helper (:87-100): cv2.cvtColor(COLOR_BGR2HSV), S = V = 255, cv2.cvtColor(COLOR_HSV2BGR) -- the hue of a flow
+    picture at full saturation and value.  Both conversions run in one launch on the device (MAV_COLOR_BGR2RADIAL: nothing comes to the
+    host in between); the bytes are those of the two calls of mavflow.vis.cvtColor with the assignment between them."""
+    from . import vis as _vis
+    a = np.asarray(frame)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise TypeError(f"get_flow_radial: an (H, W, 3) uint8 BGR picture expected, got {a.dtype} {a.shape}")
+    return _ctx(a.shape[1], a.shape[0]).cvt_color(a, _vis.COLOR_BGR2RADIAL)
+
+
 def apply_colormap(img: np.ndarray, max_value: float = None, colormap: int = COLORMAP_JET) -> np.ndarray:
     """cv2.applyColorMap(img, COLORMAP_JET) (im_helpers.py:115-135) on the device: a float image goes through to_int(normalize=True,
     max_value) first, a 3-channel u8 image through BGR2GRAY (OpenCV's own first step; the identity on equal channels), then the
