@@ -5760,3 +5760,76 @@ extern "C" int mav_draw_flow(mav_ctx* c, uint8_t* img, const float* flow, int ba
     CHK(check_launch("draw_flow"));
     return h.finish();
 }
+
+// ---- what kernels_shapes.hip's host side needs of a context (mavflow_internal.h) ----------------------------------------------------------
+int ctx_fail(int code, const char* fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    g_err = buf;
+    return code;
+}
+int ctx_enter(mav_ctx* c, int batch, const char* fn, CtxView* out)
+{
+    CHK(check_dev_call(c, batch, fn));
+    *out = CtxView{c->stream, c->W, c->H, c->max_batch};
+    return MAV_OK;
+}
+int ctx_check_launch(const char* what) { return check_launch(what); }
+StagedCall::StagedCall(mav_ctx* c, const char* fn) : h(new HostCall(c, fn)) {}
+StagedCall::~StagedCall() { delete h; }
+int StagedCall::begin(int batch, CtxView* out)
+{
+    CHK(h->beside(batch));
+    *out = CtxView{h->c->stream, h->c->W, h->c->H, h->c->max_batch};
+    return MAV_OK;
+}
+void* StagedCall::in(const void* host, size_t bytes) { return h->in((const char*)host, bytes); }
+void* StagedCall::out(void* host, size_t bytes) { return h->out((char*)host, bytes); }
+void* StagedCall::inout(void* host, size_t bytes)
+{
+    char* d = h->in((const char*)host, bytes);
+    h->fetch(host, d, bytes);
+    return d;
+}
+void* StagedCall::scratch(size_t bytes) { return h->scratch<char>(bytes); }
+int StagedCall::staged() const { return h->staged(); }
+int StagedCall::finish() { return h->finish(); }
+MiscScope::MiscScope(mav_ctx* c) : p(new ProfScope(c, K_MISC)) {}
+MiscScope::~MiscScope() { delete p; }
+
+// ---- the debug frame's pictures on the device (include/mavflow_shapes.h): mav_flow_to_color and mav_last_global_motion_render with
+// device outputs and the caller's scratch field; nothing resident is replaced, nothing is waited for
+#include "../../include/mavflow_shapes.h"
+extern "C" int mav_motion_pictures_dev(mav_ctx* c, const float* flow, int batch, float* field, uint8_t* img_flow, uint8_t* img_warped,
+                                       uint8_t* img_global)
+{
+    const char* fn = "mav_motion_pictures_dev";
+    CHK(check_dev_call(c, batch, fn));
+    if (!field) return fail(MAV_ERR_ARG, "%s: NULL field", fn);
+    if (img_flow && !flow) return fail(MAV_ERR_ARG, "%s: img_flow without flow", fn);
+    if ((uintptr_t)flow % 4 || (uintptr_t)field % 4) return fail(MAV_ERR_ARG, "%s: flow and field must be aligned to 4", fn);
+    if ((img_warped || img_global) && (!c->gm.last.batch || batch != c->gm.last.batch))
+        return fail(MAV_ERR_STATE, "%s: no flow of a %d-item global-motion call is resident", fn, batch);
+    if (!img_flow && !img_warped && !img_global) return MAV_OK;
+    CHK(ensure_render(c));
+    // float32 fields are rendered in numpy's float32 arithmetic, the frame-0 form: the renderer's mode block is made on the device from
+    // `batch` bytes of 1 at the head of the caller's field, which is written only afterwards (stream order)
+    ProfScope ps(c, K_MISC);
+    launch_fill_bytes(c->stream, (uint8_t*)field, 1, (size_t)batch);
+    launch_make_derot(c->stream, nullptr, nullptr, (const uint8_t*)field, batch, c->W, c->H, c->render_derot);
+    const DerotParams* derot = c->render_derot;
+    if (img_flow)
+        launch_render_f32(c->stream, flow, derot, nullptr, nullptr, batch, c->W, c->H, mav_thr_params{}, c->render_max, nullptr, img_flow, nullptr);
+    const mav_ctx::Motion::Last& l = c->gm.last;
+    for (int k = 0; k < 2; k++) {
+        uint8_t* img = k == 0 ? img_warped : img_global;
+        if (!img) continue;
+        launch_motion_pass_a(c->stream, l.flow, l.M, l.m_stride, batch, c->W, c->H, k == 0 ? field : nullptr, nullptr, k == 1 ? field : nullptr, nullptr);
+        launch_render_f32(c->stream, field, derot, nullptr, nullptr, batch, c->W, c->H, mav_thr_params{}, c->render_max, nullptr, img, nullptr);
+    }
+    return check_launch("motion pictures");
+}

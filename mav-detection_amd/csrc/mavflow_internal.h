@@ -543,3 +543,29 @@ hipError_t launch_flow_hsv(hipStream_t st, const float* flow, int W, int H, int 
 void launch_cvt_color(hipStream_t st, const uint8_t* src, int code, int W, int H, int B, uint8_t* dst);
 // img (B, H, W, 3) drawn into; colour: three bytes on the host; one launch (none where the grid is empty)
 void launch_draw_flow(hipStream_t st, uint8_t* img, const float* flow, int W, int H, int B, int step, float threshold, const uint8_t* colour);
+
+// ---- shapes (kernels_shapes.hip, compiled with -ffp-contract=off; include/mavflow_shapes.h) -----------------------------------------------
+// That unit holds its own host side (the entry points of its header).  What it needs of a context, which only mavflow.cpp can see:
+struct CtxView { hipStream_t stream; int W, H, max_batch; };
+int ctx_fail(int code, const char* fmt, ...);                               // sets mav_last_error(), returns code
+int ctx_enter(mav_ctx* c, int batch, const char* fn, CtxView* out);         // the prologue of a _dev entry point (check_dev_call) and the view
+int ctx_check_launch(const char* what);
+// One host-pointer call beside the resident state (HostCall::beside): staging blocks behind the last call's, given back on destruction.
+struct StagedCall {
+    StagedCall(mav_ctx* c, const char* fn);
+    ~StagedCall();
+    StagedCall(const StagedCall&) = delete;
+    int begin(int batch, CtxView* out);
+    void* in(const void* host, size_t bytes);          // a block, filled from the host now (NULL host: no block, NULL)
+    void* out(void* host, size_t bytes);               // a block, brought to the host by finish()
+    void* inout(void* host, size_t bytes);             // both
+    void* scratch(size_t bytes);
+    int staged() const;
+    int finish();
+private:
+    struct HostCall* h;
+};
+// a profiled launch section of the miscellaneous class (ProfScope)
+struct MiscScope { MiscScope(mav_ctx* c); ~MiscScope(); MiscScope(const MiscScope&) = delete; private: struct ProfScope* p; };
+// n bytes of `value` at p (the caller's memory), one launch
+void launch_fill_bytes(hipStream_t st, uint8_t* p, uint8_t value, size_t n);

@@ -13,4 +13,6 @@ def __getattr__(name):
              "FrameResult": "frame_result", "Rectangle": "utils", "Context": "_lib"}
     if name in table:
         return getattr(importlib.import_module(f"{__name__}.{table[name]}"), name)
+    if name == "shapes":                       # mavflow.shapes: cv2.line / rectangle / circle / add and the Context's drawing methods
+        return importlib.import_module(f"{__name__}.shapes")
     raise AttributeError(name)

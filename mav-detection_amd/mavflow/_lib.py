@@ -196,6 +196,11 @@ GATHER_ORDERED, GATHER_SOURCES_HELD = 1, 2      # mav_upload_gather flags
 STEP_MAX_GATHER = 4
 
 
+# every symbol include/mavflow_shapes.h declares (EXPORTS above lists include/mavflow.h alone)
+SHAPES_EXPORTS = ("mav_shapes_scratch_bytes", "mav_draw_shapes", "mav_draw_shapes_dev", "mav_shapes_form", "mav_add_saturate",
+                  "mav_add_saturate_dev", "mav_bytes_form", "mav_shapes_from_blobs_dev", "mav_mosaic", "mav_mosaic_dev", "mav_motion_pictures_dev")
+
+
 class Gather(C.Structure):
     _fields_ = [("src_host", C.POINTER(C.c_void_p)), ("count", C.c_int), ("bytes_each", C.c_size_t), ("dst_dev", C.c_void_p)]
 
@@ -417,6 +422,19 @@ def load(path: str | None = None) -> C.CDLL:
     lib.mav_history_push.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
     lib.mav_history_push_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
     lib.mav_stage_remap_linear.argtypes = [vp, vp, C.c_int, vp, vp, vp]
+    # include/mavflow_shapes.h (SHAPES_EXPORTS; the methods are mavflow.shapes')
+    i = C.c_int
+    lib.mav_shapes_scratch_bytes.restype, lib.mav_shapes_scratch_bytes.argtypes = C.c_size_t, [i, i, i]
+    lib.mav_draw_shapes.argtypes = [vp, vp, i, i, vp, i]                          # ctx, img, channels, batch, shapes, n
+    lib.mav_draw_shapes_dev.argtypes = [vp, vp, i, i, vp, i, vp, vp]              # ctx, img, channels, batch, shapes, n_max, n_dev, scratch
+    lib.mav_shapes_form.argtypes = [vp, i, i]                                     # shapes, n, channels
+    for fn in (lib.mav_add_saturate, lib.mav_add_saturate_dev):                   # ctx, a, b, channels, batch, dst
+        fn.argtypes = [vp, vp, vp, i, i, vp]
+    lib.mav_bytes_form.argtypes = [C.c_size_t, vp, vp, vp]                        # n, a, b, dst
+    lib.mav_shapes_from_blobs_dev.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp]    # ctx, blobs, counts, batch, max_blobs, thickness, colour, out, n_out
+    for fn in (lib.mav_mosaic, lib.mav_mosaic_dev):                               # ctx, tiles, tile_channels, rows, cols, batch, out
+        fn.argtypes = [vp, vp, vp, i, i, i, vp]
+    lib.mav_motion_pictures_dev.argtypes = [vp, vp, i, vp, vp, vp, vp]            # ctx, flow, batch, field, img_flow, img_warped, img_global
     _lib = lib
     return lib
 
@@ -754,7 +772,11 @@ class FlowHistory:
 
 
 class Context:
-    """One mav_ctx: (device, W, H, max_batch, Farneback parameters)."""
+    """One mav_ctx: (device, W, H, max_batch, Farneback parameters).
+
+    The methods of the headers beside include/mavflow.h are attached by the module that binds each header, when it is imported:
+    mavflow.shapes adds draw_shapes, draw_blob_boxes, add_saturate, mosaic, motion_pictures_enqueue and their *_enqueue twins (as
+    mavflow.vis, mavflow.warp, mavflow.resize and the others add theirs).  Import that module before calling them on a Context."""
 
     def __init__(self, W: int, H: int, max_batch: int = 1, fb: FbParams | None = None, device: int = 0, window="box"):
         self.lib = load()

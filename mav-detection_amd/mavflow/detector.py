@@ -479,6 +479,29 @@ class Detector:
             return flow_uv_warped_vis, self.cluster_vis, magnitude_vis.copy(), global_motion_vis
         return flow_uv_warped_vis, self.cluster_vis, self.cluster_vis.copy(), global_motion_vis
 
+    # -- drawing (detector.py:242-256, 390-394) ---------------------------------------------------------------------------------------
+    def ground_truth_shapes(self, image: int = 0) -> list:
+        """draw's rectangles as records of a shapes table: every ground-truth box in red, thickness 2"""
+        from . import shapes
+        return [shapes.shape(shapes.RECT, *gt.get_topleft_int(), *gt.get_bottomright_int(), 2, (0, 0, 255), image)
+                for gt in getattr(self.dataset, "ground_truth", [])]
+
+    def draw(self, orig_frame: np.ndarray) -> None:
+        """Render the ground truths (:242-256): cv2.rectangle(orig_frame, topleft, bottomright, (0, 0, 255), 2) for every ground-truth
+        box, into orig_frame in place -- one table, one call (Context.draw_shapes)."""
+        table = self.ground_truth_shapes()
+        if table:
+            im_helpers._ctx(orig_frame.shape[1], orig_frame.shape[0]).draw_shapes(orig_frame, table)
+
+    def predict(self, segment: np.ndarray, flow_uv: np.ndarray, orig_frame: np.ndarray) -> None:
+        """:390-394: the mean flow over `segment` (numpy, as the reference has it) moves the first ground-truth box's centre to
+        self.prediction; the line between the two, red, thickness 5, is drawn into orig_frame in place."""
+        from . import shapes
+        avg = np.average(flow_uv[segment], 0)
+        center = self.dataset.ground_truth[0].get_center_int()
+        self.prediction = (int(center[0] + avg[0]), int(center[1] + avg[1]))
+        shapes.line(orig_frame, center, self.prediction, (0, 0, 255), 5)
+
     # -- flow history (detector.py:365-388) -----------------------------------------------------------------------------------------
     @property
     def history_index(self) -> int:

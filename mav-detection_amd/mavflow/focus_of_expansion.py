@@ -140,6 +140,43 @@ class FocusOfExpansion:
                     frame[y, x0:x1 + 1] = value
         return frame
 
+    @staticmethod
+    def line_colours(lines, FoE, radial_threshold) -> List[List[int]]:
+        """The colour of every tracked line as draw (:218-236) decides it, in the reference's own arithmetic on the host: the cosine
+        between the line and the ray from the FoE to its newest point, green [0, 255, 0] unless it is below radial_threshold, then red
+        [0, 0, 255].  A zero-length line or a point on the FoE gives the quotient 0 / 0 = NaN, and `nan < t` is false: green."""
+        out = []
+        with np.errstate(all="ignore"):
+            for line in lines:
+                diff1 = np.asarray(line[0]) - np.asarray(line[1])
+                diff2 = np.asarray(line[0]) - np.asarray(FoE)
+                flow_magnitude = im_helpers.get_magnitude(diff1)
+                img_distance = im_helpers.get_magnitude(diff2)
+                angle_diff = np.dot(diff1, diff2) / (flow_magnitude * img_distance)
+                out.append([0, 0, 255] if angle_diff < radial_threshold else [0, 255, 0])
+        return out
+
+    def draw(self, frame: np.ndarray, FoE: Tuple[float, float]) -> np.ndarray:
+        """Draw the FoE algorithm's visualisation (:203-241): a filled disc of radius 20 at the FoE into `frame` (in place), every line
+        of the latest get_FOE_sparse into self.mask with thickness 2, green or red by line_colours, in the lines' order, and
+        cv2.add(frame, self.mask) as the result.  The disc, the lines and the add are one call of the shapes family each (the lines as
+        ONE table, drawn in table order); the colours are a few thousand scalars on the host, like the trace bookkeeping.  old_gray and
+        time are updated as the reference updates them."""
+        from . import shapes
+        if FoE[0] is np.nan:
+            return frame
+        ctx = im_helpers._ctx(frame.shape[1], frame.shape[0])
+        ctx.draw_shapes(frame, [shapes.shape(shapes.CIRCLE, int(FoE[0]), int(FoE[1]), 20, 0, shapes.FILLED, [0, 42, 255])])
+        frame_gray = ctx.bgr2gray(frame)
+        frame_gray = frame_gray[0] if frame_gray.ndim == 3 else frame_gray
+        colours = self.line_colours(self.lines, FoE, self.radial_threshold)
+        table = [shapes.shape(shapes.LINE, int(l[0][0]), int(l[0][1]), int(l[1][0]), int(l[1][1]), 2, c) for l, c in zip(self.lines, colours)]
+        if table:
+            ctx.draw_shapes(self.mask, table)
+        self.old_gray = frame_gray.copy()
+        self.time += 1
+        return ctx.add_saturate(frame, self.mask)
+
 
 def disc_half_widths(radius: int) -> List[int]:
     """Half-width of each row offset 0..radius of cv2.circle(thickness=-1, LINE_8, shift 0): OpenCV's Circle(..., fill=1) emits the

@@ -192,7 +192,7 @@ def _write_stream(path: str, stream) -> None:
 class Processor:
     def __init__(self, config: RunConfig, results_path: Optional[str] = None, images_path: Optional[str] = None,
                  processed_path: Optional[str] = None, png_encoder: str = "host", algorithm: Optional["Detector.Algorithm"] = None,
-                 blobs: Optional[dict] = None, roc: Optional[dict] = None, validation: str = "host") -> None:
+                 blobs: Optional[dict] = None, roc: Optional[dict] = None, debug_path: Optional[str] = None, validation: str = "host") -> None:
         if validation not in ("host", "device"):
             raise ValueError(f"validation must be 'host' or 'device', got {validation!r}")
         if png_encoder not in ("host", "device"):
@@ -207,6 +207,10 @@ class Processor:
         # averaged as today.  A frame whose drone has more than validation_max_pixels pixels takes today's host path for its pixel list.
         # FrameResult, its JSON and every file are the same either way; the global-motion branch has no validation tail and ignores it.
         self.validation = validation
+        # extra: debug_path=DIR makes run_detection() in the global-motion branch write the reference's debug frame (processor.py:295-301),
+        # image_{i:05d}.png at 3W x 2H: Detector.draw on the frame, then the six tiles, composed on the device from the pictures where
+        # they are and brought back in one download; detection_results[i] = detector.frame_result.  config.debug alone keeps raising.
+        self.debug_path = debug_path
         self.validation_max_pixels = _lib._validation.DEFAULT_MAX_PIXELS
         self._tails: Dict[int, dict] = dict()
         # extra: blobs=dict(connectivity=, min_area=, max_blobs=) (any subset; {} = the defaults 8, 1, 256) labels every frame's fixed mask
@@ -605,7 +609,7 @@ class Processor:
         in debug mode only, which this branch does not reproduce."""
         self._no_blobs_here()
         self._no_roc_here()
-        if self.debug_mode:
+        if self.debug_mode and self.debug_path is None:
             raise NotImplementedError("debug_mode in the global-motion branch draws with cv2.rectangle and writes a six-image mosaic "
                                       "(processor.py:295-301): not reproduced")
         det = self.detector
@@ -619,6 +623,9 @@ class Processor:
             self.dataset.get_annotation(i)
             dev = det._device_flow(self.flow_uv)
             if dev is None and np.asarray(self.flow_uv).dtype != np.float32:
+                if self.debug_path is not None:
+                    raise NotImplementedError("debug_path composes the debug frame from the device's float32 pictures; this flow field is "
+                                              f"{np.asarray(self.flow_uv).dtype}")
                 det.get_transformation_matrix(orig_frame, self.flow_uv)
                 _, cluster_vis, _, _ = det.flow_vec_subtract(orig_frame, self.flow_uv)
                 window = det.opt_window[1]
@@ -650,6 +657,10 @@ class Processor:
                 for gt in self.dataset.ground_truth:
                     det.iou = utils.Rectangle.calculate_iou(window, gt)
                 det.prev_frame = orig_frame
+                if self.debug_path is not None:
+                    self._queue_png(self.debug_path, i, self._debug_frame(ctx, ptr, b["gray"].ptr, orig_frame))
+                    det.frame_result = FrameResult()                   # flow_vec_subtract's fresh record (detector.py:154)
+                    self.detection_results[i] = det.frame_result
             self.detection_windows[i] = window
             if hasattr(det, "iou"):
                 self.detection_iou[i] = det.iou
@@ -659,11 +670,48 @@ class Processor:
         self._flush_images()
         return self.detection_results
 
+    def _debug_frame(self, ctx, flow_ptr, gray_ptr, orig_frame: np.ndarray) -> np.ndarray:
+        """processor.py:295-299 on the device, behind the frame's global-motion step on `ctx`: detector.draw on the uploaded frame
+        (the ground-truth rectangles, one table), get_flow_vis of the flow, of flow_uv_warped and of global_motion rendered where the
+        flow and the matrix are, and np.vstack((np.hstack((orig_frame, global_motion_vis, flow_uv_warped_vis)), np.hstack((flow_vis,
+        global_motion_vis, cluster_vis)))) as one mosaic launch -- cluster_vis is the step's gray plane, replicated.  One download, the
+        (2H, 3W, 3) frame; orig_frame receives its drawn tile, as the reference draws into it."""
+        from . import shapes
+        W, H = ctx.W, ctx.H
+        n = W * H
+        frame = np.asarray(orig_frame)
+        if frame.shape != (H, W, 3) or frame.dtype != np.uint8:
+            raise ValueError(f"debug_path: the frame is {frame.dtype} {frame.shape}; the debug frame takes uint8 ({H}, {W}, 3)")
+        frame = np.ascontiguousarray(frame)
+        table = shapes.table(self.detector.ground_truth_shapes())
+        if len(table) > self.DEBUG_MAX_BOXES:
+            raise ValueError(f"debug_path: {len(table)} ground-truth boxes; the debug frame's table holds {self.DEBUG_MAX_BOXES}")
+        blk = self._global_motion_buffers(ctx)["debug"]               # four pictures, the table, the scratch field, the mosaic
+        o_tab = 3 * n * 4
+        o_field = o_tab + 32 * self.DEBUG_MAX_BOXES
+        o_out = o_field + 8 * n
+        pic = [blk.ptr + 3 * n * k for k in range(4)]
+        _lib.check(ctx.lib.mav_memcpy_h2d(ctx.h, pic[0], _lib._ptr(frame), frame.nbytes))
+        if len(table):
+            _lib.check(ctx.lib.mav_memcpy_h2d(ctx.h, blk.ptr + o_tab, _lib._ptr(table), table.nbytes))
+            ctx.draw_shapes_enqueue(pic[0], blk.ptr + o_tab, len(table), 3, 1)              # one colour: the direct form
+        ctx.motion_pictures_enqueue(1, flow_ptr, blk.ptr + o_field, pic[1], pic[2], pic[3])
+        ctx.mosaic_enqueue([pic[0], pic[3], pic[2], pic[1], pic[3], gray_ptr], [3, 3, 3, 3, 3, 1], 2, 3, blk.ptr + o_out, 1)
+        out = np.empty((2 * H, 3 * W, 3), np.uint8)
+        _lib.check(ctx.lib.mav_memcpy_d2h(ctx.h, _lib._ptr(out), blk.ptr + o_out, out.nbytes))
+        if isinstance(orig_frame, np.ndarray) and orig_frame.flags.writeable:
+            orig_frame[...] = out[:H, :W]
+        return out
+
+    DEBUG_MAX_BOXES = 64
+
     def _global_motion_buffers(self, ctx) -> dict:
         if self._gm_bufs is None or self._gm_bufs[0] is not ctx:
             self._free_global_motion_buffers()
             n0 = ctx.W * ctx.H
             sizes = dict(res=_lib.MOTION_DTYPE.itemsize, H=72, ok=4, M=48, gray=n0, flow=8 * n0)
+            if self.debug_path is not None:                             # _debug_frame's block: 12 + 8 + 18 bytes per pixel and the table
+                sizes["debug"] = 38 * n0 + 32 * self.DEBUG_MAX_BOXES
             self._gm_bufs = (ctx, {k: ctx.alloc(v) for k, v in sizes.items()})
         return self._gm_bufs[1]
 
@@ -702,6 +750,9 @@ class Processor:
         if self.debug_mode:
             raise NotImplementedError("debug_mode in the global-motion branch draws with cv2.rectangle and writes a six-image mosaic "
                                       "(processor.py:295-301): not reproduced")
+        if self.debug_path is not None:
+            raise NotImplementedError("debug_path writes the debug frame of run_detection(), one frame at a time; run_detection_batched "
+                                      "does not compose it")
         if det.use_sparse_of:
             raise NotImplementedError("run_detection_batched takes the pairs from the flow field at detector.coords; use_sparse_of (pairs from "
                                       "the sequential tracker, frame after frame) is served by run_detection()")
