@@ -916,7 +916,7 @@ __global__ __launch_bounds__(256) void k_bgr2gray(const uint8_t* __restrict__ bg
 {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         const uint8_t* p = bgr + 3 * i;
-        gray[i] = (uint8_t)((p[0] * 1868u + p[1] * 9617u + p[2] * 4899u + 8192u) >> 14);
+        gray[i] = bgr2gray_px(p[0], p[1], p[2]);
     }
 }
 void launch_bgr2gray(hipStream_t st, const uint8_t* bgr, size_t n, uint8_t* gray)

@@ -569,3 +569,8 @@ private:
 struct MiscScope { MiscScope(mav_ctx* c); ~MiscScope(); MiscScope(const MiscScope&) = delete; private: struct ProfScope* p; };
 // n bytes of `value` at p (the caller's memory), one launch
 void launch_fill_bytes(hipStream_t st, uint8_t* p, uint8_t value, size_t n);
+
+// ---- PNG decode (kernels_png_decode.hip, integer arithmetic only; include/mavflow_png_decode.h) ---------------------------------------------
+// That unit holds its own host side, like the shapes unit.  The one gray value of a BGR pixel, cv2.cvtColor(COLOR_BGR2GRAY) on uint8
+// (SURVEY A.7): k_bgr2gray and the decoder's gray output both go through it, so their bits agree.
+__host__ __device__ inline uint8_t bgr2gray_px(unsigned b, unsigned g, unsigned r) { return (uint8_t)((b * 1868u + g * 9617u + r * 4899u + 8192u) >> 14); }

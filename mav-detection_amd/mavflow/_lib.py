@@ -4,6 +4,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import struct
 
 import numpy as np
 
@@ -199,6 +200,16 @@ STEP_MAX_GATHER = 4
 # every symbol include/mavflow_shapes.h declares (EXPORTS above lists include/mavflow.h alone)
 SHAPES_EXPORTS = ("mav_shapes_scratch_bytes", "mav_draw_shapes", "mav_draw_shapes_dev", "mav_shapes_form", "mav_add_saturate",
                   "mav_add_saturate_dev", "mav_bytes_form", "mav_shapes_from_blobs_dev", "mav_mosaic", "mav_mosaic_dev", "mav_motion_pictures_dev")
+
+
+# every symbol include/mavflow_png_decode.h declares
+PNG_DECODE_EXPORTS = ("mav_png_decode_scratch_bytes", "mav_png_decode_dev", "mav_png_decode", "mav_png_inflate_host")
+PNG_OUT = {"samples": 0, "bgr": 1, "gray": 2}                      # MAV_PNG_OUT_*
+PNG_DECODE_MAX_COUNT = 1024
+PNG_ERRORS = ("OK", "HEADER", "TRUNCATED", "BLOCK_TYPE", "STORED_LEN", "CODE_LENGTHS", "SYMBOL", "DISTANCE", "OVERFLOW", "SHORT", "ADLER", "FILTER")
+# mav_png_status, 48 bytes
+PNG_STATUS_DTYPE = np.dtype([("code", "<i4"), ("adler_stream", "<u4"), ("adler_computed", "<u4"), ("blocks", "<u4", (3,)), ("consumed", "<u8"),
+                             ("produced", "<u8"), ("max_length", "<u4"), ("max_distance", "<u4")])
 
 
 class Gather(C.Structure):
@@ -435,6 +446,14 @@ def load(path: str | None = None) -> C.CDLL:
     for fn in (lib.mav_mosaic, lib.mav_mosaic_dev):                               # ctx, tiles, tile_channels, rows, cols, batch, out
         fn.argtypes = [vp, vp, vp, i, i, i, vp]
     lib.mav_motion_pictures_dev.argtypes = [vp, vp, i, vp, vp, vp, vp]            # ctx, flow, batch, field, img_flow, img_warped, img_global
+    # include/mavflow_png_decode.h (PNG_DECODE_EXPORTS)
+    lib.mav_png_decode_scratch_bytes.restype, lib.mav_png_decode_scratch_bytes.argtypes = C.c_size_t, [i, i, i, i]     # W, H, channels, count
+    # ctx, streams, index, count, W, H, channels, out_format, out, status[, scratch]
+    lib.mav_png_decode_dev.argtypes = [vp, vp, vp, i, i, i, i, i, vp, vp, vp]
+    lib.mav_png_decode.argtypes = [vp, vp, vp, i, i, i, i, i, vp, vp]
+    lib.mav_png_inflate_host.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp]                                          # z, n, raw, raw_bytes, status
+    for fn in (lib.mav_png_decode_dev, lib.mav_png_decode, lib.mav_png_inflate_host):
+        fn.restype = C.c_int
     _lib = lib
     return lib
 
@@ -1631,6 +1650,134 @@ class Context:
         wr = np.empty(B, np.uint8)
         check(self.lib.mav_last_overlay_png(self.h, _ptr(frames), _ptr(gt), B, int(radius), _ptr(out), out.size, _ptr(index), _ptr(wr)))
         return self._png_files(out, index, 3, wrap), wr.view(np.bool_)
+
+    # -- PNG decode on the device (include/mavflow_png_decode.h) --------------------------------------------------
+    @staticmethod
+    def _png_streams(files, verify_crc: bool = False):
+        """(W, H, channels, streams u8, index (n, 2) u64) of PNG files that all hold device-eligible images of one size and colour
+        type: the IDAT bodies of each file joined into its zlib stream, the streams packed back to back.  ValueError names the file."""
+        from . import frame_source
+        shape, parts, index, at = None, [], [], 0
+        for k, data in enumerate(files):
+            try:
+                ihdr, _, _, spans = frame_source.png_chunks(data, "all" if verify_crc else "small")
+            except (ValueError, struct.error) as e:
+                raise ValueError(f"png_decode(): file {k}: {e}") from None
+            if not frame_source.device_eligible(ihdr):
+                raise ValueError(f"png_decode(): file {k} is not one the device decodes (depth {ihdr[2]}, colour type {ihdr[3]}, "
+                                 f"interlace {ihdr[6]}): frame_source.decode_png reads it")
+            this = (ihdr[0], ihdr[1], frame_source._CHANNELS[ihdr[3]])
+            if shape is None:
+                shape = this
+            elif this != shape:
+                raise ValueError(f"png_decode(): file {k} is {this[0]} x {this[1]} x {this[2]}, file 0 is {shape[0]} x {shape[1]} x {shape[2]}")
+            n = sum(length for _, length in spans)
+            parts += [data[o:o + length] for o, length in spans]
+            index.append((at, n))
+            at += n
+        if shape is None:
+            raise ValueError("png_decode(): no files")
+        if len(index) > PNG_DECODE_MAX_COUNT:
+            raise ValueError(f"png_decode(): {len(index)} files in one call, at most {PNG_DECODE_MAX_COUNT}")
+        streams = np.frombuffer(b"".join(parts) + b"\0", np.uint8)
+        return shape[0], shape[1], shape[2], streams, np.array(index, np.uint64).reshape(-1, 2)
+
+    @staticmethod
+    def _png_raise(status, what="png_decode()"):
+        bad = np.flatnonzero(status["code"] != 0)
+        if bad.size:
+            k = int(bad[0])
+            code = int(status["code"][k])
+            name = PNG_ERRORS[code] if 0 <= code < len(PNG_ERRORS) else str(code)
+            raise ValueError(f"{what}: file {k}: MAV_PNG_E_{name} ({code}) after {int(status['consumed'][k])} bytes of its stream"
+                             + (f"; files {bad.tolist()} failed" if bad.size > 1 else ""))
+
+    def png_decode(self, files, out: str = "bgr", verify_crc: bool = False, return_status: bool = False):
+        """PNG files (bytes) of ONE size and colour type, 8-bit, not interlaced -> (n, H, W, 3) BGR as cv2.imread returns them
+        (out="bgr"), (n, H, W) gray as cvtColor(BGR2GRAY) of that (out="gray"), or the files' own samples (n, H, W[, channels])
+        (out="samples").  The compressed streams go up; inflate, Adler-32, un-filtering and conversion run on the device.  The size is
+        the files' own, not the context's.  verify_crc: the IDAT CRC is checked on the host as well (the small chunks' always are).
+        ValueError names the first file the decoder refused and its MAV_PNG_E_* code; return_status=True returns (array, statuses)
+        instead and raises nothing for them (a refused image is all zero)."""
+        if out not in PNG_OUT:
+            raise ValueError(f"png_decode(): out must be one of {sorted(PNG_OUT)}, got {out!r}")
+        W, H, ch, streams, index = self._png_streams(list(files), verify_crc)
+        return self.png_decode_streams(streams, index, W, H, ch, out, return_status)
+
+    def png_decode_streams(self, streams, index, W: int, H: int, channels: int, out: str = "samples", return_status: bool = False):
+        """mav_png_decode on zlib streams: streams u8, index (n, 2) u64 of (offset, size) -> as png_decode."""
+        streams = np.ascontiguousarray(streams, np.uint8)
+        index = np.ascontiguousarray(index, np.uint64).reshape(-1, 2)
+        n = index.shape[0]
+        if n and int((index[:, 0] + index[:, 1]).max()) > streams.size:
+            raise ValueError("png_decode_streams(): a stream ends past the buffer")
+        if streams.size == 0:
+            streams = np.zeros(1, np.uint8)
+        oc = {"samples": int(channels), "bgr": 3, "gray": 1}[out]
+        img = np.empty((n, int(H), int(W), oc), np.uint8)
+        status = np.zeros(n, PNG_STATUS_DTYPE)
+        check(self.lib.mav_png_decode(self.h, _ptr(streams), _ptr(index), n, int(W), int(H), int(channels), PNG_OUT[out], _ptr(img), _ptr(status)))
+        if oc == 1:
+            img = img[..., 0]
+        if return_status:
+            return img, status
+        self._png_raise(status)
+        return img
+
+    def png_decode_dev(self, streams_ptr, index_ptr, count: int, W: int, H: int, channels: int, out: str, out_ptr, status_ptr, scratch_ptr) -> None:
+        """mav_png_decode_dev: device pointers, enqueue only.  scratch: png_decode_scratch_bytes(W, H, channels, count) bytes."""
+        check(self.lib.mav_png_decode_dev(self.h, _dev_ptr(streams_ptr), _dev_ptr(index_ptr), int(count), int(W), int(H), int(channels), PNG_OUT[out],
+                                          _dev_ptr(out_ptr), _dev_ptr(status_ptr), _dev_ptr(scratch_ptr)))
+
+    def png_decode_scratch_bytes(self, W: int, H: int, channels: int, count: int) -> int:
+        return int(self.lib.mav_png_decode_scratch_bytes(int(W), int(H), int(channels), int(count)))
+
+    def png_decode_to_device(self, files, out: str = "bgr", verify_crc: bool = False):
+        """png_decode with the frames LEFT on the device: (DeviceBuffer of (n, H, W[, c]) u8, shape).  The statuses are checked (one
+        synchronisation, 48 bytes per file come back); the caller frees the buffer."""
+        W, H, ch, streams, index = self._png_streams(list(files), verify_crc)
+        n = index.shape[0]
+        oc = {"samples": ch, "bgr": 3, "gray": 1}[out]
+        d_out = self.alloc(n * H * W * oc)
+        bufs = []
+        try:
+            bufs = [self.alloc(streams.nbytes).upload(streams), self.alloc(index.nbytes).upload(index), self.alloc(n * PNG_STATUS_DTYPE.itemsize),
+                    self.alloc(self.png_decode_scratch_bytes(W, H, ch, n))]
+            self.png_decode_dev(bufs[0], bufs[1], n, W, H, ch, out, d_out, bufs[2], bufs[3])
+            self._png_raise(bufs[2].download(PNG_STATUS_DTYPE, (n,)))      # (a stream-ordered copy and the call's one synchronisation)
+        except Exception:
+            self.sync()
+            d_out.free()
+            raise
+        finally:
+            self.sync()
+            for b in bufs:
+                b.free()
+        return d_out, ((n, H, W) if oc == 1 else (n, H, W, oc))
+
+    def farneback_png(self, files) -> np.ndarray:
+        """Flow of every consecutive pair of n + 1 PNG files of the context's size -> (n, H, W, 2) float32, with no pixel crossing
+        PCIe: the files are decoded to ONE gray block on the device and mav_farneback_dev reads frames 0 .. n - 1 as `prev` and
+        1 .. n as `next` (the frame-sequence layout).  Byte for byte farneback(gray[:-1], gray[1:]) of the decoded frames."""
+        files = list(files)
+        n = len(files) - 1
+        if n < 1:
+            raise ValueError("farneback_png(): a sequence needs at least two files")
+        if n > self.max_batch:
+            raise ValueError(f"farneback_png(): {n} pairs on a context of max_batch {self.max_batch}")
+        d_gray, shape = self.png_decode_to_device(files, "gray")
+        d_flow = None
+        try:
+            if shape[1:] != (self.H, self.W):
+                raise ValueError(f"farneback_png(): the files are {shape[2]} x {shape[1]}, the context is {self.W} x {self.H}")
+            d_flow = self.alloc(n * self.H * self.W * 8)
+            check(self.lib.mav_farneback_dev(self.h, d_gray.ptr, d_gray.ptr + self.W * self.H, n, d_flow.ptr))
+            return d_flow.download(np.float32, (n, self.H, self.W, 2))
+        finally:
+            self.sync()
+            d_gray.free()
+            if d_flow is not None:
+                d_flow.free()
 
     # -- device-pointer path (bench, multi-GPU) --------------------------------------------------------------
     def process_batch_dev(self, prev_ptr, next_ptr, samples_ptr, batch, results_ptr, flow_ptr=None, omega_ptr=None,

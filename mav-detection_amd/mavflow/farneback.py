@@ -121,11 +121,13 @@ class Farneback:
             self._device_init(prev)
 
     @classmethod
-    def from_png_sequence(cls, img_path: str, img_format: str = "image_%05d.png", output=None, vis: str = "host") -> "Farneback":
+    def from_png_sequence(cls, img_path: str, img_format: str = "image_%05d.png", output=None, vis: str = "host", decoder: str = "host",
+                          ahead: int = 64) -> "Farneback":
         """Farneback(cv2.VideoCapture(f'{img_path}/image_%05d.png'), output) with the capture this build provides for PNG sequences
-        (frame_source.PngSequenceCapture; src/datasets/dataset.py:38,57)."""
+        (frame_source.PngSequenceCapture; src/datasets/dataset.py:38,57).  decoder / ahead: the capture's (decoder="device": the
+        files are decoded on the device, `ahead` per call; the frames are the same)."""
         from .frame_source import PngSequenceCapture
-        cap = PngSequenceCapture(f"{img_path}/{img_format}")
+        cap = PngSequenceCapture(f"{img_path}/{img_format}", decoder=decoder, ahead=ahead)
         if not cap.isOpened():
             raise OSError(f"no PNG sequence at {img_path}/{img_format}")
         return cls(cap, output, vis)

@@ -68,10 +68,14 @@ class FarnebackFlowProvider:
             raise ValueError("write_flo needs img_path")
 
     @classmethod
-    def from_png_sequence(cls, img_path: str, img_format: str = "image_%05d.png", **kw) -> "FarnebackFlowProvider":
+    def from_png_sequence(cls, img_path: str, img_format: str = "image_%05d.png", png_decoder: str = "host", **kw) -> "FarnebackFlowProvider":
         """The reference's frame layout (src/datasets/dataset.py:26,38: `{img_path}/image_%05d.png`) as the source of the frames: frame i
-        = cv2.imread of file i (frame_source.imread), converted BGR -> gray on the GPU."""
+        = cv2.imread of file i (frame_source.imread), converted BGR -> gray on the GPU.  png_decoder="device" with window > 1: the
+        n + 1 files of a window go up compressed and are decoded to gray where Farneback reads them (Context.farneback_png); the
+        fields are the same.  With window = 1 the option changes nothing (one pair per call stays on the host decode)."""
         from . import frame_source
+        if png_decoder not in ("host", "device"):
+            raise ValueError(f"png_decoder must be 'host' or 'device', got {png_decoder!r}")
         pattern = f"{img_path}/{img_format}"
         first = frame_source.imread(pattern % 0)
         if first is None:
@@ -83,7 +87,10 @@ class FarnebackFlowProvider:
                 raise OSError(f"cannot read {pattern % i}")
             return f
         kw.setdefault("img_path", img_path)
-        return cls(get, first.shape[1], first.shape[0], **kw)
+        self = cls(get, first.shape[1], first.shape[0], **kw)
+        if png_decoder == "device" and self.window > 1:
+            self._png_pattern = pattern
+        return self
 
     def _gray(self, i: int) -> np.ndarray:
         f = np.asarray(self.get_gray(i))
@@ -96,7 +103,17 @@ class FarnebackFlowProvider:
             return self.ctx.farneback(self._gray(i), self._gray(i + 1))[0]
         if i not in self._cache:
             n = max(1, min(self.window, self.n_frames - 1 - i))
-            flows = self.ctx.farneback_sequence(np.stack([self._gray(j) for j in range(i, i + n + 1)]))
+            if getattr(self, "_png_pattern", None):
+                files = []
+                for j in range(i, i + n + 1):
+                    try:
+                        with open(self._png_pattern % j, "rb") as f:
+                            files.append(f.read())
+                    except OSError:
+                        raise OSError(f"cannot read {self._png_pattern % j}") from None
+                flows = self.ctx.farneback_png(files)
+            else:
+                flows = self.ctx.farneback_sequence(np.stack([self._gray(j) for j in range(i, i + n + 1)]))
             self._cache = {i + k: flows[k] for k in range(n)}         # views of one (pinned) result block
         return self._cache[i]
 

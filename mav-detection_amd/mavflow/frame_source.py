@@ -10,7 +10,10 @@ cv2 is not part of this build; this module is that capture for PNG sequences:
     imread(path) -> BGR u8 (H, W, 3)     what cv2.imread(path) (IMREAD_COLOR) returns: gray replicated, alpha dropped, palette expanded.
     png_wrap(W, H, channels, zstream)    the PNG file around a zlib stream of scanline data that was deflated elsewhere (on the device:
                                          Context.png_encode / render_last_png / overlay_last_png).
-    PngSequenceCapture(pattern)          cv2.VideoCapture(pattern)'s read() / get(3|4|7) / isOpened() / release() for an image sequence.
+    PngSequenceCapture(pattern)          cv2.VideoCapture(pattern)'s read() / get(3|4|7) / isOpened() / release() for an image sequence;
+                                         decoder="device" decodes `ahead` files per device call.
+    imread_many(files, ctx, out)         imread over a list: 8-bit non-interlaced gray / RGB (+ alpha) files are inflated, un-filtered and
+                                         converted on the device (include/mavflow_png_decode.h), the rest by decode_png.
 
 The decoder is pinned by PIL-decoded fixtures generated in the build container (tools/gen_png_fixtures.py,
 tests/golden/png_frames.npz), 16-bit and interlaced files included (round 6).
@@ -30,9 +33,11 @@ PNG_MAGIC = b"\x89PNG\r\n\x1a\n"
 _CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}          # colour type -> samples per pixel
 
 
-def decode_png(data: bytes) -> Tuple[np.ndarray, int]:
-    """(pixels, colour type): pixels u8 (H, W) for gray / (H, W, 2) gray + alpha / (H, W, 3) RGB / (H, W, 4) RGBA; palette images
-    come back expanded to RGB (or RGBA when the file has a tRNS chunk), colour type 2 / 6."""
+def png_chunks(data: bytes, crc: str = "all"):
+    """The chunk walk of a PNG file: (IHDR fields, PLTE (n, 3) u8 or None, tRNS u8 or None, [(offset, length) of every IDAT body in
+    `data`]).  crc="all": every chunk's CRC is checked as it is met; crc="small": every chunk's but IDAT's (the device route, which
+    checks the Adler-32 of the inflated bytes instead).  ValueError for a bad signature, a truncated chunk, a CRC mismatch, a file
+    without IHDR or IDAT."""
     if data[:8] != PNG_MAGIC:
         raise ValueError("not a PNG file (bad signature)")
     pos = 8
@@ -41,25 +46,41 @@ def decode_png(data: bytes) -> Tuple[np.ndarray, int]:
     plte = trns = None
     while pos + 8 <= len(data):
         (length,), kind = struct.unpack(">I", data[pos:pos + 4]), data[pos + 4:pos + 8]
-        body = data[pos + 8:pos + 8 + length]
-        if len(body) != length or pos + 12 + length > len(data):
+        if pos + 12 + length > len(data):
             raise ValueError("truncated PNG chunk")
-        (crc,) = struct.unpack(">I", data[pos + 8 + length:pos + 12 + length])
-        if zlib.crc32(kind + body) & 0xFFFFFFFF != crc:
-            raise ValueError(f"PNG chunk {kind!r}: CRC mismatch")
-        pos += 12 + length
+        body = None if kind == b"IDAT" and crc == "small" else data[pos + 8:pos + 8 + length]
+        if body is not None:
+            (want,) = struct.unpack(">I", data[pos + 8 + length:pos + 12 + length])
+            if zlib.crc32(kind + body) & 0xFFFFFFFF != want:
+                raise ValueError(f"PNG chunk {kind!r}: CRC mismatch")
         if kind == b"IHDR":
             ihdr = struct.unpack(">IIBBBBB", body)
         elif kind == b"IDAT":
-            idat.append(body)
+            idat.append((pos + 8, length))
         elif kind == b"PLTE":
             plte = np.frombuffer(body, np.uint8).reshape(-1, 3)
         elif kind == b"tRNS":
             trns = np.frombuffer(body, np.uint8)
-        elif kind == b"IEND":
+        pos += 12 + length
+        if kind == b"IEND":
             break
     if ihdr is None or not idat:
         raise ValueError("PNG without IHDR / IDAT")
+    return ihdr, plte, trns, idat
+
+
+def device_eligible(ihdr) -> bool:
+    """What the device decoder takes (include/mavflow_png_decode.h): 8-bit samples, gray / RGB / gray + alpha / RGBA, not interlaced.
+    Everything else -- 16-bit samples, depths below 8, palette, Adam7 -- stays on decode_png."""
+    W, H, depth, ctype, comp, filt, interlace = ihdr
+    return depth == 8 and ctype in (0, 2, 4, 6) and comp == 0 and filt == 0 and interlace == 0 and W >= 1 and H >= 1
+
+
+def decode_png(data: bytes) -> Tuple[np.ndarray, int]:
+    """(pixels, colour type): pixels u8 (H, W) for gray / (H, W, 2) gray + alpha / (H, W, 3) RGB / (H, W, 4) RGBA; palette images
+    come back expanded to RGB (or RGBA when the file has a tRNS chunk), colour type 2 / 6."""
+    ihdr, plte, trns, spans = png_chunks(data)
+    idat = [data[o:o + n] for o, n in spans]
     W, H, depth, ctype, comp, filt, interlace = ihdr
     if ctype not in _CHANNELS or comp != 0 or filt != 0:
         raise ValueError(f"unsupported PNG header (colour type {ctype}, compression {comp}, filter method {filt})")
@@ -136,6 +157,100 @@ def imread(path: str) -> Optional[np.ndarray]:
     return np.ascontiguousarray(px[..., 2::-1])      # RGB(A) -> BGR
 
 
+def _to_out(px: np.ndarray, ctype: int, out: str) -> np.ndarray:
+    """decode_png's pixels in one of imread_many's forms, with the arithmetic of the device route"""
+    if out == "samples":
+        return px
+    bgr = np.repeat((px if ctype == 0 else px[..., 0])[..., None], 3, axis=2) if ctype in (0, 4) else np.ascontiguousarray(px[..., 2::-1])
+    if out == "bgr":
+        return bgr
+    b, g, r = (bgr[..., k].astype(np.uint32) for k in range(3))
+    return ((b * 1868 + g * 9617 + r * 4899 + 8192) >> 14).astype(np.uint8)      # cv2.cvtColor(COLOR_BGR2GRAY), as Context.bgr2gray
+
+
+class ImreadResult:
+    """imread_many's answer: frames[k] = file k's array (None: unreadable, as cv2.imread; None as well for a device-route file when
+    to_host=False), routes[k] = "device" / "host" (None: unreadable), device[k] = (DeviceBuffer, byte offset, shape) of a frame left
+    on the device (to_host=False; free() gives the buffers back)."""
+
+    def __init__(self, n: int) -> None:
+        self.frames = [None] * n
+        self.routes = [None] * n
+        self.device = {}
+        self._buffers = []
+
+    def free(self) -> None:
+        for b in self._buffers:
+            b.free()
+        self._buffers, self.device = [], {}
+
+
+def imread_many(paths_or_bytes, ctx, out: str = "bgr", to_host: bool = True, verify_crc: bool = False) -> ImreadResult:
+    """cv2.imread over a list of files (paths, or the files' bytes).  Files the device decodes (device_eligible) go up compressed, one
+    call per (W, H, channels) group (Context.png_decode); the rest -- and nothing else -- are read by decode_png.  out: "bgr" (cv2.imread),
+    "gray" (cvtColor(BGR2GRAY) of it) or "samples" (the file's own channels).  A file neither route can read is None, as cv2.imread's.
+    The device route checks the small chunks' CRCs and the Adler-32 of the inflated bytes, and the IDAT CRC only with verify_crc=True:
+    a file with a wrong IDAT CRC and intact data decodes there and is None on the host route."""
+    if out not in ("bgr", "gray", "samples"):
+        raise ValueError(f"imread_many: out must be 'bgr', 'gray' or 'samples', got {out!r}")
+    datas = []
+    for f in paths_or_bytes:
+        if isinstance(f, (bytes, bytearray, memoryview)):
+            datas.append(bytes(f))
+        else:
+            try:
+                with open(f, "rb") as fh:
+                    datas.append(fh.read())
+            except OSError:
+                datas.append(None)
+    res = ImreadResult(len(datas))
+    groups = {}
+    for k, data in enumerate(datas):
+        if data is None:
+            continue
+        try:
+            ihdr, _, _, _ = png_chunks(data, "all" if verify_crc else "small")
+        except (ValueError, struct.error):
+            continue
+        if device_eligible(ihdr):
+            groups.setdefault((ihdr[0], ihdr[1], ihdr[3]), []).append(k)
+        else:
+            try:
+                res.frames[k] = _to_out(*decode_png(data), out)
+                res.routes[k] = "host"
+            except (ValueError, zlib.error, struct.error):
+                pass
+    for members in groups.values():
+        for lo in range(0, len(members), _lib.PNG_DECODE_MAX_COUNT):
+            part = members[lo:lo + _lib.PNG_DECODE_MAX_COUNT]
+            files = [datas[k] for k in part]
+            W, H, ch, streams, index = ctx._png_streams(files, verify_crc)
+            if to_host:
+                imgs, status = ctx.png_decode_streams(streams, index, W, H, ch, out, return_status=True)
+                for j, k in enumerate(part):
+                    if status["code"][j] == 0:
+                        res.frames[k], res.routes[k] = imgs[j], "device"
+            else:
+                oc = {"samples": ch, "bgr": 3, "gray": 1}[out]
+                n = len(part)
+                bufs = [ctx.alloc(streams.nbytes).upload(streams), ctx.alloc(index.nbytes).upload(index), ctx.alloc(n * _lib.PNG_STATUS_DTYPE.itemsize),
+                        ctx.alloc(ctx.png_decode_scratch_bytes(W, H, ch, n))]
+                d_out = ctx.alloc(n * H * W * oc)
+                try:
+                    ctx.png_decode_dev(bufs[0], bufs[1], n, W, H, ch, out, d_out, bufs[2], bufs[3])
+                    status = bufs[2].download(_lib.PNG_STATUS_DTYPE, (n,))
+                finally:
+                    ctx.sync()
+                    for b in bufs:
+                        b.free()
+                res._buffers.append(d_out)
+                for j, k in enumerate(part):
+                    if status["code"][j] == 0:
+                        res.routes[k] = "device"
+                        res.device[k] = (d_out, j * H * W * oc, (H, W) if oc == 1 else (H, W, oc))
+    return res
+
+
 def _chunk(kind: bytes, body: bytes) -> bytes:
     return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xFFFFFFFF)
 
@@ -194,15 +309,44 @@ class PngSequenceCapture:
     one is missing (OpenCV's image-sequence capture starts at the first existing index among 0 and 1; here: `start`, default the same
     probe).  read() -> (ok, BGR frame) like cv2; get(3) / get(4) / get(7) = width / height / frame count; set(1, k) seeks."""
 
-    def __init__(self, pattern: str, start: Optional[int] = None) -> None:
+    def __init__(self, pattern: str, start: Optional[int] = None, decoder: str = "host", ahead: int = 64, ctx=None) -> None:
+        """decoder="host": every read() decodes one file on the host (imread).  decoder="device": a read() whose frame is not in hand
+        decodes the next `ahead` files in one device call (imread_many: compressed bytes up, BGR frames back); the frames are the
+        same.  ctx: the context whose stream the device route runs on (its size does not matter); None: one of the capture's own,
+        created at the first device decode and closed by release()."""
+        if decoder not in ("host", "device"):
+            raise ValueError(f"decoder must be 'host' or 'device', got {decoder!r}")
+        if ahead < 1:
+            raise ValueError(f"ahead must be at least 1, got {ahead}")
         self.pattern = pattern
+        self.decoder, self.ahead = decoder, int(ahead)
+        self._ctx, self._own_ctx, self._ahead = ctx, False, {}
         if start is None:
             start = 0 if os.path.exists(pattern % 0) else 1
         self.start = self.pos = start
-        first = imread(pattern % start)
+        first = self._frame(start)
         self._opened = first is not None
         self._size = (first.shape[1], first.shape[0]) if self._opened else (0, 0)
         self._count = None
+
+    def _frame(self, k: int):
+        """frame k as imread returns it, or None"""
+        if self.decoder == "host":
+            return imread(self.pattern % k)
+        if k not in self._ahead:
+            paths = [self.pattern % j for j in range(k, k + self.ahead)]
+            while len(paths) > 1 and not os.path.exists(paths[-1]):
+                paths.pop()
+            if self._ctx is None:
+                try:
+                    with open(paths[0], "rb") as fh:
+                        W, H = png_chunks(fh.read(), "small")[0][:2]
+                except (OSError, ValueError, struct.error):
+                    return None
+                self._ctx, self._own_ctx = _lib.Context(W, H, 1), True
+            got = imread_many(paths, self._ctx, "bgr")
+            self._ahead = {k + j: f for j, f in enumerate(got.frames)}
+        return self._ahead.get(k)
 
     def isOpened(self) -> bool:
         return self._opened
@@ -210,7 +354,7 @@ class PngSequenceCapture:
     def read(self):
         if not self._opened:
             return False, None
-        frame = imread(self.pattern % self.pos)
+        frame = self._frame(self.pos)
         if frame is None:
             return False, None
         self.pos += 1
@@ -240,3 +384,7 @@ class PngSequenceCapture:
 
     def release(self) -> None:
         self._opened = False
+        self._ahead = {}
+        if self._own_ctx and self._ctx is not None:
+            self._ctx.close()
+            self._ctx, self._own_ctx = None, False
