@@ -329,10 +329,10 @@ struct Stager {
         }
     }
 };
-enum KernelId { K_BLUR_RESIZE, K_POLYEXP, K_UPDATE, K_ITER, K_ITER_COARSE, K_FOE, K_PHI, K_MISC, K_LK_CORNERS, K_LK_PYRAMID, K_LK_TRACK, K_LK_PICK, K_COMPONENTS, K_HISTORY_PUT, K_HISTORY_TRACE, K_GTS_MAX, K_GTS_COUNT, K_GTS_LIST, K_GTS_SUM, K_COUNT };
+enum KernelId { K_BLUR_RESIZE, K_POLYEXP, K_UPDATE, K_ITER, K_ITER_COARSE, K_FOE, K_PHI, K_MISC, K_LK_CORNERS, K_LK_PYRAMID, K_LK_TRACK, K_LK_PICK, K_COMPONENTS, K_HISTORY_PUT, K_HISTORY_TRACE, K_GTS_MAX, K_GTS_COUNT, K_GTS_LIST, K_GTS_SUM, K_JPEG_INTERVALS, K_JPEG_ENTROPY, K_JPEG_IDCT, K_JPEG_FINISH, K_COUNT };
 static const char* const kKernelNames[K_COUNT] = {"blur_resize", "polyexp", "update_matrices", "blur_iter", "blur_iter_coarse",
                                                   "foe_ransac", "phi_mask_box", "misc", "lk_corners", "lk_pyramid", "lk_track", "lk_pick", "components", "history_put", "history_trace",
-                                                  "gt_stats_max", "gt_stats_count", "gt_stats_list", "gt_stats_sum"};
+                                                  "gt_stats_max", "gt_stats_count", "gt_stats_list", "gt_stats_sum", "jpeg_intervals", "jpeg_entropy", "jpeg_idct", "jpeg_finish"};
 struct ProfRec { int kid; hipEvent_t a, b; int stream; };
 struct ProfInterval { int kid; float t0, t1; int stream; };      // ms since the profile was switched on
 
@@ -5833,3 +5833,6 @@ extern "C" int mav_motion_pictures_dev(mav_ctx* c, const float* flow, int batch,
     }
     return check_launch("motion pictures");
 }
+// a profiled launch section of the JPEG decoder (kernels_jpeg.hip): launch 0 .. 3 = classes jpeg_intervals, jpeg_entropy, jpeg_idct, jpeg_finish
+JpegScope::JpegScope(mav_ctx* c, int launch) : p(new ProfScope(c, K_JPEG_INTERVALS + launch)) {}
+JpegScope::~JpegScope() { delete p; }

@@ -574,3 +574,8 @@ void launch_fill_bytes(hipStream_t st, uint8_t* p, uint8_t value, size_t n);
 // That unit holds its own host side, like the shapes unit.  The one gray value of a BGR pixel, cv2.cvtColor(COLOR_BGR2GRAY) on uint8
 // (SURVEY A.7): k_bgr2gray and the decoder's gray output both go through it, so their bits agree.
 __host__ __device__ inline uint8_t bgr2gray_px(unsigned b, unsigned g, unsigned r) { return (uint8_t)((b * 1868u + g * 9617u + r * 4899u + 8192u) >> 14); }
+
+// ---- JPEG decode (kernels_jpeg.hip, integer arithmetic only; include/mavflow_jpeg.h) ---------------------------------------------------------
+// That unit holds its own host side too.  A profiled launch section of its launch 0 .. 3 (intervals, entropy, IDCT, finish: the classes
+// "jpeg_intervals", "jpeg_entropy", "jpeg_idct", "jpeg_finish" of mav_profile_get)
+struct JpegScope { JpegScope(mav_ctx* c, int launch); ~JpegScope(); JpegScope(const JpegScope&) = delete; private: struct ProfScope* p; };

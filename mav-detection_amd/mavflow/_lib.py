@@ -212,6 +212,23 @@ PNG_STATUS_DTYPE = np.dtype([("code", "<i4"), ("adler_stream", "<u4"), ("adler_c
                              ("produced", "<u8"), ("max_length", "<u4"), ("max_distance", "<u4")])
 
 
+# every symbol include/mavflow_jpeg.h declares
+JPEG_EXPORTS = ("mav_jpeg_parse", "mav_jpeg_decode_scratch_bytes", "mav_jpeg_decode_dev", "mav_jpeg_decode", "mav_jpeg_decode_host")
+JPEG_OUT = {"samples": 0, "bgr": 1, "gray": 2}                     # MAV_JPEG_OUT_*
+JPEG_MAX_COUNT = 1024
+JPEG_ERRORS = ("OK", "TRUNCATED", "CODE", "COEF_INDEX", "RESTART", "UNSUPPORTED")     # MAV_JPEG_E_*
+# mav_jpeg_status, 40 bytes
+JPEG_STATUS_DTYPE = np.dtype([("code", "<i4"), ("intervals", "<u4"), ("consumed", "<u8"), ("mcus", "<u4"), ("nonzero", "<u4"), ("zrl", "<u4"),
+                              ("stuffed", "<u4"), ("max_code_len", "<u4"), ("pad", "<u4")])
+_JPEG_COMPONENT = np.dtype([("id", "u1"), ("h", "u1"), ("v", "u1"), ("tq", "u1"), ("td", "u1"), ("ta", "u1"), ("pad", "u1", (2,))])
+_JPEG_HUFFMAN = np.dtype([("counts", "u1", (16,)), ("values", "u1", (256,))])
+# mav_jpeg_info, 2512 bytes
+JPEG_INFO_DTYPE = np.dtype([("W", "<i4"), ("H", "<i4"), ("components", "<i4"), ("restart_interval", "<i4"), ("entropy_offset", "<u8"),
+                            ("entropy_bytes", "<u8"), ("comp", _JPEG_COMPONENT, (4,)), ("quant_defined", "u1", (4,)), ("dc_defined", "u1", (4,)),
+                            ("ac_defined", "u1", (4,)), ("pad", "u1", (4,)), ("quant", "u1", (4, 64)), ("dc", _JPEG_HUFFMAN, (4,)),
+                            ("ac", _JPEG_HUFFMAN, (4,))])
+
+
 class Gather(C.Structure):
     _fields_ = [("src_host", C.POINTER(C.c_void_p)), ("count", C.c_int), ("bytes_each", C.c_size_t), ("dst_dev", C.c_void_p)]
 
@@ -454,8 +471,79 @@ def load(path: str | None = None) -> C.CDLL:
     lib.mav_png_inflate_host.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp]                                          # z, n, raw, raw_bytes, status
     for fn in (lib.mav_png_decode_dev, lib.mav_png_decode, lib.mav_png_inflate_host):
         fn.restype = C.c_int
+    # include/mavflow_jpeg.h (JPEG_EXPORTS)
+    lib.mav_jpeg_parse.argtypes = [vp, C.c_size_t, vp]                                                               # file, n, info
+    lib.mav_jpeg_decode_scratch_bytes.restype, lib.mav_jpeg_decode_scratch_bytes.argtypes = C.c_size_t, [i, i, i, i]   # W, H, components, count
+    # ctx, files, index, info, count, W, H, out_format, out, status[, scratch]
+    lib.mav_jpeg_decode_dev.argtypes = [vp, vp, vp, vp, i, i, i, i, vp, vp, vp]
+    lib.mav_jpeg_decode.argtypes = [vp, vp, vp, vp, i, i, i, i, vp, vp]
+    lib.mav_jpeg_decode_host.argtypes = [vp, C.c_size_t, vp, i, vp, vp]                                              # file, n, info, out_format, out, status
+    for fn in (lib.mav_jpeg_parse, lib.mav_jpeg_decode_dev, lib.mav_jpeg_decode, lib.mav_jpeg_decode_host):
+        fn.restype = C.c_int
     _lib = lib
     return lib
+
+
+def jpeg_info(data):
+    """(info, None) -- mav_jpeg_parse's answer as a (1,) array of JPEG_INFO_DTYPE -- or (None, the parser's reason) for a file it refuses"""
+    lib = load()
+    raw = np.frombuffer(bytes(data) + b"\0", np.uint8)
+    info = np.zeros(1, JPEG_INFO_DTYPE)
+    rc = lib.mav_jpeg_parse(raw.ctypes.data, len(data), info.ctypes.data)
+    if rc == MAV_OK:
+        return info, None
+    why = lib.mav_last_error().decode("utf-8", "replace")
+    name = JPEG_ERRORS[rc] if 0 < rc < len(JPEG_ERRORS) else str(rc)
+    return None, f"MAV_JPEG_E_{name} ({rc}): {why}"
+
+
+def jpeg_parse(data) -> dict:
+    """mav_jpeg_parse as a dict: W, H, components [(id, h, v, tq, td, ta)], quant {id: (64,) u8 in natural order}, dc / ac {id: (counts (16,),
+    values (sum,))}, restart_interval, entropy_offset, entropy_bytes.  ValueError with the parser's reason for a file it refuses."""
+    info, why = jpeg_info(data)
+    if info is None:
+        raise ValueError(f"jpeg_parse(): {why}")
+    r = info[0]
+    n = int(r["components"])
+
+    def tables(kind):
+        return {t: (r[kind][t]["counts"].copy(), r[kind][t]["values"][:int(r[kind][t]["counts"].sum())].copy())
+                for t in range(4) if r[kind + "_defined"][t]}
+    return {"W": int(r["W"]), "H": int(r["H"]),
+            "components": [tuple(int(r["comp"][c][k]) for k in ("id", "h", "v", "tq", "td", "ta")) for c in range(n)],
+            "quant": {t: r["quant"][t].copy() for t in range(4) if r["quant_defined"][t]}, "dc": tables("dc"), "ac": tables("ac"),
+            "restart_interval": int(r["restart_interval"]), "entropy_offset": int(r["entropy_offset"]), "entropy_bytes": int(r["entropy_bytes"])}
+
+
+def jpeg_decode_host(data, out: str = "bgr", return_status: bool = False):
+    """mav_jpeg_decode_host: one baseline JPEG file decoded on the host by the source the device runs -> (H, W, 3) BGR, (H, W) gray or
+    the samples (H, W[, 3]); None for a file the parser or the decoder refuses (return_status=True: (array or None, status record or
+    the parser's reason))."""
+    if out not in JPEG_OUT:
+        raise ValueError(f"jpeg_decode_host(): out must be one of {sorted(JPEG_OUT)}, got {out!r}")
+    info, why = jpeg_info(data)
+    if info is None:
+        return (None, why) if return_status else None
+    comps = int(info["components"][0])
+    oc = {"samples": comps, "bgr": 3, "gray": 1}[out]
+    raw = np.frombuffer(bytes(data) + b"\0", np.uint8)
+    img = np.empty((int(info["H"][0]), int(info["W"][0]), oc), np.uint8)
+    status = np.zeros(1, JPEG_STATUS_DTYPE)
+    check(load().mav_jpeg_decode_host(raw.ctypes.data, len(data), info.ctypes.data, JPEG_OUT[out], img.ctypes.data, status.ctypes.data))
+    if oc == 1:
+        img = img[..., 0]
+    if return_status:
+        return img, status[0]
+    return img if status["code"][0] == 0 else None
+
+
+def loaded() -> bool:
+    """True when libmavflow.so is loaded, or loads now (it is built in-tree); False where there is no library to load"""
+    try:
+        load()
+        return True
+    except (ImportError, OSError):
+        return False
 
 
 def check(rc: int) -> None:
@@ -1770,6 +1858,133 @@ class Context:
         try:
             if shape[1:] != (self.H, self.W):
                 raise ValueError(f"farneback_png(): the files are {shape[2]} x {shape[1]}, the context is {self.W} x {self.H}")
+            d_flow = self.alloc(n * self.H * self.W * 8)
+            check(self.lib.mav_farneback_dev(self.h, d_gray.ptr, d_gray.ptr + self.W * self.H, n, d_flow.ptr))
+            return d_flow.download(np.float32, (n, self.H, self.W, 2))
+        finally:
+            self.sync()
+            d_gray.free()
+            if d_flow is not None:
+                d_flow.free()
+
+    # -- JPEG decode on the device (include/mavflow_jpeg.h) --------------------------------------------------------
+    @staticmethod
+    def _jpeg_pack(files):
+        """(W, H, components, files u8, index (n, 2) u64, infos (n,) JPEG_INFO_DTYPE) of baseline JPEG files of one size and component
+        count, packed back to back as they are.  ValueError names the file and carries the parser's reason."""
+        shape, index, infos, at = None, [], [], 0
+        for k, data in enumerate(files):
+            info, why = jpeg_info(data)
+            if info is None:
+                raise ValueError(f"jpeg_decode(): file {k}: {why}")
+            this = (int(info["W"][0]), int(info["H"][0]), int(info["components"][0]))
+            if shape is None:
+                shape = this
+            elif this != shape:
+                raise ValueError(f"jpeg_decode(): file {k} is {this[0]} x {this[1]} x {this[2]}, file 0 is {shape[0]} x {shape[1]} x {shape[2]}")
+            infos.append(info)
+            index.append((at, len(data)))
+            at += len(data)
+        if shape is None:
+            raise ValueError("jpeg_decode(): no files")
+        if len(index) > JPEG_MAX_COUNT:
+            raise ValueError(f"jpeg_decode(): {len(index)} files in one call, at most {JPEG_MAX_COUNT}")
+        packed = np.frombuffer(b"".join(bytes(f) for f in files) + b"\0", np.uint8)
+        return shape[0], shape[1], shape[2], packed, np.array(index, np.uint64).reshape(-1, 2), np.concatenate(infos)
+
+    @staticmethod
+    def _jpeg_raise(status, what="jpeg_decode()"):
+        bad = np.flatnonzero(status["code"] != 0)
+        if bad.size:
+            k = int(bad[0])
+            code = int(status["code"][k])
+            name = JPEG_ERRORS[code] if 0 <= code < len(JPEG_ERRORS) else str(code)
+            raise ValueError(f"{what}: file {k}: MAV_JPEG_E_{name} ({code}) after {int(status['consumed'][k])} bytes of its entropy segment"
+                             + (f"; files {bad.tolist()} failed" if bad.size > 1 else ""))
+
+    def jpeg_decode(self, files, out: str = "bgr", return_status: bool = False):
+        """Baseline JPEG files (bytes) of ONE size and component count -> (n, H, W, 3) BGR as cv2.imread returns them (out="bgr"),
+        (n, H, W) gray as cvtColor(BGR2GRAY) of that (out="gray"; not IMREAD_GRAYSCALE), or the upsampled Y, Cb, Cr (n, H, W[, 3])
+        (out="samples").  The files go up as they are; restart-marker search, Huffman decoding, IDCT, upsampling and conversion run on
+        the device.  The size is the files' own, not the context's.  ValueError names the first file the parser or the decoder
+        refused; return_status=True returns (array, statuses) instead and raises nothing for the decoder's verdicts (a refused image
+        is all zero)."""
+        if out not in JPEG_OUT:
+            raise ValueError(f"jpeg_decode(): out must be one of {sorted(JPEG_OUT)}, got {out!r}")
+        W, H, comps, packed, index, infos = self._jpeg_pack(list(files))
+        return self.jpeg_decode_packed(packed, index, infos, W, H, out, return_status)
+
+    def jpeg_decode_packed(self, packed, index, infos, W: int, H: int, out: str = "bgr", return_status: bool = False):
+        """mav_jpeg_decode on files packed in one array: packed u8, index (n, 2) u64 of (offset, size), infos (n,) JPEG_INFO_DTYPE."""
+        packed = np.ascontiguousarray(packed, np.uint8)
+        index = np.ascontiguousarray(index, np.uint64).reshape(-1, 2)
+        infos = np.ascontiguousarray(infos, JPEG_INFO_DTYPE).reshape(-1)
+        n = index.shape[0]
+        if n != infos.shape[0] or n < 1:
+            raise ValueError(f"jpeg_decode_packed(): {n} index rows, {infos.shape[0]} infos")
+        if int((index[:, 0] + index[:, 1]).max()) > packed.size:
+            raise ValueError("jpeg_decode_packed(): a file ends past the buffer")
+        comps = 3 if int(infos["components"][0]) == 3 else 1
+        oc = {"samples": comps, "bgr": 3, "gray": 1}[out]
+        img = np.empty((n, int(H), int(W), oc), np.uint8)
+        status = np.zeros(n, JPEG_STATUS_DTYPE)
+        check(self.lib.mav_jpeg_decode(self.h, _ptr(packed), _ptr(index), _ptr(infos), n, int(W), int(H), JPEG_OUT[out], _ptr(img), _ptr(status)))
+        if oc == 1:
+            img = img[..., 0]
+        if return_status:
+            return img, status
+        self._jpeg_raise(status)
+        return img
+
+    def jpeg_decode_dev(self, files_ptr, index_ptr, info_ptr, count: int, W: int, H: int, out: str, out_ptr, status_ptr, scratch_ptr) -> None:
+        """mav_jpeg_decode_dev: device pointers, enqueue only.  scratch: jpeg_decode_scratch_bytes(W, H, components, count) bytes."""
+        check(self.lib.mav_jpeg_decode_dev(self.h, _dev_ptr(files_ptr), _dev_ptr(index_ptr), _dev_ptr(info_ptr), int(count), int(W), int(H),
+                                           JPEG_OUT[out], _dev_ptr(out_ptr), _dev_ptr(status_ptr), _dev_ptr(scratch_ptr)))
+
+    def jpeg_decode_scratch_bytes(self, W: int, H: int, components: int, count: int) -> int:
+        return int(self.lib.mav_jpeg_decode_scratch_bytes(int(W), int(H), int(components), int(count)))
+
+    def jpeg_decode_to_device(self, files, out: str = "bgr", return_status: bool = False):
+        """jpeg_decode with the frames LEFT on the device: (DeviceBuffer of (n, H, W[, c]) u8, shape[, statuses]).  The statuses are
+        checked (one synchronisation, 40 bytes per file come back) unless they are returned; the caller frees the buffer."""
+        W, H, comps, packed, index, infos = self._jpeg_pack(list(files))
+        n = index.shape[0]
+        oc = {"samples": comps, "bgr": 3, "gray": 1}[out]
+        d_out = self.alloc(n * H * W * oc)
+        bufs = []
+        try:
+            bufs = [self.alloc(packed.nbytes).upload(packed), self.alloc(index.nbytes).upload(index), self.alloc(infos.nbytes).upload(infos),
+                    self.alloc(n * JPEG_STATUS_DTYPE.itemsize), self.alloc(self.jpeg_decode_scratch_bytes(W, H, comps, n))]
+            self.jpeg_decode_dev(bufs[0], bufs[1], bufs[2], n, W, H, out, d_out, bufs[3], bufs[4])
+            status = bufs[3].download(JPEG_STATUS_DTYPE, (n,))         # (a stream-ordered copy and the call's one synchronisation)
+            if not return_status:
+                self._jpeg_raise(status)
+        except Exception:
+            self.sync()
+            d_out.free()
+            raise
+        finally:
+            self.sync()
+            for b in bufs:
+                b.free()
+        shape = (n, H, W) if oc == 1 else (n, H, W, oc)
+        return (d_out, shape, status) if return_status else (d_out, shape)
+
+    def farneback_jpeg(self, files) -> np.ndarray:
+        """farneback_png for JPEG files: the flow of every consecutive pair of n + 1 baseline JPEG files of the context's size ->
+        (n, H, W, 2) float32.  The files are decoded to ONE gray block on the device, where mav_farneback_dev reads frames 0 .. n - 1
+        as `prev` and 1 .. n as `next`.  Byte for byte farneback(gray[:-1], gray[1:]) of the decoded frames."""
+        files = list(files)
+        n = len(files) - 1
+        if n < 1:
+            raise ValueError("farneback_jpeg(): a sequence needs at least two files")
+        if n > self.max_batch:
+            raise ValueError(f"farneback_jpeg(): {n} pairs on a context of max_batch {self.max_batch}")
+        d_gray, shape = self.jpeg_decode_to_device(files, "gray")
+        d_flow = None
+        try:
+            if shape[1:] != (self.H, self.W):
+                raise ValueError(f"farneback_jpeg(): the files are {shape[2]} x {shape[1]}, the context is {self.W} x {self.H}")
             d_flow = self.alloc(n * self.H * self.W * 8)
             check(self.lib.mav_farneback_dev(self.h, d_gray.ptr, d_gray.ptr + self.W * self.H, n, d_flow.ptr))
             return d_flow.download(np.float32, (n, self.H, self.W, 2))

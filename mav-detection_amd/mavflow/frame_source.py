@@ -13,7 +13,11 @@ cv2 is not part of this build; this module is that capture for PNG sequences:
     PngSequenceCapture(pattern)          cv2.VideoCapture(pattern)'s read() / get(3|4|7) / isOpened() / release() for an image sequence;
                                          decoder="device" decodes `ahead` files per device call.
     imread_many(files, ctx, out)         imread over a list: 8-bit non-interlaced gray / RGB (+ alpha) files are inflated, un-filtered and
-                                         converted on the device (include/mavflow_png_decode.h), the rest by decode_png.
+                                         converted on the device (include/mavflow_png_decode.h), the rest by decode_png.  A file that
+                                         starts with FF D8 is a JPEG: baseline files are decoded on the device (include/mavflow_jpeg.h),
+                                         the rest are refused with the parser's reason.
+    jpg_to_png(img_path, ctx)            the reference's Dataset.jpg_to_png (src/datasets/dataset.py:240-248): N.jpg -> image_%05d.png,
+                                         decoded and encoded on the device.
 
 The decoder is pinned by PIL-decoded fixtures generated in the build container (tools/gen_png_fixtures.py,
 tests/golden/png_frames.npz), 16-bit and interlaced files included (round 6).
@@ -30,6 +34,7 @@ import numpy as np
 from . import _lib
 
 PNG_MAGIC = b"\x89PNG\r\n\x1a\n"
+JPEG_MAGIC = b"\xff\xd8"
 _CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}          # colour type -> samples per pixel
 
 
@@ -143,11 +148,14 @@ def decode_png(data: bytes) -> Tuple[np.ndarray, int]:
 
 
 def imread(path: str) -> Optional[np.ndarray]:
-    """cv2.imread(path): BGR u8 (H, W, 3), None when the file does not exist or cannot be read as a PNG.  (Gray replicated into three
-    channels, alpha dropped -- IMREAD_COLOR, the flag the reference's calls default to.)"""
+    """cv2.imread(path): BGR u8 (H, W, 3), None when the file does not exist or cannot be read as a PNG or a baseline JPEG.  (Gray
+    replicated into three channels, alpha dropped -- IMREAD_COLOR, the flag the reference's calls default to.)  The file's first bytes
+    decide: FF D8 goes to mav_jpeg_decode_host (None when the library is not loaded), anything else to decode_png."""
     try:
         with open(path, "rb") as f:
             data = f.read()
+        if data[:2] == JPEG_MAGIC:                   # baseline JPEG: the decoding source of the device route, run on the host
+            return _lib.jpeg_decode_host(data, "bgr") if _lib.loaded() else None
         px, ctype = decode_png(data)
     except (OSError, ValueError, zlib.error):
         return None
@@ -171,12 +179,14 @@ def _to_out(px: np.ndarray, ctype: int, out: str) -> np.ndarray:
 class ImreadResult:
     """imread_many's answer: frames[k] = file k's array (None: unreadable, as cv2.imread; None as well for a device-route file when
     to_host=False), routes[k] = "device" / "host" (None: unreadable), device[k] = (DeviceBuffer, byte offset, shape) of a frame left
-    on the device (to_host=False; free() gives the buffers back)."""
+    on the device (to_host=False; free() gives the buffers back), refused[k] = why file k, a JPEG, was not taken: the parser's reason
+    (a progressive file, say) or the decoder's verdict."""
 
     def __init__(self, n: int) -> None:
         self.frames = [None] * n
         self.routes = [None] * n
         self.device = {}
+        self.refused = {}
         self._buffers = []
 
     def free(self) -> None:
@@ -190,7 +200,10 @@ def imread_many(paths_or_bytes, ctx, out: str = "bgr", to_host: bool = True, ver
     call per (W, H, channels) group (Context.png_decode); the rest -- and nothing else -- are read by decode_png.  out: "bgr" (cv2.imread),
     "gray" (cvtColor(BGR2GRAY) of it) or "samples" (the file's own channels).  A file neither route can read is None, as cv2.imread's.
     The device route checks the small chunks' CRCs and the Adler-32 of the inflated bytes, and the IDAT CRC only with verify_crc=True:
-    a file with a wrong IDAT CRC and intact data decodes there and is None on the host route."""
+    a file with a wrong IDAT CRC and intact data decodes there and is None on the host route.
+    A file that starts with FF D8 is a JPEG and takes the JPEG route: baseline files go up as they are, one call per (W, H, components)
+    group (Context.jpeg_decode; "samples" are then the upsampled Y, Cb, Cr); a file mav_jpeg_parse refuses (a progressive one, say) or
+    the decoder refuses is None, and refused[k] holds the reason."""
     if out not in ("bgr", "gray", "samples"):
         raise ValueError(f"imread_many: out must be 'bgr', 'gray' or 'samples', got {out!r}")
     datas = []
@@ -204,9 +217,16 @@ def imread_many(paths_or_bytes, ctx, out: str = "bgr", to_host: bool = True, ver
             except OSError:
                 datas.append(None)
     res = ImreadResult(len(datas))
-    groups = {}
+    groups, jpeg_groups = {}, {}
     for k, data in enumerate(datas):
         if data is None:
+            continue
+        if data[:2] == JPEG_MAGIC:
+            info, why = _lib.jpeg_info(data)
+            if info is None:
+                res.refused[k] = why
+            else:
+                jpeg_groups.setdefault((int(info["W"][0]), int(info["H"][0]), int(info["components"][0])), []).append(k)
             continue
         try:
             ihdr, _, _, _ = png_chunks(data, "all" if verify_crc else "small")
@@ -248,7 +268,90 @@ def imread_many(paths_or_bytes, ctx, out: str = "bgr", to_host: bool = True, ver
                     if status["code"][j] == 0:
                         res.routes[k] = "device"
                         res.device[k] = (d_out, j * H * W * oc, (H, W) if oc == 1 else (H, W, oc))
+    for (W, H, comps), members in jpeg_groups.items():
+        for lo in range(0, len(members), _lib.JPEG_MAX_COUNT):
+            part = members[lo:lo + _lib.JPEG_MAX_COUNT]
+            files = [datas[k] for k in part]
+            oc = {"samples": comps, "bgr": 3, "gray": 1}[out]
+            if to_host:
+                imgs, status = ctx.jpeg_decode(files, out, return_status=True)
+            else:
+                d_out, _, status = ctx.jpeg_decode_to_device(files, out, return_status=True)
+                res._buffers.append(d_out)
+            for j, k in enumerate(part):
+                code = int(status["code"][j])
+                if code:
+                    res.refused[k] = f"MAV_JPEG_E_{_lib.JPEG_ERRORS[code]} ({code}) after {int(status['consumed'][j])} bytes of its entropy segment"
+                    continue
+                res.routes[k] = "device"
+                if to_host:
+                    res.frames[k] = imgs[j]
+                else:
+                    res.device[k] = (d_out, j * H * W * oc, (H, W) if oc == 1 else (H, W, oc))
     return res
+
+
+def jpg_to_png(img_path: str, ctx, png_encoder: str = "device", remove: bool = True) -> dict:
+    """The reference's Dataset.jpg_to_png (src/datasets/dataset.py:240-248): every `N.jpg` of the directory becomes `image_%05d.png` with
+    N as its index, and the .jpg is removed (remove=False keeps it).  The JPEG files go up compressed and are decoded on the device
+    (mav_jpeg_decode_dev); png_encoder="device": the BGR frames stay there as mav_png_encode_dev's input and the PNG files come back
+    compressed, so no pixel crosses PCIe (the files must then have the context's size); png_encoder="host": the frames come back and
+    are written by imwrite.  Returns {"written": [paths], "refused": {path: reason}}; a refused file is left where it is."""
+    if png_encoder not in ("device", "host"):
+        raise ValueError(f"png_encoder must be 'device' or 'host', got {png_encoder!r}")
+    names = sorted(n for n in os.listdir(img_path) if os.path.splitext(n)[1] == ".jpg")
+    for n in names:
+        int(n.replace(".jpg", ""))                   # the reference's naming: a file that is no number is an error before anything is written
+    groups, refused, written, datas = {}, {}, [], {}
+    for n in names:
+        with open(os.path.join(img_path, n), "rb") as f:
+            datas[n] = f.read()
+        info, why = _lib.jpeg_info(datas[n])
+        if info is None:
+            refused[os.path.join(img_path, n)] = why
+        else:
+            groups.setdefault((int(info["W"][0]), int(info["H"][0]), int(info["components"][0])), []).append(n)
+    for (W, H, comps), members in groups.items():
+        if png_encoder == "device" and (W, H) != (ctx.W, ctx.H):
+            raise ValueError(f"jpg_to_png: {members[0]} is {W} x {H}, the context (whose PNG encoder is used) is {ctx.W} x {ctx.H}")
+        for lo in range(0, len(members), _lib.JPEG_MAX_COUNT):
+            part = members[lo:lo + _lib.JPEG_MAX_COUNT]
+            files = [datas[n] for n in part]
+            if png_encoder == "host":
+                imgs, status = ctx.jpeg_decode(files, "bgr", return_status=True)
+                pngs = [encode_png(imgs[j]) if status["code"][j] == 0 else None for j in range(len(part))]
+            else:
+                pngs = _jpeg_to_png_on_device(ctx, files, W, H)
+            for n, png in zip(part, pngs):
+                src = os.path.join(img_path, n)
+                if png is None:
+                    refused[src] = "the decoder refused the file"
+                    continue
+                dst = os.path.join(img_path, f"image_{int(n.replace('.jpg', '')):05d}.png")
+                with open(dst, "wb") as f:
+                    f.write(png)
+                written.append(dst)
+                if remove:
+                    os.remove(src)
+    return {"written": written, "refused": refused}
+
+
+def _jpeg_to_png_on_device(ctx, files, W: int, H: int):
+    """JPEG files -> PNG files (None for one the decoder refused): mav_jpeg_decode_dev's output is mav_png_encode_dev's input"""
+    n = len(files)
+    d_bgr, _, status = ctx.jpeg_decode_to_device(files, "bgr", return_status=True)
+    bound = ctx.lib.mav_png_bound(W, H, 3)
+    bufs = [d_bgr]
+    try:
+        bufs += [ctx.alloc(n * bound), ctx.alloc(16 * n)]
+        _lib.check(ctx.lib.mav_png_encode_dev(ctx.h, d_bgr.ptr, n, 3, bufs[1].ptr, n * bound, bufs[2].ptr))
+        index = bufs[2].download(np.uint64, (n, 2))
+        streams = bufs[1].download(np.uint8, (int((index[:, 0] + index[:, 1]).max()),))
+    finally:
+        ctx.sync()
+        for b in bufs:
+            b.free()
+    return [png_wrap(W, H, 3, streams[int(o):int(o) + int(z)].tobytes()) if status["code"][j] == 0 else None for j, (o, z) in enumerate(index)]
 
 
 def _chunk(kind: bytes, body: bytes) -> bytes:
