@@ -3,6 +3,8 @@ definition) and tests/test_gpu_affine.py (the device against the restatement, by
 can go wrong: n around the wavefront (63, 64, 65), the minimum (3, 4), the detector's 1000 and one LDS chunk + 1; max_iters around the
 choice kernel's block of 64 and the default 2000; batch 1 and 3 with different data per item.  A case's reference is computed once
 (reference()) and never written again."""
+import os
+import re
 from collections import namedtuple
 
 import numpy as np
@@ -16,6 +18,37 @@ CONFIDENCES = (0.5, 0.99, 0.999)
 TIE_SIZES = (3, 4, 5, 63, 64, 65, 257, 1000, 4097)
 FLOW_FRAMES = ((66, 33), (131, 67))
 TRUE_M = np.array([[1.02, -0.03, 4.5], [0.025, 0.98, -2.25]])
+
+KERNELS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mav-detection_amd", "csrc", "kernels_affine.hip")
+CAP_BATCH = 16                             # max_batch and batch of the calls whose score grid is capped
+CAP_ITERS = (2049, 4096)                   # the first max_iters at which launch_affine_score's grid is capped at batch 16, and twice the cap
+
+
+def source_constants(text=None) -> dict:
+    """the constants of launch_affine_score as kernels_affine.hip defines them, read as text"""
+    if text is None:
+        with open(KERNELS) as f:
+            text = f.read()
+    out = {k: int(re.search(rf"^#define {k} (\d+)\b", text, re.M).group(1)) for k in ("AFF_THREADS", "AFF_CHUNK", "AFF_HYP_PER_WAVE", "AFF_GRID_CAP")}
+    assert re.search(r"^#define AFF_WAVES \(AFF_THREADS / 64\)", text, re.M)
+    out["AFF_WAVES"] = out["AFF_THREADS"] // 64
+    out["text"] = text
+    return out
+
+
+def score_blocks(max_iters: int, B: int, c=None) -> tuple:
+    """launch_affine_score: `per = ceil(max_iters / (AFF_WAVES * AFF_HYP_PER_WAVE)); cap = max(1, AFF_GRID_CAP / B)` -> (per, cap); the
+    grid is min(per, cap) workgroups per item"""
+    c = c or source_constants()
+    g = c["AFF_WAVES"] * c["AFF_HYP_PER_WAVE"]
+    return (max_iters + g - 1) // g, max(1, c["AFF_GRID_CAP"] // B)
+
+
+def score_grid(max_iters: int, B: int, c=None) -> str:
+    """"per-item": every workgroup has its AFF_WAVES * AFF_HYP_PER_WAVE hypotheses; "capped": fewer workgroups than that, a longer stride"""
+    per, cap = score_blocks(max_iters, B, c)
+    return "capped" if per > cap else "per-item"
+
 
 # dev_only: the host form refuses the case (bad triples) or the case is stated for the _dev form (non-finite pairs)
 Case = namedtuple("Case", "name src dst triples threshold confidence refine dev_only")
@@ -137,9 +170,37 @@ def _table():
     return out + _special()
 
 
+def late_winner(n, max_iters, B, seed, tail=6, **kw):
+    """_batch's scenes with the triples rearranged: every hypothesis but the last `tail` samples gross outliers alone (few inliers, need[]
+    stays above max_iters, the loop keeps running), the last `tail` sample true inliers alone -- the winner's count is one of the last the
+    score kernel writes"""
+    s = [scene(n, seed + 10 * b, M=TRUE_M + 0.01 * b, **kw) for b in range(B)]
+    t = triples_for(seed + 2, n, max_iters, B)
+    for b in range(B):
+        bad_i, good_i = np.flatnonzero(~s[b][2]), np.flatnonzero(s[b][2])
+        t[b, :max_iters - tail] = bad_i[triples_for(seed + 3 + b, len(bad_i), max_iters - tail, 1)[0]]
+        t[b, max_iters - tail:] = good_i[triples_for(seed + 4 + b, len(good_i), tail, 1)[0]]
+    return np.stack([x[0] for x in s]), np.stack([x[1] for x in s]), t
+
+
+def _cap_table():
+    """batch 16 on a context of max_batch 16, different data per item, 40 % outliers: the score grid is capped (score_grid).  The drawn
+    triples at every (max_iters, n), and at two of them the same scenes with the winner among the last hypotheses"""
+    out = []
+    for mi in CAP_ITERS:
+        for n in (65, CHUNK + 1):
+            src, dst, t = _batch(n, mi, CAP_BATCH, 400 + n + mi, noise=0.4, outliers=0.4)
+            out.append(Case(f"n{n}_it{mi}_b{CAP_BATCH}", src, dst, t, 3.0, 0.99, 1, False))
+    for mi, n in ((CAP_ITERS[0], 65), (CAP_ITERS[1], CHUNK + 1)):
+        src, dst, t = late_winner(n, mi, CAP_BATCH, 400 + n + mi, noise=0.4, outliers=0.4)
+        out.append(Case(f"n{n}_it{mi}_b{CAP_BATCH}_late", src, dst, t, 3.0, 0.99, 1, False))
+    return out
+
+
 CASES = _table()
-BY_NAME = {c.name: c for c in CASES}
-assert len(BY_NAME) == len(CASES)
+CAP_CASES = _cap_table()
+BY_NAME = {c.name: c for c in CASES + CAP_CASES}
+assert len(BY_NAME) == len(CASES) + len(CAP_CASES)
 _refs = {}
 
 

@@ -5,6 +5,8 @@ max_iters around the choice kernel's block of 64 slots (6, 7: ten slots per iter
 workgroup, the wavefront) and the default 1000; batch 1 and 3 with different data per item.  Scenes have fundamental_cases.scene's
 geometry, under the proper camera K_CAM and under the reference's literal camera (focal 1 / tan(pi / 4), pp (0, 0)) on pixel
 coordinates.  A case's reference is computed once (reference()) and never written again."""
+import os
+import re
 from collections import namedtuple
 
 import numpy as np
@@ -20,6 +22,41 @@ K_CAM = FC.K_CAM
 CAM = (500.0, 500.0, 320.0, 240.0)         # K_CAM as (fx, fy, cx, cy)
 LITERAL = (1.0 / np.tan(np.pi / 4), 1.0 / np.tan(np.pi / 4), 0.0, 0.0)     # the reference's focal_length, pp (0, 0)
 STRONG = (FC.rotation(0.1, -0.15, 0.12), np.array([3.0, 0.5, 1.0]))          # a strong camera motion
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+KERNELS = os.path.join(ROOT, "mav-detection_amd", "csrc", "kernels_essential.hip")
+INTERNAL = os.path.join(ROOT, "mav-detection_amd", "csrc", "mavflow_internal.h")
+CAP_BATCH = 16                             # max_batch and batch of the calls whose score grid is capped
+CAP_ITERS = 205                            # the first max_iters at which launch_em_score's grid is capped at batch 16
+
+
+def source_constants(text=None) -> dict:
+    """the constants of launch_em_score as kernels_essential.hip (and, EM_SLOTS, mavflow_internal.h) define them, read as text"""
+    if text is None:
+        with open(KERNELS) as f:
+            text = f.read()
+    out = {k: int(re.search(rf"^#define {k} (\d+)\b", text, re.M).group(1)) for k in ("EM_THREADS", "EM_CHUNK", "EM_SLOTS_PER_WAVE", "EM_GRID_CAP")}
+    assert re.search(r"^#define EM_WAVES \(EM_THREADS / 64\)", text, re.M)
+    out["EM_WAVES"] = out["EM_THREADS"] // 64
+    with open(INTERNAL) as f:
+        out["EM_SLOTS"] = int(re.search(r"^#define EM_SLOTS (\d+)\b", f.read(), re.M).group(1))
+    out["text"] = text
+    return out
+
+
+def score_blocks(max_iters: int, B: int, c=None) -> tuple:
+    """launch_em_score: `slots = EM_SLOTS * max_iters; per = ceil(slots / (EM_WAVES * EM_SLOTS_PER_WAVE)); cap = max(1, EM_GRID_CAP / B)`
+    -> (per, cap); the grid is min(per, cap) workgroups per item"""
+    c = c or source_constants()
+    g = c["EM_WAVES"] * c["EM_SLOTS_PER_WAVE"]
+    return (c["EM_SLOTS"] * max_iters + g - 1) // g, max(1, c["EM_GRID_CAP"] // B)
+
+
+def score_grid(max_iters: int, B: int, c=None) -> str:
+    """"per-item": every workgroup has its EM_WAVES * EM_SLOTS_PER_WAVE slots; "capped": fewer workgroups than that, a longer stride"""
+    per, cap = score_blocks(max_iters, B, c)
+    return "capped" if per > cap else "per-item"
+
 
 # dev_only: the host form refuses the case (bad subsets) or the case is stated for the _dev form (non-finite pairs)
 Case = namedtuple("Case", "name src dst subsets threshold confidence camera dev_only")
@@ -164,9 +201,37 @@ def _table():
     return out + _special()
 
 
+def late_winner(n, max_iters, B, seed, tail=6, **kw):
+    """_batch's scenes with the subsets rearranged: every hypothesis but the last `tail` samples gross outliers alone (few inliers, need[]
+    stays above max_iters, the loop keeps running), the last `tail` sample true inliers alone -- the winner's count is one of the last the
+    score kernel writes"""
+    s = [scene(n, seed + 10 * b, k=b, **kw) for b in range(B)]
+    t = subsets_for(seed + 2, n, max_iters, B)
+    for b in range(B):
+        bad_i, good_i = np.flatnonzero(~s[b][2]), np.flatnonzero(s[b][2])
+        t[b, :max_iters - tail] = bad_i[subsets_for(seed + 3 + b, len(bad_i), max_iters - tail, 1)[0]]
+        t[b, max_iters - tail:] = good_i[subsets_for(seed + 4 + b, len(good_i), tail, 1)[0]]
+    return np.stack([x[0] for x in s]), np.stack([x[1] for x in s]), t
+
+
+def _cap_table():
+    """batch 16 on a context of max_batch 16, different data per item, 40 % outliers: the score grid is capped (score_grid).  Per n the
+    drawn subsets, and at n = CHUNK + 1 (a count added to across two chunks) the same scenes with the winner among the last
+    hypotheses"""
+    out = []
+    for n in (65, CHUNK + 1):
+        src, dst, t = _batch(n, CAP_ITERS, CAP_BATCH, 400 + n, noise=0.4, outliers=0.4)
+        out.append(Case(f"n{n}_it{CAP_ITERS}_b{CAP_BATCH}", src, dst, t, 1.0, 0.999, CAM, False))
+        if n == CHUNK + 1:
+            src, dst, t = late_winner(n, CAP_ITERS, CAP_BATCH, 400 + n, noise=0.4, outliers=0.4)
+            out.append(Case(f"n{n}_it{CAP_ITERS}_b{CAP_BATCH}_late", src, dst, t, 1.0, 0.999, CAM, False))
+    return out
+
+
 CASES = _table()
-BY_NAME = {c.name: c for c in CASES}
-assert len(BY_NAME) == len(CASES)
+CAP_CASES = _cap_table()
+BY_NAME = {c.name: c for c in CASES + CAP_CASES}
+assert len(BY_NAME) == len(CASES) + len(CAP_CASES)
 _refs = {}
 
 

@@ -4,6 +4,8 @@ restatement, byte for byte).  Shapes are the smallest at which the kernels can g
 (63, 64, 65), the detector's 1000 and one LDS chunk + 1; max_iters around the choice kernel's block of 64 slots (21, 22: three slots per
 iteration), around 64 iterations and the default 1000; batch 1 and 3 with different data per item.  A case's reference is computed once
 (reference()) and never written again."""
+import os
+import re
 from collections import namedtuple
 
 import numpy as np
@@ -17,6 +19,49 @@ CONFIDENCES = (0.5, 0.99, 0.999)
 TIE_SIZES = (7, 8, 63, 64, 65, 257, 1000, 1025)
 FLOW_FRAMES = ((66, 33), (131, 67))
 K_CAM = np.array([[500.0, 0.0, 320.0], [0.0, 500.0, 240.0], [0.0, 0.0, 1.0]])
+
+KERNELS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mav-detection_amd", "csrc", "kernels_fundamental.hip")
+CAP_BATCH = 16                             # max_batch and batch of the calls whose score grid is capped
+CAP_ITERS = 683                            # the first max_iters at which launch_fm_score's grid is capped at batch 16
+EPI_FRAME, EPI_BATCH = (397, 331), 2       # the dense pass past its cap: 131 407 px = 512 * 256 + 335
+
+
+def source_constants(text=None) -> dict:
+    """the constants of launch_fm_score and launch_epipolar_residual as kernels_fundamental.hip defines them, read as text"""
+    if text is None:
+        with open(KERNELS) as f:
+            text = f.read()
+    out = {k: int(re.search(rf"^#define {k} (\d+)\b", text, re.M).group(1)) for k in ("FM_THREADS", "FM_CHUNK", "FM_SLOTS_PER_WAVE", "FM_GRID_CAP", "EPI_WG", "EPI_CAP")}
+    assert re.search(r"^#define FM_WAVES \(FM_THREADS / 64\)", text, re.M)
+    out["FM_WAVES"] = out["FM_THREADS"] // 64
+    out["text"] = text
+    return out
+
+
+def score_blocks(max_iters: int, B: int, c=None) -> tuple:
+    """launch_fm_score: `slots = 3 * max_iters; per = ceil(slots / (FM_WAVES * FM_SLOTS_PER_WAVE)); cap = max(1, FM_GRID_CAP / B)`
+    -> (per, cap); the grid is min(per, cap) workgroups per item"""
+    c = c or source_constants()
+    g = c["FM_WAVES"] * c["FM_SLOTS_PER_WAVE"]
+    return (3 * max_iters + g - 1) // g, max(1, c["FM_GRID_CAP"] // B)
+
+
+def score_grid(max_iters: int, B: int, c=None) -> str:
+    """"per-item": every workgroup has its FM_WAVES * FM_SLOTS_PER_WAVE slots; "capped": fewer workgroups than that, a longer stride"""
+    per, cap = score_blocks(max_iters, B, c)
+    return "capped" if per > cap else "per-item"
+
+
+def epi_stride_forms(n0: int, c=None) -> set:
+    """k_epipolar_residual's `for (p = blockIdx.x * EPI_WG + threadIdx.x; p < n0; p += gridDim.x * EPI_WG)` under at most EPI_CAP workgroups"""
+    c = c or source_constants()
+    need = (n0 + c["EPI_WG"] - 1) // c["EPI_WG"]
+    T = ((need if need else 1) if need < c["EPI_CAP"] else c["EPI_CAP"]) * c["EPI_WG"]
+    trips = (n0 + T - 1) // T
+    if trips <= 1:
+        return {"1"}
+    return {">1"} | ({">1:partial-last"} if n0 % T else set())
+
 
 # dev_only: the host form refuses the case (bad subsets) or the case is stated for the _dev form (non-finite pairs)
 Case = namedtuple("Case", "name src dst subsets threshold confidence dev_only")
@@ -144,9 +189,38 @@ def _table():
     return out + _special()
 
 
+def late_winner(n, max_iters, B, seed, tail=6, **kw):
+    """_batch's scenes with the subsets rearranged: every hypothesis but the last `tail` samples gross outliers alone (few inliers, need[]
+    stays above max_iters, the loop keeps running), the last `tail` sample true inliers alone -- the winner's count is one of the last the
+    score kernel writes"""
+    s = [scene(n, seed + 10 * b, k=b, **kw) for b in range(B)]
+    t = subsets_for(seed + 2, n, max_iters, B)
+    for b in range(B):
+        good = s[b][2]
+        bad_i, good_i = np.flatnonzero(~good), np.flatnonzero(good)
+        t[b, :max_iters - tail] = bad_i[subsets_for(seed + 3 + b, len(bad_i), max_iters - tail, 1)[0]]
+        t[b, max_iters - tail:] = good_i[subsets_for(seed + 4 + b, len(good_i), tail, 1)[0]]
+    return np.stack([x[0] for x in s]), np.stack([x[1] for x in s]), t
+
+
+def _cap_table():
+    """batch 16 on a context of max_batch 16, different data per item, 40 % outliers: the score grid is capped (score_grid).  Per n the
+    drawn subsets, and at n = CHUNK + 1 (a count added to across two chunks) the same scenes with the winner among the last
+    hypotheses"""
+    out = []
+    for n in (65, CHUNK + 1):
+        src, dst, t = _batch(n, CAP_ITERS, CAP_BATCH, 400 + n, noise=0.4, outliers=0.4)
+        out.append(Case(f"n{n}_it{CAP_ITERS}_b{CAP_BATCH}", src, dst, t, 3.0, 0.99, False))
+        if n == CHUNK + 1:
+            src, dst, t = late_winner(n, CAP_ITERS, CAP_BATCH, 400 + n, noise=0.4, outliers=0.4)
+            out.append(Case(f"n{n}_it{CAP_ITERS}_b{CAP_BATCH}_late", src, dst, t, 3.0, 0.99, False))
+    return out
+
+
 CASES = _table()
-BY_NAME = {c.name: c for c in CASES}
-assert len(BY_NAME) == len(CASES)
+CAP_CASES = _cap_table()
+BY_NAME = {c.name: c for c in CASES + CAP_CASES}
+assert len(BY_NAME) == len(CASES) + len(CAP_CASES)
 _refs = {}
 
 
@@ -195,3 +269,37 @@ def flow_case(W, H, B, seed=70, n=96, max_iters=130):
     coords = np.ascontiguousarray(coords[:n])
     coords[:6] = [(0, 0), (W - 1, 0), (0, H - 1), (W - 1, H - 1), (W // 2, 0), (W - 1, H // 2)]
     return flow, coords, subsets_for(seed + 1, n, max_iters, B)
+
+
+# ---- the dense pass past its cap -------------------------------------------------------------------------------------------------------------
+def epi_cap_inputs(kind):
+    """(flow (EPI_BATCH, H, W, 2) float32, F (EPI_BATCH, 3, 3), threshold) at EPI_FRAME.  "noise": noise fields with NaN and infinite vectors
+    planted either side of pixel EPI_CAP * EPI_WG, item 1 with one long vector past it (its unique maximum); "zero_F": the zero matrix"""
+    w, h = EPI_FRAME
+    c = source_constants()
+    thr = c["EPI_CAP"] * c["EPI_WG"]
+    flow = np.random.default_rng(77).normal(0, 1.5, (EPI_BATCH, h, w, 2)).astype(np.float32)
+    K = np.array([[100.0, 0, (w - 1) / 2], [0, 100.0, (h - 1) / 2], [0, 0, 1]])
+    Fm = np.stack([true_F(K, *pose(b)) for b in range(EPI_BATCH)])
+    flat = flow.reshape(EPI_BATCH, w * h, 2)
+    for b in range(EPI_BATCH):
+        for p, v in ((3 + b, (np.nan, 0)), (thr - 300, (0, np.inf)), (thr - 1, (np.nan, np.nan)), (thr, (-np.inf, 1)), (thr + 257 + b, (1, np.nan)), (w * h - 1, (np.inf, np.inf))):
+            flat[b, p] = v
+    flat[1, thr + 200] = (300.0, -400.0)
+    if kind == "zero_F":
+        Fm = np.zeros_like(Fm)
+    return flow, Fm, 6.0                                     # leaves movers and still pixels on both sides (the residuals grow towards the last row)
+
+
+_epi_refs = {}
+
+
+def epi_cap_reference(kind):
+    """(flow, F, threshold, the restatement's dict), computed once, read-only"""
+    if kind not in _epi_refs:
+        flow, Fm, t = epi_cap_inputs(kind)
+        want = R.epipolar_residual(flow, Fm, t)
+        for a in (flow, Fm) + tuple(want.values()):
+            a.setflags(write=False)
+        _epi_refs[kind] = (flow, Fm, t, want)
+    return _epi_refs[kind]

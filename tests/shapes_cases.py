@@ -1,6 +1,8 @@
 """The case table of the shapes tests (include/mavflow_shapes.h): frames, tables of records, the forms each case must reach and the
 geometric band every thick line has to meet.  tests/test_shapes_cases_cpu.py holds the table to its own conditions without a GPU;
 tests/test_gpu_shapes.py runs every case on the device against tests/shapes_ref.py."""
+import os
+import re
 from collections import namedtuple
 
 import numpy as np
@@ -105,6 +107,76 @@ def cases():
 
 
 CASES = cases()
+
+
+# ---- past the caps of the launches (outside CASES: the tests over every case do not grow) -------------------------------------------------
+KERNELS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mav-detection_amd", "csrc", "kernels_shapes.hip")
+RESOLVE_FRAME = (701, 499)      # x B = 1 049 397 elements = 4096 * 256 + 821: k_shapes_resolve's second trip is the last 821 pixels of image 2
+ROWS_RECORDS = 8300             # k_shapes_rows: one workgroup per record up to 8192 workgroups; records 8192 .. 8299 on the second trip
+ROWS_N_DEV = 8250               # a device count below n_max, both past the cap
+
+
+def source_caps(text=None) -> dict:
+    """SH_WG and the caps draw_shapes_launch gives sh_grid, read from kernels_shapes.hip as text"""
+    if text is None:
+        with open(KERNELS) as f:
+            text = f.read()
+    return dict(wg=int(re.search(r"^#define SH_WG (\d+)\b", text, re.M).group(1)),
+                rows=int(re.search(r"rows_grid = sh_grid\(\(size_t\)n_max \* 4 \* 64, (\d+)\);", text).group(1)),
+                resolve=int(re.search(r"k_shapes_resolve, dim3\(sh_grid\(N, (\d+)\)\)", text).group(1)), text=text)
+
+
+def stride_forms(items: int, cap: int, per_group: int) -> set:
+    """a loop `for (i = first; i < items; i += gridDim.x * per_group)` under sh_grid's min(ceil(items / per_group), cap) workgroups: the
+    trips the first worker takes, and whether the last one leaves workers without an item"""
+    g = min((items + per_group - 1) // per_group, cap) or 1
+    T = g * per_group
+    trips = (items + T - 1) // T
+    if trips <= 1:
+        return {"1"}
+    return {">1"} | ({">1:partial-last"} if items % T else set())
+
+
+def resolve_forms(W, H, batch, c=None) -> set:
+    c = c or source_caps()
+    return stride_forms(W * H * batch, c["resolve"], c["wg"])
+
+
+def rows_forms(n_max, c=None) -> set:
+    """(record, part) items, four per record, one wave each: a workgroup of SH_WG / 64 = 4 waves takes one record per trip"""
+    c = c or source_caps()
+    return stride_forms(4 * n_max, c["rows"], c["wg"] // 64)
+
+
+def resolve_cap_table(W, H):
+    """about 80 records over the three images; in the last rows of image 2 (the pixels past the cap) a filled rectangle under lines of
+    other colours and a circle, then lines over those: order decides pixels there"""
+    out = []
+    for image in range(B):
+        q = heavy_overlap(W, H, n=20, seed=20 + image, image=image)
+        q += [R.shape(R.LINE, image, 5 + 97 * image, 3, W - 9, H - 7 - 50 * image, 3 + image, (RED, GREEN, WHITE)[image])]     # across the frame
+        out += q
+    out += [R.shape(R.RECT, 2, 40, H - 12, W - 30, H + 5, R.FILLED, (9, 200, 77)),
+            R.shape(R.LINE, 2, 60, H - 2, W - 170, H - 1, 3, GREEN),                    # shallow, along the last two rows
+            R.shape(R.LINE, 2, W - 200, H - 40, W - 20, H + 10, 2, RED),
+            R.shape(R.CIRCLE, 2, W - 60, H - 3, 9, 0, R.FILLED, BLUE),
+            R.shape(R.LINE, 2, W - 90, H - 1, W - 30, H - 1, 1, WHITE),
+            R.shape(R.RECT, 2, W - 150, H - 6, W - 100, H + 3, 2, RED),
+            R.shape(R.LINE, 2, W - 115, H - 30, W - 108, H + 20, 5, BLUE),               # steep, through the rectangle's outline
+            R.shape(R.RECT, 0, 40, H - 12, W - 30, H + 5, R.FILLED, (9, 200, 77)),       # the same rows of image 0: before the cap
+            R.shape(R.LINE, 0, 10, H - 2, W - 10, H - 1, 3, GREEN)]
+    for k in range(12):                                                                  # a fan of lines down through the last rows
+        out.append(R.shape(R.LINE, 2, W - 20 - 9 * k, H - 25 - k, W - 60 - 3 * k, H + 4, 1 + k % 4, (GREEN, RED, BLUE, WHITE)[k % 4]))
+    out.append(R.shape(R.CIRCLE, 2, W - 3, H - 1, 4, 0, R.FILLED, (1, 2, 3)))             # the last pixel of the plane, under a circle
+    return R.table(out)
+
+
+def rows_cap_table(W, H, green=False):
+    """heavy_overlap's lines, ROWS_RECORDS of them; green: all of one colour, the table the direct form may take"""
+    t = R.table(heavy_overlap(W, H, n=ROWS_RECORDS))
+    if green:
+        t["colour"][:, :3] = GREEN
+    return t
 
 
 def case_id(c):

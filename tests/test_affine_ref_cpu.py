@@ -160,3 +160,34 @@ def test_sample_triples(mav):
     a = affine.sample_triples(np.random, 10, 4)
     np.random.seed(5)
     assert np.array_equal(a, affine.sample_triples(np.random.RandomState(5), 10, 4))
+
+
+# ---- the case table past the score grid's cap (computed from the source's constants and the restatement alone) -----------------------------
+def test_the_score_grid_is_capped_where_the_table_says():
+    import re
+    c = T.source_constants()
+    assert re.search(r"const int cap = AFF_GRID_CAP / a\.B < 1 \? 1 : AFF_GRID_CAP / a\.B;\s*hipLaunchKernelGGL\(k_affine_score, dim3\(per < cap \? per : cap, a\.B\)", c["text"])
+    assert re.search(r"const int per = \(a\.max_iters \+ AFF_WAVES \* AFF_HYP_PER_WAVE - 1\) / \(AFF_WAVES \* AFF_HYP_PER_WAVE\);", c["text"]) and T.CHUNK == c["AFF_CHUNK"]
+    for case in T.CASES:                                       # no case of the table before these is capped
+        assert T.score_grid(case.triples.shape[1], case.src.shape[0], c) == "per-item", (case.name, "is capped")
+    capped = [case for case in T.CAP_CASES if T.score_grid(case.triples.shape[1], case.src.shape[0], c) == "capped"]
+    assert len(capped) == len(T.CAP_CASES) >= 4, ("not every case of CAP_CASES reaches the form: capped", sorted({case.name for case in T.CAP_CASES} - {case.name for case in capped}))
+    assert {(case.triples.shape[1], case.src.shape[1]) for case in capped} == {(mi, n) for mi in (2049, 4096) for n in (65, T.CHUNK + 1)}
+    assert all(case.src.shape[0] == T.CAP_BATCH == 16 for case in capped) and T.CAP_ITERS == (2049, 4096)
+    # the threshold is where the table says: one iteration fewer at the same batch is not capped
+    assert T.score_grid(T.CAP_ITERS[0], T.CAP_BATCH, c) == "capped" and T.score_grid(T.CAP_ITERS[0] - 1, T.CAP_BATCH, c) == "per-item", ("CAP_ITERS", T.CAP_ITERS)
+    for case in T.CAP_CASES:                                    # different data per item
+        assert len({case.src[b].tobytes() for b in range(T.CAP_BATCH)}) == len({case.triples[b].tobytes() for b in range(T.CAP_BATCH)}) == T.CAP_BATCH
+
+
+def test_the_late_winners_sit_among_the_last_hypotheses():
+    """what makes the capped stride's later trips decide the result: the chosen hypothesis is past every workgroup's first trip, and at
+    n = CHUNK + 1 its count is one added to across two chunks"""
+    c = T.source_constants()
+    late = [case for case in T.CAP_CASES if case.name.endswith("_late")]
+    assert {case.src.shape[1] for case in late} == {65, T.CHUNK + 1}
+    for case in late:
+        mi = case.triples.shape[1]
+        first_trip = T.score_blocks(mi, T.CAP_BATCH, c)[1] * c["AFF_WAVES"]          # hypotheses of the capped grid's first trip
+        rec = T.reference(case.name)["records"]
+        assert (rec["ok"] == 1).all() and (rec["best_iter"] >= mi - 6).all() and (rec["best_iter"] >= first_trip).all(), (case.name, rec)

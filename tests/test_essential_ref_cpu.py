@@ -291,3 +291,35 @@ def test_python_layer_refuses_what_is_not_built(mav):
     assert K.camera_of(2.0, (3.0, 4.0)) == (2.0, 2.0, 3.0, 4.0) and K.camera_of(T.K_CAM) == T.CAM
     assert list(inspect.signature(Detector.get_rotation).parameters) == ["self", "flow_uv", "use_fundamental"]
     assert "five-point" in open(os.path.join(ROOT, "DESIGN.md")).read()
+
+
+# ---- the case table past the score grid's cap (computed from the source's constants and the restatement alone) -----------------------------
+def test_the_score_grid_is_capped_where_the_table_says():
+    import re
+    c = T.source_constants()
+    assert re.search(r"const int cap = EM_GRID_CAP / a\.B < 1 \? 1 : EM_GRID_CAP / a\.B;\s*hipLaunchKernelGGL\(k_em_score, dim3\(per < cap \? per : cap, a\.B\)", c["text"])
+    assert re.search(r"const int per = \(slots \+ EM_WAVES \* EM_SLOTS_PER_WAVE - 1\) / \(EM_WAVES \* EM_SLOTS_PER_WAVE\);", c["text"]) and T.CHUNK == c["EM_CHUNK"]
+    assert "const int slots = EM_SLOTS * a.max_iters;" in c["text"] and c["EM_SLOTS"] == 10
+    for case in T.CASES:                                       # no case of the table before these is capped
+        assert T.score_grid(case.subsets.shape[1], case.src.shape[0], c) == "per-item", (case.name, "is capped")
+    capped = [case for case in T.CAP_CASES if T.score_grid(case.subsets.shape[1], case.src.shape[0], c) == "capped"]
+    assert len(capped) == len(T.CAP_CASES) >= 2, ("not every case of CAP_CASES reaches the form: capped", sorted({case.name for case in T.CAP_CASES} - {case.name for case in capped}))
+    assert {case.src.shape[1] for case in capped} == {65, T.CHUNK + 1} and all(case.src.shape[0] == T.CAP_BATCH == 16 for case in capped)
+    # the threshold is where the table says: one iteration fewer at the same batch is not capped
+    assert T.score_grid(T.CAP_ITERS, T.CAP_BATCH, c) == "capped" and T.score_grid(T.CAP_ITERS - 1, T.CAP_BATCH, c) == "per-item", ("CAP_ITERS", T.CAP_ITERS)
+    assert all(case.subsets.shape[1] == T.CAP_ITERS == 205 for case in T.CAP_CASES)
+    for case in T.CAP_CASES:                                    # different data per item
+        assert len({case.src[b].tobytes() for b in range(T.CAP_BATCH)}) == len({case.subsets[b].tobytes() for b in range(T.CAP_BATCH)}) == T.CAP_BATCH
+
+
+def test_the_late_winners_sit_among_the_last_slots():
+    """what makes the capped stride's later trips decide the result: the chosen slot is past every workgroup's first trip"""
+    c = T.source_constants()
+    first_trip = T.score_blocks(T.CAP_ITERS, T.CAP_BATCH, c)[1] * c["EM_WAVES"]          # slots the capped grid scores on its first trip
+    late = [n for n in T.CAP_CASES if n.name.endswith("_late")]
+    assert [n.src.shape[1] for n in late] == [T.CHUNK + 1]
+    for name in (n.name for n in late):
+        rec = T.reference(name)["records"]
+        slot = c["EM_SLOTS"] * rec["best_iter"] + rec["best_slot"]                       # in slots, like first_trip
+        assert (rec["ok"] == 1).all() and (rec["best_iter"] >= T.CAP_ITERS - 6).all() and (slot >= c["EM_SLOTS"] * (T.CAP_ITERS - 6)).all(), (name, rec)
+        assert c["EM_SLOTS"] * (T.CAP_ITERS - 6) >= 3 * first_trip                       # the winner is on the stride's fourth trip

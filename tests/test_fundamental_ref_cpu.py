@@ -7,6 +7,8 @@ Measured with this restatement over the case table (profiles/fundamental/README.
 pairs is 3.4e-18 px^2 (pure rounding in pixel coordinates up to 640: bounded here by 1000 x that, 3.4e-15); the largest distance of the
 fitted F from the true one over the noise-free scenes below is 1.7e-13 (at n = 8; 2.8e-16 .. 5.0e-14 elsewhere; bounded by 100 x
 that, 1.7e-11)."""
+import re
+
 import numpy as np
 import pytest
 
@@ -167,3 +169,63 @@ def test_dense_pass_marks_the_patch_and_nothing_else(frame):
     zero = R.epipolar_residual(flow, np.zeros((3, 3, 3)), 1.0)                                  # a failed fit's F
     assert not zero["residual"].any() and not zero["mask"].any() and np.all(zero["records"]["not_finite"] == w * h)
     assert np.all(zero["records"]["max_row"] == -1)
+
+
+# ---- the case table past the caps (computed from the source's constants and the restatement alone) ------------------------------------------
+def test_the_score_grid_is_capped_where_the_table_says():
+    c = T.source_constants()
+    assert re.search(r"const int cap = FM_GRID_CAP / a\.B < 1 \? 1 : FM_GRID_CAP / a\.B;\s*hipLaunchKernelGGL\(k_fm_score, dim3\(per < cap \? per : cap, a\.B\)", c["text"])
+    assert re.search(r"const int per = \(slots \+ FM_WAVES \* FM_SLOTS_PER_WAVE - 1\) / \(FM_WAVES \* FM_SLOTS_PER_WAVE\);", c["text"]) and T.CHUNK == c["FM_CHUNK"]
+    for case in T.CASES:                                       # no case of the table before these is capped
+        assert T.score_grid(case.subsets.shape[1], case.src.shape[0], c) == "per-item", (case.name, "is capped")
+    capped = [case for case in T.CAP_CASES if T.score_grid(case.subsets.shape[1], case.src.shape[0], c) == "capped"]
+    assert len(capped) == len(T.CAP_CASES) >= 2, ("not every case of CAP_CASES reaches the form: capped", sorted({case.name for case in T.CAP_CASES} - {case.name for case in capped}))
+    assert {case.src.shape[1] for case in capped} == {65, T.CHUNK + 1} and all(case.src.shape[0] == T.CAP_BATCH == 16 for case in capped)
+    # the threshold is where the table says: one iteration fewer at the same batch is not capped
+    assert T.score_grid(T.CAP_ITERS, T.CAP_BATCH, c) == "capped" and T.score_grid(T.CAP_ITERS - 1, T.CAP_BATCH, c) == "per-item", ("CAP_ITERS", T.CAP_ITERS)
+    assert all(case.subsets.shape[1] == T.CAP_ITERS for case in T.CAP_CASES)
+    for case in T.CAP_CASES:                                    # different data per item
+        assert len({case.src[b].tobytes() for b in range(T.CAP_BATCH)}) == len({case.subsets[b].tobytes() for b in range(T.CAP_BATCH)}) == T.CAP_BATCH
+
+
+def test_the_late_winners_sit_among_the_last_slots():
+    """what makes the capped stride's later trips decide the result: the chosen slot is past every workgroup's first trip, and at
+    n = CHUNK + 1 its count is one added to across two chunks"""
+    c = T.source_constants()
+    per, cap = T.score_blocks(T.CAP_ITERS, T.CAP_BATCH, c)
+    first_trip = cap * c["FM_WAVES"]                            # slots the capped grid scores on its first trip (one per wave)
+    late = [n for n in T.CAP_CASES if n.name.endswith("_late")]
+    assert [n.src.shape[1] for n in late] == [T.CHUNK + 1]
+    for name in (n.name for n in late):
+        rec = T.reference(name)["records"]
+        slot = 3 * rec["best_iter"] + rec["best_slot"]          # in slots, like first_trip
+        assert (rec["ok"] == 1).all() and (slot >= 3 * (T.CAP_ITERS - 6)).all() and (rec["iters_run"] > T.CAP_ITERS - 6).all(), (name, rec)
+        assert 3 * (T.CAP_ITERS - 6) >= 3 * first_trip          # the winner is on the stride's fourth trip or later
+        assert (rec["valid"] > first_trip).all()                # and slots past the first trip are among the valid ones counted
+
+
+def test_the_dense_pass_cases_past_the_cap():
+    c = T.source_constants()
+    (w, h), thr = T.EPI_FRAME, c["EPI_CAP"] * c["EPI_WG"]
+    assert 0 < w * h - thr <= 2 * c["EPI_WG"], ("EPI_FRAME", T.EPI_FRAME, "is not within two workgroups past EPI_CAP * EPI_WG =", thr)
+    assert ">1:partial-last" in T.epi_stride_forms(w * h, c), "EPI_FRAME does not reach the form >1:partial-last"
+    assert all(T.epi_stride_forms(W * H, c) == {"1"} for W, H in T.FLOW_FRAMES + ((1, 1), (2, 3), (5, 3), (37, 23), (131, 67)))
+    assert len(re.findall(r"p \+= \(size_t\)gridDim\.x \* EPI_WG", c["text"])) == 1 and "need < EPI_CAP ? (need ? need : 1) : EPI_CAP" in c["text"]
+    flow, Fm, t, want = T.epi_cap_reference("noise")
+    assert flow.shape == (T.EPI_BATCH, h, w, 2) and T.EPI_BATCH == 2 and not np.array_equal(flow[0], flow[1])
+    for b in range(T.EPI_BATCH):
+        bad = ~np.isfinite(flow[b].reshape(w * h, 2)).all(axis=1)
+        mask = want["mask"][b].ravel()
+        for side in (slice(0, thr), slice(thr, None)):          # movers, still pixels and not-finite pixels on each side of the threshold
+            assert bad[side].sum() >= 2 and (mask[side] == 255).any() and (mask[side] == 0).sum() > bad[side].sum()
+        assert want["records"]["not_finite"][b] == bad.sum() and want["records"]["movers"][b] == (mask == 255).sum()
+        assert np.isnan(flow[b].reshape(w * h, 2)[:thr]).any() and np.isinf(flow[b].reshape(w * h, 2)[:thr]).any()
+        assert np.isnan(flow[b].reshape(w * h, 2)[thr:]).any() and np.isinf(flow[b].reshape(w * h, 2)[thr:]).any()
+    r = want["records"][1]                                      # one item whose unique maximum lies past the threshold
+    at = np.flatnonzero(want["residual"][1].ravel() == want["residual"][1].max())
+    assert len(at) == 1 and at[0] >= thr and (int(r["max_row"]), int(r["max_col"])) == divmod(int(at[0]), w) and r["max_residual"] == want["residual"][1].max()
+    _, Fz, _, wz = T.epi_cap_reference("zero_F")
+    assert not Fz.any()
+    for r in wz["records"]:                                     # the count crosses both trips
+        assert (r["max_residual"], r["max_row"], r["max_col"], r["movers"], r["not_finite"]) == (0, -1, -1, 0, w * h)
+    assert not wz["residual"].any() and not wz["mask"].any()

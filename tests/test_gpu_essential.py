@@ -250,3 +250,19 @@ def test_refused_arguments_leave_canaries_intact(mav):
                 assert (b.download(np.uint8, (b.nbytes,)) == CANARY).all(), k
         finally:
             d.close()
+
+
+# ---- past the score kernel's grid cap --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", [c.name for c in T.CAP_CASES])
+def test_device_equals_the_restatement_under_a_capped_score_grid(mav, name):
+    """batch 16 on a context of max_batch 16: k_em_score's grid is EM_GRID_CAP / 16 workgroups per item, its counts written (and, at n = CHUNK + 1,
+    added to) under the longer stride; the _late cases' winners are among the last hypotheses"""
+    from mavflow import _lib, essential as K
+    c, want = T.BY_NAME[name], T.reference(name)
+    nb = c.src.shape[0]
+    assert nb == T.CAP_BATCH and T.score_grid(c[3].shape[1], nb) == "capped"
+    every = slice(0, nb)
+    with _lib.Context(W, H, T.CAP_BATCH) as ctx:
+        _same(_host(ctx, K, c, every), want, (name, "host"))
+        _same(_dev(ctx, K, c, every, False), want, (name, "_dev"))
+        _same(_dev(ctx, K, c, every, True), want, (name, "_dev, offset pointers"))

@@ -271,3 +271,53 @@ def test_dense_pass_equals_the_restatement(mav, frame, kind):
                               (frame, kind, nb, "_dev", res_on, mask_on))
             finally:
                 d.close()
+
+
+# ---- past the caps ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", [c.name for c in T.CAP_CASES])
+def test_device_equals_the_restatement_under_a_capped_score_grid(mav, name):
+    """batch 16 on a context of max_batch 16: k_fm_score's grid is FM_GRID_CAP / 16 workgroups per item, its slots' counts written (and,
+    at n = FM_CHUNK + 1, added to) under the longer stride; the _late cases' winners are among the last slots"""
+    from mavflow import _lib, fundamental as K
+    c, want = T.BY_NAME[name], T.reference(name)
+    nb = c.src.shape[0]
+    assert nb == T.CAP_BATCH and T.score_grid(c.subsets.shape[1], nb) == "capped"
+    every = slice(0, nb)
+    with _lib.Context(W, H, T.CAP_BATCH) as ctx:
+        _same(_host(ctx, K, c, every), want, (name, "host"))
+        _same(_dev(ctx, K, c, every, False), want, (name, "_dev"))
+        _same(_dev(ctx, K, c, every, True), want, (name, "_dev, offset pointers"))
+
+
+@pytest.mark.parametrize("kind", ("noise", "zero_F"))
+def test_dense_pass_equals_the_restatement_past_the_cap(mav, kind):
+    """397 x 331 at batch 2: the second trip of k_epipolar_residual's loop -- the last 335 pixels written, the key and both counts carried
+    across trips into the wave reduction and the atomics"""
+    from mavflow import _lib
+    (w, h), nb = T.EPI_FRAME, T.EPI_BATCH
+    flow, Fm, t, want = T.epi_cap_reference(kind)
+    with _lib.Context(w, h, nb) as ctx:
+        out = ctx.epipolar_residual(flow, Fm, t)
+        _same_epi((out["residual"], out["mask"], out["records"]), want, (kind, "host"))
+        for outputs in (("residual",), ("mask",), ()):
+            out = ctx.epipolar_residual(flow, Fm, t, outputs=outputs)
+            assert set(out) & {"residual", "mask"} == set(outputs)
+            _same_epi((out.get("residual"), out.get("mask"), out["records"]), want, (kind, outputs))
+        d = _Dev(ctx)
+        try:
+            _, df = d.put(flow, 4)
+            _, dF = d.put(Fm, 8)
+            for res_on, mask_on in ((True, True), (False, True), (True, False), (False, False)):
+                bres, dres = d.blank(4 * nb * w * h, 4)
+                bm, dm = d.blank(nb * w * h, 1)
+                be, de = d.blank(32 * nb, 16)
+                ctx.epipolar_residual_enqueue(df, dF, nb, dres if res_on else None, dm if mask_on else None, de, threshold=t)
+                ctx.sync()
+                res, mask = d.get(bres, 4, np.float32, (nb, h, w)), d.get(bm, 1, np.uint8, (nb, h, w))
+                if not res_on:
+                    assert (res.view(np.uint8) == CANARY).all()
+                if not mask_on:
+                    assert (mask == CANARY).all()
+                _same_epi((res if res_on else None, mask if mask_on else None, d.get(be, 16, R.EPI_DTYPE, (nb,))), want, (kind, "_dev", res_on, mask_on))
+        finally:
+            d.close()

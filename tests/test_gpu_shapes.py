@@ -300,3 +300,57 @@ def test_motion_pictures_equal_the_host_output_renders_and_keep_the_resident_mas
         field.take()
         res.take()
         assert np.array_equal(got[0], ctx.flow_to_color(flow))
+
+
+# ---- past the caps of the launches (tests/shapes_cases.py RESOLVE_FRAME, ROWS_RECORDS) ---------------------------------------------------------
+@pytest.mark.parametrize("channels", (3, 1))
+def test_resolve_past_its_cap_equals_the_restatement(mav, channels):
+    """701 x 499 x 3: k_shapes_resolve's second trip reads the owner plane past 2^20 elements, the last rows of image 2, where records of
+    different colours overlap and order decides"""
+    from mavflow import _lib
+    W, H = sc.RESOLVE_FRAME
+    shapes = sc.resolve_cap_table(W, H)
+    img = sc.canary(W, H, channels)
+    want = R.draw_shapes(img, shapes)
+    assert not sc.one_colour(shapes, channels)
+    with _lib.Context(W, H, sc.B) as ctx:
+        got = draw_dev(ctx, img, shapes, channels, offset=3 if channels == 3 else 0, ordered=True)
+        assert np.array_equal(got, want), ("ordered", channels, differing(got, want), np.argwhere((got != want).any(axis=-1))[:4].tolist())
+        host = img.copy()
+        assert ctx.draw_shapes(host, shapes) is host
+        assert np.array_equal(host, want), ("host form", channels, differing(host, want))
+
+
+@pytest.fixture(scope="module")
+def rows_cap():
+    """the 8 300 records and the restatement's pictures of them, computed once: (canary, table, ordered, green table, direct, ordered up to n_dev)"""
+    W, H = sc.FRAMES[0]
+    img = sc.canary(W, H, 3)
+    t, g = sc.rows_cap_table(W, H), sc.rows_cap_table(W, H, green=True)
+    out = (img, t, R.draw_shapes(img, t), g, R.draw_shapes(img, g), R.draw_shapes(img, t, sc.ROWS_N_DEV))
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+@pytest.mark.parametrize("form", ("ordered", "direct", "n_dev"))
+def test_rows_past_their_cap_equal_the_restatement(mav, rows_cap, form):
+    """8 300 records: k_shapes_rows reaches records 8192 .. on its workgroups' second trip -- in ORDERED form the records that must win
+    every overlap"""
+    from mavflow import _lib
+    W, H = sc.FRAMES[0]
+    img, t, want, g, want_g, want_n = rows_cap
+    assert len(t) == sc.ROWS_RECORDS and ">1:partial-last" in sc.rows_forms(len(t))
+    with _lib.Context(W, H, sc.B) as ctx:
+        if form == "ordered":
+            got = draw_dev(ctx, img, t, 3, offset=5, ordered=True)
+            assert np.array_equal(got, want), (form, differing(got, want))
+            assert (want != want_n).any()                                                  # the records past n_dev decide pixels
+        elif form == "direct":
+            assert sc.one_colour(g, 3)
+            for ordered in (False, True):
+                got = draw_dev(ctx, img, g, 3, ordered=ordered)
+                assert np.array_equal(got, want_g), (form, ordered, differing(got, want_g))
+        else:
+            got = draw_dev(ctx, img, t, 3, ordered=True, n_dev=sc.ROWS_N_DEV)
+            assert np.array_equal(got, want_n), (form, differing(got, want_n))

@@ -271,3 +271,76 @@ def test_refusals_that_need_the_context(contexts):
         assert lib.mav_warp_perspective(ctx.h, s, 3, _ptr(Ms), warp.WARP_INVERSE_MAP_FLAG, T.B, d) == 0      # nothing to invert: taken
     finally:
         blk.free()
+
+
+# ---- past the caps: the second trip of the grid-stride loops (tests/warp_cases.py CAP_FRAME, METHOD_CAP_FRAME) ---------------------------------
+@pytest.mark.parametrize("fmt", list(T.FORMATS), ids=str)
+@pytest.mark.parametrize("policy", list(T.POLICIES), ids=str)
+def test_device_bytes_equal_the_restatement_past_the_cap(contexts, policy, fmt):
+    """one _dev call at batch 2 per instance, plain and on pointers one element into their blocks (F32C2, CoordMap and CoordFlow on
+    their scalar access), into canary-filled blocks; one host-form call per policy"""
+    from mavflow import warp
+    lib = warp.load()
+    (W, H), f = T.CAP_FRAME, T.FORMATS[fmt]
+    ctx = contexts(W, H)
+    names, src, ops, fl, want, _ = T.cap_reference(policy, fmt)
+    n = T.CAP_B
+    what = (policy, fmt, T.CAP_FRAME, names, fl)
+    dev = _Dev(ctx)
+    try:
+        if fmt == "F32C2":
+            dst = np.full(want.shape, np.float32(-777.25))
+            assert _host_call(lib, ctx, policy, f, src, ops, fl, n, dst) == 0, (what, lib.mav_last_error())
+            _same(dst, want, ("host",) + what)
+        for shifted in (False, True):
+            rc, db, e = _dev_call(lib, ctx, dev, policy, f, src, ops, fl, n, shifted)
+            assert rc == 0, (what, shifted, lib.mav_last_error())
+            ctx.sync()
+            _same(dev.get(db, e, want.dtype, want.shape), want, ("dev", shifted) + what)
+            dev.close()
+    finally:
+        dev.close()
+
+
+@pytest.mark.parametrize("kind", [R.AFFINE, R.PERSPECTIVE], ids=["affine", "perspective"])
+def test_warp_method_equals_the_restatement_past_the_cap(contexts, kind):
+    """batch 3, host and _dev forms, diff and mag present and both NULL: keys and the first pixel among equals carried across trips and
+    workgroups into the one atomic per workgroup"""
+    from mavflow import warp
+    from mavflow._lib import _ptr
+    lib = warp.load()
+    W, H = T.METHOD_CAP_FRAME
+    ctx = contexts(W, H)
+    vp = lambda p: C.c_void_p(int(p))
+    n = T.B
+    dev = _Dev(ctx)
+    try:
+        for names, flow, M, wd, wm, wr in T.method_cap_reference(kind):
+            what = (kind, T.METHOD_CAP_FRAME, names)
+            diff, mag, rec = np.full((n, H, W, 2), np.float32(-7)), np.full((n, H, W), np.float32(-7)), np.full(n, -1, np.int32).repeat(4).view(R.RECORD_DTYPE)
+            assert lib.mav_warp_method(ctx.h, _ptr(flow), _ptr(M), kind, n, _ptr(diff), _ptr(mag), _ptr(rec)) == 0, lib.mav_last_error()
+            _same(diff, wd, ("diff",) + what)
+            _same(mag, wm, ("mag",) + what)
+            assert rec.tobytes() == wr.tobytes(), (what, rec, wr)
+            rec2 = np.full(n, -1, np.int32).repeat(4).view(R.RECORD_DTYPE)
+            assert lib.mav_warp_method(ctx.h, _ptr(flow), _ptr(M), kind, n, None, None, _ptr(rec2)) == 0
+            assert rec2.tobytes() == wr.tobytes(), (what, rec2, wr)
+            for shifted, outputs in ((False, True), (True, True), (False, False)):
+                s4 = 4 if shifted else 0
+                _, df = dev.put(flow, s4)
+                _, dm = dev.put(M, 8 if shifted else 0)
+                bd, dd = dev.blank(diff.nbytes, s4)
+                bg, dg = dev.blank(mag.nbytes, s4)
+                br, dr = dev.blank(16 * n, 16 if shifted else 0)
+                assert lib.mav_warp_method_dev(ctx.h, vp(df), vp(dm), kind, n, vp(dd) if outputs else None, vp(dg) if outputs else None, vp(dr)) == 0, lib.mav_last_error()
+                ctx.sync()
+                if outputs:
+                    _same(dev.get(bd, s4, np.float32, diff.shape), wd, ("dev diff", shifted) + what)
+                    _same(dev.get(bg, s4, np.float32, mag.shape), wm, ("dev mag", shifted) + what)
+                else:
+                    assert (dev.get(bd, s4, np.uint8, (diff.nbytes,)) == CANARY).all() and (dev.get(bg, s4, np.uint8, (mag.nbytes,)) == CANARY).all()
+                got = dev.get(br, 16 if shifted else 0, R.RECORD_DTYPE, (n,))
+                assert got.tobytes() == wr.tobytes(), (what, shifted, outputs, got, wr)
+                dev.close()
+    finally:
+        dev.close()

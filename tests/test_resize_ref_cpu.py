@@ -2,6 +2,11 @@
 bilinear interpolate and a float64 bilinear written from the clipped coordinate, uint8 linear against the exact bilinear value, the
 area forms against the box integral and the block mean, the 2 x 2 uint8 rounding, the linear-to-area and copy dispatch, and nearest
 against its index formula.  Every tolerance is derived where it is used, from the number formats and the definition, not measured."""
+import os
+import subprocess
+import sys
+import tempfile
+
 import numpy as np
 import pytest
 
@@ -35,6 +40,45 @@ def _bilinear64(S, dw, dh):
     return top * (1 - ay) + bot * ay
 
 
+# torch's kernel runs in a process of its own, once for all shapes.  torch ships its own HIP and HSA runtimes, and its libraries ask for
+# them by file name, not by SONAME: imported into a process that has already loaded libmavflow.so (every test that takes `mav`), it maps
+# a second HIP runtime beside the one the library is linked to, and a process with two of them has ended in glibc's "double free or
+# corruption" at exit after every test had passed.  Nothing of the library is imported there.
+_TORCH_WORKER = """
+import sys
+import numpy as np
+import torch
+src = np.load(sys.argv[1])
+out = {}
+for key in src.files:
+    dh, dw = (int(v) for v in key.split("|")[1].split(","))
+    S = src[key]
+    t = torch.nn.functional.interpolate(torch.from_numpy(S.transpose(2, 0, 1)[None].copy()), size=(dh, dw), mode="bilinear", align_corners=False)
+    out[key] = t[0].numpy().transpose(1, 2, 0)
+np.savez(sys.argv[2], **out)
+"""
+_torch = {}
+
+
+def _torch_input(fmt, shape):
+    (sw, sh) = shape.src
+    return T.images(fmt, sw, sh, special=False)[1].reshape(sh, sw, -1)
+
+
+def _torch_bilinear(fmt, shape):
+    """torch.nn.functional.interpolate(mode="bilinear", align_corners=False) of the case's image, (dh, dw, C) float32"""
+    key = lambda f, s: f"{f}:{ids(s)}|{s.dst[1]},{s.dst[0]}"
+    if not _torch:
+        with tempfile.TemporaryDirectory() as d:
+            a, b = os.path.join(d, "in.npz"), os.path.join(d, "out.npz")
+            np.savez(a, **{key(f, s): _torch_input(f, s) for f in (R.F32C1, R.F32C2) for s in LINEAR_SHAPES})
+            r = subprocess.run([sys.executable, "-c", _TORCH_WORKER, a, b], capture_output=True, text=True)
+            assert r.returncode == 0, r.stderr[-2000:]
+            with np.load(b) as z:
+                _torch.update({k: z[k] for k in z.files})
+    return _torch[key(fmt, shape)]
+
+
 def _steps(S):
     """the largest difference of two taps a pixel blends along x and along y"""
     S = S.astype(np.float64)
@@ -52,17 +96,17 @@ def test_float32_linear_against_float64_and_torch(mav, fmt, shape):
     torch's kernel takes scale and coordinate in float32: a rounded scale (2^-24 relative, times d + 0.5 <= dsize), a rounded product
     and a rounded difference, so three such coordinate errors where the restatement has one (in units of max(sw, sh, dw, dh), its
     coordinates being as large as the larger side), and its own 8 roundings of the blend."""
-    import torch
     (sw, sh), (dw, dh) = shape.src, shape.dst
-    S = T.images(fmt, sw, sh, special=False)[1].reshape(sh, sw, -1)
+    S = _torch_input(fmt, shape)
     got = R.resize(S, dw, dh, R.LINEAR).astype(np.float64)
     top = np.abs(S).max()
     dx, dy = _steps(S)
     coord = EPS32 * max(sw, sh, dw, dh)
     tol64 = coord * (dx + dy) + 8 * EPS32 * top
     err64 = np.abs(got - _bilinear64(S, dw, dh)).max()
-    t = torch.nn.functional.interpolate(torch.from_numpy(S.transpose(2, 0, 1)[None].copy()), size=(dh, dw), mode="bilinear", align_corners=False)
-    err_t = np.abs(got - t[0].numpy().transpose(1, 2, 0).astype(np.float64)).max()
+    t = _torch_bilinear(fmt, shape)
+    assert t.shape == got.shape and t.dtype == np.float32
+    err_t = np.abs(got - t.astype(np.float64)).max()
     tol_t = 4 * coord * (dx + dy) + 16 * EPS32 * top
     print(f"{ids(shape)} fmt {fmt}: |ref - float64| {err64:.3e} (bound {tol64:.3e}), |ref - torch| {err_t:.3e} (bound {tol_t:.3e}), max|S| {top:.3g}")
     assert err64 <= tol64

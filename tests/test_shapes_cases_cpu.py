@@ -147,3 +147,60 @@ def test_every_form_and_situation_is_reached(mav):
     t = R.table(bad[0])
     assert sum(not R.valid(s, sc.B) for s in t) == bad[1] and sum(R.valid(s, sc.B) for s in t) == bad[1] + 2
     assert (np.dtype(shapes.SHAPE_DTYPE) == R.SHAPE_DTYPE) and shapes.scratch_bytes(131, 67, 3) == 4 * 131 * 67 * 3
+
+
+# ---- past the caps of the launches ---------------------------------------------------------------------------------------------------------
+def test_the_cap_cases_sit_just_past_the_caps_the_source_defines():
+    c = sc.source_caps()
+    W, H = sc.RESOLVE_FRAME
+    N, thr = W * H * sc.B, c["resolve"] * c["wg"]
+    # the frame 701 x 499 x 3 is 821 elements past the cap, more than the 2 * SH_WG the other frames are held to: the bound here is
+    # 4 * SH_WG, and fewer than two rows of the last image
+    assert 0 < N - thr <= 4 * c["wg"] and N - thr < 2 * W, ("RESOLVE_FRAME", sc.RESOLVE_FRAME, "is not just past the resolve cap * SH_WG =", thr)
+    assert ">1:partial-last" in sc.resolve_forms(W, H, sc.B, c), "RESOLVE_FRAME does not reach the form >1:partial-last"
+    assert 0 < sc.ROWS_N_DEV - c["rows"] < sc.ROWS_RECORDS - c["rows"] <= c["wg"], ("ROWS_RECORDS / ROWS_N_DEV", sc.ROWS_RECORDS, sc.ROWS_N_DEV, "against the rows cap", c["rows"])
+    assert ">1:partial-last" in sc.rows_forms(sc.ROWS_RECORDS, c) and ">1:partial-last" in sc.rows_forms(sc.ROWS_N_DEV, c), "ROWS_RECORDS does not reach the form >1:partial-last"
+    assert sc.rows_forms(c["rows"], c) == {"1"} and sc.rows_forms(c["rows"] + 1, c) == {">1", ">1:partial-last"} and sc.rows_forms(2 * c["rows"], c) == {">1"}
+    # the loops the caps bound, read as text
+    assert "stride = (unsigned long long)gridDim.x * SH_WAVES" in c["text"] and "stride = (size_t)gridDim.x * SH_WG" in c["text"]
+    assert "#define SH_WAVES (SH_WG / 64)" in c["text"]
+    # without these no case reaches a second trip of either loop
+    for case in sc.CASES:
+        assert sc.resolve_forms(case.W, case.H, sc.B, c) == {"1"} and sc.rows_forms(len(case.shapes), c) == {"1"}, sc.case_id(case)
+
+
+def test_order_decides_pixels_past_the_resolve_cap():
+    c = sc.source_caps()
+    W, H = sc.RESOLVE_FRAME
+    thr = c["resolve"] * c["wg"]
+    t = sc.resolve_cap_table(W, H)
+    assert 75 <= len(t) <= 90 and {int(i) for i in t["image"]} == {0, 1, 2} and not sc.one_colour(t, 3) and not sc.one_colour(t, 1)
+    assert all(R.valid(s, sc.B) for s in t)
+    own, cnt = R.owner_plane(t, sc.B, H, W)
+    o = own.ravel()[thr:]
+    owners = set(np.unique(o[o > 0]).tolist())
+    assert (o > 0).sum() >= 200 and len(owners) >= 3 and (o == 0).any()
+    assert len({tuple(t["colour"][i - 1]) for i in owners}) >= 3                          # of different colours
+    kinds = {(int(t["kind"][i - 1]), int(t["thickness"][i - 1]) == R.FILLED) for i in owners}
+    assert (R.RECT, True) in kinds and (R.CIRCLE, True) in kinds and any(k == R.LINE for k, _ in kinds)
+    # a lower-numbered record beneath the owner, from the records' own masks
+    beneath = np.zeros(W * H * sc.B - thr, bool)
+    for i, s in enumerate(t):
+        if int(s["image"]) == 2:
+            m = np.zeros((sc.B, H, W), bool)
+            m[2] = R.record_mask(s, W, H)
+            beneath |= m.ravel()[thr:] & (o > i + 1)
+    assert beneath.sum() >= 100 and (cnt.ravel()[thr:] > 2).any()
+    assert (own[0] > 0).any() and (own[1] > 0).any()
+
+
+def test_the_records_past_the_rows_cap_own_pixels_over_earlier_records():
+    c = sc.source_caps()
+    W, H = sc.FRAMES[0]
+    t = sc.rows_cap_table(W, H)
+    assert len(t) == sc.ROWS_RECORDS and not sc.one_colour(t, 3) and sc.one_colour(sc.rows_cap_table(W, H, green=True), 3)
+    own, cnt = R.owner_plane(t, sc.B, H, W)
+    late = own >= c["rows"] + 1                                                           # owner index + 1 of a record i >= 8192
+    assert late.sum() >= 100 and (late & (cnt > 1)).sum() >= 1
+    # (the owner is the last record that reaches a pixel: where more than one does, the others are earlier records' masks)
+    assert (own[0] > sc.ROWS_N_DEV).any() and ((own[0] > c["rows"]) & (own[0] <= sc.ROWS_N_DEV)).any()     # either side of the device count

@@ -185,3 +185,90 @@ def test_warp_method_fields_reach_the_mask_and_the_tie(frame):
     f[H - 1, W - 2] = f[0, 0] = (3.0, 4.0)                               # both land inside, one pixel to the right
     diff, mag, rec = R.warp_method(f, [[1, 0, 1], [0, 1, 0]], R.AFFINE)
     assert (mag == mag.max()).sum() >= 2 and (rec["row"], rec["col"]) == tuple(np.argwhere(mag == mag.max())[0])
+
+
+# ---- past the caps: the second trip of the grid-stride loops ---------------------------------------------------------------------------------
+def test_the_cap_frames_sit_just_past_the_caps_the_source_defines():
+    c = T.source_caps()
+    wg = c["WARP_WG"]
+    for name, frame, cap in (("CAP_FRAME", T.CAP_FRAME, c["WARP_CAP"]), ("METHOD_CAP_FRAME", T.METHOD_CAP_FRAME, c["WARP_METHOD_CAP"])):
+        n0 = frame[0] * frame[1]
+        assert 0 < n0 - cap * wg <= 2 * wg, (name, frame, "is not within two workgroups past cap * WG =", cap * wg)
+        assert ">1:partial-last" in T.stride_forms(n0, cap, wg), (name, "does not reach the form >1:partial-last")
+        assert frame[0] % 2 and frame[1] % 2 and frame not in T.FRAMES
+    # the launches read as text: the caps are the ones warp_grid is given
+    s = T.source_forms()["text"]
+    assert re.search(r"warp_grid\(int W, int H, int B, size_t cap = WARP_CAP\)", s) and len(re.findall(r"warp_grid\(W, H, B, WARP_METHOD_CAP\)", s)) == 2
+    assert len(re.findall(r"p \+= \(size_t\)gridDim\.x \* WARP_WG", s)) == 2
+    # with the two frames removed no case reaches a second trip, under either cap
+    for W, H in T.FRAMES:
+        assert T.stride_forms(W * H, c["WARP_CAP"], wg) == T.stride_forms(W * H, c["WARP_METHOD_CAP"], wg) == {"1"}, ("a frame of FRAMES reaches >1", W, H)
+    assert T.stride_forms(cap * wg, cap, wg) == {"1"} and T.stride_forms(2 * cap * wg, cap, wg) == {">1"}
+    assert T.stride_forms(cap * wg + 1, cap, wg) == {">1", ">1:partial-last"} and T.stride_forms(0, cap, wg) == {"1"}
+
+
+def _weighted_inside_tap(s):
+    """per pixel: some tap lies inside the image under a nonzero weight (the restatement's trace)"""
+    W, H, ax, ay = s["W"], s["H"], s["ax"], s["ay"]
+    out = np.zeros(s["inside"].shape, bool)
+    for dy, wy in ((0, 32 - ay), (1, ay)):
+        for dx, wx in ((0, 32 - ax), (1, ax)):
+            r, c = s["sy"] + dy, s["sx"] + dx
+            out |= s["inside"] & (r >= 0) & (r < H) & (c >= 0) & (c < W) & (wy * wx != 0)
+    return out
+
+
+@pytest.mark.parametrize("policy,fmt", T.INSTANCES, ids=lambda v: str(v))
+def test_every_instance_samples_the_image_past_the_cap(policy, fmt):
+    """at least half of the pixels past cap * WG have an inside tap under a nonzero weight: per item, but for "rotation with scale"
+    at flags 0 -- the operand the affine instances are to run -- which turns four fifths of the last row out of sight (0.198 inside);
+    for that call the share is counted over its two items, the second of which keeps every pixel in"""
+    c = T.source_caps()
+    thr = c["WARP_CAP"] * c["WARP_WG"]
+    W, H = T.CAP_FRAME
+    names, src, ops, fl, want, traces = T.cap_reference(policy, fmt)
+    assert len(names) == T.CAP_B == 2 and src.shape[0] == ops.shape[0] == want.shape[0] == 2 and not np.array_equal(ops[0], ops[1]) and not np.array_equal(src[0], src[1])
+    tail = np.concatenate([_weighted_inside_tap(s).ravel()[thr:] for s in traces])
+    assert len(tail) == 2 * (W * H - thr) > 0 and tail.mean() >= 0.5, (policy, fmt, tail.mean())
+    for b in range(2):
+        region = want[b].reshape(W * H, -1)[thr:]
+        share = _weighted_inside_tap(traces[b]).ravel()[thr:].mean()
+        assert share >= 0.5 or (names[b] == "rotation with scale" and share >= 0.15), (policy, fmt, names[b], share)
+        assert len(np.unique(R.bits(region) if region.dtype == np.float32 else region)) > 2, (policy, fmt, b)
+    if policy in ("map", "planes", "flow"):
+        # every special coordinate lands on the second trip as well as the first
+        sp = T.special_coords(W, H)
+        assert W * H - len(sp) >= thr
+        s = traces[0]
+        last = lambda k: s[k].ravel()[W * H - len(sp):]
+        assert np.array_equal(last("qx"), s["qx"].ravel()[:len(sp)]) and np.array_equal(last("fits"), s["fits"].ravel()[:len(sp)])
+        notes = [n.split(" ", 1)[1] for _, _, n in sp]
+        for what in ("NaN", "+inf", "-inf", "+3e9", "-3e9"):
+            assert not any(last("fits")[i] for i, n in enumerate(notes) if n == what), what
+        assert all(last("fits")[i] and last("int16_clamped")[i] and not last("inside")[i] for i, n in enumerate(notes) if n == "past int16")
+        assert any(last("fits")[i] and not last("inside")[i] for i, n in enumerate(notes) if n == "n")                        # the outside cases
+        assert any(last("inside")[i] and last("partial")[i] for i, n in enumerate(notes) if n in ("-1", "n-1"))
+    else:
+        assert fl == 0 and names[0] in ("rotation with scale", "mild tilt") and names[1] in ("half pixel", "tilt, W crosses zero")
+
+
+def test_warp_method_references_past_the_cap():
+    c = T.source_caps()
+    thr = c["WARP_METHOD_CAP"] * c["WARP_WG"]
+    W, H = T.METHOD_CAP_FRAME
+    for kind in (R.AFFINE, R.PERSPECTIVE):
+        calls = T.method_cap_reference(kind)
+        recs = [(n, r) for names, f, M, d, m, rec in calls for n, r in zip(names, rec)]
+        assert any(int(r["row"]) * W + int(r["col"]) >= thr for _, r in recs[:-T.B])                     # among method_matrices over method_flow
+        ident = [r for n, r in recs if n == "identity"]
+        assert ident and all(r.tobytes() == np.zeros((), R.RECORD_DTYPE).tobytes() for r in ident)      # every pixel ties at +0.0 across both trips: the first
+        names, f, M, d, mag, rec = calls[-1]
+        assert names == ("tie", "the later is larger", "the earlier is larger")
+        at = np.flatnonzero(mag[0].ravel() == mag[0].max())
+        assert len(at) == 2 and at[0] < thr <= at[1] and at[0] // c["WARP_WG"] % c["WARP_METHOD_CAP"] != at[1] // c["WARP_WG"] % c["WARP_METHOD_CAP"]
+        assert R.bits(mag[0].ravel()[at[0]]) == R.bits(mag[0].ravel()[at[1]]) and mag[0].max() == 5
+        assert (int(rec[0]["row"]), int(rec[0]["col"])) == divmod(int(at[0]), W) and rec[0]["max_mag"] == 5
+        assert (int(rec[1]["row"]), int(rec[1]["col"])) == divmod(int(at[1]), W) and rec[1]["max_mag"] == 10
+        assert (int(rec[2]["row"]), int(rec[2]["col"])) == divmod(int(at[0]), W) and rec[2]["max_mag"] == 10
+        for y, x in T.method_cap_plants(W, H, thr):
+            assert 0 < y < H - 1 and 0 < x < W - 1 and y == H - 2                                        # sources off the rim, landing in the last row

@@ -20,6 +20,10 @@ POLICIES = {"map": "CoordMap", "planes": "CoordPlanes", "flow": "CoordFlow", "af
 FORMATS = {"U8C1": R.U8C1, "U8C3": R.U8C3, "F32C1": R.F32C1, "F32C2": R.F32C2}
 INSTANCES = [(p, f) for p in POLICIES for f in FORMATS]
 FEATURE_FRAME = 15          # pixels from which a frame has room for what an input is noted for (the smaller frames run the same inputs)
+# The frames past a launch's cap, outside FRAMES (the full cross product above does not grow): the grid-stride loops' second trip.
+CAP_FRAME = (1031, 509)         # 524 779 px = 2048 * 256 + 491: k_warp's second trip is one full workgroup and 235 lanes of the next
+METHOD_CAP_FRAME = (397, 331)   # 131 407 px = 512 * 256 + 335: k_warp_method's second trip is the last row from column 62 onward
+CAP_B = 2                       # batch of the calls at CAP_FRAME (those at METHOD_CAP_FRAME run at B)
 
 
 def source_forms() -> dict:
@@ -29,6 +33,29 @@ def source_forms() -> dict:
     return dict(structs=set(re.findall(r"^struct (Coord\w+)", src, re.M)), dispatched=set(re.findall(r"launch_policy<(Coord\w+)>", src)),
                 formats=set(re.findall(r"k_warp<P, MAV_WARP_(\w+)>", src)), fmt_structs=set(re.findall(r"struct WarpFmt<MAV_WARP_(\w+)>", src)),
                 method=set(re.findall(r"k_warp_method<(Coord\w+)>", src)), text=src)
+
+
+def source_caps(text: str | None = None) -> dict:
+    """WARP_WG, WARP_CAP and WARP_METHOD_CAP as kernels_warp.hip defines them, read as text"""
+    text = source_forms()["text"] if text is None else text
+    return {k: int(re.search(rf"^#define {k} (\d+)\b", text, re.M).group(1)) for k in ("WARP_WG", "WARP_CAP", "WARP_METHOD_CAP")}
+
+
+def warp_blocks(n0: int, cap: int, wg: int) -> int:
+    """warp_grid: `need = (W * H + WARP_WG - 1) / WARP_WG; need < cap ? (need ? need : 1) : cap` workgroups per image"""
+    need = (n0 + wg - 1) // wg
+    return (need if need else 1) if need < cap else cap
+
+
+def stride_forms(n0: int, cap: int, wg: int | None = None) -> set:
+    """`for (p = blockIdx.x * WARP_WG + threadIdx.x; p < n0; p += gridDim.x * WARP_WG)` under a grid of at most `cap` workgroups: the
+    trips thread 0 takes, and whether the last one leaves threads without a pixel."""
+    wg = source_caps()["WARP_WG"] if wg is None else wg
+    T = warp_blocks(n0, cap, wg) * wg
+    trips = (n0 + T - 1) // T
+    if trips <= 1:
+        return {"1"}
+    return {">1"} | ({">1:partial-last"} if n0 % T else set())
 
 
 # ---- images --------------------------------------------------------------------------------------------------------------------------------
@@ -195,3 +222,101 @@ def method_matrices(kind: int, W: int, H: int) -> list:
     names = ("identity", "shift (1, -1)", "half pixel", "rotation with scale", "reflection", "scale 2")
     ms = [m for m in (affine_matrices(W, H) if kind == R.AFFINE else perspective_matrices(W, H)) if m.name in names + ("mild tilt",)]
     return ms
+
+
+# ---- past the caps ---------------------------------------------------------------------------------------------------------------------------
+def cap_maps(W: int, H: int) -> np.ndarray:
+    """(CAP_B, H, W, 2) float32: per item another smooth map with every special coordinate planted over the LAST pixels in raster order
+    (the second trip of the grid-stride loop) as well as the first; item 1 plants them in reverse order"""
+    sp = special_coords(W, H)
+    n0 = W * H
+    assert 2 * len(sp) <= n0
+    out = []
+    for k in range(CAP_B):
+        m = smooth_map(W, H, k + 1).reshape(n0, 2)
+        for p, (mx, my, _) in enumerate(sp[::-1] if k else sp):
+            m[p] = m[n0 - len(sp) + p] = (mx, my)
+        out.append(m.reshape(H, W, 2))
+    return np.stack(out)
+
+
+def cap_operands(policy: str, W: int, H: int) -> tuple:
+    """(names, operands (CAP_B, ...), flags) of the one call per instance at CAP_FRAME.  The matrix policies run at flags 0 (the kernel
+    inverts): the rotation turns most of the last row out of sight, its neighbour in the batch keeps it in."""
+    if policy in ("map", "planes", "flow"):
+        m = cap_maps(W, H)
+        if policy == "flow":
+            y, x = np.mgrid[0:H, 0:W].astype(np.float32)
+            with np.errstate(all="ignore"):
+                m = (np.stack([x, y], axis=-1)[None] - m).astype(np.float32)
+        return ("special first and last", "special first and last, reversed"), m, 0
+    names = ("rotation with scale", "half pixel") if policy == "affine" else ("mild tilt", "tilt, W crosses zero")
+    by = {m.name: m for m in matrices(policy, W, H)}
+    return names, np.stack([np.array(by[n].M, np.float64) for n in names]), 0
+
+
+_cap_refs = {}
+
+
+def cap_reference(policy: str, fmt: str) -> tuple:
+    """(names, src (CAP_B, ...), operands, flags, want (CAP_B, ...), traces): the call of one instance at CAP_FRAME and the
+    restatement's bytes, computed once and shared, read-only"""
+    if (policy, fmt) not in _cap_refs:
+        W, H = CAP_FRAME
+        names, ops, fl = cap_operands(policy, W, H)
+        src = images(FORMATS[fmt], W, H)[:CAP_B]
+        traces = [[] for _ in range(CAP_B)]
+        want = np.stack([reference(policy, src[b], ops[b], fl, traces[b]) for b in range(CAP_B)])
+        for a in (src, ops, want):
+            a.setflags(write=False)
+        _cap_refs[(policy, fmt)] = (names, src, ops, fl, want, [t[-1] for t in traces])
+    return _cap_refs[(policy, fmt)]
+
+
+PLANT = (3.0, 4.0)
+
+
+def method_cap_plants(W: int, H: int, threshold: int) -> tuple:
+    """Two source pixels, off the rim, whose destinations under "shift (-2, 1)" (x - 2, y + 1) are the pixel 22 before `threshold` and
+    the pixel 138 at or past it -- on different trips of k_warp_method's loop and in different workgroups.  -> ((y, x), (y, x))"""
+    out = []
+    for p in (threshold - 22, threshold + 138):
+        y, x = divmod(p, W)
+        out.append((y - 1, x + 2))
+    return tuple(out)
+
+
+def method_cap_fields(W: int, H: int, threshold: int) -> tuple:
+    """(names, flow (B, H, W, 2), M (B, 3, 3) or its first two rows): zeros with the same vector at both plants (equal magnitudes, the
+    first pixel wins); the later one twice as long (it wins); the earlier one twice as long"""
+    (y0, x0), (y1, x1) = method_cap_plants(W, H, threshold)
+    f = np.zeros((B, H, W, 2), np.float32)
+    v = np.array(PLANT, np.float32)
+    f[0, y0, x0], f[0, y1, x1] = v, v
+    f[1, y0, x0], f[1, y1, x1] = v, 2 * v
+    f[2, y0, x0], f[2, y1, x1] = 2 * v, v
+    shift = [m for m in perspective_matrices(W, H) if m.name == "shift (-2, 1)"][0]
+    return ("tie", "the later is larger", "the earlier is larger"), f, np.stack([np.array(shift.M, np.float64)] * B)
+
+
+_method_refs = {}
+
+
+def method_cap_reference(kind: int) -> list:
+    """[(names, flow (B, ...), M (B, ...), diff, mag, records)] per call of batch B at METHOD_CAP_FRAME: method_matrices over method_flow in
+    groups, then the constructed fields; computed once and shared, read-only"""
+    if kind not in _method_refs:
+        W, H = METHOD_CAP_FRAME
+        c = source_caps()
+        calls = [(tuple(m.name for m in g), method_flow(W, H), np.stack([np.array(m.M, np.float64) for m in g])) for g in groups(method_matrices(kind, W, H))]
+        names, f, M = method_cap_fields(W, H, c["WARP_METHOD_CAP"] * c["WARP_WG"])
+        calls.append((names, f, M if kind == R.PERSPECTIVE else np.ascontiguousarray(M[:, :2, :])))
+        out = []
+        for names, f, M in calls:
+            ref = [R.warp_method(f[b], M[b], kind) for b in range(B)]
+            item = (names, f, M) + tuple(np.stack([r[i] for r in ref]) for i in range(3))
+            for a in item[1:]:
+                a.setflags(write=False)
+            out.append(item)
+        _method_refs[kind] = out
+    return _method_refs[kind]
